@@ -2,8 +2,16 @@
 """bench.py — BASELINE.json metric on MI355X: Gibbs-steps/sec of the CD-k loop,
 784x1024 Bernoulli RBM, batch 512 per GPU, fp32 MFMA — plus the other BASELINE configurations.
 
-    python bench.py --gpus N --steps K --warmup W [--config rbm|gibbs|grbm|dbm|ais] [--k 1] [--no-cpu]
+    python bench.py --gpus N --steps K --warmup W [--config rbm|gibbs|grbm|dbm|ais] [--k 1] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-others]]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run measures the headline only: set-up, the untimed precondition and warm-up steps, EXACTLY K timed steps, the
+JSON line.  --full adds what takes runs of its own: the instrumented per-kernel pass (`roofline.kernels`, rbm), the short
+passes of the other configurations (`other_configs`, rbm) and the CPU baselines (`cpu_baseline`, rbm at N = 1).
+--dump-outputs DIR writes what the timed path computed, as it stands after the last timed step (the parameters, the
+persistent chains or samples, the AIS log-weights), to DIR/<name>.npy; the inputs are seeded, so two builds run with the
+same arguments can be compared array by array.
 
 --config rbm (default) is BASELINE.json's metric on configs[1]: one "step" = one CD-k update
 (base_rbm.py:566 `session.run(train_op)`) of one 512-row minibatch per GPU, already resident in HBM
@@ -24,9 +32,9 @@ numbers DESIGN.md quotes for BASELINE configs[2..4] and of SURVEY §8d(ii)):
 
 The JSON line carries
   roofline     : fp32-MFMA roofline.  achieved = algorithmic GEMM flops per step (SURVEY §8d formulas) /
-                 HIP-event time of the step's kernels on the engine stream; `kernels` holds the
+                 HIP-event time of the step's kernels on the engine stream; with --full, `kernels` holds the
                  per-kernel-class durations from a second, event-instrumented pass (rbm only).
-  cpu_baseline : CPU restatements of the reference maths (NOT TF1 itself, which cannot run here) timed on
+  cpu_baseline : (--full) CPU restatements of the reference maths (NOT TF1 itself, which cannot run here) timed on
                  this box's host cores on a bounded sample: the canonical-order OpenMP C oracle and a
                  NumPy + BLAS (sgemm) restatement; CPU model, core count and threads are stated.
 """
@@ -215,6 +223,10 @@ class Workload(object):
         for i in range(i0, i0 + n):
             self.step(i)
 
+    def outputs(self):
+        """{name: array}: what a caller of the timed path holds after the last step (--dump-outputs)"""
+        return {}
+
 
 class RbmCD(Workload):
     name = 'rbm'
@@ -291,6 +303,9 @@ class RbmCD(Workload):
             self.eng.set_from_device(name, d)
         self.eng.seed(1337)
 
+    def outputs(self):
+        return {n: self.eng.get(n) for n in ('W', 'vb', 'hb', 'dW', 'dvb', 'dhb')}
+
     def kernel_pass(self, steps, ev_ms):
         """second, instrumented pass: per-kernel-class durations (HIP events on the engine stream)"""
         eng, k = self.eng, self.k
@@ -323,8 +338,8 @@ class RbmCD(Workload):
         k = self.k
         F = 2.0 * B * V * H
         flops = (2 * k + 3) * F
-        kern = self.kernel_pass(args.steps, ev_ms)
-        up_us = kern.get('act_up', {}).get('avg_us')
+        kern = self.kernel_pass(args.steps, ev_ms) if getattr(args, 'full', False) else None
+        up_us = kern.get('act_up', {}).get('avg_us') if kern else None
         return {
             'metric': 'Gibbs-steps/sec (CD-k, 784x1024 RBM, batch 512)',
             'value': round(world * k * args.steps / dt, 2),
@@ -343,7 +358,7 @@ class RbmCD(Workload):
                          'HIP events on the engine stream over the timed region' % (k, flops / 1e9),
                 'dominant_kernel': 'act_kernel (propagation GEMM + sigmoid + Philox Bernoulli, 3 of the 4 launches)',
                 'dominant_kernel_tflops': round(F / (up_us * 1e-6) / 1e12, 3) if up_us else None,
-                'kernels': kern},
+                'kernels': kern if kern is not None else 'per-kernel pass: --full'},
         }
 
 
@@ -369,6 +384,10 @@ class RbmGibbs(Workload):
 
     def step(self, i):
         self.eng.gibbs(self.Hd, self.Vd, B, self.k)
+
+    def outputs(self):
+        self.eng.sync()
+        return {'v_samples': self.Vd.numpy().reshape(B, V), 'h_samples': self.Hd.numpy().reshape(B, H)}
 
     def precondition_steps(self, seconds):
         return int(seconds * 30000 / self.k)
@@ -412,6 +431,14 @@ class RbmGibbs(Workload):
 
 
 class _DbmBase(Workload):
+    def outputs(self):
+        L = len(self.eng.n_hiddens)
+        names = ['W', 'vb', 'hb', 'v', 'h'] + ['%s_%d' % (n, i) for i in range(1, L) for n in ('W', 'hb', 'h')]
+        out = {n: self.eng.get(n) for n in names}
+        if getattr(self, 'nmf', None):
+            out['n_mf_updates'] = np.array([self.nmf[-1]], dtype=np.float64)
+        return out
+
     def _dp_setup(self, args, rank, world, dist):
         self.comm, self.collective, self.collective_note = None, None, None
         if world > 1 or args.force_dp:
@@ -614,6 +641,9 @@ class Ais(_DbmBase):
                                              self.R, self.rank, self.world, allgather)
         else:
             self.last = self.eng.ais(self.nb, self.R, self.k, 2222)
+
+    def outputs(self):
+        return {'log_weights': np.asarray(self.last)} if self.last is not None else {}
 
     def report(self, args, world, dt, ev_ms):
         from boltzmann_machines_amd.utils import log_mean_exp
@@ -955,6 +985,32 @@ def make_record(wl, rep, world, steps, warmup, precondition_s, dt, ev_ms):
             'data': 'synthetic', 'config': rep['config'], 'roofline': roof}
 
 
+DUMP_LIMIT = 64 << 20          # bytes, all files together
+DUMP_SAMPLE = 1 << 20          # elements kept of an array above DUMP_LIMIT / 8
+
+
+def dump_outputs(wl, path):
+    """--dump-outputs: every array of wl.outputs() as <path>/<name>.npy (float32, or float64 where the array is).  An array
+    of more than DUMP_LIMIT / 8 bytes is written as <name>_sample.npy: DUMP_SAMPLE elements at fixed, seeded positions of
+    its flattened form (<name>_sample_index.npy holds them).  Returns the list of file names."""
+    os.makedirs(path, exist_ok=True)
+    written = []
+    for name, a in sorted(wl.outputs().items()):
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > DUMP_LIMIT // 8:
+            idx = np.sort(np.random.RandomState(20261016).choice(a.size, DUMP_SAMPLE, replace=False)).astype(np.int64)
+            np.save(os.path.join(path, name + '_sample_index.npy'), idx)
+            written.append(name + '_sample_index.npy')
+            a, name = a.reshape(-1)[idx], name + '_sample'
+        np.save(os.path.join(path, name + '.npy'), a)
+        written.append(name + '.npy')
+    total = sum(os.path.getsize(os.path.join(path, f)) for f in written)
+    if total > DUMP_LIMIT:
+        raise SystemExit('bench.py: --dump-outputs wrote %d bytes, above the %d-byte limit' % (total, DUMP_LIMIT))
+    return written
+
+
 def with_summary(out):
     """the line with a compact `summary` of EVERY configuration right behind metric / value / unit - {config: [ms_per_step,
     roofline.frac (HIP events), roofline.frac_wall]} - so that a reader who keeps only the head or the tail of the line (the
@@ -988,12 +1044,17 @@ def main():
     ap.add_argument('--dbm-mf-tol', type=float, default=1e-7,
                     help='dbm: mean-field tolerance (BASELINE configs[3]: 1e-7 = the loop runs to its 50-sweep cap; a looser one '
                          'measures the update with the SHORT loop of a trained model - a developer setting, named in config.workload)')
-    ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: the per-kernel pass (rbm), the short passes of the other '
+                         'configurations (rbm, unless --no-others) and the CPU baselines (rbm at N = 1, unless --no-cpu)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed (as of its last step) to DIR/<name>.npy')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: without the CPU baselines')
     ap.add_argument('--fast-binary', action='store_true',
                     help='gibbs / ais / grbm / dbm: the opt-in exact-product bf16 x 3 mode (bm_*_set_fast_binary); a NON-default, '
                          'tolerance-parity mode, reported separately from the f32 figures')
     ap.add_argument('--no-others', action='store_true',
-                    help='rbm: do not add the short passes of the other BASELINE configurations (`other_configs`)')
+                    help='rbm --full: do not add the short passes of the other BASELINE configurations (`other_configs`)')
     ap.add_argument('--others-budget-s', type=float, default=150.0,
                     help='wall-clock budget of the `other_configs` passes; a pass still running when it expires is '
                          'abandoned (the headline line is printed with what finished)')
@@ -1025,6 +1086,8 @@ def main():
         args.steps = DEFAULTS[args.config][0]
     if args.warmup is None:
         args.warmup = DEFAULTS[args.config][1]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)                # does not return
@@ -1074,6 +1137,8 @@ def main():
     trace('workload ready (collective: %s)' % (getattr(wl, 'collective', None),))
     dt, ev_ms = measure(wl, args.steps, args.warmup, args.precondition_s, barrier, dist)
     dp_check = check_data_parallel_run(wl, args, rank, world, dist)      # (after the clock stopped)
+    if rank == 0 and args.dump_outputs:       # before anything else runs on the model (the --full per-kernel pass does)
+        dump_outputs(wl, args.dump_outputs)
     rep = wl.report(args, world, dt, ev_ms) if rank == 0 else None
     barrier()
     out = make_record(wl, rep, world, args.steps, args.warmup, args.precondition_s, dt, ev_ms) if rank == 0 else None
@@ -1110,7 +1175,7 @@ def main():
     # ---- the other BASELINE configurations, short passes, embedded in the same line (rbm default run only).
     # Every rank runs the same sequence.  A watchdog bounds the whole block: if a pass hangs (a collective that
     # never completes on some rank), rank 0 prints the headline line with what finished and all ranks leave.
-    if args.config == 'rbm' and not args.no_others and not args.delayed_grads:
+    if args.full and args.config == 'rbm' and not args.no_others and not args.delayed_grads:
         import threading
         others = {}
         if rank == 0:
@@ -1163,7 +1228,7 @@ def main():
                     others[name] = {'error': '%s: %s' % (type(e).__name__, str(e)[:300])}
         done.set()
 
-    if rank == 0 and not args.no_cpu and world == 1 and args.config == 'rbm':
+    if rank == 0 and args.full and not args.no_cpu and world == 1 and args.config == 'rbm':
         out['cpu_baseline'] = cpu_baseline(args.k)
     emit()
     if dist is not None:

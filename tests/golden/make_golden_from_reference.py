@@ -118,10 +118,47 @@ class ReferencePackage(object):
         self.n_draw_ops += 1
 
 
+def ais_literal_20_12_16(pkg, d):
+    """The reference's AIS graph (dbm.py:696-736, float32 `log_Z +=` / `-=` by construction) on a 20-12-16 DBM: the
+    parameters it ran on, the seed of its chains and the per-run values it returned (tests/test_reference_shim.py
+    replays them on the oracle)"""
+    from tests.golden import scenarios
+    V = 20
+    X = (pkg.RNG(seed=5).rand(40, V) < 0.3).astype(np.float32)
+    rbms, _ = scenarios._pretrain(pkg, d, X, (V, 12, 16))
+    dbm = pkg.DBM(rbms=rbms, n_particles=10, batch_size=10, max_epoch=1, random_seed=13, verbose=False,
+                  model_path=os.path.join(d, 'dbm') + '/')
+    dbm.init()
+    seeds = []
+    orig = pkg.tf.set_random_seed
+    pkg.tf.set_random_seed = lambda s: (seeds.append(s), orig(s))[1]
+    try:
+        _, _, values = dbm.log_Z(n_betas=600, n_runs=12, n_gibbs_steps=1)
+    finally:
+        pkg.tf.set_random_seed = orig
+    out = {k: np.asarray(v) for k, v in dbm.get_tf_params(scope='weights').items()}
+    out['seed'] = np.array([seeds[-1]], dtype=np.int64)
+    out['values'] = np.asarray(values)
+    return out
+
+
+# fixtures of the reference's internals rather than of a scenario of its public API (no near-tie bookkeeping)
+EXTRA = {'ais_literal_20_12_16': ais_literal_20_12_16}
+
+
 def generate(name, pkg=None):
     from tests.golden import scenarios
     pkg = pkg or ReferencePackage()
     pkg.reset()
+    if name in EXTRA:
+        d = tempfile.mkdtemp(prefix='bm_ref_%s_' % name)
+        cwd = os.getcwd()
+        try:
+            os.chdir(d)
+            return EXTRA[name](pkg, d)
+        finally:
+            os.chdir(cwd)
+            shutil.rmtree(d, ignore_errors=True)
     d = tempfile.mkdtemp(prefix='bm_ref_%s_' % name)
     cwd = os.getcwd()
     try:
@@ -148,6 +185,9 @@ def main(argv):
         out = generate(name, pkg)
         path = os.path.join(HERE, 'ref_%s.npz' % name)
         np.savez_compressed(path, **out)
+        if name in EXTRA:
+            print('%-40s %3d arrays  %7.1f KiB' % (name, len(out), os.path.getsize(path) / 1024.0))
+            continue
         print('%-40s %3d arrays  %7.1f KiB  %.3g Bernoulli draws, %d within %.0e of a tie, min |u - p| = %.2e'
               % (name, len(out), os.path.getsize(path) / 1024.0, float(out['n_bernoulli_draws'][0]),
                  len(out['near_ties']), TIE_EPS, float(out['min_bernoulli_margin'][0])))

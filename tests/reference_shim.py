@@ -36,6 +36,16 @@ class _LayersAlias(object):
         return None
 
 
+def stand_in():
+    """the tensorflow stand-in module alone (no reference checkout needed)"""
+    if SHIM in sys.path:
+        sys.path.remove(SHIM)
+    sys.path.insert(0, SHIM)
+    import tensorflow as tf
+    assert 'numpy-shim' in tf.__version__, 'a real TensorFlow shadows the shim'
+    return tf
+
+
 def activate():
     """returns (tensorflow shim module, reference `boltzmann_machines` package)"""
     if not available():

@@ -115,7 +115,7 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.bm_version().startswith(b'bm355')
 
 
-def test_no_cpu_fallback_without_gpu():
+def test_no_cpu_fallback_without_gpu(tmp_path):
     """Without a visible GPU the product path must fail loudly, not compute on the CPU."""
     from boltzmann_machines_amd import _ffi
     lib = _ffi.load()
@@ -126,7 +126,7 @@ def test_no_cpu_fallback_without_gpu():
         RbmEngine(8, 4, max_batch=2)
     from boltzmann_machines_amd import BernoulliRBM
     with pytest.raises(_ffi.Bm355Error):
-        BernoulliRBM(n_visible=8, n_hidden=4, verbose=False, model_path='/tmp/bm355_nogpu/').fit(np.zeros((4, 8)))
+        BernoulliRBM(n_visible=8, n_hidden=4, verbose=False, model_path=str(tmp_path / 'nogpu') + '/').fit(np.zeros((4, 8)))
 
 
 def test_dataset_readers(tmp_path):
@@ -198,7 +198,7 @@ class _StubModel(object):
         return Stub(model_path=str(tmp_path / 'm') + '/', random_seed=5)
 
 
-def test_checkpoint_write_is_atomic_and_errors_reach_the_caller(tmp_path):
+def test_checkpoint_write_atomically_and_errors_reach_the_caller(tmp_path):
     """round-2 advisor: the background checkpoint writer must not lose its exception (the reference's synchronous
     save raises), and a failed write must not leave a half-written file behind."""
     m = _StubModel.make(tmp_path)
@@ -271,7 +271,7 @@ def test_checkpoint_writer_never_blocks_the_training_loop(tmp_path, monkeypatch)
     assert n['written'] == [1, 4, 5, 6]
 
 
-def test_data_parallel_is_opt_in(monkeypatch):
+def test_data_parallel_is_opt_in(monkeypatch, tmp_path):
     """round-2 advisor: RANK / WORLD_SIZE set by a launcher must not switch a model into data-parallel mode
     (collectives, rank-0-only checkpoints) unless BM355_DATA_PARALLEL=1 asks for it."""
     src = open(os.path.join(ROOT, 'boltzmann_machines_amd', 'base.py')).read()
@@ -281,7 +281,7 @@ def test_data_parallel_is_opt_in(monkeypatch):
     assert parallel.dist_env() == (1, 1, 4)
     from boltzmann_machines_amd import BernoulliRBM
     from boltzmann_machines_amd import _ffi
-    rbm = BernoulliRBM(n_visible=4, n_hidden=3, model_path='/tmp/bm355_optin/')
+    rbm = BernoulliRBM(n_visible=4, n_hidden=3, model_path=str(tmp_path / 'optin') + '/')
     monkeypatch.delenv('BM355_DATA_PARALLEL', raising=False)
     if _ffi.load().bm_device_count() == 0:
         with pytest.raises(_ffi.Bm355Error):         # reaches engine creation (no GPU here) ...
@@ -429,3 +429,30 @@ def test_pipelined_fit_flushes_the_owed_report_when_the_next_epoch_aborts(monkey
     lines, scal, _, err = _fit_lines(monkeypatch, tmp_path, 'boom', every, boom_at=boom_at)
     assert err == 'boom'
     assert lines == lines_ok[:1], (lines, lines_ok)
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path):
+    """bench.py --dump-outputs: one <name>.npy per output in float32 / float64; an array above 8 MiB becomes a fixed,
+    seeded sample (the same positions every run) with its index; all files together stay within 64 MiB."""
+    import bench
+
+    class Wl(object):
+        def __init__(self, seed):
+            rs = np.random.RandomState(seed)
+            self.big = rs.rand(3072, 5000).astype(np.float32)
+            self.small = rs.rand(7).astype(np.float64)
+
+        def outputs(self):
+            return {'big': self.big, 'small': self.small, 'ints': np.arange(4, dtype=np.int32)}
+
+    w = Wl(1)
+    names = bench.dump_outputs(w, str(tmp_path / 'a'))
+    assert sorted(names) == ['big_sample.npy', 'big_sample_index.npy', 'ints.npy', 'small.npy']
+    idx = np.load(str(tmp_path / 'a' / 'big_sample_index.npy'))
+    big = np.load(str(tmp_path / 'a' / 'big_sample.npy'))
+    assert big.dtype == np.float32 and big.shape == (bench.DUMP_SAMPLE,) and np.array_equal(big, w.big.reshape(-1)[idx])
+    assert np.load(str(tmp_path / 'a' / 'small.npy')).dtype == np.float64
+    assert np.load(str(tmp_path / 'a' / 'ints.npy')).dtype == np.float32
+    assert sum(os.path.getsize(str(tmp_path / 'a' / n)) for n in names) <= bench.DUMP_LIMIT
+    bench.dump_outputs(Wl(2), str(tmp_path / 'b'))
+    assert np.array_equal(np.load(str(tmp_path / 'b' / 'big_sample_index.npy')), idx)

@@ -1,7 +1,8 @@
 """The reference's OWN tests, run against the unmodified reference package on the NumPy TF-1 stand-in
 (tests/tf1_shim): if these pass, the stand-in carries the reference's graph builders, session / Saver round trips,
 `load_model` and resume correctly - which is what entitles the fixtures it generates (tests/golden/ref_*.npz) to be
-called reference output.  Runs where /root/reference exists (the build container); skipped on the GPU box."""
+called reference output.  The tests that import the reference run where its checkout exists (BM_REFERENCE_ROOT) and are
+skipped elsewhere; the last two need only the stand-in and the committed fixtures and run everywhere."""
 import os
 import sys
 
@@ -9,7 +10,7 @@ import pytest
 
 from tests import reference_shim
 
-pytestmark = pytest.mark.skipif(not reference_shim.available(), reason='the reference checkout is not on this box')
+needs_reference = pytest.mark.skipif(not reference_shim.available(), reason='the reference checkout is not on this box')
 
 
 @pytest.fixture()
@@ -29,6 +30,7 @@ def reference_tests(tmp_path, monkeypatch):
     return test_rbm.TestRBM()
 
 
+@needs_reference
 @pytest.mark.parametrize('case', ['test_W_init', 'test_initialization', 'test_consistency', 'test_consistency_val'])
 def test_reference_test_rbm(reference_tests, case):
     """rbm/tests/test_rbm.py:29-131: constructor errors, the W-init known answers through the reference's `init()`
@@ -40,6 +42,7 @@ def test_reference_test_rbm(reference_tests, case):
         reference_tests.cleanup()
 
 
+@needs_reference
 def test_reference_path_table(monkeypatch):
     """base/tests/test_tf_model.py: the working-path table of TensorFlowModel.compute_working_paths"""
     reference_shim.activate()
@@ -54,33 +57,26 @@ def test_reference_path_table(monkeypatch):
     assert ran >= 3
 
 
-def test_reference_ais_is_the_literal_float32_accumulation(tmp_path, monkeypatch):
+def test_reference_ais_is_the_literal_float32_accumulation():
     """The reference's AIS graph (dbm.py:696-736) run on the stand-in - float32 `log_Z +=` / `-=` by construction -
     against the oracle on the same parameters and chains: the oracle's LITERAL mode follows it to float32 round-off;
-    the default double accumulation stays within the 1e-5 parity bar at this length."""
+    the default double accumulation stays within the 1e-5 parity bar at this length.  The reference's parameters, seed
+    and values are the committed fixture tests/golden/ref_ais_literal_20_12_16.npz (generator:
+    tests/golden/make_golden_from_reference.py `ais_literal_20_12_16`; re-checked against the reference by
+    tests/test_reference_fixtures.py where its checkout exists)."""
     import numpy as np
-    from tests.golden import make_golden_from_reference as gen, scenarios
     from oracle import oracle as orc
-    monkeypatch.chdir(tmp_path)
-    pkg = gen.ReferencePackage()
+    from tests import reference_fixtures as rf
+    ref = rf.load('ais_literal_20_12_16')
     V = 20
-    X = (pkg.RNG(seed=5).rand(40, V) < 0.3).astype(np.float32)
-    rbms, _ = scenarios._pretrain(pkg, str(tmp_path), X, (V, 12, 16))
-    dbm = pkg.DBM(rbms=rbms, n_particles=10, batch_size=10, max_epoch=1, random_seed=13, verbose=False,
-                  model_path=str(tmp_path / 'dbm') + '/')
-    dbm.init()
-    seeds = []
-    orig = pkg.tf.set_random_seed
-    monkeypatch.setattr(pkg.tf, 'set_random_seed', lambda s: (seeds.append(s), orig(s))[1])
-    _, _, values = dbm.log_Z(n_betas=600, n_runs=12, n_gibbs_steps=1)
-    p = dbm.get_tf_params(scope='weights')
     twin = orc.OracleDBM(V, [12, 16], n_particles=10, batch_size=10)
     for k in ('W', 'W_1', 'vb', 'hb', 'hb_1'):
-        twin.p[k][...] = p[k]
-    lit = twin.ais(600, 12, 1, seeds[-1], literal=True)
-    dbl = twin.ais(600, 12, 1, seeds[-1])
-    np.testing.assert_allclose(lit, values, rtol=2e-6)
-    np.testing.assert_allclose(dbl, values, rtol=1e-5)
+        twin.p[k][...] = ref[k]
+    seed = int(ref['seed'][0])
+    lit = twin.ais(600, 12, 1, seed, literal=True)
+    dbl = twin.ais(600, 12, 1, seed)
+    np.testing.assert_allclose(lit, ref['values'], rtol=2e-6)
+    np.testing.assert_allclose(dbl, ref['values'], rtol=1e-5)
 
 
 def test_literal_sigmoid_is_the_stand_ins_tf_sigmoid_bit_for_bit():
@@ -96,7 +92,7 @@ def test_literal_sigmoid_is_the_stand_ins_tf_sigmoid_bit_for_bit():
     reference's behaviour.  With Eigen's exp restated no step exceeds 5.96e-8 and the stand-in runs 5 - 6 sweeps at
     784-512-1024: the 50 was NumPy's, not the reference's.  Asserted below so the finding stays checked.)"""
     import numpy as np
-    tf, _ = reference_shim.activate()
+    tf = reference_shim.stand_in()
     from oracle import oracle as orc
     step = dict(lit=0.0, ours=0.0, npexp=0.0)
     err = dict(lit=0.0, ours=0.0)

@@ -8,8 +8,8 @@ for rep in 1 2; do
   for v in old new; do
     if [ $v = old ]; then cp tools/_old_libbm355.so $L; else cp /tmp/new.so $L; fi
     touch $L
-    timeout 200 python bench.py --no-others --no-cpu 2>/dev/null | line "$v 2000"
-    timeout 200 python bench.py --no-others --no-cpu --steps 20 --warmup 5 2>/dev/null | line "$v 20"
+    timeout 200 python bench.py --full --no-others --no-cpu 2>/dev/null | line "$v 2000"
+    timeout 200 python bench.py --full --no-others --no-cpu --steps 20 --warmup 5 2>/dev/null | line "$v 20"
   done
 done
 cp /tmp/new.so $L

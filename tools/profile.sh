@@ -22,14 +22,14 @@ for c in $CONFIGS; do
     grbmfast) cc=grbm; X="--fast-binary"; A="--steps 10 --warmup 3"; P="--steps 4 --warmup 2";;
     aisfast) cc=ais; X="--fast-binary"; A="--steps 1 --warmup 1 --ais-betas 60"; P="--steps 1 --warmup 0 --ais-betas 20";;
   esac
-  B="python $R/bench.py --config $cc $X --no-cpu --no-others --precondition-s 0.1"
+  B="python $R/bench.py --config $cc $X --full --no-cpu --no-others --precondition-s 0.1"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$c/stats -o s -- $B $A > $OUT/$c.stats.log 2>&1
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/$c/fetch -o f -- $B $P > $OUT/$c.fetch.log 2>&1
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/$c/write -o w -- $B $P > $OUT/$c.write.log 2>&1
   rocprofv3 --pmc $SQ --output-format csv -d $OUT/$c/sq -o q -- $B $P > $OUT/$c.sq.log 2>&1
   # keep only what the summary needs (the merged-back directory is capped at 64 MiB)
   find $OUT/$c -name '*_kernel_trace.csv' -delete; find $OUT/$c -name '*.db' -delete
-  (cd $R && python bench.py --config $cc $X --no-cpu --no-others > $OUT/$c.bench.json 2> $OUT/$c.bench.err)
+  (cd $R && python bench.py --config $cc $X --full --no-cpu --no-others > $OUT/$c.bench.json 2> $OUT/$c.bench.err)
   tail -c 300 $OUT/$c.bench.json; echo
   ls -la $OUT/$c/sq/* 2>/dev/null | head -3
 done
