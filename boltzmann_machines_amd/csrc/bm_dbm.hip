@@ -89,10 +89,15 @@ struct bm_dbm {
                                                    // sweeps, double-buffered by sweep parity (ActArgs::chk_ctl)
     Mat xw0;                                       // [N][n1] hoisted X.W0 of the current minibatch
     double *scal = nullptr;
-    // AIS / ELBO workspaces (allocated on demand)
+    // AIS / ELBO workspaces (allocated on demand).  AIS state by depth (depth 0 = v, depth i + 1 = hidden layer i): the
+    // odd-depth layers {h1, h3} are the chain x, the even-depth layers {v, h2, h4} are summed out analytically
     int ais_rows = 0;
-    Mat ax, ax2, av, ah2;
-    DevBuf apart_v, apart_h, apart_x[2], rowtmp;   // per-16-column slot partial sums (ActArgs::rowacc / rowdot_out)
+    Mat ae[3];                                     // even-depth states (v, h2, h4)
+    Mat ao[2][2];                                  // odd-depth states (h1, h3), ping-pong pairs
+    DevBuf apart_e[3];                             // per-16-column slot partial sums (ActArgs::rowacc): softplus terms of the
+                                                   // even-depth layers (AIS) / the layers' sum((mu_{l-1} W_l) * mu_l) (ELBO)
+    DevBuf apart_o[2][2];                          // x.hb of the odd-depth layers, current / next (ActArgs::rowdot_out)
+    DevBuf rowtmp;
     double *alogw = nullptr;                       // [ais_rows] log-weights, accumulated in double in a fixed order
     DevBuf ais_send, ais_recv;                     // bm_dbm_ais_sharded: this rank's values / the all-gathered values
     // fast-binary mode (bm_bf3.h, bm_dbm_set_fast_binary): bf16 planes of W_l (x = below unit, k = above unit) and of
@@ -127,10 +132,10 @@ static PhiloxKey dkey(const bm_dbm *h, uint32_t site, int t, uint64_t seed, uint
 
 // the bf16 shadow of a state matrix of the running fast-binary sweep (null: none)
 static const Mat16 *fast_shadow(bm_dbm *h, const float *p, bool **ok = nullptr) {
-    if (p == h->ax.p) return &h->ax16;
-    if (p == h->ax2.p) return &h->ax2_16;
-    if (p == h->av.p) return &h->av16;
-    if (p == h->ah2.p) return &h->ah2_16;
+    if (p == h->ao[0][0].p) return &h->ax16;
+    if (p == h->ao[0][1].p) return &h->ax2_16;
+    if (p == h->ae[0].p) return &h->av16;
+    if (p == h->ae[1].p) return &h->ah2_16;
     for (int b = 0; b < 2; ++b) {
         if (p && p == h->pv_key[b]) { if (ok) *ok = &h->pv_ok[b]; return &h->pv16[b]; }
         for (int i = 0; i < h->L; ++i) if (p && p == h->pH_key[i][b]) { if (ok) *ok = &h->pH_ok[i][b]; return &h->pH16[i][b]; }
@@ -740,6 +745,37 @@ static void reconstruct_from_mu(bm_dbm *h, float *R, int ldr) {
                  dkey(h, 0, 0, h->seed, h->call), 0);
 }
 
+// AIS at any depth (dbm.py:650-736 for L = 2, extended): the odd-depth layers are the chain x, the even-depth layers are
+// conditionally independent given x and summed out analytically.  `ev`: layer_update index of the even-depth layers in
+// ascending depth (-1 = v, then hidden 1, 3); `od`: hidden index of the odd-depth layers (0, 2)
+struct AisLayers { int ne, no; int ev[3]; int od[2]; };
+static AisLayers ais_layers(const bm_dbm *h) {
+    AisLayers s;
+    s.ne = 0; s.no = 0;
+    s.ev[s.ne++] = -1;
+    for (int i = 0; i < h->L; ++i) {                 // hidden layer i has depth i + 1
+        if (i & 1) s.ev[s.ne++] = i;
+        else s.od[s.no++] = i;
+    }
+    return s;
+}
+
+// log Z_0 = (V + sum_i n_i) log 2 (dbm.py:731-734); `literal`: the reference's float32 node
+static double ais_log_Z0(const bm_dbm *h, bool literal) {
+    int units = h->V;
+    for (int i = 1; i <= h->L; ++i) units += h->n[i];
+    return literal ? (double)((float)units * logf(2.0f)) : (double)units * (double)logf(2.0f);
+}
+
+static void release_ais(bm_dbm *h) {
+    for (int e = 0; e < 3; ++e) { h->ae[e].release(); h->apart_e[e].release(); }
+    for (int o = 0; o < 2; ++o) for (int b = 0; b < 2; ++b) { h->ao[o][b].release(); h->apart_o[o][b].release(); }
+    h->rowtmp.release();
+    if (h->alogw) { (void)hipFree(h->alogw); h->alogw = nullptr; }
+    h->ax16.release(); h->ax2_16.release(); h->av16.release(); h->ah2_16.release();     // (re)allocated by the fast path
+    h->ais_rows = 0;
+}
+
 extern "C" {
 
 int bm_dbm_create(const bm_dbm_config *cfg, bm_dbm **out) {
@@ -830,12 +866,11 @@ int bm_dbm_destroy(bm_dbm *h) {
     }
     h->ax16.release(); h->ax2_16.release(); h->av16.release(); h->ah2_16.release();
     for (int b = 0; b < 2; ++b) { h->pv16[b].release(); for (int i = 0; i < MAXL; ++i) h->pH16[i][b].release(); }
-    Mat *ms[] = {&h->v, &h->v_new, &h->recon, &h->ax, &h->ax2, &h->av, &h->ah2};
+    Mat *ms[] = {&h->v, &h->v_new, &h->recon};
     for (Mat *m : ms) m->release();
-    DevBuf *bs[] = {&h->vb, &h->dvb, &h->sigma, &h->grad, &h->apart_v, &h->apart_h, &h->apart_x[0], &h->apart_x[1], &h->rowtmp,
-                     &h->ais_send, &h->ais_recv};
+    DevBuf *bs[] = {&h->vb, &h->dvb, &h->sigma, &h->grad, &h->ais_send, &h->ais_recv};
     for (DevBuf *b : bs) b->release();
-    if (h->alogw) (void)hipFree(h->alogw);
+    release_ais(h);
     if (h->ctl) (void)hipFree(h->ctl);
     if (h->ctl_host) (void)hipHostFree(h->ctl_host);
     for (int i = 0; i < bm_dbm::MF_RING; ++i) if (h->ctl_ev[i]) (void)hipEventDestroy(h->ctl_ev[i]);
@@ -1142,20 +1177,23 @@ static inline int nslots(int n) { return (n + 15) / 16; }
 
 static int ensure_ais(bm_dbm *h, int rows) {
     if (rows <= h->ais_rows) return 0;
-    Mat *ms[] = {&h->ax, &h->ax2, &h->av, &h->ah2};
-    for (Mat *m : ms) m->release();
-    DevBuf *bs[] = {&h->apart_v, &h->apart_h, &h->apart_x[0], &h->apart_x[1], &h->rowtmp};
-    for (DevBuf *b : bs) b->release();
-    if (h->alogw) { (void)hipFree(h->alogw); h->alogw = nullptr; }
-    const int H2 = h->L >= 2 ? h->n[2] : 1;
-    BM_TRY(h->ax.alloc(rows, h->n[1])); BM_TRY(h->ax2.alloc(rows, h->n[1]));
-    BM_TRY(h->av.alloc(rows, h->V)); BM_TRY(h->ah2.alloc(rows, H2));
-    BM_TRY(h->apart_v.alloc((size_t)nslots(h->V > h->n[1] ? h->V : h->n[1]) * rows));   // AIS: V slots; ELBO: n1 slots
-    BM_TRY(h->apart_h.alloc((size_t)nslots(H2 > h->n[1] ? H2 : h->n[1]) * rows));
-    BM_TRY(h->apart_x[0].alloc((size_t)nslots(h->n[1]) * rows)); BM_TRY(h->apart_x[1].alloc((size_t)nslots(h->n[1]) * rows));
+    release_ais(h);
+    const AisLayers s = ais_layers(h);
+    int nmax = 1;
+    for (int l = 0; l <= h->L; ++l) nmax = h->n[l] > nmax ? h->n[l] : nmax;
+    // every partial buffer holds the slots of the widest layer: AIS and ELBO use them for different layers
+    const size_t part = (size_t)nslots(nmax) * rows;
+    for (int e = 0; e < s.ne; ++e) {
+        BM_TRY(h->ae[e].alloc(rows, s.ev[e] < 0 ? h->V : h->n[s.ev[e] + 1]));
+        BM_TRY(h->apart_e[e].alloc(part));
+    }
+    for (int o = 0; o < s.no; ++o)
+        for (int b = 0; b < 2; ++b) {
+            BM_TRY(h->ao[o][b].alloc(rows, h->n[s.od[o] + 1]));
+            BM_TRY(h->apart_o[o][b].alloc(part));
+        }
     BM_TRY(h->rowtmp.alloc(rows));
     BM_HIP(hipMalloc((void **)&h->alogw, (size_t)rows * sizeof(double)));
-    h->ax16.release(); h->ax2_16.release(); h->av16.release(); h->ah2_16.release();     // (re)allocated by the fast path
     h->ais_rows = rows;
     return 0;
 }
@@ -1180,23 +1218,31 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const float *X, int ld, int
     if (lane == 0) out[row] = s;
 }
 
-// One AIS score: logw[j] += sum_slots pv + sum_slots ph + (beta_b - beta_a) * sum_slots pd   (dbm.py:650-660)
+// the slot partials one AIS score reads: softplus terms of the even-depth layers, x.hb of the odd-depth layers
+struct AisScoreArgs {
+    const float *pe[3]; int ne_slots[3]; int ne;
+    const float *po[2]; int no_slots[2]; int no;
+};
+
+// One AIS score: logw[j] += sum_even sum_slots pe + (beta_b - beta_a) * sum_odd sum_slots po   (dbm.py:650-660)
 // from the slot partials act_kernel left (ActArgs::rowacc / rowdot_out), in double, in a FIXED order: 32 chains per
-// workgroup, 8 thread groups per chain; group t adds the slots q = t, t + 8, ... of each of the three partial arrays in
-// ascending order (consecutive threads read consecutive chains: full lines), the 8 group sums are added as a fixed
+// workgroup, 8 thread groups per chain; group t adds the slots q = t, t + 8, ... of each partial array, layers in
+// ascending depth (consecutive threads read consecutive chains: full lines), the 8 group sums are added as a fixed
 // tree.  (Round 2: one thread per chain walked all 113 slots, 79 workgroups for 20 000 chains: 37 us per beta, 4 % of
 // an AIS run.)  Deterministic; sums of <= 113 floats in double are exact to ~1e-16, far below the float the value
 // is finally rounded to.
-__global__ __launch_bounds__(256) void ais_score_kernel(double *logw, int J, int ld, const float *pv, int nv, const float *ph, int nh,
-                                                        const float *pd, int nd, float dbeta) {
+__global__ __launch_bounds__(256) void ais_score_kernel(double *logw, int J, int ld, AisScoreArgs p, float dbeta) {
     __shared__ double s_s[8][32], s_d[8][32];
     const int c = threadIdx.x & 31, t = threadIdx.x >> 5;
     const int j = blockIdx.x * 32 + c;
     double s = 0.0, d = 0.0;
     if (j < J) {
-        for (int q = t; q < nv; q += 8) s += (double)pv[(size_t)q * ld + j];
-        for (int q = t; q < nh; q += 8) s += (double)ph[(size_t)q * ld + j];
-        for (int q = t; q < nd; q += 8) d += (double)pd[(size_t)q * ld + j];
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+            if (e < p.ne) for (int q = t; q < p.ne_slots[e]; q += 8) s += (double)p.pe[e][(size_t)q * ld + j];
+#pragma unroll
+        for (int o = 0; o < 2; ++o)
+            if (o < p.no) for (int q = t; q < p.no_slots[o]; q += 8) d += (double)p.po[o][(size_t)q * ld + j];
     }
     s_s[t][c] = s; s_d[t][c] = d;
     __syncthreads();
@@ -1208,74 +1254,112 @@ __global__ __launch_bounds__(256) void ais_score_kernel(double *logw, int J, int
 }
 
 // LITERAL accumulation (bm_dbm_set_ais_literal; the reference's arithmetic, dbm.py:650-660 and :708-728): one call
-// adds or subtracts ONE log p*_beta(x) to the running log-weight, everything in float32 -
+// adds or subtracts ONE log p*_beta(x) to the running log-weight, everything in float32 - for L = 2
 //   lp = (x.hb0 * beta + sum_i softplus(beta (x W0^T + vb)_i)) + sum_k softplus(beta (x W1 + hb1)_k);   lz = lz -/+ lp
-// (`T1 *= beta; log_p = T1; log_p += reduce_sum(..); log_p += reduce_sum(..)`; `log_Z += / -= ...`).  The row sums
-// are the slot partials added in ascending order in float32.  logw holds the float value (exactly) in its double.
-__global__ __launch_bounds__(256) void ais_score_literal_kernel(double *logw, int J, int ld, const float *pv, int nv, const float *ph,
-                                                                int nh, const float *pd, int nd, float beta, int sign) {
+// (`T1 *= beta; log_p = T1; log_p += reduce_sum(..); log_p += reduce_sum(..)`; `log_Z += / -= ...`); at other depths
+// the odd-depth x.hb terms times beta in ascending depth, then the even-depth softplus sums in ascending depth.  The row
+// sums are the slot partials added in ascending order in float32.  logw holds the float value (exactly) in its double.
+__global__ __launch_bounds__(256) void ais_score_literal_kernel(double *logw, int J, int ld, AisScoreArgs p, float beta, int sign) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= J) return;
-    float sv = 0.f, sh = 0.f, dot = 0.f;
-    for (int q = 0; q < nv; ++q) sv = sv + pv[(size_t)q * ld + j];
-    for (int q = 0; q < nh; ++q) sh = sh + ph[(size_t)q * ld + j];
-    for (int q = 0; q < nd; ++q) dot = dot + pd[(size_t)q * ld + j];
-    float lp = dot * beta;
-    lp = lp + sv;
-    lp = lp + sh;
+    float lp = 0.f;
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+        if (o >= p.no) break;
+        float dot = 0.f;
+        for (int q = 0; q < p.no_slots[o]; ++q) dot = dot + p.po[o][(size_t)q * ld + j];
+        lp = (o == 0) ? dot * beta : lp + dot * beta;
+    }
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        if (e >= p.ne) break;
+        float sv = 0.f;
+        for (int q = 0; q < p.ne_slots[e]; ++q) sv = sv + p.pe[e][(size_t)q * ld + j];
+        lp = lp + sv;
+    }
     const float lz = (float)logw[j];
     logw[j] = (double)(sign > 0 ? lz + lp : lz - lp);
 }
 
-// the AIS run itself: leaves the per-chain log-weights (without log Z_0) in h->alogw [n_runs] (device, double)
+// the AIS run itself: leaves the per-chain log-weights (without log Z_0) in h->alogw [n_runs] (device, double).
+// Any depth: the chain is x = the odd-depth layers, log p*_beta(x) = beta sum_odd b_l.x_l + sum_even sum_i
+// softplus(beta a_{l,i}); one transition step updates the even-depth layers given x, then the odd-depth layers given
+// them, both in ascending depth.  For L = 2 this is the reference's construction (dbm.py:650-736) launch for launch.
 static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint64_t seed, int64_t chain0) {
-    BM_CHECK(h->L == 2, "AIS is implemented for 2-layer DBMs only (dbm.py:925)");
     BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "AIS needs Bernoulli visible units (dbm.py:926-927)");
-    BM_CHECK(!h->multinomial(0) && !h->multinomial(1), "AIS needs Bernoulli hidden layers (dbm.py:926-927)");
+    for (int i = 0; i < h->L; ++i) BM_CHECK(!h->multinomial(i), "AIS needs Bernoulli hidden layers (dbm.py:926-927)");
     BM_CHECK(n_betas >= 2 && n_runs >= 1 && k >= 1, "bad AIS arguments");
     BM_TRY(ensure_ais(h, n_runs));
-    const int R = n_runs, V = h->V, H1 = h->n[1], H2 = h->n[2];
+    const AisLayers S = ais_layers(h);
+    const int R = n_runs, V = h->V, H1 = h->n[1];
     const float db = 1.0f / (float)n_betas;                               // delta_beta (dbm.py:929)
-    // x.hb0 of the current / next state as slot partials (pitch ldp); x0's comes from rowdot_kernel as ONE slot
+    // x.hb of the current / next state as slot partials (pitch ldp); x0's comes from rowdot_kernel as ONE slot
     const int ldp = h->ais_rows;
-    float *rdot_cur = h->apart_x[0].p, *rdot_next = h->apart_x[1].p;
-    int nd_cur = 1;
+    Mat *x[2], *xn[2];                                                    // odd-depth states: current / next
+    float *rdot_cur[2], *rdot_next[2];
+    int nd_cur[2];
+    for (int o = 0; o < S.no; ++o) {
+        x[o] = &h->ao[o][0]; xn[o] = &h->ao[o][1];
+        rdot_cur[o] = h->apart_o[o][0].p; rdot_next[o] = h->apart_o[o][1].p;
+        nd_cur[o] = 1;
+    }
     BM_HIP(hipMemsetAsync(h->alogw, 0, (size_t)R * sizeof(double), h->stream));
-    Mat *x = &h->ax, *xn = &h->ax2;
-    hipLaunchKernelGGL(ais_init_kernel, dim3(512), dim3(256), 0, h->stream, x->p, x->ld, R, H1,
-                       dkey(h, SITE_AIS_X0, 0, seed, 0), (unsigned long long)chain0);
-    // fast-binary mode: every state of the run is a {0,1} bitmap when all three layers are sampled (the default)
+    for (int o = 0; o < S.no; ++o)                                        // odd-depth layer o: site SITE_AIS_X0 + 16 o
+        hipLaunchKernelGGL(ais_init_kernel, dim3(512), dim3(256), 0, h->stream, x[o]->p, x[o]->ld, R, h->n[S.od[o] + 1],
+                           dkey(h, SITE_AIS_X0, o, seed, 0), (unsigned long long)chain0);
+    // fast-binary mode: every state of the run is a {0,1} bitmap when all three layers are sampled (the default).
+    // 2-layer DBMs only: at other depths the run takes the fp32 path (bm355.h)
     struct FastScope { bm_dbm *h; ~FastScope() { h->fast_now = false; } } fast_scope{h};
-    if (h->fast && h->cfg.sample_v_states && h->cfg.sample_h_states[0] && h->cfg.sample_h_states[1]) {
+    if (h->fast && h->L == 2 && h->cfg.sample_v_states && h->cfg.sample_h_states[0] && h->cfg.sample_h_states[1]) {
+        const int H2 = h->n[2];
         BM_TRY(fast_build_planes(h));
         if (h->ax16.rows != h->ais_rows) {
             BM_TRY(h->ax16.alloc(1, h->ais_rows, H1)); BM_TRY(h->ax2_16.alloc(1, h->ais_rows, H1));
             BM_TRY(h->av16.alloc(1, h->ais_rows, V)); BM_TRY(h->ah2_16.alloc(1, h->ais_rows, H2));
         }
-        hipLaunchKernelGGL(shadow16_kernel, dim3(512), dim3(256), 0, h->stream, (const float *)x->p, x->ld, R, H1, h->ax16.p, h->ax16.ld);
+        hipLaunchKernelGGL(shadow16_kernel, dim3(512), dim3(256), 0, h->stream, (const float *)x[0]->p, x[0]->ld, R, H1, h->ax16.p, h->ax16.ld);
         h->fast_now = true; h->fast_ais = true;
     }
-    hipLaunchKernelGGL(rowdot_kernel, dim3((R + 3) / 4), dim3(256), 0, h->stream, (const float *)x->p, x->ld, R, H1,
-                       (const float *)h->hb[0].p, rdot_cur);
+    for (int o = 0; o < S.no; ++o)
+        hipLaunchKernelGGL(rowdot_kernel, dim3((R + 3) / 4), dim3(256), 0, h->stream, (const float *)x[o]->p, x[o]->ld, R,
+                           h->n[S.od[o] + 1], (const float *)h->hb[S.od[o]].p, rdot_cur[o]);
+
+    // the inputs of a layer update from the AIS states: an even-depth layer reads the odd-depth states x, an odd-depth
+    // layer the even-depth states (its neighbours in depth; the top layer has no `above`)
+    auto state_of = [&](int hidden) -> LayerIn {                          // state of hidden layer `hidden` (-1: v)
+        const int d = hidden + 1;
+        if (d & 1) { const Mat *m = x[d >> 1]; return LayerIn{m->p, m->ld}; }
+        return LayerIn{h->ae[d >> 1].p, h->ae[d >> 1].ld};
+    };
+    auto below_of = [&](int li) { return li < 0 ? LayerIn{nullptr, 0} : state_of(li - 1); };
+    auto above_of = [&](int li) { return li + 1 < h->L ? state_of(li + 1) : LayerIn{nullptr, 0}; };
+    auto site_of = [](int li) -> uint32_t { return li < 0 ? SITE_DBM_V : SITE_DBM_H + (uint32_t)li; };
+    auto width_of = [&](int li) { return li < 0 ? V : h->n[li + 1]; };
+    auto score_args = [&]() {
+        AisScoreArgs p;
+        memset(&p, 0, sizeof(p));
+        p.ne = S.ne; p.no = S.no;
+        for (int e = 0; e < S.ne; ++e) { p.pe[e] = h->apart_e[e].p; p.ne_slots[e] = nslots(width_of(S.ev[e])); }
+        for (int o = 0; o < S.no; ++o) { p.po[o] = rdot_cur[o]; p.no_slots[o] = nd_cur[o]; }
+        return p;
+    };
 
     // visit(x; beta_a, beta_b, beta_c): logw += log p*_{beta_b}(x) - log p*_{beta_a}(x) (score != 0),
     // then k transitions T_{beta_c} (dbm.py:662-694).  `step` feeds the RNG call counter.
     const bool literal = h->ais_literal != 0;
-    // literal mode: -log p*_{ba}(x) as its own pair of score-only launches (the default path shares the pre-activations
+    // literal mode: -log p*_{ba}(x) as its own score-only launches (the default path shares the pre-activations
     // of the transition and accumulates the DIFFERENCE of the two softplus terms per element, in double)
     auto score_only = [&](float bscore, int sign) -> int {
-        ActArgs e;
-        memset(&e, 0, sizeof(e));
-        e.rowacc = h->apart_v.p; e.ld_part = ldp; e.beta_b = bscore; e.rowacc_single = 1;
-        layer_update(h, -1, R, LayerIn{nullptr, 0}, LayerIn{x->p, x->ld}, bscore, bscore, 0, nullptr, nullptr, h->av.ld,
-                     dkey(h, SITE_DBM_V, 0, seed, 0), chain0, nullptr, nullptr, &e);
-        memset(&e, 0, sizeof(e));
-        e.rowacc = h->apart_h.p; e.ld_part = ldp; e.beta_b = bscore; e.rowacc_single = 1;
-        layer_update(h, 1, R, LayerIn{x->p, x->ld}, LayerIn{nullptr, 0}, bscore, bscore, 0, nullptr, nullptr, h->ah2.ld,
-                     dkey(h, SITE_DBM_H + 1, 0, seed, 0), chain0, nullptr, nullptr, &e);
+        for (int e = 0; e < S.ne; ++e) {
+            const int li = S.ev[e];
+            ActArgs a;
+            memset(&a, 0, sizeof(a));
+            a.rowacc = h->apart_e[e].p; a.ld_part = ldp; a.beta_b = bscore; a.rowacc_single = 1;
+            layer_update(h, li, R, below_of(li), above_of(li), bscore, bscore, 0, nullptr, nullptr, h->ae[e].ld,
+                         dkey(h, site_of(li), 0, seed, 0), chain0, nullptr, nullptr, &a);
+        }
         hipLaunchKernelGGL(ais_score_literal_kernel, dim3((R + 255) / 256), dim3(256), 0, h->stream, h->alogw, R, ldp,
-                           (const float *)h->apart_v.p, nslots(V), (const float *)h->apart_h.p, nslots(H2),
-                           (const float *)rdot_cur, nd_cur, bscore, sign);
+                           score_args(), bscore, sign);
         return 0;
     };
     auto visit = [&](bool score, float ba, float bb, bool transit, float bc, uint32_t step) -> int {
@@ -1286,35 +1370,39 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
         }
         for (int t = 0; t < (transit ? k : 1); ++t) {
             const bool sc = score && t == 0;
-            ActArgs e;
-            // v~ <- P(v | h = x): sigma(beta*x W0^T + beta*vb)  — and the visible softplus term of log p*
-            memset(&e, 0, sizeof(e));
-            if (sc) { e.rowacc = h->apart_v.p; e.ld_part = ldp; e.beta_a = ba; e.beta_b = bb; }
-            const int smp_v = transit && h->cfg.sample_v_states;
-            layer_update(h, -1, R, LayerIn{nullptr, 0}, LayerIn{x->p, x->ld}, bc, bc, smp_v,
-                         (transit && !smp_v) ? h->av.p : nullptr, (transit && smp_v) ? h->av.p : nullptr, h->av.ld,
-                         dkey(h, SITE_DBM_V, t, seed, step), chain0, nullptr, nullptr, &e);
-            // h2~ <- P(h2 | h = x): sigma(beta*x W1 + beta*hb1)  — and the top softplus term
-            memset(&e, 0, sizeof(e));
-            if (sc) { e.rowacc = h->apart_h.p; e.ld_part = ldp; e.beta_a = ba; e.beta_b = bb; }
-            const int smp_2 = transit && h->cfg.sample_h_states[1];
-            layer_update(h, 1, R, LayerIn{x->p, x->ld}, LayerIn{nullptr, 0}, bc, bc, smp_2,
-                         (transit && !smp_2) ? h->ah2.p : nullptr, (transit && smp_2) ? h->ah2.p : nullptr, h->ah2.ld,
-                         dkey(h, SITE_DBM_H + 1, t, seed, step), chain0, nullptr, nullptr, &e);
-            if (sc)     // both softplus terms + (bb - ba) * x.hb0, slots in fixed order, into the double log-weights
+            // even-depth layers given x: v~ <- sigma(beta*x W0^T + beta*vb), h2~ <- sigma(beta*(x1 W1 + x3 W2^T) + beta*hb1),
+            // ... - and each layer's softplus term of log p*
+            for (int e = 0; e < S.ne; ++e) {
+                const int li = S.ev[e];
+                ActArgs a;
+                memset(&a, 0, sizeof(a));
+                if (sc) { a.rowacc = h->apart_e[e].p; a.ld_part = ldp; a.beta_a = ba; a.beta_b = bb; }
+                const int smp = transit && (li < 0 ? h->cfg.sample_v_states : h->cfg.sample_h_states[li]);
+                float *out = h->ae[e].p;
+                layer_update(h, li, R, below_of(li), above_of(li), bc, bc, smp,
+                             (transit && !smp) ? out : nullptr, (transit && smp) ? out : nullptr, h->ae[e].ld,
+                             dkey(h, site_of(li), t, seed, step), chain0, nullptr, nullptr, &a);
+            }
+            if (sc)     // the softplus terms + (bb - ba) * x.hb, slots in fixed order, into the double log-weights
                 hipLaunchKernelGGL(ais_score_kernel, dim3((R + 31) / 32), dim3(256), 0, h->stream, h->alogw, R, ldp,
-                                   (const float *)h->apart_v.p, nslots(V), (const float *)h->apart_h.p, nslots(H2),
-                                   (const float *)rdot_cur, nd_cur, bb - ba);
+                                   score_args(), bb - ba);
             if (!transit) break;
-            // x^ <- P(h | v~, h2~): sigma(beta*(v W0 + h2 W1^T) + beta*hb0); also x^.hb0 for the next score
-            memset(&e, 0, sizeof(e));
-            e.rowdot_out = rdot_next; e.ld_part = ldp; e.dot_vec = h->hb[0].p;
-            const int smp_x = h->cfg.sample_h_states[0];
-            layer_update(h, 0, R, LayerIn{h->av.p, h->av.ld}, LayerIn{h->ah2.p, h->ah2.ld}, bc, bc, smp_x,
-                         nullptr, xn->p, xn->ld, dkey(h, SITE_DBM_H + 0, t, seed, step), chain0, nullptr, nullptr, &e);
-            Mat *tm = x; x = xn; xn = tm;
-            float *tr = rdot_cur; rdot_cur = rdot_next; rdot_next = tr;
-            nd_cur = nslots(H1);
+            // odd-depth layers given the new even-depth ones: x^ <- sigma(beta*(v W0 + h2 W1^T) + beta*hb0), ...; also
+            // x^.hb for the next score
+            for (int o = 0; o < S.no; ++o) {
+                const int li = S.od[o];
+                ActArgs a;
+                memset(&a, 0, sizeof(a));
+                a.rowdot_out = rdot_next[o]; a.ld_part = ldp; a.dot_vec = h->hb[li].p;
+                const int smp = h->cfg.sample_h_states[li];
+                layer_update(h, li, R, below_of(li), above_of(li), bc, bc, smp,
+                             nullptr, xn[o]->p, xn[o]->ld, dkey(h, site_of(li), t, seed, step), chain0, nullptr, nullptr, &a);
+            }
+            for (int o = 0; o < S.no; ++o) {
+                Mat *tm = x[o]; x[o] = xn[o]; xn[o] = tm;
+                float *tr = rdot_cur[o]; rdot_cur[o] = rdot_next[o]; rdot_next[o] = tr;
+                nd_cur[o] = nslots(h->n[S.od[o] + 1]);
+            }
         }
         return 0;
     };
@@ -1334,10 +1422,6 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
     return 0;
 }
 
-static double ais_log_Z0(const bm_dbm *h) {                                  // (:731-734)
-    return (double)(h->V + h->n[1] + h->n[2]) * (double)logf(2.0f);
-}
-
 int bm_dbm_ais(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint64_t seed, int64_t chain0,
                float *values_host) {
     BM_CHECK(values_host, "null output");
@@ -1346,9 +1430,9 @@ int bm_dbm_ais(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint64_t s
     std::vector<double> w(R);
     BM_HIP(hipMemcpyAsync(w.data(), h->alogw, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
-    const double logZ0 = ais_log_Z0(h);
+    const double logZ0 = ais_log_Z0(h, h->ais_literal != 0);
     if (h->ais_literal) {                        // log_Z += log_Z0 in float32 (:731-734)
-        const float z0 = (float)(h->V + h->n[1] + h->n[2]) * logf(2.0f);
+        const float z0 = (float)logZ0;
         for (int r = 0; r < R; ++r) values_host[r] = (float)w[r] + z0;
     } else {
         for (int r = 0; r < R; ++r) values_host[r] = (float)(w[r] + logZ0);
@@ -1395,7 +1479,7 @@ int bm_dbm_ais_sharded(bm_dbm *h, bm_comm *c, int32_t n_betas, int32_t n_runs_to
         (void)hipMemcpyAsync(send, nan.data(), nan.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
         (void)hipStreamSynchronize(h->stream);
     } else {
-        const double z0 = h->ais_literal ? (double)((float)(h->V + h->n[1] + h->n[2]) * logf(2.0f)) : ais_log_Z0(h);
+        const double z0 = ais_log_Z0(h, h->ais_literal != 0);
         hipLaunchKernelGGL(ais_finish_kernel, dim3((npad + 255) / 256), dim3(256), 0, h->stream, (const double *)h->alogw, send,
                            n, npad, z0, h->ais_literal);
     }
@@ -1418,60 +1502,69 @@ int bm_dbm_ais_sharded(bm_dbm *h, bm_comm *c, int32_t n_betas, int32_t n_runs_to
     return 0;
 }
 
-// per-row bias terms and entropies of the ELBO (dbm.py:746-756), one wave per row; p0 / p1: slot partials of
-// sum((X W0) * mu0) and sum((mu0 W1) * mu1) from the two propagations (pitch ldp), added in slot order
-__global__ __launch_bounds__(256) void elbo_row_kernel(const float *X, int ldx, int V, const float *vb,
-                                                       const float *mu0, int ld0, int H1, const float *hb0,
-                                                       const float *mu1, int ld1, int H2, const float *hb1,
-                                                       int rows, const float *p0, int n0, const float *p1, int n1, int ldp,
-                                                       float *out) {
+// the per-layer inputs of elbo_row_kernel: mu_l (pitch ld), its width, its bias, and the slot partials of
+// sum((mu_{l-1} W_l) * mu_l) (mu_{-1} = X) from layer l's propagation
+struct ElboLayers {
+    const float *mu[MAXL]; int ld[MAXL], n[MAXL]; const float *hb[MAXL];
+    const float *part[MAXL]; int nslot[MAXL];
+    int L;
+};
+
+// per-row bias terms and entropies of the ELBO (dbm.py:746-756, every layer), one wave per row; the slot partials of
+// the propagations (pitch ldp) are added layer after layer in slot order
+__global__ __launch_bounds__(256) void elbo_row_kernel(const float *X, int ldx, int V, const float *vb, ElboLayers m,
+                                                       int rows, int ldp, float *out) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     float s = 0.f;
     for (int c = lane; c < V; c += 64) s += X[(size_t)row * ldx + c] * vb[c];
-    for (int c = lane; c < H1; c += 64) {
-        const float m = mu0[(size_t)row * ld0 + c];
-        s += m * hb0[c];
-        const float q = fminf(fmaxf(m, 1e-7f), 1.f - 1e-7f);
-        s += -q * logf(q) - (1.f - q) * logf(1.f - q);
-    }
-    for (int c = lane; c < H2; c += 64) {
-        const float m = mu1[(size_t)row * ld1 + c];
-        s += m * hb1[c];
-        const float q = fminf(fmaxf(m, 1e-7f), 1.f - 1e-7f);
-        s += -q * logf(q) - (1.f - q) * logf(1.f - q);
+#pragma unroll
+    for (int l = 0; l < MAXL; ++l) {
+        if (l >= m.L) break;
+        for (int c = lane; c < m.n[l]; c += 64) {
+            const float u = m.mu[l][(size_t)row * m.ld[l] + c];
+            s += u * m.hb[l][c];
+            const float q = fminf(fmaxf(u, 1e-7f), 1.f - 1e-7f);
+            s += -q * logf(q) - (1.f - q) * logf(1.f - q);
+        }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if (lane == 0) {
         double e = 0.0;
-        for (int q = 0; q < n0; ++q) e += (double)p0[(size_t)q * ldp + row];
-        for (int q = 0; q < n1; ++q) e += (double)p1[(size_t)q * ldp + row];
+#pragma unroll
+        for (int l = 0; l < MAXL; ++l) {
+            if (l >= m.L) break;
+            for (int q = 0; q < m.nslot[l]; ++q) e += (double)m.part[l][(size_t)q * ldp + row];
+        }
         out[row] = (float)(e + (double)s);
     }
 }
 
 int bm_dbm_log_proba(bm_dbm *h, const float *X_dev, float *out_host) {
-    BM_CHECK(h->L == 2, "log_proba is implemented for 2-layer DBMs only (dbm.py:741-756)");
-    BM_CHECK(!h->multinomial(0) && !h->multinomial(1), "log_proba needs Bernoulli hidden layers (dbm.py:947-948)");
+    for (int i = 0; i < h->L; ++i) BM_CHECK(!h->multinomial(i), "log_proba needs Bernoulli hidden layers (dbm.py:947-948)");
     BM_CHECK(out_host, "null output");
     BM_TRY(mean_field(h, X_dev, nullptr));
     BM_TRY(ensure_ais(h, h->N));
-    // sum((X W0) * mu0) and sum((mu0 W1) * mu1) as dot-epilogues of the two propagations (slot partials)
+    // sum((X W0) * mu0), sum((mu0 W1) * mu1), ... as dot-epilogues of the layers' propagations (slot partials; the
+    // AIS partial buffers, of which ensure_ais allocates at least L)
     const int ldp = h->ais_rows;
-    ActArgs e;
-    memset(&e, 0, sizeof(e));
-    e.rowacc = h->apart_v.p; e.ld_part = ldp; e.dot_mat = h->mu[0].p; e.ld_dot = h->mu[0].ld;
-    layer_update(h, 0, h->N, LayerIn{X_dev, h->V}, LayerIn{nullptr, 0}, 1.f, 1.f, 0, nullptr, nullptr, h->mu[0].ld,
-                 dkey(h, 0, 0, h->seed, h->call), 0, nullptr, nullptr, &e);
-    memset(&e, 0, sizeof(e));
-    e.rowacc = h->apart_h.p; e.ld_part = ldp; e.dot_mat = h->mu[1].p; e.ld_dot = h->mu[1].ld;
-    layer_update(h, 1, h->N, LayerIn{h->mu[0].p, h->mu[0].ld}, LayerIn{nullptr, 0}, 1.f, 1.f, 0, nullptr, nullptr,
-                 h->mu[1].ld, dkey(h, 0, 0, h->seed, h->call), 0, nullptr, nullptr, &e);
+    DevBuf *parts[MAXL] = {&h->apart_e[0], &h->apart_e[1], &h->apart_o[0][0], &h->apart_o[0][1]};
+    ElboLayers m;
+    memset(&m, 0, sizeof(m));
+    m.L = h->L;
+    for (int l = 0; l < h->L; ++l) {
+        ActArgs e;
+        memset(&e, 0, sizeof(e));
+        e.rowacc = parts[l]->p; e.ld_part = ldp; e.dot_mat = h->mu[l].p; e.ld_dot = h->mu[l].ld;
+        const LayerIn below = l == 0 ? LayerIn{X_dev, h->V} : LayerIn{h->mu[l - 1].p, h->mu[l - 1].ld};
+        layer_update(h, l, h->N, below, LayerIn{nullptr, 0}, 1.f, 1.f, 0, nullptr, nullptr, h->mu[l].ld,
+                     dkey(h, 0, 0, h->seed, h->call), 0, nullptr, nullptr, &e);
+        m.mu[l] = h->mu[l].p; m.ld[l] = h->mu[l].ld; m.n[l] = h->n[l + 1]; m.hb[l] = h->hb[l].p;
+        m.part[l] = parts[l]->p; m.nslot[l] = nslots(h->n[l + 1]);
+    }
     hipLaunchKernelGGL(elbo_row_kernel, dim3((h->N + 3) / 4), dim3(256), 0, h->stream, X_dev, h->V, h->V,
-                       (const float *)h->vb.p, (const float *)h->mu[0].p, h->mu[0].ld, h->n[1], (const float *)h->hb[0].p,
-                       (const float *)h->mu[1].p, h->mu[1].ld, h->n[2], (const float *)h->hb[1].p, h->N,
-                       (const float *)h->apart_v.p, nslots(h->n[1]), (const float *)h->apart_h.p, nslots(h->n[2]), ldp, h->rowtmp.p);
+                       (const float *)h->vb.p, m, h->N, ldp, h->rowtmp.p);
     BM_HIP(hipMemcpyAsync(out_host, h->rowtmp.p, (size_t)h->N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     h->call++;

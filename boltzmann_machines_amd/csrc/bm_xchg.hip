@@ -1074,7 +1074,7 @@ int bm_dbm_ais_sharded_direct(bm_dbm *h, bm_xchg *x, int32_t n_betas, int32_t n_
     int rc = 0;
     if (b > a) rc = ais_core(h, n_betas, b - a, k, seed, a);
     if (rc) { first_err = bm_last_error(); (void)hipGetLastError(); }
-    const double z0 = h->ais_literal ? (double)((float)(h->V + h->n[1] + h->n[2]) * logf(2.0f)) : ais_log_Z0(h);
+    const double z0 = ais_log_Z0(h, h->ais_literal != 0);
     h->xchg_used = x; x->user = &h->xchg_used;
     int rc_x = 0, rc_m = 0;
     for (size_t lo = 0; lo < (size_t)n_runs_total && !rc_x && !rc_m; lo += x->count) {

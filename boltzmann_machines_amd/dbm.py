@@ -474,9 +474,20 @@ class DBM(EngineModel):
 
     @run_on_engine(update_seed=True)
     def log_Z(self, n_betas=100, n_runs=100, n_gibbs_steps=5):
-        """AIS estimate of the log partition function of the 2-layer binary DBM
-        (reference dbm.py:899-939).  Returns log_mean, (log_low, log_high), values."""
-        assert self.n_layers_ == 2
+        """AIS estimate of the log partition function of a binary DBM of any depth (reference dbm.py:899-939 for two
+        layers).  Returns log_mean, (log_low, log_high), values.
+
+        The AIS chain runs over the odd-depth layers x = {h1, h3} (the visible layer has depth 0); the even-depth
+        layers {v, h2, h4} are conditionally independent given x and summed out analytically:
+        log p*_beta(x) = beta sum_odd b_l.x_l + sum_even sum_i softplus(beta a_{l,i}), with a_l the pre-activation of
+        layer l from its neighbours in x and its bias.  One transition updates the even-depth layers given x, then the
+        odd-depth layers given them.  For two layers this is exactly the reference's construction.
+
+        A one-layer `DBM(rbms=[rbm])` is not the distribution of `rbm`: the DBM composition halves the hidden bias of
+        the first layer at every depth (`_make_vars`, reference dbm.py:266-291).  The value estimated here is the log
+        partition function of the DBM's own parameters.  float64 models: two layers only."""
+        if np.dtype(self.dtype) == np.float64:
+            assert self.n_layers_ == 2         # the float64 path (csrc/bm_dbm64.hip) has the 2-layer AIS only
         assert self._all_bernoulli()           # reference dbm.py:926-927: every layer is a BernoulliLayer
         self._engine.set_ais_literal(self._ais_literal)
         if getattr(self, '_comm', None) is not None:
@@ -493,8 +504,11 @@ class DBM(EngineModel):
 
     @run_on_engine()
     def log_proba(self, X_test, log_Z):
-        """Variational lower bound on log p(x) for the 2-layer binary DBM (reference dbm.py:941-957)."""
-        assert self.n_layers_ == 2
+        """Variational lower bound on log p(x) for a binary DBM of any depth (reference dbm.py:941-957 for two layers):
+        per row, sum_l sum((mu_{l-1} W_l) * mu_l) (mu_{-1} = x) + x.vb + sum_l mu_l.hb_l + the entropies of every
+        mean-field posterior mu_l (clipped to [1e-7, 1 - 1e-7]), minus `log_Z`.  float64 models: two layers only."""
+        if np.dtype(self.dtype) == np.float64:
+            assert self.n_layers_ == 2
         assert self._all_bernoulli()           # reference dbm.py:947-948
         X_test = np.ascontiguousarray(X_test, dtype=self._engine.dtype)
         self._check_batches(X_test)

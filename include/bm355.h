@@ -285,18 +285,29 @@ int bm_dbm_reconstruct(bm_dbm *h, const float *X_dev, float *R_dev);
 /* sample_v op (dbm.py:641-648, public :887-897): k PCD sweeps, one mean
  * sweep, v <- v_means; copies v to V_dev [M, V] if non-NULL. */
 int bm_dbm_sample_v(bm_dbm *h, int32_t n_gibbs_steps, float *V_dev);
-/* AIS (dbm.py:650-736; public log_Z :899-939) for the 2-layer Bernoulli
- * DBM: n_runs chains, n_betas temperatures, n_gibbs_steps transitions per
- * temperature.  values_host [n_runs] receives the per-chain log Z estimates
- * (host post-processing with log_mean_exp stays in Python, dbm.py:935-939).
- * chain0 = global index of this rank's first chain (chains shard over ranks).
+/* AIS (dbm.py:650-736; public log_Z :899-939) for a Bernoulli DBM of any
+ * depth (1..4 layers): n_runs chains, n_betas temperatures, n_gibbs_steps
+ * transitions per temperature.  values_host [n_runs] receives the per-chain
+ * log Z estimates (host post-processing with log_mean_exp stays in Python,
+ * dbm.py:935-939).  chain0 = global index of this rank's first chain (chains
+ * shard over ranks).
+ * Depth rule: v has depth 0, hidden layer i depth i + 1.  The chain x is the
+ * odd-depth layers {h1, h3}; the even-depth layers {v, h2, h4} are summed out
+ * analytically: log p*_beta(x) = beta sum_odd b.x + sum_even sum softplus(beta a),
+ * log Z_0 = (V + sum n_i) log 2.  A transition updates the even-depth layers
+ * given x, then the odd-depth layers given them, each in ascending depth.  For
+ * two layers this is the reference's construction.
+ * RNG sites (Philox, counter word site + 16 t, call = beta step, row offset =
+ * global chain index): 12 for v, 8 + i for hidden layer i; x_0 ~ Ber(1/2) of
+ * the j-th odd-depth layer from site 13 + 16 j, call 0.
  * The per-beta terms are fp32 as in the reference; their sum over the betas is kept in DOUBLE on the device (the
  * reference accumulates it in fp32, dbm.py:708-728, and loses nats at 1000 betas): a deliberate, documented deviation. */
 int bm_dbm_ais(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t n_gibbs_steps,
                uint64_t seed, int64_t chain0, float *values_host);
-/* log_proba op (dbm.py:738-759): MF then -E_q[E] + H(mu) per row of
- * X_dev [batch_size, V] into out_host [batch_size] (log Z is subtracted by
- * the Python caller, dbm.py:955-956). */
+/* log_proba op (dbm.py:738-759, any depth): MF then -E_q[E] + H(mu) per row
+ * of X_dev [batch_size, V] into out_host [batch_size]: sum_l sum((mu_{l-1} W_l)
+ * * mu_l) (mu_{-1} = X) + X.vb + sum_l mu_l.hb_l + the entropies of every mu_l
+ * (log Z is subtracted by the Python caller, dbm.py:955-956). */
 int bm_dbm_log_proba(bm_dbm *h, const float *X_dev, float *out_host);
 
 int bm_dbm_timer_start(bm_dbm *h);
@@ -410,6 +421,7 @@ int bm_dbm_ais_sharded_direct(bm_dbm *h, bm_xchg *x, int32_t n_betas, int32_t n_
  * EXACTLY into three bf16 planes and run on the bf16 matrix cores - exact products, fp32 accumulation in a
  * different order than the default chain: results agree to fp32 round-off (free energy / log-weights 1e-5, bitmaps
  * identical except where |u - p| is at round-off distance), NOT bit for bit.  Never the default.
+ * AIS in this mode: 2-layer DBMs only; at other depths bm_dbm_ais runs the fp32 path (the default's values, bit for bit).
  * on = 1: where the mode was measured FASTER than the fp32 path - AIS always; the sampling sweep of an RBM and the particle
  * sweeps of a DBM only from 8M weights in the (bottom) weight matrix upwards (3072 x 5000 gains, 784 x 1024 loses: there the
  * passes are bound by their fill and epilogue, not by matrix time).  on = 2: wherever legal (tests, measurements). */
