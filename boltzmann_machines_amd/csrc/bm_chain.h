@@ -214,6 +214,10 @@ struct ChainState {
     long long *stamps = nullptr;                     // BM355_DEBUG=chain_stamps=file: timeline of the LAST chained launch, dumped at release
     static constexpr int CLAIM_SLOTS = 16;
     static constexpr size_t STAMP_WORDS = 256 * 16 * 8;
+    ChainState() = default;
+    ChainState(const ChainState &) = delete;
+    ChainState &operator=(const ChainState &) = delete;
+    ~ChainState() { release(); }
     void release() {
         if (stamps) {
             const char *f = bm::dbg("chain_stamps");

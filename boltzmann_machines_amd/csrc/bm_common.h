@@ -1,11 +1,13 @@
-// bm_common.h — error plumbing + device buffer helper shared by the API files.
+// bm_common.h — error plumbing + the owners of device buffers, streams and events shared by the API files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <string>
+#include <utility>
 #include <map>
 #include <vector>
 
@@ -62,23 +64,81 @@ static inline const char *dbg(const char *name) {
         if (_r) return _r;        \
     } while (0)
 
-struct DevBuf {
-    float *p = nullptr;
+// ---- owners of the engines' HIP resources.  Each is move-only and frees what it holds when it is destroyed or
+// overwritten, so a handle frees itself member by member and an early return frees whatever was built so far.  A failed
+// allocation or creation records the message (set_error), clears HIP's last error - a later, unrelated
+// hipGetLastError() must not report it - and leaves the owner empty.
+static inline int hip_failed(hipError_t e, const char *what, size_t bytes = 0) {
+    (void)hipGetLastError();
+    if (bytes) set_error("%s of %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
+    else set_error("%s failed: %s", what, hipGetErrorString(e));
+    return 1;
+}
+
+// a typed device array of n elements, zero-filled
+template <class T> struct DevArray {
+    T *p = nullptr;
     size_t n = 0;
-    int alloc(size_t count) {
-        n = count;
-        count = (count + 3) & ~(size_t)3;      // whole 16-byte groups: vector kernels (bm_xchg) may touch the round-up
-        if (count == 0) count = 4;
-        BM_HIP(hipMalloc((void **)&p, count * sizeof(float)));
-        BM_HIP(hipMemset(p, 0, count * sizeof(float)));
+    DevArray() = default;
+    DevArray(DevArray &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevArray &operator=(DevArray o) noexcept { std::swap(p, o.p); std::swap(n, o.n); return *this; }
+    ~DevArray() { if (p) (void)hipFree(p); }
+    // n = count; max(count, room, 1) elements are allocated and zeroed.  Any earlier allocation is freed first.
+    int alloc(size_t count, size_t room = 1) {
+        *this = DevArray();
+        DevArray a;
+        const size_t bytes = std::max(count, room) * sizeof(T);
+        hipError_t e = hipMalloc((void **)&a.p, bytes);
+        if (e != hipSuccess) { a.p = nullptr; return hip_failed(e, "hipMalloc", bytes); }
+        if ((e = hipMemset(a.p, 0, bytes)) != hipSuccess) return hip_failed(e, "hipMemset", bytes);
+        a.n = count;
+        *this = std::move(a);
         return 0;
     }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
 };
+
+// float vector: the allocation is rounded up to whole 16-byte groups (vector kernels of bm_xchg may touch the round-up)
+struct DevBuf : DevArray<float> {
+    int alloc(size_t count) { return DevArray::alloc(count, count ? (count + 3) & ~(size_t)3 : 4); }
+};
+
+// a stream, an event or pinned host memory (the raw value converts implicitly, so call sites use it as before)
+static inline void hip_destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
+static inline void hip_destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+static inline void hip_destroy(void *host) { (void)hipHostFree(host); }
+template <class H> struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(Owned &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned &operator=(Owned o) noexcept { std::swap(h, o.h); return *this; }
+    ~Owned() { if (h) hip_destroy(h); }
+    operator H() const { return h; }
+};
+using Stream = Owned<hipStream_t>;
+using Event = Owned<hipEvent_t>;
+template <class T> using Pinned = Owned<T *>;
+
+static inline int create(Stream &s, unsigned flags = hipStreamDefault) {
+    Stream t;
+    const hipError_t e = hipStreamCreateWithFlags(&t.h, flags);
+    if (e != hipSuccess) { t.h = nullptr; return hip_failed(e, "hipStreamCreateWithFlags"); }
+    s = std::move(t);
+    return 0;
+}
+static inline int create(Event &ev, unsigned flags = hipEventDefault) {
+    Event t;
+    const hipError_t e = hipEventCreateWithFlags(&t.h, flags);
+    if (e != hipSuccess) { t.h = nullptr; return hip_failed(e, "hipEventCreateWithFlags"); }
+    ev = std::move(t);
+    return 0;
+}
+template <class T> static inline int create(Pinned<T> &m, size_t count) {
+    Pinned<T> t;
+    const hipError_t e = hipHostMalloc((void **)&t.h, count * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess) { t.h = nullptr; return hip_failed(e, "hipHostMalloc", count * sizeof(T)); }
+    m = std::move(t);
+    return 0;
+}
 
 // Leading dimension for matrices owned by the library.  A row pitch that is a
 // multiple of 256 B (e.g. H = 1024 floats = 4 KiB) makes every row of a K-chunk
@@ -90,15 +150,13 @@ static inline int pad_ld(int n) {
 }
 
 // row-major [rows][cols] matrix in HBM with padded pitch `ld`
-struct Mat {
-    float *p = nullptr;
+struct Mat : DevArray<float> {
     int rows = 0, cols = 0, ld = 0;
     size_t count() const { return (size_t)rows * ld; }
     int alloc(int r, int c) {
+        rows = cols = ld = 0;
+        BM_TRY(DevArray::alloc((size_t)r * pad_ld(c)));
         rows = r; cols = c; ld = pad_ld(c);
-        size_t cnt = count() ? count() : 1;
-        BM_HIP(hipMalloc((void **)&p, cnt * sizeof(float)));
-        BM_HIP(hipMemset(p, 0, cnt * sizeof(float)));
         return 0;
     }
     int upload(const float *host) {   // dense host [rows][cols] -> device
@@ -111,29 +169,19 @@ struct Mat {
                            (size_t)cols * sizeof(float), rows, hipMemcpyDeviceToHost));
         return 0;
     }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
 };
 
 // bf16 matrix [planes][rows][ld] (bm_bf3.h): weight planes or the shadow of a {0,1} state matrix; ld % 64 == 0,
 // zero initialised (the padding must stay zero: the bf16 contraction has no K tail handling)
-struct Mat16 {
-    uint16_t *p = nullptr;
+struct Mat16 : DevArray<uint16_t> {
     int planes = 0, rows = 0, cols = 0, ld = 0;
     long long plane_stride() const { return (long long)rows * ld; }
     int alloc(int np, int r, int c) {
-        release();
-        planes = np; rows = r; cols = c; ld = (c + 63) & ~63;
-        const size_t bytes = (size_t)np * r * ld * sizeof(uint16_t);
-        BM_HIP(hipMalloc((void **)&p, bytes ? bytes : 2));
-        BM_HIP(hipMemset(p, 0, bytes ? bytes : 2));
+        planes = rows = cols = ld = 0;
+        const int l = (c + 63) & ~63;
+        BM_TRY(DevArray::alloc((size_t)np * r * l));
+        planes = np; rows = r; cols = c; ld = l;
         return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr; planes = rows = cols = ld = 0;
     }
 };
 

@@ -10,6 +10,7 @@
 #include "bm_kernels.h"
 
 #include <math.h>
+#include <memory>
 
 using namespace bm;
 
@@ -33,14 +34,15 @@ struct bm_dbm {
     unsigned dw_set_mask = 0;              // layers whose dW the host has replaced since the buffers became sharded
     int L, V, N, M;
     int n[MAXL + 1];                       // n[0] = V, n[i+1] = hidden layer i
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Stream stream;                         // (streams first: members are destroyed in reverse order)
+    Event ev0, ev1;
     // The fantasy-particle sweeps (PCD) read only the parameters and the particles, the mean-field only the
     // parameters, X and mu: within one update they are independent, so the particle sweeps run on a second stream
     // (fork at the start of the update, join before the gradients) and fill the launch / fill / tail gaps of the
     // small mean-field kernels.  `cur` is the stream layer_update / gibbs_sweep enqueue on.
-    hipStream_t stream2 = nullptr, cur = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Stream stream2;
+    hipStream_t cur = nullptr;
+    Event ev_fork, ev_join;
     int pcd_geo = 0;                               // tile of the particle passes while they share the chip with the mean-field
                                                    // loop (ActArgs::geo_hint; BM355_DEBUG=dbm_pcd_geo=N, 0 = the tuner's choice):
                                                    // 3 (32 x 32, 32 KiB) where there IS a loop of small latency-bound passes to
@@ -59,8 +61,8 @@ struct bm_dbm {
     // mean-field loop control mirror: pinned host copies of `ctl`, one per enqueued group of sweeps, so that the next
     // group is enqueued BEFORE the previous group's result is read (the GPU never waits for the host)
     static constexpr int MF_RING = 4;
-    MfCtl *ctl_host = nullptr;
-    hipEvent_t ctl_ev[MF_RING] = {nullptr, nullptr, nullptr, nullptr};
+    Pinned<MfCtl> ctl_host;
+    Event ctl_ev[MF_RING];
     int mf_pred = 0;                               // trip count of the previous mean-field call (size of the first group)
     // variables
     Mat W[MAXL], Wt[MAXL], dW[MAXL];       // W[i]: [n[i]][n[i+1]]
@@ -84,11 +86,11 @@ struct bm_dbm {
     bool failed = false;                           // a launch helper could not allocate (sticky; reported by the entry points)
     bool multinomial(int layer) const { return layer >= 0 && cfg.h_unit[layer] == BM_UNIT_MULTINOMIAL; }
     unsigned *flag = nullptr;                      // mean-field residual cell (= &ctl->maxdiff)
-    MfCtl *ctl = nullptr;                          // device-side loop control
+    DevArray<MfCtl> ctl;                           // device-side loop control
     DevBuf mfblk;                                  // [2][MAXL * BM_MF_SLOTS] per-workgroup residual slots of the mean-field
                                                    // sweeps, double-buffered by sweep parity (ActArgs::chk_ctl)
     Mat xw0;                                       // [N][n1] hoisted X.W0 of the current minibatch
-    double *scal = nullptr;
+    DevArray<double> scal;
     // AIS / ELBO workspaces (allocated on demand).  AIS state by depth (depth 0 = v, depth i + 1 = hidden layer i): the
     // odd-depth layers {h1, h3} are the chain x, the even-depth layers {v, h2, h4} are summed out analytically
     int ais_rows = 0;
@@ -98,8 +100,9 @@ struct bm_dbm {
                                                    // even-depth layers (AIS) / the layers' sum((mu_{l-1} W_l) * mu_l) (ELBO)
     DevBuf apart_o[2][2];                          // x.hb of the odd-depth layers, current / next (ActArgs::rowdot_out)
     DevBuf rowtmp;
-    double *alogw = nullptr;                       // [ais_rows] log-weights, accumulated in double in a fixed order
+    DevArray<double> alogw;                        // [ais_rows] log-weights, accumulated in double in a fixed order
     DevBuf ais_send, ais_recv;                     // bm_dbm_ais_sharded: this rank's values / the all-gathered values
+    Mat sv_v[2], sv_H[2][MAXL];                    // bm_dbm_sample_v: ping-pong states of its mean sweeps [M][*]
     // fast-binary mode (bm_bf3.h, bm_dbm_set_fast_binary): bf16 planes of W_l (x = below unit, k = above unit) and of
     // W_l^T, bf16 shadows of the AIS state matrices; `fast_now` is set while a sweep with all-binary states runs
     int ais_literal = 0;                           // bm_dbm_set_ais_literal: float32 accumulation in the reference's order
@@ -155,7 +158,7 @@ static int fast_build_planes(bm_dbm *h, hipStream_t st = nullptr, bool skip_t0 =
     if (!st) st = h->stream;
     for (int l = 0; l < h->L; ++l) {
         const int a = h->n[l], b = h->n[l + 1];
-        if (h->W3[l].rows != a || h->W3[l].cols != b) { BM_TRY(h->W3[l].alloc(3, a, b)); BM_TRY(h->W3t[l].alloc(3, b, a)); }
+        if (h->W3t[l].rows != b || h->W3t[l].cols != a) { BM_TRY(h->W3[l].alloc(3, a, b)); BM_TRY(h->W3t[l].alloc(3, b, a)); }
         hipLaunchKernelGGL(split3_kernel, dim3(1024), dim3(256), 0, st, (const float *)h->W[l].p, h->W[l].ld, a, b,
                            h->W3[l].p, h->W3[l].plane_stride(), h->W3[l].ld, 0);
         if (!(skip_t0 && l == 0))
@@ -251,7 +254,6 @@ static void layer_update(bm_dbm *h, int layer /* hidden layer index, -1 = visibl
         if (!lg) {                                 // sampled sweep: the means are not kept, they pass through a row store
             if (h->logit_rows[layer] < J) {
                 // (bm_dbm_create preallocates max(N, M) rows: this only grows the store for an unusual row count)
-                h->logits[layer].release();
                 if (h->logits[layer].alloc(J, a.I)) { h->failed = true; h->logit_rows[layer] = 0; return; }
                 h->logit_rows[layer] = J;
             }
@@ -289,7 +291,7 @@ static void gibbs_sweep(bm_dbm *h, int J, LayerIn vin, const Mat *Hin, Mat *vout
         e.skip = skip;
         e.maxdiff_blk = (maxdiff && mfblk) ? mfblk + (size_t)i * BM_MF_SLOTS : nullptr;
         if (i == 0 && chk_slots) {     // the sweep's first kernel evaluates the loop control of the previous sweep
-            e.chk_ctl = h->ctl; e.chk_slots = chk_slots; e.chk_n = L * BM_MF_SLOTS; e.chk_tol = h->cfg.mf_tol;
+            e.chk_ctl = h->ctl.p; e.chk_slots = chk_slots; e.chk_n = L * BM_MF_SLOTS; e.chk_tol = h->cfg.mf_tol;
         }
         if (i == 0 && xw0 && above.p && !h->multinomial(0)) {
             // mean-field: X.W0 is loop invariant — start the chain from the hoisted partial sum and
@@ -425,16 +427,16 @@ static int mean_field(bm_dbm *h, const float *X_dev, int *out_n, MfMid *mid = nu
         // needed and the ranks stay in lockstep)
         auto ctl_step = [&](int init) -> int {
             if (!h->comm && !h->xchg) {
-                hipLaunchKernelGGL(mf_ctl_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl, h->cfg.mf_tol, init,
+                hipLaunchKernelGGL(mf_ctl_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl.p, h->cfg.mf_tol, init,
                                    h->mfblk.p, h->L * BM_MF_SLOTS);
                 return 0;
             }
             if (h->xchg)     // residual -> max over the ranks -> latch in ONE launch (three launches per sweep were 0.4 ms of a
                              // 1.8 ms data-parallel update at 45 sweeps)
-                return xchg_mf_ctl_step(h->xchg, h->ctl, h->mfblk.p, h->L * BM_MF_SLOTS, h->cfg.mf_tol, init, h->stream);
-            hipLaunchKernelGGL(mf_resid_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl, h->mfblk.p, h->L * BM_MF_SLOTS);
-            BM_TRY(bm_comm_allreduce_max(h->comm, &h->ctl->resid, 1, (void *)h->stream));
-            hipLaunchKernelGGL(mf_latch_kernel, dim3(1), dim3(64), 0, h->stream, h->ctl, h->cfg.mf_tol, init);
+                return xchg_mf_ctl_step(h->xchg, h->ctl.p, h->mfblk.p, h->L * BM_MF_SLOTS, h->cfg.mf_tol, init, h->stream);
+            hipLaunchKernelGGL(mf_resid_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl.p, h->mfblk.p, h->L * BM_MF_SLOTS);
+            BM_TRY(bm_comm_allreduce_max(h->comm, &h->ctl.p->resid, 1, (void *)h->stream));
+            hipLaunchKernelGGL(mf_latch_kernel, dim3(1), dim3(64), 0, h->stream, h->ctl.p, h->cfg.mf_tol, init);
             return 0;
         };
         // Self-controlled sweeps (single GPU, Bernoulli layers, grids that fit the residual slots): the loop-control
@@ -466,24 +468,24 @@ static int mean_field(bm_dbm *h, const float *X_dev, int *out_n, MfMid *mid = nu
                 if (self_ctl) {
                     float *mine = h->mfblk.p + (size_t)(sw & 1) * set_sz, *prev = h->mfblk.p + (size_t)((sw & 1) ^ 1) * set_sz;
                     gibbs_sweep(h, N, LayerIn{X_dev, h->V}, src, nullptr, dst, false, false, 0, 0, h->flag,
-                                hoist ? &h->xw0 : nullptr, &h->ctl->done, mine, s > 0 ? prev : nullptr);
+                                hoist ? &h->xw0 : nullptr, &h->ctl.p->done, mine, s > 0 ? prev : nullptr);
                     if (s == g - 1)      // Check(last sweep of the group); it also clears the slots it read
-                        hipLaunchKernelGGL(mf_ctl_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl, h->cfg.mf_tol, 0,
+                        hipLaunchKernelGGL(mf_ctl_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl.p, h->cfg.mf_tol, 0,
                                            mine, h->L * BM_MF_SLOTS);
                 } else {
                     gibbs_sweep(h, N, LayerIn{X_dev, h->V}, src, nullptr, dst, false, false, 0, 0, h->flag,
-                                hoist ? &h->xw0 : nullptr, &h->ctl->done, h->mfblk.p);
+                                hoist ? &h->xw0 : nullptr, &h->ctl.p->done, h->mfblk.p);
                     BM_TRY(ctl_step(0));
                 }
             }
             enq += g;
-            BM_HIP(hipMemcpyAsync(&h->ctl_host[g_enq % R], h->ctl, sizeof(MfCtl), hipMemcpyDeviceToHost, h->stream));
+            BM_HIP(hipMemcpyAsync(&h->ctl_host[g_enq % R], h->ctl.p, sizeof(MfCtl), hipMemcpyDeviceToHost, h->stream));
             BM_HIP(hipEventRecord(h->ctl_ev[g_enq % R], h->stream));
             ++g_enq;
             return 0;
         };
         if (max_it <= 0) {                 // no sweeps: fetch the step-0 record
-            BM_HIP(hipMemcpyAsync(&h->ctl_host[0], h->ctl, sizeof(MfCtl), hipMemcpyDeviceToHost, h->stream));
+            BM_HIP(hipMemcpyAsync(&h->ctl_host[0], h->ctl.p, sizeof(MfCtl), hipMemcpyDeviceToHost, h->stream));
             BM_HIP(hipStreamSynchronize(h->stream));
             host = h->ctl_host[0];
         }
@@ -516,7 +518,7 @@ static int mean_field(bm_dbm *h, const float *X_dev, int *out_n, MfMid *mid = nu
         if (step & 1) { cur = h->mu_alt; alt = h->mu; }
     }
     if (cur != h->mu)                  // `self._mu[i].assign(mu[i])` (:477): keep the handle's mu as the result
-        for (int i = 0; i < L; ++i) { Mat t = h->mu[i]; h->mu[i] = h->mu_alt[i]; h->mu_alt[i] = t; }
+        for (int i = 0; i < L; ++i) std::swap(h->mu[i], h->mu_alt[i]);
     if (out_n) *out_n = step;
     return 0;
 }
@@ -534,14 +536,14 @@ static bool fast_pcd_ok(const bm_dbm *h, bool sample) {
 }
 static int fast_pcd_begin(bm_dbm *h) {
     const bool vbits = h->cfg.v_unit == BM_UNIT_BERNOULLI && h->cfg.sample_v_states;
-    if (!h->pH_key[0][0]) {                       // one shadow per physical particle buffer
-        Mat *vb[2] = {&h->v, &h->v_new};
+    if (!h->pH_key[0][0]) {                       // one shadow per physical particle buffer (keyed once all exist)
         for (int b = 0; b < 2; ++b) {
-            if (vbits) { BM_TRY(h->pv16[b].alloc(1, h->M, h->V)); h->pv_key[b] = vb[b]->p; }
-            for (int i = 0; i < h->L; ++i) {
-                Mat *hb = b ? &h->H_new[i] : &h->H[i];
-                BM_TRY(h->pH16[i][b].alloc(1, h->M, h->n[i + 1])); h->pH_key[i][b] = hb->p;
-            }
+            if (vbits) BM_TRY(h->pv16[b].alloc(1, h->M, h->V));
+            for (int i = 0; i < h->L; ++i) BM_TRY(h->pH16[i][b].alloc(1, h->M, h->n[i + 1]));
+        }
+        for (int b = 0; b < 2; ++b) {
+            if (vbits) h->pv_key[b] = (b ? h->v_new : h->v).p;
+            for (int i = 0; i < h->L; ++i) h->pH_key[i][b] = (b ? h->H_new[i] : h->H[i]).p;
         }
     }
     for (int b = 0; b < 2; ++b) { h->pv_ok[b] = false; for (int i = 0; i < h->L; ++i) h->pH_ok[i][b] = false; }
@@ -559,8 +561,8 @@ static void particles_update(bm_dbm *h, int k, bool sample, bool update_only_v_a
         // (fast-binary: sweep 0 reads the particles it starts from in fp32 and leaves shadows of what it samples; from
         // then on every sampled Bernoulli input is a bitmap with a valid shadow)
         gibbs_sweep(h, h->M, LayerIn{h->v.p, h->v.ld}, h->H, &h->v_new, h->H_new, true, sample, t, h->prow0);
-        Mat tv = h->v; h->v = h->v_new; h->v_new = tv;                    // swap particles (:493)
-        for (int i = 0; i < h->L; ++i) { Mat th = h->H[i]; h->H[i] = h->H_new[i]; h->H_new[i] = th; }
+        std::swap(h->v, h->v_new);                                        // swap particles (:493)
+        for (int i = 0; i < h->L; ++i) std::swap(h->H[i], h->H_new[i]);
     }
 }
 
@@ -767,15 +769,6 @@ static double ais_log_Z0(const bm_dbm *h, bool literal) {
     return literal ? (double)((float)units * logf(2.0f)) : (double)units * (double)logf(2.0f);
 }
 
-static void release_ais(bm_dbm *h) {
-    for (int e = 0; e < 3; ++e) { h->ae[e].release(); h->apart_e[e].release(); }
-    for (int o = 0; o < 2; ++o) for (int b = 0; b < 2; ++b) { h->ao[o][b].release(); h->apart_o[o][b].release(); }
-    h->rowtmp.release();
-    if (h->alogw) { (void)hipFree(h->alogw); h->alogw = nullptr; }
-    h->ax16.release(); h->ax2_16.release(); h->av16.release(); h->ah2_16.release();     // (re)allocated by the fast path
-    h->ais_rows = 0;
-}
-
 extern "C" {
 
 int bm_dbm_create(const bm_dbm_config *cfg, bm_dbm **out) {
@@ -783,7 +776,7 @@ int bm_dbm_create(const bm_dbm_config *cfg, bm_dbm **out) {
     BM_CHECK(cfg->n_layers >= 1 && cfg->n_layers <= MAXL, "n_layers %d outside [1, %d]", cfg->n_layers, MAXL);
     BM_CHECK(cfg->n_visible >= 1 && cfg->n_particles >= 1 && cfg->batch_size >= 1, "bad sizes");
     BM_CHECK(bm_device_count() > 0, "no HIP device visible: libbm355 has no CPU fallback");
-    bm_dbm *h = new bm_dbm();
+    auto h = std::make_unique<bm_dbm>();
     h->cfg = *cfg;
     h->L = cfg->n_layers; h->V = cfg->n_visible; h->N = cfg->batch_size; h->M = cfg->n_particles;
     h->n[0] = h->V;
@@ -798,8 +791,7 @@ int bm_dbm_create(const bm_dbm_config *cfg, bm_dbm **out) {
         }
         h->n[i + 1] = cfg->n_hiddens[i];
     }
-    BM_HIP(hipStreamCreate(&h->stream));
-    BM_HIP(hipStreamCreate(&h->stream2));
+    BM_TRY(create(h->stream)); BM_TRY(create(h->stream2));
     {
         bool small = h->L >= 2 && h->N <= 1024 && h->M <= 1024 && cfg->max_mf_updates >= 2;
         for (int i = 0; i < h->L; ++i) small = small && (long long)h->n[i] * h->n[i + 1] <= (2ll << 20);
@@ -807,12 +799,10 @@ int bm_dbm_create(const bm_dbm_config *cfg, bm_dbm **out) {
         if (bm::dbg("dbm_pcd_geo")) h->pcd_geo = atoi(bm::dbg("dbm_pcd_geo"));
     }
     h->cur = h->stream;
-    BM_HIP(hipEventCreate(&h->ev0));
-    BM_HIP(hipEventCreate(&h->ev1));
-    BM_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    BM_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    BM_HIP(hipHostMalloc((void **)&h->ctl_host, bm_dbm::MF_RING * sizeof(MfCtl)));
-    for (int i = 0; i < bm_dbm::MF_RING; ++i) BM_HIP(hipEventCreateWithFlags(&h->ctl_ev[i], hipEventDisableTiming));
+    BM_TRY(create(h->ev0)); BM_TRY(create(h->ev1));
+    BM_TRY(create(h->ev_fork, hipEventDisableTiming)); BM_TRY(create(h->ev_join, hipEventDisableTiming));
+    BM_TRY(create(h->ctl_host, bm_dbm::MF_RING));
+    for (int i = 0; i < bm_dbm::MF_RING; ++i) BM_TRY(create(h->ctl_ev[i], hipEventDisableTiming));
     size_t nsums = 2 * (size_t)h->V;
     for (int i = 0; i < h->L; ++i) {
         const int a = h->n[i], b = h->n[i + 1];
@@ -839,50 +829,22 @@ int bm_dbm_create(const bm_dbm_config *cfg, bm_dbm **out) {
         h->sums_p = h->grad.p + off;
     }
     BM_TRY(h->mfblk.alloc(2 * (size_t)BM_DBM_MAX_LAYERS * BM_MF_SLOTS));
-    BM_HIP(hipMalloc((void **)&h->ctl, sizeof(MfCtl)));
-    BM_HIP(hipMemset(h->ctl, 0, sizeof(MfCtl)));
-    h->flag = &h->ctl->maxdiff;
+    BM_TRY(h->ctl.alloc(1));
+    h->flag = &h->ctl.p->maxdiff;
     BM_TRY(h->xw0.alloc(h->N, h->n[1]));
-    BM_HIP(hipMalloc((void **)&h->scal, 4 * sizeof(double)));
+    BM_TRY(h->scal.alloc(4));
     {
         std::vector<float> ones(h->V, 1.0f);
         BM_HIP(hipMemcpy(h->sigma.p, ones.data(), h->V * sizeof(float), hipMemcpyHostToDevice));
     }
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
 int bm_dbm_destroy(bm_dbm *h) {
     if (!h) return 0;
-    (void)hipStreamSynchronize(h->stream);
+    for (hipStream_t st : {h->stream.h, h->stream2.h}) if (st) (void)hipStreamSynchronize(st);
     if (h->xchg_used) xchg_bind_user(h->xchg_used, nullptr);
-    for (int i = 0; i < h->L; ++i) {
-        Mat *ms[] = {&h->W[i], &h->Wt[i], &h->dW[i], &h->mu[i], &h->mu_alt[i], &h->mu_new[i], &h->H[i], &h->H_new[i]};
-        for (Mat *m : ms) m->release();
-        DevBuf *bs[] = {&h->hb[i], &h->dhb[i], &h->q[i], &h->mm[i], &h->pen[i], &h->wnorm[i], &h->mn_fac[i]};
-        for (DevBuf *b : bs) b->release();
-        h->logits[i].release();
-        h->W3[i].release(); h->W3t[i].release();
-    }
-    h->ax16.release(); h->ax2_16.release(); h->av16.release(); h->ah2_16.release();
-    for (int b = 0; b < 2; ++b) { h->pv16[b].release(); for (int i = 0; i < MAXL; ++i) h->pH16[i][b].release(); }
-    Mat *ms[] = {&h->v, &h->v_new, &h->recon};
-    for (Mat *m : ms) m->release();
-    DevBuf *bs[] = {&h->vb, &h->dvb, &h->sigma, &h->grad, &h->ais_send, &h->ais_recv};
-    for (DevBuf *b : bs) b->release();
-    release_ais(h);
-    if (h->ctl) (void)hipFree(h->ctl);
-    if (h->ctl_host) (void)hipHostFree(h->ctl_host);
-    for (int i = 0; i < bm_dbm::MF_RING; ++i) if (h->ctl_ev[i]) (void)hipEventDestroy(h->ctl_ev[i]);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->stream2) (void)hipStreamDestroy(h->stream2);
-    h->mfblk.release();
-    h->xw0.release();
-    if (h->scal) (void)hipFree(h->scal);
-    (void)hipEventDestroy(h->ev0);
-    (void)hipEventDestroy(h->ev1);
-    (void)hipStreamDestroy(h->stream);
     delete h;
     return 0;
 }
@@ -1002,11 +964,11 @@ int bm_dbm_train_step(bm_dbm *h, const float *X_dev, float lr, float mom, int32_
 // msre of sigma(mu0 W0^T + vb) against X (dbm.py:625-630), mu from the last mean_field()
 static int recon_msre(bm_dbm *h, const float *X_dev, float *out_msre) {
     reconstruct_from_mu(h, h->recon.p, h->recon.ld);
-    BM_HIP(hipMemsetAsync(h->scal, 0, sizeof(double), h->stream));
+    BM_HIP(hipMemsetAsync(h->scal.p, 0, sizeof(double), h->stream));
     hipLaunchKernelGGL(sqdiff_kernel, dim3(128), dim3(256), 0, h->stream, X_dev, h->V, (const float *)h->recon.p,
-                       h->recon.ld, h->N, h->V, h->scal);
+                       h->recon.ld, h->N, h->V, h->scal.p);
     double s = 0.0;
-    BM_HIP(hipMemcpyAsync(&s, h->scal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipMemcpyAsync(&s, h->scal.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     *out_msre = (float)(s / ((double)h->N * h->V));
     return 0;
@@ -1146,12 +1108,13 @@ int bm_dbm_sample_v(bm_dbm *h, int32_t k, float *V_dev) {
     particles_update(h, k, true);                             // :643-644
     // `_make_particles_update(sample=False)` whose v assign is the only one fetched (:646-647):
     // k mean sweeps from the sampled state; only v takes the result, H / *_new keep theirs.
-    // scratch: reuse mu_alt-sized buffers is not possible (M != N): allocate temporaries
-    Mat tv, tv2; std::vector<Mat> tH(h->L), tH2(h->L);
-    BM_TRY(tv.alloc(h->M, h->V)); BM_TRY(tv2.alloc(h->M, h->V));
-    for (int i = 0; i < h->L; ++i) { BM_TRY(tH[i].alloc(h->M, h->n[i + 1])); BM_TRY(tH2[i].alloc(h->M, h->n[i + 1])); }
+    // scratch: the mu buffers do not fit (M != N); the handle's own, allocated at the first call (sv_v[1] last)
+    if (!h->sv_v[1].p) {
+        for (int b = 0; b < 2; ++b) for (int i = 0; i < h->L; ++i) BM_TRY(h->sv_H[b][i].alloc(h->M, h->n[i + 1]));
+        BM_TRY(h->sv_v[0].alloc(h->M, h->V)); BM_TRY(h->sv_v[1].alloc(h->M, h->V));
+    }
     const Mat *Hin = h->H; LayerIn vin{h->v.p, h->v.ld};
-    Mat *Hout = tH.data(), *Hout2 = tH2.data(); Mat *vout = &tv, *vout2 = &tv2;
+    Mat *Hout = h->sv_H[0], *Hout2 = h->sv_H[1]; Mat *vout = &h->sv_v[0], *vout2 = &h->sv_v[1];
     for (int t = 0; t < k; ++t) {
         gibbs_sweep(h, h->M, vin, Hin, vout, Hout, true, false, k + t, h->prow0);
         vin = LayerIn{vout->p, vout->ld}; Hin = Hout;
@@ -1167,8 +1130,6 @@ int bm_dbm_sample_v(bm_dbm *h, int32_t k, float *V_dev) {
         hipLaunchKernelGGL(copy2d_kernel, dim3(256), dim3(256), 0, h->stream, (const float *)h->v.p, h->v.ld, V_dev, h->V,
                            h->M, h->V);
     BM_HIP(hipStreamSynchronize(h->stream));
-    tv.release(); tv2.release();
-    for (int i = 0; i < h->L; ++i) { tH[i].release(); tH2[i].release(); }
     h->call++;
     return 0;
 }
@@ -1177,7 +1138,7 @@ static inline int nslots(int n) { return (n + 15) / 16; }
 
 static int ensure_ais(bm_dbm *h, int rows) {
     if (rows <= h->ais_rows) return 0;
-    release_ais(h);
+    h->ais_rows = 0;                               // (set again once every buffer exists: a failure leaves none counted)
     const AisLayers s = ais_layers(h);
     int nmax = 1;
     for (int l = 0; l <= h->L; ++l) nmax = h->n[l] > nmax ? h->n[l] : nmax;
@@ -1193,7 +1154,7 @@ static int ensure_ais(bm_dbm *h, int rows) {
             BM_TRY(h->apart_o[o][b].alloc(part));
         }
     BM_TRY(h->rowtmp.alloc(rows));
-    BM_HIP(hipMalloc((void **)&h->alogw, (size_t)rows * sizeof(double)));
+    BM_TRY(h->alogw.alloc(rows));
     h->ais_rows = rows;
     return 0;
 }
@@ -1303,7 +1264,7 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
         rdot_cur[o] = h->apart_o[o][0].p; rdot_next[o] = h->apart_o[o][1].p;
         nd_cur[o] = 1;
     }
-    BM_HIP(hipMemsetAsync(h->alogw, 0, (size_t)R * sizeof(double), h->stream));
+    BM_HIP(hipMemsetAsync(h->alogw.p, 0, (size_t)R * sizeof(double), h->stream));
     for (int o = 0; o < S.no; ++o)                                        // odd-depth layer o: site SITE_AIS_X0 + 16 o
         hipLaunchKernelGGL(ais_init_kernel, dim3(512), dim3(256), 0, h->stream, x[o]->p, x[o]->ld, R, h->n[S.od[o] + 1],
                            dkey(h, SITE_AIS_X0, o, seed, 0), (unsigned long long)chain0);
@@ -1313,7 +1274,7 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
     if (h->fast && h->L == 2 && h->cfg.sample_v_states && h->cfg.sample_h_states[0] && h->cfg.sample_h_states[1]) {
         const int H2 = h->n[2];
         BM_TRY(fast_build_planes(h));
-        if (h->ax16.rows != h->ais_rows) {
+        if (h->ah2_16.rows != h->ais_rows) {      // (ah2_16 is allocated last)
             BM_TRY(h->ax16.alloc(1, h->ais_rows, H1)); BM_TRY(h->ax2_16.alloc(1, h->ais_rows, H1));
             BM_TRY(h->av16.alloc(1, h->ais_rows, V)); BM_TRY(h->ah2_16.alloc(1, h->ais_rows, H2));
         }
@@ -1358,7 +1319,7 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
             layer_update(h, li, R, below_of(li), above_of(li), bscore, bscore, 0, nullptr, nullptr, h->ae[e].ld,
                          dkey(h, site_of(li), 0, seed, 0), chain0, nullptr, nullptr, &a);
         }
-        hipLaunchKernelGGL(ais_score_literal_kernel, dim3((R + 255) / 256), dim3(256), 0, h->stream, h->alogw, R, ldp,
+        hipLaunchKernelGGL(ais_score_literal_kernel, dim3((R + 255) / 256), dim3(256), 0, h->stream, h->alogw.p, R, ldp,
                            score_args(), bscore, sign);
         return 0;
     };
@@ -1384,7 +1345,7 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
                              dkey(h, site_of(li), t, seed, step), chain0, nullptr, nullptr, &a);
             }
             if (sc)     // the softplus terms + (bb - ba) * x.hb, slots in fixed order, into the double log-weights
-                hipLaunchKernelGGL(ais_score_kernel, dim3((R + 31) / 32), dim3(256), 0, h->stream, h->alogw, R, ldp,
+                hipLaunchKernelGGL(ais_score_kernel, dim3((R + 31) / 32), dim3(256), 0, h->stream, h->alogw.p, R, ldp,
                                    score_args(), bb - ba);
             if (!transit) break;
             // odd-depth layers given the new even-depth ones: x^ <- sigma(beta*(v W0 + h2 W1^T) + beta*hb0), ...; also
@@ -1428,7 +1389,7 @@ int bm_dbm_ais(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint64_t s
     BM_TRY(ais_core(h, n_betas, n_runs, k, seed, chain0));
     const int R = n_runs;
     std::vector<double> w(R);
-    BM_HIP(hipMemcpyAsync(w.data(), h->alogw, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipMemcpyAsync(w.data(), h->alogw.p, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     const double logZ0 = ais_log_Z0(h, h->ais_literal != 0);
     if (h->ais_literal) {                        // log_Z += log_Z0 in float32 (:731-734)
@@ -1464,8 +1425,8 @@ int bm_dbm_ais_sharded(bm_dbm *h, bm_comm *c, int32_t n_betas, int32_t n_runs_to
     shard(rank, a, b);
     const int n = b - a, npad = (n_runs_total + world - 1) / world;
     // send / receive buffers live in the handle (grown on demand, never on the steady path)
-    if (h->ais_send.n < (size_t)npad) { h->ais_send.release(); BM_TRY(h->ais_send.alloc((size_t)npad)); }
-    if (h->ais_recv.n < (size_t)npad * world) { h->ais_recv.release(); BM_TRY(h->ais_recv.alloc((size_t)npad * world)); }
+    if (h->ais_send.n < (size_t)npad) BM_TRY(h->ais_send.alloc((size_t)npad));
+    if (h->ais_recv.n < (size_t)npad * world) BM_TRY(h->ais_recv.alloc((size_t)npad * world));
     float *send = h->ais_send.p, *recv = h->ais_recv.p;
     // A rank whose sweep fails must still enter the collective - the other ranks would block in it forever - so the
     // failure is made collective: the failing rank contributes NaNs and every rank reports the error.
@@ -1480,7 +1441,7 @@ int bm_dbm_ais_sharded(bm_dbm *h, bm_comm *c, int32_t n_betas, int32_t n_runs_to
         (void)hipStreamSynchronize(h->stream);
     } else {
         const double z0 = ais_log_Z0(h, h->ais_literal != 0);
-        hipLaunchKernelGGL(ais_finish_kernel, dim3((npad + 255) / 256), dim3(256), 0, h->stream, (const double *)h->alogw, send,
+        hipLaunchKernelGGL(ais_finish_kernel, dim3((npad + 255) / 256), dim3(256), 0, h->stream, (const double *)h->alogw.p, send,
                            n, npad, z0, h->ais_literal);
     }
     const int rc_c = bm_comm_allgather(c, send, recv, (size_t)npad, (void *)h->stream);

@@ -13,6 +13,7 @@
 #include "bm_rng.h"
 
 #include <math.h>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -253,13 +254,14 @@ struct bm_dbm64 {
     bm_dbm_config cfg;
     double mf_tol, l2, max_norm, damping, sp_target[MAXL64], sp_cost[MAXL64];
     int L, V, N, M, n[MAXL64 + 1];
-    hipStream_t stream = nullptr;
-    bm64::DBuf W[MAXL64], Wt[MAXL64], dW[MAXL64], hb[MAXL64], dhb[MAXL64], q[MAXL64], mm[MAXL64], pen[MAXL64], wnorm[MAXL64];
-    bm64::DBuf vb, dvb, sigma;
-    bm64::DBuf mu[MAXL64], mu_alt[MAXL64], mu_new[MAXL64], H[MAXL64], H_new[MAXL64], v, v_new, recon;
-    bm64::DBuf pos[MAXL64], neg[MAXL64], sums;            // raw outer products; column sums [2V + 2 sum n_i]
-    bm64::DBuf ax, ax2, av, ah2, alogw; int ais_rows = 0;
-    unsigned long long *flag = nullptr; double *scal = nullptr;
+    Stream stream;
+    DevArray<double> W[MAXL64], Wt[MAXL64], dW[MAXL64], hb[MAXL64], dhb[MAXL64], q[MAXL64], mm[MAXL64], pen[MAXL64], wnorm[MAXL64];
+    DevArray<double> vb, dvb, sigma;
+    DevArray<double> mu[MAXL64], mu_alt[MAXL64], mu_new[MAXL64], H[MAXL64], H_new[MAXL64], v, v_new, recon;
+    DevArray<double> pos[MAXL64], neg[MAXL64], sums;            // raw outer products; column sums [2V + 2 sum n_i]
+    DevArray<double> ax, ax2, av, ah2, alogw; int ais_rows = 0;
+    DevArray<double> sv_v[2], sv_H[2][MAXL64];                  // bm_dbm64_sample_v: ping-pong copies of the particles
+    DevArray<unsigned long long> flag; DevArray<double> scal;
     uint64_t seed = 0; uint32_t call = 0; int64_t prow0 = 0;
     bool wt_valid = false;
 };
@@ -307,7 +309,7 @@ static void layer_update(bm_dbm64 *h, int layer, int J, const double *below, con
 }
 
 // `_make_gibbs_step` (dbm.py:385-427): NEW below / OLD above
-static void gibbs_sweep(bm_dbm64 *h, int J, const double *vin, DBuf *Hin, double *vout, DBuf *Hout, bool update_v, bool sample,
+static void gibbs_sweep(bm_dbm64 *h, int J, const double *vin, DevArray<double> *Hin, double *vout, DevArray<double> *Hout, bool update_v, bool sample,
                         int t, int64_t row0, unsigned long long *maxdiff = nullptr) {
     for (int i = 0; i < h->L; ++i) {
         const double *below = (i == 0) ? vin : Hout[i - 1].p;
@@ -325,7 +327,7 @@ static void gibbs_sweep(bm_dbm64 *h, int J, const double *vin, DBuf *Hin, double
 
 static int read_flag(bm_dbm64 *h, double *out) {
     unsigned long long bits = 0;
-    BM_HIP(hipMemcpyAsync(&bits, h->flag, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipMemcpyAsync(&bits, h->flag.p, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     memcpy(out, &bits, sizeof(double));
     return 0;
@@ -340,23 +342,23 @@ static int mean_field(bm_dbm64 *h, const double *X_dev, int *out_n) {
         const double mult = (i == 0 || i < L - 1) ? 2.0 : 1.0;
         layer_update(h, i, N, below, nullptr, mult, 1.0, 0, h->mu_new[i].p, nullptr, dkey64(0, 0, h->seed, h->call), 0);
     }
-    BM_HIP(hipMemsetAsync(h->flag, 0, sizeof(unsigned long long), h->stream));
+    BM_HIP(hipMemsetAsync(h->flag.p, 0, sizeof(unsigned long long), h->stream));
     for (int i = 0; i < L; ++i) {
         const size_t n = (size_t)N * h->n[i + 1];
-        hipLaunchKernelGGL(dmaxabsdiff_kernel, dim3(64), dim3(256), 0, h->stream, (const double *)h->mu[i].p, (const double *)h->mu_new[i].p, n, h->flag);
+        hipLaunchKernelGGL(dmaxabsdiff_kernel, dim3(64), dim3(256), 0, h->stream, (const double *)h->mu[i].p, (const double *)h->mu_new[i].p, n, h->flag.p);
     }
     double diff = 0.0;
     BM_TRY(read_flag(h, &diff));
-    DBuf *cur = h->mu, *alt = h->mu_alt;
+    DevArray<double> *cur = h->mu, *alt = h->mu_alt;
     int step = 0;
     while (step < h->cfg.max_mf_updates && diff > h->mf_tol) {
-        BM_HIP(hipMemsetAsync(h->flag, 0, sizeof(unsigned long long), h->stream));
-        gibbs_sweep(h, N, X_dev, cur, nullptr, alt, false, false, 0, 0, h->flag);
+        BM_HIP(hipMemsetAsync(h->flag.p, 0, sizeof(unsigned long long), h->stream));
+        gibbs_sweep(h, N, X_dev, cur, nullptr, alt, false, false, 0, 0, h->flag.p);
         BM_TRY(read_flag(h, &diff));
-        DBuf *t = cur; cur = alt; alt = t;
+        DevArray<double> *t = cur; cur = alt; alt = t;
         ++step;
     }
-    if (cur != h->mu) for (int i = 0; i < L; ++i) { DBuf t = h->mu[i]; h->mu[i] = h->mu_alt[i]; h->mu_alt[i] = t; }
+    if (cur != h->mu) for (int i = 0; i < L; ++i) std::swap(h->mu[i], h->mu_alt[i]);
     BM_HIP(hipGetLastError());
     if (out_n) *out_n = step;
     return 0;
@@ -366,8 +368,8 @@ static void particles_update(bm_dbm64 *h, int k, bool sample, int t0 = 0) {
     ensure_wt(h);
     for (int t = 0; t < k; ++t) {
         gibbs_sweep(h, h->M, h->v.p, h->H, h->v_new.p, h->H_new, true, sample, t0 + t, h->prow0);
-        DBuf tv = h->v; h->v = h->v_new; h->v_new = tv;
-        for (int i = 0; i < h->L; ++i) { DBuf th = h->H[i]; h->H[i] = h->H_new[i]; h->H_new[i] = th; }
+        std::swap(h->v, h->v_new);
+        for (int i = 0; i < h->L; ++i) std::swap(h->H[i], h->H_new[i]);
     }
 }
 
@@ -417,19 +419,19 @@ static int apply_update(bm_dbm64 *h, const double *X_dev, double lr, double mom)
 static int msre_of_mu(bm_dbm64 *h, const double *X_dev, double *out) {
     reconstruct_from_mu(h, h->recon.p);
     const size_t n = (size_t)h->N * h->V;
-    hipLaunchKernelGGL(sqdiff_kernel, dim3(64), dim3(256), 0, h->stream, X_dev, (const double *)h->recon.p, n, h->scal + 8);
+    hipLaunchKernelGGL(sqdiff_kernel, dim3(64), dim3(256), 0, h->stream, X_dev, (const double *)h->recon.p, n, h->scal.p + 8);
     ReduceJobs jb;
     memset(&jb, 0, sizeof(jb));
     jb.off[0] = 8; jb.cnt[0] = 64;
-    hipLaunchKernelGGL(reduce_fixed_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)h->scal, jb, h->scal);
+    hipLaunchKernelGGL(reduce_fixed_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)h->scal.p, jb, h->scal.p);
     double se = 0.0;
-    BM_HIP(hipMemcpyAsync(&se, h->scal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipMemcpyAsync(&se, h->scal.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     *out = se / ((double)h->N * h->V);
     return 0;
 }
 
-static DBuf *find(bm_dbm64 *h, const std::string &name, size_t *n) {
+static DevArray<double> *find(bm_dbm64 *h, const std::string &name, size_t *n) {
     std::string base = name; int idx = 0;
     const size_t us = name.rfind('_');
     if (us != std::string::npos && us + 1 < name.size() && isdigit((unsigned char)name[us + 1]) && name.find_first_not_of("0123456789", us + 1) == std::string::npos) {
@@ -471,11 +473,15 @@ int bm_dbm64_create(const bm_dbm_config *cfg, const double *hyper12, bm_dbm64 **
     for (int i = 0; i < cfg->n_layers; ++i)
         BM_CHECK(cfg->h_unit[i] == BM_UNIT_BERNOULLI, "float64 DBM: Bernoulli hidden layers only (Multinomial layers: the float32 path)");
     BM_CHECK(cfg->n_visible >= 1 && cfg->batch_size >= 1 && cfg->n_particles >= 1, "bad sizes");
-    bm_dbm64 *h = new bm_dbm64();
+    auto h = std::make_unique<bm_dbm64>();
     h->cfg = *cfg;
     h->L = cfg->n_layers; h->V = cfg->n_visible; h->N = cfg->batch_size; h->M = cfg->n_particles;
     h->n[0] = h->V;
-    for (int i = 0; i < h->L; ++i) { BM_CHECK(cfg->n_hiddens[i] >= 1, "bad layer size"); h->n[i + 1] = cfg->n_hiddens[i]; }
+    for (int i = 0; i < h->L; ++i) {
+        BM_CHECK(cfg->n_hiddens[i] >= 1, "bad layer size");
+        BM_CHECK(cfg->n_hiddens[i] > i, "layer %d needs more than %d units (sparsity index, dbm.py:583)", i, i);
+        h->n[i + 1] = cfg->n_hiddens[i];
+    }
     h->mf_tol = hyper12 ? hyper12[0] : (double)cfg->mf_tol;
     h->l2 = hyper12 ? hyper12[1] : (double)cfg->l2;
     h->max_norm = hyper12 ? hyper12[2] : (double)cfg->max_norm;
@@ -484,15 +490,15 @@ int bm_dbm64_create(const bm_dbm_config *cfg, const double *hyper12, bm_dbm64 **
         h->sp_target[i] = hyper12 ? hyper12[4 + i] : (double)cfg->sparsity_target[i];
         h->sp_cost[i] = hyper12 ? hyper12[8 + i] : (double)cfg->sparsity_cost[i];
     }
-    BM_HIP(hipStreamCreate(&h->stream));
+    BM_TRY(create(h->stream));
     size_t nsum = 2 * (size_t)h->V;
     for (int i = 0; i < h->L; ++i) {
         const size_t a = h->n[i], b = h->n[i + 1];
         BM_TRY(h->W[i].alloc(a * b)); BM_TRY(h->Wt[i].alloc(a * b)); BM_TRY(h->dW[i].alloc(a * b));
         BM_TRY(h->pos[i].alloc(a * b)); BM_TRY(h->neg[i].alloc(a * b));
-        for (bm64::DBuf *v : {&h->hb[i], &h->dhb[i], &h->q[i], &h->mm[i], &h->pen[i], &h->wnorm[i]}) BM_TRY(v->alloc(b));
-        for (bm64::DBuf *v : {&h->mu[i], &h->mu_alt[i], &h->mu_new[i]}) BM_TRY(v->alloc((size_t)h->N * b));
-        for (bm64::DBuf *v : {&h->H[i], &h->H_new[i]}) BM_TRY(v->alloc((size_t)h->M * b));
+        for (DevArray<double> *v : {&h->hb[i], &h->dhb[i], &h->q[i], &h->mm[i], &h->pen[i], &h->wnorm[i]}) BM_TRY(v->alloc(b));
+        for (DevArray<double> *v : {&h->mu[i], &h->mu_alt[i], &h->mu_new[i]}) BM_TRY(v->alloc((size_t)h->N * b));
+        for (DevArray<double> *v : {&h->H[i], &h->H_new[i]}) BM_TRY(v->alloc((size_t)h->M * b));
         nsum += 2 * b;
     }
     BM_TRY(h->vb.alloc(h->V)); BM_TRY(h->dvb.alloc(h->V)); BM_TRY(h->sigma.alloc(h->V));
@@ -502,22 +508,13 @@ int bm_dbm64_create(const bm_dbm_config *cfg, const double *hyper12, bm_dbm64 **
         std::vector<double> one((size_t)h->V, 1.0);
         BM_HIP(hipMemcpy(h->sigma.p, one.data(), one.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    BM_HIP(hipMalloc((void **)&h->flag, 64));
-    BM_HIP(hipMalloc((void **)&h->scal, 128 * sizeof(double)));
-    BM_HIP(hipMemset(h->scal, 0, 128 * sizeof(double)));
-    *out = h;
+    BM_TRY(h->flag.alloc(8)); BM_TRY(h->scal.alloc(128));
+    *out = h.release();
     return 0;
 }
 int bm_dbm64_destroy(bm_dbm64 *h) {
     if (!h) return 0;
-    (void)hipStreamSynchronize(h->stream);
-    if (h->flag) (void)hipFree(h->flag);
-    if (h->scal) (void)hipFree(h->scal);
-    (void)hipStreamDestroy(h->stream);
-    for (int i = 0; i < MAXL64; ++i)
-        for (bm64::DBuf *b : {&h->W[i], &h->Wt[i], &h->dW[i], &h->hb[i], &h->dhb[i], &h->q[i], &h->mm[i], &h->pen[i], &h->wnorm[i],
-                              &h->mu[i], &h->mu_alt[i], &h->mu_new[i], &h->H[i], &h->H_new[i], &h->pos[i], &h->neg[i]}) b->release();
-    for (bm64::DBuf *b : {&h->vb, &h->dvb, &h->sigma, &h->v, &h->v_new, &h->recon, &h->sums, &h->ax, &h->ax2, &h->av, &h->ah2, &h->alogw}) b->release();
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
     delete h;
     return 0;
 }
@@ -528,7 +525,7 @@ int bm_dbm64_set_row_offset(bm_dbm64 *h, int64_t row0, int64_t particle0) { BM_C
 int bm_dbm64_set_param(bm_dbm64 *h, const char *name, const double *host, size_t n) {
     BM_CHECK(h && name && host, "null argument");
     size_t want = 0;
-    bm64::DBuf *b = bm64::find(h, name, &want);
+    DevArray<double> *b = bm64::find(h, name, &want);
     BM_CHECK(b, "unknown variable '%s'", name);
     BM_CHECK(n == want, "variable '%s' has %zu elements, %zu given", name, want, n);
     BM_HIP(hipStreamSynchronize(h->stream));
@@ -539,7 +536,7 @@ int bm_dbm64_set_param(bm_dbm64 *h, const char *name, const double *host, size_t
 int bm_dbm64_get_param(bm_dbm64 *h, const char *name, double *host, size_t n) {
     BM_CHECK(h && name && host, "null argument");
     size_t want = 0;
-    bm64::DBuf *b = bm64::find(h, name, &want);
+    DevArray<double> *b = bm64::find(h, name, &want);
     BM_CHECK(b, "unknown variable '%s'", name);
     BM_CHECK(n == want, "variable '%s' has %zu elements, %zu given", name, want, n);
     BM_HIP(hipStreamSynchronize(h->stream));
@@ -594,27 +591,25 @@ int bm_dbm64_sample_v(bm_dbm64 *h, int32_t k, double *V_dev) {
     BM_CHECK(h && k >= 0, "bad argument");
     bm64::particles_update(h, k, true);
     if (k > 0) {
-        // the mean sweeps run on COPIES of the hidden particles; only v is assigned
-        bm64::DBuf Hc[MAXL64], Hn[MAXL64], vc, vn;
-        for (int i = 0; i < h->L; ++i) {
-            const size_t n = (size_t)h->M * h->n[i + 1];
-            BM_TRY(Hc[i].alloc(n)); BM_TRY(Hn[i].alloc(n));
-            BM_HIP(hipMemcpyAsync(Hc[i].p, h->H[i].p, n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        }
+        // the mean sweeps run on COPIES of the hidden particles (the handle's scratch, allocated at the first call,
+        // sv_v[1] last); only v is assigned
         const size_t nv = (size_t)h->M * h->V;
-        BM_TRY(vc.alloc(nv)); BM_TRY(vn.alloc(nv));
-        BM_HIP(hipMemcpyAsync(vc.p, h->v.p, nv * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        bm64::DBuf *Hin = Hc, *Hout = Hn;
-        double *vin = vc.p, *vout = vn.p;
+        if (!h->sv_v[1].p) {
+            for (int b = 0; b < 2; ++b) for (int i = 0; i < h->L; ++i) BM_TRY(h->sv_H[b][i].alloc((size_t)h->M * h->n[i + 1]));
+            BM_TRY(h->sv_v[0].alloc(nv)); BM_TRY(h->sv_v[1].alloc(nv));
+        }
+        for (int i = 0; i < h->L; ++i)
+            BM_HIP(hipMemcpyAsync(h->sv_H[0][i].p, h->H[i].p, h->sv_H[0][i].n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        BM_HIP(hipMemcpyAsync(h->sv_v[0].p, h->v.p, nv * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        DevArray<double> *Hin = h->sv_H[0], *Hout = h->sv_H[1];
+        double *vin = h->sv_v[0].p, *vout = h->sv_v[1].p;
         for (int t = 0; t < k; ++t) {
             bm64::gibbs_sweep(h, h->M, vin, Hin, vout, Hout, true, false, k + t, h->prow0);
             double *tv = vin; vin = vout; vout = tv;
-            bm64::DBuf *th = Hin; Hin = Hout; Hout = th;
+            DevArray<double> *th = Hin; Hin = Hout; Hout = th;
         }
         BM_HIP(hipMemcpyAsync(h->v.p, vin, nv * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        BM_HIP(hipStreamSynchronize(h->stream));        // the temporaries die here
-        for (int i = 0; i < h->L; ++i) { Hc[i].release(); Hn[i].release(); }
-        vc.release(); vn.release();
+        BM_HIP(hipStreamSynchronize(h->stream));
     }
     if (V_dev) BM_HIP(hipMemcpyAsync(V_dev, h->v.p, (size_t)h->M * h->V * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     BM_HIP(hipGetLastError());
@@ -630,17 +625,19 @@ int bm_dbm64_ais(bm_dbm64 *h, int32_t n_betas, int32_t R, int32_t k, uint64_t se
     BM_CHECK(n_betas >= 1 && R >= 1 && k >= 1, "bad AIS arguments");
     const int V = h->V, H1 = h->n[1], H2 = h->n[2];
     if (h->ais_rows < R) {
-        for (bm64::DBuf *b : {&h->ax, &h->ax2, &h->av, &h->ah2, &h->alogw}) b->release();
+        h->ais_rows = 0;                                  // (set again once every buffer exists)
         BM_TRY(h->ax.alloc((size_t)R * H1)); BM_TRY(h->ax2.alloc((size_t)R * H1)); BM_TRY(h->av.alloc((size_t)R * V));
         BM_TRY(h->ah2.alloc((size_t)R * H2)); BM_TRY(h->alogw.alloc((size_t)R));
         h->ais_rows = R;
     }
     bm64::ensure_wt(h);
-    const uint64_t seed0 = h->seed; const uint32_t call0 = h->call;
+    // the handle's own seed and call counter come back on every way out
+    struct Restore { bm_dbm64 *h; uint64_t seed; uint32_t call; ~Restore() { h->seed = seed; h->call = call; } };
+    const Restore restore{h, h->seed, h->call};
     h->seed = seed;                                       // the streams of an AIS run are keyed by ITS seed (oracle: orc_dbm_ais_d)
     hipLaunchKernelGGL(bm64::dais_x0_kernel, dim3(256), dim3(256), 0, h->stream, h->ax.p, R, H1, bm64::dkey64(bm64::S_AIS_X0, 0, seed, 0), (long long)chain0);
     BM_HIP(hipMemsetAsync(h->alogw.p, 0, (size_t)R * sizeof(double), h->stream));
-    bm64::DBuf *x = &h->ax, *xn = &h->ax2;
+    DevArray<double> *x = &h->ax, *xn = &h->ax2;
     auto transit = [&](double beta, uint32_t step) {
         h->call = step;
         for (int t = 0; t < k; ++t) {
@@ -650,7 +647,7 @@ int bm_dbm64_ais(bm_dbm64 *h, int32_t n_betas, int32_t R, int32_t k, uint64_t se
                                bm64::dkey64(bm64::S_DBM_H + 1, t, seed, step), chain0);
             bm64::layer_update(h, 0, R, h->av.p, h->ah2.p, beta, beta, h->cfg.sample_h_states[0], nullptr, xn->p,
                                bm64::dkey64(bm64::S_DBM_H + 0, t, seed, step), chain0);
-            bm64::DBuf *tx = x; x = xn; xn = tx;
+            DevArray<double> *tx = x; x = xn; xn = tx;
         }
     };
     auto logp = [&](double beta, double sign) {
@@ -670,7 +667,6 @@ int bm_dbm64_ais(bm_dbm64 *h, int32_t n_betas, int32_t R, int32_t k, uint64_t se
         beta = beta + db;
     }
     logp(1.0, 1.0);
-    h->seed = seed0; h->call = call0;
     BM_HIP(hipGetLastError());
     BM_HIP(hipMemcpyAsync(values_host, h->alogw.p, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));

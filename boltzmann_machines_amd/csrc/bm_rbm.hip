@@ -11,6 +11,7 @@
 
 #include <math.h>
 #include <atomic>
+#include <memory>
 
 namespace bm {
 
@@ -43,8 +44,11 @@ struct bm_rbm {
     // reader of dW - get_param, stage (checkpoints), apply_step and the single-GPU fused update - fails (check_dw)
     bool dw_sharded = false;
     int V, H, maxB;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // (streams first: members are destroyed in reverse order, the buffers that run on a stream before it)
+    Stream stream;
+    Stream comm_stream;                // delayed data parallelism: the all-reduces (ensure_delayed)
+    Stream stage_stream;               // bm_rbm_get_staged: the snapshot read-backs
+    Event ev0, ev1;
     // variables (padded pitch, see pad_ld).  The prop-down reads W itself as an x-major operand (ActArgs::p_xm).
     Mat W, dW;                         // [V][H], [V][H]
     // the transpose [H][V], written by the fused update next to W: the prop-up then reads its weights x-major as well
@@ -63,13 +67,12 @@ struct bm_rbm {
     // the other slot, the stream the reductions run on and their events; allocated at the first use of slot 1
     DevBuf grad_alt;
     int grad_slot = 0;
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_ready[2] = {nullptr, nullptr}, ev_reduced[2] = {nullptr, nullptr};
+    Event ev_ready[2], ev_reduced[2];
     DevBuf pen;       // [H]
     DevBuf rowacc;    // [3*maxB]
     DevBuf hhat;      // [3*H] MultinomialRBM free-energy h_hat vectors (rbm.py:58)
-    int *flip = nullptr;
-    double *scal = nullptr;   // [6] device accumulators: msre, l2, F(x), F(x~), F'(x) (multinomial), spare
+    DevArray<int> flip;
+    DevArray<double> scal;    // [6] device accumulators: msre, l2, F(x), F(x~), F'(x) (multinomial), spare
     bool multinomial() const { return cfg.h_unit == BM_UNIT_MULTINOMIAL; }
     uint64_t seed = 0;
     uint32_t call = 0;
@@ -86,25 +89,25 @@ struct bm_rbm {
     int fast = 0;
     bool fast_now = false;
     Mat16 W3, W3t, hs16, vs16;
-    int *nonbinary = nullptr;  // device flag: a state handed to the fast path was not a {0,1} bitmap
+    DevArray<int> nonbinary;   // device flag: a state handed to the fast path was not a {0,1} bitmap
     // bm_rbm_stage / bm_rbm_get_staged: device-side copies of every variable taken in stream order (a checkpoint
     // snapshot that does not stop the stream), read back on their own stream by whoever writes the checkpoint
-    struct Stage { Mat W, dW; DevBuf vb, hb, dvb, dhb, q, sigma; hipEvent_t ev = nullptr; bool ready = false;
+    struct Stage { Mat W, dW; DevBuf vb, hb, dvb, dhb, q, sigma; Event ev; bool ready = false;
                    std::atomic<int> readers{0}; } stage[2];
-    hipStream_t stage_stream = nullptr;
     int last_stage = -1;
-    float *stage_host = nullptr;     // pinned bounce buffer of bm_rbm_get_staged ([V][H])
+    Pinned<float> stage_host;        // pinned bounce buffer of bm_rbm_get_staged ([V][H])
     int device = 0;
     // bm_rbm_train_step_metrics_async: pinned ring of the six device sums of every pending metrics fetch
     static constexpr int MRING = 4096;
-    double *mring = nullptr, *mring_dev = nullptr;    // pinned host ring and its device-side address
+    Pinned<double> mring;                             // pinned host ring ...
+    double *mring_dev = nullptr;                      // ... and its device-side address
     std::vector<int> mring_B;
     int mring_n = 0;
-    hipEvent_t ev_mlast = nullptr;   // behind the last pending fetch: bm_rbm_collect_metrics waits for IT, not for the stream -
+    Event ev_mlast;                  // behind the last pending fetch: bm_rbm_collect_metrics waits for IT, not for the stream -
                                      // updates queued after the fetch (the next epoch's first run) keep the device busy meanwhile
     // optional per-kernel-class event timing
     bool prof = false;
-    struct Rec { int cls; hipEvent_t a, b; };
+    struct Rec { int cls; Event a, b; };
     std::vector<Rec> recs;
     size_t grad_tail() const { return (size_t)V * W.ld; }
     // a run of dependent propagation passes recorded by launch_up / launch_down and issued as ONE launch (bm_chain.h)
@@ -124,10 +127,11 @@ struct ProfScope {
     bm_rbm *h; hipEvent_t b = nullptr;
     ProfScope(bm_rbm *h_, int cls) : h(h_) {
         if (!h->prof) return;
-        hipEvent_t a;
-        (void)hipEventCreate(&a); (void)hipEventCreate(&b);
-        (void)hipEventRecord(a, h->stream);
-        h->recs.push_back({cls, a, b});
+        bm_rbm::Rec r{cls};
+        (void)create(r.a); (void)create(r.b);
+        (void)hipEventRecord(r.a, h->stream);
+        b = r.b;
+        h->recs.push_back(std::move(r));
     }
     ~ProfScope() { if (b) (void)hipEventRecord(b, h->stream); }
 };
@@ -197,7 +201,7 @@ static void launch_up(bm_rbm *h, const float *v, int ldv, int B, float *means, f
         a.fe_rowacc2 = h->fe_part.p + (size_t)rm * h->maxB;
         // the flip columns straight from their Philox stream and the zeroing of the six accumulators ride on this pass: the
         // fused fetch has no prep launch
-        a.fe_flip = FE_FLIP_FROM_KEY; a.fe_key = make_key(h, SITE_PLL, 0); a.fe_zero = h->scal;
+        a.fe_flip = FE_FLIP_FROM_KEY; a.fe_key = make_key(h, SITE_PLL, 0); a.fe_zero = h->scal.p;
         a.fe_x = v; a.fe_ldx = ldv; a.fe_w = h->W.p; a.fe_ldw = h->W.ld;
     }
     if (h->fast_now && v == h->vs.p) {           // fast-binary: W^T planes x the bf16 shadow of the visible bitmap
@@ -388,7 +392,7 @@ static void launch_fe(bm_rbm *h, const float *Xin, int ldx, int B, bool with_fli
     f.K = h->V; f.I = h->H; f.J = B;
     f.hb = h->hb.p;
     f.rowacc = h->rowacc.p;
-    if (with_flip) { f.rowacc2 = h->rowacc.p + h->maxB; f.flip_col = h->flip; }
+    if (with_flip) { f.rowacc2 = h->rowacc.p + h->maxB; f.flip_col = h->flip.p; }
     if (h->multinomial()) {                    // rbm.py:52-62: fresh h_hat draws, streams t = 0, 1, 2
         (void)hipMemsetAsync(h->hhat.p, 0, 3 * (size_t)h->H * sizeof(float), h->stream);
         const int M = h->cfg.n_samples;
@@ -402,7 +406,7 @@ static void launch_fe(bm_rbm *h, const float *Xin, int ldx, int B, bool with_fli
     memset(&r, 0, sizeof(r));
     r.X = Xin; r.ld = ldx; r.V = h->V; r.B = B;
     r.vb = h->vb.p; r.sigma = (h->cfg.v_unit == BM_UNIT_GAUSSIAN) ? h->sigma.p : nullptr;
-    r.rowacc = f.rowacc; r.rowacc2 = f.rowacc2; r.rowacc3 = f.rowacc3; r.flip_col = f.flip_col; r.out = h->scal + 2;
+    r.rowacc = f.rowacc; r.rowacc2 = f.rowacc2; r.rowacc3 = f.rowacc3; r.flip_col = f.flip_col; r.out = h->scal.p + 2;
     hipLaunchKernelGGL(fe_row_kernel, dim3((B + FE_ROWS_PER_WG - 1) / FE_ROWS_PER_WG), dim3(256), 0, h->stream, r);
 }
 
@@ -423,21 +427,21 @@ static bool metrics_fused_ok(const bm_rbm *h) {
 }
 static void metrics_prep(bm_rbm *h, int B) {
     MetricsPrepArgs mp;
-    mp.scal = h->scal; mp.rowacc = h->rowacc.p; mp.n_rowacc = 3 * h->maxB; mp.flip = h->flip; mp.B = B; mp.V = h->V;
+    mp.scal = h->scal.p; mp.rowacc = h->rowacc.p; mp.n_rowacc = 3 * h->maxB; mp.flip = h->flip.p; mp.B = B; mp.V = h->V;
     mp.key = make_key(h, SITE_PLL, 0); mp.row0 = (unsigned long long)h->row0;
     hipLaunchKernelGGL(metrics_prep_kernel, dim3(8), dim3(256), 0, h->stream, mp);
 }
 // the rest of the fetch, behind a run_chain(..., fetch = true): squared sums, the visible terms of the free energies
 static int metrics_from_chain(bm_rbm *h, int B, float *out4) {
-    const SqJob msre{h->Xin, h->Xin_ld, h->vm.p, h->vm.ld, B, h->V, h->scal + 0};                        // :486-488
-    const SqJob l2{h->W.p, h->W.ld, nullptr, 0, h->V, h->H, h->scal + 1};                                 // :482-484
+    const SqJob msre{h->Xin, h->Xin_ld, h->vm.p, h->vm.ld, B, h->V, h->scal.p + 0};                        // :486-488
+    const SqJob l2{h->W.p, h->W.ld, nullptr, 0, h->V, h->H, h->scal.p + 1};                                 // :482-484
     if (h->fe_in_chain) {       // the hidden terms are in fe_part already: squared sums and the row sums as ONE launch
         FeRowArgs r;
         memset(&r, 0, sizeof(r));
         r.X = h->Xin; r.ld = h->Xin_ld; r.V = h->V; r.B = B;
         r.vb = h->vb.p; r.sigma = (h->cfg.v_unit == BM_UNIT_GAUSSIAN) ? h->sigma.p : nullptr;
         r.nslot = (h->H + 15) / 16; r.ld_part = (r.nslot + 3) & ~3;
-        r.rowacc = h->fe_part.p; r.rowacc2 = h->fe_part.p + (size_t)r.ld_part * h->maxB; r.out = h->scal + 2;
+        r.rowacc = h->fe_part.p; r.rowacc2 = h->fe_part.p + (size_t)r.ld_part * h->maxB; r.out = h->scal.p + 2;
         r.flip_col = nullptr; r.has_key = 1; r.key = make_key(h, SITE_PLL, 0); r.row0 = (unsigned long long)h->row0;
         const int nb_sq = 256, nb_fe = (B + FE_ROWS_PER_WG - 1) / FE_ROWS_PER_WG;
         hipLaunchKernelGGL(metrics_tail_kernel, dim3(nb_sq + nb_fe), dim3(256), 0, h->stream, msre, l2, r, nb_sq);
@@ -447,7 +451,7 @@ static int metrics_from_chain(bm_rbm *h, int B, float *out4) {
     }
     if (!out4) return 0;                                    // asynchronous caller: the sums stay in h->scal
     double host[6];
-    BM_HIP(hipMemcpyAsync(host, h->scal, sizeof(host), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipMemcpyAsync(host, h->scal.p, sizeof(host), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     metrics_to_out4(h, host, B, out4);
     return 0;
@@ -522,14 +526,12 @@ int bm_rbm_create(const bm_rbm_config *cfg, bm_rbm **out) {
         BM_CHECK(cfg->n_hidden <= 8192, "MultinomialRBM: n_hidden %d > 8192 (softmax row staged in LDS)", cfg->n_hidden);
     }
     BM_CHECK(bm_device_count() > 0, "no HIP device visible: libbm355 has no CPU fallback");
-    bm_rbm *h = new bm_rbm();
+    auto h = std::make_unique<bm_rbm>();
     h->cfg = *cfg;
     h->V = cfg->n_visible; h->H = cfg->n_hidden; h->maxB = cfg->max_batch;
     const int V = h->V, H = h->H, B = h->maxB;
     BM_HIP(hipGetDevice(&h->device));
-    BM_HIP(hipStreamCreate(&h->stream));
-    BM_HIP(hipEventCreate(&h->ev0));
-    BM_HIP(hipEventCreate(&h->ev1));
+    BM_TRY(create(h->stream)); BM_TRY(create(h->ev0)); BM_TRY(create(h->ev1));
     BM_TRY(h->W.alloc(V, H)); BM_TRY(h->dW.alloc(V, H));
     {
         const char *e = bm::dbg("up_xm");          // default on; 0 keeps the k-major prop-up
@@ -543,48 +545,19 @@ int bm_rbm_create(const bm_rbm_config *cfg, bm_rbm **out) {
     BM_TRY(h->grad.alloc(h->grad_tail() + V + 2 * (size_t)H));
     BM_TRY(h->pen.alloc(H));
     BM_TRY(h->rowacc.alloc(3 * (size_t)B)); BM_TRY(h->hhat.alloc(3 * (size_t)H));
-    BM_HIP(hipMalloc((void **)&h->flip, B * sizeof(int)));
-    BM_HIP(hipMalloc((void **)&h->scal, 6 * sizeof(double)));
+    BM_TRY(h->flip.alloc(B)); BM_TRY(h->scal.alloc(6));
     {   // sigma defaults to 1 (rbm.py:88)
         std::vector<float> ones(V, 1.0f);
         BM_HIP(hipMemcpy(h->sigma.p, ones.data(), V * sizeof(float), hipMemcpyHostToDevice));
     }
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
 int bm_rbm_destroy(bm_rbm *h) {
     if (!h) return 0;
-    (void)hipStreamSynchronize(h->stream);
+    for (hipStream_t st : {h->stream.h, h->comm_stream.h, h->stage_stream.h}) if (st) (void)hipStreamSynchronize(st);
     if (h->xchg_used) xchg_bind_user(h->xchg_used, nullptr);
-    Mat *mats[] = {&h->W, &h->dW, &h->Wt, &h->h0m, &h->h0s, &h->hm, &h->hs, &h->hneg, &h->vm, &h->vs, &h->Xs, &h->Xd};
-    for (Mat *m : mats) m->release();
-    DevBuf *all[] = {&h->vb, &h->hb, &h->dvb, &h->dhb, &h->q, &h->sigma, &h->grad, &h->grad_alt, &h->pen, &h->rowacc, &h->hhat, &h->fe_part};
-    for (int i = 0; i < 2; ++i) {
-        if (h->ev_ready[i]) (void)hipEventDestroy(h->ev_ready[i]);
-        if (h->ev_reduced[i]) (void)hipEventDestroy(h->ev_reduced[i]);
-    }
-    if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
-    if (h->stage_stream) { (void)hipStreamSynchronize(h->stage_stream); (void)hipStreamDestroy(h->stage_stream); }
-    if (h->stage_host) (void)hipHostFree(h->stage_host);
-    if (h->mring) (void)hipHostFree(h->mring);
-    if (h->ev_mlast) (void)hipEventDestroy(h->ev_mlast);
-    for (auto &sg : h->stage) {
-        sg.W.release(); sg.dW.release();
-        DevBuf *sv[] = {&sg.vb, &sg.hb, &sg.dvb, &sg.dhb, &sg.q, &sg.sigma};
-        for (DevBuf *b : sv) b->release();
-        if (sg.ev) (void)hipEventDestroy(sg.ev);
-    }
-    for (DevBuf *b : all) b->release();
-    h->W3.release(); h->W3t.release(); h->hs16.release(); h->vs16.release();
-    if (h->nonbinary) (void)hipFree(h->nonbinary);
-    if (h->flip) (void)hipFree(h->flip);
-    if (h->scal) (void)hipFree(h->scal);
-    h->chain.release();
-    for (auto &r : h->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    (void)hipEventDestroy(h->ev0);
-    (void)hipEventDestroy(h->ev1);
-    (void)hipStreamDestroy(h->stream);
     delete h;
     return 0;
 }
@@ -616,11 +589,11 @@ static int check_device_status(bm_rbm *h) {
 int bm_rbm_sync(bm_rbm *h) {
     BM_HIP(hipStreamSynchronize(h->stream));
     BM_TRY(check_device_status(h));
-    if (h->nonbinary) {
+    if (h->nonbinary.p) {
         int bad = 0;
-        BM_HIP(hipMemcpy(&bad, h->nonbinary, sizeof(int), hipMemcpyDeviceToHost));
+        BM_HIP(hipMemcpy(&bad, h->nonbinary.p, sizeof(int), hipMemcpyDeviceToHost));
         if (bad) {
-            BM_HIP(hipMemset(h->nonbinary, 0, sizeof(int)));
+            BM_HIP(hipMemset(h->nonbinary.p, 0, sizeof(int)));
             BM_CHECK(false, "fast-binary mode: bm_rbm_gibbs was given hidden states that are not a {0,1} bitmap");
         }
     }
@@ -720,9 +693,9 @@ int bm_rbm_stage(bm_rbm *h, int32_t slot) {
         BM_TRY(sg.W.alloc(h->V, h->H)); BM_TRY(sg.dW.alloc(h->V, h->H));
         BM_TRY(sg.vb.alloc(h->V)); BM_TRY(sg.dvb.alloc(h->V)); BM_TRY(sg.sigma.alloc(h->V));
         BM_TRY(sg.hb.alloc(h->H)); BM_TRY(sg.dhb.alloc(h->H)); BM_TRY(sg.q.alloc(h->H));
-        BM_HIP(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+        BM_TRY(create(sg.ev, hipEventDisableTiming));            // last: the slot is complete once it exists
     }
-    if (!h->stage_stream) BM_HIP(hipStreamCreateWithFlags(&h->stage_stream, hipStreamNonBlocking));
+    if (!h->stage_stream) BM_TRY(create(h->stage_stream, hipStreamNonBlocking));
     // Bound the host's run-ahead to one snapshot interval: a training loop that never fetches anything would otherwise
     // queue every epoch of the call at once (measured: 4000 updates = 16 000 launches in flight ran 101 instead of
     // 77 us per update).  Waiting for the PREVIOUS snapshot's copies leaves the whole current epoch queued: no bubble.
@@ -750,14 +723,14 @@ int bm_rbm_get_staged(bm_rbm *h, int32_t slot, const char *name, float *host, si
     // launches stalled behind it, 101 instead of 76 us per update)
     BM_HIP(hipEventSynchronize(sg.ev));
     const size_t need = (size_t)h->V * h->H * sizeof(float);
-    if (!h->stage_host) BM_HIP(hipHostMalloc((void **)&h->stage_host, need, hipHostMallocDefault));
+    if (!h->stage_host) BM_TRY(create(h->stage_host, (size_t)h->V * h->H));
     if (h->chain.status) {
         // the sticky error word of the chained launches (not the tile count: the training thread may be ahead of the
         // device): a checkpoint must not be written from tiles a failed launch left invalid
         BM_HIP(hipMemcpyAsync(h->stage_host, h->chain.status, sizeof(int), hipMemcpyDeviceToHost, h->stage_stream));
         BM_HIP(hipStreamSynchronize(h->stage_stream));
-        BM_CHECK(*(const int *)h->stage_host == 0, "a chained propagation launch failed (status %d) before this snapshot: "
-                 "it is invalid (bm_rbm_sync reports and recovers)", *(const int *)h->stage_host);
+        BM_CHECK(*(const int *)h->stage_host.h == 0, "a chained propagation launch failed (status %d) before this snapshot: "
+                 "it is invalid (bm_rbm_sync reports and recovers)", *(const int *)h->stage_host.h);
     }
     if (nm == "W" || nm == "dW") {
         BM_CHECK(n == (size_t)h->V * h->H, "variable '%s' has %zu elements, got %zu", name, (size_t)h->V * h->H, n);
@@ -817,18 +790,20 @@ int bm_rbm_train_step_metrics(bm_rbm *h, const float *X_dev, int32_t B, float lr
 // synchronisation per epoch instead of one per fetch: fit() with the reference's default cadence ran 81 - 98 us per
 // update against 68 without metrics, almost all of it the GPU idling behind the host round trips).
 int bm_rbm_train_step_metrics_async(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
-    if (!h->mring) {
-        BM_HIP(hipHostMalloc((void **)&h->mring, (size_t)bm_rbm::MRING * 6 * sizeof(double), hipHostMallocDefault));
-        BM_HIP(hipHostGetDevicePointer((void **)&h->mring_dev, h->mring, 0));
+    if (!h->mring) {                  // (the ring is set last: it marks the setup as complete)
+        Pinned<double> ring;
+        BM_TRY(create(ring, (size_t)bm_rbm::MRING * 6));
+        BM_TRY(create(h->ev_mlast, hipEventDisableTiming));
+        BM_HIP(hipHostGetDevicePointer((void **)&h->mring_dev, ring, 0));
         h->mring_B.resize(bm_rbm::MRING);
+        h->mring = std::move(ring);
     }
     BM_CHECK(h->mring_n < bm_rbm::MRING, "%d metric fetches are pending: call bm_rbm_collect_metrics", h->mring_n);
     BM_TRY(check_dw(h, "bm_rbm_train_step_metrics_async"));
     BM_TRY(run_chain(h, X_dev, B, k, nullptr, true, false, false, true));
     BM_TRY(metrics_from_chain(h, B, nullptr));
-    hipLaunchKernelGGL(scal_to_host_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)h->scal,
+    hipLaunchKernelGGL(scal_to_host_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)h->scal.p,
                        h->mring_dev + (size_t)h->mring_n * 6);
-    if (!h->ev_mlast) BM_HIP(hipEventCreateWithFlags(&h->ev_mlast, hipEventDisableTiming));
     BM_HIP(hipEventRecord(h->ev_mlast, h->stream));
     h->mring_B[h->mring_n++] = B;
     launch_update_fused(h, B, lr, mom);
@@ -883,18 +858,17 @@ int bm_rbm_grad_step(bm_rbm *h, const float *X_dev, int32_t B, int32_t k) {
 static int ensure_delayed(bm_rbm *h) {
     if (h->comm_stream) return 0;
     BM_TRY(h->grad_alt.alloc(h->grad.n));
-    BM_HIP(hipStreamCreate(&h->comm_stream));
     for (int i = 0; i < 2; ++i) {
-        BM_HIP(hipEventCreateWithFlags(&h->ev_ready[i], hipEventDisableTiming));
-        BM_HIP(hipEventCreateWithFlags(&h->ev_reduced[i], hipEventDisableTiming));
+        BM_TRY(create(h->ev_ready[i], hipEventDisableTiming));
+        BM_TRY(create(h->ev_reduced[i], hipEventDisableTiming));
     }
-    return 0;
+    return create(h->comm_stream);    // last: the setup is complete once it exists
 }
 int bm_rbm_set_grad_slot(bm_rbm *h, int32_t slot) {
     BM_CHECK(h && (slot == 0 || slot == 1), "slot must be 0 or 1");
     if (slot == h->grad_slot) return 0;
     BM_TRY(ensure_delayed(h));
-    DevBuf t = h->grad; h->grad = h->grad_alt; h->grad_alt = t;
+    std::swap(h->grad, h->grad_alt);
     h->grad_slot = slot;
     return 0;
 }
@@ -972,11 +946,11 @@ int bm_rbm_free_energy(bm_rbm *h, const float *X_dev, int32_t B, float *out1) {
         Xin = h->Xd.p; ldx = h->Xd.ld;
         dropped = true;
     }
-    BM_HIP(hipMemsetAsync(h->scal, 0, 6 * sizeof(double), h->stream));
+    BM_HIP(hipMemsetAsync(h->scal.p, 0, 6 * sizeof(double), h->stream));
     BM_HIP(hipMemsetAsync(h->rowacc.p, 0, 3 * (size_t)h->maxB * sizeof(float), h->stream));
     launch_fe(h, Xin, ldx, B, false);
     double host[6];
-    BM_HIP(hipMemcpyAsync(host, h->scal, sizeof(host), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipMemcpyAsync(host, h->scal.p, sizeof(host), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     *out1 = (float)(host[2] / B + mn_fe_const(h));
     if (h->multinomial() || dropped) h->call++;   // the random h_hat / the dropout mask consumed one call of the stream
@@ -1013,18 +987,18 @@ int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_ste
     if (fast) {
         // fast-binary sweep: both layers are sampled, so every contraction has a {0,1} operand (the caller's hidden
         // states must be a bitmap as well: checked on the device, reported by bm_rbm_sync)
-        if (h->W3.rows != h->V) {
+        if (!h->nonbinary.p) {        // (allocated last: the planes and shadows are complete once it exists)
             BM_TRY(h->W3.alloc(3, h->V, h->H)); BM_TRY(h->W3t.alloc(3, h->H, h->V));
             BM_TRY(h->hs16.alloc(1, h->maxB, h->H)); BM_TRY(h->vs16.alloc(1, h->maxB, h->V));
-            BM_HIP(hipMalloc((void **)&h->nonbinary, sizeof(int)));
-            BM_HIP(hipMemsetAsync(h->nonbinary, 0, sizeof(int), h->stream));
+            BM_TRY(h->nonbinary.alloc(1));
+            BM_HIP(hipMemsetAsync(h->nonbinary.p, 0, sizeof(int), h->stream));
         }
         hipLaunchKernelGGL(split3_kernel, dim3(512), dim3(256), 0, h->stream, (const float *)h->W.p, h->W.ld, h->V, h->H,
                            h->W3.p, h->W3.plane_stride(), h->W3.ld, 0);
         hipLaunchKernelGGL(split3_kernel, dim3(512), dim3(256), 0, h->stream, (const float *)h->W.p, h->W.ld, h->V, h->H,
                            h->W3t.p, h->W3t.plane_stride(), h->W3t.ld, 1);
         hipLaunchKernelGGL(shadow16_check_kernel, dim3(256), dim3(256), 0, h->stream, (const float *)h->hs.p, h->hs.ld, B, h->H,
-                           h->hs16.p, h->hs16.ld, h->nonbinary);
+                           h->hs16.p, h->hs16.ld, h->nonbinary.p);
         h->fast_now = true;
     }
     for (int t = 0; t < n_steps; ++t) {
@@ -1054,7 +1028,6 @@ int bm_rbm_stream(bm_rbm *h, void **out_stream) { *out_stream = (void *)h->strea
 
 int bm_rbm_profile(bm_rbm *h, int32_t enable) {
     BM_HIP(hipStreamSynchronize(h->stream));
-    for (auto &r : h->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     h->recs.clear();
     h->prof = enable != 0;
     return 0;

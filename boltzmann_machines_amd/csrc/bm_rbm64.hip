@@ -628,28 +628,19 @@ __global__ __launch_bounds__(256) void free_energy_kernel(const double *X, int l
     block_store(t2, rows + ldr + b, s_w, 1);
 }
 
-struct DBuf {
-    double *p = nullptr; size_t n = 0;
-    int alloc(size_t count) {
-        n = count;
-        if (hipMalloc((void **)&p, (count ? count : 1) * sizeof(double)) != hipSuccess) { bm::set_error("hipMalloc of %zu doubles failed", count); return 1; }
-        return hipMemset(p, 0, (count ? count : 1) * sizeof(double)) == hipSuccess ? 0 : 1;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
 enum : uint32_t { SITE_DROPOUT = 1, SITE_H0 = 2, SITE_V = 3, SITE_H = 4, SITE_PLL = 5, SITE_FE = 6 };
 }  // namespace bm64
 
 struct bm_rbm64 {
     bm_rbm_config cfg;
     int V, H, maxB;
-    hipStream_t stream = nullptr;
-    bm64::DBuf W, Wt, dW, vb, hb, dvb, dhb, q, sigma, pen;
-    bm64::DBuf h0m, h0s, hm, hs, vm, vs, Xp;
-    int *flip = nullptr;
-    double *scal = nullptr;      // [6] msre, l2, F(x), F(x~), F'(x) (multinomial: the PLL's own h_hat), spare
-    bm64::DBuf hhat;             // [3*H] MultinomialRBM free-energy h_hat vectors (rbm.py:58)
-    bm64::DBuf part;             // partial sums of the metric reductions: [2][SQ_BLOCKS] msre / l2 | [3][maxB] free-energy rows
+    Stream stream;
+    DevArray<double> W, Wt, dW, vb, hb, dvb, dhb, q, sigma, pen;
+    DevArray<double> h0m, h0s, hm, hs, vm, vs, Xp;
+    DevArray<int> flip;
+    DevArray<double> scal;       // [6] msre, l2, F(x), F(x~), F'(x) (multinomial: the PLL's own h_hat), spare
+    DevArray<double> hhat;             // [3*H] MultinomialRBM free-energy h_hat vectors (rbm.py:58)
+    DevArray<double> part;             // partial sums of the metric reductions: [2][SQ_BLOCKS] msre / l2 | [3][maxB] free-energy rows
     bool multinomial() const { return cfg.h_unit == BM_UNIT_MULTINOMIAL; }
     uint64_t seed = 0; uint32_t call = 0; int64_t row0 = 0;
     const double *Xin = nullptr; int Xin_ld = 0;
@@ -717,7 +708,7 @@ static void launch_reduce(bm_rbm64 *h, int B, bool with_sq, bool with_flip) {
     jb.off[2] = fe0;                 jb.cnt[2] = B;
     jb.off[3] = fe0 + h->maxB;       jb.cnt[3] = with_flip ? B : 0;
     jb.off[4] = fe0 + 2 * h->maxB;   jb.cnt[4] = h->multinomial() ? B : 0;
-    hipLaunchKernelGGL(reduce_fixed_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)h->part.p, jb, h->scal);
+    hipLaunchKernelGGL(reduce_fixed_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)h->part.p, jb, h->scal.p);
 }
 // input preprocessing + h0 + k Gibbs steps (base_rbm.py:417-426)
 static int run_chain(bm_rbm64 *h, const double *X_dev, int B, int k, double *hm_out) {
@@ -761,15 +752,15 @@ static void launch_update(bm_rbm64 *h, int B, double lr, double mom) {
     hipLaunchKernelGGL(grad_kernel, dim3(nx, ny + extra), dim3(256), 0, h->stream, g);
 }
 static int metrics_from_chain(bm_rbm64 *h, int B, double *out4) {
-    BM_HIP(hipMemsetAsync(h->scal, 0, 6 * sizeof(double), h->stream));
+    BM_HIP(hipMemsetAsync(h->scal.p, 0, 6 * sizeof(double), h->stream));
     hipLaunchKernelGGL(sqdiff_kernel, dim3(SQ_BLOCKS), dim3(256), 0, h->stream, h->Xin, (const double *)h->vm.p, (size_t)B * h->V, h->part.p);
     hipLaunchKernelGGL(sqdiff_kernel, dim3(SQ_BLOCKS), dim3(256), 0, h->stream, (const double *)h->W.p, (const double *)nullptr, (size_t)h->V * h->H, h->part.p + SQ_BLOCKS);
-    hipLaunchKernelGGL(pll_index_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->flip, B, h->V,
+    hipLaunchKernelGGL(pll_index_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->flip.p, B, h->V,
                        make_key(h, SITE_PLL, 0), (unsigned long long)h->row0);
-    launch_fe(h, h->Xin, h->Xin_ld, B, (const int *)h->flip);
+    launch_fe(h, h->Xin, h->Xin_ld, B, (const int *)h->flip.p);
     launch_reduce(h, B, true, true);
     double host[6];
-    BM_HIP(hipMemcpyAsync(host, h->scal, sizeof(host), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipMemcpyAsync(host, h->scal.p, sizeof(host), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     // MultinomialRBM: every _free_energy() call draws its own h_hat (host[4] = F(x) of the PLL pair) and carries the
     // constant of rbm.py:61 (it cancels in the PLL difference)
@@ -781,8 +772,8 @@ static int metrics_from_chain(bm_rbm64 *h, int B, double *out4) {
     out4[3] = fe;
     return 0;
 }
-static DBuf *find(bm_rbm64 *h, const char *name) {
-    struct { const char *n; DBuf *b; } t[] = {{"W", &h->W}, {"vb", &h->vb}, {"hb", &h->hb}, {"dW", &h->dW}, {"dvb", &h->dvb},
+static DevArray<double> *find(bm_rbm64 *h, const char *name) {
+    struct { const char *n; DevArray<double> *b; } t[] = {{"W", &h->W}, {"vb", &h->vb}, {"hb", &h->hb}, {"dW", &h->dW}, {"dvb", &h->dvb},
                                               {"dhb", &h->dhb}, {"q_means", &h->q}, {"sigma", &h->sigma}};
     for (auto &e : t) if (!strcmp(e.n, name)) return e.b;
     return nullptr;
@@ -802,7 +793,7 @@ int bm_rbm64_create(const bm_rbm_config *cfg, const double *hyper5, bm_rbm64 **o
     BM_CHECK(cfg->h_unit != BM_UNIT_MULTINOMIAL || (cfg->n_samples >= 1 && cfg->n_hidden <= 8192),
              "MultinomialRBM needs n_samples >= 1 and n_hidden <= 8192 (got %d, %d)", cfg->n_samples, cfg->n_hidden);
     BM_CHECK(bm_device_count() > 0, "no HIP device visible: libbm355 has no CPU fallback");
-    bm_rbm64 *h = new bm_rbm64();
+    auto h = std::make_unique<bm_rbm64>();
     h->cfg = *cfg;
     h->V = cfg->n_visible; h->H = cfg->n_hidden; h->maxB = cfg->max_batch;
     h->l2 = hyper5 ? hyper5[0] : (double)cfg->l2;
@@ -811,33 +802,24 @@ int bm_rbm64_create(const bm_rbm_config *cfg, const double *hyper5, bm_rbm64 **o
     h->sp_damping = hyper5 ? hyper5[3] : (double)cfg->sparsity_damping;
     h->dropout = hyper5 ? hyper5[4] : (double)cfg->dropout;
     const size_t V = h->V, H = h->H, B = h->maxB;
-    BM_HIP(hipStreamCreate(&h->stream));
+    BM_TRY(create(h->stream));
     BM_TRY(h->W.alloc(V * H)); BM_TRY(h->Wt.alloc(V * H)); BM_TRY(h->dW.alloc(V * H));
     BM_TRY(h->vb.alloc(V)); BM_TRY(h->hb.alloc(H)); BM_TRY(h->dvb.alloc(V)); BM_TRY(h->dhb.alloc(H));
     BM_TRY(h->q.alloc(H)); BM_TRY(h->sigma.alloc(V)); BM_TRY(h->pen.alloc(H));
     BM_TRY(h->h0m.alloc(B * H)); BM_TRY(h->h0s.alloc(B * H)); BM_TRY(h->hm.alloc(B * H)); BM_TRY(h->hs.alloc(B * H));
     BM_TRY(h->vm.alloc(B * V)); BM_TRY(h->vs.alloc(B * V)); BM_TRY(h->Xp.alloc(B * V));
-    BM_HIP(hipMalloc((void **)&h->flip, B * sizeof(int)));
-    BM_HIP(hipMalloc((void **)&h->scal, 6 * sizeof(double)));
+    BM_TRY(h->flip.alloc(B)); BM_TRY(h->scal.alloc(6));
     BM_TRY(h->hhat.alloc(3 * H));
     BM_TRY(h->part.alloc(2 * (size_t)bm64::SQ_BLOCKS + 3 * (size_t)h->maxB));
     std::vector<double> ones(V, 1.0);
     BM_HIP(hipMemcpy(h->sigma.p, ones.data(), V * sizeof(double), hipMemcpyHostToDevice));
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
 int bm_rbm64_destroy(bm_rbm64 *h) {
     if (!h) return 0;
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    DBuf *all[] = {&h->W, &h->Wt, &h->dW, &h->vb, &h->hb, &h->dvb, &h->dhb, &h->q, &h->sigma, &h->pen,
-                   &h->h0m, &h->h0s, &h->hm, &h->hs, &h->vm, &h->vs, &h->Xp};
-    for (DBuf *b : all) b->release();
-    if (h->flip) (void)hipFree(h->flip);
-    if (h->scal) (void)hipFree(h->scal);
-    h->hhat.release();
-    h->part.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return 0;
 }
@@ -847,7 +829,7 @@ int bm_rbm64_seed(bm_rbm64 *h, uint64_t seed) { h->seed = seed; h->call = 0; ret
 int bm_rbm64_set_row_offset(bm_rbm64 *h, int64_t row0) { h->row0 = row0; return 0; }
 
 int bm_rbm64_set_param(bm_rbm64 *h, const char *name, const double *host, size_t n) {
-    DBuf *b = find(h, name);
+    DevArray<double> *b = find(h, name);
     BM_CHECK(b, "unknown variable '%s'", name);
     BM_CHECK(n == b->n, "variable '%s' has %zu elements, got %zu", name, b->n, n);
     BM_HIP(hipStreamSynchronize(h->stream));
@@ -859,7 +841,7 @@ int bm_rbm64_set_param(bm_rbm64 *h, const char *name, const double *host, size_t
     return 0;
 }
 int bm_rbm64_get_param(bm_rbm64 *h, const char *name, double *host, size_t n) {
-    DBuf *b = find(h, name);
+    DevArray<double> *b = find(h, name);
     BM_CHECK(b, "unknown variable '%s'", name);
     BM_CHECK(n == b->n, "variable '%s' has %zu elements, got %zu", name, b->n, n);
     BM_HIP(hipStreamSynchronize(h->stream));
@@ -906,11 +888,11 @@ int bm_rbm64_free_energy(bm_rbm64 *h, const double *X_dev, int32_t B, double *ou
                            (unsigned long long)h->row0 * (unsigned long long)h->V);
         Xin = h->Xp.p;
     }
-    BM_HIP(hipMemsetAsync(h->scal, 0, 6 * sizeof(double), h->stream));
+    BM_HIP(hipMemsetAsync(h->scal.p, 0, 6 * sizeof(double), h->stream));
     launch_fe(h, Xin, h->V, B, (const int *)nullptr);
     bm64::launch_reduce(h, B, false, false);
     double host[6];
-    BM_HIP(hipMemcpyAsync(host, h->scal, sizeof(host), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipMemcpyAsync(host, h->scal.p, sizeof(host), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     *out1 = host[2] / B + mn_fe_const(h);
     if (dropped || h->multinomial()) h->call++;  // the dropout mask / the random h_hat consumed one call of the stream

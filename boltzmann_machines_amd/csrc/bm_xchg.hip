@@ -1080,7 +1080,7 @@ int bm_dbm_ais_sharded_direct(bm_dbm *h, bm_xchg *x, int32_t n_betas, int32_t n_
     for (size_t lo = 0; lo < (size_t)n_runs_total && !rc_x && !rc_m; lo += x->count) {
         const size_t nw = (size_t)n_runs_total - lo < x->count ? (size_t)n_runs_total - lo : x->count;
         hipLaunchKernelGGL(ais_window_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, h->stream,
-                           (const double *)h->alogw, x->buf, (int)lo, (int)nw, a, b, z0, h->ais_literal, rc ? 1 : 0);
+                           (const double *)h->alogw.p, x->buf, (int)lo, (int)nw, a, b, z0, h->ais_literal, rc ? 1 : 0);
         rc_x = xchg_allreduce_prefix(x, nw, h->stream);
         if (rc_x) { if (first_err.empty()) first_err = bm_last_error(); break; }
         if (hipMemcpyAsync(values_host + lo, x->buf, nw * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc_m = 1;

@@ -14,6 +14,8 @@
  *     means, chain workspaces) in HBM and one HIP stream; calls on one handle
  *     are asynchronous on that stream and must not be issued concurrently
  *     from several host threads.  bm_*_sync() blocks until the stream drains.
+ *   - a failed bm_*_create (bm_rbm, bm_rbm64, bm_dbm, bm_dbm64) frees everything
+ *     it had allocated and leaves *out untouched; bm_*_destroy(NULL) is a no-op.
  *   - all arithmetic is fp32 (reference default dtype, base/mixin.py:15).
  *   - matrices are row-major; W is [n_below, n_above] like the reference
  *     (base_rbm.py:277-293).
@@ -74,6 +76,7 @@ typedef struct bm_rbm_config {
     int32_t n_samples;         /* MultinomialLayer.n_samples (rbm.py:46); ignored for Bernoulli hidden units */
 } bm_rbm_config;
 
+/* on failure nothing stays allocated and *out is not written (the same for bm_rbm64 / bm_dbm / bm_dbm64_create) */
 int bm_rbm_create(const bm_rbm_config *cfg, bm_rbm **out);
 int bm_rbm_destroy(bm_rbm *h);
 int bm_rbm_sync(bm_rbm *h);

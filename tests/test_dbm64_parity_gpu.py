@@ -173,3 +173,11 @@ def test_public_class_float64_runs_on_the_device(gpu_lib, tmp_path):
     assert dbm.sample_v(n_gibbs_steps=2).shape == (10, V)
     log_Z = dbm.log_Z(n_betas=50, n_runs=8, n_gibbs_steps=1)[0]
     assert np.isfinite(log_Z) and np.all(np.isfinite(dbm.log_proba(X, log_Z)))
+
+
+def test_layer_narrower_than_its_index_is_rejected_f64(gpu_lib):
+    """layer i needs more than i units (the sparsity index of dbm.py:583), as in the float32 DBM"""
+    from boltzmann_machines_amd._ffi import Bm355Error
+    from boltzmann_machines_amd.engine import DbmEngine64
+    with pytest.raises(Bm355Error, match='layer 1 needs more than 1 units'):
+        DbmEngine64(16, (8, 1), batch_size=4, n_particles=4)
