@@ -12,9 +12,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <array>
-#include <map>
-#include <mutex>
 #include "bm_gemm.h"
 #include "bm_bf3.h"
 #include "bm_numerics.h"
@@ -1177,22 +1174,6 @@ __global__ __launch_bounds__(256) void apply_w_tiled_kernel(ApplyWArgs a, RbmBia
         }
     }
 }
-// host: tiled path needs whole 16-byte groups (I % 4 == 0, pitches % 4 == 0); else the elementwise kernels
-static inline void launch_apply_w(const ApplyWArgs &a, const RbmBiasArgs *bias, hipStream_t st) {
-    const bool tiled = (a.I % 4 == 0) && (a.ldw % 4 == 0) && (!a.Wt || a.ldwt % 4 == 0);
-    if (tiled) {
-        RbmBiasArgs b;
-        memset(&b, 0, sizeof(b));
-        int nb = 0;
-        if (bias) { b = *bias; nb = (b.V + b.H + 255) / 256; }
-        const int ntile = ((a.I + 63) / 64) * ((a.J + 63) / 64);
-        hipLaunchKernelGGL(apply_w_tiled_kernel, dim3(ntile + nb), dim3(256), 0, st, a, b, nb);
-    } else {
-        if (bias) hipLaunchKernelGGL(rbm_bias_kernel, dim3((bias->V + bias->H + 255) / 256), dim3(256), 0, st, *bias);
-        hipLaunchKernelGGL(apply_w_kernel, dim3(1024), dim3(256), 0, st, a);
-    }
-}
-
 // ------------------------------------------------------ MultinomialLayer (layers.py:54-70)
 // One wave per row of logits L[j][0..I) (written by act_kernel kind 3), in place:
 //   means = M * softmax(l);  states = counts of M categorical draws (or = means when !sample).
@@ -1910,529 +1891,6 @@ __global__ __launch_bounds__(256) void mf_init0_kernel(const float *Z, int ldz, 
     }
 }
 
-// ------------------------------------------------------------- host launchers
-template <class G> static inline int tile_grid(int I, int J) { return ((I + G::TI - 1) / G::TI) * ((J + G::TJ - 1) / G::TJ); }
-
-template <class G, int MINB, int STG>
-static inline void launch_act_geo(const ActArgs &a_in, hipStream_t st) {
-    const ActArgs &a = a_in;
-    TileMap tmap;
-    {   // operand bytes one tile row (TI outputs along i) / one tile column (TJ rows) pulls through the L2
-        const double kt = (double)a.K1 + (double)a.K2;
-        tmap = make_tile_map((a.I + G::TI - 1) / G::TI, (a.J + G::TJ - 1) / G::TJ, kt * G::TI * 4.0, kt * G::TJ * 4.0, a.map_xi);
-    }
-    const bool seg2 = a.K2 > 0;
-    const int pl = a.p_xm ? XM : KM;
-    const bool fast = operand_fast(a.P1, pl, a.K1) && operand_fast(a.Q1, XM, a.K1) &&
-                      (!seg2 || (operand_fast(a.P2, KM, a.K2) && operand_fast(a.Q2, XM, a.K2)));
-    const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
-    // (shapes without 16-byte loads have ONE flavour: every chunk passes through registers)
-    if constexpr (G::MI == 1) {
-        if (a.p_xm) {                       // x-major P: single segment only (RBM prop-down from W)
-            if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, false, true, 0, XM, STG>), grid, blk, 0, st, a, tmap);
-            else      hipLaunchKernelGGL((act_kernel<G, MINB, false, false, 0, XM, STG_DMA>), grid, blk, 0, st, a, tmap);
-            return;
-        }
-    }
-    if (seg2) {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, true, true, 0, KM, STG>), grid, blk, 0, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, MINB, true, false, 0, KM, STG_DMA>), grid, blk, 0, st, a, tmap);
-    } else {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, false, true, 0, KM, STG>), grid, blk, 0, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, MINB, false, false, 0, KM, STG_DMA>), grid, blk, 0, st, a, tmap);
-    }
-}
-
-// the h0 pass of a fused metric fetch (ActArgs::fe_flip): the 8-wave 32 x 64 tile, LDS-DMA, slab order - a compile-time
-// flavour of its own (FE) and not a tuner case, so that the kernels of the plain update carry none of its code (same-box A/B:
-// a runtime branch in the shared epilogue cost the headline 0.5 us per update).  The 32 x 32 tiles measured within 1 us of it.
-static inline void launch_act_fe(const ActArgs &a, hipStream_t st) {
-    using G = GeoAct8;
-    const double kt = (double)a.K1;
-    const TileMap tmap = make_tile_map((a.I + G::TI - 1) / G::TI, (a.J + G::TJ - 1) / G::TJ, kt * G::TI * 4.0, kt * G::TJ * 4.0, -1);
-    const bool fast = operand_fast(a.P1, a.p_xm ? XM : KM, a.K1) && operand_fast(a.Q1, XM, a.K1);
-    const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
-    if (a.p_xm) {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, 1, false, true, 0, XM, STG_DMA, true>), grid, blk, 0, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, 1, false, false, 0, XM, STG_DMA, true>), grid, blk, 0, st, a, tmap);
-    } else {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, 1, false, true, 0, KM, STG_DMA, true>), grid, blk, 0, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, 1, false, false, 0, KM, STG_DMA, true>), grid, blk, 0, st, a, tmap);
-    }
-}
-
-// "reference arithmetic" launches (ActArgs::lit, bm_dbm_set_sigmoid_literal): the literal float32 tf.sigmoid in the epilogue -
-// a compile-time flavour (LIT) on ONE geometry (32 x 32 tiles, LDS-DMA, slab order; x-major P needs MI == 1): a parity mode,
-// not a tuner case, so the kernels of the default path carry none of its code.  Same canonical accumulation order as
-// every other geometry (bm_gemm.h), hence the same pre-activations bit for bit.
-static inline void launch_act_lit(const ActArgs &a, hipStream_t st) {
-    using G = GeoActS;
-    const double kt = (double)a.K1 + (double)a.K2;
-    const TileMap tmap = make_tile_map((a.I + G::TI - 1) / G::TI, (a.J + G::TJ - 1) / G::TJ, kt * G::TI * 4.0, kt * G::TJ * 4.0, -1);
-    const bool seg2 = a.K2 > 0;
-    const bool fast = operand_fast(a.P1, a.p_xm ? XM : KM, a.K1) && operand_fast(a.Q1, XM, a.K1) &&
-                      (!seg2 || (operand_fast(a.P2, KM, a.K2) && operand_fast(a.Q2, XM, a.K2)));
-    const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
-    if (a.p_xm) {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, 2, false, true, 0, XM, STG_DMA, false, true>), grid, blk, 0, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, 2, false, false, 0, XM, STG_DMA, false, true>), grid, blk, 0, st, a, tmap);
-    } else if (seg2) {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, 2, true, true, 0, KM, STG_DMA, false, true>), grid, blk, 0, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, 2, true, false, 0, KM, STG_DMA, false, true>), grid, blk, 0, st, a, tmap);
-    } else {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, 2, false, true, 0, KM, STG_DMA, false, true>), grid, blk, 0, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, 2, false, false, 0, KM, STG_DMA, false, true>), grid, blk, 0, st, a, tmap);
-    }
-}
-
-// mean-field passes (ActArgs::prev / maxdiff / skip / chk_ctl / acc_init): the MF flavour (ActSide<.., MF>), LDS-DMA, slab order.
-// Two tiles, by rule: 32 x 64 (8 waves, one workgroup per CU) where that gives every CU a tile, else 32 x 32 (4 waves) - what the
-// launch tuner picked for these passes at 784-512-1024 x 512 (profiles/r5_dbm_kernel_stats.csv); BM355_DEBUG=mf_geo=8|1 forces
-// one.  The literal-sigmoid mode (LIT) takes the 32 x 32 tile.
-template <class G, int MINB, bool LIT>
-static inline void launch_act_mf_geo(const ActArgs &a, hipStream_t st, unsigned dyn_lds = 0) {
-    const double kt = (double)a.K1 + (double)a.K2;
-    const TileMap tmap = make_tile_map((a.I + G::TI - 1) / G::TI, (a.J + G::TJ - 1) / G::TJ, kt * G::TI * 4.0, kt * G::TJ * 4.0, -1);
-    const bool seg2 = a.K2 > 0;
-    const bool fast = operand_fast(a.P1, a.p_xm ? XM : KM, a.K1) && operand_fast(a.Q1, XM, a.K1) &&
-                      (!seg2 || (operand_fast(a.P2, KM, a.K2) && operand_fast(a.Q2, XM, a.K2)));
-    const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
-    if (a.p_xm) {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, false, true, 0, XM, STG_DMA, false, LIT, true>), grid, blk, dyn_lds, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, MINB, false, false, 0, XM, STG_DMA, false, LIT, true>), grid, blk, dyn_lds, st, a, tmap);
-    } else if (seg2) {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, true, true, 0, KM, STG_DMA, false, LIT, true>), grid, blk, dyn_lds, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, MINB, true, false, 0, KM, STG_DMA, false, LIT, true>), grid, blk, dyn_lds, st, a, tmap);
-    } else {
-        if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, false, true, 0, KM, STG_DMA, false, LIT, true>), grid, blk, dyn_lds, st, a, tmap);
-        else      hipLaunchKernelGGL((act_kernel<G, MINB, false, false, 0, KM, STG_DMA, false, LIT, true>), grid, blk, dyn_lds, st, a, tmap);
-    }
-}
-static inline void launch_act_mf(const ActArgs &a, hipStream_t st) {
-    if (a.lit && a.kind == 0) { launch_act_mf_geo<GeoActS, 1, true>(a, st); return; }
-    static const int force = bm::dbg("mf_geo") ? atoi(bm::dbg("mf_geo")) : 0;
-    int dev = 0, ncu = 256;
-    static int ncu_cached = 0;
-    if (!ncu_cached) {
-        hipDeviceProp_t pr;
-        (void)hipGetDevice(&dev);
-        ncu_cached = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    }
-    ncu = ncu_cached;
-    const bool wide = force ? force == 8 : tile_grid<GeoAct8>(a.I, a.J) >= ncu;
-    // (the 32 x 32 tile of this flavour takes 64 KiB for its ring + 16 KiB for the control words: one workgroup per CU)
-    if (wide) launch_act_mf_geo<GeoAct8, 1, false>(a, st);
-    else      launch_act_mf_geo<GeoActS, 1, false>(a, st);
-}
-
-// fast-binary launch (a.b3 filled).  Three tiles: 64 x 64 / 8 waves and 64 x 32 / 4 waves (one workgroup per CU: the
-// ring takes most of the LDS), 32 x 64 / 4 waves with TWO workgroups per CU (80 KiB each: one workgroup's epilogue -
-// sigmoid, draw, the AIS softplus terms - runs under the other's matrix work).  Every workgroup owns a strip of
-// tile columns.  BM355_DEBUG=bf3_geo=8|4|2 forces one.
-template <class G, int WGS_PER_CU>
-static inline void launch_act_bf3_geo(const ActArgs &a, hipStream_t st) {
-    static int ncu = 0;
-    if (!ncu) { hipDeviceProp_t pr; int d = 0; (void)hipGetDevice(&d); ncu = (hipGetDeviceProperties(&pr, d) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
-    Bf3Strip sp;
-    sp.tiles_i = (a.I + G::TI - 1) / G::TI; sp.tiles_j = (a.J + G::TJ - 1) / G::TJ;
-    static const int abl_env = bm::dbg("bf3_abl") ? atoi(bm::dbg("bf3_abl")) : 0;
-    sp.abl = abl_env;
-    sp.strips = (ncu * WGS_PER_CU) / sp.tiles_i;
-    if (sp.strips < 1) sp.strips = 1;
-    if (sp.strips > sp.tiles_j) sp.strips = sp.tiles_j;
-    const dim3 grid(sp.tiles_i * sp.strips), blk(G::NT);
-    constexpr int MINW = WGS_PER_CU * G::NW / 4 > 0 ? WGS_PER_CU * G::NW / 4 : 1;          // waves per SIMD the grid needs
-    if (a.b3.K2 > 0) hipLaunchKernelGGL((act_bf3_kernel<G, true, MINW>), grid, blk, 0, st, a, sp);
-    else             hipLaunchKernelGGL((act_bf3_kernel<G, false, MINW>), grid, blk, 0, st, a, sp);
-}
-static inline void launch_act_bf3_as(int geo, const ActArgs &a, hipStream_t st) {
-    if (geo == 8)      launch_act_bf3_geo<GeoGrad8, 1>(a, st);
-    else if (geo == 2) launch_act_bf3_geo<GeoBf3S, 2>(a, st);
-    else               launch_act_bf3_geo<GeoAct, 1>(a, st);
-}
-
-// ---- act_kernel geometry choice ---------------------------------------------------------
-// Four geometries compute bit-identical results (tests run all of them); which one is fastest
-// depends on how the output tiles fill the 256 CUs and on the K length, and did not follow a
-// simple rule in measurements (784x1024x512: 8-wave; AIS 20000 chains and 3072x5000: 32x32
-// tiles with BK = 32, four workgroups per CU; DBM 784-512-1024 mean-field: 64x32).  So the
-// launcher measures, ONCE per distinct shape and process, SYNCHRONOUSLY at the first launch of
-// that shape: every candidate runs the caller's contraction on the caller's (read-only)
-// operands with all OUTPUTS redirected to a scratch pool (so the tuning launches have no side
-// effects: no double-counted row accumulators, no early write of a mean-field result), timed
-// with one HIP event pair around TUNE_REP back-to-back launches, best of TUNE_ROUNDS rounds.
-// After that the launch path is one table lookup: no event, no allocation, no synchronisation
-// (round 1 rotated the candidates through the first 12 real launches, which put slower
-// geometries and event markers into short timed runs).  BM355_DEBUG=act_geo=4|8|1|3 forces one
-// geometry (experiments, tests); BM355_DEBUG=tune_log=1 prints the decisions.
-static inline int act_geo_override() {
-    static int v = -1;
-    if (v < 0) { const char *e = bm::dbg("act_geo"); v = e ? atoi(e) : 0; }
-    return v;
-}
-// geo: tile geometry 8 | 4 | 1 | 3, + 100 for register staging of the full chunks (default: LDS-DMA)
-static inline void launch_act_as(int geo, const ActArgs &a, hipStream_t st) {
-    // 208: 8 waves, DMA issued by waves 0-3 only (not a tuner candidate: within noise of 8 on every shape measured)
-    if (geo == 208) { launch_act_geo<GeoAct8, 1, STG_DMAH>(a, st); return; }
-    // 6: 64 x 64 tile, 8 waves of 32 x 16 (the outer-product geometry): half the operand traffic per flop of the
-    // 32 x 64 tile, for outputs large enough to fill the chip with tiles of that size
-    if (geo == 6 && !a.p_xm) { launch_act_geo<GeoGrad8, 1, STG_DMA>(a, st); return; }
-    if (geo == 6) geo = 8;
-    // 9: the 64 x 64 tile with BK = 32: 64 KiB LDS, two workgroups per CU (k-major P only)
-    // (the second template argument is the kernel's waves per SIMD: 2 workgroups x 8 waves / 4 SIMDs)
-    if (geo == 9 && !a.p_xm) { launch_act_geo<GeoGrad8h, 4, STG_DMA>(a, st); return; }
-    if (geo == 9) geo = 8;
-    // 5: 64 x 32 tile with BK = 32, three workgroups per CU (k-major P only)
-    if (geo == 5 && !a.p_xm) { launch_act_geo<GeoAct32, 3, STG_DMA>(a, st); return; }
-    // 7: the same with two workgroups per CU (256 registers per wave: the two-segment variant spills 140 bytes at 168)
-    if (geo == 7 && !a.p_xm) { launch_act_geo<GeoAct32, 2, STG_DMA>(a, st); return; }
-    if (geo == 5 || geo == 7) geo = 3;
-    const bool reg = geo >= 100;
-    geo %= 100;
-    if (a.p_xm && geo == 4) geo = 8;        // x-major P exists for the MI == 1 geometries only
-    if (reg) {
-        if (geo == 8)      launch_act_geo<GeoAct8, 1, STG_REG>(a, st);
-        else if (geo == 1) launch_act_geo<GeoActS, 2, STG_REG>(a, st);
-        else if (geo == 3) launch_act_geo<GeoActS32, 4, STG_REG>(a, st);
-        else               launch_act_geo<GeoAct, 1, STG_REG>(a, st);
-    } else {
-        if (geo == 8)      launch_act_geo<GeoAct8, 1, STG_DMA>(a, st);
-        else if (geo == 1) launch_act_geo<GeoActS, 2, STG_DMA>(a, st);
-        else if (geo == 3) launch_act_geo<GeoActS32, 4, STG_DMA>(a, st);
-        else               launch_act_geo<GeoAct, 1, STG_DMA>(a, st);
-    }
-}
-struct ActTune {
-    static constexpr int NC = 12;
-    int best = 0;
-    int xi = 0;                  // XCD grid of the block -> tile map (TileMap), measured with the chosen geometry
-    float t_us[NC] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-};
-// scratch pool of the tuning launches (per process and device; grown on demand, never on the hot path)
-struct TuneScratch {
-    float *p = nullptr; size_t cap = 0; int dev = -1;
-    float *get(size_t nfloats) {
-        int d = 0; (void)hipGetDevice(&d);
-        if (p && (d != dev || nfloats > cap)) { (void)hipFree(p); p = nullptr; cap = 0; }
-        if (!p) {
-            if (hipMalloc((void **)&p, nfloats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return nullptr; }
-            cap = nfloats; dev = d;
-        }
-        return p;
-    }
-};
-// the caller's launch with every OUTPUT redirected into the scratch pool (false: no memory, keep the default choice)
-static inline bool tune_redirect(const ActArgs &a, ActArgs &t) {
-    static TuneScratch pool;
-    const size_t mat = ((size_t)a.J * (size_t)a.ldo + 3) & ~(size_t)3;
-    const size_t rowv = (((size_t)((a.I + 15) / 16) * (size_t)(a.ld_part > a.J ? a.ld_part : a.J)) + 3) & ~(size_t)3;   // slot partials
-    const size_t sh16 = a.states16 ? ((size_t)a.J * (size_t)a.ld16 / 2 + 4) & ~(size_t)3 : 0;                           // bf16 shadow, in floats
-    const size_t fe = a.fe_flip ? ((size_t)a.J * (size_t)a.fe_rm + 3) & ~(size_t)3 : 0;
-    float *s = pool.get(3 * mat + 2 * rowv + BM_MF_SLOTS + 4 + sh16 + fe);
-    if (!s) return false;
-    t = a;
-    if (a.fe_flip) t.fe_rowacc2 = s + 3 * mat + 2 * rowv + BM_MF_SLOTS + 4 + sh16;
-    t.skip = nullptr;
-    t.chk_ctl = nullptr;
-    if (a.means) t.means = s;
-    if (a.states) t.states = s + mat;
-    if (a.negmeans) t.negmeans = s + 2 * mat;
-    if (a.rowacc) t.rowacc = s + 3 * mat;        // (fe_flip: [J][fe_rm] <= rowv floats: fe_rm >= ceil(I/16), ld_part >= J)
-    if (a.rowdot_out) t.rowdot_out = s + 3 * mat + rowv;
-    if (a.maxdiff_blk) t.maxdiff_blk = s + 3 * mat + 2 * rowv;
-    if (a.maxdiff) t.maxdiff = reinterpret_cast<unsigned *>(s + 3 * mat + 2 * rowv + BM_MF_SLOTS);
-    if (a.states16) t.states16 = reinterpret_cast<uint16_t *>(s + 3 * mat + 2 * rowv + BM_MF_SLOTS + 4);
-#ifdef BM_PROBE
-    t.dbg = nullptr;
-#endif
-    return true;
-}
-static inline void tune_act_shape(const ActArgs &a, hipStream_t st, ActTune &T, long long flags) {
-    static const int cand_geo[ActTune::NC] = {8, 4, 1, 3, 108, 104, 101, 103, 6, 5, 7, 9};
-    constexpr int TUNE_REP = 4, TUNE_ROUNDS = 3;
-    T.best = a.p_xm ? 8 : 4;
-    ActArgs t;
-    if (!tune_redirect(a, t)) return;                // no memory for the scratch outputs: keep the default
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { (void)hipGetLastError(); return; }
-    float best_us[ActTune::NC] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
-    for (int round = 0; round < TUNE_ROUNDS; ++round) {
-        for (int c = 0; c < ActTune::NC; ++c) {
-            if (a.p_xm && (cand_geo[c] % 100 == 4 || cand_geo[c] == 6 || cand_geo[c] == 5 || cand_geo[c] == 7 || cand_geo[c] == 9)) continue;   // not instantiated for an x-major P
-            launch_act_as(cand_geo[c], t, st);                    // warm (instruction cache, clocks)
-            (void)hipEventRecord(e0, st);
-            for (int r = 0; r < TUNE_REP; ++r) launch_act_as(cand_geo[c], t, st);
-            (void)hipEventRecord(e1, st);
-            if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && 1e3f * ms / TUNE_REP < best_us[c]) best_us[c] = 1e3f * ms / TUNE_REP;
-        }
-    }
-    int b = -1;
-    for (int c = 0; c < ActTune::NC; ++c) {
-        T.t_us[c] = best_us[c];
-        if (best_us[c] < 1e29f && (b < 0 || best_us[c] < best_us[b])) b = c;
-    }
-    // run-off: candidates within 3 % of the winner meet it again, alternating, over longer runs (the first pass times
-    // 4 launches per sample; a pick that is wrong by noise costs a whole run 2 - 4 %)
-    if (b >= 0) {
-        constexpr int RUN_REP = 16;
-        int second = -1;
-        for (int c = 0; c < ActTune::NC; ++c)
-            if (c != b && best_us[c] < 1.03f * best_us[b] && (second < 0 || best_us[c] < best_us[second])) second = c;
-        if (second >= 0) {
-            float ro[2] = {1e30f, 1e30f};
-            const int pair[2] = {b, second};
-            for (int round = 0; round < 3; ++round)
-                for (int q = 0; q < 2; ++q) {
-                    launch_act_as(cand_geo[pair[q]], t, st);
-                    (void)hipEventRecord(e0, st);
-                    for (int r = 0; r < RUN_REP; ++r) launch_act_as(cand_geo[pair[q]], t, st);
-                    (void)hipEventRecord(e1, st);
-                    if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-                    float ms = 0.f;
-                    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && 1e3f * ms / RUN_REP < ro[q]) ro[q] = 1e3f * ms / RUN_REP;
-                }
-            if (ro[1] < ro[0]) b = second;
-        }
-    }
-    if (b >= 0) T.best = cand_geo[b];
-    // second dimension: the XCD grid of the block -> tile map, with the chosen geometry (the traffic model's choice is
-    // one of the four; which one is fastest also depends on how the panels fall onto the memory channels)
-    float xi_us[5] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
-    static const int cand_xi[5] = {8, 4, 2, 1, -1};
-    static const bool tune_xi = !(bm::dbg("xcd_map") || (bm::dbg("tune_xcd") && atoi(bm::dbg("tune_xcd")) == 0));
-    T.xi = -1;                                   // the slab order unless a grid is measurably (>= 2 %) faster
-    if (tune_xi) {
-        for (int round = 0; round < TUNE_ROUNDS; ++round)
-            for (int c = 0; c < 5; ++c) {
-                t.map_xi = cand_xi[c];
-                launch_act_as(T.best, t, st);
-                (void)hipEventRecord(e0, st);
-                for (int r = 0; r < TUNE_REP; ++r) launch_act_as(T.best, t, st);
-                (void)hipEventRecord(e1, st);
-                if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && 1e3f * ms / TUNE_REP < xi_us[c]) xi_us[c] = 1e3f * ms / TUNE_REP;
-            }
-        int bx = 0;
-        for (int c = 1; c < 4; ++c) if (xi_us[c] < xi_us[bx]) bx = c;
-        if (xi_us[bx] < 0.98f * xi_us[4]) T.xi = cand_xi[bx];
-    } else T.xi = 0;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    static const bool log = bm::dbg("tune_log") != nullptr;
-    if (log)
-        fprintf(stderr, "bm355 tune: act I=%d J=%d K=%d+%d flags=%lld -> geometry %d (us, dma: 8w %.1f, 64x32 %.1f, 32x32 %.1f, 32x32/bk32 %.1f; "
-                        "reg: 8w %.1f, 64x32 %.1f, 32x32 %.1f, 32x32/bk32 %.1f; 64x64 8w: %.1f; 64x32/bk32 x3: %.1f, x2: %.1f; 64x64/bk32 x2: %.1f)\n",
-                a.I, a.J, a.K1, a.K2, flags, T.best, T.t_us[0] > 1e29f ? -1.f : T.t_us[0], T.t_us[1] > 1e29f ? -1.f : T.t_us[1], T.t_us[2], T.t_us[3],
-                T.t_us[4], T.t_us[5] > 1e29f ? -1.f : T.t_us[5], T.t_us[6], T.t_us[7], T.t_us[8] > 1e29f ? -1.f : T.t_us[8],
-                T.t_us[9] > 1e29f ? -1.f : T.t_us[9], T.t_us[10] > 1e29f ? -1.f : T.t_us[10], T.t_us[11] > 1e29f ? -1.f : T.t_us[11]);
-    if (log && tune_xi)
-        fprintf(stderr, "bm355 tune: act I=%d J=%d K=%d+%d flags=%lld -> tile map %d (-1 slab, else XCD grid xi; us: slab %.1f, 8x1 %.1f, 4x2 %.1f, 2x4 %.1f, 1x8 %.1f)\n",
-                a.I, a.J, a.K1, a.K2, flags, T.xi, xi_us[4], xi_us[0], xi_us[1], xi_us[2], xi_us[3]);
-}
-// fast-binary launches: three tile geometries (2: 64 x 32 tiles, two workgroups per CU; 4: 64 x 64, one; 8: 128 x 32
-// with 8 waves), measured once per shape like the fp32 ones.  Which one wins follows the tile count and K, not one
-// rule: 20000 AIS chains take 2, the 3072 x 256 x 5000 top-down pass of BASELINE configs[2] takes 8 or 2 (68 / 71 us)
-// where 4 needs 117 us (192 tiles on 256 CUs).  BM355_DEBUG=bf3_geo=8|4|2 forces one.
-static inline void launch_act_bf3(const ActArgs &a, hipStream_t st) {
-    static int geo_env = -1;
-    if (geo_env < 0) { const char *e = bm::dbg("bf3_geo"); geo_env = e ? atoi(e) : 0; }
-    if (geo_env) { launch_act_bf3_as(geo_env, a, st); return; }
-    static std::mutex mu;
-    static std::map<std::array<long long, 6>, int> table;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const long long flags = (long long)((a.sample ? 1 : 0) | (a.kind << 1) | (a.rowacc ? 32 : 0) | (a.rowdot_out ? 256 : 0) |
-                                        (a.dot_mat ? 512 : 0) | (a.states ? 1024 : 0) | (a.means ? 2048 : 0));
-    const std::array<long long, 6> key = {a.I, a.J, a.b3.K1, a.b3.K2, flags, (long long)dev};
-    std::lock_guard<std::mutex> lk(mu);
-    int &geo = table[key];
-    if (!geo) {
-        static const int cand[3] = {2, 8, 4};
-        constexpr int TUNE_REP = 4, TUNE_ROUNDS = 3;
-        geo = tile_grid<GeoBf3S>(a.I, a.J) >= 1024 ? 2 : 8;
-        ActArgs t;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (tune_redirect(a, t) && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-            float best[3] = {1e30f, 1e30f, 1e30f};
-            for (int round = 0; round < TUNE_ROUNDS; ++round)
-                for (int c = 0; c < 3; ++c) {
-                    launch_act_bf3_as(cand[c], t, st);
-                    (void)hipEventRecord(e0, st);
-                    for (int r = 0; r < TUNE_REP; ++r) launch_act_bf3_as(cand[c], t, st);
-                    (void)hipEventRecord(e1, st);
-                    if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-                    float ms = 0.f;
-                    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && 1e3f * ms / TUNE_REP < best[c]) best[c] = 1e3f * ms / TUNE_REP;
-                }
-            int b = 0;
-            for (int c = 1; c < 3; ++c) if (best[c] < best[b]) b = c;
-            if (best[b] < 1e29f) geo = cand[b];
-            static const bool log = bm::dbg("tune_log") != nullptr;
-            if (log) fprintf(stderr, "bm355 tune: bf16x3 act I=%d J=%d K=%d+%d flags=%lld -> geometry %d (us: 64x32 %.1f, 128x32 8w %.1f, 64x64 %.1f)\n",
-                             a.I, a.J, a.b3.K1, a.b3.K2, flags, geo, best[0], best[1], best[2]);
-        } else (void)hipGetLastError();
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    launch_act_bf3_as(geo, a, st);
-}
-static inline void launch_act_f32(const ActArgs &a, hipStream_t st);
-static inline void launch_act(const ActArgs &a, hipStream_t st) {
-    if (a.b3.K1 > 0) { launch_act_bf3(a, st); return; }
-    if (a.fe_flip) { launch_act_fe(a, st); return; }     // the h0 pass of a fused metric fetch: its own kernel flavour
-    if (a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init) { launch_act_mf(a, st); return; }   // a mean-field pass: its own flavour
-    if (a.lit && a.kind == 0) { launch_act_lit(a, st); return; }   // literal tf.sigmoid: its own kernel flavour
-    launch_act_f32(a, st);
-    // fast-binary mode, an fp32 launch whose sampled states the NEXT launches read as a bf16 shadow: converted here (the
-    // strip kernel writes its shadow itself; keeping the branch out of the fp32 epilogue is worth ~0.2 us per launch)
-    if (a.states16 && a.states)
-        hipLaunchKernelGGL(shadow16_kernel, dim3(256), dim3(256), 0, st, (const float *)a.states, a.ldo, a.J, a.I, a.states16, a.ld16);
-}
-static inline void launch_act_f32(const ActArgs &a, hipStream_t st) {
-    const int ov = act_geo_override() ? act_geo_override() : a.geo_hint;
-    if (ov) { launch_act_as(ov, a, st); return; }
-    static std::mutex mu;
-    static std::map<std::array<long long, 6>, ActTune> table;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const long long flags = (long long)((a.sample ? 1 : 0) | (a.kind << 1) | (a.prev ? 16 : 0) | (a.rowacc ? 32 : 0) |
-                                        (a.acc_init ? 64 : 0) | (a.p_xm ? 128 : 0) | (a.rowdot_out ? 256 : 0) |
-                                        (a.dot_mat ? 512 : 0) | (a.negmeans ? 1024 : 0));
-    const std::array<long long, 6> key = {a.I, a.J, a.K1, a.K2, flags, (long long)dev};
-    int geo, xi;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        ActTune &T = table[key];
-        if (!T.best) tune_act_shape(a, st, T, flags);
-        geo = T.best; xi = T.xi;
-    }
-    if (xi && !a.map_xi) {
-        ActArgs a2 = a;
-        a2.map_xi = xi;
-        launch_act_as(geo, a2, st);
-        return;
-    }
-    launch_act_as(geo, a, st);
-}
-
-// ---- grad_kernel geometry choice: 4 waves of 32 x 32 or 8 waves of 32 x 16 (bit-identical results), measured
-// once per shape like the act geometries (tune_act_shape), on scratch copies of every buffer the kernel writes.
-// BM355_DEBUG=grad_geo=4|8 forces one.
-template <class G, int STG, int MINB = 1>
-static inline void launch_grad_geo(const GradArgs &g_in, hipStream_t st) {
-    const GradArgs &g = g_in;
-    TileMap tmap;
-    {
-        const double kt = (double)g.Kpos + (double)g.Kneg;
-        tmap = make_tile_map((g.I + G::TI - 1) / G::TI, (g.J + G::TJ - 1) / G::TJ, kt * G::TI * 4.0, kt * G::TJ * 4.0, g.map_xi);
-    }
-    const bool fast = operand_fast(g.Ppos, KM, g.Kpos) && operand_fast(g.Qpos, KM, g.Kpos) &&
-                      operand_fast(g.Pneg, KM, g.Kneg) && operand_fast(g.Qneg, KM, g.Kneg);
-    const dim3 grid(tile_grid<G>(g.I, g.J) + g.nbias), blk(G::NT);
-    if (fast) hipLaunchKernelGGL((grad_kernel<G, true, 0, STG, MINB>), grid, blk, 0, st, g, tmap);
-    else      hipLaunchKernelGGL((grad_kernel<G, false, 0, STG_DMA, MINB>), grid, blk, 0, st, g, tmap);
-}
-// geo: 4 | 8 waves, + 100 for register staging of the full chunks
-static inline void launch_grad_as(int geo, const GradArgs &g, hipStream_t st) {
-    // 9: 8 waves, BK = 32, two workgroups per CU - for outputs of many tiles per CU and a short K (3072 x 5000 x 512:
-    // a tile's fill and read-modify-write epilogue take as long as its K loop)
-    if (geo == 9 && g.nbias == 0) launch_grad_geo<GeoGrad8h, STG_DMA, 4>(g, st);       // 4 waves per SIMD = 2 workgroups per CU
-    else if (geo == 9)   launch_grad_geo<GeoGrad8, STG_DMA>(g, st);
-    else if (geo == 208) launch_grad_geo<GeoGrad8, STG_DMAH>(g, st);
-    else if (geo == 108) launch_grad_geo<GeoGrad8, STG_REG>(g, st);
-    else if (geo == 104) launch_grad_geo<GeoGrad, STG_REG>(g, st);
-    else if (geo == 8)   launch_grad_geo<GeoGrad8, STG_DMA>(g, st);
-    else                 launch_grad_geo<GeoGrad, STG_DMA>(g, st);
-}
-static inline int tune_grad_shape(const GradArgs &g, hipStream_t st) {
-    // the tile workgroups only: scratch W / dW / raw (the update is not idempotent), no bias groups
-    static TuneScratch pool;
-    const size_t mat = (((size_t)g.J * (size_t)g.ldw) + 3) & ~(size_t)3;
-    float *s = pool.get(4 * mat);
-    if (!s) return 4;
-    GradArgs t = g;
-    t.nbias = 0; t.pen = nullptr; t.Wt = nullptr;
-    t.W = s; t.dW = s + mat; t.raw = s + 2 * mat; t.raw2 = s + 3 * mat;
-    (void)hipMemsetAsync(s, 0, 4 * mat * sizeof(float), st);
-#ifdef BM_PROBE
-    t.dbg = nullptr;
-#endif
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { (void)hipGetLastError(); return 4; }
-    constexpr int NC = 5;
-    const int cand[NC] = {4, 8, 104, 108, 9};          // 208 (half-wave DMA) is forceable, never the fastest
-    float best_us[NC] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
-    for (int round = 0; round < 3; ++round)
-        for (int c = 0; c < NC; ++c) {
-            launch_grad_as(cand[c], t, st);
-            (void)hipEventRecord(e0, st);
-            for (int r = 0; r < 4; ++r) launch_grad_as(cand[c], t, st);
-            (void)hipEventRecord(e1, st);
-            if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && 250.f * ms < best_us[c]) best_us[c] = 250.f * ms;
-        }
-    int b = 0;
-    for (int c = 1; c < NC; ++c) if (best_us[c] < best_us[b]) b = c;
-    const int best = cand[b];
-    // the XCD grid of the block -> tile map with that geometry (see tune_act_shape)
-    float xi_us[5] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
-    static const int cand_xi[5] = {8, 4, 2, 1, -1};
-    static const bool tune_xi = !(bm::dbg("xcd_map") || (bm::dbg("tune_xcd") && atoi(bm::dbg("tune_xcd")) == 0));
-    int xi = 9;                                  // 9 = the slab order (map_xi -1), unless a grid is >= 2 % faster
-    if (tune_xi) {
-        for (int round = 0; round < 3; ++round)
-            for (int c = 0; c < 5; ++c) {
-                t.map_xi = cand_xi[c];
-                launch_grad_as(best, t, st);
-                (void)hipEventRecord(e0, st);
-                for (int r = 0; r < 4; ++r) launch_grad_as(best, t, st);
-                (void)hipEventRecord(e1, st);
-                if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && 250.f * ms < xi_us[c]) xi_us[c] = 250.f * ms;
-            }
-        int bx = 0;
-        for (int c = 1; c < 4; ++c) if (xi_us[c] < xi_us[bx]) bx = c;
-        if (xi_us[bx] < 0.98f * xi_us[4]) xi = cand_xi[bx];
-    } else xi = 0;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    static const bool log = bm::dbg("tune_log") != nullptr;
-    if (log)
-        fprintf(stderr, "bm355 tune: grad I=%d J=%d K=%d+%d form=%d fused=%d -> geometry %d (us, dma: 4w %.1f, 8w %.1f; reg: 4w %.1f, 8w %.1f; 8w bk32 x2: %.1f), "
-                        "tile map %d (9 slab, else XCD grid xi; us: slab %.1f, 8x1 %.1f, 4x2 %.1f, 2x4 %.1f, 1x8 %.1f)\n",
-                g.I, g.J, g.Kpos, g.Kneg, g.form, g.fused, best, best_us[0], best_us[1], best_us[2], best_us[3], best_us[4], xi, xi_us[4], xi_us[0], xi_us[1], xi_us[2], xi_us[3]);
-    return best + 1000 * xi;
-}
-static inline void launch_grad(const GradArgs &g_in, hipStream_t st) {
-    static int fetch_env = -1, geo_env = -1;          // BM355_DEBUG=grad_fetch=0|1, BM355_DEBUG=grad_geo=4|8 override (experiments)
-    if (fetch_env < 0) { const char *e = bm::dbg("grad_fetch"); fetch_env = e ? 2 + atoi(e) : 0; }
-    if (geo_env < 0) { const char *e = bm::dbg("grad_geo"); geo_env = e ? atoi(e) : 0; }
-    GradArgs g = g_in;
-    g.fetch_at_fill = fetch_env >= 2 ? fetch_env - 2 : 0;      // measured (same box, 784x1024x512): epilogue 66.6 us/update, fill 67.5
-    int geo = geo_env;
-    if (!geo) {
-        static std::mutex mu;
-        static std::map<std::array<long long, 7>, int> table;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const std::array<long long, 7> key = {g.I, g.J, g.Kpos, g.Kneg, (long long)(g.form | (g.fused << 1)), (long long)g.ldw, (long long)dev};
-        std::lock_guard<std::mutex> lk(mu);
-        int &b = table[key];
-        if (!b) b = tune_grad_shape(g, st);
-        geo = b;
-    }
-    if (geo >= 1000) { if (!g.map_xi) g.map_xi = (geo / 1000 == 9) ? -1 : geo / 1000; geo %= 1000; }
-    launch_grad_as(geo, g, st);
-}
-
-static inline void launch_fe_hidden(const FeArgs &f, hipStream_t st) {
-    const bool fast = operand_fast(f.P, KM, f.K) && operand_fast(f.Q, XM, f.K);
-    const dim3 grid(tile_grid<GeoAct>(f.I, f.J)), blk(NT);
-    if (fast) hipLaunchKernelGGL((fe_hidden_kernel<true>), grid, blk, 0, st, f);
-    else      hipLaunchKernelGGL((fe_hidden_kernel<false>), grid, blk, 0, st, f);
-}
-
 }  // namespace bm
+
+#include "bm_launch.h"      // the host side: launchers and the launch tuner

@@ -1,5 +1,5 @@
 """-m gpu: every act_kernel geometry, deterministically.  The launcher picks a geometry per shape by
-measurement (bm_kernels.h launch_act), so a normal test run exercises whichever wins on that box;
+measurement (bm_launch.h launch_act), so a normal test run exercises whichever wins on that box;
 here each one is forced through BM355_DEBUG=act_geo=<n> (read once per process -> one subprocess per geometry)
 and must reproduce the oracle bit for bit on an RBM update, a DBM update and a mean-field pass."""
 import os
