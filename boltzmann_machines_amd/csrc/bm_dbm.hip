@@ -39,7 +39,7 @@ struct bm_dbm {
     // The fantasy-particle sweeps (PCD) read only the parameters and the particles, the mean-field only the
     // parameters, X and mu: within one update they are independent, so the particle sweeps run on a second stream
     // (fork at the start of the update, join before the gradients) and fill the launch / fill / tail gaps of the
-    // small mean-field kernels.  `cur` is the stream layer_update / gibbs_sweep enqueue on.
+    // small mean-field kernels.  `cur` is the stream issue() / gibbs_sweep enqueue on.
     Stream stream2;
     hipStream_t cur = nullptr;
     Event ev_fork, ev_join;
@@ -114,16 +114,17 @@ struct bm_dbm {
     Mat16 ax16, ax2_16, av16, ah2_16;
     // PCD particles: one shadow per physical buffer (the Mat structs swap, the buffers keep their shadows)
     Mat16 pv16[2], pH16[MAXL][2];
-    const float *pv_key[2] = {nullptr, nullptr}, *pH_key[MAXL][2] = {};
-    // a particle shadow is valid once a launch of the running call has written it (the particles a call starts from
-    // may be non-binary initial values: they are read in fp32)
-    bool pv_ok[2] = {false, false}, pH_ok[MAXL][2] = {};
+    // the one table of shadows: state buffer -> its bf16 image, filled where the images are allocated (the fast AIS set-up,
+    // fast_pcd_begin).  An AIS shadow is always valid; a particle shadow is valid once a launch of the running call has
+    // written it (the particles a call starts from may be non-binary initial values: they are read in fp32)
+    struct Shadow { const float *state = nullptr; const Mat16 *m = nullptr; bool valid = false; };
+    static constexpr int AIS_SHADOWS = 4, SHADOWS = AIS_SHADOWS + 2 * (1 + MAXL);
+    Shadow shadow[SHADOWS];                        // [0, AIS_SHADOWS): AIS states; then per particle buffer set b: v, H_0 ..
+    Shadow &particle_shadow(int b, int layer /* -1 = v */) { return shadow[AIS_SHADOWS + b * (1 + MAXL) + 1 + layer]; }
     uint64_t seed = 0;
     uint32_t call = 0;
     int64_t row0 = 0, prow0 = 0;
 };
-
-static void issue_act(bm_dbm *h, const ActArgs &a) { launch_act(a, h->cur); }
 
 static PhiloxKey dkey(const bm_dbm *h, uint32_t site, int t, uint64_t seed, uint32_t call) {
     PhiloxKey k;
@@ -134,22 +135,14 @@ static PhiloxKey dkey(const bm_dbm *h, uint32_t site, int t, uint64_t seed, uint
 }
 
 // the bf16 shadow of a state matrix of the running fast-binary sweep (null: none)
-static const Mat16 *fast_shadow(bm_dbm *h, const float *p, bool **ok = nullptr) {
-    if (p == h->ao[0][0].p) return &h->ax16;
-    if (p == h->ao[0][1].p) return &h->ax2_16;
-    if (p == h->ae[0].p) return &h->av16;
-    if (p == h->ae[1].p) return &h->ah2_16;
-    for (int b = 0; b < 2; ++b) {
-        if (p && p == h->pv_key[b]) { if (ok) *ok = &h->pv_ok[b]; return &h->pv16[b]; }
-        for (int i = 0; i < h->L; ++i) if (p && p == h->pH_key[i][b]) { if (ok) *ok = &h->pH_ok[i][b]; return &h->pH16[i][b]; }
-    }
+static bm_dbm::Shadow *fast_shadow(bm_dbm *h, const float *p) {
+    if (p) for (bm_dbm::Shadow &s : h->shadow) if (s.state == p) return &s;
     return nullptr;
 }
 // the shadow of an INPUT state matrix: only one whose contents are known to mirror the fp32 matrix
 static const Mat16 *fast_shadow_in(bm_dbm *h, const float *p) {
-    bool *ok = nullptr;
-    const Mat16 *m = fast_shadow(h, p, &ok);
-    return (m && (!ok || *ok)) ? m : nullptr;
+    const bm_dbm::Shadow *s = fast_shadow(h, p);
+    return (s && s->valid) ? s->m : nullptr;
 }
 
 // (re)build the bf16 weight planes from the current parameters (fast-binary mode; cheap next to any sweep), on stream
@@ -177,148 +170,169 @@ static bool dbm_xm() {
     return on;
 }
 
-// one layer update: out = act(mult * (below.W_lo [+ above.W_hi^T]) + bmult * bias)
+// ---- a layer pass as a value (layer_pass() describes it, issue() launches it): out = act(mult * (below.W_lo [+ above.W_hi^T]) + bmult * bias)
 //   below [J][n_lo] (pitch ldb) with W_lo = W[lo] ([n_lo][I]);  above [J][n_hi] with Wt[lo+1] ([n_hi][I])
 struct LayerIn { const float *p; int ld; };
-static void layer_update(bm_dbm *h, int layer /* hidden layer index, -1 = visible */, int J,
-                         LayerIn below, LayerIn above, float mult, float bmult, int sample,
-                         float *means, float *states, int ldo, const PhiloxKey &key, int64_t row0,
-                         const float *prev = nullptr, unsigned *maxdiff = nullptr, ActArgs *extra = nullptr) {
+static constexpr LayerIn NO_IN{nullptr, 0};
+static LayerIn in_of(const Mat &m) { return LayerIn{m.p, m.ld}; }
+// what a pass writes (either pointer may be null) and draws with
+struct LayerOut { int sample; float *means, *states; int ld; PhiloxKey key; int64_t row0; };
+// the layer's value: its sample, or - without sampling - its mean, written as `means` only
+static LayerOut value_out(int sample, float *p, int ld, const PhiloxKey &key, int64_t row0) {
+    return LayerOut{sample, sample ? nullptr : p, sample ? p : nullptr, ld, key, row0};
+}
+static LayerOut mean_out(const bm_dbm *h, float *p, int ld) { return LayerOut{0, p, nullptr, ld, dkey(h, 0, 0, h->seed, h->call), 0}; }
+
+struct LayerPass {
     ActArgs a;
-    if (extra) a = *extra; else memset(&a, 0, sizeof(a));
-    if (layer >= 0) {
-        a.I = h->n[layer + 1];
-        a.P1 = make_operand(h->W[layer].p, h->W[layer].ld, a.I);          // W[layer][k = below][i]
-        a.Q1 = make_operand(below.p, below.ld, J);
-        a.K1 = h->n[layer];
-        if (above.p) {
-            a.P2 = make_operand(h->Wt[layer + 1].p, h->Wt[layer + 1].ld, a.I);   // W[layer+1]^T [k = above][i]
-            a.Q2 = make_operand(above.p, above.ld, J);
-            a.K2 = h->n[layer + 2];
-        } else if (dbm_xm() && (a.K1 & 3) == 0) {
-            a.P1 = make_operand(h->Wt[layer].p, h->Wt[layer].ld, a.I);           // W[layer]^T [i][k = below], x-major
-            a.p_xm = 1;
-        }
-        a.bias = h->hb[layer].p; a.sigma = nullptr; a.kind = BM_UNIT_BERNOULLI;
-    } else {
-        a.I = h->V;
-        a.P1 = make_operand(h->Wt[0].p, h->Wt[0].ld, a.I);               // W[0]^T [k = h0][i = v]
-        a.Q1 = make_operand(above.p, above.ld, J);
-        a.K1 = h->n[1];
-        if (dbm_xm() && (a.K1 & 3) == 0) { a.P1 = make_operand(h->W[0].p, h->W[0].ld, a.I); a.p_xm = 1; }   // W[0] [i = v][k = h0]
+    int layer;                        // hidden layer index, -1 = visible
+    const float *below, *above;       // the state matrices the segments read (fast-binary: their shadows)
+    // ---- optional parts of the request
+    LayerPass &raw() { a.kind = 2; return *this; }                       // the raw pre-activation mult * z (mean-field hoist)
+    // mean-field residual max |out - prev| into the atomic cell and / or the workgroups' slots
+    LayerPass &residual(const float *prev, unsigned *cell, float *slots) { a.prev = prev; a.maxdiff = cell; a.maxdiff_blk = slots; return *this; }
+    LayerPass &skip_if(const int *skip) { a.skip = skip; return *this; }             // device int != 0: the launch returns at once
+    // the first kernel of a sweep evaluates the loop control of the previous sweep from the slots it left
+    LayerPass &check(MfCtl *ctl, const float *slots, int n, float tol) { a.chk_ctl = ctl; a.chk_slots = slots; a.chk_n = n; a.chk_tol = tol; return *this; }
+    // row-reduction epilogues into slot partials of pitch ldp: softplus(beta_b .) - softplus(beta_a .), or softplus(beta_b .)
+    // alone (single); states . vec; z . mat
+    LayerPass &softplus_rows(float *out, int ldp, float beta_a, float beta_b, int single) {
+        a.rowacc = out; a.ld_part = ldp; a.beta_a = beta_a; a.beta_b = beta_b; a.rowacc_single = single;
+        return *this;
+    }
+    LayerPass &statedot_rows(float *out, int ldp, const float *vec) { a.rowdot_out = out; a.ld_part = ldp; a.dot_vec = vec; return *this; }
+    LayerPass &zdot_rows(float *out, int ldp, const Mat &mat) { a.rowacc = out; a.ld_part = ldp; a.dot_mat = mat.p; a.ld_dot = mat.ld; return *this; }
+};
+
+// Operands of a pass with ONE K segment, through W_l - up: below [J][n_l] -> [J][n_{l+1}], down: above [J][n_{l+1}] -> [J][n_l] -
+// x-major where the kernel can read it (dbm_xm above)
+static void single_segment(const bm_dbm *h, ActArgs &a, int l, bool up, LayerIn in) {
+    a.K1 = up ? h->n[l] : h->n[l + 1];
+    a.p_xm = (dbm_xm() && (a.K1 & 3) == 0) ? 1 : 0;
+    const Mat &w = (up != (a.p_xm != 0)) ? h->W[l] : h->Wt[l];           // k-major: W_l (up), W_l^T (down); x-major: the other
+    a.P1 = make_operand(w.p, w.ld, a.I); a.Q1 = make_operand(in.p, in.ld, a.J);
+}
+
+// Describes one layer update; queues nothing, allocates nothing.  `below_sum`: the below segment of the pre-activation is
+// already summed there (the hoisted X.W0 of the mean-field sweeps: continuing the chain from it is bit-identical to
+// recomputing it), only the top-down segment is streamed.
+static LayerPass layer_pass(const bm_dbm *h, int layer, int J, LayerIn below, LayerIn above, float mult, float bmult,
+                            const LayerOut &out, const Mat *below_sum = nullptr) {
+    LayerPass p;
+    ActArgs &a = p.a;
+    memset(&a, 0, sizeof(ActArgs));
+    p.layer = layer; p.below = below_sum ? nullptr : below.p; p.above = above.p;
+    a.J = J; a.I = h->n[layer + 1];
+    if (layer < 0) {
+        single_segment(h, a, 0, false, above);                            // W[0]^T [k = h0][i = v]
         a.bias = h->vb.p; a.sigma = h->sigma.p; a.kind = h->cfg.v_unit;
-    }
-    if (extra && extra->kind == 2) a.kind = 2;     // raw pre-activation requested (mean-field hoist)
-    a.J = J;
-    a.mult = mult; a.bmult = bmult;
-    a.sample = sample;
-    a.means = means; a.states = states; a.ldo = ldo;
-    a.key = key; a.row0 = row0;
-    a.prev = prev; a.maxdiff = maxdiff;
-    a.lit = h->sigmoid_literal;
-    if (h->cur == h->stream2 && h->pcd_geo_now) a.geo_hint = h->pcd_geo_now;   // a pass that runs beside the mean-field loop
-    if (h->fast_now && !h->multinomial(layer) && a.kind != 2) {
-        // fast-binary: the same contraction from the bf16 weight planes and the bf16 shadows of the {0,1} inputs
-        // (a state matrix without a valid shadow - real-valued visibles, the first PCD sweep - keeps the fp32 path)
-        const Mat16 *sb = below.p ? fast_shadow_in(h, below.p) : nullptr;
-        const Mat16 *sa = above.p ? fast_shadow_in(h, above.p) : nullptr;
-        auto opnd = [](const Mat16 &m, int nx) { Bf3Operand o; o.p = m.p; o.plane_stride = m.plane_stride(); o.ld = m.ld; o.nx = nx; return o; };
-        bool ok = false;
-        Bf3Range r;
-        memset(&r, 0, sizeof(r));
-        if (layer >= 0 && sb && (!above.p || sa)) {
-            r.P1 = opnd(h->W3t[layer], a.I); r.Q1 = opnd(*sb, J); r.K1 = sb->ld;          // W_layer^T: [i][k = below]
-            if (above.p) { r.P2 = opnd(h->W3[layer + 1], a.I); r.Q2 = opnd(*sa, J); r.K2 = sa->ld; }   // W_{layer+1}: [i][k = above]
-            ok = true;
-        } else if (layer < 0 && sa) {
-            r.P1 = opnd(h->W3[0], a.I); r.Q1 = opnd(*sa, J); r.K1 = sa->ld;               // W_0: [i = v][k = h0]
-            ok = true;
+    } else {
+        if (below_sum) {
+            a.acc_init = below_sum->p; a.ld_init = below_sum->ld;
+            single_segment(h, a, layer + 1, false, above);                // W[layer+1]^T [k = above][i]
+        } else if (!above.p) {
+            single_segment(h, a, layer, true, below);                     // W[layer][k = below][i]
+        } else {
+            a.P1 = make_operand(h->W[layer].p, h->W[layer].ld, a.I); a.Q1 = make_operand(below.p, below.ld, J); a.K1 = h->n[layer];
+            a.P2 = make_operand(h->Wt[layer + 1].p, h->Wt[layer + 1].ld, a.I); a.Q2 = make_operand(above.p, above.ld, J); a.K2 = h->n[layer + 2];
         }
-        if (ok) a.b3 = r;
-        // the shadow of what this launch writes, when that is a sampled bitmap (written by either path's epilogue)
-        bool *so_ok = nullptr;
-        const Mat16 *so = (states && sample && a.kind == BM_UNIT_BERNOULLI) ? fast_shadow(h, states, &so_ok) : nullptr;
-        if (so) {
-            a.states16 = so->p; a.ld16 = so->ld;
-            if (so_ok) *so_ok = true;
-            // AIS: the fp32 copy of a state matrix that only fast-binary launches read is not written at all (visible /
-            // top-layer states: 145 MB per beta); x keeps it for the x.hb0 partial sums of the epilogue
-            if (ok && h->fast_ais && !a.rowdot_out) a.states = nullptr;
-        }
+        a.bias = h->hb[layer].p; a.kind = BM_UNIT_BERNOULLI;
     }
-    if (h->multinomial(layer) && a.kind != 2) {
-        // MultinomialLayer inside the stack (layers.py:54-70): the GEMM writes the logits mult*z + bmult*b, then one
-        // wave per row does the softmax (activation = n_samples * softmax) and, when sampling, the n_samples
-        // categorical draws (counts); same two kernels as the MultinomialRBM hidden layer (bm_rbm.hip launch_up)
-        float *lg = means; int ldl = ldo;
-        if (!lg) {                                 // sampled sweep: the means are not kept, they pass through a row store
-            if (h->logit_rows[layer] < J) {
-                // (bm_dbm_create preallocates max(N, M) rows: this only grows the store for an unusual row count)
-                if (h->logits[layer].alloc(J, a.I)) { h->failed = true; h->logit_rows[layer] = 0; return; }
-                h->logit_rows[layer] = J;
-            }
-            lg = h->logits[layer].p; ldl = h->logits[layer].ld;
-        }
-        a.kind = 3; a.sample = 0; a.means = lg; a.ldo = ldl; a.states = nullptr; a.negmeans = nullptr;
-        a.prev = nullptr; a.maxdiff = nullptr; a.maxdiff_blk = nullptr;
-        launch_act(a, h->cur);
-        SmArgs m;
-        memset(&m, 0, sizeof(m));
-        m.L = lg; m.ld = ldl; m.ld_states = ldo; m.I = a.I; m.J = J; m.M = h->cfg.n_samples[layer]; m.sample = sample;
-        m.states = (states && (sample || states != lg)) ? states : nullptr;
-        m.key = key; m.row0 = row0;
-        m.prev = prev; m.ld_prev = ldo; m.maxdiff = maxdiff; m.skip = a.skip;
-        hipLaunchKernelGGL(softmax_multinomial_kernel, dim3(J), dim3(64), 2 * (size_t)a.I * sizeof(float), h->cur, m);
-        return;
+    a.mult = mult; a.bmult = bmult; a.lit = h->sigmoid_literal;
+    a.sample = out.sample; a.means = out.means; a.states = out.states; a.ldo = out.ld; a.key = out.key; a.row0 = out.row0;
+    return p;
+}
+
+// fast-binary: the same contraction from the bf16 weight planes and the bf16 shadows of the {0,1} inputs (a state matrix
+// without a valid shadow - real-valued visibles, the first PCD sweep - keeps the fp32 path), and the shadow of the output
+static void fast_substitute(bm_dbm *h, LayerPass &p) {
+    ActArgs &a = p.a;
+    const Mat16 *sb = fast_shadow_in(h, p.below), *sa = fast_shadow_in(h, p.above);
+    auto opnd = [](const Mat16 &m, int nx) { Bf3Operand o; o.p = m.p; o.plane_stride = m.plane_stride(); o.ld = m.ld; o.nx = nx; return o; };
+    bool ok = false;
+    Bf3Range r;
+    memset(&r, 0, sizeof(r));
+    if (p.layer >= 0 && sb && (!p.above || sa)) {
+        r.P1 = opnd(h->W3t[p.layer], a.I); r.Q1 = opnd(*sb, a.J); r.K1 = sb->ld;          // W_layer^T: [i][k = below]
+        if (p.above) { r.P2 = opnd(h->W3[p.layer + 1], a.I); r.Q2 = opnd(*sa, a.J); r.K2 = sa->ld; }   // W_{layer+1}: [i][k = above]
+        ok = true;
+    } else if (p.layer < 0 && sa) {
+        r.P1 = opnd(h->W3[0], a.I); r.Q1 = opnd(*sa, a.J); r.K1 = sa->ld;                 // W_0: [i = v][k = h0]
+        ok = true;
     }
-    issue_act(h, a);
+    if (ok) a.b3 = r;
+    // the shadow of what this launch writes, when that is a sampled bitmap (written by either path's epilogue)
+    bm_dbm::Shadow *so = (a.states && a.sample && a.kind == BM_UNIT_BERNOULLI) ? fast_shadow(h, a.states) : nullptr;
+    if (so) {
+        a.states16 = so->m->p; a.ld16 = so->m->ld;
+        so->valid = true;
+        // AIS: the fp32 copy of a state matrix that only fast-binary launches read is not written at all (visible /
+        // top-layer states: 145 MB per beta); x keeps it for the x.hb0 partial sums of the epilogue
+        if (ok && h->fast_ais && !a.rowdot_out) a.states = nullptr;
+    }
+}
+
+// MultinomialLayer inside the stack (layers.py:54-70): the GEMM writes the logits mult*z + bmult*b, then one
+// wave per row does the softmax (activation = n_samples * softmax) and, when sampling, the n_samples
+// categorical draws (counts); same two kernels as the MultinomialRBM hidden layer (bm_rbm.hip launch_up)
+static void issue_multinomial(bm_dbm *h, ActArgs a, int layer) {
+    float *lg = a.means; int ldl = a.ldo;
+    if (!lg) {                                 // sampled sweep: the means are not kept, they pass through a row store
+        if (h->logit_rows[layer] < a.J) {
+            // (bm_dbm_create preallocates max(N, M) rows: this only grows the store for an unusual row count)
+            if (h->logits[layer].alloc(a.J, a.I)) { h->failed = true; h->logit_rows[layer] = 0; return; }
+            h->logit_rows[layer] = a.J;
+        }
+        lg = h->logits[layer].p; ldl = h->logits[layer].ld;
+    }
+    SmArgs m;
+    memset(&m, 0, sizeof(m));
+    m.L = lg; m.ld = ldl; m.ld_states = a.ldo; m.I = a.I; m.J = a.J; m.M = h->cfg.n_samples[layer]; m.sample = a.sample;
+    m.states = (a.states && (a.sample || a.states != lg)) ? a.states : nullptr;
+    m.key = a.key; m.row0 = a.row0; m.prev = a.prev; m.ld_prev = a.ldo; m.maxdiff = a.maxdiff; m.skip = a.skip;
+    a.kind = 3; a.sample = 0; a.means = lg; a.ldo = ldl; a.states = nullptr; a.negmeans = nullptr;
+    a.prev = nullptr; a.maxdiff = nullptr; a.maxdiff_blk = nullptr;
+    launch_act(a, h->cur);
+    hipLaunchKernelGGL(softmax_multinomial_kernel, dim3(a.J), dim3(64), 2 * (size_t)a.I * sizeof(float), h->cur, m);
+}
+
+// everything that is about launching a pass, on h->cur
+static void issue(bm_dbm *h, LayerPass p) {
+    if (h->cur == h->stream2 && h->pcd_geo_now) p.a.geo_hint = h->pcd_geo_now;   // a pass that runs beside the mean-field loop
+    const bool act = p.a.kind != 2, multinomial = h->multinomial(p.layer);
+    if (h->fast_now && act && !multinomial) fast_substitute(h, p);
+    if (act && multinomial) issue_multinomial(h, p.a, p.layer);
+    else launch_act(p.a, h->cur);
 }
 
 // `_make_gibbs_step` (dbm.py:385-427): bottom-up Gauss-Seidel sweep.
 //   vin / Hin  : current states (Hin[i] may alias mu)      vout / Hout : new states
 //   out_means  : Hout receives means (sample == 0) or samples (per-layer flags)
+// A mean-field sweep (null: a plain one) also leaves its residual against Hin in the atomic cell `maxdiff` and the slots
+// `slots_mine` (null: the cell alone), starts the first layer from the hoisted `xw0` (null: recomputes it), returns at once when
+// `*skip`, and its first kernel evaluates the loop control of the sweep before it from `slots_prev` (null: no check)
+struct MfSweep { unsigned *maxdiff; const Mat *xw0; const int *skip; float *slots_mine; const float *slots_prev; };
 static void gibbs_sweep(bm_dbm *h, int J, LayerIn vin, const Mat *Hin, Mat *vout, Mat *Hout,
-                        bool update_v, bool sample, int t, int64_t row0,
-                        unsigned *maxdiff = nullptr, const Mat *xw0 = nullptr, const int *skip = nullptr,
-                        float *mfblk = nullptr, const float *chk_slots = nullptr) {
+                        bool update_v, bool sample, int t, int64_t row0, const MfSweep *mf = nullptr) {
     const int L = h->L;
     for (int i = 0; i < L; ++i) {
-        LayerIn below = (i == 0) ? vin : LayerIn{Hout[i - 1].p, Hout[i - 1].ld};       // NEW below   :400-402
-        LayerIn above = (i + 1 < L) ? LayerIn{Hin[i + 1].p, Hin[i + 1].ld} : LayerIn{nullptr, 0};   // OLD above
+        const LayerIn below = (i == 0) ? vin : in_of(Hout[i - 1]);                        // NEW below   :400-402
+        const LayerIn above = (i + 1 < L) ? in_of(Hin[i + 1]) : NO_IN;                   // OLD above
         const int smp = sample && h->cfg.sample_h_states[i];
-        ActArgs e;
-        memset(&e, 0, sizeof(e));
-        e.skip = skip;
-        e.maxdiff_blk = (maxdiff && mfblk) ? mfblk + (size_t)i * BM_MF_SLOTS : nullptr;
-        if (i == 0 && chk_slots) {     // the sweep's first kernel evaluates the loop control of the previous sweep
-            e.chk_ctl = h->ctl.p; e.chk_slots = chk_slots; e.chk_n = L * BM_MF_SLOTS; e.chk_tol = h->cfg.mf_tol;
+        const LayerOut out = value_out(smp, Hout[i].p, Hout[i].ld, dkey(h, SITE_DBM_H + i, t, h->seed, h->call), row0);
+        // mean-field: X.W0 is loop invariant - start the chain from the hoisted partial sum
+        const Mat *xw0 = (i == 0 && mf && mf->xw0 && above.p && !h->multinomial(0)) ? mf->xw0 : nullptr;
+        LayerPass p = layer_pass(h, i, J, below, above, 1.f, 1.f, out, xw0);
+        if (mf) {
+            p.residual(Hin[i].p, mf->maxdiff, mf->slots_mine ? mf->slots_mine + (size_t)i * BM_MF_SLOTS : nullptr).skip_if(mf->skip);
+            if (i == 0 && mf->slots_prev) p.check(h->ctl.p, mf->slots_prev, L * BM_MF_SLOTS, h->cfg.mf_tol);
         }
-        if (i == 0 && xw0 && above.p && !h->multinomial(0)) {
-            // mean-field: X.W0 is loop invariant — start the chain from the hoisted partial sum and
-            // stream only the top-down segment (bit-identical to recomputing X.W0 every sweep)
-            e.acc_init = xw0->p; e.ld_init = xw0->ld;
-            e.I = h->n[1]; e.J = J;
-            e.P1 = make_operand(h->Wt[1].p, h->Wt[1].ld, e.I);
-            e.Q1 = make_operand(above.p, above.ld, J);
-            e.K1 = h->n[2];
-            if (dbm_xm() && (e.K1 & 3) == 0) { e.P1 = make_operand(h->W[1].p, h->W[1].ld, e.I); e.p_xm = 1; }   // W[1] [i = h1][k = h2]
-            e.bias = h->hb[0].p; e.kind = BM_UNIT_BERNOULLI;
-            e.mult = 1.f; e.bmult = 1.f; e.sample = 0; e.lit = h->sigmoid_literal;
-            e.means = Hout[0].p; e.ldo = Hout[0].ld;
-            e.prev = maxdiff ? Hin[0].p : nullptr; e.maxdiff = maxdiff;
-            issue_act(h, e);
-            continue;
-        }
-        // without sampling the layer's value is its mean: write it as `means` only
-        layer_update(h, i, J, below, above, 1.f, 1.f, smp, smp ? nullptr : Hout[i].p, smp ? Hout[i].p : nullptr,
-                     Hout[i].ld, dkey(h, SITE_DBM_H + i, t, h->seed, h->call), row0,
-                     maxdiff ? Hin[i].p : nullptr, maxdiff, &e);
+        issue(h, p);
     }
     if (update_v) {                                                                       // :419-425
         const int smp = sample && h->cfg.sample_v_states;
-        layer_update(h, -1, J, LayerIn{nullptr, 0}, LayerIn{Hout[0].p, Hout[0].ld}, 1.f, 1.f, smp,
-                     smp ? nullptr : vout->p, smp ? vout->p : nullptr, vout->ld,
-                     dkey(h, SITE_DBM_V, t, h->seed, h->call), row0);
+        issue(h, layer_pass(h, -1, J, NO_IN, in_of(Hout[0]), 1.f, 1.f,
+                            value_out(smp, vout->p, vout->ld, dkey(h, SITE_DBM_V, t, h->seed, h->call), row0)));
     }
 }
 
@@ -339,14 +353,14 @@ static int read_flag(bm_dbm *h, float *out) {
 // group from a pinned mirror while the next group is already queued.  With the library's communicator
 // installed (bm_dbm_set_comm) the residual is all-reduced (max) on the device, in stream order, per sweep;
 // only the host-callback hook (bm_dbm_set_mf_allreduce) costs a host round trip per sweep.
-// the part of `_make_mf` in front of the loop: approximate-inference init, the hoisted X.W0, the step-0 condition
 static bool mf_self_ctl(const bm_dbm *h) {
-    // Self-controlled sweeps (single GPU, Bernoulli layers, grids that fit the residual slots), see mean_field()
+    // Self-controlled sweeps (single GPU, Bernoulli layers, grids that fit the residual slots), see MfRing
     bool ok = !h->comm && !h->xchg && !h->mf_reduce;
     for (int i = 0; i < h->L; ++i)
         ok = ok && !h->multinomial(i) && ((h->n[i + 1] + 31) / 32) * ((h->N + 31) / 32) <= BM_MF_SLOTS;
     return ok;
 }
+// the part of `_make_mf` in front of the loop: approximate-inference init, the hoisted X.W0, the step-0 condition
 static int mf_prologue(bm_dbm *h, const float *X_dev, bool &hoist) {
     const int L = h->L, N = h->N;
     static const bool fold = !(bm::dbg("mf_fold") && atoi(bm::dbg("mf_fold")) == 0);   // =0: the separate residual kernels (A/B)
@@ -354,40 +368,36 @@ static int mf_prologue(bm_dbm *h, const float *X_dev, bool &hoist) {
     // its tile in its residual slot (or, where there are no slots, in the atomic cell) - the mean-field passes' own epilogue
     // path - instead of two more kernels reading both matrices again
     BM_HIP(hipMemsetAsync(h->flag, 0, sizeof(unsigned), h->stream));
+    // the residual slots of self-controlled sweeps start from zero: in front of the init passes that write them, else behind them
+    const bool self_ctl = mf_self_ctl(h);
+    const size_t slot_bytes = 2 * (size_t)MAXL * BM_MF_SLOTS * sizeof(float);
+    if (self_ctl && fold) BM_HIP(hipMemsetAsync(h->mfblk.p, 0, slot_bytes, h->stream));
     const bool slots = fold && !h->mf_reduce;                  // (the host-callback path reads the atomic cell alone)
-    if (slots && mf_self_ctl(h)) BM_HIP(hipMemsetAsync(h->mfblk.p, 0, 2 * (size_t)MAXL * BM_MF_SLOTS * sizeof(float), h->stream));
     // hoisted loop invariant of the sweeps: z0 = X.W0 (raw chain, no activation)
     hoist = L >= 2 && !h->multinomial(0);
-    if (hoist) {
-        ActArgs e;
-        memset(&e, 0, sizeof(e));
-        e.kind = 2;
-        layer_update(h, 0, N, LayerIn{X_dev, h->V}, LayerIn{nullptr, 0}, 1.f, 1.f, 0, h->xw0.p, nullptr, h->xw0.ld,
-                     dkey(h, 0, 0, h->seed, h->call), 0, nullptr, nullptr, &e);
-    }
+    if (hoist) issue(h, layer_pass(h, 0, N, LayerIn{X_dev, h->V}, NO_IN, 1.f, 1.f, mean_out(h, h->xw0.p, h->xw0.ld)).raw());
     // approximate-inference init into the mu_new VARIABLES (:434-446): doubled bottom-up pass
     for (int i = 0; i < L; ++i) {
-        LayerIn below = (i == 0) ? LayerIn{X_dev, h->V} : LayerIn{h->mu_new[i - 1].p, h->mu_new[i - 1].ld};
+        const LayerIn below = (i == 0) ? LayerIn{X_dev, h->V} : in_of(h->mu_new[i - 1]);
         const float mult = (i == 0 || i < L - 1) ? 2.f : 1.f;
         float *blk = slots ? h->mfblk.p + (size_t)i * BM_MF_SLOTS : nullptr;
         if (i == 0 && hoist && fold) {
             // the first layer's init is the activation of the chain just stored: sigmoid(2 z0 + hb) elementwise, same bits
-            const int nwg = N < 256 ? N : 256;
-            hipLaunchKernelGGL(mf_init0_kernel, dim3(nwg), dim3(256), 0, h->stream, (const float *)h->xw0.p, h->xw0.ld,
+            hipLaunchKernelGGL(mf_init0_kernel, dim3(N < 256 ? N : 256), dim3(256), 0, h->stream, (const float *)h->xw0.p, h->xw0.ld,
                                (const float *)h->hb[0].p, (const float *)h->mu[0].p, h->mu[0].ld, h->mu_new[0].p, h->mu_new[0].ld,
                                N, h->n[1], mult, 1.f, h->sigmoid_literal ? 1 : 0, h->flag, blk);
             continue;
         }
-        ActArgs e;
-        memset(&e, 0, sizeof(e));
-        e.maxdiff_blk = blk;
-        layer_update(h, i, N, below, LayerIn{nullptr, 0}, mult, 1.f, 0, h->mu_new[i].p, nullptr, h->mu_new[i].ld,
-                     dkey(h, 0, 0, h->seed, h->call), 0, fold ? h->mu[i].p : nullptr, fold ? h->flag : nullptr, fold ? &e : nullptr);
+        LayerPass p = layer_pass(h, i, N, below, NO_IN, mult, 1.f, mean_out(h, h->mu_new[i].p, h->mu_new[i].ld));
+        if (fold) p.residual(h->mu[i].p, h->flag, blk);
+        issue(h, p);
     }
-    if (!fold)
+    if (!fold) {
         for (int i = 0; i < L; ++i)
             hipLaunchKernelGGL(maxabsdiff_kernel, dim3(N < 256 ? N : 256), dim3(256), 0, h->stream, (const float *)h->mu[i].p, h->mu[i].ld,
                                (const float *)h->mu_new[i].p, h->mu_new[i].ld, N, h->n[i + 1], h->flag);
+        if (self_ctl) BM_HIP(hipMemsetAsync(h->mfblk.p, 0, slot_bytes, h->stream));
+    }
     return 0;
 }
 
@@ -401,125 +411,125 @@ static int mf_mid(bm_dbm *h, MfMid *m) {
     m->called = true;
     return m->fn(h, m->ctx);
 }
-static int mean_field(bm_dbm *h, const float *X_dev, int *out_n, MfMid *mid = nullptr) {
-    const int L = h->L, N = h->N;
-    constexpr int MF_GROUP = 8;
-    bool hoist = false;
-    BM_TRY(mf_prologue(h, X_dev, hoist));
-    BM_TRY(mf_mid(h, mid));
-    int step = 0;
+
+// loop driver 1, the host-callback hook: a host round trip per sweep.  Returns the executed sweeps in *steps
+static int mf_loop_host(bm_dbm *h, const float *X_dev, bool hoist, int *steps) {
     Mat *cur = h->mu, *alt = h->mu_alt;
-    if (h->mf_reduce) {
-        float diff = 0.f;
+    const MfSweep mf{h->flag, hoist ? &h->xw0 : nullptr, nullptr, nullptr, nullptr};
+    float diff = 0.f;
+    BM_TRY(read_flag(h, &diff));
+    // body (:454-457): mu_new = sweep(X, mu) (values, not the mu_new variables), then swap
+    for (*steps = 0; *steps < h->cfg.max_mf_updates && diff > h->cfg.mf_tol; ++*steps) {
+        BM_HIP(hipMemsetAsync(h->flag, 0, sizeof(unsigned), h->stream));
+        gibbs_sweep(h, h->N, LayerIn{X_dev, h->V}, cur, nullptr, alt, false, false, 0, 0, &mf);
         BM_TRY(read_flag(h, &diff));
-        // body (:454-457): mu_new = sweep(X, mu) (values, not the mu_new variables), then swap
-        while (step < h->cfg.max_mf_updates && diff > h->cfg.mf_tol) {
-            BM_HIP(hipMemsetAsync(h->flag, 0, sizeof(unsigned), h->stream));
-            gibbs_sweep(h, N, LayerIn{X_dev, h->V}, cur, nullptr, alt, false, false, 0, 0, h->flag,
-                        hoist ? &h->xw0 : nullptr);
-            BM_TRY(read_flag(h, &diff));
-            Mat *t = cur; cur = alt; alt = t;
-            ++step;
-        }
-    } else {
-        // loop control of one sweep: local (one kernel) or global (residual all-reduced over the ranks in stream
-        // order: every rank enqueues the same sequence and latches the same `done`, so no host round trip is
-        // needed and the ranks stay in lockstep)
-        auto ctl_step = [&](int init) -> int {
-            if (!h->comm && !h->xchg) {
-                hipLaunchKernelGGL(mf_ctl_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl.p, h->cfg.mf_tol, init,
-                                   h->mfblk.p, h->L * BM_MF_SLOTS);
-                return 0;
-            }
-            if (h->xchg)     // residual -> max over the ranks -> latch in ONE launch (three launches per sweep were 0.4 ms of a
-                             // 1.8 ms data-parallel update at 45 sweeps)
-                return xchg_mf_ctl_step(h->xchg, h->ctl.p, h->mfblk.p, h->L * BM_MF_SLOTS, h->cfg.mf_tol, init, h->stream);
-            hipLaunchKernelGGL(mf_resid_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl.p, h->mfblk.p, h->L * BM_MF_SLOTS);
-            BM_TRY(bm_comm_allreduce_max(h->comm, &h->ctl.p->resid, 1, (void *)h->stream));
-            hipLaunchKernelGGL(mf_latch_kernel, dim3(1), dim3(64), 0, h->stream, h->ctl.p, h->cfg.mf_tol, init);
-            return 0;
-        };
-        // Self-controlled sweeps (single GPU, Bernoulli layers, grids that fit the residual slots): the loop-control
-        // update of sweep s-1 is evaluated by the first kernel of sweep s (ActArgs::chk_ctl) from the slot set of
-        // the other parity; only the LAST sweep of a group needs the one-workgroup control kernel.  Otherwise
-        // (communicator installed, Multinomial layers, > BM_MF_SLOTS workgroups possible) one control step per sweep.
-        const bool self_ctl = mf_self_ctl(h);
-        const size_t set_sz = (size_t)MAXL * BM_MF_SLOTS;
-        {
-            static const bool fold = !(bm::dbg("mf_fold") && atoi(bm::dbg("mf_fold")) == 0);
-            if (self_ctl && !fold) BM_HIP(hipMemsetAsync(h->mfblk.p, 0, 2 * set_sz * sizeof(float), h->stream));   // (else: mf_prologue)
-        }
-        BM_TRY(ctl_step(1));
-        // Groups of sweeps are enqueued without host round trips; the loop-control record is copied to a pinned
-        // mirror after each group and READ ONE GROUP LATE: group g+1 is already in the queue when the host looks at
-        // group g, so the GPU never idles waiting for the host (sweeps enqueued past the end of the loop return at
-        // once).  The first group is as long as the previous call's trip count - for a training run the count
-        // barely moves from one minibatch to the next - so a typical call costs one or two reads.
-        constexpr int R = bm_dbm::MF_RING;
-        int enq = 0, g_enq = 0, g_read = 0;
-        MfCtl host;
-        host.done = 0; host.steps = 0;
-        const int max_it = h->cfg.max_mf_updates;
-        auto enqueue_group = [&](int g) -> int {
-            for (int s = 0; s < g; ++s) {
-                // sweep number enq+s runs only if all before it ran, so its ping-pong parity is static
-                const int sw = enq + s;
-                Mat *src = (sw & 1) ? h->mu_alt : h->mu, *dst = (sw & 1) ? h->mu : h->mu_alt;
-                if (self_ctl) {
-                    float *mine = h->mfblk.p + (size_t)(sw & 1) * set_sz, *prev = h->mfblk.p + (size_t)((sw & 1) ^ 1) * set_sz;
-                    gibbs_sweep(h, N, LayerIn{X_dev, h->V}, src, nullptr, dst, false, false, 0, 0, h->flag,
-                                hoist ? &h->xw0 : nullptr, &h->ctl.p->done, mine, s > 0 ? prev : nullptr);
-                    if (s == g - 1)      // Check(last sweep of the group); it also clears the slots it read
-                        hipLaunchKernelGGL(mf_ctl_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl.p, h->cfg.mf_tol, 0,
-                                           mine, h->L * BM_MF_SLOTS);
-                } else {
-                    gibbs_sweep(h, N, LayerIn{X_dev, h->V}, src, nullptr, dst, false, false, 0, 0, h->flag,
-                                hoist ? &h->xw0 : nullptr, &h->ctl.p->done, h->mfblk.p);
-                    BM_TRY(ctl_step(0));
-                }
-            }
-            enq += g;
-            BM_HIP(hipMemcpyAsync(&h->ctl_host[g_enq % R], h->ctl.p, sizeof(MfCtl), hipMemcpyDeviceToHost, h->stream));
-            BM_HIP(hipEventRecord(h->ctl_ev[g_enq % R], h->stream));
-            ++g_enq;
-            return 0;
-        };
-        if (max_it <= 0) {                 // no sweeps: fetch the step-0 record
-            BM_HIP(hipMemcpyAsync(&h->ctl_host[0], h->ctl.p, sizeof(MfCtl), hipMemcpyDeviceToHost, h->stream));
-            BM_HIP(hipStreamSynchronize(h->stream));
-            host = h->ctl_host[0];
-        }
-        auto read_oldest = [&]() -> int {
-            BM_HIP(hipEventSynchronize(h->ctl_ev[g_read % R]));
-            host = h->ctl_host[g_read % R];
-            ++g_read;
-            return 0;
-        };
-        if (max_it > 0) {
-            // first group: the previous trip count + 1 (a sweep too many costs two kernels that return at once,
-            // a sweep too few costs a host round trip), read before anything else is enqueued
-            int g0 = h->mf_pred > 0 ? h->mf_pred + 1 : MF_GROUP;
-            if (g0 > max_it) g0 = max_it;
-            BM_TRY(enqueue_group(g0));
-            BM_TRY(read_oldest());
-            // not converged yet: short groups, one of them always queued behind the one being read
-            while (!host.done && (enq < max_it || g_read < g_enq)) {
-                while (enq < max_it && g_enq - g_read < 2)
-                    BM_TRY(enqueue_group(max_it - enq < MF_GROUP / 2 ? max_it - enq : MF_GROUP / 2));
-                BM_TRY(read_oldest());
-            }
-            if (g_read < g_enq) {          // groups enqueued past the end of the loop do nothing; free their ring slots
-                BM_HIP(hipEventSynchronize(h->ctl_ev[(g_enq - 1) % R]));
-                g_read = g_enq;
-            }
-        }
-        h->mf_pred = host.steps > 0 ? host.steps : 0;
-        step = host.steps;
-        if (step & 1) { cur = h->mu_alt; alt = h->mu; }
+        std::swap(cur, alt);
     }
-    if (cur != h->mu)                  // `self._mu[i].assign(mu[i])` (:477): keep the handle's mu as the result
-        for (int i = 0; i < L; ++i) std::swap(h->mu[i], h->mu_alt[i]);
-    if (out_n) *out_n = step;
+    return 0;
+}
+
+// loop control of one sweep: local (one kernel) or global (residual all-reduced over the ranks in stream order: every rank
+// enqueues the same sequence and latches the same `done`, so no host round trip is needed and the ranks stay in lockstep)
+typedef int (*MfCtlStep)(bm_dbm *h, int init);
+static int mf_ctl_local(bm_dbm *h, int init) {
+    hipLaunchKernelGGL(mf_ctl_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl.p, h->cfg.mf_tol, init, h->mfblk.p, h->L * BM_MF_SLOTS);
+    return 0;
+}
+static int mf_ctl_xchg(bm_dbm *h, int init) {     // ONE launch (three per sweep were 0.4 ms of a 1.8 ms data-parallel update at 45 sweeps)
+    return xchg_mf_ctl_step(h->xchg, h->ctl.p, h->mfblk.p, h->L * BM_MF_SLOTS, h->cfg.mf_tol, init, h->stream);
+}
+static int mf_ctl_rccl(bm_dbm *h, int init) {
+    hipLaunchKernelGGL(mf_resid_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl.p, h->mfblk.p, h->L * BM_MF_SLOTS);
+    BM_TRY(bm_comm_allreduce_max(h->comm, &h->ctl.p->resid, 1, (void *)h->stream));
+    hipLaunchKernelGGL(mf_latch_kernel, dim3(1), dim3(64), 0, h->stream, h->ctl.p, h->cfg.mf_tol, init);
+    return 0;
+}
+
+// The groups of sweeps in flight: the loop-control record is copied to a pinned mirror after each group and READ ONE GROUP
+// LATE, so the GPU never idles waiting for the host (sweeps enqueued past the end of the loop return at once).
+// Self-controlled sweeps (single GPU, Bernoulli layers, grids that fit the residual slots): the loop-control update of
+// sweep s-1 is evaluated by the first kernel of sweep s (ActArgs::chk_ctl) from the slot set of the other parity; only the
+// LAST sweep of a group needs the one-workgroup control kernel.  Otherwise (communicator installed, Multinomial layers,
+// > BM_MF_SLOTS workgroups possible) one control step per sweep.
+struct MfRing {
+    bm_dbm *h; const float *X_dev; bool hoist, self_ctl; MfCtlStep ctl_step;
+    int enq = 0, g_enq = 0, g_read = 0;       // sweeps enqueued; groups enqueued / read
+    MfCtl host{0, 0, 0, 0.f};                 // the newest record read
+    static constexpr int R = bm_dbm::MF_RING;
+
+    int enqueue_group(int g) {
+        const size_t set_sz = (size_t)MAXL * BM_MF_SLOTS;
+        for (int s = 0; s < g; ++s) {
+            // sweep number enq+s runs only if all before it ran, so its ping-pong parity is static
+            const int sw = enq + s;
+            Mat *src = (sw & 1) ? h->mu_alt : h->mu, *dst = (sw & 1) ? h->mu : h->mu_alt;
+            MfSweep mf{h->flag, hoist ? &h->xw0 : nullptr, &h->ctl.p->done, h->mfblk.p, nullptr};
+            if (self_ctl) {
+                mf.slots_mine = h->mfblk.p + (size_t)(sw & 1) * set_sz;
+                if (s > 0) mf.slots_prev = h->mfblk.p + (size_t)((sw & 1) ^ 1) * set_sz;
+            }
+            gibbs_sweep(h, h->N, LayerIn{X_dev, h->V}, src, nullptr, dst, false, false, 0, 0, &mf);
+            if (!self_ctl) BM_TRY(ctl_step(h, 0));
+            else if (s == g - 1)      // Check(last sweep of the group); it also clears the slots it read
+                hipLaunchKernelGGL(mf_ctl_kernel, dim3(1), dim3(256), 0, h->stream, h->ctl.p, h->cfg.mf_tol, 0,
+                                   mf.slots_mine, h->L * BM_MF_SLOTS);
+        }
+        enq += g;
+        BM_HIP(hipMemcpyAsync(&h->ctl_host[g_enq % R], h->ctl.p, sizeof(MfCtl), hipMemcpyDeviceToHost, h->stream));
+        BM_HIP(hipEventRecord(h->ctl_ev[g_enq % R], h->stream));
+        ++g_enq;
+        return 0;
+    }
+    int read_oldest() {
+        BM_HIP(hipEventSynchronize(h->ctl_ev[g_read % R]));
+        host = h->ctl_host[g_read++ % R];
+        return 0;
+    }
+    int drain() {                      // groups enqueued past the end of the loop do nothing; free their ring slots
+        if (g_read < g_enq) BM_HIP(hipEventSynchronize(h->ctl_ev[(g_enq - 1) % R]));
+        g_read = g_enq;
+        return 0;
+    }
+};
+
+// loop driver 2, device-controlled: the first group is as long as the previous call's trip count - for a training run the
+// count barely moves from one minibatch to the next - so a typical call costs one or two reads
+static int mf_loop_device(bm_dbm *h, const float *X_dev, bool hoist, int *steps) {
+    constexpr int MF_GROUP = 8;
+    MfRing ring{h, X_dev, hoist, mf_self_ctl(h), h->xchg ? mf_ctl_xchg : h->comm ? mf_ctl_rccl : mf_ctl_local};
+    BM_TRY(ring.ctl_step(h, 1));
+    const int max_it = h->cfg.max_mf_updates;
+    if (max_it <= 0) {                 // no sweeps: fetch the step-0 record
+        BM_HIP(hipMemcpyAsync(&h->ctl_host[0], h->ctl.p, sizeof(MfCtl), hipMemcpyDeviceToHost, h->stream));
+        BM_HIP(hipStreamSynchronize(h->stream));
+        ring.host = h->ctl_host[0];
+    } else {
+        // first group: the previous trip count + 1 (a sweep too many costs two kernels that return at once,
+        // a sweep too few costs a host round trip), read before anything else is enqueued
+        BM_TRY(ring.enqueue_group(std::min(max_it, h->mf_pred > 0 ? h->mf_pred + 1 : MF_GROUP)));
+        BM_TRY(ring.read_oldest());
+        // not converged yet: short groups, one of them always queued behind the one being read
+        while (!ring.host.done && (ring.enq < max_it || ring.g_read < ring.g_enq)) {
+            while (ring.enq < max_it && ring.g_enq - ring.g_read < 2)
+                BM_TRY(ring.enqueue_group(std::min(max_it - ring.enq, MF_GROUP / 2)));
+            BM_TRY(ring.read_oldest());
+        }
+        BM_TRY(ring.drain());
+    }
+    h->mf_pred = ring.host.steps > 0 ? ring.host.steps : 0;
+    *steps = ring.host.steps;
+    return 0;
+}
+
+static int mean_field(bm_dbm *h, const float *X_dev, int *out_n, MfMid *mid = nullptr) {
+    bool hoist = false;
+    int steps = 0;                     // executed sweeps
+    BM_TRY(mf_prologue(h, X_dev, hoist));                                                  // in front of the loop
+    BM_TRY(mf_mid(h, mid));                                                                // work for the second stream
+    BM_TRY((h->mf_reduce ? mf_loop_host : mf_loop_device)(h, X_dev, hoist, &steps));       // the loop, by its driver
+    if (steps & 1)                     // `self._mu[i].assign(mu[i])` (:477): keep the handle's mu as the result
+        for (int i = 0; i < h->L; ++i) std::swap(h->mu[i], h->mu_alt[i]);
+    if (out_n) *out_n = steps;
     return 0;
 }
 
@@ -534,33 +544,34 @@ static bool fast_pcd_ok(const bm_dbm *h, bool sample) {
     for (int i = 0; i < h->L; ++i) if (h->multinomial(i) || !h->cfg.sample_h_states[i]) return false;
     return true;
 }
+// fast_now lasts as long as the sweeps of one call (AIS run, particle update)
+struct FastScope { bm_dbm *h; ~FastScope() { h->fast_now = false; } void begin(bool ais) { h->fast_now = true; h->fast_ais = ais; } };
 static int fast_pcd_begin(bm_dbm *h) {
     const bool vbits = h->cfg.v_unit == BM_UNIT_BERNOULLI && h->cfg.sample_v_states;
-    if (!h->pH_key[0][0]) {                       // one shadow per physical particle buffer (keyed once all exist)
+    if (!h->particle_shadow(0, 0).state) {        // one shadow per physical particle buffer (entered once all exist)
         for (int b = 0; b < 2; ++b) {
             if (vbits) BM_TRY(h->pv16[b].alloc(1, h->M, h->V));
             for (int i = 0; i < h->L; ++i) BM_TRY(h->pH16[i][b].alloc(1, h->M, h->n[i + 1]));
         }
         for (int b = 0; b < 2; ++b) {
-            if (vbits) h->pv_key[b] = (b ? h->v_new : h->v).p;
-            for (int i = 0; i < h->L; ++i) h->pH_key[i][b] = (b ? h->H_new[i] : h->H[i]).p;
+            if (vbits) h->particle_shadow(b, -1) = {(b ? h->v_new : h->v).p, &h->pv16[b], false};
+            for (int i = 0; i < h->L; ++i) h->particle_shadow(b, i) = {(b ? h->H_new[i] : h->H[i]).p, &h->pH16[i][b], false};
         }
     }
-    for (int b = 0; b < 2; ++b) { h->pv_ok[b] = false; for (int i = 0; i < h->L; ++i) h->pH_ok[i][b] = false; }
+    for (int s = bm_dbm::AIS_SHADOWS; s < bm_dbm::SHADOWS; ++s) h->shadow[s].valid = false;
     return fast_build_planes(h, h->cur, !vbits);  // the parameters changed since the last update
 }
 
-static void particles_update(bm_dbm *h, int k, bool sample, bool update_only_v_at_end = false) {
-    (void)update_only_v_at_end;
-    struct FastScope { bm_dbm *h; bool on; ~FastScope() { if (on) h->fast_now = false; } } scope{h, false};
+static void particles_update(bm_dbm *h, int k, bool sample) {
+    FastScope scope{h};
     if (fast_pcd_ok(h, sample)) {
-        if (fast_pcd_begin(h) == 0) { scope.on = true; h->fast_now = true; h->fast_ais = false; }
+        if (fast_pcd_begin(h) == 0) scope.begin(false);
         else h->failed = true;
     }
     for (int t = 0; t < k; ++t) {
         // (fast-binary: sweep 0 reads the particles it starts from in fp32 and leaves shadows of what it samples; from
         // then on every sampled Bernoulli input is a bitmap with a valid shadow)
-        gibbs_sweep(h, h->M, LayerIn{h->v.p, h->v.ld}, h->H, &h->v_new, h->H_new, true, sample, t, h->prow0);
+        gibbs_sweep(h, h->M, in_of(h->v), h->H, &h->v_new, h->H_new, true, sample, t, h->prow0);
         std::swap(h->v, h->v_new);                                        // swap particles (:493)
         for (int i = 0; i < h->L; ++i) std::swap(h->H[i], h->H_new[i]);
     }
@@ -743,12 +754,11 @@ static int apply_update(bm_dbm *h, const float *X_dev, float lr, float mom) {
 
 // reconstruction sigma(mu0 W0^T + vb) (dbm.py:625-628) into R (pitch ldr)
 static void reconstruct_from_mu(bm_dbm *h, float *R, int ldr) {
-    layer_update(h, -1, h->N, LayerIn{nullptr, 0}, LayerIn{h->mu[0].p, h->mu[0].ld}, 1.f, 1.f, 0, R, nullptr, ldr,
-                 dkey(h, 0, 0, h->seed, h->call), 0);
+    issue(h, layer_pass(h, -1, h->N, NO_IN, in_of(h->mu[0]), 1.f, 1.f, mean_out(h, R, ldr)));
 }
 
 // AIS at any depth (dbm.py:650-736 for L = 2, extended): the odd-depth layers are the chain x, the even-depth layers are
-// conditionally independent given x and summed out analytically.  `ev`: layer_update index of the even-depth layers in
+// conditionally independent given x and summed out analytically.  `ev`: layer_pass index of the even-depth layers in
 // ascending depth (-1 = v, then hidden 1, 3); `od`: hidden index of the odd-depth layers (0, 2)
 struct AisLayers { int ne, no; int ev[3]; int od[2]; };
 static AisLayers ais_layers(const bm_dbm *h) {
@@ -1113,11 +1123,11 @@ int bm_dbm_sample_v(bm_dbm *h, int32_t k, float *V_dev) {
         for (int b = 0; b < 2; ++b) for (int i = 0; i < h->L; ++i) BM_TRY(h->sv_H[b][i].alloc(h->M, h->n[i + 1]));
         BM_TRY(h->sv_v[0].alloc(h->M, h->V)); BM_TRY(h->sv_v[1].alloc(h->M, h->V));
     }
-    const Mat *Hin = h->H; LayerIn vin{h->v.p, h->v.ld};
+    const Mat *Hin = h->H; LayerIn vin = in_of(h->v);
     Mat *Hout = h->sv_H[0], *Hout2 = h->sv_H[1]; Mat *vout = &h->sv_v[0], *vout2 = &h->sv_v[1];
     for (int t = 0; t < k; ++t) {
         gibbs_sweep(h, h->M, vin, Hin, vout, Hout, true, false, k + t, h->prow0);
-        vin = LayerIn{vout->p, vout->ld}; Hin = Hout;
+        vin = in_of(*vout); Hin = Hout;
         Mat *x = Hout; Hout = Hout2; Hout2 = x;
         Mat *y = vout; vout = vout2; vout2 = y;
     }
@@ -1270,7 +1280,7 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
                            dkey(h, SITE_AIS_X0, o, seed, 0), (unsigned long long)chain0);
     // fast-binary mode: every state of the run is a {0,1} bitmap when all three layers are sampled (the default).
     // 2-layer DBMs only: at other depths the run takes the fp32 path (bm355.h)
-    struct FastScope { bm_dbm *h; ~FastScope() { h->fast_now = false; } } fast_scope{h};
+    FastScope fast_scope{h};
     if (h->fast && h->L == 2 && h->cfg.sample_v_states && h->cfg.sample_h_states[0] && h->cfg.sample_h_states[1]) {
         const int H2 = h->n[2];
         BM_TRY(fast_build_planes(h));
@@ -1278,8 +1288,11 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
             BM_TRY(h->ax16.alloc(1, h->ais_rows, H1)); BM_TRY(h->ax2_16.alloc(1, h->ais_rows, H1));
             BM_TRY(h->av16.alloc(1, h->ais_rows, V)); BM_TRY(h->ah2_16.alloc(1, h->ais_rows, H2));
         }
+        // (entered on every run: ensure_ais may have moved the state matrices since the last one)
+        h->shadow[0] = {h->ao[0][0].p, &h->ax16, true}; h->shadow[1] = {h->ao[0][1].p, &h->ax2_16, true};
+        h->shadow[2] = {h->ae[0].p, &h->av16, true};    h->shadow[3] = {h->ae[1].p, &h->ah2_16, true};
         hipLaunchKernelGGL(shadow16_kernel, dim3(512), dim3(256), 0, h->stream, (const float *)x[0]->p, x[0]->ld, R, H1, h->ax16.p, h->ax16.ld);
-        h->fast_now = true; h->fast_ais = true;
+        fast_scope.begin(true);
     }
     for (int o = 0; o < S.no; ++o)
         hipLaunchKernelGGL(rowdot_kernel, dim3((R + 3) / 4), dim3(256), 0, h->stream, (const float *)x[o]->p, x[o]->ld, R,
@@ -1289,11 +1302,10 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
     // layer the even-depth states (its neighbours in depth; the top layer has no `above`)
     auto state_of = [&](int hidden) -> LayerIn {                          // state of hidden layer `hidden` (-1: v)
         const int d = hidden + 1;
-        if (d & 1) { const Mat *m = x[d >> 1]; return LayerIn{m->p, m->ld}; }
-        return LayerIn{h->ae[d >> 1].p, h->ae[d >> 1].ld};
+        return in_of((d & 1) ? *x[d >> 1] : h->ae[d >> 1]);
     };
-    auto below_of = [&](int li) { return li < 0 ? LayerIn{nullptr, 0} : state_of(li - 1); };
-    auto above_of = [&](int li) { return li + 1 < h->L ? state_of(li + 1) : LayerIn{nullptr, 0}; };
+    auto below_of = [&](int li) { return li < 0 ? NO_IN : state_of(li - 1); };
+    auto above_of = [&](int li) { return li + 1 < h->L ? state_of(li + 1) : NO_IN; };
     auto site_of = [](int li) -> uint32_t { return li < 0 ? SITE_DBM_V : SITE_DBM_H + (uint32_t)li; };
     auto width_of = [&](int li) { return li < 0 ? V : h->n[li + 1]; };
     auto score_args = [&]() {
@@ -1313,11 +1325,9 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
     auto score_only = [&](float bscore, int sign) -> int {
         for (int e = 0; e < S.ne; ++e) {
             const int li = S.ev[e];
-            ActArgs a;
-            memset(&a, 0, sizeof(a));
-            a.rowacc = h->apart_e[e].p; a.ld_part = ldp; a.beta_b = bscore; a.rowacc_single = 1;
-            layer_update(h, li, R, below_of(li), above_of(li), bscore, bscore, 0, nullptr, nullptr, h->ae[e].ld,
-                         dkey(h, site_of(li), 0, seed, 0), chain0, nullptr, nullptr, &a);
+            const LayerOut none{0, nullptr, nullptr, h->ae[e].ld, dkey(h, site_of(li), 0, seed, 0), chain0};
+            issue(h, layer_pass(h, li, R, below_of(li), above_of(li), bscore, bscore, none)
+                         .softplus_rows(h->apart_e[e].p, ldp, 0.f, bscore, 1));
         }
         hipLaunchKernelGGL(ais_score_literal_kernel, dim3((R + 255) / 256), dim3(256), 0, h->stream, h->alogw.p, R, ldp,
                            score_args(), bscore, sign);
@@ -1335,14 +1345,11 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
             // ... - and each layer's softplus term of log p*
             for (int e = 0; e < S.ne; ++e) {
                 const int li = S.ev[e];
-                ActArgs a;
-                memset(&a, 0, sizeof(a));
-                if (sc) { a.rowacc = h->apart_e[e].p; a.ld_part = ldp; a.beta_a = ba; a.beta_b = bb; }
                 const int smp = transit && (li < 0 ? h->cfg.sample_v_states : h->cfg.sample_h_states[li]);
-                float *out = h->ae[e].p;
-                layer_update(h, li, R, below_of(li), above_of(li), bc, bc, smp,
-                             (transit && !smp) ? out : nullptr, (transit && smp) ? out : nullptr, h->ae[e].ld,
-                             dkey(h, site_of(li), t, seed, step), chain0, nullptr, nullptr, &a);
+                LayerPass p = layer_pass(h, li, R, below_of(li), above_of(li), bc, bc,
+                                         value_out(smp, transit ? h->ae[e].p : nullptr, h->ae[e].ld, dkey(h, site_of(li), t, seed, step), chain0));
+                if (sc) p.softplus_rows(h->apart_e[e].p, ldp, ba, bb, 0);
+                issue(h, p);
             }
             if (sc)     // the softplus terms + (bb - ba) * x.hb, slots in fixed order, into the double log-weights
                 hipLaunchKernelGGL(ais_score_kernel, dim3((R + 31) / 32), dim3(256), 0, h->stream, h->alogw.p, R, ldp,
@@ -1352,12 +1359,8 @@ static int ais_core(bm_dbm *h, int32_t n_betas, int32_t n_runs, int32_t k, uint6
             // x^.hb for the next score
             for (int o = 0; o < S.no; ++o) {
                 const int li = S.od[o];
-                ActArgs a;
-                memset(&a, 0, sizeof(a));
-                a.rowdot_out = rdot_next[o]; a.ld_part = ldp; a.dot_vec = h->hb[li].p;
-                const int smp = h->cfg.sample_h_states[li];
-                layer_update(h, li, R, below_of(li), above_of(li), bc, bc, smp,
-                             nullptr, xn[o]->p, xn[o]->ld, dkey(h, site_of(li), t, seed, step), chain0, nullptr, nullptr, &a);
+                const LayerOut out{h->cfg.sample_h_states[li], nullptr, xn[o]->p, xn[o]->ld, dkey(h, site_of(li), t, seed, step), chain0};
+                issue(h, layer_pass(h, li, R, below_of(li), above_of(li), bc, bc, out).statedot_rows(rdot_next[o], ldp, h->hb[li].p));
             }
             for (int o = 0; o < S.no; ++o) {
                 Mat *tm = x[o]; x[o] = xn[o]; xn[o] = tm;
@@ -1515,12 +1518,8 @@ int bm_dbm_log_proba(bm_dbm *h, const float *X_dev, float *out_host) {
     memset(&m, 0, sizeof(m));
     m.L = h->L;
     for (int l = 0; l < h->L; ++l) {
-        ActArgs e;
-        memset(&e, 0, sizeof(e));
-        e.rowacc = parts[l]->p; e.ld_part = ldp; e.dot_mat = h->mu[l].p; e.ld_dot = h->mu[l].ld;
-        const LayerIn below = l == 0 ? LayerIn{X_dev, h->V} : LayerIn{h->mu[l - 1].p, h->mu[l - 1].ld};
-        layer_update(h, l, h->N, below, LayerIn{nullptr, 0}, 1.f, 1.f, 0, nullptr, nullptr, h->mu[l].ld,
-                     dkey(h, 0, 0, h->seed, h->call), 0, nullptr, nullptr, &e);
+        const LayerIn below = l == 0 ? LayerIn{X_dev, h->V} : in_of(h->mu[l - 1]);
+        issue(h, layer_pass(h, l, h->N, below, NO_IN, 1.f, 1.f, mean_out(h, nullptr, h->mu[l].ld)).zdot_rows(parts[l]->p, ldp, h->mu[l]));
         m.mu[l] = h->mu[l].p; m.ld[l] = h->mu[l].ld; m.n[l] = h->n[l + 1]; m.hb[l] = h->hb[l].p;
         m.part[l] = parts[l]->p; m.nslot[l] = nslots(h->n[l + 1]);
     }

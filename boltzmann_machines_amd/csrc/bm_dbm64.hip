@@ -285,26 +285,26 @@ static void ensure_wt(bm_dbm64 *h) {
     h->wt_valid = true;
 }
 
-struct In64 { const double *p; };
+// optional parts of a layer update: the mean-field residual max |out - prev| (atomicMax cell); a unit kind other than the layer's
+struct LayerOpts { const double *prev = nullptr; unsigned long long *maxdiff = nullptr; int kind = -1; };
+static LayerOpts residual_of(const double *prev, unsigned long long *maxdiff) { LayerOpts o; o.prev = prev; o.maxdiff = maxdiff; return o; }
+static LayerOpts as_kind(int kind) { LayerOpts o; o.kind = kind; return o; }
 // layer >= 0: hidden layer `layer` from below (x W_layer) and, optionally, above (x W_{layer+1}^T); -1: visible from h0
 static void layer_update(bm_dbm64 *h, int layer, int J, const double *below, const double *above, double mult, double bmult,
-                         int sample, double *means, double *states, const PhiloxKey &key, int64_t row0,
-                         const double *prev = nullptr, unsigned long long *maxdiff = nullptr, int kind_override = -1) {
+                         int sample, double *means, double *states, const PhiloxKey &key, int64_t row0, const LayerOpts &o = {}) {
     DActArgs a;
     memset(&a, 0, sizeof(a));
     if (layer >= 0) {
-        a.I = h->n[layer + 1];
-        a.P1 = h->W[layer].p; a.ldp1 = a.I; a.Q1 = below; a.K1 = h->n[layer]; a.ldq1 = a.K1;
+        a.I = h->n[layer + 1]; a.P1 = h->W[layer].p; a.ldp1 = a.I; a.Q1 = below; a.K1 = h->n[layer]; a.ldq1 = a.K1;
         if (above) { a.P2 = h->Wt[layer + 1].p; a.ldp2 = a.I; a.Q2 = above; a.K2 = h->n[layer + 2]; a.ldq2 = a.K2; }
         a.bias = h->hb[layer].p; a.sigma = nullptr; a.kind = BM_UNIT_BERNOULLI;
     } else {
-        a.I = h->V;
-        a.P1 = h->Wt[0].p; a.ldp1 = a.I; a.Q1 = above; a.K1 = h->n[1]; a.ldq1 = a.K1;
+        a.I = h->V; a.P1 = h->Wt[0].p; a.ldp1 = a.I; a.Q1 = above; a.K1 = h->n[1]; a.ldq1 = a.K1;
         a.bias = h->vb.p; a.sigma = h->sigma.p; a.kind = h->cfg.v_unit;
     }
-    if (kind_override >= 0) a.kind = kind_override;
+    if (o.kind >= 0) a.kind = o.kind;
     a.J = J; a.mult = mult; a.bmult = bmult; a.sample = sample;
-    a.means = means; a.states = states; a.key = key; a.row0 = row0; a.prev = prev; a.maxdiff = maxdiff;
+    a.means = means; a.states = states; a.key = key; a.row0 = row0; a.prev = o.prev; a.maxdiff = o.maxdiff;
     hipLaunchKernelGGL(dact_kernel, dim3((a.I + T64_TI - 1) / T64_TI, (J + T64_TJ - 1) / T64_TJ), dim3(256), 0, h->stream, a);
 }
 
@@ -316,7 +316,7 @@ static void gibbs_sweep(bm_dbm64 *h, int J, const double *vin, DevArray<double> 
         const double *above = (i + 1 < h->L) ? Hin[i + 1].p : nullptr;
         const int smp = sample && h->cfg.sample_h_states[i];
         layer_update(h, i, J, below, above, 1.0, 1.0, smp, smp ? nullptr : Hout[i].p, smp ? Hout[i].p : nullptr,
-                     dkey64(S_DBM_H + i, t, h->seed, h->call), row0, maxdiff ? Hin[i].p : nullptr, maxdiff);
+                     dkey64(S_DBM_H + i, t, h->seed, h->call), row0, maxdiff ? residual_of(Hin[i].p, maxdiff) : LayerOpts{});
     }
     if (update_v) {
         const int smp = sample && h->cfg.sample_v_states;
@@ -642,7 +642,7 @@ int bm_dbm64_ais(bm_dbm64 *h, int32_t n_betas, int32_t R, int32_t k, uint64_t se
         h->call = step;
         for (int t = 0; t < k; ++t) {
             bm64::layer_update(h, -1, R, nullptr, x->p, beta, beta, h->cfg.sample_v_states, nullptr, h->av.p,
-                               bm64::dkey64(bm64::S_DBM_V, t, seed, step), chain0, nullptr, nullptr, BM_UNIT_BERNOULLI);
+                               bm64::dkey64(bm64::S_DBM_V, t, seed, step), chain0, bm64::as_kind(BM_UNIT_BERNOULLI));
             bm64::layer_update(h, 1, R, x->p, nullptr, beta, beta, h->cfg.sample_h_states[1], nullptr, h->ah2.p,
                                bm64::dkey64(bm64::S_DBM_H + 1, t, seed, step), chain0);
             bm64::layer_update(h, 0, R, h->av.p, h->ah2.p, beta, beta, h->cfg.sample_h_states[0], nullptr, xn->p,
