@@ -137,6 +137,8 @@ SIGNATURES = {
     'bm_rbm_transform': [_vp, _vp, _i32, _i32, _vp],
     'bm_rbm_metrics': [_vp, _vp, _i32, _i32, _fp],
     'bm_rbm_free_energy': [_vp, _vp, _i32, _fp],
+    'bm_rbm_free_energy_rows': [_vp, _vp, _i32, _vp],
+    'bm_rbm_ais': [_vp, _i32, _i32, _i32, _vp, _u64, _i64, _vp],
     'bm_rbm_gibbs': [_vp, _vp, _vp, _i32, _i32],
     'bm_rbm_stream': [_vp, C.POINTER(_vp)],
     'bm_rbm_profile': [_vp, _i32],

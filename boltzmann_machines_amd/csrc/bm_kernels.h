@@ -1891,6 +1891,45 @@ __global__ __launch_bounds__(256) void mf_init0_kernel(const float *Z, int ldz, 
     }
 }
 
+// ------------------------------------------------------------------ AIS scores (bm_dbm_ais, bm_rbm_ais)
+static inline int nslots(int n) { return (n + 15) / 16; }
+
+// the slot partials one AIS score reads: softplus terms of the even-depth layers, x.hb of the odd-depth layers
+struct AisScoreArgs {
+    const float *pe[3]; int ne_slots[3]; int ne;
+    const float *po[2]; int no_slots[2]; int no;
+};
+
+// One AIS score: logw[j] += sum_even sum_slots pe + (beta_b - beta_a) * sum_odd sum_slots po   (dbm.py:650-660)
+// from the slot partials act_kernel left (ActArgs::rowacc / rowdot_out), in double, in a FIXED order: 32 chains per
+// workgroup, 8 thread groups per chain; group t adds the slots q = t, t + 8, ... of each partial array, layers in
+// ascending depth (consecutive threads read consecutive chains: full lines), the 8 group sums are added as a fixed
+// tree.  (Round 2: one thread per chain walked all 113 slots, 79 workgroups for 20 000 chains: 37 us per beta, 4 % of
+// an AIS run.)  Deterministic; sums of <= 113 floats in double are exact to ~1e-16, far below the float the value
+// is finally rounded to.
+__global__ __launch_bounds__(256) void ais_score_kernel(double *logw, int J, int ld, AisScoreArgs p, float dbeta) {
+    __shared__ double s_s[8][32], s_d[8][32];
+    const int c = threadIdx.x & 31, t = threadIdx.x >> 5;
+    const int j = blockIdx.x * 32 + c;
+    double s = 0.0, d = 0.0;
+    if (j < J) {
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+            if (e < p.ne) for (int q = t; q < p.ne_slots[e]; q += 8) s += (double)p.pe[e][(size_t)q * ld + j];
+#pragma unroll
+        for (int o = 0; o < 2; ++o)
+            if (o < p.no) for (int q = t; q < p.no_slots[o]; q += 8) d += (double)p.po[o][(size_t)q * ld + j];
+    }
+    s_s[t][c] = s; s_d[t][c] = d;
+    __syncthreads();
+    if (t == 0 && j < J) {
+        const double ss = ((s_s[0][c] + s_s[1][c]) + (s_s[2][c] + s_s[3][c])) + ((s_s[4][c] + s_s[5][c]) + (s_s[6][c] + s_s[7][c]));
+        const double dd = ((s_d[0][c] + s_d[1][c]) + (s_d[2][c] + s_d[3][c])) + ((s_d[4][c] + s_d[5][c]) + (s_d[6][c] + s_d[7][c]));
+        logw[j] += ss + (double)dbeta * dd;
+    }
+}
+
+
 }  // namespace bm
 
 #include "bm_launch.h"      // the host side: launchers and the launch tuner

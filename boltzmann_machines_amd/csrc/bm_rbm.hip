@@ -25,6 +25,8 @@ void set_error(const char *fmt, ...) {
 
 // RNG site ids (counter word 2 = site + 16 * gibbs_step); DESIGN.md "RNG"
 enum : uint32_t { SITE_DROPOUT = 1, SITE_H0 = 2, SITE_V = 3, SITE_H = 4, SITE_PLL = 5, SITE_FE = 6 };
+// bm_rbm_ais (bm355.h): streams of their own, call = beta step, row offset = global chain index
+enum : uint32_t { SITE_AIS_V0 = 7, SITE_AIS_V = 8, SITE_AIS_H = 9 };
 
 }  // namespace bm
 
@@ -83,6 +85,15 @@ struct bm_rbm {
     bool hm_is_neg = false;    // the last run_chain() wrote -h_k (hneg) instead of h_k (hm)
     bool fe_in_chain = false;  // the last run_chain() left the free-energy slot partials of its input in fe_part (metric fetch)
     DevBuf fe_part;            // [2][ceil(H/16)][maxB]: slot partials of sum softplus for x and for its PLL partner
+    // bm_rbm_ais / bm_rbm_free_energy_rows: workspaces for `ais_rows` chains (rows), allocated on demand - max_batch does not
+    // bound them
+    int ais_rows = 0;
+    Mat av, ah;                        // chain states [ais_rows][V], [ais_rows][H]
+    DevBuf apart_h, apart_v;           // slot partials (ActArgs::rowacc / rowdot_out): [ceil(H/16)][ais_rows], [ceil(V/16)][ais_rows]
+    DevArray<double> alogw;            // [ais_rows] log-weights, accumulated in double in a fixed order
+    DevBuf abase, adot, abeta, atable; // a [V], vb - a [V], beta [n_betas], the mixed biases a + beta_k (vb - a) [n_betas][V]
+    int fer_rows = 0;
+    DevBuf fer_part, fer_out;          // bm_rbm_free_energy_rows: slot partials [ceil(H/16)][fer_rows] of sum softplus, F [fer_rows]
     // fast-binary mode (bm_bf3.h, bm_rbm_set_fast_binary): bf16 planes of W ([V][H]: the prop-down operand) and of
     // W^T ([H][V]: the prop-up operand), bf16 shadows of the state workspaces hs / vs; `fast_now` while a sweep with
     // {0,1} states on both sides runs (bm_rbm_gibbs)
@@ -467,6 +478,116 @@ static void metrics_to_out4(const bm_rbm *h, const double *host, int B, float *o
     out4[1] = (float)h->V * ls;
     out4[2] = h->cfg.l2 * (float)(0.5 * host[1]);               // l2_loss       :483
     out4[3] = (float)fe;                                        // free energy   :516
+}
+
+// ---- AIS log Z of the RBM itself and per-row free energies (bm355.h: bm_rbm_ais, bm_rbm_free_energy_rows)
+
+// dvec = vb - a and the mixed visible biases of every temperature, table[k][i] = a_i + beta_k (vb_i - a_i): one launch in
+// front of the beta loop, so that no pass of the loop waits for the host
+__global__ void rbm_ais_prep_kernel(const float *vb, const float *abase, const float *beta, int n_betas, int V, float *dvec, float *table) {
+    const size_t n = (size_t)n_betas * V;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t k = e / (size_t)V, i = e % (size_t)V;
+        const float d = vb[i] - abase[i];
+        if (k == 0) dvec[i] = d;
+        table[e] = abase[i] + beta[k] * d;
+    }
+}
+
+// v_0 ~ Ber(sigmoid(a)) and the slot partials of v_0.(vb - a) for the first score: the whole dot product in slot 0 (one wave per
+// row, lane-strided sums + butterfly: a fixed order), zeros in the other slots
+__global__ __launch_bounds__(256) void rbm_ais_init_kernel(float *v, int ld, int rows, int V, const float *abase, const float *dvec,
+                                                           PhiloxKey key, unsigned long long row0, float *part, int ld_part, int nslot) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    float s = 0.f;
+    for (int c = lane; c < V; c += 64) {
+        const float x = (philox_uniform_at(key, (row0 + row) * (unsigned long long)V + c) < sigmoid(abase[c])) ? 1.f : 0.f;
+        v[(size_t)row * ld + c] = x;
+        s += x * dvec[c];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) part[row] = s;
+    for (int q = 1 + lane; q < nslot; q += 64) part[(size_t)q * ld_part + row] = 0.f;
+}
+
+// F(x_j) = -x_j.vb - sum_i softplus(z_ji) from the slot partials a prop-up left (ActArgs::rowacc_single), in double: one wave
+// per row, lane-strided sums + butterfly (a fixed order)
+__global__ __launch_bounds__(256) void rbm_fe_rows_kernel(const float *X, int ldx, int rows, int V, const float *vb, const float *part,
+                                                          int ld_part, int nslot, float *out) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    double s = 0.0;
+    for (int c = lane; c < V; c += 64) s += (double)(X[(size_t)row * ldx + c] * vb[c]);
+    for (int q = lane; q < nslot; q += 64) s += (double)part[(size_t)q * ld_part + row];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) out[row] = (float)(-s);
+}
+
+// the two entry points are about the joint p(v, h) of ONE Bernoulli-Bernoulli RBM
+static int check_single_joint(const bm_rbm *h, const char *what) {
+    BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "%s needs Bernoulli visible units (this handle's are Gaussian)", what);
+    BM_CHECK(!h->multinomial(), "%s needs Bernoulli hidden units (this handle's are Multinomial)", what);
+    BM_CHECK(!h->cfg.dbm_first && !h->cfg.dbm_last, "%s: the conditionals of a dbm_first / dbm_last handle (one of them doubled) "
+             "belong to no single joint distribution", what);
+    return 0;
+}
+
+static int ensure_ais_rows(bm_rbm *h, int rows) {
+    if (rows <= h->ais_rows) return 0;
+    h->ais_rows = 0;                               // (set again once every buffer exists: a failure leaves none counted)
+    BM_TRY(h->av.alloc(rows, h->V)); BM_TRY(h->ah.alloc(rows, h->H));
+    BM_TRY(h->apart_h.alloc((size_t)nslots(h->H) * rows)); BM_TRY(h->apart_v.alloc((size_t)nslots(h->V) * rows));
+    BM_TRY(h->alogw.alloc(rows));
+    h->ais_rows = rows;
+    return 0;
+}
+
+static PhiloxKey ais_key(uint64_t seed, uint32_t site, int t, uint32_t step) {
+    PhiloxKey k;
+    k.k0 = (uint32_t)seed; k.k1 = (uint32_t)(seed >> 32);
+    k.site = site + 16u * (uint32_t)t;
+    k.call = step;
+    return k;
+}
+
+// the weights as the prop-up's P operand: W^T x-major where the handle keeps it, else W k-major (launch_up)
+static void up_weights(const bm_rbm *h, ActArgs &a) {
+    if (h->use_wt && h->wt_valid) { a.P1 = make_operand(h->Wt.p, h->Wt.ld, h->H); a.p_xm = 1; }
+    else a.P1 = make_operand(h->W.p, h->W.ld, h->H);
+}
+
+// h ~ Ber(sigmoid(beta z)), z = v W + hb, from the chain state av into ah; score: the same pass leaves the slot partials of
+// sum_j softplus(beta z_j) - softplus(beta_a z_j) in apart_h.  sample = 0: the score alone (the last beta)
+static void ais_up(bm_rbm *h, int R, float beta, int sample, const PhiloxKey &key, int64_t chain0, bool score, float beta_a) {
+    ActArgs a;
+    memset(&a, 0, sizeof(a));
+    up_weights(h, a);
+    a.Q1 = make_operand(h->av.p, h->av.ld, R);
+    a.K1 = h->V; a.I = h->H; a.J = R;
+    a.bias = h->hb.p; a.mult = beta; a.bmult = beta;
+    a.kind = BM_UNIT_BERNOULLI;
+    a.sample = sample; a.states = sample ? h->ah.p : nullptr; a.ldo = h->ah.ld;
+    a.key = key; a.row0 = chain0;
+    if (score) { a.rowacc = h->apart_h.p; a.ld_part = h->ais_rows; a.beta_a = beta_a; a.beta_b = beta; }
+    launch_act(a, h->stream);
+}
+// v ~ Ber(sigmoid(beta h W^T + a + beta (vb - a))) from ah into av, the mixed bias from row `kbeta` of the table; dot: the pass
+// leaves the slot partials of v.(vb - a) in apart_v for the next score
+static void ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &key, int64_t chain0, bool dot) {
+    ActArgs a;
+    memset(&a, 0, sizeof(a));
+    a.P1 = make_operand(h->W.p, h->W.ld, h->V); a.p_xm = 1;
+    a.Q1 = make_operand(h->ah.p, h->ah.ld, R);
+    a.K1 = h->H; a.I = h->V; a.J = R;
+    a.bias = h->atable.p + (size_t)kbeta * h->V; a.mult = beta; a.bmult = 1.0f;
+    a.kind = BM_UNIT_BERNOULLI;
+    a.sample = 1; a.states = h->av.p; a.ldo = h->av.ld;
+    a.key = key; a.row0 = chain0;
+    if (dot) { a.rowdot_out = h->apart_v.p; a.ld_part = h->ais_rows; a.dot_vec = h->adot.p; }
+    launch_act(a, h->stream);
 }
 
 extern "C" {
@@ -954,6 +1075,96 @@ int bm_rbm_free_energy(bm_rbm *h, const float *X_dev, int32_t B, float *out1) {
     BM_HIP(hipStreamSynchronize(h->stream));
     *out1 = (float)(host[2] / B + mn_fe_const(h));
     if (h->multinomial() || dropped) h->call++;   // the random h_hat / the dropout mask consumed one call of the stream
+    return 0;
+}
+
+// Per-row free energies F(x) = -x.vb - sum_j softplus(x W + hb)_j of the RBM's own parameters (no dropout, no multiplier, no
+// change of the RNG call counter): one prop-up that only leaves its softplus slot partials, one row kernel
+int bm_rbm_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, float *out_host) {
+    BM_CHECK(h && X_dev && out_host, "null argument");
+    BM_TRY(check_single_joint(h, "bm_rbm_free_energy_rows"));
+    BM_CHECK(B >= 1, "bad row count %d", (int)B);
+    if (B > h->fer_rows) {
+        h->fer_rows = 0;
+        BM_TRY(h->fer_part.alloc((size_t)nslots(h->H) * B)); BM_TRY(h->fer_out.alloc(B));
+        h->fer_rows = B;
+    }
+    ensure_wt(h);
+    ActArgs a;
+    memset(&a, 0, sizeof(a));
+    up_weights(h, a);
+    a.Q1 = make_operand(X_dev, h->V, B);
+    a.K1 = h->V; a.I = h->H; a.J = B;
+    a.bias = h->hb.p; a.mult = 1.0f; a.bmult = 1.0f;
+    a.kind = BM_UNIT_BERNOULLI;
+    a.ldo = pad_ld(h->H);
+    a.rowacc = h->fer_part.p; a.rowacc_single = 1; a.beta_b = 1.0f; a.ld_part = h->fer_rows;
+    launch_act(a, h->stream);
+    hipLaunchKernelGGL(rbm_fe_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, h->stream, X_dev, h->V, (int)B, h->V, (const float *)h->vb.p,
+                       (const float *)h->fer_part.p, h->fer_rows, nslots(h->H), h->fer_out.p);
+    BM_HIP(hipGetLastError());
+    BM_HIP(hipMemcpyAsync(out_host, h->fer_out.p, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// AIS from the base-rate model p_0(v) ~ exp(a.v) to the RBM, the hidden layer summed out (Salakhutdinov & Murray 2008):
+//   log p*_beta(v) = (1 - beta) a.v + beta vb.v + sum_j softplus(beta z_j),   z = v W + hb,   beta_k = linspace(0, 1, n_betas)[k]
+// Per beta step k: ONE prop-up scores v_{k-1} (softplus differences of (beta_{k-1}, beta_k) as slot partials) and samples h at
+// beta_k from the same pre-activation; the score kernel adds them and (beta_k - beta_{k-1}) v_{k-1}.(vb - a) - the slot partials
+// the prop-down that made v_{k-1} left - to the double log-weights; then the prop-down, and n_gibbs_steps - 1 more up / down
+// pairs.  Between the uploads in front of the loop and the download behind it the host only enqueues.  fp32 path always.
+int bm_rbm_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t k, const float *base_bias_host, uint64_t seed, int64_t chain0,
+               float *values_host) {
+    BM_CHECK(h && values_host, "null argument");
+    BM_TRY(check_single_joint(h, "bm_rbm_ais"));
+    BM_CHECK(n_betas >= 2 && n_runs >= 1 && k >= 1, "bad AIS arguments (n_betas %d >= 2, n_runs %d >= 1, n_gibbs_steps %d >= 1)",
+             (int)n_betas, (int)n_runs, (int)k);
+    const int R = n_runs, V = h->V, H = h->H;
+    BM_TRY(ensure_ais_rows(h, R));
+    if (!h->abase.p) { BM_TRY(h->adot.alloc(V)); BM_TRY(h->abase.alloc(V)); }
+    if (h->atable.n < (size_t)n_betas * V) { BM_TRY(h->abeta.alloc(n_betas)); BM_TRY(h->atable.alloc((size_t)n_betas * V)); }
+    // beta_k as float(np.linspace(0, 1, n_betas)[k]); log Z_0 = H log 2 + sum_i softplus(a_i) in double
+    std::vector<float> beta(n_betas);
+    const double step = 1.0 / (double)(n_betas - 1);
+    for (int b = 0; b < n_betas; ++b) beta[b] = (float)((double)b * step);
+    beta[n_betas - 1] = 1.0f;
+    double logZ0 = (double)H * log(2.0);
+    for (int i = 0; i < V; ++i) {
+        const double ai = base_bias_host ? (double)base_bias_host[i] : 0.0;
+        logZ0 += fmax(ai, 0.0) + log1p(exp(-fabs(ai)));
+    }
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_HIP(hipMemcpy(h->abeta.p, beta.data(), (size_t)n_betas * sizeof(float), hipMemcpyHostToDevice));
+    if (base_bias_host) BM_HIP(hipMemcpy(h->abase.p, base_bias_host, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
+    else BM_HIP(hipMemset(h->abase.p, 0, (size_t)V * sizeof(float)));
+    ensure_wt(h);
+    hipLaunchKernelGGL(rbm_ais_prep_kernel, dim3(512), dim3(256), 0, h->stream, (const float *)h->vb.p, (const float *)h->abase.p,
+                       (const float *)h->abeta.p, (int)n_betas, V, h->adot.p, h->atable.p);
+    BM_HIP(hipMemsetAsync(h->alogw.p, 0, (size_t)R * sizeof(double), h->stream));
+    const int ldp = h->ais_rows;
+    hipLaunchKernelGGL(rbm_ais_init_kernel, dim3((R + 3) / 4), dim3(256), 0, h->stream, h->av.p, h->av.ld, R, V, (const float *)h->abase.p,
+                       (const float *)h->adot.p, ais_key(seed, SITE_AIS_V0, 0, 0), (unsigned long long)chain0, h->apart_v.p, ldp, nslots(V));
+    AisScoreArgs sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.ne = 1; sc.pe[0] = h->apart_h.p; sc.ne_slots[0] = nslots(H);
+    sc.no = 1; sc.po[0] = h->apart_v.p; sc.no_slots[0] = nslots(V);
+    for (int b = 1; b < n_betas; ++b) {
+        const bool last = b == n_betas - 1;            // no transition behind the last score
+        const float ba = beta[b - 1], bb = beta[b];
+        ais_up(h, R, bb, last ? 0 : 1, ais_key(seed, SITE_AIS_H, 0, (uint32_t)b), chain0, true, ba);
+        hipLaunchKernelGGL(ais_score_kernel, dim3((R + 31) / 32), dim3(256), 0, h->stream, h->alogw.p, R, ldp, sc, bb - ba);
+        if (last) break;
+        for (int t = 0; t < k; ++t) {
+            if (t > 0) ais_up(h, R, bb, 1, ais_key(seed, SITE_AIS_H, t, (uint32_t)b), chain0, false, 0.f);
+            ais_down(h, R, bb, b, ais_key(seed, SITE_AIS_V, t, (uint32_t)b), chain0, t == k - 1);
+        }
+    }
+    BM_HIP(hipGetLastError());
+    std::vector<double> w(R);
+    BM_HIP(hipMemcpyAsync(w.data(), h->alogw.p, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    for (int r = 0; r < R; ++r) values_host[r] = (float)(w[r] + logZ0);
     return 0;
 }
 

@@ -159,6 +159,25 @@ class RbmEngine(object):
         check(self.lib.bm_rbm_free_energy(self._h, Xd.offset_ptr(row * self.V), B, C.byref(out)))
         return float(out.value)
 
+    def free_energy_rows(self, Xd, B, row=0):
+        """[B] float32: F(x) of rows [row, row + B) of Xd under the RBM's own parameters (bm_rbm_free_energy_rows)"""
+        out = np.empty(B, dtype=np.float32)
+        check(self.lib.bm_rbm_free_energy_rows(self._h, Xd.offset_ptr(row * self.V), B, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def ais(self, n_betas, n_runs, k, seed, chain0=0, base_bias=None):
+        """[n_runs] float32 per-chain AIS estimates of the RBM's log Z (bm_rbm_ais); base_bias [V]: the bias `a` of the
+        base model p_0(v) ~ exp(a.v), None: the uniform base"""
+        out = np.empty(n_runs, dtype=np.float32)
+        a = None
+        if base_bias is not None:
+            a = np.ascontiguousarray(base_bias, dtype=np.float32)
+            if a.shape != (self.V,):
+                raise ValueError('base_bias has shape %r, expected (%d,)' % (a.shape, self.V))
+        check(self.lib.bm_rbm_ais(self._h, n_betas, n_runs, k, a.ctypes.data_as(C.c_void_p) if a is not None else None,
+                                  int(seed), int(chain0), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def gibbs(self, Hd, Vd, B, n_steps):
         check(self.lib.bm_rbm_gibbs(self._h, Hd.ptr, Vd.ptr, B, n_steps))
 

@@ -12,6 +12,7 @@ BernoulliRBM, MultinomialRBM (rbm.py:25-65) and GaussianRBM (rbm.py:68-116) in f
 """
 import os
 import sys
+from functools import wraps
 
 import numpy as np
 
@@ -19,6 +20,7 @@ from . import _ffi
 from .base import EngineModel, is_attribute_name, run_on_engine
 from .engine import RbmEngine, RbmEngine64
 from .utils import epoch_iter, make_list_from, write_during_training
+from .utils import log_sum_exp, log_mean_exp, log_diff_exp, log_std_exp
 from .utils import philox
 
 
@@ -32,6 +34,16 @@ def assert_len(obj, name, desired_len):
     actual_len = len(getattr(obj, name))
     if actual_len != desired_len:
         raise ValueError('`{0}` has invalid len {1} != {2}'.format(name, actual_len, desired_len))
+
+
+def single_joint_only(f):
+    """`log_Z` / `log_proba` are about the joint p(v, h) of ONE Bernoulli-Bernoulli RBM in float32: every other model is
+    refused before anything is touched (no seed drawn, no engine built)."""
+    @wraps(f)
+    def checked(model, *args, **kwargs):
+        model._check_single_joint(f.__name__)
+        return f(model, *args, **kwargs)
+    return checked
 
 
 class BaseRBM(EngineModel):
@@ -492,6 +504,70 @@ class BaseRBM(EngineModel):
             eng.transform(Xd, min(self.batch_size, N - start), k, Hd, row=start, out_row=start)
         eng.sync()
         return Hd.numpy().astype(np_dtype)
+
+
+    # ---- likelihood (no counterpart in the reference: its only AIS is the DBM's) ----------------
+    def _check_single_joint(self, what):
+        name = '%s.%s' % (self.__class__.__name__, what)
+        if self._V_UNIT != _ffi.UNIT_BERNOULLI:
+            raise NotImplementedError('%s: Gaussian visible units are not supported (Bernoulli visible units only)' % name)
+        if self._H_UNIT != _ffi.UNIT_BERNOULLI:
+            raise NotImplementedError('%s: Multinomial hidden units are not supported (Bernoulli hidden units only)' % name)
+        if np.dtype(self.dtype) != np.float32:
+            raise NotImplementedError("%s: dtype='%s' models are not supported (float32 only)" % (name, np.dtype(self.dtype).name))
+        if self.dbm_first or self.dbm_last:
+            raise NotImplementedError('%s: a dbm_first / dbm_last model doubles one of its conditionals, which then belong to '
+                                      'no single joint distribution' % name)
+
+    def _base_rate_bias(self, X_base):
+        """the bias `a` of the AIS base model p_0(v) ~ exp(a.v): None (uniform), `a` itself [V], or data [N][V] ->
+        logit((sum_n X[n, i] + 1) / (N + 2)) (Laplace smoothing)"""
+        if X_base is None:
+            return None
+        X = np.asarray(X_base, dtype=np.float64)
+        if X.ndim == 2 and X.shape[1] == self.n_visible:
+            p = (X.sum(axis=0) + 1.) / (len(X) + 2.)
+            return (np.log(p) - np.log1p(-p)).astype(np.float32)
+        if X.shape != (self.n_visible,):
+            raise ValueError('`X_base` has invalid shape {0}: expected [N, {1}] or [{1}]'.format(X.shape, self.n_visible))
+        return X.astype(np.float32)
+
+    @single_joint_only
+    @run_on_engine(update_seed=True)
+    def log_Z(self, n_betas=100, n_runs=100, n_gibbs_steps=5, X_base=None):
+        """AIS estimate of the log partition function of this RBM (Salakhutdinov & Murray 2008).
+        Returns log_mean, (log_low, log_high), values - as `DBM.log_Z`.
+
+        `n_runs` chains run from the base model p_0(v) ~ exp(a.v) through `n_betas` temperatures linspace(0, 1, n_betas)
+        with `n_gibbs_steps` transitions each, the hidden layer summed out:
+        log p*_beta(v) = (1 - beta) a.v + beta vb.v + sum_j softplus(beta (vW + hb)_j).
+        X_base : None - the uniform base (a = 0); an [N, n_visible] array - the base rates of that data,
+        a_i = logit((sum_n X[n, i] + 1) / (N + 2)), which makes AIS usable on trained models; an [n_visible] array - `a` itself.
+        Both layers are always sampled, dropout is not applied.  In a multi-GPU job every rank runs all chains."""
+        values = self._on_device().ais(n_betas, n_runs, n_gibbs_steps, seed=self._graph_seed,
+                                       base_bias=self._base_rate_bias(X_base))
+        log_mean = log_mean_exp(values)
+        log_std = log_std_exp(values, log_mean_exp_x=log_mean)
+        log_high = log_sum_exp([log_std, log_mean])
+        log_low = log_diff_exp([log_std, log_mean])[0]
+        return log_mean, (log_low, log_high), values
+
+    @single_joint_only
+    @run_on_engine()
+    def log_proba(self, X, log_Z):
+        """Exact log p(x) = -F(x) - log_Z per row of X, F the free energy -x.vb - sum_j softplus((xW + hb)_j) of the model's
+        own parameters (no dropout); `log_Z` e.g. from `log_Z()`.  Draws nothing: the model's state and seed streams stay
+        as they are."""
+        eng = self._on_device()
+        X = np.ascontiguousarray(X, dtype=eng.dtype)
+        if X.ndim != 2 or X.shape[1] != self.n_visible:
+            raise ValueError('`X` has invalid shape {0}: expected [N, {1}]'.format(X.shape, self.n_visible))
+        Xd = self._to_device(X)
+        F = np.empty(len(X))
+        for start in range(0, len(X), self.batch_size):
+            B = min(self.batch_size, len(X) - start)
+            F[start:start + B] = eng.free_energy_rows(Xd, B, row=start)
+        return -F - log_Z
 
 
 class BernoulliRBM(BaseRBM):

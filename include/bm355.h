@@ -154,6 +154,31 @@ int bm_rbm_metrics(bm_rbm *h, const float *X_dev, int32_t B, int32_t n_gibbs_ste
                    float *out4);
 /* batch-mean free energy only (free_energy_op, base_rbm.py:516-517). */
 int bm_rbm_free_energy(bm_rbm *h, const float *X_dev, int32_t B, float *out1);
+/* Per-row free energies F(x) = -x.vb - sum_j softplus((x W + hb)_j) of X_dev [B, n_visible] into out_host [B]: the
+ * RBM's own parameters, no dropout, no multiplier, no RNG call consumed; B is not bounded by max_batch.  log p(x) =
+ * -F(x) - log Z.  The softplus terms are the slot partials of one prop-up (ActArgs::rowacc_single); a row kernel adds them
+ * and x.vb in double.  Bernoulli-Bernoulli handles without dbm_first / dbm_last only (as bm_rbm_ais). */
+int bm_rbm_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, float *out_host);
+/* AIS estimate of the RBM's OWN log partition function (no counterpart in the reference, whose only AIS is the DBM's;
+ * Salakhutdinov & Murray 2008): n_runs chains from the base-rate model p_0(v) ~ exp(a.v), a = base_bias_host [n_visible]
+ * (NULL: a = 0, the uniform base), through beta_k = linspace(0, 1, n_betas)[k], the hidden layer summed out:
+ *   log p*_beta(v) = (1 - beta) a.v + beta vb.v + sum_j softplus(beta (v W + hb)_j),  log Z_0 = n_hidden log 2 + sum_i softplus(a_i).
+ * v_0 ~ Ber(sigmoid(a)); for k = 1 .. n_betas - 1: logw += log p*_{beta_k}(v_{k-1}) - log p*_{beta_{k-1}}(v_{k-1}), then
+ * n_gibbs_steps transitions h ~ Ber(sigmoid(beta_k (v W + hb))), v ~ Ber(sigmoid(beta_k (h W^T + vb) + (1 - beta_k) a)) - both
+ * layers always sampled, whatever sample_v_states / sample_h_states say; none behind the last score.  values_host [n_runs]
+ * receives logw + log Z_0 per chain (log_mean_exp and the error bars stay with the caller).  No dropout.
+ * The chain workspaces are allocated for n_runs rows on demand: max_batch does not bound the number of chains.
+ * RNG sites (Philox key = seed, counter word site + 16 t with t the Gibbs step, call = beta step k, row offset = chain0 +
+ * row, the global chain index): 7 for v_0 (call 0), 8 for v, 9 for h.  Chains [c, c + n) of a larger run are therefore the
+ * run of n chains at chain0 = c, bit for bit.
+ * The per-beta terms are fp32; their sums over the 16-column slots and over the betas are kept in DOUBLE in a fixed order
+ * (as bm_dbm_ais): the values do not depend on the tile geometry and do not vary from run to run.  Between the upload of
+ * a / the betas and the download of the values the host only enqueues launches: per beta step 2 n_gibbs_steps propagation
+ * launches and one score launch.  Fast-binary mode does not apply: the fp32 path runs, the default's bits.
+ * Refused: Gaussian visible units, Multinomial hidden units, dbm_first / dbm_last handles (their conditionals belong to no
+ * single joint distribution). */
+int bm_rbm_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t n_gibbs_steps, const float *base_bias_host,
+               uint64_t seed, int64_t chain0, float *values_host);
 
 /* Pure block-Gibbs sampling sweep (R5/R6 of SURVEY §8a; base_rbm.py:367-413):
  * n_steps of h->v->h starting from hidden states H_dev [B, n_hidden] (in/out);
