@@ -79,7 +79,9 @@ __device__ __forceinline__ float sigmoid_literal(float x) { return 1.0f / (1.0f 
 // The AIS log-weight epilogue evaluates it twice per output and was VALU-bound on the libm calls
 // (expf + log1pf, ~100 instructions each): exp(-|x|) reuses exp_neg, and log1p(e), e in [0, 1], is
 // 2*atanh(s) with s = e / (2 + e) <= 1/3 as an odd series to s^15 (truncation < 2e-8 relative).
-// Measured against double precision: max relative error 2.5e-7 over [-79, 90] (absolute error < 2e-35 below).
+// Measured against double precision: max relative error 2.5e-7 over [-79, 90] (absolute error < 2e-35 below); on the device,
+// element by element over the probe points of tests/numerics_probes.py: max 2.05 float32 ulp of the exact value (asserted:
+// <= 4, tests/test_epilogue_numerics_gpu.py).
 __device__ __forceinline__ float log1p_unit(float e) {
     const float s = e / (2.0f + e);
     const float t = s * s;
