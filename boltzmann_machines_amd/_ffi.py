@@ -140,6 +140,7 @@ SIGNATURES = {
     'bm_rbm_free_energy_rows': [_vp, _vp, _i32, _vp],
     'bm_rbm_ais': [_vp, _i32, _i32, _i32, _vp, _u64, _i64, _vp],
     'bm_rbm_gibbs': [_vp, _vp, _vp, _i32, _i32],
+    'bm_rbm_gibbs_clamped': [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     'bm_rbm_stream': [_vp, C.POINTER(_vp)],
     'bm_rbm_profile': [_vp, _i32],
     'bm_rbm_kernel_times': [_vp, _fp, _ip],
@@ -168,6 +169,7 @@ SIGNATURES = {
     'bm_dbm_mean_field': [_vp, _vp, _vp, _ip],
     'bm_dbm_reconstruct': [_vp, _vp, _vp],
     'bm_dbm_sample_v': [_vp, _i32, _vp],
+    'bm_dbm_sample_v_clamped': [_vp, _i32, _vp, _vp, _vp],
     'bm_dbm_ais': [_vp, _i32, _i32, _i32, _u64, _i64, _vp],
     'bm_dbm_log_proba': [_vp, _vp, _vp],
     'bm_dbm_timer_start': [_vp],

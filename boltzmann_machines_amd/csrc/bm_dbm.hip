@@ -202,7 +202,11 @@ struct LayerPass {
     }
     LayerPass &statedot_rows(float *out, int ldp, const float *vec) { a.rowdot_out = out; a.ld_part = ldp; a.dot_vec = vec; return *this; }
     LayerPass &zdot_rows(float *out, int ldp, const Mat &mat) { a.rowacc = out; a.ld_part = ldp; a.dot_mat = mat.p; a.ld_dot = mat.ld; return *this; }
+    // conditional sampling: outputs with a non-zero mask entry hold `val` (both [J][I], pitch ld; ActArgs::clamp_mask)
+    LayerPass &clamp(const float *val, const float *mask, int ld) { a.clamp_val = val; a.clamp_mask = mask; a.ld_clamp = ld; return *this; }
 };
+// the clamp of a call's visible-layer passes (null mask: none)
+struct Clamp { const float *val, *mask; int ld; };
 
 // Operands of a pass with ONE K segment, through W_l - up: below [J][n_l] -> [J][n_{l+1}], down: above [J][n_{l+1}] -> [J][n_l] -
 // x-major where the kernel can read it (dbm_xm above)
@@ -300,7 +304,7 @@ static void issue_multinomial(bm_dbm *h, ActArgs a, int layer) {
 static void issue(bm_dbm *h, LayerPass p) {
     if (h->cur == h->stream2 && h->pcd_geo_now) p.a.geo_hint = h->pcd_geo_now;   // a pass that runs beside the mean-field loop
     const bool act = p.a.kind != 2, multinomial = h->multinomial(p.layer);
-    if (h->fast_now && act && !multinomial) fast_substitute(h, p);
+    if (h->fast_now && act && !multinomial && !p.a.clamp_mask) fast_substitute(h, p);      // (a clamped pass is fp32, always)
     if (act && multinomial) issue_multinomial(h, p.a, p.layer);
     else launch_act(p.a, h->cur);
 }
@@ -313,7 +317,7 @@ static void issue(bm_dbm *h, LayerPass p) {
 // `*skip`, and its first kernel evaluates the loop control of the sweep before it from `slots_prev` (null: no check)
 struct MfSweep { unsigned *maxdiff; const Mat *xw0; const int *skip; float *slots_mine; const float *slots_prev; };
 static void gibbs_sweep(bm_dbm *h, int J, LayerIn vin, const Mat *Hin, Mat *vout, Mat *Hout,
-                        bool update_v, bool sample, int t, int64_t row0, const MfSweep *mf = nullptr) {
+                        bool update_v, bool sample, int t, int64_t row0, const MfSweep *mf = nullptr, const Clamp *cl = nullptr) {
     const int L = h->L;
     for (int i = 0; i < L; ++i) {
         const LayerIn below = (i == 0) ? vin : in_of(Hout[i - 1]);                        // NEW below   :400-402
@@ -331,8 +335,10 @@ static void gibbs_sweep(bm_dbm *h, int J, LayerIn vin, const Mat *Hin, Mat *vout
     }
     if (update_v) {                                                                       // :419-425
         const int smp = sample && h->cfg.sample_v_states;
-        issue(h, layer_pass(h, -1, J, NO_IN, in_of(Hout[0]), 1.f, 1.f,
-                            value_out(smp, vout->p, vout->ld, dkey(h, SITE_DBM_V, t, h->seed, h->call), row0)));
+        LayerPass p = layer_pass(h, -1, J, NO_IN, in_of(Hout[0]), 1.f, 1.f,
+                                 value_out(smp, vout->p, vout->ld, dkey(h, SITE_DBM_V, t, h->seed, h->call), row0));
+        if (cl) p.clamp(cl->val, cl->mask, cl->ld);
+        issue(h, p);
     }
 }
 
@@ -562,16 +568,16 @@ static int fast_pcd_begin(bm_dbm *h) {
     return fast_build_planes(h, h->cur, !vbits);  // the parameters changed since the last update
 }
 
-static void particles_update(bm_dbm *h, int k, bool sample) {
+static void particles_update(bm_dbm *h, int k, bool sample, const Clamp *cl = nullptr) {
     FastScope scope{h};
-    if (fast_pcd_ok(h, sample)) {
+    if (!cl && fast_pcd_ok(h, sample)) {           // (clamp values may be grey levels: a clamped call keeps the fp32 path)
         if (fast_pcd_begin(h) == 0) scope.begin(false);
         else h->failed = true;
     }
     for (int t = 0; t < k; ++t) {
         // (fast-binary: sweep 0 reads the particles it starts from in fp32 and leaves shadows of what it samples; from
         // then on every sampled Bernoulli input is a bitmap with a valid shadow)
-        gibbs_sweep(h, h->M, in_of(h->v), h->H, &h->v_new, h->H_new, true, sample, t, h->prow0);
+        gibbs_sweep(h, h->M, in_of(h->v), h->H, &h->v_new, h->H_new, true, sample, t, h->prow0, nullptr, cl);
         std::swap(h->v, h->v_new);                                        // swap particles (:493)
         for (int i = 0; i < h->L; ++i) std::swap(h->H[i], h->H_new[i]);
     }
@@ -1113,9 +1119,11 @@ int bm_dbm_reconstruct(bm_dbm *h, const float *X_dev, float *R_dev) {
     return 0;
 }
 
-int bm_dbm_sample_v(bm_dbm *h, int32_t k, float *V_dev) {
+// cl: the visible units held at observed values (bm_dbm_sample_v_clamped), null: none
+static int sample_v(bm_dbm *h, int32_t k, float *V_dev, const Clamp *cl) {
     BM_CHECK(k >= 0, "n_gibbs_steps must be >= 0");
-    particles_update(h, k, true);                             // :643-644
+    if (cl) hipLaunchKernelGGL(clamp_apply_kernel, dim3(256), dim3(256), 0, h->stream, h->v.p, h->v.ld, cl->val, cl->mask, cl->ld, h->M, h->V);
+    particles_update(h, k, true, cl);                         // :643-644
     // `_make_particles_update(sample=False)` whose v assign is the only one fetched (:646-647):
     // k mean sweeps from the sampled state; only v takes the result, H / *_new keep theirs.
     // scratch: the mu buffers do not fit (M != N); the handle's own, allocated at the first call (sv_v[1] last)
@@ -1126,7 +1134,7 @@ int bm_dbm_sample_v(bm_dbm *h, int32_t k, float *V_dev) {
     const Mat *Hin = h->H; LayerIn vin = in_of(h->v);
     Mat *Hout = h->sv_H[0], *Hout2 = h->sv_H[1]; Mat *vout = &h->sv_v[0], *vout2 = &h->sv_v[1];
     for (int t = 0; t < k; ++t) {
-        gibbs_sweep(h, h->M, vin, Hin, vout, Hout, true, false, k + t, h->prow0);
+        gibbs_sweep(h, h->M, vin, Hin, vout, Hout, true, false, k + t, h->prow0, nullptr, cl);
         vin = in_of(*vout); Hin = Hout;
         Mat *x = Hout; Hout = Hout2; Hout2 = x;
         Mat *y = vout; vout = vout2; vout2 = y;
@@ -1142,6 +1150,18 @@ int bm_dbm_sample_v(bm_dbm *h, int32_t k, float *V_dev) {
     BM_HIP(hipStreamSynchronize(h->stream));
     h->call++;
     return 0;
+}
+int bm_dbm_sample_v(bm_dbm *h, int32_t k, float *V_dev) { return sample_v(h, k, V_dev, nullptr); }
+
+// bm_dbm_sample_v with the visible units of the particles held at observed values where the mask is non-zero (DESIGN.md
+// 3.12): the clamp is applied to the particles' visible layer first, then in the epilogue of EVERY visible-layer pass of the
+// call (LayerPass::clamp; the CL flavour of act_kernel), the mean sweeps included
+int bm_dbm_sample_v_clamped(bm_dbm *h, int32_t k, const float *clamp_val_dev, const float *clamp_mask_dev, float *V_dev) {
+    BM_CHECK(h && clamp_val_dev && clamp_mask_dev, "null argument");
+    for (int i = 0; i < h->L; ++i)
+        BM_CHECK(!h->multinomial(i), "bm_dbm_sample_v_clamped: a Multinomial hidden layer (layer %d) is not supported", i);
+    const Clamp cl{clamp_val_dev, clamp_mask_dev, h->V};
+    return sample_v(h, k, V_dev, &cl);
 }
 
 static int ensure_ais(bm_dbm *h, int rows) {

@@ -99,6 +99,12 @@ struct ActArgs {
     const int *fe_flip;
     const float *fe_x; int fe_ldx;       // the pass's own input rows [J][K] (for x[j][fc])
     const float *fe_w; int fe_ldw;       // W [K][I] row-major (row fc)
+    // Conditional sampling (the CL flavour, act_kernel<..., CL = true>; launch_act_cl): outputs whose mask entry
+    // is non-zero are CLAMPED - mean and state are replaced by clamp_val AFTER the draw (a clamped output's Philox words are
+    // consumed by position like any other's: the free outputs get the bits of an unclamped pass), before the stores and
+    // before the rowdot_out read-back.  Both arrays are [J][I] with the common pitch ld_clamp.  Null mask: off.
+    const float *clamp_val, *clamp_mask;
+    int ld_clamp;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -322,7 +328,7 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // act_kernel's epilogue for the lane's outputs of ONE output tile (i0, j0): activation, draw, stores, the per-row
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
-template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false>
+template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -336,6 +342,31 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
     const float (&sg)[E] = side.sg;
     const typename PhiloxFor<G::MI>::type &rng = side.rng;
 
+    // CL: the clamp values and masks of the lane's outputs, requested HERE - ahead of the sigmoid / Box-Muller arithmetic, which
+    // covers their latency.  One 16-byte load per array and group of 4 where pitch and base allow it, scalar loads at ragged edges
+    float cv[NH][4], cm[NH][4];
+    (void)cv; (void)cm;
+    if constexpr (CL) {
+        const bool al_cl = ((a.ld_clamp & 3) == 0) && (((uintptr_t)a.clamp_val & 15u) == 0) && (((uintptr_t)a.clamp_mask & 15u) == 0);
+#pragma unroll
+        for (int hlf = 0; hlf < NH; ++hlf) {
+            const int ib = ib0 + 4 * hlf;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { cv[hlf][r] = 0.f; cm[hlf][r] = 0.f; }
+            if (j < a.J && ib < a.I) {
+                const size_t oc = (size_t)j * a.ld_clamp + ib;
+                if (al_cl && ib + 3 < a.I) {
+                    const float4 tv = *reinterpret_cast<const float4 *>(a.clamp_val + oc), tm = *reinterpret_cast<const float4 *>(a.clamp_mask + oc);
+                    cv[hlf][0] = tv.x; cv[hlf][1] = tv.y; cv[hlf][2] = tv.z; cv[hlf][3] = tv.w;
+                    cm[hlf][0] = tm.x; cm[hlf][1] = tm.y; cm[hlf][2] = tm.z; cm[hlf][3] = tm.w;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (ib + r < a.I) { cv[hlf][r] = a.clamp_val[oc + r]; cm[hlf][r] = a.clamp_mask[oc + r]; }
+                }
+            }
+        }
+    }
     float z[E];
     lane_outputs<G>(acc, 0, z);
     float dmax = 0.f;
@@ -377,6 +408,11 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                     const unsigned long long flat = (unsigned long long)(a.row0 + j) * (unsigned long long)a.I + ib;
                     draw4(a, key, flat, ib, nvalid, m, s, false);
                 }
+            }
+            if constexpr (CL) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (cm[hlf][r] != 0.f) { m[r] = cv[hlf][r]; s[r] = cv[hlf][r]; }
             }
             const size_t o = (size_t)j * a.ldo + ib;
             if constexpr (SideT::kMF) {
@@ -470,7 +506,8 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 
 // MINB: HIP's second __launch_bounds__ argument = WAVES PER SIMD the register budget must allow (for the 4-wave
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
-template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false>
+template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
+          bool CL = false>
 __global__ __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -546,7 +583,7 @@ __global__ __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tma
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];
@@ -1296,6 +1333,15 @@ __global__ void copy2d_kernel(const float *X, int ldx, float *Y, int ldy, int ro
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const size_t r = e / (size_t)cols, c = e % (size_t)cols;
         Y[r * ldy + c] = X[r * ldx + c];
+    }
+}
+
+// conditional sampling, before the first pass: X[r][c] <- val[r][c] where mask[r][c] != 0 (X pitched or dense; val / mask pitch ldc)
+__global__ void clamp_apply_kernel(float *X, int ldx, const float *val, const float *mask, int ldc, int rows, int cols) {
+    const size_t n = (size_t)rows * cols;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = e / (size_t)cols, c = e % (size_t)cols;
+        if (mask[r * ldc + c] != 0.f) X[r * ldx + c] = val[r * ldc + c];
     }
 }
 

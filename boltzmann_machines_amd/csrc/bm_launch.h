@@ -12,7 +12,11 @@
 //   MF   mean-field passes (ActArgs::prev / maxdiff / skip / chk_ctl / acc_init; ActSide<.., MF>).  Two tiles, by rule: 32 x 64
 //        (8 waves, one workgroup per CU) where that gives every CU a tile, else 32 x 32 (4 waves) - what the tuner picked for
 //        these passes at 784-512-1024 x 512 (profiles/r5_dbm_kernel_stats.csv); BM355_DEBUG=mf_geo=8|1 forces one
-// All three stage through LDS-DMA in the slab order.  dispatch_act walks the one ladder they share with the plain flavour:
+//   CL   clamped outputs (ActArgs::clamp_mask / clamp_val; conditional sampling): single-segment passes.  NOT a
+//        tile of its own: the geometry and the block -> tile map are the ones the tuner chose (or now chooses, with the plain
+//        kernels) for the same shape in the plain flavour - one memo, no tuning run with the clamp loads; act_geo forces it
+//        like any pass.  With `lit`: the 32 x 32 parity tile of LIT.  Never the chained launch or the bf16 x 3 strip kernel
+// FE, LIT and MF stage through LDS-DMA in the slab order.  dispatch_act walks the one ladder they share with the plain flavour:
 // x-major P / two K segments / one, each as the `fast` kernel (16-byte loads) or the one that passes every chunk through
 // registers (STG_DMA whatever the geometry's staging: shapes without 16-byte loads have ONE flavour).
 //
@@ -131,13 +135,13 @@ template <class Args, class F> static inline int tune_tile_map(TuneTimer &tm, Ar
 static inline bool tune_log() { static const bool on = dbg("tune_log") != nullptr; return on; }
 
 // ---- act_kernel: one dispatcher for every flavour
-enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
+enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
 template <class G, int MINB, int STG, unsigned FL, bool SEG2, int PL>
 static inline void launch_act_kernel(bool fast, unsigned dyn_lds, hipStream_t st, const ActArgs &a, const TileMap &tmap) {
     const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
-    constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0;
-    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF>), grid, blk, dyn_lds, st, a, tmap);
-    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF>), grid, blk, dyn_lds, st, a, tmap);
+    constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0, CL = (FL & FL_CL) != 0;
+    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL>), grid, blk, dyn_lds, st, a, tmap);
+    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL>), grid, blk, dyn_lds, st, a, tmap);
 }
 template <class G, int MINB, int STG, unsigned FL>
 static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, unsigned dyn_lds = 0) {
@@ -154,9 +158,11 @@ static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, un
         if (seg2) { launch_act_kernel<G, MINB, STG, FL, true, KM>(fast, dyn_lds, st, a, tmap); return; }
     launch_act_kernel<G, MINB, STG, FL, false, KM>(fast, dyn_lds, st, a, tmap);
 }
-// the plain flavour: x-major P exists for the geometries with MI == 1
-template <class G, int MINB, int STG>
-static inline void launch_act_geo(const ActArgs &a, hipStream_t st) { dispatch_act<G, MINB, STG, FL_SEG2 | (G::MI == 1 ? FL_XM : 0)>(a, st, a.map_xi); }
+// the plain flavour (FLX == 0) and CL (FLX == FL_CL: no two-segment kernels): x-major P exists for the geometries with MI == 1
+template <class G, int MINB, int STG, unsigned FLX = 0>
+static inline void launch_act_geo(const ActArgs &a, hipStream_t st) {
+    dispatch_act<G, MINB, STG, (FLX ? FLX : FL_SEG2) | (G::MI == 1 ? FL_XM : 0)>(a, st, a.map_xi);
+}
 static inline void launch_act_fe(const ActArgs &a, hipStream_t st) { dispatch_act<GeoAct8, 1, STG_DMA, FL_FE | FL_XM>(a, st, XI_SLAB); }
 static inline void launch_act_lit(const ActArgs &a, hipStream_t st) { dispatch_act<GeoActS, 2, STG_DMA, FL_LIT | FL_XM | FL_SEG2>(a, st, XI_SLAB); }
 template <class G, int MINB, bool LIT>
@@ -198,35 +204,37 @@ static inline void launch_act_bf3_as(int geo, const ActArgs &a, hipStream_t st) 
 }
 
 // geo: tile geometry 8 | 4 | 1 | 3, + 100 for register staging of the full chunks (default: LDS-DMA), or one of the specials
+// FLX: the flavour of the ladder's kernels (0 plain, FL_CL)
+template <unsigned FLX = 0>
 static inline void launch_act_as(int geo, const ActArgs &a, hipStream_t st) {
     // 208: 8 waves, DMA issued by waves 0-3 only (not a tuner candidate: within noise of 8 on every shape measured)
-    if (geo == 208) { launch_act_geo<GeoAct8, 1, STG_DMAH>(a, st); return; }
+    if (geo == 208) { launch_act_geo<GeoAct8, 1, STG_DMAH, FLX>(a, st); return; }
     // 6: 64 x 64 tile, 8 waves of 32 x 16 (the outer-product geometry): half the operand traffic per flop of the
     // 32 x 64 tile, for outputs large enough to fill the chip with tiles of that size
-    if (geo == 6 && !a.p_xm) { launch_act_geo<GeoGrad8, 1, STG_DMA>(a, st); return; }
+    if (geo == 6 && !a.p_xm) { launch_act_geo<GeoGrad8, 1, STG_DMA, FLX>(a, st); return; }
     if (geo == 6) geo = 8;
     // 9: the 64 x 64 tile with BK = 32: 64 KiB LDS, two workgroups per CU (k-major P only)
     // (the second template argument is the kernel's waves per SIMD: 2 workgroups x 8 waves / 4 SIMDs)
-    if (geo == 9 && !a.p_xm) { launch_act_geo<GeoGrad8h, 4, STG_DMA>(a, st); return; }
+    if (geo == 9 && !a.p_xm) { launch_act_geo<GeoGrad8h, 4, STG_DMA, FLX>(a, st); return; }
     if (geo == 9) geo = 8;
     // 5: 64 x 32 tile with BK = 32, three workgroups per CU (k-major P only)
-    if (geo == 5 && !a.p_xm) { launch_act_geo<GeoAct32, 3, STG_DMA>(a, st); return; }
+    if (geo == 5 && !a.p_xm) { launch_act_geo<GeoAct32, 3, STG_DMA, FLX>(a, st); return; }
     // 7: the same with two workgroups per CU (256 registers per wave: the two-segment variant spills 140 bytes at 168)
-    if (geo == 7 && !a.p_xm) { launch_act_geo<GeoAct32, 2, STG_DMA>(a, st); return; }
+    if (geo == 7 && !a.p_xm) { launch_act_geo<GeoAct32, 2, STG_DMA, FLX>(a, st); return; }
     if (geo == 5 || geo == 7) geo = 3;
     const bool reg = geo >= 100;
     geo %= 100;
     if (a.p_xm && geo == 4) geo = 8;        // x-major P exists for the MI == 1 geometries only
     if (reg) {
-        if (geo == 8)      launch_act_geo<GeoAct8, 1, STG_REG>(a, st);
-        else if (geo == 1) launch_act_geo<GeoActS, 2, STG_REG>(a, st);
-        else if (geo == 3) launch_act_geo<GeoActS32, 4, STG_REG>(a, st);
-        else               launch_act_geo<GeoAct, 1, STG_REG>(a, st);
+        if (geo == 8)      launch_act_geo<GeoAct8, 1, STG_REG, FLX>(a, st);
+        else if (geo == 1) launch_act_geo<GeoActS, 2, STG_REG, FLX>(a, st);
+        else if (geo == 3) launch_act_geo<GeoActS32, 4, STG_REG, FLX>(a, st);
+        else               launch_act_geo<GeoAct, 1, STG_REG, FLX>(a, st);
     } else {
-        if (geo == 8)      launch_act_geo<GeoAct8, 1, STG_DMA>(a, st);
-        else if (geo == 1) launch_act_geo<GeoActS, 2, STG_DMA>(a, st);
-        else if (geo == 3) launch_act_geo<GeoActS32, 4, STG_DMA>(a, st);
-        else               launch_act_geo<GeoAct, 1, STG_DMA>(a, st);
+        if (geo == 8)      launch_act_geo<GeoAct8, 1, STG_DMA, FLX>(a, st);
+        else if (geo == 1) launch_act_geo<GeoActS, 2, STG_DMA, FLX>(a, st);
+        else if (geo == 3) launch_act_geo<GeoActS32, 4, STG_DMA, FLX>(a, st);
+        else               launch_act_geo<GeoAct, 1, STG_DMA, FLX>(a, st);
     }
 }
 // the caller's launch with every OUTPUT redirected into the scratch pool (false: no memory, keep the default choice)
@@ -317,24 +325,44 @@ static inline void launch_act_bf3(const ActArgs &a, hipStream_t st) {
     const Tuned T = memo.get({a.I, a.J, a.b3.K1, a.b3.K2, flags}, [&] { return tune_bf3_shape(a, st, flags); });
     launch_act_bf3_as(T.geo, a, st);
 }
-static inline void launch_act_f32(const ActArgs &a, hipStream_t st) {
-    static const int geo_env = dbg_int("act_geo");
-    const int ov = geo_env ? geo_env : a.geo_hint;
-    if (ov) { launch_act_as(ov, a, st); return; }
+// the tuner's decision for the shape of `a` (ONE memo for the plain flavour and CL; measured with the plain kernels)
+static inline Tuned tuned_act(const ActArgs &a, hipStream_t st) {
     static TuneMemo<5> memo;
     const long long flags = (long long)((a.sample ? 1 : 0) | (a.kind << 1) | (a.prev ? 16 : 0) | (a.rowacc ? 32 : 0) |
                                         (a.acc_init ? 64 : 0) | (a.p_xm ? 128 : 0) | (a.rowdot_out ? 256 : 0) |
                                         (a.dot_mat ? 512 : 0) | (a.negmeans ? 1024 : 0));
-    const Tuned T = memo.get({a.I, a.J, a.K1, a.K2, flags}, [&] { return tune_act_shape(a, st, flags); });
+    return memo.get({a.I, a.J, a.K1, a.K2, flags}, [&] {
+        if (!a.clamp_mask) return tune_act_shape(a, st, flags);
+        ActArgs plain = a;
+        plain.clamp_mask = plain.clamp_val = nullptr; plain.ld_clamp = 0;
+        return tune_act_shape(plain, st, flags);
+    });
+}
+template <unsigned FLX = 0>
+static inline void launch_act_f32(const ActArgs &a, hipStream_t st) {
+    static const int geo_env = dbg_int("act_geo");
+    const int ov = geo_env ? geo_env : a.geo_hint;
+    if (ov) { launch_act_as<FLX>(ov, a, st); return; }
+    const Tuned T = tuned_act(a, st);
     if (T.xi != XI_MODEL && !a.map_xi) {
         ActArgs a2 = a;
         a2.map_xi = T.xi;
-        launch_act_as(T.geo, a2, st);
+        launch_act_as<FLX>(T.geo, a2, st);
         return;
     }
-    launch_act_as(T.geo, a, st);
+    launch_act_as<FLX>(T.geo, a, st);
+}
+// clamped outputs: per-pass fp32 launches always (clamp values may be grey levels: no bf16 shadow is written either)
+static inline void launch_act_cl(const ActArgs &a, hipStream_t st) {
+    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init) {
+        fprintf(stderr, "bm355: a clamped pass has one K segment and no metric-fetch or mean-field plumbing (no such kernel)\n");
+        abort();
+    }
+    if (a.lit && a.kind == 0) { dispatch_act<GeoActS, 2, STG_DMA, FL_CL | FL_LIT | FL_XM>(a, st, XI_SLAB); return; }
+    launch_act_f32<FL_CL>(a, st);
 }
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
+    if (a.clamp_mask) { launch_act_cl(a, st); return; }
     if (a.b3.K1 > 0) { launch_act_bf3(a, st); return; }
     if (a.fe_flip) { launch_act_fe(a, st); return; }
     if (a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init) { launch_act_mf(a, st); return; }

@@ -241,8 +241,9 @@ static void launch_up(bm_rbm *h, const float *v, int ldv, int B, float *means, f
 }
 
 // E[v|h] (+ sample): base_rbm.py:353-365.  hs [B][H] pitch ldh
+// clamp_mask / clamp_val (dense [B][V], or null): outputs with a non-zero mask entry are held at clamp_val (ActArgs::clamp_mask)
 static void launch_down(bm_rbm *h, const float *hs, int ldh, int B, float *means, float *states, int ldo,
-                        int sample, uint32_t site, int t) {
+                        int sample, uint32_t site, int t, const float *clamp_val = nullptr, const float *clamp_mask = nullptr) {
     ProfScope _ps(h, KC_DOWN);
     ActArgs a;
     memset(&a, 0, sizeof(a));
@@ -259,6 +260,7 @@ static void launch_down(bm_rbm *h, const float *hs, int ldh, int B, float *means
     a.means = means; a.states = states; a.ldo = ldo;
     a.key = make_key(h, site, t);
     a.row0 = h->row0;
+    a.clamp_val = clamp_val; a.clamp_mask = clamp_mask; a.ld_clamp = h->V;
     if (h->fast_now && hs == h->hs.p) {          // fast-binary: W planes x the bf16 shadow of the hidden bitmap
         a.b3.P1 = Bf3Operand{h->W3.p, h->W3.plane_stride(), h->W3.ld, h->V};
         a.b3.Q1 = Bf3Operand{h->hs16.p, 0, h->hs16.ld, B};
@@ -1218,6 +1220,33 @@ int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_ste
     }
     hipLaunchKernelGGL(copy2d_kernel, dim3(256), dim3(256), 0, h->stream, (const float *)h->hs.p, h->hs.ld, H_dev, h->H, B, h->H);
     hipLaunchKernelGGL(copy2d_kernel, dim3(256), dim3(256), 0, h->stream, (const float *)h->vs.p, h->vs.ld, V_dev, h->V, B, h->V);
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// Block-Gibbs with clamped visible units: n_steps of v -> h -> v from the visible states in V_dev, the entries
+// with a non-zero mask held at clamp_val - overwritten in V_dev first (clamp_apply_kernel), then in the epilogue of every
+// prop-down (the CL flavour of act_kernel).  Always per-pass fp32 launches - no chained launch, no fast-binary sweep (clamp
+// values may be grey levels) - so the call returns the same bits in every mode; both layers are sampled (as in bm_rbm_ais).
+// The sweeps run in place on the caller's dense buffers like bm_rbm_gibbs; hs / vs are the only workspaces touched.
+int bm_rbm_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev, int32_t B, int32_t n_steps,
+                         const float *clamp_val_dev, const float *clamp_mask_dev) {
+    BM_CHECK(h, "null argument");
+    BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
+    BM_CHECK(V_dev && H_dev && clamp_val_dev && clamp_mask_dev, "null state or clamp pointer");
+    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
+    BM_CHECK(!h->multinomial(), "bm_rbm_gibbs_clamped: Multinomial hidden units are not supported (their sweep goes through the "
+             "softmax pair and pitched copies, not the clamped epilogue)");
+    ensure_wt(h);
+    hipLaunchKernelGGL(clamp_apply_kernel, dim3(256), dim3(256), 0, h->stream, V_dev, h->V, clamp_val_dev, clamp_mask_dev, h->V, B, h->V);
+    for (int t = 0; t < n_steps; ++t) {
+        const bool first = t == 0, last = t == n_steps - 1;
+        launch_up(h, first ? V_dev : h->vs.p, first ? h->V : h->vs.ld, B, nullptr, last ? H_dev : h->hs.p,
+                  last ? h->H : h->hs.ld, 1, SITE_H, t);
+        launch_down(h, last ? H_dev : h->hs.p, last ? h->H : h->hs.ld, B, last ? Vmean_dev : nullptr, last ? V_dev : h->vs.p,
+                    last ? h->V : h->vs.ld, 1, SITE_V, t, clamp_val_dev, clamp_mask_dev);
+    }
     h->call++;
     BM_HIP(hipGetLastError());
     return 0;

@@ -18,7 +18,7 @@ import numpy as np
 from . import _ffi
 from .base import EngineModel, run_on_engine
 from .engine import DbmEngine, DbmEngine64
-from .rbm import GaussianRBM
+from .rbm import GaussianRBM, clampable_only
 from .utils import (epoch_iter, make_list_from, write_during_training,
                     log_sum_exp, log_mean_exp, log_diff_exp, log_std_exp)
 from .utils import philox
@@ -442,6 +442,56 @@ class DBM(EngineModel):
         else:
             self._restore(snap)
         return v
+
+    def _check_clampable(self, what):
+        name = '%s.%s' % (self.__class__.__name__, what)
+        if np.dtype(self.dtype) != np.float32:
+            raise NotImplementedError("%s: dtype='%s' models are not supported (the float64 engine has no clamped sweep; "
+                                      'float32 only)' % (name, np.dtype(self.dtype).name))
+        if any(int(u) == _ffi.UNIT_MULTINOMIAL for u in (self.h_units_ or [])):
+            raise NotImplementedError('%s: a Multinomial hidden layer is not supported (Bernoulli hidden layers only)' % name)
+
+    @clampable_only
+    @run_on_engine(update_seed=True)
+    def sample_v_given(self, X, mask, n_gibbs_steps=None, return_means=False, save_model=False):
+        """Conditional sampling with the fantasy particles: `sample_v` with the visible units that `mask` marks as
+        observed held at the values of `X` (inpainting, imputation, completion of a partial pattern).
+
+        X : [n_particles, n_visible] - observed values where `mask` is non-zero; the other entries become the
+            particles' visible starting values.
+        mask : [n_particles, n_visible], or [n_visible] for the same pattern in every row; non-zero = observed.
+        n_gibbs_steps : as in `sample_v` - that many sampled sweeps of the particles, then as many mean sweeps; the
+            observed entries are re-imposed inside every visible-layer pass.  None: the model's `n_gibbs_steps`.
+        Returns what `sample_v` returns: the visible activation probabilities [n_particles, n_visible] after the mean
+        sweeps, observed entries equal to X.  `return_means=True` additionally returns them as the second element of a
+        pair (the DBM's result already is the means; kept for one signature across the model classes).
+        save_model : as in `sample_v`; False leaves the persistent particles as they were.
+        The hidden layers of the particles are the chain's starting point as they stand.  Values are in the engine's
+        units (a Gaussian visible layer is not rescaled by sigma, like everywhere in the DBM).  One seed is drawn from
+        the model's host stream.  Not available for float64 models or stacks with a Multinomial hidden layer."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        shape = (self.n_particles, self.n_visible_)
+        if X.shape != shape:
+            raise ValueError('`X` has invalid shape {0}: expected [n_particles, n_visible] = {1}'.format(X.shape, shape))
+        mask = np.asarray(mask)
+        if mask.shape not in (shape, (self.n_visible_,)):
+            raise ValueError('`mask` has invalid shape {0}: expected {1} or ({2},)'.format(mask.shape, shape, self.n_visible_))
+        observed = np.broadcast_to(mask != 0, shape)
+        k = int(n_gibbs_steps) if n_gibbs_steps is not None else self._feed()[2]
+        if k < 0:
+            raise ValueError('`n_gibbs_steps` must be >= 0 (got {0})'.format(k))
+        Vd = _ffi.DeviceArray(shape, np.float32)
+        Cd, Md = as_device(X, np.float32), as_device(observed.astype(np.float32), np.float32)
+        snap = None if save_model else self._snapshot(('v', 'v_new', 'h', 'h_new'))
+        self._engine.set('v', X)
+        self._engine.sample_v_clamped(k, Cd, Md, Vd)
+        v = Vd.numpy()
+        if save_model:
+            self.n_samples_generated_ += k
+            self._save_model()
+        else:
+            self._restore(snap)
+        return (v, v.copy()) if return_means else v
 
     def set_ais_accumulation(self, dtype='float64'):
         """How `log_Z` accumulates the AIS log-weights.  'float64' (default): per chain the difference of consecutive

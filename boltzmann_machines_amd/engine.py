@@ -181,6 +181,15 @@ class RbmEngine(object):
     def gibbs(self, Hd, Vd, B, n_steps):
         check(self.lib.bm_rbm_gibbs(self._h, Hd.ptr, Vd.ptr, B, n_steps))
 
+    def gibbs_clamped(self, Vd, Hd, B, n_steps, clamp_val_d, clamp_mask_d, Vmean_d=None, row=0):
+        """n_steps of v -> h -> v from the visible states in Vd [B, V] (in/out) with the entries where clamp_mask_d is
+        non-zero held at clamp_val_d (both dense [B, V]); Hd [B, H] and Vmean_d (optional) receive the last hidden states
+        and visible means (bm_rbm_gibbs_clamped).  row: the B rows start at this row of every array"""
+        ov, oh = row * self.V, row * self.H
+        check(self.lib.bm_rbm_gibbs_clamped(self._h, Vd.offset_ptr(ov), Hd.offset_ptr(oh),
+                                            Vmean_d.offset_ptr(ov) if Vmean_d is not None else None, B, n_steps,
+                                            clamp_val_d.offset_ptr(ov), clamp_mask_d.offset_ptr(ov)))
+
     def stream(self):
         p = C.c_void_p()
         check(self.lib.bm_rbm_stream(self._h, C.byref(p)))
@@ -469,6 +478,11 @@ class DbmEngine(object):
     def sample_v(self, k, Vd=None):
         check(self.lib.bm_dbm_sample_v(self._h, k, Vd.ptr if Vd is not None else None))
 
+    def sample_v_clamped(self, k, clamp_val_d, clamp_mask_d, Vd=None):
+        """sample_v with the visible units of the particles held at clamp_val_d where clamp_mask_d is non-zero (both dense
+        [n_particles, V]; bm_dbm_sample_v_clamped)"""
+        check(self.lib.bm_dbm_sample_v_clamped(self._h, k, clamp_val_d.ptr, clamp_mask_d.ptr, Vd.ptr if Vd is not None else None))
+
     def ais(self, n_betas, n_runs, k, seed, chain0=0):
         out = np.empty(n_runs, dtype=np.float32)
         check(self.lib.bm_dbm_ais(self._h, n_betas, n_runs, k, int(seed), int(chain0), out.ctypes.data_as(C.c_void_p)))
@@ -568,6 +582,9 @@ class DbmEngine64(DbmEngine):
 
     grad_step = apply_step = set_comm = set_xchg = ais_sharded = ais_sharded_direct = set_mf_allreduce = _unsupported
     device_view = stream = timer_start = timer_stop = timer_mark = timer_elapsed = _unsupported
+
+    def sample_v_clamped(self, *a, **kw):
+        raise NotImplementedError('conditional sampling has no float64 entry (bm_dbm64_* has no clamped sample_v)')
 
     def set_fast_binary(self, on, everywhere=False):
         if on:

@@ -46,6 +46,15 @@ def single_joint_only(f):
     return checked
 
 
+def clampable_only(f):
+    """`sample_v_given` needs the clamped epilogue of the float32 engine: other models are refused before anything is touched"""
+    @wraps(f)
+    def checked(model, *args, **kwargs):
+        model._check_clampable(f.__name__)
+        return f(model, *args, **kwargs)
+    return checked
+
+
 class BaseRBM(EngineModel):
     """Restricted Boltzmann machine trained with CD-k (reference base_rbm.py:14-94)."""
 
@@ -505,6 +514,72 @@ class BaseRBM(EngineModel):
         eng.sync()
         return Hd.numpy().astype(np_dtype)
 
+
+    # ---- conditional sampling (no counterpart in the reference) ------------------------------------
+    def _check_clampable(self, what):
+        name = '%s.%s' % (self.__class__.__name__, what)
+        if self._H_UNIT != _ffi.UNIT_BERNOULLI:
+            raise NotImplementedError('%s: Multinomial hidden units are not supported (their sweep goes through the softmax '
+                                      'kernels, which have no clamped epilogue)' % name)
+        if np.dtype(self.dtype) != np.float32:
+            raise NotImplementedError("%s: dtype='%s' models are not supported (the float64 engine has no clamped sweep; "
+                                      'float32 only)' % (name, np.dtype(self.dtype).name))
+
+    @clampable_only
+    @run_on_engine(update_seed=True)
+    def sample_v_given(self, X, mask, n_gibbs_steps=None, return_means=False):
+        """Conditional sampling: draw the unobserved visible units from p(v_free | v_observed) by block-Gibbs with the
+        observed ones clamped (inpainting, imputation of missing values, completion of a partial pattern).
+
+        X : [N, n_visible] - observed values where `mask` is non-zero; the other entries are the chain's starting values.
+        mask : [N, n_visible], or [n_visible] for the same pattern in every row; non-zero = observed.
+        n_gibbs_steps : sweeps h ~ p(h|v), v ~ p(v|h) with the observed entries re-imposed inside every visible pass;
+            None: the model's `n_gibbs_steps` of the current epoch.
+        Returns the visible states [N, n_visible] after the last sweep (with `return_means`: a pair, states and the
+        means of the last visible pass); observed entries hold X in both.
+
+        Both layers are always sampled (`sample_v_states` / `sample_h_states` and dropout do not apply).  The rows are
+        processed in slices of at most `batch_size`, every row drawing from its own position of the call's random
+        stream: the result does not depend on the slicing.  One seed is drawn from the model's host stream, as by
+        every stochastic public call.  No parameter is changed.
+        GaussianRBM: X is pre-processed like `fit`'s input (divided by `sigma`, reference rbm.py:107) - so are the
+        observed values the chain holds - and the chain is the engine's own Gibbs chain of the training graph, whose
+        visible pass yields sigma * (hW^T) + vb (+ sigma * noise).  The returned observed entries are X as given."""
+        eng = self._on_device()
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.n_visible:
+            raise ValueError('`X` has invalid shape {0}: expected [N, {1}]'.format(X.shape, self.n_visible))
+        mask = np.asarray(mask)
+        if mask.shape not in (X.shape, (self.n_visible,)):
+            raise ValueError('`mask` has invalid shape {0}: expected {1} or ({2},)'.format(mask.shape, X.shape, self.n_visible))
+        observed = np.broadcast_to(mask != 0, X.shape)
+        k = int(n_gibbs_steps) if n_gibbs_steps is not None else self._feed()[2]
+        if k < 1:
+            raise ValueError('`n_gibbs_steps` must be >= 1 (got {0})'.format(k))
+        N = len(X)
+        Xin = X
+        if self._V_UNIT == _ffi.UNIT_GAUSSIAN:
+            Xin = np.ascontiguousarray(X / np.asarray(self._sigma_vector(), dtype=np.float32)[None, :], dtype=np.float32)
+        Vd = self._to_device(Xin)                    # in/out: starting values -> last states
+        Cd = self._to_device(Xin)                    # the clamp values (only the observed entries are read)
+        Md = self._to_device(observed.astype(np.float32))
+        Hd = _ffi.DeviceArray((N, self.n_hidden), np.float32)
+        Pd = _ffi.DeviceArray((N, self.n_visible), np.float32) if return_means else None
+        home = self._rank * self.batch_size if getattr(self, '_dp', None) is not None else 0
+        try:
+            for start in range(0, N, self.batch_size):
+                # every slice at call 0 of the call's seed and at its own rows of the stream (DESIGN.md 4, `row0`): a row's
+                # draws depend on its index alone
+                eng.seed(self._graph_seed)
+                eng.set_row_offset(start)
+                eng.gibbs_clamped(Vd, Hd, min(self.batch_size, N - start), k, Cd, Md, Pd, row=start)
+            eng.sync()
+        finally:
+            eng.set_row_offset(home)
+        V = np.where(observed, X, Vd.numpy())
+        if return_means:
+            return V, np.where(observed, X, Pd.numpy())
+        return V
 
     # ---- likelihood (no counterpart in the reference: its only AIS is the DBM's) ----------------
     def _check_single_joint(self, what):

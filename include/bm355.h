@@ -185,6 +185,23 @@ int bm_rbm_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t n_gibbs_steps
  * V_dev [B, n_visible] receives the last visible states.  No parameter update. */
 int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_steps);
 
+/* Conditional sampling: block-Gibbs with CLAMPED visible units.  All pointers are device pointers, dense
+ * [B, n_visible] / [B, n_hidden]; a visible unit of a row is clamped (observed) where clamp_mask_dev is non-zero and then
+ * holds clamp_val_dev (any float: {0,1}, grey levels, reals for Gaussian visibles - already divided by sigma, as the chain
+ * of bm_rbm_train_step sees its input).
+ * V_dev is in/out: the initial visible states; its clamped entries are overwritten from clamp_val_dev first.  Then, for
+ * t = 0 .. n_steps-1:  h ~ p(h|v) at site SITE_H + 16 t,  v ~ p(v|h) at site SITE_V + 16 t with the clamp applied in that
+ * pass's epilogue.  A clamped output's random words are skipped by position: the free entries get the bits an unclamped
+ * sweep from the same states would give them.  Both layers are always sampled (the handle's sample_*_states flags do not
+ * apply); the dbm_first / dbm_last multipliers do.  V_dev and H_dev receive the last states, Vmean_dev (may be NULL) the
+ * last visible pass's means - clamped entries hold the clamp value in both.  The call counter advances once; no parameter,
+ * momentum buffer or workspace another entry point reads is changed.  Always per-pass fp32 launches: BM355_DEBUG=chain= and
+ * fast-binary mode do not change its bits.  Row r draws as global row (row offset + r): a slice of rows with
+ * bm_rbm_set_row_offset reproduces those rows of the whole.
+ * Errors: B outside [1, max_batch], n_steps < 1, Multinomial hidden units.  (No float64 counterpart.) */
+int bm_rbm_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev, int32_t B, int32_t n_steps,
+                         const float *clamp_val_dev, const float *clamp_mask_dev);
+
 /* the handle's hipStream_t (as void*), so a host can enqueue collectives on
  * the same stream (torch.cuda.ExternalStream) without host synchronisation. */
 int bm_rbm_stream(bm_rbm *h, void **out_stream);
@@ -313,6 +330,16 @@ int bm_dbm_reconstruct(bm_dbm *h, const float *X_dev, float *R_dev);
 /* sample_v op (dbm.py:641-648, public :887-897): k PCD sweeps, one mean
  * sweep, v <- v_means; copies v to V_dev [M, V] if non-NULL. */
 int bm_dbm_sample_v(bm_dbm *h, int32_t n_gibbs_steps, float *V_dev);
+/* bm_dbm_sample_v with clamped visible units: clamp_val_dev / clamp_mask_dev are dense device arrays
+ * [M, V]; where the mask is non-zero the visible unit of that particle holds the clamp value.  The visible layer of the
+ * persistent particles is overwritten at the clamped entries before the first sweep, and every visible-layer pass of the
+ * call - the n_gibbs_steps sampled sweeps and the n_gibbs_steps mean sweeps behind them - applies the clamp in its epilogue.
+ * Sites, the call counter and the effect on the particles are those of bm_dbm_sample_v; with an all-zero mask the two calls
+ * are bit-identical.  n_gibbs_steps == 0: no sweep runs, the clamp alone is applied.  Visible units Bernoulli or Gaussian
+ * (clamp values in the engine's units); always fp32 launches, whatever bm_dbm_set_fast_binary says.
+ * Errors: n_gibbs_steps < 0, null clamp pointers, a Multinomial hidden layer.  (No float64 counterpart.) */
+int bm_dbm_sample_v_clamped(bm_dbm *h, int32_t n_gibbs_steps, const float *clamp_val_dev, const float *clamp_mask_dev,
+                            float *V_dev);
 /* AIS (dbm.py:650-736; public log_Z :899-939) for a Bernoulli DBM of any
  * depth (1..4 layers): n_runs chains, n_betas temperatures, n_gibbs_steps
  * transitions per temperature.  values_host [n_runs] receives the per-chain
