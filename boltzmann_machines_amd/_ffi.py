@@ -141,6 +141,9 @@ SIGNATURES = {
     'bm_rbm_ais': [_vp, _i32, _i32, _i32, _vp, _u64, _i64, _vp],
     'bm_rbm_gibbs': [_vp, _vp, _vp, _i32, _i32],
     'bm_rbm_gibbs_clamped': [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    'bm_rbm_pt_init': [_vp, _i32, _i32, _vp, _vp, _i64],
+    'bm_rbm_pt_sweep': [_vp, _i32],
+    'bm_rbm_pt_read': [_vp, _vp, _vp, _vp, _vp],
     'bm_rbm_stream': [_vp, C.POINTER(_vp)],
     'bm_rbm_profile': [_vp, _i32],
     'bm_rbm_kernel_times': [_vp, _fp, _ip],

@@ -105,6 +105,14 @@ struct ActArgs {
     // before the rowdot_out read-back.  Both arrays are [J][I] with the common pitch ld_clamp.  Null mask: off.
     const float *clamp_val, *clamp_mask;
     int ld_clamp;
+    // Parallel tempering (the RT flavour, act_kernel<..., RT = true>; launch_act_rt): a temperature PER ROW.
+    // row_mult [J]: the multiplier of z and of the bias of row j is row_mult[j] - it replaces mult / bmult,
+    // m = sigmoid(row_mult[j] * z + row_mult[j] * b): the same two multiplies and one add.  Null: off.
+    // rowen_out [ceil(I/16)][ld_part] (or null): slot partials of sum_i s_i * (z_i + b_i), s the state just drawn and z + b the
+    // UNTEMPERED float32 pre-activation (the `t` of the rowacc branch), in the slot order of rowacc; with s in {0,1} the
+    // products are exact.  For the prop-up this is h.(vW + hb), the hidden half of the energy the swap step needs.
+    const float *row_mult;
+    float *rowen_out;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -328,7 +336,7 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // act_kernel's epilogue for the lane's outputs of ONE output tile (i0, j0): activation, draw, stores, the per-row
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
-template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false>
+template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -367,6 +375,16 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
             }
         }
     }
+    // RT: the row's temperature, requested at epilogue entry like the clamp arrays (one scalar per lane, its latency sits under
+    // lane_outputs and the first multiplies; held across the K loop it would cost every wave a register for nothing); sv keeps
+    // the lane's drawn states for the rowen_out partials
+    float rm = 1.f, sv[E];
+    (void)rm; (void)sv;
+    if constexpr (RT) {
+        rm = (j < a.J) ? a.row_mult[j] : 0.f;
+#pragma unroll
+        for (int e = 0; e < E; ++e) sv[e] = 0.f;
+    }
     float z[E];
     lane_outputs<G>(acc, 0, z);
     float dmax = 0.f;
@@ -385,8 +403,8 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
             float m[4], s[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float x = a.mult * z[4 * hlf + r];
-                const float b = a.bmult * bs[4 * hlf + r];
+                const float x = (RT ? rm : a.mult) * z[4 * hlf + r];
+                const float b = (RT ? rm : a.bmult) * bs[4 * hlf + r];
                 m[r] = (a.kind == 0) ? (LIT ? sigmoid_literal(x + b) : (HWMATH ? sigmoid_hw(x + b) : sigmoid(x + b)))
                                      : (a.kind == 1 ? (x * sg[4 * hlf + r] + b) : (a.kind == 3 ? x + b : x));
                 s[r] = m[r];
@@ -413,6 +431,10 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (cm[hlf][r] != 0.f) { m[r] = cv[hlf][r]; s[r] = cv[hlf][r]; }
+            }
+            if constexpr (RT) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sv[4 * hlf + r] = s[r];
             }
             const size_t o = (size_t)j * a.ldo + ib;
             if constexpr (SideT::kMF) {
@@ -449,9 +471,12 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
     // (FE: the h0 pass of a fused metric fetch - a compile-time flavour of its own (act_kernel<..., FE = true>): as a runtime
     //  branch of the shared epilogue the extra code cost every propagation pass 0.1 - 0.2 us, 0.5 us per CD-1 update, same-box A/B)
     if constexpr (FE) { if (a.fe_zero && i0 == 0 && j0 == 0 && tid < 6) a.fe_zero[tid] = 0.0; }     // the first tile zeroes the fetch's accumulators
-    if (a.rowacc || a.rowdot_out) {           // wave-uniform
+    bool row_sums = a.rowacc || a.rowdot_out;
+    if constexpr (RT) row_sums = row_sums || a.rowen_out;
+    if (row_sums) {                           // wave-uniform
         // per-lane quads (4 consecutive i, left to right); MI == 2: the lane's two quads are added
-        float racc = 0.f, rdot = 0.f, racc2 = 0.f;
+        float racc = 0.f, rdot = 0.f, racc2 = 0.f, ren = 0.f;
+        (void)ren;
         if (j < a.J) {
             int fc = 0; float delta = 0.f;
             if constexpr (FE) {
@@ -460,7 +485,8 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
             }
 #pragma unroll
             for (int hlf = 0; hlf < NH; ++hlf) {
-                float qa = 0.f, qd = 0.f, qa2 = 0.f;
+                float qa = 0.f, qd = 0.f, qa2 = 0.f, qe = 0.f;
+                (void)qe;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int e = 4 * hlf + r, i = ib0 + e;
@@ -477,7 +503,9 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                     }
                     // the state of this element as it was just stored by this lane
                     if (a.rowdot_out) qd += a.states[(size_t)j * a.ldo + i] * a.dot_vec[i];
+                    if constexpr (RT) { if (a.rowen_out) qe += sv[e] * (z[e] + bs[e]); }
                 }
+                if constexpr (RT) ren = (hlf == 0) ? qe : ren + qe;
                 racc = (hlf == 0) ? qa : racc + qa;
                 rdot = (hlf == 0) ? qd : rdot + qd;
                 racc2 = (hlf == 0) ? qa2 : racc2 + qa2;
@@ -489,6 +517,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
         rdot += __shfl_xor(rdot, 16);
         if (G::MI == 1) { racc += __shfl_xor(racc, 32); rdot += __shfl_xor(rdot, 32); }
         if constexpr (FE) { racc2 += __shfl_xor(racc2, 16); if (G::MI == 1) racc2 += __shfl_xor(racc2, 32); }
+        if constexpr (RT) { ren += __shfl_xor(ren, 16); if (G::MI == 1) ren += __shfl_xor(ren, 32); }
         const bool writer = (G::MI == 1) ? (g == 0) : ((g & 1) == 0);
         const int slot = (i0 + wi * (16 * G::MI)) / 16 + ((G::MI == 2) ? (g >> 1) : 0);
         if (writer && j < a.J && slot * 16 < a.I) {
@@ -498,6 +527,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
             } else {
                 if (a.rowacc) a.rowacc[(size_t)slot * a.ld_part + j] = racc;
                 if (a.rowdot_out) a.rowdot_out[(size_t)slot * a.ld_part + j] = rdot;
+                if constexpr (RT) { if (a.rowen_out) a.rowen_out[(size_t)slot * a.ld_part + j] = ren; }
             }
         }
     }
@@ -507,7 +537,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 // MINB: HIP's second __launch_bounds__ argument = WAVES PER SIMD the register budget must allow (for the 4-wave
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
-          bool CL = false>
+          bool CL = false, bool RT = false>
 __global__ __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -583,7 +613,7 @@ __global__ __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tma
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];

@@ -16,6 +16,8 @@
 //        tile of its own: the geometry and the block -> tile map are the ones the tuner chose (or now chooses, with the plain
 //        kernels) for the same shape in the plain flavour - one memo, no tuning run with the clamp loads; act_geo forces it
 //        like any pass.  With `lit`: the 32 x 32 parity tile of LIT.  Never the chained launch or the bf16 x 3 strip kernel
+//   RT   a temperature per row (ActArgs::row_mult / rowen_out; parallel tempering): single-segment passes on the
+//        geometry and tile map of the plain flavour's memo for the shape, exactly as CL; combined with no other flavour
 // FE, LIT and MF stage through LDS-DMA in the slab order.  dispatch_act walks the one ladder they share with the plain flavour:
 // x-major P / two K segments / one, each as the `fast` kernel (16-byte loads) or the one that passes every chunk through
 // registers (STG_DMA whatever the geometry's staging: shapes without 16-byte loads have ONE flavour).
@@ -135,13 +137,14 @@ template <class Args, class F> static inline int tune_tile_map(TuneTimer &tm, Ar
 static inline bool tune_log() { static const bool on = dbg("tune_log") != nullptr; return on; }
 
 // ---- act_kernel: one dispatcher for every flavour
-enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
+enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
 template <class G, int MINB, int STG, unsigned FL, bool SEG2, int PL>
 static inline void launch_act_kernel(bool fast, unsigned dyn_lds, hipStream_t st, const ActArgs &a, const TileMap &tmap) {
     const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
-    constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0, CL = (FL & FL_CL) != 0;
-    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL>), grid, blk, dyn_lds, st, a, tmap);
-    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL>), grid, blk, dyn_lds, st, a, tmap);
+    constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0, CL = (FL & FL_CL) != 0,
+                   RT = (FL & FL_RT) != 0;
+    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT>), grid, blk, dyn_lds, st, a, tmap);
+    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT>), grid, blk, dyn_lds, st, a, tmap);
 }
 template <class G, int MINB, int STG, unsigned FL>
 static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, unsigned dyn_lds = 0) {
@@ -158,7 +161,7 @@ static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, un
         if (seg2) { launch_act_kernel<G, MINB, STG, FL, true, KM>(fast, dyn_lds, st, a, tmap); return; }
     launch_act_kernel<G, MINB, STG, FL, false, KM>(fast, dyn_lds, st, a, tmap);
 }
-// the plain flavour (FLX == 0) and CL (FLX == FL_CL: no two-segment kernels): x-major P exists for the geometries with MI == 1
+// the plain flavour (FLX == 0), CL and RT (FLX == FL_CL / FL_RT: no two-segment kernels): x-major P exists for the geometries with MI == 1
 template <class G, int MINB, int STG, unsigned FLX = 0>
 static inline void launch_act_geo(const ActArgs &a, hipStream_t st) {
     dispatch_act<G, MINB, STG, (FLX ? FLX : FL_SEG2) | (G::MI == 1 ? FL_XM : 0)>(a, st, a.map_xi);
@@ -204,7 +207,7 @@ static inline void launch_act_bf3_as(int geo, const ActArgs &a, hipStream_t st) 
 }
 
 // geo: tile geometry 8 | 4 | 1 | 3, + 100 for register staging of the full chunks (default: LDS-DMA), or one of the specials
-// FLX: the flavour of the ladder's kernels (0 plain, FL_CL)
+// FLX: the flavour of the ladder's kernels (0 plain, FL_CL, FL_RT)
 template <unsigned FLX = 0>
 static inline void launch_act_as(int geo, const ActArgs &a, hipStream_t st) {
     // 208: 8 waves, DMA issued by waves 0-3 only (not a tuner candidate: within noise of 8 on every shape measured)
@@ -325,16 +328,17 @@ static inline void launch_act_bf3(const ActArgs &a, hipStream_t st) {
     const Tuned T = memo.get({a.I, a.J, a.b3.K1, a.b3.K2, flags}, [&] { return tune_bf3_shape(a, st, flags); });
     launch_act_bf3_as(T.geo, a, st);
 }
-// the tuner's decision for the shape of `a` (ONE memo for the plain flavour and CL; measured with the plain kernels)
+// the tuner's decision for the shape of `a` (ONE memo for the plain flavour, CL and RT; measured with the plain kernels)
 static inline Tuned tuned_act(const ActArgs &a, hipStream_t st) {
     static TuneMemo<5> memo;
     const long long flags = (long long)((a.sample ? 1 : 0) | (a.kind << 1) | (a.prev ? 16 : 0) | (a.rowacc ? 32 : 0) |
                                         (a.acc_init ? 64 : 0) | (a.p_xm ? 128 : 0) | (a.rowdot_out ? 256 : 0) |
                                         (a.dot_mat ? 512 : 0) | (a.negmeans ? 1024 : 0));
     return memo.get({a.I, a.J, a.K1, a.K2, flags}, [&] {
-        if (!a.clamp_mask) return tune_act_shape(a, st, flags);
+        if (!a.clamp_mask && !a.row_mult) return tune_act_shape(a, st, flags);
         ActArgs plain = a;
         plain.clamp_mask = plain.clamp_val = nullptr; plain.ld_clamp = 0;
+        if (a.row_mult) { plain.row_mult = nullptr; plain.rowen_out = nullptr; plain.mult = plain.bmult = 1.0f; }
         return tune_act_shape(plain, st, flags);
     });
 }
@@ -361,7 +365,17 @@ static inline void launch_act_cl(const ActArgs &a, hipStream_t st) {
     if (a.lit && a.kind == 0) { dispatch_act<GeoActS, 2, STG_DMA, FL_CL | FL_LIT | FL_XM>(a, st, XI_SLAB); return; }
     launch_act_f32<FL_CL>(a, st);
 }
+// a temperature per row: per-pass fp32 launches always, combined with nothing (no such kernel)
+static inline void launch_act_rt(const ActArgs &a, hipStream_t st) {
+    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.b3.K1 > 0 || a.lit ||
+        a.kind != 0) {
+        fprintf(stderr, "bm355: a row-tempered pass is a single-segment Bernoulli pass of its own flavour (no such kernel)\n");
+        abort();
+    }
+    launch_act_f32<FL_RT>(a, st);
+}
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
+    if (a.row_mult) { launch_act_rt(a, st); return; }
     if (a.clamp_mask) { launch_act_cl(a, st); return; }
     if (a.b3.K1 > 0) { launch_act_bf3(a, st); return; }
     if (a.fe_flip) { launch_act_fe(a, st); return; }

@@ -27,6 +27,8 @@ void set_error(const char *fmt, ...) {
 enum : uint32_t { SITE_DROPOUT = 1, SITE_H0 = 2, SITE_V = 3, SITE_H = 4, SITE_PLL = 5, SITE_FE = 6 };
 // bm_rbm_ais (bm355.h): streams of their own, call = beta step, row offset = global chain index
 enum : uint32_t { SITE_AIS_V0 = 7, SITE_AIS_V = 8, SITE_AIS_H = 9 };
+// bm_rbm_pt_* (bm355.h): the swap uniforms (flat index = global chain * (R - 1) + ladder pair) and the random start v_0
+enum : uint32_t { SITE_PT_SWAP = 10, SITE_PT_V0 = 11 };
 
 }  // namespace bm
 
@@ -92,6 +94,16 @@ struct bm_rbm {
     DevBuf apart_h, apart_v;           // slot partials (ActArgs::rowacc / rowdot_out): [ceil(H/16)][ais_rows], [ceil(V/16)][ais_rows]
     DevArray<double> alogw;            // [ais_rows] log-weights, accumulated in double in a fixed order
     DevBuf abase, adot, abeta, atable; // a [V], vb - a [V], beta [n_betas], the mixed biases a + beta_k (vb - a) [n_betas][V]
+    // bm_rbm_pt_*: the tempered ensemble of pt_M chains x pt_R replicas, chain-major rows (row c * R + r), allocated on demand for
+    // `pt_rows` rows - max_batch does not bound it; nothing else in the handle reads or writes these
+    int pt_rows = 0, pt_M = 0, pt_R = 0;
+    int64_t pt_chain0 = 0;
+    long long pt_step = 0;             // sweeps done since bm_rbm_pt_init: its parity picks the even or the odd ladder pairs
+    Mat ptv, pth;                      // states [pt_rows][V], [pt_rows][H]
+    DevBuf ptpart_v, ptpart_h;         // slot partials of v.vb [ceil(V/16)][pt_rows] and of h.(vW + hb) [ceil(H/16)][pt_rows]
+    DevBuf pt_mult, pt_beta;           // the temperature of every row [pt_rows] (ActArgs::row_mult), the ladder [pt_R]
+    DevArray<int> pt_idx;              // the ladder index of every row [pt_rows]
+    DevArray<unsigned long long> pt_cnt;   // [2][R - 1]: swap attempts, accepts per ladder pair
     int fer_rows = 0;
     DevBuf fer_part, fer_out;          // bm_rbm_free_energy_rows: slot partials [ceil(H/16)][fer_rows] of sum softplus, F [fer_rows]
     // fast-binary mode (bm_bf3.h, bm_rbm_set_fast_binary): bf16 planes of W ([V][H]: the prop-down operand) and of
@@ -589,6 +601,124 @@ static void ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &k
     a.sample = 1; a.states = h->av.p; a.ldo = h->av.ld;
     a.key = key; a.row0 = chain0;
     if (dot) { a.rowdot_out = h->apart_v.p; a.ld_part = h->ais_rows; a.dot_vec = h->adot.p; }
+    launch_act(a, h->stream);
+}
+
+// ---- parallel tempering (bm355.h: bm_rbm_pt_init / _sweep / _read)
+
+// Start of the ensemble: one thread per row and 16-column slot.  v_0 ~ Ber(1/2) at its flat index of the global row (V0 null) or
+// the chain's row of V0 [M][V] for all its R replicas; the slot's partial of v_0.vb in the order of ActArgs::rowdot_out (quads
+// of 4 columns left to right, then (q0 + q1) + (q2 + q3)); row c * R + r starts at ladder index r, temperature beta[r]
+__global__ __launch_bounds__(256) void pt_init_kernel(float *v, int ld, int rows, int R, int V, const float *V0, const float *vb,
+                                                      const float *beta, PhiloxKey key, unsigned long long row0, float *part, int ld_part,
+                                                      float *row_mult, int *idx) {
+    const int ns = (V + 15) / 16;
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)rows * ns) return;
+    const int row = (int)(e / ns), slot = (int)(e % ns);
+    float q[4];
+    for (int g = 0; g < 4; ++g) {
+        float acc = 0.f;
+        for (int r = 0; r < 4; ++r) {
+            const int c = slot * 16 + 4 * g + r;
+            if (c >= V) break;
+            const float x = V0 ? V0[(size_t)(row / R) * V + c]
+                               : (philox_uniform_at(key, (row0 + row) * (unsigned long long)V + c) < 0.5f ? 1.f : 0.f);
+            v[(size_t)row * ld + c] = x;
+            acc += x * vb[c];
+        }
+        q[g] = acc;
+    }
+    part[(size_t)slot * ld_part + row] = (q[0] + q[1]) + (q[2] + q[3]);
+    if (slot == 0) { row_mult[row] = beta[row % R]; idx[row] = row % R; }
+}
+
+// Replica exchange: one thread per chain c and candidate ladder pair (p, p + 1) with p % 2 == parity; the pairs of one step are
+// disjoint.  a / b = the chain's rows that hold ladder index p / p + 1 (found by scanning the chain's R index entries: the
+// entries another thread of this step may change hold neither p nor p + 1 before or after).  E = -(sum of the row's v.vb slots +
+// sum of its h.(vW + hb) slots), ascending, in double; accepted iff delta = (beta_a - beta_b)(E_a - E_b) >= 0 or u < exp(delta).
+// An accepted swap exchanges the rows' temperatures and ladder indices; the states stay where they are.
+__global__ __launch_bounds__(256) void pt_swap_kernel(int M, int R, int parity, const float *part_v, int nslot_v, const float *part_h,
+                                                      int nslot_h, int ld_part, float *row_mult, int *idx, unsigned long long *cnt,
+                                                      PhiloxKey key, unsigned long long chain0) {
+    const int npair = (R - parity) / 2;                  // pairs p = parity, parity + 2, ... <= R - 2
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)M * npair) return;
+    const int c = (int)(e / npair), p = parity + 2 * (int)(e % npair);
+    int ra = -1, rb = -1;
+    for (int r = 0; r < R; ++r) {
+        const int k = idx[(size_t)c * R + r];
+        if (k == p) ra = c * R + r;
+        if (k == p + 1) rb = c * R + r;
+    }
+    if (ra < 0 || rb < 0) return;                        // (cannot happen: the index entries of a chain are a permutation)
+    double sa = 0.0, sb = 0.0;
+    for (int q = 0; q < nslot_v; ++q) { sa += (double)part_v[(size_t)q * ld_part + ra]; sb += (double)part_v[(size_t)q * ld_part + rb]; }
+    for (int q = 0; q < nslot_h; ++q) { sa += (double)part_h[(size_t)q * ld_part + ra]; sb += (double)part_h[(size_t)q * ld_part + rb]; }
+    const float ba = row_mult[ra], bb = row_mult[rb];
+    const double delta = ((double)ba - (double)bb) * ((-sa) - (-sb));
+    const float u = philox_uniform_at(key, (chain0 + (unsigned long long)c) * (unsigned long long)(R - 1) + (unsigned long long)p);
+    const bool accept = delta >= 0.0 || (double)u < exp(delta);
+    atomicAdd(cnt + p, 1ull);
+    if (accept) {
+        atomicAdd(cnt + (R - 1) + p, 1ull);
+        row_mult[ra] = bb; row_mult[rb] = ba;
+        idx[ra] = p + 1; idx[rb] = p;
+    }
+}
+
+// the beta = 1 row of every chain (ladder index R - 1: exactly one) -> dense V_out [M][V] and H_out [M][H] (or null)
+__global__ __launch_bounds__(256) void pt_gather_kernel(int M, int R, const int *idx, const float *v, int ldv, int V, const float *hs, int ldh,
+                                                        int H, float *V_out, float *H_out) {
+    const int c = blockIdx.x;
+    if (c >= M) return;
+    int src = -1;
+    for (int r = 0; r < R; ++r) if (idx[(size_t)c * R + r] == R - 1) src = c * R + r;
+    if (src < 0) return;
+    for (int i = threadIdx.x; i < V; i += blockDim.x) V_out[(size_t)c * V + i] = v[(size_t)src * ldv + i];
+    if (H_out) for (int i = threadIdx.x; i < H; i += blockDim.x) H_out[(size_t)c * H + i] = hs[(size_t)src * ldh + i];
+}
+
+static int ensure_pt_rows(bm_rbm *h, int rows, int R) {
+    if (h->pt_cnt.n < (size_t)2 * std::max(R - 1, 1)) BM_TRY(h->pt_cnt.alloc((size_t)2 * std::max(R - 1, 1)));
+    if (h->pt_beta.n < (size_t)R) BM_TRY(h->pt_beta.alloc(R));
+    if (rows <= h->pt_rows) return 0;
+    h->pt_rows = 0;                                // (set again once every buffer exists: a failure leaves none counted)
+    BM_TRY(h->ptv.alloc(rows, h->V)); BM_TRY(h->pth.alloc(rows, h->H));
+    BM_TRY(h->ptpart_v.alloc((size_t)nslots(h->V) * rows)); BM_TRY(h->ptpart_h.alloc((size_t)nslots(h->H) * rows));
+    BM_TRY(h->pt_mult.alloc(rows)); BM_TRY(h->pt_idx.alloc(rows));
+    h->pt_rows = rows;
+    return 0;
+}
+
+// one row-tempered pass of the ensemble (the RT flavour of act_kernel): up = h ~ Ber(sigmoid(beta_row (vW + hb))) from ptv into
+// pth, leaving the slot partials of h.(vW + hb); down = v ~ Ber(sigmoid(beta_row (hW^T + vb))) from pth into ptv, leaving those
+// of v.vb
+static void pt_pass(bm_rbm *h, bool up, const PhiloxKey &key) {
+    const int rows = h->pt_M * h->pt_R;
+    ActArgs a;
+    memset(&a, 0, sizeof(a));
+    if (up) {
+        up_weights(h, a);
+        a.Q1 = make_operand(h->ptv.p, h->ptv.ld, rows);
+        a.K1 = h->V; a.I = h->H; a.bias = h->hb.p;
+        a.states = h->pth.p; a.ldo = h->pth.ld;
+        a.rowen_out = h->ptpart_h.p;
+    } else {
+        a.P1 = make_operand(h->W.p, h->W.ld, h->V); a.p_xm = 1;
+        a.Q1 = make_operand(h->pth.p, h->pth.ld, rows);
+        a.K1 = h->H; a.I = h->V; a.bias = h->vb.p;
+        a.states = h->ptv.p; a.ldo = h->ptv.ld;
+        a.rowdot_out = h->ptpart_v.p; a.dot_vec = h->vb.p;
+    }
+    a.J = rows;
+    a.mult = 1.0f; a.bmult = 1.0f;                // (not read: row_mult replaces them)
+    a.row_mult = h->pt_mult.p;
+    a.ld_part = h->pt_rows;
+    a.kind = BM_UNIT_BERNOULLI;
+    a.sample = 1;
+    a.key = key;
+    a.row0 = h->pt_chain0 * h->pt_R;
     launch_act(a, h->stream);
 }
 
@@ -1249,6 +1379,76 @@ int bm_rbm_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev
     }
     h->call++;
     BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// Parallel tempering (replica exchange).  The ensemble lives in the handle; see bm355.h for the contract.
+int bm_rbm_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0) {
+    BM_CHECK(h, "null argument");
+    BM_TRY(check_single_joint(h, "bm_rbm_pt_init"));
+    BM_CHECK(n_temps >= 1, "n_temps must be >= 1 (got %d)", (int)n_temps);
+    BM_CHECK(betas_host, "null argument");
+    BM_CHECK(n_chains >= 1 && chain0 >= 0, "bad ensemble (n_chains %d >= 1, chain0 %lld >= 0)", (int)n_chains, (long long)chain0);
+    BM_CHECK((long long)n_chains * n_temps <= (1ll << 24), "n_chains * n_temps = %lld rows exceed 2^24",
+             (long long)n_chains * n_temps);
+    for (int r = 0; r < n_temps; ++r)
+        BM_CHECK(betas_host[r] > 0.f && betas_host[r] <= 1.f && (r == 0 || betas_host[r] > betas_host[r - 1]),
+                 "betas must increase strictly inside (0, 1] (betas[%d] = %g)", r, (double)betas_host[r]);
+    BM_CHECK(betas_host[n_temps - 1] == 1.0f, "the last beta must be 1 (got %g)", (double)betas_host[n_temps - 1]);
+    const int M = n_chains, R = n_temps, rows = M * R;
+    h->pt_M = 0;                                   // (an ensemble exists once everything below went through)
+    BM_TRY(ensure_pt_rows(h, rows, R));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_HIP(hipMemcpy(h->pt_beta.p, betas_host, (size_t)R * sizeof(float), hipMemcpyHostToDevice));
+    BM_HIP(hipMemsetAsync(h->pt_cnt.p, 0, (size_t)2 * std::max(R - 1, 1) * sizeof(unsigned long long), h->stream));
+    const long long nthr = (long long)rows * nslots(h->V);
+    hipLaunchKernelGGL(pt_init_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, h->ptv.p, h->ptv.ld, rows, R, h->V,
+                       V0_dev, (const float *)h->vb.p, (const float *)h->pt_beta.p, make_key(h, SITE_PT_V0, 0),
+                       (unsigned long long)chain0 * (unsigned long long)R, h->ptpart_v.p, h->pt_rows, h->pt_mult.p, h->pt_idx.p);
+    BM_HIP(hipGetLastError());
+    h->pt_M = M; h->pt_R = R; h->pt_chain0 = chain0; h->pt_step = 0;
+    return 0;
+}
+
+int bm_rbm_pt_sweep(bm_rbm *h, int32_t n_steps) {
+    BM_CHECK(h, "null argument");
+    BM_CHECK(h->pt_M > 0, "bm_rbm_pt_sweep: no ensemble (call bm_rbm_pt_init first)");
+    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
+    const int M = h->pt_M, R = h->pt_R;
+    ensure_wt(h);
+    for (int t = 0; t < n_steps; ++t) {
+        pt_pass(h, true, make_key(h, SITE_H, t));
+        const int parity = (int)((h->pt_step + t) & 1);
+        const int npair = (R - parity) / 2;
+        if (npair > 0) {
+            const long long nthr = (long long)M * npair;
+            hipLaunchKernelGGL(pt_swap_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, M, R, parity,
+                               (const float *)h->ptpart_v.p, nslots(h->V), (const float *)h->ptpart_h.p, nslots(h->H), h->pt_rows,
+                               h->pt_mult.p, h->pt_idx.p, h->pt_cnt.p, make_key(h, SITE_PT_SWAP, t), (unsigned long long)h->pt_chain0);
+        }
+        pt_pass(h, false, make_key(h, SITE_V, t));
+    }
+    h->pt_step += n_steps;
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
+    BM_CHECK(h, "null argument");
+    BM_CHECK(h->pt_M > 0, "bm_rbm_pt_read: no ensemble (call bm_rbm_pt_init first)");
+    const int M = h->pt_M, R = h->pt_R;
+    if (V_dev)
+        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, (const float *)h->ptv.p,
+                           h->ptv.ld, h->V, (const float *)h->pth.p, h->pth.ld, h->H, V_dev, H_dev);
+    else BM_CHECK(!H_dev, "bm_rbm_pt_read: H_dev without V_dev");
+    BM_HIP(hipGetLastError());
+    BM_HIP(hipStreamSynchronize(h->stream));
+    if (swaps_host && R > 1) {
+        static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counter width");
+        BM_HIP(hipMemcpy(swaps_host, h->pt_cnt.p, (size_t)2 * (R - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    if (ladder_idx_host) BM_HIP(hipMemcpy(ladder_idx_host, h->pt_idx.p, (size_t)M * R * sizeof(int32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

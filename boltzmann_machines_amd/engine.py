@@ -190,6 +190,30 @@ class RbmEngine(object):
                                             Vmean_d.offset_ptr(ov) if Vmean_d is not None else None, B, n_steps,
                                             clamp_val_d.offset_ptr(ov), clamp_mask_d.offset_ptr(ov)))
 
+    # parallel tempering (bm355.h: bm_rbm_pt_init / _sweep / _read)
+    def pt_init(self, n_chains, betas, V0_d=None, chain0=0):
+        """build the tempered ensemble of n_chains x len(betas) replicas in the handle; V0_d [n_chains, V] (DeviceArray): every
+        chain's replicas start there, None: v_0 ~ Ber(1/2)"""
+        b = np.ascontiguousarray(betas, dtype=np.float32).ravel()
+        check(self.lib.bm_rbm_pt_init(self._h, int(n_chains), len(b), b.ctypes.data_as(C.c_void_p),
+                                      V0_d.ptr if V0_d is not None else None, int(chain0)))
+        self._pt_shape = (int(n_chains), len(b))
+
+    def pt_sweep(self, n_steps):
+        """n_steps of (tempered prop-up, replica exchange, tempered prop-down) on the whole ensemble"""
+        check(self.lib.bm_rbm_pt_sweep(self._h, int(n_steps)))
+
+    def pt_read(self, Vd=None, Hd=None):
+        """beta = 1 rows -> Vd [n_chains, V] / Hd [n_chains, H] (DeviceArrays, optional); returns (swaps [2, R-1] int64:
+        attempts and accepts per ladder pair, ladder_idx [n_chains, R] int32: the ladder index of every row)"""
+        M, R = getattr(self, '_pt_shape', (0, 1))
+        swaps = np.zeros((2, max(R - 1, 0)), dtype=np.int64)
+        idx = np.zeros((M, R), dtype=np.int32)
+        check(self.lib.bm_rbm_pt_read(self._h, Vd.ptr if Vd is not None else None, Hd.ptr if Hd is not None else None,
+                                      swaps.ctypes.data_as(C.c_void_p) if swaps.size else None,
+                                      idx.ctypes.data_as(C.c_void_p) if idx.size else None))
+        return swaps, idx
+
     def stream(self):
         p = C.c_void_p()
         check(self.lib.bm_rbm_stream(self._h, C.byref(p)))

@@ -581,6 +581,48 @@ class BaseRBM(EngineModel):
             return V, np.where(observed, X, Pd.numpy())
         return V
 
+    # ---- unconditional sampling by parallel tempering (no counterpart in the reference) -----------
+    @single_joint_only
+    @run_on_engine(update_seed=True)
+    def sample_v(self, n_samples, n_gibbs_steps=1000, n_temperatures=10, betas=None, V_init=None, return_stats=False):
+        """Unconditional samples of the visible units by parallel tempering (replica exchange; Desjardins et al. 2010,
+        Cho et al. 2010): `n_samples` independent chains, each with one replica per temperature of the ladder
+        0 < betas[0] < ... < betas[-1] = 1, run `n_gibbs_steps` steps of (h ~ p_beta(h|v), exchange of neighbouring
+        temperatures, v ~ p_beta(v|h)); the replica at beta = 1 of every chain is returned.  The hot replicas cross between
+        modes a single Gibbs chain stays in, and the exchanges carry those moves down to beta = 1.
+
+        betas : the ladder; None: float32(linspace(0, 1, n_temperatures + 1)[1:]).  `n_temperatures=1` is plain Gibbs.
+        V_init : [n_samples, n_visible] start of every chain (all its replicas); None: v_0 ~ Ber(1/2).
+        Returns [n_samples, n_visible]; with `return_stats` also the acceptance rate of every neighbouring pair of
+        temperatures, [n_temperatures - 1] (accepts / attempts).
+        Both layers are always sampled, dropout is not applied.  One seed is drawn from the model's host stream; no
+        parameter is changed.  In a multi-GPU job every rank runs all chains."""
+        eng = self._on_device()
+        n_samples = int(n_samples)
+        if n_samples < 1 or int(n_gibbs_steps) < 1:
+            raise ValueError('`n_samples` and `n_gibbs_steps` must be >= 1 (got {0}, {1})'.format(n_samples, n_gibbs_steps))
+        if betas is None:
+            if int(n_temperatures) < 1:
+                raise ValueError('`n_temperatures` must be >= 1 (got {0})'.format(n_temperatures))
+            betas = np.linspace(0., 1., int(n_temperatures) + 1)[1:]
+        betas = np.asarray(betas, dtype=np.float32).ravel()
+        if len(betas) < 1 or betas[-1] != 1. or betas[0] <= 0. or np.any(np.diff(betas) <= 0.):
+            raise ValueError('`betas` must increase strictly inside (0, 1] and end at 1 (got {0})'.format(betas))
+        V0d = None
+        if V_init is not None:
+            V_init = np.ascontiguousarray(V_init, dtype=np.float32)
+            if V_init.shape != (n_samples, self.n_visible):
+                raise ValueError('`V_init` has invalid shape {0}: expected [{1}, {2}]'.format(V_init.shape, n_samples, self.n_visible))
+            V0d = self._to_device(V_init)
+        eng.pt_init(n_samples, betas, V0d)
+        eng.pt_sweep(int(n_gibbs_steps))
+        Vd = _ffi.DeviceArray((n_samples, self.n_visible), np.float32)
+        swaps, _ = eng.pt_read(Vd)
+        V = Vd.numpy()
+        if return_stats:
+            return V, swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
+        return V
+
     # ---- likelihood (no counterpart in the reference: its only AIS is the DBM's) ----------------
     def _check_single_joint(self, what):
         name = '%s.%s' % (self.__class__.__name__, what)

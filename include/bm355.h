@@ -202,6 +202,37 @@ int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_ste
 int bm_rbm_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev, int32_t B, int32_t n_steps,
                          const float *clamp_val_dev, const float *clamp_mask_dev);
 
+/* Parallel tempering (replica exchange; Desjardins et al. 2010, Cho et al. 2010): unconditional samples of a
+ * trained RBM that mix between modes.  The tempered family is p_beta(v, h) ~ exp(-beta E(v, h)), E = -v.vb - h.hb - vWh, on a
+ * ladder betas[0] < ... < betas[R-1] = 1.  An ensemble of n_chains independent chains with R = n_temps replicas each lives in
+ * the handle: rows are chain-major (row c R + r is slot r of chain c; a slot starts at ladder index r), allocated on demand -
+ * max_batch does not bound it - and freed with the handle.  Every replica of every chain takes part in ONE launch per pass,
+ * each row at its own temperature (the RT flavour of act_kernel, ActArgs::row_mult).
+ *   bm_rbm_pt_init   builds the ensemble: v_0 ~ Ber(1/2) (site 11, the handle's current call) or, with V0_dev [n_chains,
+ *                    n_visible] (device, dense), every chain's R replicas start from its row of V0_dev.  Resets the swap counters
+ *                    and the step parity.  Does not advance the call counter.
+ *   bm_rbm_pt_sweep  n_steps steps; step t: h ~ p_beta(h | v) for every row (site SITE_H + 16 t), leaving h.(vW + hb) as slot
+ *                    partials; the swap step; v ~ p_beta(v | h) (site SITE_V + 16 t), leaving v.vb.  The swap step proposes,
+ *                    per chain, to exchange the replicas at ladder indices (p, p + 1) for the even p when the global step number
+ *                    (counted from bm_rbm_pt_init, across calls) is even, for the odd p otherwise:
+ *                    delta = (beta_p - beta_{p+1})(E_p - E_{p+1}) in double from the float32 slot partials added in ascending
+ *                    order; accepted iff delta >= 0 or u < exp(delta), u the uniform at flat index (chain0 + c)(R - 1) + p of
+ *                    site 10 + 16 t.  An accepted swap exchanges the two rows' temperatures and ladder indices; states stay in
+ *                    place.  The call counter advances once per bm_rbm_pt_sweep.
+ *   bm_rbm_pt_read   copies, for every chain, the row at beta = 1 to V_dev [n_chains, n_visible] (NULL: nothing is copied) and
+ *                    its hidden states - the ones that row's v was drawn from - to H_dev [n_chains, n_hidden] (NULL ok);
+ *                    swaps_host [2][R-1] (NULL ok) receives attempts, then accepts, per ladder pair since bm_rbm_pt_init;
+ *                    ladder_idx_host [n_chains R] (NULL ok) the ladder index of every row.  Waits for the stream.
+ * The global row of the RNG streams is (chain0 + c) R + r: chains [c, c + n) of a larger ensemble are the ensemble of n chains
+ * at chain0 = c, bit for bit.  Always per-pass fp32 launches (as bm_rbm_ais): BM355_DEBUG=chain= and fast-binary mode do not
+ * change the bits.  With n_temps = 1 a sweep from V0 equals bm_rbm_gibbs_clamped with an all-zero mask from the same V0, seed
+ * and call, bit for bit.  No parameter, momentum buffer or workspace another entry point reads is touched.
+ * Errors: n_temps < 1, n_chains < 1, betas not strictly increasing inside (0, 1] or betas[R-1] != 1, sweep or read before
+ * init, n_steps < 1, and the refusals of bm_rbm_ais (Gaussian visible units, Multinomial hidden units, dbm_first / dbm_last). */
+int bm_rbm_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0);
+int bm_rbm_pt_sweep(bm_rbm *h, int32_t n_steps);
+int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host);
+
 /* the handle's hipStream_t (as void*), so a host can enqueue collectives on
  * the same stream (torch.cuda.ExternalStream) without host synchronisation. */
 int bm_rbm_stream(bm_rbm *h, void **out_stream);
