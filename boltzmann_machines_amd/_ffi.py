@@ -144,6 +144,8 @@ SIGNATURES = {
     'bm_rbm_pt_init': [_vp, _i32, _i32, _vp, _vp, _i64],
     'bm_rbm_pt_sweep': [_vp, _i32],
     'bm_rbm_pt_read': [_vp, _vp, _vp, _vp, _vp],
+    'bm_rbm_train_step_pt': [_vp, _vp, _i32, _f32, _f32, _i32],
+    'bm_rbm_train_epoch_pt': [_vp, _vp, _i64, _i32, _f32, _f32, _i32],
     'bm_rbm_stream': [_vp, C.POINTER(_vp)],
     'bm_rbm_profile': [_vp, _i32],
     'bm_rbm_kernel_times': [_vp, _fp, _ip],

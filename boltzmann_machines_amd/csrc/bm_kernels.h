@@ -113,6 +113,12 @@ struct ActArgs {
     // products are exact.  For the prop-up this is h.(vW + hb), the hidden half of the energy the swap step needs.
     const float *row_mult;
     float *rowen_out;
+    // The hand-over of a tempered update (RT only, the other flavours never read these): rows are grouped in
+    // runs of sel_R (the replicas of one chain), and the row of group c = j / sel_R whose row_mult[j] == 1 - the caller
+    // guarantees exactly one per group - ALSO stores its states at sel_out + c * sel_ld, for the groups c < sel_rows: the
+    // dense negative particles of the update that follows.  The lane holds row_mult[j] already; no further load.  Null: off.
+    float *sel_out;
+    int sel_ld, sel_R, sel_rows;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -453,6 +459,14 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                 store4<HWMATH>(a.negmeans, o, nm, nvalid, v4 && (((uintptr_t)a.negmeans & 15u) == 0));
             }
             if (a.states) store4<HWMATH>(a.states, o, s, nvalid, v4 && (((uintptr_t)a.states & 15u) == 0));
+            if constexpr (RT) {                // the chain's beta = 1 row repeats its state stores in the dense particle store
+                if (a.sel_out && rm == 1.0f) {
+                    const int c = j / a.sel_R;
+                    if (c < a.sel_rows)
+                        store4<HWMATH>(a.sel_out, (size_t)c * a.sel_ld + ib, s, nvalid,
+                                       nvalid == 4 && ((a.sel_ld & 3) == 0) && (((uintptr_t)a.sel_out & 15u) == 0));
+                }
+            }
             if (HWMATH && a.states16) {        // fast-binary strip kernel only: bf16 shadow of the {0,1} states (exact),
                                                // pitch ld16 % 64 == 0; fp32 launches get it from shadow16_kernel (launch_act)
                 uint16_t *d = a.states16 + (size_t)j * a.ld16 + ib;

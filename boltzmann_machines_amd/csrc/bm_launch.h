@@ -338,7 +338,7 @@ static inline Tuned tuned_act(const ActArgs &a, hipStream_t st) {
         if (!a.clamp_mask && !a.row_mult) return tune_act_shape(a, st, flags);
         ActArgs plain = a;
         plain.clamp_mask = plain.clamp_val = nullptr; plain.ld_clamp = 0;
-        if (a.row_mult) { plain.row_mult = nullptr; plain.rowen_out = nullptr; plain.mult = plain.bmult = 1.0f; }
+        if (a.row_mult) { plain.row_mult = nullptr; plain.rowen_out = nullptr; plain.sel_out = nullptr; plain.mult = plain.bmult = 1.0f; }
         return tune_act_shape(plain, st, flags);
     });
 }

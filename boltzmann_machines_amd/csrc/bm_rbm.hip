@@ -606,9 +606,26 @@ static void ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &k
 
 // ---- parallel tempering (bm355.h: bm_rbm_pt_init / _sweep / _read)
 
+// The partial of x.vb over the 16-column slot `slot`, in the order of ActArgs::rowdot_out (quads of 4 columns left
+// to right, then (q0 + q1) + (q2 + q3)); x_at(c) supplies column c of the row (and may store it)
+template <class F>
+__device__ __forceinline__ float pt_vb_slot(int slot, int V, const float *vb, F x_at) {
+    float q[4];
+    for (int g = 0; g < 4; ++g) {
+        float acc = 0.f;
+        for (int r = 0; r < 4; ++r) {
+            const int c = slot * 16 + 4 * g + r;
+            if (c >= V) break;
+            acc += x_at(c) * vb[c];
+        }
+        q[g] = acc;
+    }
+    return (q[0] + q[1]) + (q[2] + q[3]);
+}
+
 // Start of the ensemble: one thread per row and 16-column slot.  v_0 ~ Ber(1/2) at its flat index of the global row (V0 null) or
-// the chain's row of V0 [M][V] for all its R replicas; the slot's partial of v_0.vb in the order of ActArgs::rowdot_out (quads
-// of 4 columns left to right, then (q0 + q1) + (q2 + q3)); row c * R + r starts at ladder index r, temperature beta[r]
+// the chain's row of V0 [M][V] for all its R replicas; the slot's partial of v_0.vb (pt_vb_slot); row c * R + r starts at ladder
+// index r, temperature beta[r]
 __global__ __launch_bounds__(256) void pt_init_kernel(float *v, int ld, int rows, int R, int V, const float *V0, const float *vb,
                                                       const float *beta, PhiloxKey key, unsigned long long row0, float *part, int ld_part,
                                                       float *row_mult, int *idx) {
@@ -616,21 +633,24 @@ __global__ __launch_bounds__(256) void pt_init_kernel(float *v, int ld, int rows
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (long long)rows * ns) return;
     const int row = (int)(e / ns), slot = (int)(e % ns);
-    float q[4];
-    for (int g = 0; g < 4; ++g) {
-        float acc = 0.f;
-        for (int r = 0; r < 4; ++r) {
-            const int c = slot * 16 + 4 * g + r;
-            if (c >= V) break;
-            const float x = V0 ? V0[(size_t)(row / R) * V + c]
-                               : (philox_uniform_at(key, (row0 + row) * (unsigned long long)V + c) < 0.5f ? 1.f : 0.f);
-            v[(size_t)row * ld + c] = x;
-            acc += x * vb[c];
-        }
-        q[g] = acc;
-    }
-    part[(size_t)slot * ld_part + row] = (q[0] + q[1]) + (q[2] + q[3]);
+    part[(size_t)slot * ld_part + row] = pt_vb_slot(slot, V, vb, [&](int c) {
+        const float x = V0 ? V0[(size_t)(row / R) * V + c]
+                           : (philox_uniform_at(key, (row0 + row) * (unsigned long long)V + c) < 0.5f ? 1.f : 0.f);
+        v[(size_t)row * ld + c] = x;
+        return x;
+    });
     if (slot == 0) { row_mult[row] = beta[row % R]; idx[row] = row % R; }
+}
+
+// Re-scoring at the start of a tempered update: the v.vb slot partials of every row from its stored state and the
+// CURRENT vb - the previous update changed vb after the prop-down that left them.  One thread per row and slot, the same
+// computation as pt_init_kernel's: with an unchanged vb it rewrites the bits that are there.
+__global__ __launch_bounds__(256) void pt_rescore_kernel(const float *v, int ld, int rows, int V, const float *vb, float *part, int ld_part) {
+    const int ns = (V + 15) / 16;
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)rows * ns) return;
+    const int row = (int)(e / ns), slot = (int)(e % ns);
+    part[(size_t)slot * ld_part + row] = pt_vb_slot(slot, V, vb, [&](int c) { return v[(size_t)row * ld + c]; });
 }
 
 // Replica exchange: one thread per chain c and candidate ladder pair (p, p + 1) with p % 2 == parity; the pairs of one step are
@@ -667,15 +687,15 @@ __global__ __launch_bounds__(256) void pt_swap_kernel(int M, int R, int parity, 
     }
 }
 
-// the beta = 1 row of every chain (ladder index R - 1: exactly one) -> dense V_out [M][V] and H_out [M][H] (or null)
+// the beta = 1 row of every chain (ladder index R - 1: exactly one) -> V_out [M][V] pitch ldvo and dense H_out [M][H] (or null)
 __global__ __launch_bounds__(256) void pt_gather_kernel(int M, int R, const int *idx, const float *v, int ldv, int V, const float *hs, int ldh,
-                                                        int H, float *V_out, float *H_out) {
+                                                        int H, float *V_out, int ldvo, float *H_out) {
     const int c = blockIdx.x;
     if (c >= M) return;
     int src = -1;
     for (int r = 0; r < R; ++r) if (idx[(size_t)c * R + r] == R - 1) src = c * R + r;
     if (src < 0) return;
-    for (int i = threadIdx.x; i < V; i += blockDim.x) V_out[(size_t)c * V + i] = v[(size_t)src * ldv + i];
+    for (int i = threadIdx.x; i < V; i += blockDim.x) V_out[(size_t)c * ldvo + i] = v[(size_t)src * ldv + i];
     if (H_out) for (int i = threadIdx.x; i < H; i += blockDim.x) H_out[(size_t)c * H + i] = hs[(size_t)src * ldh + i];
 }
 
@@ -694,7 +714,8 @@ static int ensure_pt_rows(bm_rbm *h, int rows, int R) {
 // one row-tempered pass of the ensemble (the RT flavour of act_kernel): up = h ~ Ber(sigmoid(beta_row (vW + hb))) from ptv into
 // pth, leaving the slot partials of h.(vW + hb); down = v ~ Ber(sigmoid(beta_row (hW^T + vb))) from pth into ptv, leaving those
 // of v.vb
-static void pt_pass(bm_rbm *h, bool up, const PhiloxKey &key) {
+// sel_rows > 0 (down only): the beta = 1 row of every chain c < sel_rows is also left in vs[c] (ActArgs::sel_out)
+static void pt_pass(bm_rbm *h, bool up, const PhiloxKey &key, int sel_rows = 0) {
     const int rows = h->pt_M * h->pt_R;
     ActArgs a;
     memset(&a, 0, sizeof(a));
@@ -719,7 +740,24 @@ static void pt_pass(bm_rbm *h, bool up, const PhiloxKey &key) {
     a.sample = 1;
     a.key = key;
     a.row0 = h->pt_chain0 * h->pt_R;
+    if (sel_rows > 0 && !up) { a.sel_out = h->vs.p; a.sel_ld = h->vs.ld; a.sel_R = h->pt_R; a.sel_rows = sel_rows; }
     launch_act(a, h->stream);
+}
+
+// step t of a tempered call: the RT prop-up, the swap of the parity of the global step number, the RT prop-down (which hands the
+// beta = 1 rows of the chains [0, sel_rows) over to vs, if asked)
+static void pt_step(bm_rbm *h, int t, int sel_rows = 0) {
+    const int M = h->pt_M, R = h->pt_R;
+    pt_pass(h, true, make_key(h, SITE_H, t));
+    const int parity = (int)((h->pt_step + t) & 1);
+    const int npair = (R - parity) / 2;
+    if (npair > 0) {
+        const long long nthr = (long long)M * npair;
+        hipLaunchKernelGGL(pt_swap_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, M, R, parity,
+                           (const float *)h->ptpart_v.p, nslots(h->V), (const float *)h->ptpart_h.p, nslots(h->H), h->pt_rows,
+                           h->pt_mult.p, h->pt_idx.p, h->pt_cnt.p, make_key(h, SITE_PT_SWAP, t), (unsigned long long)h->pt_chain0);
+    }
+    pt_pass(h, false, make_key(h, SITE_V, t), sel_rows);
 }
 
 extern "C" {
@@ -1414,20 +1452,8 @@ int bm_rbm_pt_sweep(bm_rbm *h, int32_t n_steps) {
     BM_CHECK(h, "null argument");
     BM_CHECK(h->pt_M > 0, "bm_rbm_pt_sweep: no ensemble (call bm_rbm_pt_init first)");
     BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
-    const int M = h->pt_M, R = h->pt_R;
     ensure_wt(h);
-    for (int t = 0; t < n_steps; ++t) {
-        pt_pass(h, true, make_key(h, SITE_H, t));
-        const int parity = (int)((h->pt_step + t) & 1);
-        const int npair = (R - parity) / 2;
-        if (npair > 0) {
-            const long long nthr = (long long)M * npair;
-            hipLaunchKernelGGL(pt_swap_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, M, R, parity,
-                               (const float *)h->ptpart_v.p, nslots(h->V), (const float *)h->ptpart_h.p, nslots(h->H), h->pt_rows,
-                               h->pt_mult.p, h->pt_idx.p, h->pt_cnt.p, make_key(h, SITE_PT_SWAP, t), (unsigned long long)h->pt_chain0);
-        }
-        pt_pass(h, false, make_key(h, SITE_V, t));
-    }
+    for (int t = 0; t < n_steps; ++t) pt_step(h, t);
     h->pt_step += n_steps;
     h->call++;
     BM_HIP(hipGetLastError());
@@ -1440,7 +1466,7 @@ int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, i
     const int M = h->pt_M, R = h->pt_R;
     if (V_dev)
         hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, (const float *)h->ptv.p,
-                           h->ptv.ld, h->V, (const float *)h->pth.p, h->pth.ld, h->H, V_dev, H_dev);
+                           h->ptv.ld, h->V, (const float *)h->pth.p, h->pth.ld, h->H, V_dev, h->V, H_dev);
     else BM_CHECK(!H_dev, "bm_rbm_pt_read: H_dev without V_dev");
     BM_HIP(hipGetLastError());
     BM_HIP(hipStreamSynchronize(h->stream));
@@ -1449,6 +1475,53 @@ int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, i
         BM_HIP(hipMemcpy(swaps_host, h->pt_cnt.p, (size_t)2 * (R - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
     }
     if (ladder_idx_host) BM_HIP(hipMemcpy(ladder_idx_host, h->pt_idx.p, (size_t)M * R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// One update whose negative phase is the tempered ensemble (bm355.h).  No host synchronisation.
+int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
+    BM_CHECK(h && X_dev, "null argument");
+    BM_TRY(check_dw(h, "bm_rbm_train_step_pt"));
+    BM_CHECK(h->pt_M > 0, "bm_rbm_train_step_pt: no ensemble (call bm_rbm_pt_init first)");
+    BM_CHECK(h->cfg.dropout < 0.f, "bm_rbm_train_step_pt: the tempered family has no dropout (this handle's is %g)", (double)h->cfg.dropout);
+    const int Bmax = std::min(h->maxB, h->pt_M);
+    BM_CHECK(B >= 1 && B <= Bmax, "bm_rbm_train_step_pt: batch %d outside [1, min(max_batch=%d, n_chains=%d)]", (int)B, h->maxB, h->pt_M);
+    BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
+    static const bool sel_in_pass = !dbg("pt_sel") || atoi(dbg("pt_sel")) != 0;     // BM355_DEBUG=pt_sel=0: a gather launch instead
+    const int rows = h->pt_M * h->pt_R;
+    ensure_wt(h);
+    // 1. the v.vb partials of the swap energy under the vb of NOW (the previous update changed it)
+    const long long nthr = (long long)rows * nslots(h->V);
+    hipLaunchKernelGGL(pt_rescore_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, (const float *)h->ptv.p, h->ptv.ld,
+                       rows, h->V, (const float *)h->vb.p, h->ptpart_v.p, h->pt_rows);
+    // 2. positive phase: the h0 means alone
+    h->Xin = X_dev; h->Xin_ld = h->V;
+    h->fe_in_chain = false;
+    launch_up(h, X_dev, h->V, B, h->h0m.p, nullptr, h->h0m.ld, 0, SITE_H0, 0);
+    // 3. + 4. the tempered steps; the last prop-down leaves the beta = 1 rows of the chains [0, B) in vs
+    for (int t = 0; t < k; ++t) pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
+    if (!sel_in_pass)
+        hipLaunchKernelGGL(pt_gather_kernel, dim3(B), dim3(256), 0, h->stream, (int)B, h->pt_R, (const int *)h->pt_idx.p, (const float *)h->ptv.p,
+                           h->ptv.ld, h->V, (const float *)nullptr, 0, h->H, h->vs.p, h->vs.ld, (float *)nullptr);
+    // 5. negative means: only -h is consumed (run_chain's neg_only form)
+    launch_up(h, h->vs.p, h->vs.ld, B, nullptr, nullptr, h->hm.ld, 0, SITE_H, 0, h->hneg.p);
+    h->hm_is_neg = true;
+    // 6. + 7.
+    launch_update_fused(h, B, lr, mom);
+    h->pt_step += k;
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// the native batch loop of bm_rbm_train_step_pt (as bm_rbm_train_epoch is to bm_rbm_train_step)
+int bm_rbm_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t k) {
+    BM_CHECK(h && X_dev, "null argument");
+    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
+    for (int64_t s = 0; s < N; s += batch) {
+        const int B = (int)((N - s < batch) ? (N - s) : batch);
+        BM_TRY(bm_rbm_train_step_pt(h, X_dev + (size_t)s * h->V, B, lr, mom, k));
+    }
     return 0;
 }
 

@@ -198,6 +198,7 @@ class RbmEngine(object):
         check(self.lib.bm_rbm_pt_init(self._h, int(n_chains), len(b), b.ctypes.data_as(C.c_void_p),
                                       V0_d.ptr if V0_d is not None else None, int(chain0)))
         self._pt_shape = (int(n_chains), len(b))
+        self._pt_train_key = None                 # (whoever builds the ensemble for training records its ladder: rbm.py)
 
     def pt_sweep(self, n_steps):
         """n_steps of (tempered prop-up, replica exchange, tempered prop-down) on the whole ensemble"""
@@ -213,6 +214,14 @@ class RbmEngine(object):
                                       swaps.ctypes.data_as(C.c_void_p) if swaps.size else None,
                                       idx.ctypes.data_as(C.c_void_p) if idx.size else None))
         return swaps, idx
+
+    # tempered negative phase (bm355.h: bm_rbm_train_step_pt / _train_epoch_pt); the ensemble of pt_init supplies the particles
+    def train_step_pt(self, Xd, B, lr, momentum, k, row=0):
+        check(self.lib.bm_rbm_train_step_pt(self._h, Xd.offset_ptr(row * self.V), B, lr, momentum, k))
+
+    def train_epoch_pt(self, Xd, N, batch, lr, momentum, k, row=0):
+        """N rows starting at `row`, consecutive batches of `batch` rows, one tempered update each, driven from C"""
+        check(self.lib.bm_rbm_train_epoch_pt(self._h, Xd.offset_ptr(row * self.V), N, batch, lr, momentum, k))
 
     def stream(self):
         p = C.c_void_p()

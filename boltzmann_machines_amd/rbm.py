@@ -143,6 +143,10 @@ class BaseRBM(EngineModel):
         self.epoch_ = 0
         self.iter_ = 0
 
+        # the negative phase of fit(): None = CD-k from the batch, else (betas, n_chains) of the tempered ensemble
+        # (set_negative_phase; not a constructor keyword and not written to checkpoints)
+        self._neg_phase = None
+
     # ---- variables -----------------------------------------------------------------
     def _sigma_vector(self):
         return np.ones(self.n_visible, dtype=self._np_dtype)
@@ -277,6 +281,9 @@ class BaseRBM(EngineModel):
         results = {m: [] for m in names}
         lr, mom, k = self._feed()
         every = self.metrics_config['train_metrics_every_iter']
+        if self._neg_phase is not None:
+            out = self._train_epoch_tempered(eng, Xd, N, names, results, lr, mom, k, every, after_first)
+            return (lambda: out) if defer else out
         if getattr(self, '_dp', None) is not None:
             # data-parallel epoch: global minibatches of world * batch_size rows (train metrics are not fetched:
             # they would be rank-local numbers; validation metrics are evaluated on this rank's replica)
@@ -369,6 +376,103 @@ class BaseRBM(EngineModel):
         out = {m: (np.mean(r) if r else None) for m, r in results.items()}
         return (lambda: out) if defer else out
 
+    # ---- tempered negative phase (no counterpart in the reference) --------------
+    def _check_tempered(self, what='set_negative_phase'):
+        self._check_single_joint(what)
+        name = '%s.%s' % (self.__class__.__name__, what)
+        if self.dropout is not None:
+            raise NotImplementedError('%s: a tempered negative phase is not combined with dropout (the tempered family '
+                                      'p_beta has none)' % name)
+        if os.environ.get('BM355_DATA_PARALLEL', '0') == '1':
+            raise NotImplementedError('%s: a tempered negative phase is not combined with BM355_DATA_PARALLEL (chains are '
+                                      'not sharded over ranks)' % name)
+
+    def set_negative_phase(self, kind='cd', n_temperatures=10, betas=None, n_chains=None):
+        """Where the negative particles of `fit` come from.
+
+        kind='cd' (the default, the reference's training graph): a k-step Gibbs chain started at the minibatch.
+        kind='tempered': parallel tempering (Desjardins et al. 2010, Cho et al. 2010).  A persistent ensemble of `n_chains`
+        chains with one replica per temperature of the ladder 0 < betas[0] < ... < betas[-1] = 1 lives on the device; every
+        update sweeps all of it for `n_gibbs_steps` tempered steps (h ~ p_beta(h|v), exchange of neighbouring temperatures,
+        v ~ p_beta(v|h) - as `sample_v`) and takes the beta = 1 replicas of the first len(batch) chains as its negative
+        particles; the positive phase, momentum, l2 and the sparsity terms are those of CD.  The hot replicas keep crossing
+        between the modes a CD or single persistent chain stays in.
+
+        betas : the ladder; None: float32(linspace(0, 1, n_temperatures + 1)[1:]), `sample_v`'s default.
+        n_chains : None: `batch_size`; must be >= `batch_size`.
+        The ensemble is built at the first update of every `fit()` call (v_0 ~ Ber(1/2) under that call's seed from the host
+        stream: no further seed is drawn) and again whenever the ladder or `n_chains` changed; `sample_v` replaces it.
+        Neither the ensemble nor this setting is written to checkpoints - params.json keeps the reference's schema - so a
+        loaded model trains with CD until this method is called again, and a resumed fit starts a fresh ensemble.
+        A train-metrics iteration reports the metrics of the CD reconstruction (as `kind='cd'` would) and then makes its
+        tempered update.  BernoulliRBM in float32 only: GaussianRBM, MultinomialRBM, float64, `dbm_first` / `dbm_last`,
+        dropout and BM355_DATA_PARALLEL jobs raise NotImplementedError.  Returns self."""
+        if kind == 'cd':
+            self._neg_phase = None
+            return self
+        if kind != 'tempered':
+            raise ValueError("`kind` must be 'cd' or 'tempered' (got {0!r})".format(kind))
+        self._check_tempered()
+        if betas is None:
+            if int(n_temperatures) < 1:
+                raise ValueError('`n_temperatures` must be >= 1 (got {0})'.format(n_temperatures))
+            betas = np.linspace(0., 1., int(n_temperatures) + 1)[1:]
+        betas = np.asarray(betas, dtype=np.float32).ravel()
+        if len(betas) < 1 or betas[-1] != 1. or betas[0] <= 0. or np.any(np.diff(betas) <= 0.):
+            raise ValueError('`betas` must increase strictly inside (0, 1] and end at 1 (got {0})'.format(betas))
+        n_chains = self.batch_size if n_chains is None else int(n_chains)
+        if n_chains < self.batch_size:
+            raise ValueError('`n_chains` must be >= batch_size (got {0} < {1})'.format(n_chains, self.batch_size))
+        self._neg_phase = (tuple(float(b) for b in betas), n_chains)
+        return self
+
+    def tempering_stats(self):
+        """Acceptance rate (accepts / attempts) of every neighbouring pair of temperatures, [n_temperatures - 1], since the
+        ensemble of the tempered negative phase was built.  Waits for the device; copies no states."""
+        eng = self._engine
+        if not isinstance(eng, RbmEngine) or getattr(eng, '_pt_train_key', None) is None:
+            raise RuntimeError('`tempering_stats`: no tempered ensemble (call set_negative_phase(\'tempered\') and fit first)')
+        swaps, _ = eng.pt_read()
+        return swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
+
+    def _check_tempered_fit(self):
+        """what may have changed since set_negative_phase (set_params): refused before an epoch starts"""
+        self._check_tempered('fit')
+        if getattr(self, '_dp', None) is not None:
+            raise NotImplementedError('%s.fit: a tempered negative phase is not combined with data parallelism' % self.__class__.__name__)
+        if self._neg_phase[1] < self.batch_size:
+            raise ValueError('`n_chains` must be >= batch_size (got {0} < {1})'.format(self._neg_phase[1], self.batch_size))
+
+    def _train_epoch_tempered(self, eng, Xd, N, names, results, lr, mom, k, every, after_first):
+        """one epoch with the tempered negative phase: runs of batches go to bm_rbm_train_epoch_pt; a metrics iteration
+        fetches synchronously (bm_rbm_metrics, the CD reconstruction), then updates (not optimised)"""
+        self._check_tempered_fit()
+        betas, n_chains = self._neg_phase
+        if getattr(self, '_pt_fresh', True) or getattr(eng, '_pt_train_key', None) != self._neg_phase:
+            eng.pt_init(n_chains, betas)
+            eng._pt_train_key = self._neg_phase
+            self._pt_fresh = False
+        run_start = None
+        for start in range(0, N, self.batch_size):
+            B = min(self.batch_size, N - start)
+            self.iter_ += 1
+            if self.iter_ % every == 0:
+                if run_start is not None:
+                    eng.train_epoch_pt(Xd, start - run_start, self.batch_size, lr, mom, k, row=run_start)
+                    run_start = None
+                out = eng.metrics(Xd, B, k, row=start)
+                vals = dict(msre=out[0], pll=out[1], l2_loss=out[2])
+                for m in names:
+                    results[m].append(vals[m])
+                eng.train_step_pt(Xd, B, lr, mom, k, row=start)
+            elif run_start is None:
+                run_start = start
+        if run_start is not None:
+            eng.train_epoch_pt(Xd, N - run_start, self.batch_size, lr, mom, k, row=run_start)
+        if after_first is not None:
+            after_first()
+        return {m: (np.mean(r) if r else None) for m, r in results.items()}
+
     def _run_val_metrics(self, Xvd, N):
         eng = self._on_device()
         names = sorted(m for m in self._val_metrics_names if self.metrics_config[m])
@@ -395,6 +499,9 @@ class BaseRBM(EngineModel):
 
     def _fit(self, X, X_val=None, *args, **kwargs):
         self._on_device()
+        self._pt_fresh = True          # a tempered negative phase builds its ensemble at this call's first update
+        if self._neg_phase is not None:
+            self._check_tempered_fit()
         Xd = self._to_device(X, 'fit_X')
         N = len(X)
         Xvd, Nv = None, 0

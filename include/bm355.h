@@ -233,6 +233,26 @@ int bm_rbm_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *be
 int bm_rbm_pt_sweep(bm_rbm *h, int32_t n_steps);
 int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host);
 
+/* Tempered negative phase: one CD-style update whose negative particles are the beta = 1 rows of the
+ * ensemble bm_rbm_pt_init built, instead of a chain started at the batch.  On the handle's stream, no host synchronisation:
+ *   1. the v.vb slot partials of every ensemble row are recomputed from its state and the CURRENT vb (the previous update
+ *      changed vb after the prop-down that left them; with an unchanged vb this rewrites the same bits);
+ *   2. positive phase: the means E[h | x] of the batch (nothing is drawn);
+ *   3. n_gibbs_steps steps of bm_rbm_pt_sweep on all n_chains R rows (sites SITE_H + 16 t, 10 + 16 t, SITE_V + 16 t of the
+ *      handle's call counter; the swap parity continues the ensemble's step count);
+ *   4. the last prop-down also leaves the beta = 1 row of every chain c < B as negative particle c (in its epilogue;
+ *      BM355_DEBUG=pt_sel=0: by a gather launch - the same bits);
+ *   5. negative phase: the means E[h | particle];
+ *   6. the fused update of bm_rbm_train_step (momentum, l2, sparsity, q_means) on these statistics.
+ * The call counter advances once per update, the ensemble's step count by n_gibbs_steps.  A batch shorter than n_chains
+ * uses the chains [0, B); every row still sweeps.
+ * bm_rbm_train_epoch_pt is the native batch loop: the launches and call counters of one bm_rbm_train_step_pt per batch of
+ * `batch` rows (the last batch may be short).
+ * Errors: no ensemble, B outside [1, min(max_batch, n_chains)], n_gibbs_steps < 1, a handle with dropout, a momentum buffer
+ * sharded by bm_rbm_exchange_apply_direct (as bm_rbm_train_step).  Float32, one process. */
+int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t n_gibbs_steps);
+int bm_rbm_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t n_gibbs_steps);
+
 /* the handle's hipStream_t (as void*), so a host can enqueue collectives on
  * the same stream (torch.cuda.ExternalStream) without host synchronisation. */
 int bm_rbm_stream(bm_rbm *h, void **out_stream);
