@@ -175,6 +175,9 @@ SIGNATURES = {
     'bm_dbm_reconstruct': [_vp, _vp, _vp],
     'bm_dbm_sample_v': [_vp, _i32, _vp],
     'bm_dbm_sample_v_clamped': [_vp, _i32, _vp, _vp, _vp],
+    'bm_dbm_pt_init': [_vp, _i32, _i32, _vp, _vp, _i64],
+    'bm_dbm_pt_sweep': [_vp, _i32],
+    'bm_dbm_pt_read': [_vp, _vp, _vp, _vp, _vp, _vp],
     'bm_dbm_ais': [_vp, _i32, _i32, _i32, _u64, _i64, _vp],
     'bm_dbm_log_proba': [_vp, _vp, _vp],
     'bm_dbm_timer_start': [_vp],

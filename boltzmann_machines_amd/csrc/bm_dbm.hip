@@ -8,6 +8,7 @@
 #include "../../include/bm355.h"
 #include "bm_common.h"
 #include "bm_kernels.h"
+#include "bm_pt.h"
 
 #include <math.h>
 #include <memory>
@@ -22,6 +23,9 @@ static int xchg_mf_ctl_step(bm_xchg *x, MfCtl *ctl, float *blk, int nblk, float 
 namespace {
 // RNG sites (counter word 2 = site + 16 * sweep index); DESIGN.md "RNG"
 enum : uint32_t { SITE_DBM_H = 8 /* + layer */, SITE_DBM_V = 12, SITE_AIS_X0 = 13 };
+// bm_dbm_pt_* (bm355.h): the swap uniforms (flat index = global chain * (R - 1) + ladder pair) and the random start (v_0 at
+// t = 0, h2_0 at t = 1 of the site)
+enum : uint32_t { SITE_DBM_PT_SWAP = 14, SITE_DBM_PT_START = 15 };
 constexpr int MAXL = BM_DBM_MAX_LAYERS;
 }  // namespace
 
@@ -103,6 +107,16 @@ struct bm_dbm {
     DevArray<double> alogw;                        // [ais_rows] log-weights, accumulated in double in a fixed order
     DevBuf ais_send, ais_recv;                     // bm_dbm_ais_sharded: this rank's values / the all-gathered values
     Mat sv_v[2], sv_H[2][MAXL];                    // bm_dbm_sample_v: ping-pong states of its mean sweeps [M][*]
+    // bm_dbm_pt_*: the tempered ensemble of pt_M chains x pt_R replicas, chain-major rows (row c * R + r), allocated on demand for
+    // `pt_rows` rows; nothing else in the handle reads or writes these (L <= 2)
+    int pt_rows = 0, pt_M = 0, pt_R = 0;
+    int64_t pt_chain0 = 0;
+    long long pt_step = 0;                         // steps done since bm_dbm_pt_init: its parity picks the even or the odd ladder pairs
+    Mat ptv, pth[2];                               // states [pt_rows][V], [pt_rows][n1], [pt_rows][n2] (L == 2)
+    DevBuf ptpart_v, ptpart_h1, ptpart_h2;         // slot partials of v.vb, h1.(vW0 + h2W1^T + b1), h2.b2: [ceil(n/16)][pt_rows]
+    DevBuf pt_mult, pt_beta;                       // the temperature of every row [pt_rows] (ActArgs::row_mult), the ladder [pt_R]
+    DevArray<int> pt_idx;                          // the ladder index of every row [pt_rows]
+    DevArray<unsigned long long> pt_cnt;           // [2][R - 1]: swap attempts, accepts per ladder pair
     // fast-binary mode (bm_bf3.h, bm_dbm_set_fast_binary): bf16 planes of W_l (x = below unit, k = above unit) and of
     // W_l^T, bf16 shadows of the AIS state matrices; `fast_now` is set while a sweep with all-binary states runs
     int ais_literal = 0;                           // bm_dbm_set_ais_literal: float32 accumulation in the reference's order
@@ -1162,6 +1176,167 @@ int bm_dbm_sample_v_clamped(bm_dbm *h, int32_t k, const float *clamp_val_dev, co
         BM_CHECK(!h->multinomial(i), "bm_dbm_sample_v_clamped: a Multinomial hidden layer (layer %d) is not supported", i);
     const Clamp cl{clamp_val_dev, clamp_mask_dev, h->V};
     return sample_v(h, k, V_dev, &cl);
+}
+
+// ---- parallel tempering (bm355.h: bm_dbm_pt_init / _sweep / _read)
+
+// Start of the ensemble: one thread per row and 16-column slot of the visible layer, then of h2 (nH2 == 0: a one-layer stack has
+// none).  v_0 ~ Ber(1/2) at its flat index of the global row (V0 null) or the chain's row of V0 [M][V] for all its R replicas;
+// h2_0 ~ Ber(1/2) always (key_h2); the slot's partial of v_0.vb / h2_0.b2 (pt_vb_slot); row c * R + r starts at ladder index r,
+// temperature beta[r]
+__global__ __launch_bounds__(256) void dbm_pt_init_kernel(float *v, int ldv, int rows, int R, int V, const float *V0, const float *vb,
+                                                          float *h2, int ldh2, int nH2, const float *b2, const float *beta,
+                                                          PhiloxKey key_v, PhiloxKey key_h2, unsigned long long row0, float *part_v,
+                                                          float *part_h2, int ld_part, float *row_mult, int *idx) {
+    const int nsv = (V + 15) / 16, ns = nsv + (nH2 + 15) / 16;
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)rows * ns) return;
+    const int row = (int)(e / ns), slot = (int)(e % ns);
+    if (slot < nsv) {
+        part_v[(size_t)slot * ld_part + row] = pt_vb_slot(slot, V, vb, [&](int c) {
+            const float x = V0 ? V0[(size_t)(row / R) * V + c]
+                               : (philox_uniform_at(key_v, (row0 + row) * (unsigned long long)V + c) < 0.5f ? 1.f : 0.f);
+            v[(size_t)row * ldv + c] = x;
+            return x;
+        });
+    } else {
+        const int s2 = slot - nsv;
+        part_h2[(size_t)s2 * ld_part + row] = pt_vb_slot(s2, nH2, b2, [&](int c) {
+            const float x = philox_uniform_at(key_h2, (row0 + row) * (unsigned long long)nH2 + c) < 0.5f ? 1.f : 0.f;
+            h2[(size_t)row * ldh2 + c] = x;
+            return x;
+        });
+    }
+    if (slot == 0) { row_mult[row] = beta[row % R]; idx[row] = row % R; }
+}
+
+static int ensure_pt_rows(bm_dbm *h, int rows, int R) {
+    if (h->pt_cnt.n < (size_t)2 * std::max(R - 1, 1)) BM_TRY(h->pt_cnt.alloc((size_t)2 * std::max(R - 1, 1)));
+    if (h->pt_beta.n < (size_t)R) BM_TRY(h->pt_beta.alloc(R));
+    if (rows <= h->pt_rows) return 0;
+    h->pt_rows = 0;                                // (set again once every buffer exists: a failure leaves none counted)
+    BM_TRY(h->ptv.alloc(rows, h->V)); BM_TRY(h->ptpart_v.alloc((size_t)nslots(h->V) * rows));
+    BM_TRY(h->pth[0].alloc(rows, h->n[1])); BM_TRY(h->ptpart_h1.alloc((size_t)nslots(h->n[1]) * rows));
+    if (h->L == 2) { BM_TRY(h->pth[1].alloc(rows, h->n[2])); BM_TRY(h->ptpart_h2.alloc((size_t)nslots(h->n[2]) * rows)); }
+    BM_TRY(h->pt_mult.alloc(rows)); BM_TRY(h->pt_idx.alloc(rows));
+    h->pt_rows = rows;
+    return 0;
+}
+
+// what the tempered family is defined for (the messages name the reason; bm355.h)
+static int check_pt_model(const bm_dbm *h, const char *what) {
+    BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "%s: Gaussian visible units are not supported (their tempered noise scale differs; "
+             "Bernoulli visible units only)", what);
+    for (int i = 0; i < h->L; ++i)
+        BM_CHECK(!h->multinomial(i), "%s: a Multinomial hidden layer (layer %d) is not supported (Bernoulli hidden layers only)", what, i);
+    BM_CHECK(h->L <= 2, "%s: %d hidden layers are not supported (at most 2): from three layers on a pass reads the OLD layer above, "
+             "so at no point of the sweep do the slot partials hold every interaction term of ONE consistent state and the swap "
+             "energy would have to be recomputed", what, h->L);
+    BM_CHECK(!h->sigmoid_literal, "%s: the handle is in literal-sigmoid mode (bm_dbm_set_sigmoid_literal); the row-tempered kernels "
+             "have no literal flavour", what);
+    return 0;
+}
+
+// one row-tempered pass of the ensemble (the RT flavour of act_kernel), always a per-pass fp32 launch on the main stream:
+//   layer 0: h1 ~ Ber(sigmoid(beta_row (v W0 + h2 W1^T + b1))) from (ptv, pth[1]) - two K segments at L == 2 - leaving the slot
+//            partials of h1.(v W0 + h2 W1^T + b1);  layer 1: h2 from pth[0], leaving those of h2.b2;  layer -1: v from pth[0],
+//            leaving those of v.vb
+static void pt_pass(bm_dbm *h, int layer, int t) {
+    const int rows = h->pt_M * h->pt_R;
+    const int64_t row0 = h->pt_chain0 * h->pt_R;
+    const LayerIn below = layer == 0 ? in_of(h->ptv) : (layer == 1 ? in_of(h->pth[0]) : NO_IN);
+    const LayerIn above = layer == 0 ? (h->L == 2 ? in_of(h->pth[1]) : NO_IN) : (layer == 1 ? NO_IN : in_of(h->pth[0]));
+    Mat &out = layer < 0 ? h->ptv : h->pth[layer];
+    const PhiloxKey key = dkey(h, layer < 0 ? SITE_DBM_V : SITE_DBM_H + layer, t, h->seed, h->call);
+    LayerPass p = layer_pass(h, layer, rows, below, above, 1.f, 1.f, value_out(1, out.p, out.ld, key, row0));   // (mult: not read)
+    if (layer == 0) { p.a.rowen_out = h->ptpart_h1.p; p.a.ld_part = h->pt_rows; }
+    else if (layer == 1) p.statedot_rows(h->ptpart_h2.p, h->pt_rows, h->hb[1].p);
+    else p.statedot_rows(h->ptpart_v.p, h->pt_rows, h->vb.p);
+    p.a.row_mult = h->pt_mult.p;
+    launch_act(p.a, h->stream);
+}
+
+// step t of a tempered call, in gibbs_sweep's order with every layer sampled: h1 from (v, OLD h2); the swap of the parity of the
+// global step number - the state is (v_t, h1_{t+1}, h2_t) and the three partial arrays are exactly its -E; h2; v
+static void pt_step(bm_dbm *h, int t) {
+    const int M = h->pt_M, R = h->pt_R;
+    pt_pass(h, 0, t);
+    const int parity = (int)((h->pt_step + t) & 1);
+    const int npair = (R - parity) / 2;
+    if (npair > 0) {
+        const long long nthr = (long long)M * npair;
+        hipLaunchKernelGGL(pt_swap_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, M, R, parity,
+                           (const float *)h->ptpart_v.p, nslots(h->V), (const float *)h->ptpart_h2.p, h->L == 2 ? nslots(h->n[2]) : 0,
+                           (const float *)h->ptpart_h1.p, nslots(h->n[1]), h->pt_rows, h->pt_mult.p, h->pt_idx.p, h->pt_cnt.p,
+                           dkey(h, SITE_DBM_PT_SWAP, t, h->seed, h->call), (unsigned long long)h->pt_chain0);
+    }
+    if (h->L == 2) pt_pass(h, 1, t);
+    pt_pass(h, -1, t);
+}
+
+// Parallel tempering of a DBM (replica exchange).  The ensemble lives in the handle; see bm355.h for the contract.
+int bm_dbm_pt_init(bm_dbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0) {
+    BM_CHECK(h, "null argument");
+    BM_TRY(check_pt_model(h, "bm_dbm_pt_init"));
+    BM_CHECK(n_temps >= 1, "n_temps must be >= 1 (got %d)", (int)n_temps);
+    BM_CHECK(betas_host, "null argument");
+    BM_CHECK(n_chains >= 1 && chain0 >= 0, "bad ensemble (n_chains %d >= 1, chain0 %lld >= 0)", (int)n_chains, (long long)chain0);
+    BM_CHECK((long long)n_chains * n_temps <= (1ll << 24), "n_chains * n_temps = %lld rows exceed 2^24",
+             (long long)n_chains * n_temps);
+    for (int r = 0; r < n_temps; ++r)
+        BM_CHECK(betas_host[r] > 0.f && betas_host[r] <= 1.f && (r == 0 || betas_host[r] > betas_host[r - 1]),
+                 "betas must increase strictly inside (0, 1] (betas[%d] = %g)", r, (double)betas_host[r]);
+    BM_CHECK(betas_host[n_temps - 1] == 1.0f, "the last beta must be 1 (got %g)", (double)betas_host[n_temps - 1]);
+    const int M = n_chains, R = n_temps, rows = M * R;
+    h->pt_M = 0;                                   // (an ensemble exists once everything below went through)
+    BM_TRY(ensure_pt_rows(h, rows, R));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_HIP(hipMemcpy(h->pt_beta.p, betas_host, (size_t)R * sizeof(float), hipMemcpyHostToDevice));
+    BM_HIP(hipMemsetAsync(h->pt_cnt.p, 0, (size_t)2 * std::max(R - 1, 1) * sizeof(unsigned long long), h->stream));
+    const int nH2 = h->L == 2 ? h->n[2] : 0;
+    const long long nthr = (long long)rows * (nslots(h->V) + nslots(nH2));
+    hipLaunchKernelGGL(dbm_pt_init_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, h->ptv.p, h->ptv.ld, rows, R,
+                       h->V, V0_dev, (const float *)h->vb.p, h->pth[1].p, h->pth[1].ld, nH2, (const float *)h->hb[1].p,
+                       (const float *)h->pt_beta.p, dkey(h, SITE_DBM_PT_START, 0, h->seed, h->call),
+                       dkey(h, SITE_DBM_PT_START, 1, h->seed, h->call), (unsigned long long)chain0 * (unsigned long long)R,
+                       h->ptpart_v.p, h->ptpart_h2.p, h->pt_rows, h->pt_mult.p, h->pt_idx.p);
+    BM_HIP(hipGetLastError());
+    h->pt_M = M; h->pt_R = R; h->pt_chain0 = chain0; h->pt_step = 0;
+    return 0;
+}
+
+int bm_dbm_pt_sweep(bm_dbm *h, int32_t n_steps) {
+    BM_CHECK(h, "null argument");
+    BM_CHECK(h->pt_M > 0, "bm_dbm_pt_sweep: no ensemble (call bm_dbm_pt_init first)");
+    BM_TRY(check_pt_model(h, "bm_dbm_pt_sweep"));  // (the literal-sigmoid mode may have been switched on since the init)
+    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
+    for (int t = 0; t < n_steps; ++t) pt_step(h, t);
+    h->pt_step += n_steps;
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+int bm_dbm_pt_read(bm_dbm *h, float *V_dev, float *H1_dev, float *H2_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
+    BM_CHECK(h, "null argument");
+    BM_CHECK(h->pt_M > 0, "bm_dbm_pt_read: no ensemble (call bm_dbm_pt_init first)");
+    BM_CHECK(!H2_dev || h->L == 2, "bm_dbm_pt_read: H2_dev for a stack of one hidden layer");
+    const int M = h->pt_M, R = h->pt_R;
+    if (V_dev)
+        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, (const float *)h->ptv.p,
+                           h->ptv.ld, h->V, (const float *)h->pth[0].p, h->pth[0].ld, h->n[1], V_dev, h->V, H1_dev);
+    else BM_CHECK(!H1_dev, "bm_dbm_pt_read: H1_dev without V_dev");
+    if (H2_dev)                                    // (the same kernel, h2 in the place of v)
+        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, (const float *)h->pth[1].p,
+                           h->pth[1].ld, h->n[2], (const float *)nullptr, 0, 0, H2_dev, h->n[2], (float *)nullptr);
+    BM_HIP(hipGetLastError());
+    BM_HIP(hipStreamSynchronize(h->stream));
+    if (swaps_host && R > 1) {
+        static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counter width");
+        BM_HIP(hipMemcpy(swaps_host, h->pt_cnt.p, (size_t)2 * (R - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    if (ladder_idx_host) BM_HIP(hipMemcpy(ladder_idx_host, h->pt_idx.p, (size_t)M * R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 static int ensure_ais(bm_dbm *h, int rows) {

@@ -16,8 +16,9 @@
 //        tile of its own: the geometry and the block -> tile map are the ones the tuner chose (or now chooses, with the plain
 //        kernels) for the same shape in the plain flavour - one memo, no tuning run with the clamp loads; act_geo forces it
 //        like any pass.  With `lit`: the 32 x 32 parity tile of LIT.  Never the chained launch or the bf16 x 3 strip kernel
-//   RT   a temperature per row (ActArgs::row_mult / rowen_out; parallel tempering): single-segment passes on the
-//        geometry and tile map of the plain flavour's memo for the shape, exactly as CL; combined with no other flavour
+//   RT   a temperature per row (ActArgs::row_mult / rowen_out; parallel tempering): passes of one or two
+//        K segments (the interior layer of a DBM: below first, above chained onto the same accumulator) on the geometry and
+//        tile map of the plain flavour's memo for the shape, exactly as CL; combined with no other flavour
 // FE, LIT and MF stage through LDS-DMA in the slab order.  dispatch_act walks the one ladder they share with the plain flavour:
 // x-major P / two K segments / one, each as the `fast` kernel (16-byte loads) or the one that passes every chunk through
 // registers (STG_DMA whatever the geometry's staging: shapes without 16-byte loads have ONE flavour).
@@ -161,10 +162,11 @@ static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, un
         if (seg2) { launch_act_kernel<G, MINB, STG, FL, true, KM>(fast, dyn_lds, st, a, tmap); return; }
     launch_act_kernel<G, MINB, STG, FL, false, KM>(fast, dyn_lds, st, a, tmap);
 }
-// the plain flavour (FLX == 0), CL and RT (FLX == FL_CL / FL_RT: no two-segment kernels): x-major P exists for the geometries with MI == 1
+// the plain flavour (FLX == 0) and RT (FLX == FL_RT) have two-segment kernels, CL (FLX == FL_CL) has none; x-major P exists for
+// the geometries with MI == 1
 template <class G, int MINB, int STG, unsigned FLX = 0>
 static inline void launch_act_geo(const ActArgs &a, hipStream_t st) {
-    dispatch_act<G, MINB, STG, (FLX ? FLX : FL_SEG2) | (G::MI == 1 ? FL_XM : 0)>(a, st, a.map_xi);
+    dispatch_act<G, MINB, STG, FLX | (FLX == FL_CL ? 0 : FL_SEG2) | (G::MI == 1 ? FL_XM : 0)>(a, st, a.map_xi);
 }
 static inline void launch_act_fe(const ActArgs &a, hipStream_t st) { dispatch_act<GeoAct8, 1, STG_DMA, FL_FE | FL_XM>(a, st, XI_SLAB); }
 static inline void launch_act_lit(const ActArgs &a, hipStream_t st) { dispatch_act<GeoActS, 2, STG_DMA, FL_LIT | FL_XM | FL_SEG2>(a, st, XI_SLAB); }
@@ -365,11 +367,11 @@ static inline void launch_act_cl(const ActArgs &a, hipStream_t st) {
     if (a.lit && a.kind == 0) { dispatch_act<GeoActS, 2, STG_DMA, FL_CL | FL_LIT | FL_XM>(a, st, XI_SLAB); return; }
     launch_act_f32<FL_CL>(a, st);
 }
-// a temperature per row: per-pass fp32 launches always, combined with nothing (no such kernel)
+// a temperature per row: per-pass fp32 launches always, one or two K segments, combined with nothing else (no such kernel)
 static inline void launch_act_rt(const ActArgs &a, hipStream_t st) {
-    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.b3.K1 > 0 || a.lit ||
+    if ((a.K2 > 0 && a.p_xm) || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.b3.K1 > 0 || a.lit ||
         a.kind != 0) {
-        fprintf(stderr, "bm355: a row-tempered pass is a single-segment Bernoulli pass of its own flavour (no such kernel)\n");
+        fprintf(stderr, "bm355: a row-tempered pass is a Bernoulli pass of its own flavour (no such kernel)\n");
         abort();
     }
     launch_act_f32<FL_RT>(a, st);

@@ -8,6 +8,7 @@
 #include "bm_common.h"
 #include "bm_kernels.h"
 #include "bm_chain.h"
+#include "bm_pt.h"
 
 #include <math.h>
 #include <atomic>
@@ -606,22 +607,7 @@ static void ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &k
 
 // ---- parallel tempering (bm355.h: bm_rbm_pt_init / _sweep / _read)
 
-// The partial of x.vb over the 16-column slot `slot`, in the order of ActArgs::rowdot_out (quads of 4 columns left
-// to right, then (q0 + q1) + (q2 + q3)); x_at(c) supplies column c of the row (and may store it)
-template <class F>
-__device__ __forceinline__ float pt_vb_slot(int slot, int V, const float *vb, F x_at) {
-    float q[4];
-    for (int g = 0; g < 4; ++g) {
-        float acc = 0.f;
-        for (int r = 0; r < 4; ++r) {
-            const int c = slot * 16 + 4 * g + r;
-            if (c >= V) break;
-            acc += x_at(c) * vb[c];
-        }
-        q[g] = acc;
-    }
-    return (q[0] + q[1]) + (q[2] + q[3]);
-}
+// (pt_vb_slot, pt_swap_kernel and pt_gather_kernel: bm_pt.h, shared with bm_dbm_pt_*)
 
 // Start of the ensemble: one thread per row and 16-column slot.  v_0 ~ Ber(1/2) at its flat index of the global row (V0 null) or
 // the chain's row of V0 [M][V] for all its R replicas; the slot's partial of v_0.vb (pt_vb_slot); row c * R + r starts at ladder
@@ -651,52 +637,6 @@ __global__ __launch_bounds__(256) void pt_rescore_kernel(const float *v, int ld,
     if (e >= (long long)rows * ns) return;
     const int row = (int)(e / ns), slot = (int)(e % ns);
     part[(size_t)slot * ld_part + row] = pt_vb_slot(slot, V, vb, [&](int c) { return v[(size_t)row * ld + c]; });
-}
-
-// Replica exchange: one thread per chain c and candidate ladder pair (p, p + 1) with p % 2 == parity; the pairs of one step are
-// disjoint.  a / b = the chain's rows that hold ladder index p / p + 1 (found by scanning the chain's R index entries: the
-// entries another thread of this step may change hold neither p nor p + 1 before or after).  E = -(sum of the row's v.vb slots +
-// sum of its h.(vW + hb) slots), ascending, in double; accepted iff delta = (beta_a - beta_b)(E_a - E_b) >= 0 or u < exp(delta).
-// An accepted swap exchanges the rows' temperatures and ladder indices; the states stay where they are.
-__global__ __launch_bounds__(256) void pt_swap_kernel(int M, int R, int parity, const float *part_v, int nslot_v, const float *part_h,
-                                                      int nslot_h, int ld_part, float *row_mult, int *idx, unsigned long long *cnt,
-                                                      PhiloxKey key, unsigned long long chain0) {
-    const int npair = (R - parity) / 2;                  // pairs p = parity, parity + 2, ... <= R - 2
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long long)M * npair) return;
-    const int c = (int)(e / npair), p = parity + 2 * (int)(e % npair);
-    int ra = -1, rb = -1;
-    for (int r = 0; r < R; ++r) {
-        const int k = idx[(size_t)c * R + r];
-        if (k == p) ra = c * R + r;
-        if (k == p + 1) rb = c * R + r;
-    }
-    if (ra < 0 || rb < 0) return;                        // (cannot happen: the index entries of a chain are a permutation)
-    double sa = 0.0, sb = 0.0;
-    for (int q = 0; q < nslot_v; ++q) { sa += (double)part_v[(size_t)q * ld_part + ra]; sb += (double)part_v[(size_t)q * ld_part + rb]; }
-    for (int q = 0; q < nslot_h; ++q) { sa += (double)part_h[(size_t)q * ld_part + ra]; sb += (double)part_h[(size_t)q * ld_part + rb]; }
-    const float ba = row_mult[ra], bb = row_mult[rb];
-    const double delta = ((double)ba - (double)bb) * ((-sa) - (-sb));
-    const float u = philox_uniform_at(key, (chain0 + (unsigned long long)c) * (unsigned long long)(R - 1) + (unsigned long long)p);
-    const bool accept = delta >= 0.0 || (double)u < exp(delta);
-    atomicAdd(cnt + p, 1ull);
-    if (accept) {
-        atomicAdd(cnt + (R - 1) + p, 1ull);
-        row_mult[ra] = bb; row_mult[rb] = ba;
-        idx[ra] = p + 1; idx[rb] = p;
-    }
-}
-
-// the beta = 1 row of every chain (ladder index R - 1: exactly one) -> V_out [M][V] pitch ldvo and dense H_out [M][H] (or null)
-__global__ __launch_bounds__(256) void pt_gather_kernel(int M, int R, const int *idx, const float *v, int ldv, int V, const float *hs, int ldh,
-                                                        int H, float *V_out, int ldvo, float *H_out) {
-    const int c = blockIdx.x;
-    if (c >= M) return;
-    int src = -1;
-    for (int r = 0; r < R; ++r) if (idx[(size_t)c * R + r] == R - 1) src = c * R + r;
-    if (src < 0) return;
-    for (int i = threadIdx.x; i < V; i += blockDim.x) V_out[(size_t)c * ldvo + i] = v[(size_t)src * ldv + i];
-    if (H_out) for (int i = threadIdx.x; i < H; i += blockDim.x) H_out[(size_t)c * H + i] = hs[(size_t)src * ldh + i];
 }
 
 static int ensure_pt_rows(bm_rbm *h, int rows, int R) {
@@ -754,7 +694,8 @@ static void pt_step(bm_rbm *h, int t, int sel_rows = 0) {
     if (npair > 0) {
         const long long nthr = (long long)M * npair;
         hipLaunchKernelGGL(pt_swap_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, M, R, parity,
-                           (const float *)h->ptpart_v.p, nslots(h->V), (const float *)h->ptpart_h.p, nslots(h->H), h->pt_rows,
+                           (const float *)h->ptpart_v.p, nslots(h->V), (const float *)nullptr, 0, (const float *)h->ptpart_h.p,
+                           nslots(h->H), h->pt_rows,
                            h->pt_mult.p, h->pt_idx.p, h->pt_cnt.p, make_key(h, SITE_PT_SWAP, t), (unsigned long long)h->pt_chain0);
     }
     pt_pass(h, false, make_key(h, SITE_V, t), sel_rows);

@@ -493,6 +493,69 @@ class DBM(EngineModel):
             self._restore(snap)
         return (v, v.copy()) if return_means else v
 
+    # ---- unconditional sampling by parallel tempering (no counterpart in the reference) -----------
+    def _check_temperable(self, what):
+        name = '%s.%s' % (self.__class__.__name__, what)
+        if np.dtype(self.dtype) != np.float32:
+            raise NotImplementedError("%s: dtype='%s' models are not supported (the float64 engine has no tempered sweep; "
+                                      'float32 only)' % (name, np.dtype(self.dtype).name))
+        if self.v_unit_ != _ffi.UNIT_BERNOULLI:
+            raise NotImplementedError('%s: Gaussian visible units are not supported (Bernoulli visible units only)' % name)
+        if any(int(u) == _ffi.UNIT_MULTINOMIAL for u in (self.h_units_ or [])):
+            raise NotImplementedError('%s: a Multinomial hidden layer is not supported (Bernoulli hidden layers only)' % name)
+        if self.n_layers_ is not None and self.n_layers_ > 2:
+            raise NotImplementedError('%s: %d hidden layers are not supported (at most 2): from three layers on a pass of the '
+                                      'sweep reads the OLD layer above, so the energy of one consistent state is never at '
+                                      'hand for the exchange' % (name, self.n_layers_))
+        if self._sigmoid_literal:
+            raise NotImplementedError("%s: not available under set_mean_field_arithmetic('reference') (the row-tempered "
+                                      'kernels have no literal-sigmoid flavour)' % name)
+
+    def sample_v_tempered(self, n_samples, n_gibbs_steps=1000, n_temperatures=10, betas=None, V_init=None, return_stats=False):
+        """Unconditional samples of the visible units by parallel tempering (replica exchange; as `BernoulliRBM.sample_v`, on
+        the DBM's own joint p(v, h1, h2) ~ exp(-E)): `n_samples` independent chains, each with one replica per temperature
+        of the ladder 0 < betas[0] < ... < betas[-1] = 1, run `n_gibbs_steps` steps of (h1 ~ p_beta(h1|v, h2), exchange of
+        neighbouring temperatures, h2 ~ p_beta(h2|h1), v ~ p_beta(v|h1)); the visible STATES of the replica at beta = 1 of
+        every chain are returned.  `sample_v` keeps the reference's behaviour: one temperature, from the fantasy particles.
+
+        betas : the ladder; None: float32(linspace(0, 1, n_temperatures + 1)[1:]).  `n_temperatures=1` is plain Gibbs.
+        V_init : [n_samples, n_visible] start of every chain (all its replicas); None: v_0 ~ Ber(1/2).  h2_0 ~ Ber(1/2).
+        Returns [n_samples, n_visible]; with `return_stats` also the acceptance rate of every neighbouring pair of
+        temperatures, [n_temperatures - 1] (accepts / attempts).
+        Every layer is always sampled.  One seed is drawn from the model's host stream; no parameter, particle or
+        variational parameter is changed.  Stacks of one or two Bernoulli hidden layers over Bernoulli visible units,
+        float32; everything else raises NotImplementedError.  In a multi-GPU job every rank runs all chains."""
+        self._check_temperable('sample_v_tempered')
+        return self._sample_v_tempered(n_samples, n_gibbs_steps, n_temperatures, betas, V_init, return_stats)
+
+    @run_on_engine(update_seed=True)
+    def _sample_v_tempered(self, n_samples, n_gibbs_steps, n_temperatures, betas, V_init, return_stats):
+        n_samples = int(n_samples)
+        if n_samples < 1 or int(n_gibbs_steps) < 1:
+            raise ValueError('`n_samples` and `n_gibbs_steps` must be >= 1 (got {0}, {1})'.format(n_samples, n_gibbs_steps))
+        if betas is None:
+            if int(n_temperatures) < 1:
+                raise ValueError('`n_temperatures` must be >= 1 (got {0})'.format(n_temperatures))
+            betas = np.linspace(0., 1., int(n_temperatures) + 1)[1:]
+        betas = np.asarray(betas, dtype=np.float32).ravel()
+        if len(betas) < 1 or betas[-1] != 1. or betas[0] <= 0. or np.any(np.diff(betas) <= 0.):
+            raise ValueError('`betas` must increase strictly inside (0, 1] and end at 1 (got {0})'.format(betas))
+        V0d = None
+        if V_init is not None:
+            V_init = np.ascontiguousarray(V_init, dtype=np.float32)
+            if V_init.shape != (n_samples, self.n_visible_):
+                raise ValueError('`V_init` has invalid shape {0}: expected [{1}, {2}]'.format(V_init.shape, n_samples, self.n_visible_))
+            V0d = as_device(V_init, np.float32)
+        eng = self._engine
+        eng.pt_init(n_samples, betas, V0d)
+        eng.pt_sweep(int(n_gibbs_steps))
+        Vd = _ffi.DeviceArray((n_samples, self.n_visible_), np.float32)
+        swaps, _ = eng.pt_read(Vd)
+        V = Vd.numpy()
+        if return_stats:
+            return V, swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
+        return V
+
     def set_ais_accumulation(self, dtype='float64'):
         """How `log_Z` accumulates the AIS log-weights.  'float64' (default): per chain the difference of consecutive
         log p*, row sums and running sum in double, fixed order - deterministic and closer to the exactly enumerable

@@ -516,6 +516,31 @@ class DbmEngine(object):
         [n_particles, V]; bm_dbm_sample_v_clamped)"""
         check(self.lib.bm_dbm_sample_v_clamped(self._h, k, clamp_val_d.ptr, clamp_mask_d.ptr, Vd.ptr if Vd is not None else None))
 
+    # parallel tempering (bm355.h: bm_dbm_pt_init / _sweep / _read)
+    def pt_init(self, n_chains, betas, V0_d=None, chain0=0):
+        """build the tempered ensemble of n_chains x len(betas) replicas in the handle; V0_d [n_chains, V] (DeviceArray): every
+        chain's replicas start there, None: v_0 ~ Ber(1/2); h2_0 ~ Ber(1/2) either way"""
+        b = np.ascontiguousarray(betas, dtype=np.float32).ravel()
+        check(self.lib.bm_dbm_pt_init(self._h, int(n_chains), len(b), b.ctypes.data_as(C.c_void_p),
+                                      V0_d.ptr if V0_d is not None else None, int(chain0)))
+        self._pt_shape = (int(n_chains), len(b))
+
+    def pt_sweep(self, n_steps):
+        """n_steps of (tempered h1 pass, replica exchange, tempered h2 pass, tempered v pass) on the whole ensemble"""
+        check(self.lib.bm_dbm_pt_sweep(self._h, int(n_steps)))
+
+    def pt_read(self, Vd=None, H1d=None, H2d=None):
+        """beta = 1 rows -> Vd [n_chains, V] / H1d [n_chains, n_1] / H2d [n_chains, n_2] (DeviceArrays, optional); returns
+        (swaps [2, R-1] int64: attempts and accepts per ladder pair, ladder_idx [n_chains, R] int32)"""
+        M, R = getattr(self, '_pt_shape', (0, 1))
+        swaps = np.zeros((2, max(R - 1, 0)), dtype=np.int64)
+        idx = np.zeros((M, R), dtype=np.int32)
+        ptr = lambda d: d.ptr if d is not None else None
+        check(self.lib.bm_dbm_pt_read(self._h, ptr(Vd), ptr(H1d), ptr(H2d),
+                                      swaps.ctypes.data_as(C.c_void_p) if swaps.size else None,
+                                      idx.ctypes.data_as(C.c_void_p) if idx.size else None))
+        return swaps, idx
+
     def ais(self, n_betas, n_runs, k, seed, chain0=0):
         out = np.empty(n_runs, dtype=np.float32)
         check(self.lib.bm_dbm_ais(self._h, n_betas, n_runs, k, int(seed), int(chain0), out.ctypes.data_as(C.c_void_p)))
@@ -618,6 +643,11 @@ class DbmEngine64(DbmEngine):
 
     def sample_v_clamped(self, *a, **kw):
         raise NotImplementedError('conditional sampling has no float64 entry (bm_dbm64_* has no clamped sample_v)')
+
+    def _no_pt(self, *a, **kw):
+        raise NotImplementedError('parallel tempering has no float64 entry (bm_dbm64_* has no pt_init / pt_sweep / pt_read)')
+
+    pt_init = pt_sweep = pt_read = _no_pt
 
     def set_fast_binary(self, on, everywhere=False):
         if on:

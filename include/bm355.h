@@ -391,6 +391,37 @@ int bm_dbm_sample_v(bm_dbm *h, int32_t n_gibbs_steps, float *V_dev);
  * Errors: n_gibbs_steps < 0, null clamp pointers, a Multinomial hidden layer.  (No float64 counterpart.) */
 int bm_dbm_sample_v_clamped(bm_dbm *h, int32_t n_gibbs_steps, const float *clamp_val_dev, const float *clamp_mask_dev,
                             float *V_dev);
+/* Parallel tempering of a DBM (replica exchange), the counterpart of bm_rbm_pt_*: n_chains independent chains,
+ * each with one replica per temperature of the ladder 0 < betas[0] < ... < betas[n_temps-1] = 1 of the family
+ *   p_beta(v, h1, h2) ~ exp(-beta E),  -E = v.vb + h1.b1 + h2.b2 + v W0 h1 + h1 W1 h2
+ * on the handle's own parameters, for stacks of ONE or TWO Bernoulli hidden layers over Bernoulli visible units (float32).  The
+ * ensemble lives in the handle: rows are chain-major (row c R + r is slot r of chain c; a slot starts at ladder index r),
+ * allocated on demand - neither batch_size nor n_particles bounds it - and freed with the handle.
+ *   bm_dbm_pt_init   builds the ensemble: v_0 ~ Ber(1/2) (site 15 of the handle's current call) or, with V0_dev [n_chains,
+ *                    n_visible] (device, dense), every chain's R replicas start from its row of V0_dev; h2_0 ~ Ber(1/2) always
+ *                    (site 15 + 16).  Resets the swap counters and the step parity.  Does not advance the call counter.
+ *   bm_dbm_pt_sweep  n_steps steps in the order of a Gibbs sweep, every layer sampled; step t: h1 ~ p_beta(h1 | v, h2) for every
+ *                    row (site 8 + 16 t; one launch of two K segments), leaving h1.(v W0 + h2 W1^T + b1) as slot partials; the
+ *                    swap step; h2 ~ p_beta(h2 | h1) (site 9 + 16 t), leaving h2.b2; v ~ p_beta(v | h1) (site 12 + 16 t),
+ *                    leaving v.vb.  At the swap the state of a row is (v_t, h1_{t+1}, h2_t) and the three partial arrays are its
+ *                    -E: per row the v.vb slots, then the h2.b2 slots, then the h1 slots are added in ascending order in double.
+ *                    Pairing, parity (global step number since the init, across calls), acceptance rule and counters are those
+ *                    of bm_rbm_pt_sweep; the uniform of chain c, pair p is the one at flat index (chain0 + c)(R - 1) + p of site
+ *                    14 + 16 t.  The call counter advances once per bm_dbm_pt_sweep.
+ *   bm_dbm_pt_read   copies, for every chain, the row at beta = 1 to V_dev [n_chains, n_visible] (NULL: nothing is copied), its
+ *                    h1 to H1_dev [n_chains, n_1] (NULL ok; needs V_dev) and its h2 to H2_dev [n_chains, n_2] (NULL ok; two-layer
+ *                    stacks only); swaps_host [2][R-1] (NULL ok) receives attempts, then accepts, per ladder pair since the init;
+ *                    ladder_idx_host [n_chains R] (NULL ok) the ladder index of every row.  Waits for the stream.
+ * The global row of the RNG streams is (chain0 + c) R + r: chains [c, c + n) of a larger ensemble are the ensemble of n chains
+ * at chain0 = c, bit for bit.  Always per-pass fp32 launches on the handle's main stream, whatever bm_dbm_set_fast_binary says.
+ * No parameter, particle, mean-field state or workspace of another entry point is touched.
+ * Errors: Gaussian visible units, a Multinomial hidden layer, three or more hidden layers (a pass would read the OLD layer
+ * above: no point of the sweep has the energy of one consistent state in the partials), a handle in literal-sigmoid mode;
+ * n_temps < 1, n_chains < 1, betas not strictly increasing inside (0, 1] or betas[R-1] != 1, sweep or read before init,
+ * n_steps < 1.  (No float64 counterpart.) */
+int bm_dbm_pt_init(bm_dbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0);
+int bm_dbm_pt_sweep(bm_dbm *h, int32_t n_steps);
+int bm_dbm_pt_read(bm_dbm *h, float *V_dev, float *H1_dev, float *H2_dev, int64_t *swaps_host, int32_t *ladder_idx_host);
 /* AIS (dbm.py:650-736; public log_Z :899-939) for a Bernoulli DBM of any
  * depth (1..4 layers): n_runs chains, n_betas temperatures, n_gibbs_steps
  * transitions per temperature.  values_host [n_runs] receives the per-chain
