@@ -91,6 +91,8 @@ SIGNATURES = {
     'bm_dbm_set_sigmoid_literal': [_vp, _i32],
     'bm_rbm_set_fast_binary': [_vp, _i32],
     'bm_rbm64_create': [C.POINTER(RbmConfig), C.POINTER(C.c_double), C.POINTER(_vp)],
+    'bm_rbm_multinomial_limit': [C.POINTER(C.c_int64)],
+    'bm_rbm64_multinomial_limit': [C.POINTER(C.c_int64)],
     'bm_rbm64_destroy': [_vp],
     'bm_rbm64_sync': [_vp],
     'bm_rbm64_seed': [_vp, C.c_uint64],

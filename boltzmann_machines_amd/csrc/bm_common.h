@@ -75,6 +75,22 @@ static inline int hip_failed(hipError_t e, const char *what, size_t bytes = 0) {
     return 1;
 }
 
+// What the runtime allows one workgroup of `kernel` in DYNAMIC LDS - a query, no launch: out3 = {the device's
+// hipDeviceAttributeMaxSharedMemoryPerBlock, the kernel's static LDS bytes, the dynamic bytes a launch may ask for = min(the
+// kernel's maxDynamicSharedSizeBytes, per block - static)}.  The row-staging kernels (softmax_multinomial_kernel) size their
+// width limit by it at create, so a handle that exists can launch.
+static inline int dyn_lds_query(const void *kernel, long long out3[3]) {
+    int dev = 0, per_block = 0;
+    BM_HIP(hipGetDevice(&dev));
+    BM_HIP(hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    hipFuncAttributes fa;
+    BM_HIP(hipFuncGetAttributes(&fa, kernel));
+    const long long room = (long long)per_block - (long long)fa.sharedSizeBytes;
+    out3[0] = per_block; out3[1] = (long long)fa.sharedSizeBytes;
+    out3[2] = std::max(0ll, std::min(room, (long long)fa.maxDynamicSharedSizeBytes));
+    return 0;
+}
+
 // a typed device array of n elements, zero-filled
 template <class T> struct DevArray {
     T *p = nullptr;

@@ -817,7 +817,10 @@ int bm_dbm_create(const bm_dbm_config *cfg, bm_dbm **out) {
                  cfg->h_unit[i], i);
         if (cfg->h_unit[i] == BM_UNIT_MULTINOMIAL) {
             BM_CHECK(cfg->n_samples[i] >= 1, "Multinomial layer %d: n_samples must be >= 1 (got %d)", i, cfg->n_samples[i]);
-            BM_CHECK(cfg->n_hiddens[i] <= 8192, "Multinomial layer %d: %d units > 8192 (softmax row staged in LDS)", i, cfg->n_hiddens[i]);
+            int64_t q[4];
+            BM_TRY(bm_rbm_multinomial_limit(q));
+            BM_CHECK(cfg->n_hiddens[i] <= q[3], "Multinomial layer %d: %d units > %lld (softmax row staged in LDS: 8 bytes per unit, the "
+                     "runtime allows a workgroup %lld bytes of dynamic LDS; at most 8192 units)", i, cfg->n_hiddens[i], (long long)q[3], (long long)q[2]);
         }
         h->n[i + 1] = cfg->n_hiddens[i];
     }

@@ -706,6 +706,15 @@ extern "C" {
 const char *bm_last_error(void) { return bm::g_err; }
 const char *bm_version(void) { return "bm355 0.1 gfx950"; }
 
+int bm_rbm_multinomial_limit(int64_t *out4) {
+    BM_CHECK(out4, "null argument");
+    long long q[3];
+    BM_TRY(bm::dyn_lds_query(reinterpret_cast<const void *>(bm::softmax_multinomial_kernel), q));
+    out4[0] = q[0]; out4[1] = q[1]; out4[2] = q[2];
+    out4[3] = std::min<long long>(8192, q[2] / (long long)(2 * sizeof(float)));
+    return 0;
+}
+
 int bm_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -755,9 +764,14 @@ int bm_rbm_create(const bm_rbm_config *cfg, bm_rbm **out) {
     BM_CHECK(cfg->h_unit == BM_UNIT_BERNOULLI || cfg->h_unit == BM_UNIT_MULTINOMIAL, "unknown hidden unit %d", cfg->h_unit);
     if (cfg->h_unit == BM_UNIT_MULTINOMIAL) {
         BM_CHECK(cfg->n_samples >= 1, "MultinomialRBM: n_samples must be >= 1 (got %d)", cfg->n_samples);
-        BM_CHECK(cfg->n_hidden <= 8192, "MultinomialRBM: n_hidden %d > 8192 (softmax row staged in LDS)", cfg->n_hidden);
     }
     BM_CHECK(bm_device_count() > 0, "no HIP device visible: libbm355 has no CPU fallback");
+    if (cfg->h_unit == BM_UNIT_MULTINOMIAL) {
+        int64_t q[4];
+        BM_TRY(bm_rbm_multinomial_limit(q));
+        BM_CHECK(cfg->n_hidden <= q[3], "MultinomialRBM: n_hidden %d > %lld (softmax row staged in LDS: 8 bytes per unit, the runtime "
+                 "allows a workgroup %lld bytes of dynamic LDS; at most 8192 units)", cfg->n_hidden, (long long)q[3], (long long)q[2]);
+    }
     auto h = std::make_unique<bm_rbm>();
     h->cfg = *cfg;
     h->V = cfg->n_visible; h->H = cfg->n_hidden; h->maxB = cfg->max_batch;

@@ -784,15 +784,30 @@ using namespace bm64;
 
 extern "C" {
 
+int bm_rbm64_multinomial_limit(int64_t *out4) {
+    BM_CHECK(out4, "null argument");
+    long long q[3];
+    void (*kern)(double *, int, int, int, double *, PhiloxKey, long long) = softmax_multinomial_kernel;
+    BM_TRY(bm::dyn_lds_query(reinterpret_cast<const void *>(kern), q));
+    out4[0] = q[0]; out4[1] = q[1]; out4[2] = q[2];
+    out4[3] = std::min<long long>(8192, q[2] / (long long)(2 * sizeof(double)));
+    return 0;
+}
+
 int bm_rbm64_create(const bm_rbm_config *cfg, const double *hyper5, bm_rbm64 **out) {
     BM_CHECK(cfg && out, "null argument");
     BM_CHECK(cfg->n_visible >= 1 && cfg->n_hidden >= 1, "bad layer sizes %d x %d", cfg->n_visible, cfg->n_hidden);
     BM_CHECK(cfg->max_batch >= 1, "max_batch must be >= 1");
     BM_CHECK(cfg->v_unit == BM_UNIT_BERNOULLI || cfg->v_unit == BM_UNIT_GAUSSIAN, "unknown visible unit %d", cfg->v_unit);
     BM_CHECK(cfg->h_unit == BM_UNIT_BERNOULLI || cfg->h_unit == BM_UNIT_MULTINOMIAL, "unknown hidden unit %d", cfg->h_unit);
-    BM_CHECK(cfg->h_unit != BM_UNIT_MULTINOMIAL || (cfg->n_samples >= 1 && cfg->n_hidden <= 8192),
-             "MultinomialRBM needs n_samples >= 1 and n_hidden <= 8192 (got %d, %d)", cfg->n_samples, cfg->n_hidden);
+    BM_CHECK(cfg->h_unit != BM_UNIT_MULTINOMIAL || cfg->n_samples >= 1, "MultinomialRBM needs n_samples >= 1 (got %d)", cfg->n_samples);
     BM_CHECK(bm_device_count() > 0, "no HIP device visible: libbm355 has no CPU fallback");
+    if (cfg->h_unit == BM_UNIT_MULTINOMIAL) {
+        int64_t q[4];
+        BM_TRY(bm_rbm64_multinomial_limit(q));
+        BM_CHECK(cfg->n_hidden <= q[3], "MultinomialRBM (float64): n_hidden %d > %lld (softmax row staged in LDS: 16 bytes per unit, "
+                 "the runtime allows a workgroup %lld bytes of dynamic LDS; at most 8192 units)", cfg->n_hidden, (long long)q[3], (long long)q[2]);
+    }
     auto h = std::make_unique<bm_rbm64>();
     h->cfg = *cfg;
     h->V = cfg->n_visible; h->H = cfg->n_hidden; h->maxB = cfg->max_batch;

@@ -288,6 +288,12 @@ typedef struct bm_rbm64 bm_rbm64;
 /* hyper5 = {l2, sparsity_target, sparsity_cost, sparsity_damping, dropout (<0: off)} as doubles (a Python
  * float is a double; the float fields of cfg would round them); NULL: take them from cfg */
 int bm_rbm64_create(const bm_rbm_config *cfg, const double *hyper5, bm_rbm64 **out);
+/* The width limit of a Multinomial hidden layer, float32 (RBM and DBM) and float64: the softmax stages a row in DYNAMIC LDS
+ * (two reals per unit), so the limit is what the runtime allows one workgroup of that kernel, capped at 8192.  A query, no
+ * launch: out4 = {hipDeviceAttributeMaxSharedMemoryPerBlock, the kernel's static LDS bytes, the dynamic LDS bytes a launch of
+ * it may ask for, the largest n_hidden the create calls accept}. */
+int bm_rbm_multinomial_limit(int64_t *out4);
+int bm_rbm64_multinomial_limit(int64_t *out4);
 int bm_rbm64_destroy(bm_rbm64 *h);
 int bm_rbm64_sync(bm_rbm64 *h);
 int bm_rbm64_seed(bm_rbm64 *h, uint64_t seed);                                  /* tf_model.py:20-21 */

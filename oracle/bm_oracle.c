@@ -311,6 +311,11 @@ static void softmax_multinomial_row(const float *l, int I, int M, int sample, fl
     }
 }
 
+/* e[i] and the prefix sums c[i] that the draws of a row search (tests/multinomial_probes.py: which units can be drawn at all) */
+void orc_softmax_prefix(const float *l, int I, float *e, float *c) {
+    softmax_multinomial_row(l, I, 1, 0, NULL, NULL, make_key(0, 0, 0), 0, e, c);
+}
+
 /* bmult: multiplier of the bias (== mult except in the mean-field init, dbm.py:434-446) */
 void orc_act2(const float *Q1, int K1, const float *P1k,
               const float *Q2, int K2, const float *P2k,
@@ -1083,6 +1088,10 @@ static void softmax_multinomial_row_d(const double *l, int I, int M, int sample,
             states[lo] = states[lo] + 1.0;
         }
     }
+}
+
+void orc_softmax_prefix_d(const double *l, int I, double *e, double *c) {
+    softmax_multinomial_row_d(l, I, 1, 0, NULL, NULL, make_key(0, 0, 0), 0, e, c);
 }
 
 /* z[j][i] = sum_k Q[j][k] * Pk[k][i], then the layer activation / draw (layers.py:34-36,47-51,84-89);
