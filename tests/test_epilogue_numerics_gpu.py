@@ -218,8 +218,10 @@ def test_dbm_ais_brackets_the_closed_form_with_saturated_chain_biases(gpu_lib):
 
 # ---- e. sampling at saturation, default and fast-binary
 def test_sampling_at_saturation_default_and_fast_binary(gpu_lib):
-    """What this can and cannot see: fast-binary mode is legal only with both samplers on, so the public ABI never returns the
-    means of sigmoid_hw - only the bitmap `u < p`.  Above 17.33 a sigmoid_hw that failed to round to 1.0f would lose draws
+    """What this can and cannot see: in the RBM fast-binary mode is legal only with both samplers on, so the RBM ABI never
+    returns the means of sigmoid_hw - only the bitmap `u < p`.  (The DBM gates the mode per pass and only asks for sampled
+    hidden layers: a one-layer DbmEngine with sample_v_states = False does return them, and
+    tests/test_fast_binary_exact_gpu.py holds them to float64 there.)  Above 17.33 a sigmoid_hw that failed to round to 1.0f would lose draws
     with u close to 1 (seen here: all ones is asserted for both paths).  Below -20 a sigmoid_hw that flushed to zero would
     change a draw only where u == 0, which these ~8 000 draws meet with a probability of about 0.1 %: positivity down to -80 is
     NOT established by the bitmap equality, only that no draw decides differently.  That the fast path really ran (and the
