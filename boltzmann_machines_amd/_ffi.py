@@ -180,6 +180,7 @@ SIGNATURES = {
     'bm_dbm_pt_init': [_vp, _i32, _i32, _vp, _vp, _i64],
     'bm_dbm_pt_sweep': [_vp, _i32],
     'bm_dbm_pt_read': [_vp, _vp, _vp, _vp, _vp, _vp],
+    'bm_dbm_train_step_pt': [_vp, _vp, _f32, _f32, _i32, _ip, _fp],
     'bm_dbm_ais': [_vp, _i32, _i32, _i32, _u64, _i64, _vp],
     'bm_dbm_log_proba': [_vp, _vp, _vp],
     'bm_dbm_timer_start': [_vp],

@@ -1325,13 +1325,13 @@ int bm_dbm_pt_read(bm_dbm *h, float *V_dev, float *H1_dev, float *H2_dev, int64_
     BM_CHECK(h->pt_M > 0, "bm_dbm_pt_read: no ensemble (call bm_dbm_pt_init first)");
     BM_CHECK(!H2_dev || h->L == 2, "bm_dbm_pt_read: H2_dev for a stack of one hidden layer");
     const int M = h->pt_M, R = h->pt_R;
-    if (V_dev)
-        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, (const float *)h->ptv.p,
-                           h->ptv.ld, h->V, (const float *)h->pth[0].p, h->pth[0].ld, h->n[1], V_dev, h->V, H1_dev);
-    else BM_CHECK(!H1_dev, "bm_dbm_pt_read: H1_dev without V_dev");
-    if (H2_dev)                                    // (the same kernel, h2 in the place of v)
-        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, (const float *)h->pth[1].p,
-                           h->pth[1].ld, h->n[2], (const float *)nullptr, 0, 0, H2_dev, h->n[2], (float *)nullptr);
+    BM_CHECK(V_dev || !H1_dev, "bm_dbm_pt_read: H1_dev without V_dev");
+    if (V_dev || H2_dev) {                         // (one launch for the up to three matrices)
+        PtGatherJobs g{};
+        if (V_dev) { g.j[0] = {h->ptv.p, h->ptv.ld, h->V, V_dev, h->V}; g.j[1] = {h->pth[0].p, h->pth[0].ld, h->n[1], H1_dev, h->n[1]}; }
+        if (H2_dev) g.j[2] = {h->pth[1].p, h->pth[1].ld, h->n[2], H2_dev, h->n[2]};
+        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, g);
+    }
     BM_HIP(hipGetLastError());
     BM_HIP(hipStreamSynchronize(h->stream));
     if (swaps_host && R > 1) {
@@ -1339,6 +1339,51 @@ int bm_dbm_pt_read(bm_dbm *h, float *V_dev, float *H1_dev, float *H2_dev, int64_
         BM_HIP(hipMemcpy(swaps_host, h->pt_cnt.p, (size_t)2 * (R - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
     }
     if (ladder_idx_host) BM_HIP(hipMemcpy(ladder_idx_host, h->pt_idx.p, (size_t)M * R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// One update whose negative particles are the beta = 1 rows of the tempered ensemble (bm355.h): bm_dbm_train_step
+// with another source for h->v / h->H[i].  Everything on the main stream, no host synchronisation of its own.
+int bm_dbm_train_step_pt(bm_dbm *h, const float *X_dev, float lr, float mom, int32_t k, int32_t *out_n_mf, float *out_msre) {
+    BM_CHECK(h && X_dev, "null argument");
+    BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
+    BM_TRY(check_dw(h, "bm_dbm_train_step_pt"));
+    BM_CHECK(h->pt_M > 0, "bm_dbm_train_step_pt: no ensemble (call bm_dbm_pt_init first)");
+    BM_CHECK(h->pt_M >= h->M, "bm_dbm_train_step_pt: the ensemble has %d chains, fewer than n_particles = %d (every particle is the "
+             "beta = 1 row of a chain of its own)", h->pt_M, h->M);
+    BM_TRY(check_pt_model(h, "bm_dbm_train_step_pt"));
+    BM_CHECK(!h->comm && !h->xchg && !h->mf_reduce, "bm_dbm_train_step_pt: the handle has a communicator or a direct exchange attached "
+             "(data-parallel job); the chains of the ensemble are not sharded over ranks");
+    const int rows = h->pt_M * h->pt_R, nH2 = h->L == 2 ? h->n[2] : 0;
+    // 1. the v.vb and h2.b2 partials of the swap energy under the biases of NOW (the previous update moved them)
+    {
+        const PtRescoreJob jv{h->ptv.p, h->ptv.ld, h->V, h->vb.p, h->ptpart_v.p};
+        const PtRescoreJob jh{h->pth[1].p, h->pth[1].ld, nH2, h->hb[1].p, h->ptpart_h2.p};
+        const long long nthr = (long long)rows * (nslots(h->V) + nslots(nH2));
+        hipLaunchKernelGGL(pt_rescore_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, rows, h->pt_rows, jv, jh);
+    }
+    // 2. positive phase
+    int nmf = 0;
+    BM_TRY(mean_field(h, X_dev, &nmf));
+    // 3. the tempered steps of all rows: a sweep at the handle's call
+    for (int t = 0; t < k; ++t) pt_step(h, t);
+    // 4. hand-over: the beta = 1 rows of the chains [0, n_particles) become the dense particles the update reads (a launch of
+    //    its own: h1 is stored BEFORE the swap that settles which row is at beta = 1)
+    {
+        PtGatherJobs g{};
+        g.j[0] = {h->ptv.p, h->ptv.ld, h->V, h->v.p, h->v.ld};
+        g.j[1] = {h->pth[0].p, h->pth[0].ld, h->n[1], h->H[0].p, h->H[0].ld};
+        if (h->L == 2) g.j[2] = {h->pth[1].p, h->pth[1].ld, h->n[2], h->H[1].p, h->H[1].ld};
+        hipLaunchKernelGGL(pt_gather_kernel, dim3(h->M), dim3(256), 0, h->stream, h->M, h->pt_R, (const int *)h->pt_idx.p, g);
+    }
+    h->updates_seen++;
+    h->pt_step += k;
+    BM_HIP(hipGetLastError());
+    // 5. + 6. as bm_dbm_train_step
+    if (out_msre) BM_TRY(recon_msre(h, X_dev, out_msre));
+    BM_TRY(apply_update(h, X_dev, lr, mom));
+    if (out_n_mf) *out_n_mf = nmf;
+    h->call++;
     return 0;
 }
 

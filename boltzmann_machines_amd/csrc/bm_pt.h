@@ -1,5 +1,6 @@
 // bm_pt.h — the small kernels of parallel tempering that the RBM and the DBM engine share: the slot
-// partial of a state . bias product in the epilogue's order, the replica exchange, the gather of the beta = 1 rows.
+// partial of a state . bias product in the epilogue's order, the re-scoring of those partials under moved biases, the replica
+// exchange, the gather of the beta = 1 rows.
 #pragma once
 #include "bm_rng.h"
 
@@ -59,16 +60,37 @@ __global__ __launch_bounds__(256) void pt_swap_kernel(int M, int R, int parity, 
     }
 }
 
-// the beta = 1 row of every chain (ladder index R - 1: exactly one) -> V_out [M][V] pitch ldvo and dense H_out [M][H] (or null)
-__global__ __launch_bounds__(256) void pt_gather_kernel(int M, int R, const int *idx, const float *v, int ldv, int V, const float *hs, int ldh,
-                                                        int H, float *V_out, int ldvo, float *H_out) {
+// Re-scoring at the start of a tempered update: the state . bias slot partials of every row from its stored
+// state and the CURRENT bias - the previous update changed the bias after the pass that left them.  Up to two jobs in one launch
+// (the RBM: v.vb; the DBM: v.vb and, at two hidden layers, h2.b2; n == 0: absent), one thread per row and slot of either, the
+// computation of the init kernels': with an unchanged bias it rewrites the bits that are there.
+struct PtRescoreJob { const float *x; int ld, n; const float *bias; float *part; };
+__global__ __launch_bounds__(256) void pt_rescore_kernel(int rows, int ld_part, PtRescoreJob a, PtRescoreJob b) {
+    const int nsa = (a.n + 15) / 16, ns = nsa + (b.n + 15) / 16;
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)rows * ns) return;
+    const int row = (int)(e / ns), s = (int)(e % ns);
+    const PtRescoreJob &j = s < nsa ? a : b;
+    const int slot = s < nsa ? s : s - nsa;
+    j.part[(size_t)slot * ld_part + row] = pt_vb_slot(slot, j.n, j.bias, [&](int c) { return j.x[(size_t)row * j.ld + c]; });
+}
+
+// the beta = 1 row of every chain c < M (ladder index R - 1: exactly one) -> row c of up to three matrices (src [.][n] pitch lds ->
+// dst [M][n] pitch ldd; dst null: absent): bm_*_pt_read, the gather form of the RBM's hand-over, the DBM's hand-over of
+// (v, h1, h2) to its dense particle matrices.  One workgroup per chain.
+struct PtGatherJob { const float *src; int lds, n; float *dst; int ldd; };
+struct PtGatherJobs { PtGatherJob j[3]; };
+__global__ __launch_bounds__(256) void pt_gather_kernel(int M, int R, const int *idx, PtGatherJobs g) {
     const int c = blockIdx.x;
     if (c >= M) return;
     int src = -1;
     for (int r = 0; r < R; ++r) if (idx[(size_t)c * R + r] == R - 1) src = c * R + r;
     if (src < 0) return;
-    for (int i = threadIdx.x; i < V; i += blockDim.x) V_out[(size_t)c * ldvo + i] = v[(size_t)src * ldv + i];
-    if (H_out) for (int i = threadIdx.x; i < H; i += blockDim.x) H_out[(size_t)c * H + i] = hs[(size_t)src * ldh + i];
+    for (int m = 0; m < 3; ++m) {
+        const PtGatherJob &j = g.j[m];
+        if (!j.dst) continue;
+        for (int i = threadIdx.x; i < j.n; i += blockDim.x) j.dst[(size_t)c * j.ldd + i] = j.src[(size_t)src * j.lds + i];
+    }
 }
 
 }  // namespace bm

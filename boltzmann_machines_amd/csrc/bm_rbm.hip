@@ -607,7 +607,7 @@ static void ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &k
 
 // ---- parallel tempering (bm355.h: bm_rbm_pt_init / _sweep / _read)
 
-// (pt_vb_slot, pt_swap_kernel and pt_gather_kernel: bm_pt.h, shared with bm_dbm_pt_*)
+// (pt_vb_slot, pt_rescore_kernel, pt_swap_kernel and pt_gather_kernel: bm_pt.h, shared with bm_dbm_pt_*)
 
 // Start of the ensemble: one thread per row and 16-column slot.  v_0 ~ Ber(1/2) at its flat index of the global row (V0 null) or
 // the chain's row of V0 [M][V] for all its R replicas; the slot's partial of v_0.vb (pt_vb_slot); row c * R + r starts at ladder
@@ -626,17 +626,6 @@ __global__ __launch_bounds__(256) void pt_init_kernel(float *v, int ld, int rows
         return x;
     });
     if (slot == 0) { row_mult[row] = beta[row % R]; idx[row] = row % R; }
-}
-
-// Re-scoring at the start of a tempered update: the v.vb slot partials of every row from its stored state and the
-// CURRENT vb - the previous update changed vb after the prop-down that left them.  One thread per row and slot, the same
-// computation as pt_init_kernel's: with an unchanged vb it rewrites the bits that are there.
-__global__ __launch_bounds__(256) void pt_rescore_kernel(const float *v, int ld, int rows, int V, const float *vb, float *part, int ld_part) {
-    const int ns = (V + 15) / 16;
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long long)rows * ns) return;
-    const int row = (int)(e / ns), slot = (int)(e % ns);
-    part[(size_t)slot * ld_part + row] = pt_vb_slot(slot, V, vb, [&](int c) { return v[(size_t)row * ld + c]; });
 }
 
 static int ensure_pt_rows(bm_rbm *h, int rows, int R) {
@@ -1419,9 +1408,10 @@ int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, i
     BM_CHECK(h, "null argument");
     BM_CHECK(h->pt_M > 0, "bm_rbm_pt_read: no ensemble (call bm_rbm_pt_init first)");
     const int M = h->pt_M, R = h->pt_R;
-    if (V_dev)
-        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, (const float *)h->ptv.p,
-                           h->ptv.ld, h->V, (const float *)h->pth.p, h->pth.ld, h->H, V_dev, h->V, H_dev);
+    if (V_dev) {
+        const PtGatherJobs g{{{h->ptv.p, h->ptv.ld, h->V, V_dev, h->V}, {h->pth.p, h->pth.ld, h->H, H_dev, h->H}, {}}};
+        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, g);
+    }
     else BM_CHECK(!H_dev, "bm_rbm_pt_read: H_dev without V_dev");
     BM_HIP(hipGetLastError());
     BM_HIP(hipStreamSynchronize(h->stream));
@@ -1447,17 +1437,18 @@ int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, flo
     ensure_wt(h);
     // 1. the v.vb partials of the swap energy under the vb of NOW (the previous update changed it)
     const long long nthr = (long long)rows * nslots(h->V);
-    hipLaunchKernelGGL(pt_rescore_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, (const float *)h->ptv.p, h->ptv.ld,
-                       rows, h->V, (const float *)h->vb.p, h->ptpart_v.p, h->pt_rows);
+    const PtRescoreJob rescore{h->ptv.p, h->ptv.ld, h->V, h->vb.p, h->ptpart_v.p}, none{};
+    hipLaunchKernelGGL(pt_rescore_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, rows, h->pt_rows, rescore, none);
     // 2. positive phase: the h0 means alone
     h->Xin = X_dev; h->Xin_ld = h->V;
     h->fe_in_chain = false;
     launch_up(h, X_dev, h->V, B, h->h0m.p, nullptr, h->h0m.ld, 0, SITE_H0, 0);
     // 3. + 4. the tempered steps; the last prop-down leaves the beta = 1 rows of the chains [0, B) in vs
     for (int t = 0; t < k; ++t) pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
-    if (!sel_in_pass)
-        hipLaunchKernelGGL(pt_gather_kernel, dim3(B), dim3(256), 0, h->stream, (int)B, h->pt_R, (const int *)h->pt_idx.p, (const float *)h->ptv.p,
-                           h->ptv.ld, h->V, (const float *)nullptr, 0, h->H, h->vs.p, h->vs.ld, (float *)nullptr);
+    if (!sel_in_pass) {
+        const PtGatherJobs g{{{h->ptv.p, h->ptv.ld, h->V, h->vs.p, h->vs.ld}, {}, {}}};
+        hipLaunchKernelGGL(pt_gather_kernel, dim3(B), dim3(256), 0, h->stream, (int)B, h->pt_R, (const int *)h->pt_idx.p, g);
+    }
     // 5. negative means: only -h is consumed (run_chain's neg_only form)
     launch_up(h, h->vs.p, h->vs.ld, B, nullptr, nullptr, h->hm.ld, 0, SITE_H, 0, h->hneg.p);
     h->hm_is_neg = true;

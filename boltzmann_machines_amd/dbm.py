@@ -103,6 +103,9 @@ class DBM(EngineModel):
         self._ais_literal = os.environ.get('BM355_AIS_LITERAL', '0') == '1'
         # sigmoid of the Bernoulli layers (set_mean_field_arithmetic / BM355_SIGMOID_LITERAL=1)
         self._sigmoid_literal = os.environ.get('BM355_SIGMOID_LITERAL', '0') == '1'
+        # source of the negative particles of fit() (set_negative_phase; not a constructor keyword and not written to
+        # checkpoints): None = the persistent particles, else (betas, n_chains) of the tempered ensemble
+        self._neg_phase = None
 
     # ---- composition from pre-trained RBMs (reference dbm.py:207-231) ------------------
     def load_rbms(self, rbms):
@@ -301,6 +304,9 @@ class DBM(EngineModel):
     def _train_epoch(self, Xd, N):
         lr, mom, k = self._feed()
         msres, nmfs = [], []
+        step = self._engine.train_step
+        if self._neg_phase is not None:
+            step = self._tempered_step()
         if self._dp is not None:
             # data-parallel: the global minibatch is world * batch_size rows, this rank's slice starts at
             # rank * batch_size inside it (the msre summary is not fetched: it would be a rank-local number)
@@ -313,12 +319,24 @@ class DBM(EngineModel):
         for start in range(0, N, self.batch_size):
             self.iter_ += 1
             if self.iter_ % self.train_metrics_every_iter == 0:
-                nmf, msre = self._engine.train_step(Xd, lr, mom, k, row=start, want_msre=True)
+                nmf, msre = step(Xd, lr, mom, k, row=start, want_msre=True)
                 msres.append(msre)
                 nmfs.append(nmf)
             else:
-                self._engine.train_step(Xd, lr, mom, k, row=start)
+                step(Xd, lr, mom, k, row=start)
         return (np.mean(msres) if msres else None, np.mean(nmfs) if nmfs else None)
+
+    def _tempered_step(self):
+        """the update of an epoch with the tempered negative phase: bm_dbm_train_step_pt, its ensemble built first where this
+        fit() call has none yet or the ladder / n_chains changed (random start under the call's seed: no host seed is drawn)"""
+        self._check_tempered_fit()
+        eng = self._engine
+        betas, n_chains = self._neg_phase
+        if getattr(self, '_pt_fresh', True) or getattr(eng, '_pt_train_key', None) != self._neg_phase:
+            eng.pt_init(n_chains, betas)
+            eng._pt_train_key = self._neg_phase
+            self._pt_fresh = False
+        return eng.train_step_pt
 
     def _run_val_metrics(self, X_val, Xvd):
         # one fetch of [msre, n_mf_updates] per batch (reference dbm.py:810-816).  Both tensors sit under the
@@ -336,6 +354,9 @@ class DBM(EngineModel):
         return np.mean(msres), np.mean(nmfs)
 
     def _fit(self, X, X_val=None, *args, **kwargs):
+        self._pt_fresh = True          # a tempered negative phase builds its ensemble at this call's first update
+        if self._neg_phase is not None:
+            self._check_tempered_fit()
         dt = self._engine.dtype
         X = np.ascontiguousarray(X, dtype=dt)
         self._check_batches(X, sharded=True)
@@ -547,7 +568,7 @@ class DBM(EngineModel):
                 raise ValueError('`V_init` has invalid shape {0}: expected [{1}, {2}]'.format(V_init.shape, n_samples, self.n_visible_))
             V0d = as_device(V_init, np.float32)
         eng = self._engine
-        eng.pt_init(n_samples, betas, V0d)
+        eng.pt_init(n_samples, betas, V0d)          # (replaces the ensemble of a tempered negative phase: _pt_train_key)
         eng.pt_sweep(int(n_gibbs_steps))
         Vd = _ffi.DeviceArray((n_samples, self.n_visible_), np.float32)
         swaps, _ = eng.pt_read(Vd)
@@ -555,6 +576,70 @@ class DBM(EngineModel):
         if return_stats:
             return V, swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
         return V
+
+    # ---- tempered negative phase (no counterpart in the reference) ---------------
+    def _check_tempered_fit(self, what='fit'):
+        """what may have changed since set_negative_phase (set_params, a data-parallel engine): refused before an epoch starts"""
+        self._check_temperable(what)
+        if getattr(self, '_dp', None) is not None or os.environ.get('BM355_DATA_PARALLEL', '0') == '1':
+            raise NotImplementedError('%s.%s: a tempered negative phase is not combined with data parallelism (the chains of '
+                                      'the ensemble are not sharded over ranks)' % (self.__class__.__name__, what))
+        if self._neg_phase is not None and self._neg_phase[1] < self.n_particles:
+            raise ValueError('`n_chains` must be >= n_particles (got {0} < {1})'.format(self._neg_phase[1], self.n_particles))
+
+    def set_negative_phase(self, kind='cd', n_temperatures=10, betas=None, n_chains=None):
+        """Where the negative particles of `fit` come from.
+
+        kind='cd' (the default, the reference's training graph): `n_particles` persistent particles, advanced by
+        `n_gibbs_steps` single-temperature Gibbs sweeps per update.
+        kind='tempered': parallel tempering on the DBM's joint (as `sample_v_tempered`).  A persistent ensemble of `n_chains`
+        chains with one replica per temperature of the ladder 0 < betas[0] < ... < betas[-1] = 1 lives on the device; every
+        update sweeps all of it for `n_gibbs_steps` tempered steps (h1 ~ p_beta(h1|v, h2), exchange of neighbouring
+        temperatures, h2 ~ p_beta(h2|h1), v ~ p_beta(v|h1)) and takes the beta = 1 replicas of the first `n_particles` chains
+        as its negative particles; mean-field, gradients, momentum, l2, max-norm and the sparsity terms are unchanged.  The
+        hot replicas keep crossing between the modes that single-temperature particles stay in.
+
+        betas : the ladder; None: float32(linspace(0, 1, n_temperatures + 1)[1:]), `BernoulliRBM.sample_v`'s default.
+        n_chains : None: `n_particles`; must be >= `n_particles` (further chains sweep and exchange, but hand nothing over).
+        The ensemble is built at the first update of every `fit()` call (random start under that call's seed from the host
+        stream: no further seed is drawn) and again whenever the ladder or `n_chains` changed; `sample_v_tempered` replaces
+        it.  Neither the ensemble nor this setting is written to checkpoints - params.json keeps the reference's schema - so a
+        loaded model trains with the default until this method is called again, and a resumed fit starts a fresh ensemble.
+        The persistent particles `v`, `h`, `h_1` the checkpoint does hold are, after a tempered update, the handed-over
+        beta = 1 rows; `sample_v()` continues from them.
+        The ensemble samples every layer, whatever `sample_v_states` / `sample_h_states` say.  The validation pass
+        (`X_val`) still advances the persistent particles by plain sweeps, as the reference's does; the next tempered update
+        overwrites them.  BM355_FAST_BINARY and chained launches do not apply to the tempered sweeps.
+        Stacks of one or two Bernoulli hidden layers over Bernoulli visible units in float32 only: Gaussian visible units,
+        Multinomial layers, three or more hidden layers, float64, set_mean_field_arithmetic('reference') and data-parallel
+        jobs raise NotImplementedError.  Returns self."""
+        if kind == 'cd':
+            self._neg_phase = None
+            return self
+        if kind != 'tempered':
+            raise ValueError("`kind` must be 'cd' or 'tempered' (got {0!r})".format(kind))
+        self._check_tempered_fit('set_negative_phase')
+        if betas is None:
+            if int(n_temperatures) < 1:
+                raise ValueError('`n_temperatures` must be >= 1 (got {0})'.format(n_temperatures))
+            betas = np.linspace(0., 1., int(n_temperatures) + 1)[1:]
+        betas = np.asarray(betas, dtype=np.float32).ravel()
+        if len(betas) < 1 or betas[-1] != 1. or betas[0] <= 0. or np.any(np.diff(betas) <= 0.):
+            raise ValueError('`betas` must increase strictly inside (0, 1] and end at 1 (got {0})'.format(betas))
+        n_chains = self.n_particles if n_chains is None else int(n_chains)
+        if n_chains < self.n_particles:
+            raise ValueError('`n_chains` must be >= n_particles (got {0} < {1})'.format(n_chains, self.n_particles))
+        self._neg_phase = (tuple(float(b) for b in betas), n_chains)
+        return self
+
+    def tempering_stats(self):
+        """Acceptance rate (accepts / attempts) of every neighbouring pair of temperatures, [n_temperatures - 1], since the
+        ensemble of the tempered negative phase was built.  Waits for the device; copies no states."""
+        eng = self._engine
+        if not isinstance(eng, DbmEngine) or getattr(eng, '_pt_train_key', None) is None:
+            raise RuntimeError('`tempering_stats`: no tempered ensemble (call set_negative_phase(\'tempered\') and fit first)')
+        swaps, _ = eng.pt_read()
+        return swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
 
     def set_ais_accumulation(self, dtype='float64'):
         """How `log_Z` accumulates the AIS log-weights.  'float64' (default): per chain the difference of consecutive

@@ -524,6 +524,7 @@ class DbmEngine(object):
         check(self.lib.bm_dbm_pt_init(self._h, int(n_chains), len(b), b.ctypes.data_as(C.c_void_p),
                                       V0_d.ptr if V0_d is not None else None, int(chain0)))
         self._pt_shape = (int(n_chains), len(b))
+        self._pt_train_key = None                 # (whoever builds the ensemble for training records its ladder: dbm.py)
 
     def pt_sweep(self, n_steps):
         """n_steps of (tempered h1 pass, replica exchange, tempered h2 pass, tempered v pass) on the whole ensemble"""
@@ -540,6 +541,15 @@ class DbmEngine(object):
                                       swaps.ctypes.data_as(C.c_void_p) if swaps.size else None,
                                       idx.ctypes.data_as(C.c_void_p) if idx.size else None))
         return swaps, idx
+
+    # tempered negative phase (bm355.h: bm_dbm_train_step_pt); the ensemble of pt_init supplies the particles
+    def train_step_pt(self, Xd, lr, momentum, k, row=0, want_msre=False):
+        """train_step whose negative particles are the beta = 1 rows of the chains [0, n_particles) after k tempered steps of
+        the whole ensemble; returns (n_mf, msre or None)"""
+        nmf, msre = C.c_int32(), C.c_float()
+        check(self.lib.bm_dbm_train_step_pt(self._h, Xd.offset_ptr(row * self.V), lr, momentum, k, C.byref(nmf),
+                                            C.byref(msre) if want_msre else None))
+        return int(nmf.value), (float(msre.value) if want_msre else None)
 
     def ais(self, n_betas, n_runs, k, seed, chain0=0):
         out = np.empty(n_runs, dtype=np.float32)
@@ -645,9 +655,10 @@ class DbmEngine64(DbmEngine):
         raise NotImplementedError('conditional sampling has no float64 entry (bm_dbm64_* has no clamped sample_v)')
 
     def _no_pt(self, *a, **kw):
-        raise NotImplementedError('parallel tempering has no float64 entry (bm_dbm64_* has no pt_init / pt_sweep / pt_read)')
+        raise NotImplementedError('parallel tempering has no float64 entry (bm_dbm64_* has no pt_init / pt_sweep / pt_read / '
+                                  'train_step_pt)')
 
-    pt_init = pt_sweep = pt_read = _no_pt
+    pt_init = pt_sweep = pt_read = train_step_pt = _no_pt
 
     def set_fast_binary(self, on, everywhere=False):
         if on:

@@ -428,6 +428,28 @@ int bm_dbm_sample_v_clamped(bm_dbm *h, int32_t n_gibbs_steps, const float *clamp
 int bm_dbm_pt_init(bm_dbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0);
 int bm_dbm_pt_sweep(bm_dbm *h, int32_t n_steps);
 int bm_dbm_pt_read(bm_dbm *h, float *V_dev, float *H1_dev, float *H2_dev, int64_t *swaps_host, int32_t *ladder_idx_host);
+/* Tempered negative phase of the DBM: one update of bm_dbm_train_step whose negative particles are the beta = 1
+ * rows of the chains [0, n_particles) of the ensemble bm_dbm_pt_init built, instead of the handle's persistent particles swept at
+ * one temperature.  On the handle's main stream, no host synchronisation of its own (out_msre waits, as in bm_dbm_train_step):
+ *   1. the v.vb and - at two hidden layers - the h2.b2 slot partials of every ensemble row are recomputed from its state and the
+ *      CURRENT biases in one launch (the previous update moved the biases after the passes that left them; with unchanged
+ *      biases this rewrites the same bits);
+ *   2. positive phase: the mean-field loop of bm_dbm_train_step on X_dev, in the handle's arithmetic mode;
+ *   3. n_gibbs_steps steps of bm_dbm_pt_sweep on ALL n_chains R rows (sites 8 + 16 t, 14 + 16 t, 9 + 16 t, 12 + 16 t of the
+ *      handle's call counter; the swap parity continues the ensemble's step count);
+ *   4. one gather launch copies, for every chain c < n_particles, the row at beta = 1 into particle c: v, h1 and h2 (a launch of
+ *      its own because h1 is stored before the swap that settles which row is at beta = 1);
+ *   5. out_msre (NULL ok): the reconstruction error of bm_dbm_train_step, before the update;
+ *   6. the update of bm_dbm_train_step - gradients, sparsity, momentum, max-norm - on these statistics.
+ * The call counter advances once per update, the ensemble's step count by n_gibbs_steps.  The persistent particles v, h, h_1
+ * are afterwards the handed-over rows; chains beyond n_particles sweep and exchange but hand nothing over.  Every layer of the
+ * ensemble is sampled, whatever sample_v_states / sample_h_states say; fast-binary mode does not apply to the tempered sweeps.
+ * Errors: no ensemble, an ensemble of fewer chains than n_particles, everything bm_dbm_pt_init refuses (Gaussian visible units, a
+ * Multinomial hidden layer, three or more hidden layers, literal-sigmoid mode), n_gibbs_steps < 1, a momentum buffer sharded by
+ * bm_dbm_exchange_apply_direct, a handle with a communicator, a direct exchange or a mean-field all-reduce callback attached
+ * (the chains are not sharded over ranks).  Float32, one process.  (No float64 counterpart.) */
+int bm_dbm_train_step_pt(bm_dbm *h, const float *X_dev, float learning_rate, float momentum, int32_t n_gibbs_steps,
+                         int32_t *out_n_mf, float *out_msre);
 /* AIS (dbm.py:650-736; public log_Z :899-939) for a Bernoulli DBM of any
  * depth (1..4 layers): n_runs chains, n_betas temperatures, n_gibbs_steps
  * transitions per temperature.  values_host [n_runs] receives the per-chain
