@@ -187,6 +187,9 @@ struct Mat : DevArray<float> {
     }
 };
 
+// the 16-column slots of a row of n columns: the epilogues leave one partial of a row sum per slot (ActArgs::rowdot_out)
+static inline int nslots(int n) { return (n + 15) / 16; }
+
 // bf16 matrix [planes][rows][ld] (bm_bf3.h): weight planes or the shadow of a {0,1} state matrix; ld % 64 == 0,
 // zero initialised (the padding must stay zero: the bf16 contraction has no K tail handling)
 struct Mat16 : DevArray<uint16_t> {

@@ -107,16 +107,9 @@ struct bm_dbm {
     DevArray<double> alogw;                        // [ais_rows] log-weights, accumulated in double in a fixed order
     DevBuf ais_send, ais_recv;                     // bm_dbm_ais_sharded: this rank's values / the all-gathered values
     Mat sv_v[2], sv_H[2][MAXL];                    // bm_dbm_sample_v: ping-pong states of its mean sweeps [M][*]
-    // bm_dbm_pt_*: the tempered ensemble of pt_M chains x pt_R replicas, chain-major rows (row c * R + r), allocated on demand for
-    // `pt_rows` rows; nothing else in the handle reads or writes these (L <= 2)
-    int pt_rows = 0, pt_M = 0, pt_R = 0;
-    int64_t pt_chain0 = 0;
-    long long pt_step = 0;                         // steps done since bm_dbm_pt_init: its parity picks the even or the odd ladder pairs
-    Mat ptv, pth[2];                               // states [pt_rows][V], [pt_rows][n1], [pt_rows][n2] (L == 2)
-    DevBuf ptpart_v, ptpart_h1, ptpart_h2;         // slot partials of v.vb, h1.(vW0 + h2W1^T + b1), h2.b2: [ceil(n/16)][pt_rows]
-    DevBuf pt_mult, pt_beta;                       // the temperature of every row [pt_rows] (ActArgs::row_mult), the ladder [pt_R]
-    DevArray<int> pt_idx;                          // the ladder index of every row [pt_rows]
-    DevArray<unsigned long long> pt_cnt;           // [2][R - 1]: swap attempts, accepts per ladder pair
+    // bm_dbm_pt_*: the tempered ensemble (bm_pt.h; layers v, h1 and, at L == 2, h2), allocated on demand; nothing else in the
+    // handle reads or writes it (L <= 2)
+    PtEnsemble pt;
     // fast-binary mode (bm_bf3.h, bm_dbm_set_fast_binary): bf16 planes of W_l (x = below unit, k = above unit) and of
     // W_l^T, bf16 shadows of the AIS state matrices; `fast_now` is set while a sweep with all-binary states runs
     int ais_literal = 0;                           // bm_dbm_set_ais_literal: float32 accumulation in the reference's order
@@ -1183,48 +1176,7 @@ int bm_dbm_sample_v_clamped(bm_dbm *h, int32_t k, const float *clamp_val_dev, co
 
 // ---- parallel tempering (bm355.h: bm_dbm_pt_init / _sweep / _read)
 
-// Start of the ensemble: one thread per row and 16-column slot of the visible layer, then of h2 (nH2 == 0: a one-layer stack has
-// none).  v_0 ~ Ber(1/2) at its flat index of the global row (V0 null) or the chain's row of V0 [M][V] for all its R replicas;
-// h2_0 ~ Ber(1/2) always (key_h2); the slot's partial of v_0.vb / h2_0.b2 (pt_vb_slot); row c * R + r starts at ladder index r,
-// temperature beta[r]
-__global__ __launch_bounds__(256) void dbm_pt_init_kernel(float *v, int ldv, int rows, int R, int V, const float *V0, const float *vb,
-                                                          float *h2, int ldh2, int nH2, const float *b2, const float *beta,
-                                                          PhiloxKey key_v, PhiloxKey key_h2, unsigned long long row0, float *part_v,
-                                                          float *part_h2, int ld_part, float *row_mult, int *idx) {
-    const int nsv = (V + 15) / 16, ns = nsv + (nH2 + 15) / 16;
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long long)rows * ns) return;
-    const int row = (int)(e / ns), slot = (int)(e % ns);
-    if (slot < nsv) {
-        part_v[(size_t)slot * ld_part + row] = pt_vb_slot(slot, V, vb, [&](int c) {
-            const float x = V0 ? V0[(size_t)(row / R) * V + c]
-                               : (philox_uniform_at(key_v, (row0 + row) * (unsigned long long)V + c) < 0.5f ? 1.f : 0.f);
-            v[(size_t)row * ldv + c] = x;
-            return x;
-        });
-    } else {
-        const int s2 = slot - nsv;
-        part_h2[(size_t)s2 * ld_part + row] = pt_vb_slot(s2, nH2, b2, [&](int c) {
-            const float x = philox_uniform_at(key_h2, (row0 + row) * (unsigned long long)nH2 + c) < 0.5f ? 1.f : 0.f;
-            h2[(size_t)row * ldh2 + c] = x;
-            return x;
-        });
-    }
-    if (slot == 0) { row_mult[row] = beta[row % R]; idx[row] = row % R; }
-}
-
-static int ensure_pt_rows(bm_dbm *h, int rows, int R) {
-    if (h->pt_cnt.n < (size_t)2 * std::max(R - 1, 1)) BM_TRY(h->pt_cnt.alloc((size_t)2 * std::max(R - 1, 1)));
-    if (h->pt_beta.n < (size_t)R) BM_TRY(h->pt_beta.alloc(R));
-    if (rows <= h->pt_rows) return 0;
-    h->pt_rows = 0;                                // (set again once every buffer exists: a failure leaves none counted)
-    BM_TRY(h->ptv.alloc(rows, h->V)); BM_TRY(h->ptpart_v.alloc((size_t)nslots(h->V) * rows));
-    BM_TRY(h->pth[0].alloc(rows, h->n[1])); BM_TRY(h->ptpart_h1.alloc((size_t)nslots(h->n[1]) * rows));
-    if (h->L == 2) { BM_TRY(h->pth[1].alloc(rows, h->n[2])); BM_TRY(h->ptpart_h2.alloc((size_t)nslots(h->n[2]) * rows)); }
-    BM_TRY(h->pt_mult.alloc(rows)); BM_TRY(h->pt_idx.alloc(rows));
-    h->pt_rows = rows;
-    return 0;
-}
+// (the ensemble, its start, the replica exchange, the rescore and the gather: bm_pt.h, shared with bm_rbm_pt_*)
 
 // what the tempered family is defined for (the messages name the reason; bm355.h)
 static int check_pt_model(const bm_dbm *h, const char *what) {
@@ -1241,38 +1193,28 @@ static int check_pt_model(const bm_dbm *h, const char *what) {
 }
 
 // one row-tempered pass of the ensemble (the RT flavour of act_kernel), always a per-pass fp32 launch on the main stream:
-//   layer 0: h1 ~ Ber(sigmoid(beta_row (v W0 + h2 W1^T + b1))) from (ptv, pth[1]) - two K segments at L == 2 - leaving the slot
-//            partials of h1.(v W0 + h2 W1^T + b1);  layer 1: h2 from pth[0], leaving those of h2.b2;  layer -1: v from pth[0],
+//   layer 0: h1 ~ Ber(sigmoid(beta_row (v W0 + h2 W1^T + b1))) from (pt.v, pt.h2) - two K segments at L == 2 - leaving the slot
+//            partials of h1.(v W0 + h2 W1^T + b1);  layer 1: h2 from pt.h1, leaving those of h2.b2;  layer -1: v from pt.h1,
 //            leaving those of v.vb
 static void pt_pass(bm_dbm *h, int layer, int t) {
-    const int rows = h->pt_M * h->pt_R;
-    const int64_t row0 = h->pt_chain0 * h->pt_R;
-    const LayerIn below = layer == 0 ? in_of(h->ptv) : (layer == 1 ? in_of(h->pth[0]) : NO_IN);
-    const LayerIn above = layer == 0 ? (h->L == 2 ? in_of(h->pth[1]) : NO_IN) : (layer == 1 ? NO_IN : in_of(h->pth[0]));
-    Mat &out = layer < 0 ? h->ptv : h->pth[layer];
+    PtEnsemble &e = h->pt;
+    const LayerIn below = layer == 0 ? in_of(e.v.x) : (layer == 1 ? in_of(e.h1.x) : NO_IN);
+    const LayerIn above = layer == 0 ? (h->L == 2 ? in_of(e.h2.x) : NO_IN) : (layer == 1 ? NO_IN : in_of(e.h1.x));
+    PtLayer &out = e.layer(layer + 1);
     const PhiloxKey key = dkey(h, layer < 0 ? SITE_DBM_V : SITE_DBM_H + layer, t, h->seed, h->call);
-    LayerPass p = layer_pass(h, layer, rows, below, above, 1.f, 1.f, value_out(1, out.p, out.ld, key, row0));   // (mult: not read)
-    if (layer == 0) { p.a.rowen_out = h->ptpart_h1.p; p.a.ld_part = h->pt_rows; }
-    else if (layer == 1) p.statedot_rows(h->ptpart_h2.p, h->pt_rows, h->hb[1].p);
-    else p.statedot_rows(h->ptpart_v.p, h->pt_rows, h->vb.p);
-    p.a.row_mult = h->pt_mult.p;
+    LayerPass p = layer_pass(h, layer, e.nrows(), below, above, 1.f, 1.f,
+                             value_out(1, out.x.p, out.x.ld, key, e.row0()));   // (mult: not read)
+    if (layer == 0) { p.a.rowen_out = out.part.p; p.a.ld_part = e.rows; }
+    else p.statedot_rows(out.part.p, e.rows, layer == 1 ? h->hb[1].p : h->vb.p);
+    p.a.row_mult = e.mult.p;
     launch_act(p.a, h->stream);
 }
 
 // step t of a tempered call, in gibbs_sweep's order with every layer sampled: h1 from (v, OLD h2); the swap of the parity of the
 // global step number - the state is (v_t, h1_{t+1}, h2_t) and the three partial arrays are exactly its -E; h2; v
 static void pt_step(bm_dbm *h, int t) {
-    const int M = h->pt_M, R = h->pt_R;
     pt_pass(h, 0, t);
-    const int parity = (int)((h->pt_step + t) & 1);
-    const int npair = (R - parity) / 2;
-    if (npair > 0) {
-        const long long nthr = (long long)M * npair;
-        hipLaunchKernelGGL(pt_swap_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, M, R, parity,
-                           (const float *)h->ptpart_v.p, nslots(h->V), (const float *)h->ptpart_h2.p, h->L == 2 ? nslots(h->n[2]) : 0,
-                           (const float *)h->ptpart_h1.p, nslots(h->n[1]), h->pt_rows, h->pt_mult.p, h->pt_idx.p, h->pt_cnt.p,
-                           dkey(h, SITE_DBM_PT_SWAP, t, h->seed, h->call), (unsigned long long)h->pt_chain0);
-    }
+    pt_launch_swap(h->pt, h->stream, t, dkey(h, SITE_DBM_PT_SWAP, t, h->seed, h->call));
     if (h->L == 2) pt_pass(h, 1, t);
     pt_pass(h, -1, t);
 }
@@ -1281,40 +1223,19 @@ static void pt_step(bm_dbm *h, int t) {
 int bm_dbm_pt_init(bm_dbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0) {
     BM_CHECK(h, "null argument");
     BM_TRY(check_pt_model(h, "bm_dbm_pt_init"));
-    BM_CHECK(n_temps >= 1, "n_temps must be >= 1 (got %d)", (int)n_temps);
-    BM_CHECK(betas_host, "null argument");
-    BM_CHECK(n_chains >= 1 && chain0 >= 0, "bad ensemble (n_chains %d >= 1, chain0 %lld >= 0)", (int)n_chains, (long long)chain0);
-    BM_CHECK((long long)n_chains * n_temps <= (1ll << 24), "n_chains * n_temps = %lld rows exceed 2^24",
-             (long long)n_chains * n_temps);
-    for (int r = 0; r < n_temps; ++r)
-        BM_CHECK(betas_host[r] > 0.f && betas_host[r] <= 1.f && (r == 0 || betas_host[r] > betas_host[r - 1]),
-                 "betas must increase strictly inside (0, 1] (betas[%d] = %g)", r, (double)betas_host[r]);
-    BM_CHECK(betas_host[n_temps - 1] == 1.0f, "the last beta must be 1 (got %g)", (double)betas_host[n_temps - 1]);
-    const int M = n_chains, R = n_temps, rows = M * R;
-    h->pt_M = 0;                                   // (an ensemble exists once everything below went through)
-    BM_TRY(ensure_pt_rows(h, rows, R));
-    BM_HIP(hipStreamSynchronize(h->stream));
-    BM_HIP(hipMemcpy(h->pt_beta.p, betas_host, (size_t)R * sizeof(float), hipMemcpyHostToDevice));
-    BM_HIP(hipMemsetAsync(h->pt_cnt.p, 0, (size_t)2 * std::max(R - 1, 1) * sizeof(unsigned long long), h->stream));
-    const int nH2 = h->L == 2 ? h->n[2] : 0;
-    const long long nthr = (long long)rows * (nslots(h->V) + nslots(nH2));
-    hipLaunchKernelGGL(dbm_pt_init_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, h->ptv.p, h->ptv.ld, rows, R,
-                       h->V, V0_dev, (const float *)h->vb.p, h->pth[1].p, h->pth[1].ld, nH2, (const float *)h->hb[1].p,
-                       (const float *)h->pt_beta.p, dkey(h, SITE_DBM_PT_START, 0, h->seed, h->call),
-                       dkey(h, SITE_DBM_PT_START, 1, h->seed, h->call), (unsigned long long)chain0 * (unsigned long long)R,
-                       h->ptpart_v.p, h->ptpart_h2.p, h->pt_rows, h->pt_mult.p, h->pt_idx.p);
-    BM_HIP(hipGetLastError());
-    h->pt_M = M; h->pt_R = R; h->pt_chain0 = chain0; h->pt_step = 0;
-    return 0;
+    BM_TRY(pt_check_ladder(n_chains, n_temps, betas_host, chain0));
+    const int widths[3] = {h->V, h->n[1], h->L == 2 ? h->n[2] : 0};
+    return pt_begin(h->pt, h->stream, widths, n_chains, n_temps, chain0, betas_host, V0_dev, h->vb.p, h->hb[1].p,
+                    dkey(h, SITE_DBM_PT_START, 0, h->seed, h->call), dkey(h, SITE_DBM_PT_START, 1, h->seed, h->call));
 }
 
 int bm_dbm_pt_sweep(bm_dbm *h, int32_t n_steps) {
     BM_CHECK(h, "null argument");
-    BM_CHECK(h->pt_M > 0, "bm_dbm_pt_sweep: no ensemble (call bm_dbm_pt_init first)");
+    BM_CHECK(h->pt.M > 0, "bm_dbm_pt_sweep: no ensemble (call bm_dbm_pt_init first)");
     BM_TRY(check_pt_model(h, "bm_dbm_pt_sweep"));  // (the literal-sigmoid mode may have been switched on since the init)
     BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
     for (int t = 0; t < n_steps; ++t) pt_step(h, t);
-    h->pt_step += n_steps;
+    h->pt.step += n_steps;
     h->call++;
     BM_HIP(hipGetLastError());
     return 0;
@@ -1322,24 +1243,13 @@ int bm_dbm_pt_sweep(bm_dbm *h, int32_t n_steps) {
 
 int bm_dbm_pt_read(bm_dbm *h, float *V_dev, float *H1_dev, float *H2_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
     BM_CHECK(h, "null argument");
-    BM_CHECK(h->pt_M > 0, "bm_dbm_pt_read: no ensemble (call bm_dbm_pt_init first)");
+    BM_CHECK(h->pt.M > 0, "bm_dbm_pt_read: no ensemble (call bm_dbm_pt_init first)");
     BM_CHECK(!H2_dev || h->L == 2, "bm_dbm_pt_read: H2_dev for a stack of one hidden layer");
-    const int M = h->pt_M, R = h->pt_R;
     BM_CHECK(V_dev || !H1_dev, "bm_dbm_pt_read: H1_dev without V_dev");
-    if (V_dev || H2_dev) {                         // (one launch for the up to three matrices)
-        PtGatherJobs g{};
-        if (V_dev) { g.j[0] = {h->ptv.p, h->ptv.ld, h->V, V_dev, h->V}; g.j[1] = {h->pth[0].p, h->pth[0].ld, h->n[1], H1_dev, h->n[1]}; }
-        if (H2_dev) g.j[2] = {h->pth[1].p, h->pth[1].ld, h->n[2], H2_dev, h->n[2]};
-        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, g);
-    }
-    BM_HIP(hipGetLastError());
-    BM_HIP(hipStreamSynchronize(h->stream));
-    if (swaps_host && R > 1) {
-        static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counter width");
-        BM_HIP(hipMemcpy(swaps_host, h->pt_cnt.p, (size_t)2 * (R - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    }
-    if (ladder_idx_host) BM_HIP(hipMemcpy(ladder_idx_host, h->pt_idx.p, (size_t)M * R * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return 0;
+    float *const dst[3] = {V_dev, H1_dev, H2_dev};
+    const int ldd[3] = {h->V, h->n[1], h->L == 2 ? h->n[2] : 0};
+    pt_launch_gather(h->pt, h->stream, h->pt.M, dst, ldd);               // (one launch for the up to three matrices)
+    return pt_read_host(h->pt, h->stream, swaps_host, ladder_idx_host);
 }
 
 // One update whose negative particles are the beta = 1 rows of the tempered ensemble (bm355.h): bm_dbm_train_step
@@ -1348,20 +1258,14 @@ int bm_dbm_train_step_pt(bm_dbm *h, const float *X_dev, float lr, float mom, int
     BM_CHECK(h && X_dev, "null argument");
     BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
     BM_TRY(check_dw(h, "bm_dbm_train_step_pt"));
-    BM_CHECK(h->pt_M > 0, "bm_dbm_train_step_pt: no ensemble (call bm_dbm_pt_init first)");
-    BM_CHECK(h->pt_M >= h->M, "bm_dbm_train_step_pt: the ensemble has %d chains, fewer than n_particles = %d (every particle is the "
-             "beta = 1 row of a chain of its own)", h->pt_M, h->M);
+    BM_CHECK(h->pt.M > 0, "bm_dbm_train_step_pt: no ensemble (call bm_dbm_pt_init first)");
+    BM_CHECK(h->pt.M >= h->M, "bm_dbm_train_step_pt: the ensemble has %d chains, fewer than n_particles = %d (every particle is the "
+             "beta = 1 row of a chain of its own)", h->pt.M, h->M);
     BM_TRY(check_pt_model(h, "bm_dbm_train_step_pt"));
     BM_CHECK(!h->comm && !h->xchg && !h->mf_reduce, "bm_dbm_train_step_pt: the handle has a communicator or a direct exchange attached "
              "(data-parallel job); the chains of the ensemble are not sharded over ranks");
-    const int rows = h->pt_M * h->pt_R, nH2 = h->L == 2 ? h->n[2] : 0;
     // 1. the v.vb and h2.b2 partials of the swap energy under the biases of NOW (the previous update moved them)
-    {
-        const PtRescoreJob jv{h->ptv.p, h->ptv.ld, h->V, h->vb.p, h->ptpart_v.p};
-        const PtRescoreJob jh{h->pth[1].p, h->pth[1].ld, nH2, h->hb[1].p, h->ptpart_h2.p};
-        const long long nthr = (long long)rows * (nslots(h->V) + nslots(nH2));
-        hipLaunchKernelGGL(pt_rescore_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, rows, h->pt_rows, jv, jh);
-    }
+    pt_launch_rescore(h->pt, h->stream, h->vb.p, h->hb[1].p);
     // 2. positive phase
     int nmf = 0;
     BM_TRY(mean_field(h, X_dev, &nmf));
@@ -1370,14 +1274,12 @@ int bm_dbm_train_step_pt(bm_dbm *h, const float *X_dev, float lr, float mom, int
     // 4. hand-over: the beta = 1 rows of the chains [0, n_particles) become the dense particles the update reads (a launch of
     //    its own: h1 is stored BEFORE the swap that settles which row is at beta = 1)
     {
-        PtGatherJobs g{};
-        g.j[0] = {h->ptv.p, h->ptv.ld, h->V, h->v.p, h->v.ld};
-        g.j[1] = {h->pth[0].p, h->pth[0].ld, h->n[1], h->H[0].p, h->H[0].ld};
-        if (h->L == 2) g.j[2] = {h->pth[1].p, h->pth[1].ld, h->n[2], h->H[1].p, h->H[1].ld};
-        hipLaunchKernelGGL(pt_gather_kernel, dim3(h->M), dim3(256), 0, h->stream, h->M, h->pt_R, (const int *)h->pt_idx.p, g);
+        float *const dst[3] = {h->v.p, h->H[0].p, h->L == 2 ? h->H[1].p : nullptr};
+        const int ldd[3] = {h->v.ld, h->H[0].ld, h->L == 2 ? h->H[1].ld : 0};
+        pt_launch_gather(h->pt, h->stream, h->M, dst, ldd);
     }
     h->updates_seen++;
-    h->pt_step += k;
+    h->pt.step += k;
     BM_HIP(hipGetLastError());
     // 5. + 6. as bm_dbm_train_step
     if (out_msre) BM_TRY(recon_msre(h, X_dev, out_msre));

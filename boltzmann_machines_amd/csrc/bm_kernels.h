@@ -1982,8 +1982,6 @@ __global__ __launch_bounds__(256) void mf_init0_kernel(const float *Z, int ldz, 
 }
 
 // ------------------------------------------------------------------ AIS scores (bm_dbm_ais, bm_rbm_ais)
-static inline int nslots(int n) { return (n + 15) / 16; }
-
 // the slot partials one AIS score reads: softplus terms of the even-depth layers, x.hb of the odd-depth layers
 struct AisScoreArgs {
     const float *pe[3]; int ne_slots[3]; int ne;

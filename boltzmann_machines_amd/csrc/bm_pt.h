@@ -1,7 +1,11 @@
-// bm_pt.h — the small kernels of parallel tempering that the RBM and the DBM engine share: the slot
-// partial of a state . bias product in the epilogue's order, the re-scoring of those partials under moved biases, the replica
-// exchange, the gather of the beta = 1 rows.
+// bm_pt.h — parallel tempering, everything that does not depend on the model: the tempered ensemble as a type
+// (PtEnsemble: up to three layers of states and slot partials, the rows' temperatures and ladder indices, the ladder, the swap
+// counters), the checks of a ladder, the start of an ensemble, and the small kernels with their launches - the slot partial of a
+// state . bias product in the epilogue's order, the start, the replica exchange, the re-scoring of the partials under moved
+// biases, the gather of the beta = 1 rows, the read-out of counters and ladder indices.  An engine adds its model's check, its
+// row-tempered passes and their order within a step, and its Philox sites (bm_rbm.hip, bm_dbm.hip).
 #pragma once
+#include "bm_common.h"
 #include "bm_rng.h"
 
 namespace bm {
@@ -21,6 +25,36 @@ __device__ __forceinline__ float pt_vb_slot(int slot, int V, const float *vb, F 
         q[g] = acc;
     }
     return (q[0] + q[1]) + (q[2] + q[3]);
+}
+
+// Start of the ensemble: one thread per row and 16-column slot of the visible layer, then of h2 (nH2 == 0: the model has none - an
+// RBM, a one-layer stack - and every thread is a visible slot).  v_0 ~ Ber(1/2) at its flat index of the global row (V0 null) or
+// the chain's row of V0 [M][V] for all its R replicas; h2_0 ~ Ber(1/2) always (key_h2); the slot's partial of v_0.vb / h2_0.b2
+// (pt_vb_slot); row c * R + r starts at ladder index r, temperature beta[r]
+__global__ __launch_bounds__(256) void pt_init_kernel(float *v, int ldv, int rows, int R, int V, const float *V0, const float *vb,
+                                                      float *h2, int ldh2, int nH2, const float *b2, const float *beta,
+                                                      PhiloxKey key_v, PhiloxKey key_h2, unsigned long long row0, float *part_v,
+                                                      float *part_h2, int ld_part, float *row_mult, int *idx) {
+    const int nsv = (V + 15) / 16, ns = nsv + (nH2 + 15) / 16;
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)rows * ns) return;
+    const int row = (int)(e / ns), slot = (int)(e % ns);
+    if (slot < nsv) {
+        part_v[(size_t)slot * ld_part + row] = pt_vb_slot(slot, V, vb, [&](int c) {
+            const float x = V0 ? V0[(size_t)(row / R) * V + c]
+                               : (philox_uniform_at(key_v, (row0 + row) * (unsigned long long)V + c) < 0.5f ? 1.f : 0.f);
+            v[(size_t)row * ldv + c] = x;
+            return x;
+        });
+    } else {
+        const int s2 = slot - nsv;
+        part_h2[(size_t)s2 * ld_part + row] = pt_vb_slot(s2, nH2, b2, [&](int c) {
+            const float x = philox_uniform_at(key_h2, (row0 + row) * (unsigned long long)nH2 + c) < 0.5f ? 1.f : 0.f;
+            h2[(size_t)row * ldh2 + c] = x;
+            return x;
+        });
+    }
+    if (slot == 0) { row_mult[row] = beta[row % R]; idx[row] = row % R; }
 }
 
 // Replica exchange: one thread per chain c and candidate ladder pair (p, p + 1) with p % 2 == parity; the pairs of one step are
@@ -63,7 +97,7 @@ __global__ __launch_bounds__(256) void pt_swap_kernel(int M, int R, int parity, 
 // Re-scoring at the start of a tempered update: the state . bias slot partials of every row from its stored
 // state and the CURRENT bias - the previous update changed the bias after the pass that left them.  Up to two jobs in one launch
 // (the RBM: v.vb; the DBM: v.vb and, at two hidden layers, h2.b2; n == 0: absent), one thread per row and slot of either, the
-// computation of the init kernels': with an unchanged bias it rewrites the bits that are there.
+// computation of the init kernel's: with an unchanged bias it rewrites the bits that are there.
 struct PtRescoreJob { const float *x; int ld, n; const float *bias; float *part; };
 __global__ __launch_bounds__(256) void pt_rescore_kernel(int rows, int ld_part, PtRescoreJob a, PtRescoreJob b) {
     const int nsa = (a.n + 15) / 16, ns = nsa + (b.n + 15) / 16;
@@ -91,6 +125,130 @@ __global__ __launch_bounds__(256) void pt_gather_kernel(int M, int R, const int 
         if (!j.dst) continue;
         for (int i = threadIdx.x; i < j.n; i += blockDim.x) j.dst[(size_t)c * j.ldd + i] = j.src[(size_t)src * j.lds + i];
     }
+}
+
+// ---- the ensemble and its launches (host)
+
+// one layer of the ensemble: its states, the slot partials the swap energy sums, its width (0: the model has no such layer)
+struct PtLayer {
+    Mat x;                                         // [rows][n]
+    DevBuf part;                                   // [nslots(n)][rows]
+    int n = 0;
+};
+
+// The tempered ensemble of M chains x R replicas, chain-major rows (row c * R + r), allocated on demand for `rows` rows; the
+// handle that holds one frees it member by member.  The partials are those of v.vb, of h1.(its whole input + b1) and of h2.b2.
+struct PtEnsemble {
+    PtLayer v, h1, h2;
+    DevBuf mult, beta;                             // the temperature of every row [rows] (ActArgs::row_mult), the ladder [R]
+    DevArray<int> idx;                             // the ladder index of every row [rows]
+    DevArray<unsigned long long> cnt;              // [2][R - 1]: swap attempts, accepts per ladder pair
+    int rows = 0, M = 0, R = 0;                    // row capacity (the pitch of the partials); M == 0: no ensemble
+    int64_t chain0 = 0;                            // global index of chain 0 (Philox flat indices)
+    long long step = 0;                            // steps done since the start: its parity picks the even or the odd ladder pairs
+
+    PtLayer &layer(int i) { return i == 0 ? v : (i == 1 ? h1 : h2); }
+    int nrows() const { return M * R; }
+    int64_t row0() const { return chain0 * R; }    // global index of row 0 (Philox flat indices)
+
+    // room for `want` rows of the widths {V, n1, n2} and a ladder of R_; grows only
+    int ensure(int want, int R_, const int widths[3]) {
+        const size_t ncnt = (size_t)2 * std::max(R_ - 1, 1);
+        if (cnt.n < ncnt) BM_TRY(cnt.alloc(ncnt));
+        if (beta.n < (size_t)R_) BM_TRY(beta.alloc(R_));
+        if (want <= rows) return 0;
+        rows = 0;                                  // (set again once every buffer exists: a failure leaves none counted)
+        for (int i = 0; i < 3; ++i) {
+            PtLayer &l = layer(i);
+            l.n = widths[i];
+            if (!l.n) continue;
+            BM_TRY(l.x.alloc(want, l.n)); BM_TRY(l.part.alloc((size_t)nslots(l.n) * want));
+        }
+        BM_TRY(mult.alloc(want)); BM_TRY(idx.alloc(want));
+        rows = want;
+        return 0;
+    }
+};
+
+// the arguments of a *_pt_init that do not depend on the model
+static inline int pt_check_ladder(int32_t n_chains, int32_t n_temps, const float *betas_host, int64_t chain0) {
+    BM_CHECK(n_temps >= 1, "n_temps must be >= 1 (got %d)", (int)n_temps);
+    BM_CHECK(betas_host, "null argument");
+    BM_CHECK(n_chains >= 1 && chain0 >= 0, "bad ensemble (n_chains %d >= 1, chain0 %lld >= 0)", (int)n_chains, (long long)chain0);
+    BM_CHECK((long long)n_chains * n_temps <= (1ll << 24), "n_chains * n_temps = %lld rows exceed 2^24",
+             (long long)n_chains * n_temps);
+    for (int r = 0; r < n_temps; ++r)
+        BM_CHECK(betas_host[r] > 0.f && betas_host[r] <= 1.f && (r == 0 || betas_host[r] > betas_host[r - 1]),
+                 "betas must increase strictly inside (0, 1] (betas[%d] = %g)", r, (double)betas_host[r]);
+    BM_CHECK(betas_host[n_temps - 1] == 1.0f, "the last beta must be 1 (got %g)", (double)betas_host[n_temps - 1]);
+    return 0;
+}
+
+// Start an ensemble of M chains x R replicas of the widths {V, n1, n2} (n2 == 0: no h2) from a checked ladder: v_0 from V0_dev
+// (null: Ber(1/2) under key_v), h2_0 ~ Ber(1/2) under key_h2; vb / b2: the biases the first partials are scored with.
+static inline int pt_begin(PtEnsemble &e, hipStream_t stream, const int widths[3], int M, int R, int64_t chain0,
+                           const float *betas_host, const float *V0_dev, const float *vb, const float *b2, PhiloxKey key_v,
+                           PhiloxKey key_h2) {
+    const int rows = M * R;
+    e.M = 0;                                       // (an ensemble exists once everything below went through)
+    BM_TRY(e.ensure(rows, R, widths));
+    BM_HIP(hipStreamSynchronize(stream));
+    BM_HIP(hipMemcpy(e.beta.p, betas_host, (size_t)R * sizeof(float), hipMemcpyHostToDevice));
+    BM_HIP(hipMemsetAsync(e.cnt.p, 0, (size_t)2 * std::max(R - 1, 1) * sizeof(unsigned long long), stream));
+    const long long nthr = (long long)rows * (nslots(e.v.n) + nslots(e.h2.n));
+    hipLaunchKernelGGL(pt_init_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, e.v.x.p, e.v.x.ld, rows, R, e.v.n,
+                       V0_dev, vb, e.h2.x.p, e.h2.x.ld, e.h2.n, b2, (const float *)e.beta.p, key_v, key_h2,
+                       (unsigned long long)chain0 * (unsigned long long)R, e.v.part.p, e.h2.part.p, e.rows, e.mult.p, e.idx.p);
+    BM_HIP(hipGetLastError());
+    e.M = M; e.R = R; e.chain0 = chain0; e.step = 0;
+    return 0;
+}
+
+// The replica exchange of step t of a call (parity of the global step number e.step + t); nothing to launch at R == 1 or where
+// the parity has no pair.  The partial arrays go to the kernel as v, then h2 (its part_m; absent: no slots), then h1: that is the
+// order of the double additions in the swap energy, so changing it changes accept decisions.
+static inline void pt_launch_swap(PtEnsemble &e, hipStream_t stream, int t, PhiloxKey key) {
+    const int parity = (int)((e.step + t) & 1);
+    const int npair = (e.R - parity) / 2;
+    if (npair <= 0) return;
+    const long long nthr = (long long)e.M * npair;
+    hipLaunchKernelGGL(pt_swap_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, e.M, e.R, parity,
+                       (const float *)e.v.part.p, nslots(e.v.n), (const float *)e.h2.part.p, nslots(e.h2.n),
+                       (const float *)e.h1.part.p, nslots(e.h1.n), e.rows, e.mult.p, e.idx.p, e.cnt.p, key,
+                       (unsigned long long)e.chain0);
+}
+
+// the v.vb and (where there is an h2) h2.b2 partials of every row under the biases of NOW, one launch
+static inline void pt_launch_rescore(PtEnsemble &e, hipStream_t stream, const float *vb, const float *b2) {
+    const PtRescoreJob jv{e.v.x.p, e.v.x.ld, e.v.n, vb, e.v.part.p};
+    const PtRescoreJob jh{e.h2.x.p, e.h2.x.ld, e.h2.n, b2, e.h2.part.p};
+    const long long nthr = (long long)e.nrows() * (nslots(e.v.n) + nslots(e.h2.n));
+    hipLaunchKernelGGL(pt_rescore_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, e.nrows(), e.rows, jv, jh);
+}
+
+// the beta = 1 rows of the chains [0, n_chains) of the layers v, h1, h2 -> dst[i] with pitch ldd[i] (null: not wanted), one
+// launch; none where nothing is wanted
+static inline void pt_launch_gather(PtEnsemble &e, hipStream_t stream, int n_chains, float *const dst[3], const int ldd[3]) {
+    if (!dst[0] && !dst[1] && !dst[2]) return;
+    PtGatherJobs g{};
+    for (int i = 0; i < 3; ++i) {
+        const PtLayer &l = e.layer(i);
+        if (dst[i]) g.j[i] = {l.x.p, l.x.ld, l.n, dst[i], ldd[i]};
+    }
+    hipLaunchKernelGGL(pt_gather_kernel, dim3(n_chains), dim3(256), 0, stream, n_chains, e.R, (const int *)e.idx.p, g);
+}
+
+// the end of a *_pt_read: wait for the stream, then the swap counters [2][R - 1] and the ladder indices [M][R] (either null:
+// skipped)
+static inline int pt_read_host(PtEnsemble &e, hipStream_t stream, int64_t *swaps_host, int32_t *ladder_idx_host) {
+    BM_HIP(hipGetLastError());
+    BM_HIP(hipStreamSynchronize(stream));
+    if (swaps_host && e.R > 1) {
+        static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counter width");
+        BM_HIP(hipMemcpy(swaps_host, e.cnt.p, (size_t)2 * (e.R - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    if (ladder_idx_host) BM_HIP(hipMemcpy(ladder_idx_host, e.idx.p, (size_t)e.nrows() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 }  // namespace bm

@@ -95,16 +95,9 @@ struct bm_rbm {
     DevBuf apart_h, apart_v;           // slot partials (ActArgs::rowacc / rowdot_out): [ceil(H/16)][ais_rows], [ceil(V/16)][ais_rows]
     DevArray<double> alogw;            // [ais_rows] log-weights, accumulated in double in a fixed order
     DevBuf abase, adot, abeta, atable; // a [V], vb - a [V], beta [n_betas], the mixed biases a + beta_k (vb - a) [n_betas][V]
-    // bm_rbm_pt_*: the tempered ensemble of pt_M chains x pt_R replicas, chain-major rows (row c * R + r), allocated on demand for
-    // `pt_rows` rows - max_batch does not bound it; nothing else in the handle reads or writes these
-    int pt_rows = 0, pt_M = 0, pt_R = 0;
-    int64_t pt_chain0 = 0;
-    long long pt_step = 0;             // sweeps done since bm_rbm_pt_init: its parity picks the even or the odd ladder pairs
-    Mat ptv, pth;                      // states [pt_rows][V], [pt_rows][H]
-    DevBuf ptpart_v, ptpart_h;         // slot partials of v.vb [ceil(V/16)][pt_rows] and of h.(vW + hb) [ceil(H/16)][pt_rows]
-    DevBuf pt_mult, pt_beta;           // the temperature of every row [pt_rows] (ActArgs::row_mult), the ladder [pt_R]
-    DevArray<int> pt_idx;              // the ladder index of every row [pt_rows]
-    DevArray<unsigned long long> pt_cnt;   // [2][R - 1]: swap attempts, accepts per ladder pair
+    // bm_rbm_pt_*: the tempered ensemble (bm_pt.h; layers v and h1), allocated on demand - max_batch does not bound it; nothing
+    // else in the handle reads or writes it
+    PtEnsemble pt;
     int fer_rows = 0;
     DevBuf fer_part, fer_out;          // bm_rbm_free_energy_rows: slot partials [ceil(H/16)][fer_rows] of sum softplus, F [fer_rows]
     // fast-binary mode (bm_bf3.h, bm_rbm_set_fast_binary): bf16 planes of W ([V][H]: the prop-down operand) and of
@@ -607,86 +600,47 @@ static void ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &k
 
 // ---- parallel tempering (bm355.h: bm_rbm_pt_init / _sweep / _read)
 
-// (pt_vb_slot, pt_rescore_kernel, pt_swap_kernel and pt_gather_kernel: bm_pt.h, shared with bm_dbm_pt_*)
+// (the ensemble, its start, the replica exchange, the rescore and the gather: bm_pt.h, shared with bm_dbm_pt_*)
 
-// Start of the ensemble: one thread per row and 16-column slot.  v_0 ~ Ber(1/2) at its flat index of the global row (V0 null) or
-// the chain's row of V0 [M][V] for all its R replicas; the slot's partial of v_0.vb (pt_vb_slot); row c * R + r starts at ladder
-// index r, temperature beta[r]
-__global__ __launch_bounds__(256) void pt_init_kernel(float *v, int ld, int rows, int R, int V, const float *V0, const float *vb,
-                                                      const float *beta, PhiloxKey key, unsigned long long row0, float *part, int ld_part,
-                                                      float *row_mult, int *idx) {
-    const int ns = (V + 15) / 16;
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long long)rows * ns) return;
-    const int row = (int)(e / ns), slot = (int)(e % ns);
-    part[(size_t)slot * ld_part + row] = pt_vb_slot(slot, V, vb, [&](int c) {
-        const float x = V0 ? V0[(size_t)(row / R) * V + c]
-                           : (philox_uniform_at(key, (row0 + row) * (unsigned long long)V + c) < 0.5f ? 1.f : 0.f);
-        v[(size_t)row * ld + c] = x;
-        return x;
-    });
-    if (slot == 0) { row_mult[row] = beta[row % R]; idx[row] = row % R; }
-}
-
-static int ensure_pt_rows(bm_rbm *h, int rows, int R) {
-    if (h->pt_cnt.n < (size_t)2 * std::max(R - 1, 1)) BM_TRY(h->pt_cnt.alloc((size_t)2 * std::max(R - 1, 1)));
-    if (h->pt_beta.n < (size_t)R) BM_TRY(h->pt_beta.alloc(R));
-    if (rows <= h->pt_rows) return 0;
-    h->pt_rows = 0;                                // (set again once every buffer exists: a failure leaves none counted)
-    BM_TRY(h->ptv.alloc(rows, h->V)); BM_TRY(h->pth.alloc(rows, h->H));
-    BM_TRY(h->ptpart_v.alloc((size_t)nslots(h->V) * rows)); BM_TRY(h->ptpart_h.alloc((size_t)nslots(h->H) * rows));
-    BM_TRY(h->pt_mult.alloc(rows)); BM_TRY(h->pt_idx.alloc(rows));
-    h->pt_rows = rows;
-    return 0;
-}
-
-// one row-tempered pass of the ensemble (the RT flavour of act_kernel): up = h ~ Ber(sigmoid(beta_row (vW + hb))) from ptv into
-// pth, leaving the slot partials of h.(vW + hb); down = v ~ Ber(sigmoid(beta_row (hW^T + vb))) from pth into ptv, leaving those
+// one row-tempered pass of the ensemble (the RT flavour of act_kernel): up = h ~ Ber(sigmoid(beta_row (vW + hb))) from pt.v into
+// pt.h1, leaving the slot partials of h.(vW + hb); down = v ~ Ber(sigmoid(beta_row (hW^T + vb))) from pt.h1 into pt.v, leaving those
 // of v.vb
 // sel_rows > 0 (down only): the beta = 1 row of every chain c < sel_rows is also left in vs[c] (ActArgs::sel_out)
 static void pt_pass(bm_rbm *h, bool up, const PhiloxKey &key, int sel_rows = 0) {
-    const int rows = h->pt_M * h->pt_R;
+    PtEnsemble &e = h->pt;
+    const int rows = e.nrows();
     ActArgs a;
     memset(&a, 0, sizeof(a));
     if (up) {
         up_weights(h, a);
-        a.Q1 = make_operand(h->ptv.p, h->ptv.ld, rows);
+        a.Q1 = make_operand(e.v.x.p, e.v.x.ld, rows);
         a.K1 = h->V; a.I = h->H; a.bias = h->hb.p;
-        a.states = h->pth.p; a.ldo = h->pth.ld;
-        a.rowen_out = h->ptpart_h.p;
+        a.states = e.h1.x.p; a.ldo = e.h1.x.ld;
+        a.rowen_out = e.h1.part.p;
     } else {
         a.P1 = make_operand(h->W.p, h->W.ld, h->V); a.p_xm = 1;
-        a.Q1 = make_operand(h->pth.p, h->pth.ld, rows);
+        a.Q1 = make_operand(e.h1.x.p, e.h1.x.ld, rows);
         a.K1 = h->H; a.I = h->V; a.bias = h->vb.p;
-        a.states = h->ptv.p; a.ldo = h->ptv.ld;
-        a.rowdot_out = h->ptpart_v.p; a.dot_vec = h->vb.p;
+        a.states = e.v.x.p; a.ldo = e.v.x.ld;
+        a.rowdot_out = e.v.part.p; a.dot_vec = h->vb.p;
     }
     a.J = rows;
     a.mult = 1.0f; a.bmult = 1.0f;                // (not read: row_mult replaces them)
-    a.row_mult = h->pt_mult.p;
-    a.ld_part = h->pt_rows;
+    a.row_mult = e.mult.p;
+    a.ld_part = e.rows;
     a.kind = BM_UNIT_BERNOULLI;
     a.sample = 1;
     a.key = key;
-    a.row0 = h->pt_chain0 * h->pt_R;
-    if (sel_rows > 0 && !up) { a.sel_out = h->vs.p; a.sel_ld = h->vs.ld; a.sel_R = h->pt_R; a.sel_rows = sel_rows; }
+    a.row0 = e.row0();
+    if (sel_rows > 0 && !up) { a.sel_out = h->vs.p; a.sel_ld = h->vs.ld; a.sel_R = e.R; a.sel_rows = sel_rows; }
     launch_act(a, h->stream);
 }
 
 // step t of a tempered call: the RT prop-up, the swap of the parity of the global step number, the RT prop-down (which hands the
 // beta = 1 rows of the chains [0, sel_rows) over to vs, if asked)
 static void pt_step(bm_rbm *h, int t, int sel_rows = 0) {
-    const int M = h->pt_M, R = h->pt_R;
     pt_pass(h, true, make_key(h, SITE_H, t));
-    const int parity = (int)((h->pt_step + t) & 1);
-    const int npair = (R - parity) / 2;
-    if (npair > 0) {
-        const long long nthr = (long long)M * npair;
-        hipLaunchKernelGGL(pt_swap_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, M, R, parity,
-                           (const float *)h->ptpart_v.p, nslots(h->V), (const float *)nullptr, 0, (const float *)h->ptpart_h.p,
-                           nslots(h->H), h->pt_rows,
-                           h->pt_mult.p, h->pt_idx.p, h->pt_cnt.p, make_key(h, SITE_PT_SWAP, t), (unsigned long long)h->pt_chain0);
-    }
+    pt_launch_swap(h->pt, h->stream, t, make_key(h, SITE_PT_SWAP, t));
     pt_pass(h, false, make_key(h, SITE_V, t), sel_rows);
 }
 
@@ -1368,37 +1322,20 @@ int bm_rbm_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev
 int bm_rbm_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0) {
     BM_CHECK(h, "null argument");
     BM_TRY(check_single_joint(h, "bm_rbm_pt_init"));
-    BM_CHECK(n_temps >= 1, "n_temps must be >= 1 (got %d)", (int)n_temps);
-    BM_CHECK(betas_host, "null argument");
-    BM_CHECK(n_chains >= 1 && chain0 >= 0, "bad ensemble (n_chains %d >= 1, chain0 %lld >= 0)", (int)n_chains, (long long)chain0);
-    BM_CHECK((long long)n_chains * n_temps <= (1ll << 24), "n_chains * n_temps = %lld rows exceed 2^24",
-             (long long)n_chains * n_temps);
-    for (int r = 0; r < n_temps; ++r)
-        BM_CHECK(betas_host[r] > 0.f && betas_host[r] <= 1.f && (r == 0 || betas_host[r] > betas_host[r - 1]),
-                 "betas must increase strictly inside (0, 1] (betas[%d] = %g)", r, (double)betas_host[r]);
-    BM_CHECK(betas_host[n_temps - 1] == 1.0f, "the last beta must be 1 (got %g)", (double)betas_host[n_temps - 1]);
-    const int M = n_chains, R = n_temps, rows = M * R;
-    h->pt_M = 0;                                   // (an ensemble exists once everything below went through)
-    BM_TRY(ensure_pt_rows(h, rows, R));
-    BM_HIP(hipStreamSynchronize(h->stream));
-    BM_HIP(hipMemcpy(h->pt_beta.p, betas_host, (size_t)R * sizeof(float), hipMemcpyHostToDevice));
-    BM_HIP(hipMemsetAsync(h->pt_cnt.p, 0, (size_t)2 * std::max(R - 1, 1) * sizeof(unsigned long long), h->stream));
-    const long long nthr = (long long)rows * nslots(h->V);
-    hipLaunchKernelGGL(pt_init_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, h->ptv.p, h->ptv.ld, rows, R, h->V,
-                       V0_dev, (const float *)h->vb.p, (const float *)h->pt_beta.p, make_key(h, SITE_PT_V0, 0),
-                       (unsigned long long)chain0 * (unsigned long long)R, h->ptpart_v.p, h->pt_rows, h->pt_mult.p, h->pt_idx.p);
-    BM_HIP(hipGetLastError());
-    h->pt_M = M; h->pt_R = R; h->pt_chain0 = chain0; h->pt_step = 0;
+    BM_TRY(pt_check_ladder(n_chains, n_temps, betas_host, chain0));
+    const int widths[3] = {h->V, h->H, 0};
+    const PhiloxKey key = make_key(h, SITE_PT_V0, 0);
+    BM_TRY(pt_begin(h->pt, h->stream, widths, n_chains, n_temps, chain0, betas_host, V0_dev, h->vb.p, nullptr, key, key));
     return 0;
 }
 
 int bm_rbm_pt_sweep(bm_rbm *h, int32_t n_steps) {
     BM_CHECK(h, "null argument");
-    BM_CHECK(h->pt_M > 0, "bm_rbm_pt_sweep: no ensemble (call bm_rbm_pt_init first)");
+    BM_CHECK(h->pt.M > 0, "bm_rbm_pt_sweep: no ensemble (call bm_rbm_pt_init first)");
     BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
     ensure_wt(h);
     for (int t = 0; t < n_steps; ++t) pt_step(h, t);
-    h->pt_step += n_steps;
+    h->pt.step += n_steps;
     h->call++;
     BM_HIP(hipGetLastError());
     return 0;
@@ -1406,39 +1343,27 @@ int bm_rbm_pt_sweep(bm_rbm *h, int32_t n_steps) {
 
 int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
     BM_CHECK(h, "null argument");
-    BM_CHECK(h->pt_M > 0, "bm_rbm_pt_read: no ensemble (call bm_rbm_pt_init first)");
-    const int M = h->pt_M, R = h->pt_R;
-    if (V_dev) {
-        const PtGatherJobs g{{{h->ptv.p, h->ptv.ld, h->V, V_dev, h->V}, {h->pth.p, h->pth.ld, h->H, H_dev, h->H}, {}}};
-        hipLaunchKernelGGL(pt_gather_kernel, dim3(M), dim3(256), 0, h->stream, M, R, (const int *)h->pt_idx.p, g);
-    }
-    else BM_CHECK(!H_dev, "bm_rbm_pt_read: H_dev without V_dev");
-    BM_HIP(hipGetLastError());
-    BM_HIP(hipStreamSynchronize(h->stream));
-    if (swaps_host && R > 1) {
-        static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counter width");
-        BM_HIP(hipMemcpy(swaps_host, h->pt_cnt.p, (size_t)2 * (R - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    }
-    if (ladder_idx_host) BM_HIP(hipMemcpy(ladder_idx_host, h->pt_idx.p, (size_t)M * R * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return 0;
+    BM_CHECK(h->pt.M > 0, "bm_rbm_pt_read: no ensemble (call bm_rbm_pt_init first)");
+    BM_CHECK(V_dev || !H_dev, "bm_rbm_pt_read: H_dev without V_dev");
+    float *const dst[3] = {V_dev, H_dev, nullptr};
+    const int ldd[3] = {h->V, h->H, 0};
+    pt_launch_gather(h->pt, h->stream, h->pt.M, dst, ldd);
+    return pt_read_host(h->pt, h->stream, swaps_host, ladder_idx_host);
 }
 
 // One update whose negative phase is the tempered ensemble (bm355.h).  No host synchronisation.
 int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
     BM_CHECK(h && X_dev, "null argument");
     BM_TRY(check_dw(h, "bm_rbm_train_step_pt"));
-    BM_CHECK(h->pt_M > 0, "bm_rbm_train_step_pt: no ensemble (call bm_rbm_pt_init first)");
+    BM_CHECK(h->pt.M > 0, "bm_rbm_train_step_pt: no ensemble (call bm_rbm_pt_init first)");
     BM_CHECK(h->cfg.dropout < 0.f, "bm_rbm_train_step_pt: the tempered family has no dropout (this handle's is %g)", (double)h->cfg.dropout);
-    const int Bmax = std::min(h->maxB, h->pt_M);
-    BM_CHECK(B >= 1 && B <= Bmax, "bm_rbm_train_step_pt: batch %d outside [1, min(max_batch=%d, n_chains=%d)]", (int)B, h->maxB, h->pt_M);
+    const int Bmax = std::min(h->maxB, h->pt.M);
+    BM_CHECK(B >= 1 && B <= Bmax, "bm_rbm_train_step_pt: batch %d outside [1, min(max_batch=%d, n_chains=%d)]", (int)B, h->maxB, h->pt.M);
     BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
     static const bool sel_in_pass = !dbg("pt_sel") || atoi(dbg("pt_sel")) != 0;     // BM355_DEBUG=pt_sel=0: a gather launch instead
-    const int rows = h->pt_M * h->pt_R;
     ensure_wt(h);
     // 1. the v.vb partials of the swap energy under the vb of NOW (the previous update changed it)
-    const long long nthr = (long long)rows * nslots(h->V);
-    const PtRescoreJob rescore{h->ptv.p, h->ptv.ld, h->V, h->vb.p, h->ptpart_v.p}, none{};
-    hipLaunchKernelGGL(pt_rescore_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, rows, h->pt_rows, rescore, none);
+    pt_launch_rescore(h->pt, h->stream, h->vb.p, nullptr);
     // 2. positive phase: the h0 means alone
     h->Xin = X_dev; h->Xin_ld = h->V;
     h->fe_in_chain = false;
@@ -1446,15 +1371,16 @@ int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, flo
     // 3. + 4. the tempered steps; the last prop-down leaves the beta = 1 rows of the chains [0, B) in vs
     for (int t = 0; t < k; ++t) pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
     if (!sel_in_pass) {
-        const PtGatherJobs g{{{h->ptv.p, h->ptv.ld, h->V, h->vs.p, h->vs.ld}, {}, {}}};
-        hipLaunchKernelGGL(pt_gather_kernel, dim3(B), dim3(256), 0, h->stream, (int)B, h->pt_R, (const int *)h->pt_idx.p, g);
+        float *const dst[3] = {h->vs.p, nullptr, nullptr};
+        const int ldd[3] = {h->vs.ld, 0, 0};
+        pt_launch_gather(h->pt, h->stream, B, dst, ldd);
     }
     // 5. negative means: only -h is consumed (run_chain's neg_only form)
     launch_up(h, h->vs.p, h->vs.ld, B, nullptr, nullptr, h->hm.ld, 0, SITE_H, 0, h->hneg.p);
     h->hm_is_neg = true;
     // 6. + 7.
     launch_update_fused(h, B, lr, mom);
-    h->pt_step += k;
+    h->pt.step += k;
     h->call++;
     BM_HIP(hipGetLastError());
     return 0;

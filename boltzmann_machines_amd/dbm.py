@@ -19,6 +19,7 @@ from . import _ffi
 from .base import EngineModel, run_on_engine
 from .engine import DbmEngine, DbmEngine64
 from .rbm import GaussianRBM, clampable_only
+from .tempering import TemperedNegativePhase, resolve_ladder, run_tempered_sampler
 from .utils import (epoch_iter, make_list_from, write_during_training,
                     log_sum_exp, log_mean_exp, log_diff_exp, log_std_exp)
 from .utils import philox
@@ -32,7 +33,7 @@ def as_device(X, dtype=np.float32):
     return X if isinstance(X, _ffi.DeviceArray) else _ffi.DeviceArray.from_numpy(np.asarray(X), dtype)
 
 
-class DBM(EngineModel):
+class DBM(TemperedNegativePhase, EngineModel):
     def __init__(self, rbms=None,
                  n_particles=100, v_particle_init=None, h_particles_init=None,
                  n_gibbs_steps=5, max_mf_updates=10, mf_tol=1e-7,
@@ -330,13 +331,8 @@ class DBM(EngineModel):
         """the update of an epoch with the tempered negative phase: bm_dbm_train_step_pt, its ensemble built first where this
         fit() call has none yet or the ladder / n_chains changed (random start under the call's seed: no host seed is drawn)"""
         self._check_tempered_fit()
-        eng = self._engine
-        betas, n_chains = self._neg_phase
-        if getattr(self, '_pt_fresh', True) or getattr(eng, '_pt_train_key', None) != self._neg_phase:
-            eng.pt_init(n_chains, betas)
-            eng._pt_train_key = self._neg_phase
-            self._pt_fresh = False
-        return eng.train_step_pt
+        self._ensure_train_ensemble(self._engine)
+        return self._engine.train_step_pt
 
     def _run_val_metrics(self, X_val, Xvd):
         # one fetch of [msre, n_mf_updates] per batch (reference dbm.py:810-816).  Both tensors sit under the
@@ -554,28 +550,8 @@ class DBM(EngineModel):
         n_samples = int(n_samples)
         if n_samples < 1 or int(n_gibbs_steps) < 1:
             raise ValueError('`n_samples` and `n_gibbs_steps` must be >= 1 (got {0}, {1})'.format(n_samples, n_gibbs_steps))
-        if betas is None:
-            if int(n_temperatures) < 1:
-                raise ValueError('`n_temperatures` must be >= 1 (got {0})'.format(n_temperatures))
-            betas = np.linspace(0., 1., int(n_temperatures) + 1)[1:]
-        betas = np.asarray(betas, dtype=np.float32).ravel()
-        if len(betas) < 1 or betas[-1] != 1. or betas[0] <= 0. or np.any(np.diff(betas) <= 0.):
-            raise ValueError('`betas` must increase strictly inside (0, 1] and end at 1 (got {0})'.format(betas))
-        V0d = None
-        if V_init is not None:
-            V_init = np.ascontiguousarray(V_init, dtype=np.float32)
-            if V_init.shape != (n_samples, self.n_visible_):
-                raise ValueError('`V_init` has invalid shape {0}: expected [{1}, {2}]'.format(V_init.shape, n_samples, self.n_visible_))
-            V0d = as_device(V_init, np.float32)
-        eng = self._engine
-        eng.pt_init(n_samples, betas, V0d)          # (replaces the ensemble of a tempered negative phase: _pt_train_key)
-        eng.pt_sweep(int(n_gibbs_steps))
-        Vd = _ffi.DeviceArray((n_samples, self.n_visible_), np.float32)
-        swaps, _ = eng.pt_read(Vd)
-        V = Vd.numpy()
-        if return_stats:
-            return V, swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
-        return V
+        return run_tempered_sampler(self._engine, n_samples, int(n_gibbs_steps), resolve_ladder(n_temperatures, betas), V_init,
+                                    self.n_visible_, return_stats)
 
     # ---- tempered negative phase (no counterpart in the reference) ---------------
     def _check_tempered_fit(self, what='fit'):
@@ -586,6 +562,9 @@ class DBM(EngineModel):
                                       'the ensemble are not sharded over ranks)' % (self.__class__.__name__, what))
         if self._neg_phase is not None and self._neg_phase[1] < self.n_particles:
             raise ValueError('`n_chains` must be >= n_particles (got {0} < {1})'.format(self._neg_phase[1], self.n_particles))
+
+    _PT_MIN_CHAINS = 'n_particles'
+    _check_tempered_setting = _check_tempered_fit
 
     def set_negative_phase(self, kind='cd', n_temperatures=10, betas=None, n_chains=None):
         """Where the negative particles of `fit` come from.
@@ -613,33 +592,7 @@ class DBM(EngineModel):
         Stacks of one or two Bernoulli hidden layers over Bernoulli visible units in float32 only: Gaussian visible units,
         Multinomial layers, three or more hidden layers, float64, set_mean_field_arithmetic('reference') and data-parallel
         jobs raise NotImplementedError.  Returns self."""
-        if kind == 'cd':
-            self._neg_phase = None
-            return self
-        if kind != 'tempered':
-            raise ValueError("`kind` must be 'cd' or 'tempered' (got {0!r})".format(kind))
-        self._check_tempered_fit('set_negative_phase')
-        if betas is None:
-            if int(n_temperatures) < 1:
-                raise ValueError('`n_temperatures` must be >= 1 (got {0})'.format(n_temperatures))
-            betas = np.linspace(0., 1., int(n_temperatures) + 1)[1:]
-        betas = np.asarray(betas, dtype=np.float32).ravel()
-        if len(betas) < 1 or betas[-1] != 1. or betas[0] <= 0. or np.any(np.diff(betas) <= 0.):
-            raise ValueError('`betas` must increase strictly inside (0, 1] and end at 1 (got {0})'.format(betas))
-        n_chains = self.n_particles if n_chains is None else int(n_chains)
-        if n_chains < self.n_particles:
-            raise ValueError('`n_chains` must be >= n_particles (got {0} < {1})'.format(n_chains, self.n_particles))
-        self._neg_phase = (tuple(float(b) for b in betas), n_chains)
-        return self
-
-    def tempering_stats(self):
-        """Acceptance rate (accepts / attempts) of every neighbouring pair of temperatures, [n_temperatures - 1], since the
-        ensemble of the tempered negative phase was built.  Waits for the device; copies no states."""
-        eng = self._engine
-        if not isinstance(eng, DbmEngine) or getattr(eng, '_pt_train_key', None) is None:
-            raise RuntimeError('`tempering_stats`: no tempered ensemble (call set_negative_phase(\'tempered\') and fit first)')
-        swaps, _ = eng.pt_read()
-        return swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
+        return self._set_negative_phase(kind, n_temperatures, betas, n_chains)
 
     def set_ais_accumulation(self, dtype='float64'):
         """How `log_Z` accumulates the AIS log-weights.  'float64' (default): per chain the difference of consecutive

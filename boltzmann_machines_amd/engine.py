@@ -22,8 +22,48 @@ def as_device(X):
     return DeviceArray.from_numpy(np.asarray(X), np.float32)
 
 
-class RbmEngine(object):
+class _PtCalls(object):
+    """Parallel tempering (bm355.h: bm_rbm_pt_* / bm_dbm_pt_*): the three calls on the handle's tempered ensemble, the same for
+    both engines but for the symbol prefix and the hidden state matrices pt_read hands out."""
+    _pt_prefix = None                             # 'bm_rbm' / 'bm_dbm'
+    _pt_n_hidden = 0                              # hidden state matrices pt_read accepts: 1 (Hd) / 2 (H1d, H2d)
+
+    def _pt_call(self, name):
+        return getattr(self.lib, '%s_pt_%s' % (self._pt_prefix, name))
+
+    def pt_init(self, n_chains, betas, V0_d=None, chain0=0):
+        """build the tempered ensemble of n_chains x len(betas) replicas in the handle; V0_d [n_chains, V] (DeviceArray): every
+        chain's replicas start there, None: v_0 ~ Ber(1/2); a DBM's h2_0 ~ Ber(1/2) either way"""
+        b = np.ascontiguousarray(betas, dtype=np.float32).ravel()
+        check(self._pt_call('init')(self._h, int(n_chains), len(b), b.ctypes.data_as(C.c_void_p),
+                                    V0_d.ptr if V0_d is not None else None, int(chain0)))
+        self._pt_shape = (int(n_chains), len(b))
+        self._pt_train_key = None                 # (whoever builds the ensemble for training records its ladder: tempering.py)
+
+    def pt_sweep(self, n_steps):
+        """n_steps on the whole ensemble, each the tempered passes of one Gibbs sweep with the replica exchange after the first
+        (RBM: prop-up, exchange, prop-down; DBM: h1, exchange, h2, v)"""
+        check(self._pt_call('sweep')(self._h, int(n_steps)))
+
+    def pt_read(self, Vd=None, *Hd):
+        """beta = 1 rows -> Vd [n_chains, V] and the hidden states (RBM: Hd [n_chains, H]; DBM: H1d [n_chains, n_1], H2d
+        [n_chains, n_2]), all DeviceArrays, all optional; returns (swaps [2, R-1] int64: attempts and accepts per ladder pair,
+        ladder_idx [n_chains, R] int32: the ladder index of every row)"""
+        if len(Hd) > self._pt_n_hidden:
+            raise TypeError('pt_read() takes at most %d hidden state matrices (%d given)' % (self._pt_n_hidden, len(Hd)))
+        mats = (Vd,) + Hd + (None,) * (self._pt_n_hidden - len(Hd))
+        M, R = getattr(self, '_pt_shape', (0, 1))
+        swaps = np.zeros((2, max(R - 1, 0)), dtype=np.int64)
+        idx = np.zeros((M, R), dtype=np.int32)
+        check(self._pt_call('read')(self._h, *[d.ptr if d is not None else None for d in mats],
+                                    swaps.ctypes.data_as(C.c_void_p) if swaps.size else None,
+                                    idx.ctypes.data_as(C.c_void_p) if idx.size else None))
+        return swaps, idx
+
+
+class RbmEngine(_PtCalls):
     dtype = np.float32
+    _pt_prefix, _pt_n_hidden = 'bm_rbm', 1
 
     def __init__(self, n_visible, n_hidden, v_unit=_ffi.UNIT_BERNOULLI, sample_v_states=False,
                  sample_h_states=True, dbm_first=False, dbm_last=False, max_batch=10, l2=1e-4,
@@ -190,31 +230,6 @@ class RbmEngine(object):
                                             Vmean_d.offset_ptr(ov) if Vmean_d is not None else None, B, n_steps,
                                             clamp_val_d.offset_ptr(ov), clamp_mask_d.offset_ptr(ov)))
 
-    # parallel tempering (bm355.h: bm_rbm_pt_init / _sweep / _read)
-    def pt_init(self, n_chains, betas, V0_d=None, chain0=0):
-        """build the tempered ensemble of n_chains x len(betas) replicas in the handle; V0_d [n_chains, V] (DeviceArray): every
-        chain's replicas start there, None: v_0 ~ Ber(1/2)"""
-        b = np.ascontiguousarray(betas, dtype=np.float32).ravel()
-        check(self.lib.bm_rbm_pt_init(self._h, int(n_chains), len(b), b.ctypes.data_as(C.c_void_p),
-                                      V0_d.ptr if V0_d is not None else None, int(chain0)))
-        self._pt_shape = (int(n_chains), len(b))
-        self._pt_train_key = None                 # (whoever builds the ensemble for training records its ladder: rbm.py)
-
-    def pt_sweep(self, n_steps):
-        """n_steps of (tempered prop-up, replica exchange, tempered prop-down) on the whole ensemble"""
-        check(self.lib.bm_rbm_pt_sweep(self._h, int(n_steps)))
-
-    def pt_read(self, Vd=None, Hd=None):
-        """beta = 1 rows -> Vd [n_chains, V] / Hd [n_chains, H] (DeviceArrays, optional); returns (swaps [2, R-1] int64:
-        attempts and accepts per ladder pair, ladder_idx [n_chains, R] int32: the ladder index of every row)"""
-        M, R = getattr(self, '_pt_shape', (0, 1))
-        swaps = np.zeros((2, max(R - 1, 0)), dtype=np.int64)
-        idx = np.zeros((M, R), dtype=np.int32)
-        check(self.lib.bm_rbm_pt_read(self._h, Vd.ptr if Vd is not None else None, Hd.ptr if Hd is not None else None,
-                                      swaps.ctypes.data_as(C.c_void_p) if swaps.size else None,
-                                      idx.ctypes.data_as(C.c_void_p) if idx.size else None))
-        return swaps, idx
-
     # tempered negative phase (bm355.h: bm_rbm_train_step_pt / _train_epoch_pt); the ensemble of pt_init supplies the particles
     def train_step_pt(self, Xd, B, lr, momentum, k, row=0):
         check(self.lib.bm_rbm_train_step_pt(self._h, Xd.offset_ptr(row * self.V), B, lr, momentum, k))
@@ -337,10 +352,11 @@ class RbmEngine64(object):
         return float(out.value)
 
 
-class DbmEngine(object):
+class DbmEngine(_PtCalls):
     """One bm_dbm handle: the variables, variational parameters and fantasy particles
     of a DBM in HBM + the fetch sites of boltzmann_machines/dbm.py (`session.run` at
     :798,:805,:813,:869,:882,:893,:930,:954)."""
+    _pt_prefix, _pt_n_hidden = 'bm_dbm', 2
 
     def __init__(self, n_visible, n_hiddens, v_unit=_ffi.UNIT_BERNOULLI, sample_v_states=True,
                  sample_h_states=None, n_particles=100, batch_size=100, max_mf_updates=10, mf_tol=1e-7,
@@ -515,32 +531,6 @@ class DbmEngine(object):
         """sample_v with the visible units of the particles held at clamp_val_d where clamp_mask_d is non-zero (both dense
         [n_particles, V]; bm_dbm_sample_v_clamped)"""
         check(self.lib.bm_dbm_sample_v_clamped(self._h, k, clamp_val_d.ptr, clamp_mask_d.ptr, Vd.ptr if Vd is not None else None))
-
-    # parallel tempering (bm355.h: bm_dbm_pt_init / _sweep / _read)
-    def pt_init(self, n_chains, betas, V0_d=None, chain0=0):
-        """build the tempered ensemble of n_chains x len(betas) replicas in the handle; V0_d [n_chains, V] (DeviceArray): every
-        chain's replicas start there, None: v_0 ~ Ber(1/2); h2_0 ~ Ber(1/2) either way"""
-        b = np.ascontiguousarray(betas, dtype=np.float32).ravel()
-        check(self.lib.bm_dbm_pt_init(self._h, int(n_chains), len(b), b.ctypes.data_as(C.c_void_p),
-                                      V0_d.ptr if V0_d is not None else None, int(chain0)))
-        self._pt_shape = (int(n_chains), len(b))
-        self._pt_train_key = None                 # (whoever builds the ensemble for training records its ladder: dbm.py)
-
-    def pt_sweep(self, n_steps):
-        """n_steps of (tempered h1 pass, replica exchange, tempered h2 pass, tempered v pass) on the whole ensemble"""
-        check(self.lib.bm_dbm_pt_sweep(self._h, int(n_steps)))
-
-    def pt_read(self, Vd=None, H1d=None, H2d=None):
-        """beta = 1 rows -> Vd [n_chains, V] / H1d [n_chains, n_1] / H2d [n_chains, n_2] (DeviceArrays, optional); returns
-        (swaps [2, R-1] int64: attempts and accepts per ladder pair, ladder_idx [n_chains, R] int32)"""
-        M, R = getattr(self, '_pt_shape', (0, 1))
-        swaps = np.zeros((2, max(R - 1, 0)), dtype=np.int64)
-        idx = np.zeros((M, R), dtype=np.int32)
-        ptr = lambda d: d.ptr if d is not None else None
-        check(self.lib.bm_dbm_pt_read(self._h, ptr(Vd), ptr(H1d), ptr(H2d),
-                                      swaps.ctypes.data_as(C.c_void_p) if swaps.size else None,
-                                      idx.ctypes.data_as(C.c_void_p) if idx.size else None))
-        return swaps, idx
 
     # tempered negative phase (bm355.h: bm_dbm_train_step_pt); the ensemble of pt_init supplies the particles
     def train_step_pt(self, Xd, lr, momentum, k, row=0, want_msre=False):

@@ -19,6 +19,7 @@ import numpy as np
 from . import _ffi
 from .base import EngineModel, is_attribute_name, run_on_engine
 from .engine import RbmEngine, RbmEngine64
+from .tempering import TemperedNegativePhase, resolve_ladder, run_tempered_sampler
 from .utils import epoch_iter, make_list_from, write_during_training
 from .utils import log_sum_exp, log_mean_exp, log_diff_exp, log_std_exp
 from .utils import philox
@@ -55,7 +56,7 @@ def clampable_only(f):
     return checked
 
 
-class BaseRBM(EngineModel):
+class BaseRBM(TemperedNegativePhase, EngineModel):
     """Restricted Boltzmann machine trained with CD-k (reference base_rbm.py:14-94)."""
 
     _V_UNIT = _ffi.UNIT_BERNOULLI
@@ -377,7 +378,9 @@ class BaseRBM(EngineModel):
         return (lambda: out) if defer else out
 
     # ---- tempered negative phase (no counterpart in the reference) --------------
-    def _check_tempered(self, what='set_negative_phase'):
+    _PT_MIN_CHAINS = 'batch_size'
+
+    def _check_tempered_setting(self, what):
         self._check_single_joint(what)
         name = '%s.%s' % (self.__class__.__name__, what)
         if self.dropout is not None:
@@ -407,37 +410,11 @@ class BaseRBM(EngineModel):
         A train-metrics iteration reports the metrics of the CD reconstruction (as `kind='cd'` would) and then makes its
         tempered update.  BernoulliRBM in float32 only: GaussianRBM, MultinomialRBM, float64, `dbm_first` / `dbm_last`,
         dropout and BM355_DATA_PARALLEL jobs raise NotImplementedError.  Returns self."""
-        if kind == 'cd':
-            self._neg_phase = None
-            return self
-        if kind != 'tempered':
-            raise ValueError("`kind` must be 'cd' or 'tempered' (got {0!r})".format(kind))
-        self._check_tempered()
-        if betas is None:
-            if int(n_temperatures) < 1:
-                raise ValueError('`n_temperatures` must be >= 1 (got {0})'.format(n_temperatures))
-            betas = np.linspace(0., 1., int(n_temperatures) + 1)[1:]
-        betas = np.asarray(betas, dtype=np.float32).ravel()
-        if len(betas) < 1 or betas[-1] != 1. or betas[0] <= 0. or np.any(np.diff(betas) <= 0.):
-            raise ValueError('`betas` must increase strictly inside (0, 1] and end at 1 (got {0})'.format(betas))
-        n_chains = self.batch_size if n_chains is None else int(n_chains)
-        if n_chains < self.batch_size:
-            raise ValueError('`n_chains` must be >= batch_size (got {0} < {1})'.format(n_chains, self.batch_size))
-        self._neg_phase = (tuple(float(b) for b in betas), n_chains)
-        return self
-
-    def tempering_stats(self):
-        """Acceptance rate (accepts / attempts) of every neighbouring pair of temperatures, [n_temperatures - 1], since the
-        ensemble of the tempered negative phase was built.  Waits for the device; copies no states."""
-        eng = self._engine
-        if not isinstance(eng, RbmEngine) or getattr(eng, '_pt_train_key', None) is None:
-            raise RuntimeError('`tempering_stats`: no tempered ensemble (call set_negative_phase(\'tempered\') and fit first)')
-        swaps, _ = eng.pt_read()
-        return swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
+        return self._set_negative_phase(kind, n_temperatures, betas, n_chains)
 
     def _check_tempered_fit(self):
         """what may have changed since set_negative_phase (set_params): refused before an epoch starts"""
-        self._check_tempered('fit')
+        self._check_tempered_setting('fit')
         if getattr(self, '_dp', None) is not None:
             raise NotImplementedError('%s.fit: a tempered negative phase is not combined with data parallelism' % self.__class__.__name__)
         if self._neg_phase[1] < self.batch_size:
@@ -447,11 +424,7 @@ class BaseRBM(EngineModel):
         """one epoch with the tempered negative phase: runs of batches go to bm_rbm_train_epoch_pt; a metrics iteration
         fetches synchronously (bm_rbm_metrics, the CD reconstruction), then updates (not optimised)"""
         self._check_tempered_fit()
-        betas, n_chains = self._neg_phase
-        if getattr(self, '_pt_fresh', True) or getattr(eng, '_pt_train_key', None) != self._neg_phase:
-            eng.pt_init(n_chains, betas)
-            eng._pt_train_key = self._neg_phase
-            self._pt_fresh = False
+        self._ensure_train_ensemble(eng)
         run_start = None
         for start in range(0, N, self.batch_size):
             B = min(self.batch_size, N - start)
@@ -708,27 +681,8 @@ class BaseRBM(EngineModel):
         n_samples = int(n_samples)
         if n_samples < 1 or int(n_gibbs_steps) < 1:
             raise ValueError('`n_samples` and `n_gibbs_steps` must be >= 1 (got {0}, {1})'.format(n_samples, n_gibbs_steps))
-        if betas is None:
-            if int(n_temperatures) < 1:
-                raise ValueError('`n_temperatures` must be >= 1 (got {0})'.format(n_temperatures))
-            betas = np.linspace(0., 1., int(n_temperatures) + 1)[1:]
-        betas = np.asarray(betas, dtype=np.float32).ravel()
-        if len(betas) < 1 or betas[-1] != 1. or betas[0] <= 0. or np.any(np.diff(betas) <= 0.):
-            raise ValueError('`betas` must increase strictly inside (0, 1] and end at 1 (got {0})'.format(betas))
-        V0d = None
-        if V_init is not None:
-            V_init = np.ascontiguousarray(V_init, dtype=np.float32)
-            if V_init.shape != (n_samples, self.n_visible):
-                raise ValueError('`V_init` has invalid shape {0}: expected [{1}, {2}]'.format(V_init.shape, n_samples, self.n_visible))
-            V0d = self._to_device(V_init)
-        eng.pt_init(n_samples, betas, V0d)
-        eng.pt_sweep(int(n_gibbs_steps))
-        Vd = _ffi.DeviceArray((n_samples, self.n_visible), np.float32)
-        swaps, _ = eng.pt_read(Vd)
-        V = Vd.numpy()
-        if return_stats:
-            return V, swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
-        return V
+        return run_tempered_sampler(eng, n_samples, int(n_gibbs_steps), resolve_ladder(n_temperatures, betas), V_init,
+                                    self.n_visible, return_stats)
 
     # ---- likelihood (no counterpart in the reference: its only AIS is the DBM's) ----------------
     def _check_single_joint(self, what):

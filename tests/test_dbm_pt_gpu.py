@@ -1,5 +1,5 @@
-"""-m gpu: parallel tempering of a DBM - the two-segment RT flavour of act_kernel, dbm_pt_init_kernel, the shared
-pt_swap / pt_gather kernels, bm_dbm_pt_init / _sweep / _read and DBM.sample_v_tempered.
+"""-m gpu: parallel tempering of a DBM - the two-segment RT flavour of act_kernel, pt_init_kernel with an h2
+layer, the shared pt_swap / pt_gather kernels, bm_dbm_pt_init / _sweep / _read and DBM.sample_v_tempered.
 
 The engine is compared BIT FOR BIT (view(uint32)) with the CPU twin of tests/dbm_pt_twin.py: the states of all three layers at
 beta = 1, the ladder index of every row and the swap counters, after each of two consecutive calls.  Shapes (v, h1, h2), the
