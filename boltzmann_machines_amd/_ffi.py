@@ -90,6 +90,8 @@ SIGNATURES = {
     'bm_dbm_set_ais_literal': [_vp, _i32],
     'bm_dbm_set_sigmoid_literal': [_vp, _i32],
     'bm_rbm_set_fast_binary': [_vp, _i32],
+    'bm_rbm_set_centering': [_vp, _i32, C.c_float, C.c_float],
+    'bm_dbm_set_centering': [_vp, _i32, C.POINTER(C.c_float)],
     'bm_rbm64_create': [C.POINTER(RbmConfig), C.POINTER(C.c_double), C.POINTER(_vp)],
     'bm_rbm_multinomial_limit': [C.POINTER(C.c_int64)],
     'bm_rbm64_multinomial_limit': [C.POINTER(C.c_int64)],

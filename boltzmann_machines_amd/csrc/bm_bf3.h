@@ -256,7 +256,7 @@ __device__ __forceinline__ void split3_body(const float *W, int ldw, int nx, int
         split3_emit(w0, out, plane_stride, ld, nx, kg, transpose, e);
     }
 }
-__global__ __launch_bounds__(256) void split3_kernel(const float *W, int ldw, int rows, int cols, uint16_t *out, long long plane_stride, int ld, int transpose) {
+BM_KERNEL __launch_bounds__(256) void split3_kernel(const float *W, int ldw, int rows, int cols, uint16_t *out, long long plane_stride, int ld, int transpose) {
     const int nx = transpose ? cols : rows, nk = transpose ? rows : cols;      // operand rows / contraction length
     const bool vec = !transpose && (ldw & 3) == 0 && (((uintptr_t)W & 15u) == 0) && (nk & 7) == 0;
     if (vec) split3_body<true>(W, ldw, nx, nk, out, plane_stride, ld, transpose);
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void split3_kernel(const float *W, int ldw, in
 }
 
 // fp32 {0,1} states -> bf16 shadow (for states that were not produced by an act_kernel: AIS x_0, user input)
-__global__ void shadow16_kernel(const float *X, int ldx, int rows, int cols, uint16_t *out, int ld) {
+BM_KERNEL void shadow16_kernel(const float *X, int ldx, int rows, int cols, uint16_t *out, int ld) {
     const size_t n = (size_t)rows * cols;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const size_t r = e / (size_t)cols, c = e % (size_t)cols;
@@ -273,7 +273,7 @@ __global__ void shadow16_kernel(const float *X, int ldx, int rows, int cols, uin
 }
 
 // the same for caller-provided states: anything that is not exactly 0.0f or 1.0f raises *bad
-__global__ void shadow16_check_kernel(const float *X, int ldx, int rows, int cols, uint16_t *out, int ld, int *bad) {
+BM_KERNEL void shadow16_check_kernel(const float *X, int ldx, int rows, int cols, uint16_t *out, int ld, int *bad) {
     const size_t n = (size_t)rows * cols;
     bool any = false;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {

@@ -9,6 +9,7 @@
 #include "bm_common.h"
 #include "bm_kernels.h"
 #include "bm_pt.h"
+#include "bm_center.h"
 
 #include <math.h>
 #include <memory>
@@ -84,6 +85,12 @@ struct bm_dbm {
                                                    // engine stream, by the library's own RCCL communicator
     bm_xchg *xchg = nullptr;                       // bm_dbm_set_xchg: the same through the direct peer-memory exchange
     DevBuf wnorm[MAXL];
+    // centred update (bm_dbm_set_centering), by layer 0 = v, l = hidden layer l - 1: the offsets are variables
+    // ("ov", "oh", "oh_1", ...; zero until set), the rest is workspace allocated when the mode is first switched on
+    bool cen_on = false;
+    float cen_nu[MAXL + 1] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    DevBuf cen_o[MAXL + 1], cen_g[MAXL + 1];       // [n_l] offsets, plain bias gradients of the running update
+    DevBuf cen_a;                                  // [L + 1][N + M] row scalars: positive rows, then negative rows
     DevBuf mn_fac[MAXL];                           // max-norm column factors [2][n_{i+1}]: min(norm, c) | max(norm, 1e-8)
     Mat logits[MAXL];                              // Multinomial layers: row store of the logits / means [rows][n_i], on demand
     int logit_rows[MAXL] = {0, 0, 0, 0};
@@ -719,7 +726,56 @@ static void launch_dbm_grad(bm_dbm *h, const float *X_dev, int i, int fused, flo
     g.ldw = h->W[i].ld; g.ldwt = h->Wt[i].ld;
     g.pen = h->pen[i].p;
     g.N = N; g.M = M; g.l2 = h->cfg.l2; g.lr = lr; g.mom = mom;
-    launch_grad(g, st ? st : h->stream);
+    if (h->cen_on && fused) {
+        const GradCen cen{h->cen_o[i].p, h->cen_g[i].p, h->cen_o[i + 1].p, h->cen_g[i + 1].p};
+        launch_grad(g, st ? st : h->stream, &cen);
+    } else launch_grad(g, st ? st : h->stream);
+}
+
+// The centred form of launch_dbm_biases, three launches behind the column sums, all on the main stream and
+// in front of the fork of apply_update:
+//   1. offsets o_l and plain bias gradients g_l of every layer from the column sums   (cen_ema_kernel)
+//   2. row scalars a = (x - o).o of every layer's positive and negative rows         (cen_rowscal_kernel)
+//   3. bias corrections r_l + the bias / running-mean / penalty updates               (cen_bias_kernel)
+static void launch_dbm_center(bm_dbm *h, const float *X_dev, float lr, float mom) {
+    const int L = h->L, N = h->N, M = h->M;
+    const float *pos[MAXL + 1], *neg[MAXL + 1]; int ldp[MAXL + 1], ldn[MAXL + 1];
+    pos[0] = X_dev; ldp[0] = h->V; neg[0] = h->v.p; ldn[0] = h->v.ld;
+    for (int i = 0; i < L; ++i) { pos[i + 1] = h->mu[i].p; ldp[i + 1] = h->mu[i].ld; neg[i + 1] = h->H[i].p; ldn[i + 1] = h->H[i].ld; }
+    auto a_pos = [&](int l) { return h->cen_a.p + (size_t)l * (N + M); };
+    auto a_neg = [&](int l) { return h->cen_a.p + (size_t)l * (N + M) + N; };
+    CenEmaArgs e;
+    memset(&e, 0, sizeof(e));
+    CenRowArgs r;
+    memset(&r, 0, sizeof(r));
+    CenBiasArgs b;
+    memset(&b, 0, sizeof(b));
+    e.N = (float)N; e.M = (float)M; b.N = N; b.M = M;
+    int nmax = 0;
+    for (int l = 0; l <= L; ++l) {
+        const int n = h->n[l];
+        if (n > nmax) nmax = n;
+        const float *sp = h->sums_p + sums_off(h, 2 * l), *sn = h->sums_p + sums_off(h, 2 * l + 1);
+        e.job[l] = CenEmaJob{sp, sn, h->cen_o[l].p, h->cen_g[l].p, n, h->cen_nu[l]};
+        r.job[r.njobs++] = CenRowJob{pos[l], h->cen_o[l].p, a_pos(l), ldp[l], N, n, 0};
+        r.job[r.njobs++] = CenRowJob{neg[l], h->cen_o[l].p, a_neg(l), ldn[l], M, n, 0};
+        CenBiasJob &j = b.job[b.njobs++];
+        j.pos = pos[l]; j.ldp = ldp[l]; j.neg = neg[l]; j.ldn = ldn[l]; j.n = n;
+        if (l > 0) { j.wp0 = a_pos(l - 1); j.wn0 = a_neg(l - 1); }
+        if (l < L) { j.wp1 = a_pos(l + 1); j.wn1 = a_neg(l + 1); }
+        j.o = h->cen_o[l].p; j.g = h->cen_g[l].p;
+        DbmBiasArgs &d = j.d;
+        d.s_pos = sp; d.s_neg = sn; d.n = n; d.N = (float)N; d.M = (float)M; d.lr = lr; d.mom = mom;
+        if (l == 0) { d.b = h->vb.p; d.db = h->dvb.p; }
+        else {
+            const int i = l - 1;
+            d.b = h->hb[i].p; d.db = h->dhb[i].p; d.q = h->q[i].p; d.mm = h->mm[i].p; d.pen = h->pen[i].p; d.layer = i;
+            d.damping = h->cfg.sparsity_damping; d.cost = h->cfg.sparsity_cost[i]; d.target = h->cfg.sparsity_target[i];
+        }
+    }
+    hipLaunchKernelGGL(cen_ema_kernel, dim3((nmax + 255) / 256, L + 1), dim3(256), 0, h->stream, e);
+    launch_cen_rowscal(r, h->stream);
+    launch_cen_bias(b, h->stream);
 }
 
 static int recon_msre(bm_dbm *h, const float *X_dev, float *out_msre);
@@ -741,7 +797,8 @@ static void launch_dbm_maxnorm(bm_dbm *h, int i, int c_first = 0, int c_end = -1
 static int apply_update(bm_dbm *h, const float *X_dev, float lr, float mom) {
     const float N = (float)h->N, M = (float)h->M;
     launch_dbm_colsums(h, X_dev);
-    launch_dbm_biases(h, N, M, lr, mom);
+    if (h->cen_on) launch_dbm_center(h, X_dev, lr, mom);
+    else launch_dbm_biases(h, N, M, lr, mom);
     // The layers' outer products + max-norm passes are independent of each other (each reads mu / particles and its own
     // penalty vector, writes its own W / dW / W^T): odd layers go to the second stream, between a fork and a join event, so
     // that the 104 + 128 tiles of a 784-512-1024 stack share the chip instead of taking turns (once the launches are tuned).
@@ -845,6 +902,7 @@ int bm_dbm_create(const bm_dbm_config *cfg, bm_dbm **out) {
         nsums += 2 * (size_t)b;
     }
     BM_TRY(h->vb.alloc(h->V)); BM_TRY(h->dvb.alloc(h->V)); BM_TRY(h->sigma.alloc(h->V));
+    for (int l = 0; l <= h->L; ++l) BM_TRY(h->cen_o[l].alloc(h->n[l]));
     BM_TRY(h->v.alloc(h->M, h->V)); BM_TRY(h->v_new.alloc(h->M, h->V));
     BM_TRY(h->recon.alloc(h->N, h->V));
     {   // one contiguous buffer so that data-parallel training needs ONE all-reduce
@@ -916,7 +974,27 @@ static int resolve(bm_dbm *h, const char *name, Mat **mat, DevBuf **vec, bool *i
     else if (base == "vb" && idx == 0) *vec = &h->vb;
     else if (base == "dvb" && idx == 0) *vec = &h->dvb;
     else if (base == "sigma" && idx == 0) *vec = &h->sigma;
+    else if (base == "ov" && idx == 0) *vec = &h->cen_o[0];      // centering offsets (bm_dbm_set_centering)
+    else if (base == "oh") *vec = &h->cen_o[idx + 1];
     BM_CHECK(*mat || *vec, "unknown DBM variable '%s'", name ? name : "(null)");
+    return 0;
+}
+
+// Centred update (bm355.h).  A property of the handle: while it is on, bm_dbm_train_step and
+// bm_dbm_train_step_pt take the centred update.  nu [n_layers + 1]: the sliding factors of v, h_1, ... (read when `on`).
+int bm_dbm_set_centering(bm_dbm *h, int32_t on, const float *nu) {
+    BM_CHECK(h, "null argument");
+    if (!on) { h->cen_on = false; return 0; }
+    BM_CHECK(nu, "centering: null sliding factors");
+    BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "centering needs Bernoulli visible units (this handle's are Gaussian)");
+    for (int i = 0; i < h->L; ++i) BM_CHECK(!h->multinomial(i), "centering needs Bernoulli hidden units (layer %d of this handle is Multinomial)", i);
+    for (int l = 0; l <= h->L; ++l) BM_CHECK(nu[l] >= 0.f && nu[l] <= 1.f, "centering: sliding factor %g of layer %d outside [0, 1]", (double)nu[l], l);
+    if (!h->cen_a.p) {
+        for (int l = 0; l <= h->L; ++l) BM_TRY(h->cen_g[l].alloc(h->n[l]));
+        BM_TRY(h->cen_a.alloc((size_t)(h->L + 1) * (h->N + h->M)));      // last: the workspace is complete once it exists
+    }
+    for (int l = 0; l <= h->L; ++l) h->cen_nu[l] = nu[l];
+    h->cen_on = true;
     return 0;
 }
 
@@ -1071,6 +1149,7 @@ int bm_dbm_set_mf_allreduce(bm_dbm *h, float (*fn)(float, void *), void *ctx) {
 // data-parallel halves: phase 1 leaves the raw local sums in "grad", the caller
 // all-reduces that buffer, phase 2 normalises with the GLOBAL N and M and applies the update.
 int bm_dbm_grad_step(bm_dbm *h, const float *X_dev, int32_t k, int32_t *out_n_mf) {
+    BM_CHECK(!h->cen_on, "bm_dbm_grad_step: the split step has no centred form; switch centering off (bm_dbm_set_centering)");
     BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", k);
     int nmf = 0;
     BM_TRY(mean_field_and_particles(h, X_dev, k, &nmf));
@@ -1084,6 +1163,7 @@ int bm_dbm_grad_step(bm_dbm *h, const float *X_dev, int32_t k, int32_t *out_n_mf
 }
 
 int bm_dbm_apply_step(bm_dbm *h, int32_t N_global, int32_t M_global, float lr, float mom) {
+    BM_CHECK(!h->cen_on, "bm_dbm_apply_step: the split step has no centred form; switch centering off (bm_dbm_set_centering)");
     const float N = (float)N_global, M = (float)M_global;
     BM_TRY(check_dw(h, "bm_dbm_apply_step"));
     launch_dbm_biases(h, N, M, lr, mom);

@@ -90,6 +90,14 @@ struct NoSide {
 //   bit 9: only every other Q piece is moved (wrong results: what would half the Q bytes - a 16-bit state operand - buy?)
 #define BM_ABL(bit) ((ABL >> (bit)) & 1)
 
+// Every kernel of the shared headers is declared BM_KERNEL.  A translation unit that only borrows ONE kernel family from them
+// (bm_grad_cen.hip) defines BM_KERNELS_ONLY: its copies get internal linkage, so the ones it does not launch are dropped and
+// none collides with bm355.hip's at link time.
+#ifdef BM_KERNELS_ONLY
+#define BM_KERNEL static __global__
+#else
+#define BM_KERNEL __global__
+#endif
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 

@@ -552,7 +552,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
           bool CL = false, bool RT = false>
-__global__ __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
+BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
     //  instead of 22, +1 us on the prop-down; round 4, same-box A/B)
@@ -656,7 +656,7 @@ struct Bf3Strip { int tiles_i, tiles_j, strips, abl; };  // grid = tiles_i * str
                                                          // abl (BM355_DEBUG=bf3_abl, measurements only): 1 no epilogue, 2 no K loop
 
 template <class G, bool SEG2, int MINW>
-__global__ __launch_bounds__(G::NT, MINW) void act_bf3_kernel(ActArgs a, Bf3Strip sp) {
+BM_KERNEL __launch_bounds__(G::NT, MINW) void act_bf3_kernel(ActArgs a, Bf3Strip sp) {
     __shared__ __attribute__((aligned(16))) float smem[Bf3Geo<G>::SMEM_FLOATS];
     constexpr int E = G::E;
     const int ti = (int)blockIdx.x / sp.strips, st = (int)blockIdx.x % sp.strips;
@@ -805,7 +805,7 @@ __device__ __forceinline__ void block_colsum(const float *A, int lda, const floa
     if (negB) sum2 = -sum2;
 }
 
-__global__ __launch_bounds__(NT) void colsum_kernel(ColSumArgs a) {
+BM_KERNEL __launch_bounds__(NT) void colsum_kernel(ColSumArgs a) {
     __shared__ __attribute__((aligned(16))) float smem[CS_SMEM_FLOATS];
     const int wv = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int jb = 0;
@@ -832,7 +832,7 @@ struct RbmBiasArgs {
     int V, H;
     float N, lr, mom, damping, cost, target;
 };
-__global__ void rbm_bias_kernel(RbmBiasArgs a) {
+BM_KERNEL void rbm_bias_kernel(RbmBiasArgs a) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < a.V) {
         const float g = a.sv[c] / a.N;                       // reduce_mean(X - v, 0)     :451
@@ -912,7 +912,7 @@ __device__ __forceinline__ void rbm_bias_fused_block(const RbmBiasFusedArgs &a, 
     }
 }
 
-__global__ __launch_bounds__(NT) void rbm_bias_fused_kernel(RbmBiasFusedArgs a) {
+BM_KERNEL __launch_bounds__(NT) void rbm_bias_fused_kernel(RbmBiasFusedArgs a) {
     __shared__ __attribute__((aligned(16))) float smem[CS_SMEM_FLOATS];
     rbm_bias_fused_block(a, blockIdx.x, smem);
 }
@@ -1009,8 +1009,17 @@ template <int NJ> struct GradSide {
     }
 };
 
-template <class G, bool FAST, int ABL = 0, int STG = STG_DMA, int MINB = 1>
-__global__ __launch_bounds__(G::NT, MINB) void grad_kernel(GradArgs a, TileMap tmap) {
+// The centred flavour: offsets and plain bias gradients of the below-layer [J] and of the above-layer [I];
+// g -= oj[j] * gi[i] + gj[j] * oi[i] leaves the gradient in the epilogue, between the normalisation and apply_w_update.
+struct GradCen { const float *oj, *gj, *oi, *gi; };
+__device__ __forceinline__ const GradCen &grad_cen_of(const GradCen &c) { return c; }
+// The flavour is compile-time, as FE / LIT / MF / CL / RT are for act_kernel: the plain instantiations (CENP empty) carry none
+// of the centred code and keep their kernel arguments; the centred ones (CENP = GradCen) take a GradCen behind them.  The
+// fused-bias tail (nbias) does not exist in the centred flavour: the tiles need the bias gradients before the tail would form them.
+template <class G, bool FAST, int ABL = 0, int STG = STG_DMA, int MINB = 1, class... CENP>
+BM_KERNEL __launch_bounds__(G::NT, MINB) void grad_kernel(GradArgs a, TileMap tmap, CENP... cenp) {
+    constexpr int CEN = (int)sizeof...(CENP);
+    static_assert(CEN <= 1, "grad_kernel: at most one GradCen");
     constexpr int TI = G::TI, NJ = G::NJ;
     static_assert(G::MI == 2 && G::TI == 64 && G::TJ == 64, "grad_kernel: 64 x 64 tiles, 8 consecutive outputs per lane");
     __shared__ __attribute__((aligned(16))) float smem[G::SMEM_FLOATS];
@@ -1087,6 +1096,15 @@ __global__ __launch_bounds__(G::NT, MINB) void grad_kernel(GradArgs a, TileMap t
     const DivBy divN(a.N), divM(a.M);
     float wt[NJ][8];                // updated W values of the lane's j (NJ == 2: adjacent columns of Wt)
     bool jok[NJ];
+    float coi[CEN ? 8 : 1], cgi[CEN ? 8 : 1];
+    if constexpr (CEN != 0) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const bool ok = ib0 + e < a.I;
+            coi[e] = ok ? grad_cen_of(cenp...).oi[ib0 + e] : 0.f;
+            cgi[e] = ok ? grad_cen_of(cenp...).gi[ib0 + e] : 0.f;
+        }
+    }
 #pragma unroll
     for (int n = 0; n < NJ; ++n) {
         const int j = side.jb[n];
@@ -1119,6 +1137,11 @@ __global__ __launch_bounds__(G::NT, MINB) void grad_kernel(GradArgs a, TileMap t
 #pragma unroll
             for (int e = 0; e < 8; ++e) gr[e] = (a.form == 0) ? grad_norm1(pv[e], a.N, 0.f, false)
                                                               : grad_norm2(pv[e], nv[e], a.N, a.M, 0.f, 0.f, false);
+        }
+        if constexpr (CEN != 0) {
+            const float oj = grad_cen_of(cenp...).oj[j], gj = grad_cen_of(cenp...).gj[j];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) gr[e] = __fsub_rn(gr[e], __fadd_rn(__fmul_rn(oj, cgi[e]), __fmul_rn(gj, coi[e])));
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -1163,7 +1186,7 @@ struct ApplyWArgs {
     int form;
     float N, M, l2, lr, mom;
 };
-__global__ void apply_w_kernel(ApplyWArgs a) {
+BM_KERNEL void apply_w_kernel(ApplyWArgs a) {
     const size_t n = (size_t)a.I * a.J;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const int i = (int)(e % (size_t)a.I), j = (int)(e / (size_t)a.I);
@@ -1181,26 +1204,29 @@ __global__ void apply_w_kernel(ApplyWArgs a) {
 // 16-byte one, the transpose for Wt staged through LDS.  The trailing `nbias` workgroups run
 // rbm_bias_kernel's update (legal in the same launch when the W update does not need the
 // penalty they produce, i.e. sparsity_cost == 0: `a.pen` is then null).
-__device__ __forceinline__ void rbm_bias_update(const RbmBiasArgs &a, int c) {
-    if (c < a.V) {
-        const float g = a.sv[c] / a.N;
+// the bias / q_means / penalty update of ONE unit from its bias gradient g before the sparsity term (c: a visible unit, or a
+// hidden one when `hidden`); the plain split update forms g from the raw sums, the centred one hands in its corrected gradient
+__device__ __forceinline__ void rbm_bias_apply(const RbmBiasArgs &a, bool hidden, int c, float g) {
+    if (!hidden) {
         const float d = a.lr * (a.mom * a.dvb[c] + g);
         a.dvb[c] = d;
         a.vb[c] = a.vb[c] + d;
-    } else if (c < a.V + a.H) {
-        const int h = c - a.V;
-        const float qn = a.damping * a.q[h] + (1.0f - a.damping) * a.sq[h];
-        a.q[h] = qn;
+    } else {
+        const float qn = a.damping * a.q[c] + (1.0f - a.damping) * a.sq[c];
+        a.q[c] = qn;
         const float pen = a.cost * (qn - a.target);
-        a.pen[h] = pen;
-        float g = a.sh[h] / a.N;
+        a.pen[c] = pen;
         g = g - pen;
-        const float d = a.lr * (a.mom * a.dhb[h] + g);
-        a.dhb[h] = d;
-        a.hb[h] = a.hb[h] + d;
+        const float d = a.lr * (a.mom * a.dhb[c] + g);
+        a.dhb[c] = d;
+        a.hb[c] = a.hb[c] + d;
     }
 }
-__global__ __launch_bounds__(256) void apply_w_tiled_kernel(ApplyWArgs a, RbmBiasArgs b, int nbias) {
+__device__ __forceinline__ void rbm_bias_update(const RbmBiasArgs &a, int c) {
+    if (c < a.V) rbm_bias_apply(a, false, c, a.sv[c] / a.N);
+    else if (c < a.V + a.H) rbm_bias_apply(a, true, c - a.V, a.sh[c - a.V] / a.N);
+}
+BM_KERNEL __launch_bounds__(256) void apply_w_tiled_kernel(ApplyWArgs a, RbmBiasArgs b, int nbias) {
     __shared__ float tile[64][65];
     const int ntile = (int)gridDim.x - nbias;
     if ((int)blockIdx.x >= ntile) {
@@ -1272,7 +1298,7 @@ struct SmArgs {
     const float *prev; int ld_prev; unsigned *maxdiff;
     const int *skip;
 };
-__global__ __launch_bounds__(64) void softmax_multinomial_kernel(SmArgs a) {
+BM_KERNEL __launch_bounds__(64) void softmax_multinomial_kernel(SmArgs a) {
     extern __shared__ float sm_dyn[];
     float *c = sm_dyn, *e = sm_dyn + a.I;
     const int row = blockIdx.x, lane = threadIdx.x;
@@ -1337,7 +1363,7 @@ __global__ __launch_bounds__(64) void softmax_multinomial_kernel(SmArgs a) {
 
 // h_hat ~ Multinomial(M, uniform over K) (rbm.py:58): counts of floor(u * K); three independent
 // vectors (streams t = 0, 1, 2: free_energy_op, F(x) and F(x~) of the PLL), hhat [3][K] zeroed by the caller
-__global__ void mn_hhat_kernel(float *hhat, int K, int M, PhiloxKey k0, PhiloxKey k1, PhiloxKey k2) {
+BM_KERNEL void mn_hhat_kernel(float *hhat, int K, int M, PhiloxKey k0, PhiloxKey k1, PhiloxKey k2) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= M) return;
     const PhiloxKey keys[3] = {k0, k1, k2};
@@ -1352,7 +1378,7 @@ __global__ void mn_hhat_kernel(float *hhat, int K, int M, PhiloxKey k0, PhiloxKe
 // ----------------------------------------------------------------- elementwise
 // tf.nn.dropout(x, keep): x / keep * floor(keep + u)   (base_rbm.py:417-418)
 // X [rows][cols] pitch ldx -> Y pitch ldy; RNG index = flat0 + row*cols + col
-__global__ void dropout_kernel(const float *X, int ldx, float *Y, int ldy, int rows, int cols, float keep,
+BM_KERNEL void dropout_kernel(const float *X, int ldx, float *Y, int ldy, int rows, int cols, float keep,
                                PhiloxKey key, unsigned long long flat0) {
     const size_t n = (size_t)rows * cols;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
@@ -1363,7 +1389,7 @@ __global__ void dropout_kernel(const float *X, int ldx, float *Y, int ldy, int r
 }
 
 // GaussianRBM placeholder: X / sigma (rbm.py:107)
-__global__ void div_cols_kernel(const float *X, int ldx, const float *sigma, float *Y, int ldy, int rows, int cols) {
+BM_KERNEL void div_cols_kernel(const float *X, int ldx, const float *sigma, float *Y, int ldy, int rows, int cols) {
     const size_t n = (size_t)rows * cols;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const size_t r = e / (size_t)cols, c = e % (size_t)cols;
@@ -1372,7 +1398,7 @@ __global__ void div_cols_kernel(const float *X, int ldx, const float *sigma, flo
 }
 
 // strided 2-D copy (dense user buffer <-> padded internal matrix)
-__global__ void copy2d_kernel(const float *X, int ldx, float *Y, int ldy, int rows, int cols) {
+BM_KERNEL void copy2d_kernel(const float *X, int ldx, float *Y, int ldy, int rows, int cols) {
     const size_t n = (size_t)rows * cols;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const size_t r = e / (size_t)cols, c = e % (size_t)cols;
@@ -1381,7 +1407,7 @@ __global__ void copy2d_kernel(const float *X, int ldx, float *Y, int ldy, int ro
 }
 
 // conditional sampling, before the first pass: X[r][c] <- val[r][c] where mask[r][c] != 0 (X pitched or dense; val / mask pitch ldc)
-__global__ void clamp_apply_kernel(float *X, int ldx, const float *val, const float *mask, int ldc, int rows, int cols) {
+BM_KERNEL void clamp_apply_kernel(float *X, int ldx, const float *val, const float *mask, int ldc, int rows, int cols) {
     const size_t n = (size_t)rows * cols;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const size_t r = e / (size_t)cols, c = e % (size_t)cols;
@@ -1390,7 +1416,7 @@ __global__ void clamp_apply_kernel(float *X, int ldx, const float *val, const fl
 }
 
 // T[c][r] = A[r][c], 32 x 32 tiles through LDS (full-line reads and writes)
-__global__ __launch_bounds__(256) void transpose_kernel(const float *A, int lda, float *T, int ldt, int rows, int cols) {
+BM_KERNEL __launch_bounds__(256) void transpose_kernel(const float *A, int lda, float *T, int ldt, int rows, int cols) {
     __shared__ float t[32][33];
     const int tiles_c = (cols + 31) / 32;
     const int r0 = ((int)blockIdx.x / tiles_c) * 32, c0 = ((int)blockIdx.x % tiles_c) * 32;
@@ -1410,7 +1436,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 // sum of (A-B)^2 (B may be null) over a [rows][cols] window into a double accumulator
 // (msre :486-488; l2 :482-484)
-__global__ void sqdiff_kernel(const float *A, int lda, const float *B, int ldb, int rows, int cols, double *out) {
+BM_KERNEL void sqdiff_kernel(const float *A, int lda, const float *B, int ldb, int rows, int cols, double *out) {
     const size_t n = (size_t)rows * cols;
     double s = 0.0;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
@@ -1432,7 +1458,7 @@ __global__ void sqdiff_kernel(const float *A, int lda, const float *B, int ldb, 
 struct MetricsPrepArgs {
     double *scal; float *rowacc; int n_rowacc; int *flip; int B, V; PhiloxKey key; unsigned long long row0;
 };
-__global__ __launch_bounds__(256) void metrics_prep_kernel(MetricsPrepArgs a) {
+BM_KERNEL __launch_bounds__(256) void metrics_prep_kernel(MetricsPrepArgs a) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
     if (t < 6) a.scal[t] = 0.0;
     for (int e = t; e < a.n_rowacc; e += nt) a.rowacc[e] = 0.f;
@@ -1487,8 +1513,8 @@ __device__ __forceinline__ void sqdiff2_body(const SqJob &j0, const SqJob &j1, i
     __syncthreads();
     if (threadIdx.x == 0 && j.rows > 0) atomicAdd(j.out, (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]));
 }
-__global__ __launch_bounds__(256) void sqdiff2_kernel(SqJob j0, SqJob j1) { sqdiff2_body(j0, j1, (int)blockIdx.x, (int)gridDim.x); }
-__global__ void scal_to_host_kernel(const double *scal, double *dst) {
+BM_KERNEL __launch_bounds__(256) void sqdiff2_kernel(SqJob j0, SqJob j1) { sqdiff2_body(j0, j1, (int)blockIdx.x, (int)gridDim.x); }
+BM_KERNEL void scal_to_host_kernel(const double *scal, double *dst) {
     if (threadIdx.x < 6) dst[threadIdx.x] = scal[threadIdx.x];
 }
 
@@ -1509,7 +1535,7 @@ struct FeArgs {
     float *rowacc3;
 };
 template <bool FAST>
-__global__ __launch_bounds__(NT, 1) void fe_hidden_kernel(FeArgs a) {
+BM_KERNEL __launch_bounds__(NT, 1) void fe_hidden_kernel(FeArgs a) {
     using G = GeoAct;
     constexpr int TI = G::TI, TJ = G::TJ;
     __shared__ __attribute__((aligned(16))) float smem[G::SMEM_FLOATS];
@@ -1654,15 +1680,15 @@ __device__ __forceinline__ void fe_row_body(const FeRowArgs &a, int blk) {
         if (threadIdx.x == 0 || (threadIdx.x == 1 && a.rowacc2) || (threadIdx.x == 2 && a.rowacc3)) atomicAdd(a.out + threadIdx.x, v);
     }
 }
-__global__ __launch_bounds__(256) void fe_row_kernel(FeRowArgs a) { fe_row_body(a, (int)blockIdx.x); }
+BM_KERNEL __launch_bounds__(256) void fe_row_kernel(FeRowArgs a) { fe_row_body(a, (int)blockIdx.x); }
 // the tail of a fused metric fetch in ONE launch: blocks [0, nb_sq) the two squared sums, the rest the free-energy rows
-__global__ __launch_bounds__(256) void metrics_tail_kernel(SqJob j0, SqJob j1, FeRowArgs r, int nb_sq) {
+BM_KERNEL __launch_bounds__(256) void metrics_tail_kernel(SqJob j0, SqJob j1, FeRowArgs r, int nb_sq) {
     if ((int)blockIdx.x < nb_sq) sqdiff2_body(j0, j1, (int)blockIdx.x, nb_sq);     // workgroup-uniform
     else fe_row_body(r, (int)blockIdx.x - nb_sq);
 }
 
 // pll_rand = tf.random_uniform([B], 0, V, int32): minval + u32 % range (base_rbm.py:500-501)
-__global__ void pll_index_kernel(int *out, int B, int V, PhiloxKey key, unsigned long long row0) {
+BM_KERNEL void pll_index_kernel(int *out, int B, int V, PhiloxKey key, unsigned long long row0) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const unsigned long long idx = row0 + b;
@@ -1682,8 +1708,9 @@ struct DbmBiasArgs {
     int n, layer;
     float N, M, lr, mom, damping, cost, target;
 };
-__device__ __forceinline__ void dbm_bias_update(const DbmBiasArgs &a, int c) {
-    float g = a.s_pos[c] / a.N - a.s_neg[c] / a.M;           // reduce_mean(mu) - reduce_mean(H)   :553,573-576
+// ... from the bias gradient g before the sparsity term (the plain update forms it from the column sums, the centred one
+// hands in its corrected gradient: bm_center.h)
+__device__ __forceinline__ void dbm_bias_apply(const DbmBiasArgs &a, int c, float g) {
     if (a.q) {
         const float qn = a.damping * a.q[c] + (1.0f - a.damping) * a.s_neg[a.layer];    // :582-584 (q_means[i] scalar)
         const float mn = a.damping * a.mm[c] + (1.0f - a.damping) * a.s_pos[a.layer];   // :585-587
@@ -1699,7 +1726,10 @@ __device__ __forceinline__ void dbm_bias_update(const DbmBiasArgs &a, int c) {
     a.db[c] = d;
     a.b[c] = a.b[c] + d;
 }
-__global__ void dbm_bias_kernel(DbmBiasArgs a) {
+__device__ __forceinline__ void dbm_bias_update(const DbmBiasArgs &a, int c) {
+    dbm_bias_apply(a, c, a.s_pos[c] / a.N - a.s_neg[c] / a.M);           // reduce_mean(mu) - reduce_mean(H)   :553,573-576
+}
+BM_KERNEL void dbm_bias_kernel(DbmBiasArgs a) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < a.n) dbm_bias_update(a, c);
 }
@@ -1707,7 +1737,7 @@ __global__ void dbm_bias_kernel(DbmBiasArgs a) {
 // three launches of a 2-layer stack were 3 us of work each behind 4 - 8 us of launch latency at the tail of the update
 constexpr int DBM_BIAS_JOBS = 1 + 4;              // 1 + BM_DBM_MAX_LAYERS
 struct DbmBiasMulti { DbmBiasArgs job[DBM_BIAS_JOBS]; };
-__global__ void dbm_bias_multi_kernel(DbmBiasMulti m) {
+BM_KERNEL void dbm_bias_multi_kernel(DbmBiasMulti m) {
     const DbmBiasArgs &a = m.job[blockIdx.y];
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < a.n) dbm_bias_update(a, c);
@@ -1775,7 +1805,7 @@ __device__ __forceinline__ void maxnorm_store(const MaxNormArgs &a, int c0, int 
         *reinterpret_cast<float4 *>(buf + row * 16 + 4 * c4) = v;
     }
 }
-__global__ __launch_bounds__(NT) void maxnorm_kernel(MaxNormArgs a) {
+BM_KERNEL __launch_bounds__(NT) void maxnorm_kernel(MaxNormArgs a) {
     static_assert(NT == 256 && MN_NV >= 1 && MN_NV * NT == MN_CH * (MN_COLS / 4), "loader split");
     __shared__ __attribute__((aligned(16))) float sA[2][MN_CH * 16];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1821,7 +1851,7 @@ __global__ __launch_bounds__(NT) void maxnorm_kernel(MaxNormArgs a) {
         if (a.norm_out) a.norm_out[c] = nrm;
     }
 }
-__global__ __launch_bounds__(256) void maxnorm_scale_kernel(MaxNormArgs a) {
+BM_KERNEL __launch_bounds__(256) void maxnorm_scale_kernel(MaxNormArgs a) {
     __shared__ float t[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int tiles_c = (a.c_end - a.c_first + 31) / 32;
@@ -1852,7 +1882,7 @@ __global__ __launch_bounds__(256) void maxnorm_scale_kernel(MaxNormArgs a) {
 // and latch `done` when the residual no longer exceeds the tolerance; `init` evaluates the
 // step-0 condition from the residual between the persistent mu and the init values.
 // blk [nblk]: per-workgroup residuals of the sweep's act_kernel launches (read, then zeroed for the next sweep)
-__global__ __launch_bounds__(256) void mf_ctl_kernel(MfCtl *c, float tol, int init, float *blk, int nblk) {
+BM_KERNEL __launch_bounds__(256) void mf_ctl_kernel(MfCtl *c, float tol, int init, float *blk, int nblk) {
     __shared__ float s_m[4];
     float m = 0.f;
     for (int e = threadIdx.x; e < nblk; e += 256) { m = fmaxf(m, blk[e]); blk[e] = 0.f; }
@@ -1877,7 +1907,7 @@ __global__ __launch_bounds__(256) void mf_ctl_kernel(MfCtl *c, float tol, int in
 //   mf_resid_kernel: local residual of the sweep -> c->resid (slots and the atomic cell are reset)
 //   [ncclAllReduce(max) of c->resid on the same stream]
 //   mf_latch_kernel: the counter / `done` update of mf_ctl_kernel from the reduced value
-__global__ __launch_bounds__(256) void mf_resid_kernel(MfCtl *c, float *blk, int nblk) {
+BM_KERNEL __launch_bounds__(256) void mf_resid_kernel(MfCtl *c, float *blk, int nblk) {
     __shared__ float s_m[4];
     float m = 0.f;
     for (int e = threadIdx.x; e < nblk; e += 256) { m = fmaxf(m, blk[e]); blk[e] = 0.f; }
@@ -1889,7 +1919,7 @@ __global__ __launch_bounds__(256) void mf_resid_kernel(MfCtl *c, float *blk, int
     c->resid = fmaxf(fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3])), __uint_as_float(c->maxdiff));
     c->maxdiff = 0u;
 }
-__global__ void mf_latch_kernel(MfCtl *c, float tol, int init) {
+BM_KERNEL void mf_latch_kernel(MfCtl *c, float tol, int init) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     if (init) {
         c->steps = 0;
@@ -1903,7 +1933,7 @@ __global__ void mf_latch_kernel(MfCtl *c, float tol, int init) {
 // ||A - B||_inf over a [rows][cols] window -> atomicMax on float bits (mean-field cond, dbm.py:449-452).
 // Rows over workgroups, columns over threads (coalesced), ONE atomic per workgroup: same-address atomics serialise
 // in the L2 at ~12 ns each (2048 of them made this kernel take 25 us).
-__global__ __launch_bounds__(256) void maxabsdiff_kernel(const float *A, int lda, const float *B, int ldb, int rows, int cols, unsigned *out) {
+BM_KERNEL __launch_bounds__(256) void maxabsdiff_kernel(const float *A, int lda, const float *B, int ldb, int rows, int cols, unsigned *out) {
     __shared__ float s_m[4];
     float m = 0.f;
     const bool vec = ((lda | ldb) & 3) == 0 && ((((uintptr_t)A) | ((uintptr_t)B)) & 15u) == 0;
@@ -1954,7 +1984,7 @@ __global__ __launch_bounds__(256) void maxabsdiff_kernel(const float *A, int lda
 // out = sigmoid(mult * z + bmult * b) with z = the stored raw pre-activation - the arithmetic of act_epilogue, operation by
 // operation, so the result is the bits of the GEMM pass it replaces - and the step-0 residual max |out - prev| of the loop
 // condition (dbm.py:449-452) into this workgroup's slot (gridDim.x <= BM_MF_SLOTS) or one atomic.  Rows over workgroups.
-__global__ __launch_bounds__(256) void mf_init0_kernel(const float *Z, int ldz, const float *bias, const float *prev, int ldp,
+BM_KERNEL __launch_bounds__(256) void mf_init0_kernel(const float *Z, int ldz, const float *bias, const float *prev, int ldp,
                                                        float *out, int ldo, int rows, int cols, float mult, float bmult, int lit,
                                                        unsigned *maxdiff, float *blk) {
     __shared__ float s_m[4];
@@ -1995,7 +2025,7 @@ struct AisScoreArgs {
 // tree.  (Round 2: one thread per chain walked all 113 slots, 79 workgroups for 20 000 chains: 37 us per beta, 4 % of
 // an AIS run.)  Deterministic; sums of <= 113 floats in double are exact to ~1e-16, far below the float the value
 // is finally rounded to.
-__global__ __launch_bounds__(256) void ais_score_kernel(double *logw, int J, int ld, AisScoreArgs p, float dbeta) {
+BM_KERNEL __launch_bounds__(256) void ais_score_kernel(double *logw, int J, int ld, AisScoreArgs p, float dbeta) {
     __shared__ double s_s[8][32], s_d[8][32];
     const int c = threadIdx.x & 31, t = threadIdx.x >> 5;
     const int j = blockIdx.x * 32 + c;
@@ -2020,4 +2050,6 @@ __global__ __launch_bounds__(256) void ais_score_kernel(double *logw, int J, int
 
 }  // namespace bm
 
+#ifndef BM_KERNELS_ONLY       // (bm_grad_cen.hip: a unit that launches ONE kernel family does not pay for every instantiation)
 #include "bm_launch.h"      // the host side: launchers and the launch tuner
+#endif

@@ -401,6 +401,13 @@ static inline void launch_grad_geo(const GradArgs &g, hipStream_t st) {
     if (fast) hipLaunchKernelGGL((grad_kernel<G, true, 0, STG, MINB>), grid, blk, 0, st, g, tmap);
     else      hipLaunchKernelGGL((grad_kernel<G, false, 0, STG_DMA, MINB>), grid, blk, 0, st, g, tmap);
 }
+// centred flavour (grad_kernel<..., GradCen>): instantiated for the geometries 4 and 8 with DMA staging.  A forced
+// geometry (BM355_DEBUG=grad_geo) runs as asked when it is 8 and FALLS BACK TO 4 otherwise; a tuned one takes the centred
+// kernel of its wave count (8, 9, 108, 208 -> 8; 4, 104 -> 4).  Bit-identical results either way.
+// Defined in bm_grad_cen.hip, a translation unit of its own: with the centred instantiations in the same module the compiler
+// allocates the plain 8-wave instantiations' registers differently (170 / 188 instead of 173 / 190 VGPRs), and the plain
+// kernels are to stay exactly what they were.
+void launch_grad_cen(int geo, const GradArgs &g, const GradCen &cen, hipStream_t st);
 // geo: 4 | 8 waves, + 100 for register staging of the full chunks, or one of the specials
 static inline void launch_grad_as(int geo, const GradArgs &g, hipStream_t st) {
     // 9: 8 waves, BK = 32, two workgroups per CU - for outputs of many tiles per CU and a short K (3072 x 5000 x 512:
@@ -442,15 +449,19 @@ static inline Tuned tune_grad_shape(const GradArgs &g, hipStream_t st) {
                 g.I, g.J, g.Kpos, g.Kneg, g.form, g.fused, T.geo, us[0], us[1], us[2], us[3], us[4], T.xi == XI_SLAB ? 9 : T.xi, xi_us[4], xi_us[0], xi_us[1], xi_us[2], xi_us[3]);
     return T;
 }
-static inline void launch_grad(const GradArgs &g_in, hipStream_t st) {
+// cen: the centred flavour (fused, no bias tail - its callers see to both)
+static inline void launch_grad(const GradArgs &g_in, hipStream_t st, const GradCen *cen = nullptr) {
     static const int fetch_env = std::max(0, dbg_int("grad_fetch")), geo_env = dbg_int("grad_geo");   // overrides (experiments)
     GradArgs g = g_in;
     g.fetch_at_fill = fetch_env;      // measured (same box, 784x1024x512): epilogue 66.6 us/update, fill 67.5
-    if (geo_env) { launch_grad_as(geo_env, g, st); return; }
+    if (geo_env) { if (cen) launch_grad_cen(geo_env, g, *cen, st); else launch_grad_as(geo_env, g, st); return; }
     static TuneMemo<6> memo;
+    // (the centred flavour shares the plain flavour's entry for the shape, as CL and RT do for act_kernel)
     const Tuned T = memo.get({g.I, g.J, g.Kpos, g.Kneg, g.form | (g.fused << 1), g.ldw}, [&] { return tune_grad_shape(g, st); });
     if (T.xi != XI_MODEL && !g.map_xi) g.map_xi = T.xi;
-    launch_grad_as(T.geo, g, st);
+    // (a tuned 8-wave geometry - 8, 9, 108, 208 - takes the centred 8-wave kernel, the others the 4-wave one)
+    if (cen) launch_grad_cen((T.geo == 8 || T.geo == 9 || T.geo == 108 || T.geo == 208) ? 8 : 4, g, *cen, st);
+    else launch_grad_as(T.geo, g, st);
 }
 
 static inline void launch_fe_hidden(const FeArgs &f, hipStream_t st) {

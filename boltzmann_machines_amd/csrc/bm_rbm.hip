@@ -9,6 +9,7 @@
 #include "bm_kernels.h"
 #include "bm_chain.h"
 #include "bm_pt.h"
+#include "bm_center.h"
 
 #include <math.h>
 #include <atomic>
@@ -74,6 +75,13 @@ struct bm_rbm {
     int grad_slot = 0;
     Event ev_ready[2], ev_reduced[2];
     DevBuf pen;       // [H]
+    // centred update (bm_rbm_set_centering): the offsets are variables ("ov", "oh", zero until set), the rest
+    // is workspace allocated when the mode is first switched on
+    bool cen_on = false;
+    float cen_nu_v = 0.f, cen_nu_h = 0.f;
+    DevBuf ov, oh;            // [V], [H]
+    DevBuf cen_gv, cen_gh;    // [V], [H] plain bias gradients of the running update
+    DevBuf cen_a;             // [4][maxB] row scalars: X, v_k, h0, h_k
     DevBuf rowacc;    // [3*maxB]
     DevBuf hhat;      // [3*H] MultinomialRBM free-energy h_hat vectors (rbm.py:58)
     DevArray<int> flip;
@@ -362,9 +370,11 @@ static void launch_bias_fused(bm_rbm *h, int B, float lr, float mom) {
 }
 
 static void rbm_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom, bool with_bias);
+static void launch_update_centred(bm_rbm *h, int B, float lr, float mom);
 
 // whole parameter update of the fused single-GPU step (base_rbm.py:443-478)
 static void launch_update_fused(bm_rbm *h, int B, float lr, float mom) {
+    if (h->cen_on) { launch_update_centred(h, B, lr, mom); return; }
     if (h->cfg.sparsity_cost != 0.f) {      // W update needs the penalty: bias kernel first
         launch_bias_fused(h, B, lr, mom);
         rbm_grad(h, B, 1, (float)B, lr, mom, false);
@@ -398,9 +408,59 @@ static void rbm_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom, 
         g.nbias = fill_bias_fused(h, B, lr, mom, g.bias);
         g.bias.raw_only = fused ? 0 : 1;      // split (data-parallel) step: raw column sums only
     }
-    bm::launch_grad(g, h->stream);
+    if (h->cen_on && fused) {
+        const GradCen cen{h->ov.p, h->cen_gv.p, h->oh.p, h->cen_gh.p};
+        bm::launch_grad(g, h->stream, &cen);
+    } else bm::launch_grad(g, h->stream);
     if (fused && h->use_wt) h->wt_valid = true;      // the fused update wrote W and W^T together (every other writer of W
                                                      // clears the flag: set_param, apply_step, the exchange)
+}
+
+// The centred form of launch_update_fused, four launches in stream order:
+//   1. column sums, raw tail, plain bias gradients g_v / g_h, offsets o_v / o_h   (rbm_cen_stats_kernel)
+//   2. row scalars a = (x - o).o of X, v_k, h0, h_k under the NEW offsets          (cen_rowscal_kernel)
+//   3. bias corrections r_v / r_h + the bias / q_means / penalty update            (cen_bias_kernel)
+//   4. outer products + centred W update                                           (grad_kernel, CEN flavour, no bias tail)
+static void launch_update_centred(bm_rbm *h, int B, float lr, float mom) {
+    const float *hk = h->hm_is_neg ? h->hneg.p : h->hm.p;      // the last prop-up may have left only -h_k: read negated (exact)
+    const int ldhk = h->hm_is_neg ? h->hneg.ld : h->hm.ld, hk_neg = h->hm_is_neg ? 1 : 0;
+    float *aX = h->cen_a.p, *av = aX + h->maxB, *ah0 = av + h->maxB, *ahk = ah0 + h->maxB;
+    {
+        ProfScope _ps(h, KC_COLSUM);
+        RbmCenStatsArgs s;
+        memset(&s, 0, sizeof(s));
+        s.X = h->Xin; s.ldx = h->Xin_ld; s.vs = h->vs.p; s.ldv = h->vs.ld;
+        s.h0m = h->h0m.p; s.ldh0 = h->h0m.ld; s.hm = hk; s.ldh = ldhk; s.hm_negated = hk_neg;
+        s.B = B; s.V = h->V; s.H = h->H;
+        s.raw_tail = h->grad.p + h->grad_tail();
+        s.ov = h->ov.p; s.oh = h->oh.p; s.gv = h->cen_gv.p; s.gh = h->cen_gh.p;
+        s.nu_v = h->cen_nu_v; s.nu_h = h->cen_nu_h; s.N = (float)B;
+        hipLaunchKernelGGL(rbm_cen_stats_kernel, dim3((h->V + 63) / 64 + (h->H + 63) / 64), dim3(NT), 0, h->stream, s);
+        CenRowArgs r;
+        memset(&r, 0, sizeof(r));
+        r.job[0] = CenRowJob{h->Xin, h->ov.p, aX, h->Xin_ld, B, h->V, 0};
+        r.job[1] = CenRowJob{h->vs.p, h->ov.p, av, h->vs.ld, B, h->V, 0};
+        r.job[2] = CenRowJob{h->h0m.p, h->oh.p, ah0, h->h0m.ld, B, h->H, 0};
+        r.job[3] = CenRowJob{hk, h->oh.p, ahk, ldhk, B, h->H, hk_neg};
+        r.njobs = 4;
+        launch_cen_rowscal(r, h->stream);
+    }
+    {
+        ProfScope _ps(h, KC_BIAS);
+        CenBiasArgs b;
+        memset(&b, 0, sizeof(b));
+        b.N = B; b.M = B; b.njobs = 2;
+        CenBiasJob &jv = b.job[0], &jh = b.job[1];
+        jv.pos = h->Xin; jv.ldp = h->Xin_ld; jv.neg = h->vs.p; jv.ldn = h->vs.ld; jv.n = h->V;
+        jv.wp1 = ah0; jv.wn1 = ahk; jv.o = h->ov.p; jv.g = h->cen_gv.p;
+        jh.pos = h->h0m.p; jh.ldp = h->h0m.ld; jh.neg = hk; jh.ldn = ldhk; jh.neg_negated = hk_neg; jh.n = h->H;
+        jh.wp0 = aX; jh.wn0 = av; jh.o = h->oh.p; jh.g = h->cen_gh.p;
+        jv.rbm = jh.rbm = 1; jh.rbm_hidden = 1;
+        fill_bias(h, (float)B, lr, mom, jv.r);
+        jh.r = jv.r;
+        launch_cen_bias(b, h->stream);
+    }
+    rbm_grad(h, B, 1, (float)B, lr, mom, false);
 }
 
 static void launch_fe(bm_rbm *h, const float *Xin, int ldx, int B, bool with_flip) {
@@ -733,6 +793,7 @@ int bm_rbm_create(const bm_rbm_config *cfg, bm_rbm **out) {
     BM_TRY(h->vm.alloc(B, V)); BM_TRY(h->vs.alloc(B, V)); BM_TRY(h->Xs.alloc(B, V)); BM_TRY(h->Xd.alloc(B, V));
     BM_TRY(h->grad.alloc(h->grad_tail() + V + 2 * (size_t)H));
     BM_TRY(h->pen.alloc(H));
+    BM_TRY(h->ov.alloc(V)); BM_TRY(h->oh.alloc(H));
     BM_TRY(h->rowacc.alloc(3 * (size_t)B)); BM_TRY(h->hhat.alloc(3 * (size_t)H));
     BM_TRY(h->flip.alloc(B)); BM_TRY(h->scal.alloc(6));
     {   // sigma defaults to 1 (rbm.py:88)
@@ -801,6 +862,25 @@ int bm_rbm_set_fast_binary(bm_rbm *h, int32_t on) {
     return 0;
 }
 
+// Centred update (bm355.h).  A property of the handle: while it is on, every fused update entry - train_step,
+// _metrics, _metrics_async, train_epoch, train_step_pt, train_epoch_pt - takes the centred update.
+int bm_rbm_set_centering(bm_rbm *h, int32_t on, float nu_v, float nu_h) {
+    BM_CHECK(h, "null argument");
+    if (!on) { h->cen_on = false; return 0; }
+    BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "centering needs Bernoulli visible units (this handle's are Gaussian)");
+    BM_CHECK(!h->multinomial(), "centering needs Bernoulli hidden units (this handle's are Multinomial)");
+    BM_CHECK(!h->cfg.dbm_first && !h->cfg.dbm_last, "centering: a dbm_first / dbm_last handle (one conditional doubled) is not centred");
+    BM_CHECK(h->cfg.dropout < 0.f, "centering does not combine with dropout (this handle's is %g)", (double)h->cfg.dropout);
+    BM_CHECK(nu_v >= 0.f && nu_v <= 1.f && nu_h >= 0.f && nu_h <= 1.f, "centering: sliding factors (%g, %g) outside [0, 1]", (double)nu_v, (double)nu_h);
+    if (!h->cen_a.p) {
+        BM_TRY(h->cen_gv.alloc(h->V)); BM_TRY(h->cen_gh.alloc(h->H));
+        BM_TRY(h->cen_a.alloc(4 * (size_t)h->maxB));      // last: the workspace is complete once it exists
+    }
+    h->cen_nu_v = nu_v; h->cen_nu_h = nu_h;
+    h->cen_on = true;
+    return 0;
+}
+
 // name -> vector variable
 static DevBuf *find_vec(bm_rbm *h, const std::string &n) {
     if (n == "vb") return &h->vb;
@@ -809,6 +889,8 @@ static DevBuf *find_vec(bm_rbm *h, const std::string &n) {
     if (n == "dhb") return &h->dhb;
     if (n == "q_means") return &h->q;
     if (n == "sigma") return &h->sigma;
+    if (n == "ov") return &h->ov;             // centering offsets (bm_rbm_set_centering)
+    if (n == "oh") return &h->oh;
     return nullptr;
 }
 
@@ -1034,6 +1116,7 @@ int bm_rbm_train_epoch(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, 
 }
 
 int bm_rbm_grad_step(bm_rbm *h, const float *X_dev, int32_t B, int32_t k) {
+    BM_CHECK(!h->cen_on, "bm_rbm_grad_step: the split step has no centred form; switch centering off (bm_rbm_set_centering)");
     BM_TRY(run_chain(h, X_dev, B, k, nullptr, false, false, true));
     rbm_grad(h, B, 0, (float)B, 0.f, 0.f, true);     // raw outer products + raw column sums, one launch
     h->call++;
@@ -1078,6 +1161,7 @@ int bm_rbm_wait_grads(bm_rbm *h, int32_t slot) {
 }
 
 int bm_rbm_apply_step(bm_rbm *h, int32_t B_global, float lr, float mom) {
+    BM_CHECK(!h->cen_on, "bm_rbm_apply_step: the split step has no centred form; switch centering off (bm_rbm_set_centering)");
     BM_TRY(check_dw(h, "bm_rbm_apply_step"));
     ProfScope _ps(h, KC_BIAS);
     RbmBiasArgs b;

@@ -877,6 +877,7 @@ static int xchg_launch_apply(bm_rbm *h, bm_xchg *x, float N_global, float lr, fl
 // bm_rbm_apply_step (same bits).  After it every replica holds the new W, vb, hb, dvb, dhb, q_means; of dW every rank
 // holds ITS slice (bm_rbm_exchange_gather_dw completes the replicas, e.g. before a checkpoint).
 int bm_rbm_exchange_apply_direct(bm_rbm *h, bm_xchg *x, int32_t B_global, float lr, float mom) {
+    BM_CHECK(!h || !h->cen_on, "bm_rbm_exchange_apply_direct: the exchange's fused apply has no centred form; switch centering off");
     BM_CHECK(h && x, "null argument");
     BM_CHECK(B_global > 0, "bm_rbm_exchange_apply_direct: B_global = %d must be positive", B_global);
     BM_TRY(xchg_launch_apply(h, x, (float)B_global, lr, mom, 0));
@@ -960,6 +961,7 @@ static int dbm_fill_exchange(bm_dbm *h, bm_xchg *x, bmx::Args &a, bmx::DbmApply 
 // bm_dbm_allreduce_grads_direct + bm_dbm_apply_step, same bits.  Afterwards every replica holds the new W_i, W_i^T, column
 // norms, biases, running means; of the momentum buffers dW_i a rank holds its columns (bm_dbm_exchange_gather_dw).
 int bm_dbm_exchange_apply_direct(bm_dbm *h, bm_xchg *x, int32_t N_global, int32_t M_global, float lr, float mom) {
+    BM_CHECK(!h || !h->cen_on, "bm_dbm_exchange_apply_direct: the exchange's fused apply has no centred form; switch centering off");
     BM_CHECK(h && x, "null argument");
     BM_CHECK(N_global > 0 && M_global > 0, "bm_dbm_exchange_apply_direct: N_global = %d and M_global = %d must be positive", N_global, M_global);
     BM_CHECK(!h->failed, "an earlier launch of this engine failed");

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _ffi
 from .base import EngineModel, run_on_engine
+from .centering import CenteredTraining
 from .engine import DbmEngine, DbmEngine64
 from .rbm import GaussianRBM, clampable_only
 from .tempering import TemperedNegativePhase, resolve_ladder, run_tempered_sampler
@@ -33,7 +34,7 @@ def as_device(X, dtype=np.float32):
     return X if isinstance(X, _ffi.DeviceArray) else _ffi.DeviceArray.from_numpy(np.asarray(X), dtype)
 
 
-class DBM(TemperedNegativePhase, EngineModel):
+class DBM(CenteredTraining, TemperedNegativePhase, EngineModel):
     def __init__(self, rbms=None,
                  n_particles=100, v_particle_init=None, h_particles_init=None,
                  n_gibbs_steps=5, max_mf_updates=10, mf_tol=1e-7,
@@ -245,6 +246,7 @@ class DBM(TemperedNegativePhase, EngineModel):
             self._dp = parallel.DataParallelDBM(self._engine, self._rank, self._world,
                                                 parallel.native_allreduce_on_engine_stream(self._engine, self._comm),
                                                 comm=self._comm)
+        self._apply_centering()
 
     def _on_graph_build(self):
         # `_make_ais` draws the op-level seed of x_0 from the host MT stream WHILE THE GRAPH IS BUILT
@@ -263,7 +265,9 @@ class DBM(TemperedNegativePhase, EngineModel):
         self._engine.seed(seed)
 
     def _variables(self):
-        return {name: self._engine.get(name) for name, _ in self._var_names()}
+        out = {name: self._engine.get(name) for name, _ in self._var_names()}
+        out.update(self._centering_variables())       # (nothing unless centering is on)
+        return out
 
     def _scoped_variables(self):
         """the reference's variable names (dbm.py:294-383): layer i > 0 gets TF's `_i` suffix, the hidden particles live
@@ -286,7 +290,46 @@ class DBM(TemperedNegativePhase, EngineModel):
     def load_model(cls, model_path):
         model = super(DBM, cls).load_model(model_path)
         model.n_layers_ = len(model.n_hiddens_)
+        model._centering_restore(model._pending_vars)
         return model
+
+    # ---- centred training (no counterpart in the reference) -------------------
+    def _centering_sizes(self):
+        if self.n_layers_ is None:
+            raise RuntimeError('DBM has no layers: pass `rbms` or use `load_model`')
+        return [self.n_visible_] + list(self.n_hiddens_)
+
+    def _check_centering(self, what):
+        name = self._check_centering_common(what)
+        if self.n_layers_ is not None and self.v_unit_ != _ffi.UNIT_BERNOULLI:
+            raise NotImplementedError('%s: centering needs Bernoulli visible units (Gaussian visible units are not centred)' % name)
+        if self.n_layers_ is not None and any(self._h_unit(i) != _ffi.UNIT_BERNOULLI for i in range(self.n_layers_)):
+            raise NotImplementedError('%s: centering needs Bernoulli hidden layers (Multinomial layers are not centred)' % name)
+
+    def _engine_set_centering(self, on, nus):
+        self._engine.set_centering(on, nus)
+
+    def set_centering(self, enabled=True, nu=0.01, offsets=None):
+        """Centred updates in `fit` (the centering trick: Montavon & Mueller 2012; Melchior, Fischer & Wiskott 2016).
+
+        The weight gradients are taken between units minus running offsets, <(x_{l-1} - o_{l-1})(x_l - o_l)^T>, and the bias
+        gradients are corrected accordingly; the model stays in the standard parameters, so sampling, mean-field, AIS and
+        `log_proba` are unchanged.  Every update first moves the offsets, o_l <- (1 - nu_l) o_l + nu_l * mean of the
+        positive phase (X, the mean-field mu_l).
+
+        nu : one sliding factor in [0, 1] or one per layer, visible layer first (n_layers + 1 values).
+        offsets : one vector per layer, visible first (entries may be None); None: at the first update of the next `fit(X)`
+        the mean of X (float64 sum, rounded to float32) for the visible layer and 0.5 for every hidden layer.
+        Works with both negative phases of `set_negative_phase`.  The offsets are optimiser state: while centering is on
+        they are written to model.npz (`centering_ov`, `centering_oh[_i]`, `centering_nu`) and `load_model` re-enables the
+        mode from them; params.json keeps the reference's schema.  All-Bernoulli DBMs in float32 only: Gaussian visible
+        units, Multinomial layers, float64 and BM355_DATA_PARALLEL jobs raise NotImplementedError.  Returns self."""
+        if not enabled:
+            return self._set_centering(False, None, None)
+        self._check_centering('set_centering')
+        n = len(self._centering_sizes())
+        nus = list(nu) if hasattr(nu, '__iter__') else [nu] * n
+        return self._set_centering(enabled, nus, offsets)
 
     # ---- schedules (reference dbm.py:771-791) -------------------------------------------
     def _feed(self, n_gibbs_steps=None):
@@ -356,6 +399,7 @@ class DBM(TemperedNegativePhase, EngineModel):
         dt = self._engine.dtype
         X = np.ascontiguousarray(X, dtype=dt)
         self._check_batches(X, sharded=True)
+        self._centering_begin_fit(X)
         Xd, N = as_device(X, dt), len(X)
         Xvd = None
         if X_val is not None:

@@ -94,7 +94,7 @@ class RbmEngine(_PtCalls):
     # -- variables
     def _size(self, name):
         return {'W': self.V * self.H, 'dW': self.V * self.H, 'vb': self.V, 'dvb': self.V, 'sigma': self.V,
-                'hb': self.H, 'dhb': self.H, 'q_means': self.H,
+                'hb': self.H, 'dhb': self.H, 'q_means': self.H, 'ov': self.V, 'oh': self.H,
                 'grad': self.V * self.H + self.V + 2 * self.H}[name]
 
     def _shape(self, name):
@@ -123,6 +123,11 @@ class RbmEngine(_PtCalls):
         """opt-in exact-product bf16 x 3 mode of the sampling sweep (bm_rbm_set_fast_binary): where it pays (>= 8M weights);
         everywhere=True: wherever legal (tests, measurements)"""
         check(self.lib.bm_rbm_set_fast_binary(self._h, (2 if everywhere else 1) if on else 0))
+
+    def set_centering(self, on, nu_v=0.01, nu_h=0.01):
+        """centred update (bm_rbm_set_centering): while on, every fused update entry of this handle takes it; the offsets are
+        the variables 'ov' / 'oh'"""
+        check(self.lib.bm_rbm_set_centering(self._h, int(bool(on)), float(nu_v), float(nu_h)))
 
     def set_from_device(self, name, darr):
         """variable <- dense DeviceArray, asynchronously on the engine's stream (bm_rbm_set_param_dev)"""
@@ -419,8 +424,10 @@ class DbmEngine(_PtCalls):
             return (self.M, self.V)
         if base in ('hb', 'dhb', 'q_means', 'mu_means', 'W_norm'):
             return (n[idx + 1],)
-        if base in ('vb', 'dvb', 'sigma'):
+        if base in ('vb', 'dvb', 'sigma', 'ov'):
             return (self.V,)
+        if base == 'oh':
+            return (n[idx + 1],)
         raise KeyError(name)
 
     def set(self, name, value):
@@ -471,6 +478,14 @@ class DbmEngine(_PtCalls):
         """opt-in exact-product bf16 x 3 mode (bm_dbm_set_fast_binary): AIS, and the particle sweeps where they gain (>= 8M
         weights in the bottom layer); everywhere=True: wherever legal (tests, measurements)"""
         check(self.lib.bm_dbm_set_fast_binary(self._h, (2 if everywhere else 1) if on else 0))
+
+    def set_centering(self, on, nu=0.01):
+        """centred update (bm_dbm_set_centering): while on, train_step and train_step_pt take it; nu: one sliding factor or
+        one per layer (v, h_1, ...); the offsets are the variables 'ov', 'oh', 'oh_1', ..."""
+        nus = [float(x) for x in nu] if hasattr(nu, '__iter__') else [float(nu)] * (self.L + 1)
+        if len(nus) != self.L + 1:
+            raise ValueError('centering: %d sliding factors for %d layers' % (len(nus), self.L + 1))
+        check(self.lib.bm_dbm_set_centering(self._h, int(bool(on)), (C.c_float * (self.L + 1))(*nus)))
 
     def set_ais_literal(self, on):
         """AIS log-weights accumulated in float32 in the reference graph's order (bm_dbm_set_ais_literal)"""
@@ -643,6 +658,9 @@ class DbmEngine64(DbmEngine):
 
     def sample_v_clamped(self, *a, **kw):
         raise NotImplementedError('conditional sampling has no float64 entry (bm_dbm64_* has no clamped sample_v)')
+
+    def set_centering(self, *a, **kw):
+        raise NotImplementedError('centering has no float64 entry (bm_dbm64_* has no centred update)')
 
     def _no_pt(self, *a, **kw):
         raise NotImplementedError('parallel tempering has no float64 entry (bm_dbm64_* has no pt_init / pt_sweep / pt_read / '

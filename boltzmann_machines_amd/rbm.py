@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _ffi
 from .base import EngineModel, is_attribute_name, run_on_engine
+from .centering import CenteredTraining
 from .engine import RbmEngine, RbmEngine64
 from .tempering import TemperedNegativePhase, resolve_ladder, run_tempered_sampler
 from .utils import epoch_iter, make_list_from, write_during_training
@@ -56,7 +57,7 @@ def clampable_only(f):
     return checked
 
 
-class BaseRBM(TemperedNegativePhase, EngineModel):
+class BaseRBM(CenteredTraining, TemperedNegativePhase, EngineModel):
     """Restricted Boltzmann machine trained with CD-k (reference base_rbm.py:14-94)."""
 
     _V_UNIT = _ffi.UNIT_BERNOULLI
@@ -202,6 +203,7 @@ class BaseRBM(TemperedNegativePhase, EngineModel):
                 from . import parallel
                 self._dp = parallel.DataParallelRBM(self._engine, self._rank, self._world, self.batch_size,
                                                     parallel.native_allreduce_on_engine_stream(self._engine, self._comm))
+            self._apply_centering()
         else:
             raise NotImplementedError("%s: dtype must be 'float32' or 'float64' (got %r)" % (self.__class__.__name__, self.dtype))
 
@@ -233,7 +235,9 @@ class BaseRBM(TemperedNegativePhase, EngineModel):
             self._engine.seed(seed)
 
     def _variables(self):
-        return {name: self._engine.get(name) for name, _ in self._VAR_SCOPES}
+        out = {name: self._engine.get(name) for name, _ in self._VAR_SCOPES}
+        out.update(self._centering_variables())       # (nothing unless centering is on)
+        return out
 
     def _scoped_variables(self):
         # the reference's variable names (base_rbm.py:271-327); `sigma` is a variable of the GaussianRBM only, created
@@ -246,8 +250,8 @@ class BaseRBM(TemperedNegativePhase, EngineModel):
         """checkpoint snapshot without stopping the stream (bm_rbm_stage): float32 engine only; BM355_STAGED_SAVE=0
         restores the host-side snapshot"""
         eng = self._engine
-        if not isinstance(eng, RbmEngine) or os.environ.get('BM355_STAGED_SAVE', '1') == '0':
-            return None
+        if not isinstance(eng, RbmEngine) or os.environ.get('BM355_STAGED_SAVE', '1') == '0' or self._centering is not None:
+            return None          # (the staged slots hold the reference's variables only: a centred model snapshots on the host)
         eng.stage(slot)
         names = [name for name, _ in self._VAR_SCOPES]
         return lambda: {name: eng.get_staged(slot, name) for name in names}
@@ -258,7 +262,8 @@ class BaseRBM(TemperedNegativePhase, EngineModel):
                    'sparsity_cost', 'sparsity_damping', 'dbm_first', 'dbm_last'}
         super(BaseRBM, self).set_params(**params)
         if self._engine is not None and isinstance(self._engine, (RbmEngine, RbmEngine64)) and rebuild & set(params):
-            self._pending_vars = self._variables()
+            self._pending_vars = {name: self._engine.get(name) for name, _ in self._VAR_SCOPES}
+            self._centering_detach()          # (the offsets wait on the host for the next engine: _apply_centering)
             self._engine.close()
             self._engine = None
         return self
@@ -377,6 +382,47 @@ class BaseRBM(TemperedNegativePhase, EngineModel):
         out = {m: (np.mean(r) if r else None) for m, r in results.items()}
         return (lambda: out) if defer else out
 
+    # ---- centred training (no counterpart in the reference) ---------------------
+    def _centering_sizes(self):
+        return [self.n_visible, self.n_hidden]
+
+    def _check_centering(self, what):
+        name = self._check_centering_common(what)
+        if self._V_UNIT != _ffi.UNIT_BERNOULLI:
+            raise NotImplementedError('%s: centering needs Bernoulli visible units (Gaussian visible units are not centred)' % name)
+        if self._H_UNIT != _ffi.UNIT_BERNOULLI:
+            raise NotImplementedError('%s: centering needs Bernoulli hidden units (Multinomial hidden units are not centred)' % name)
+        if self.dbm_first or self.dbm_last:
+            raise NotImplementedError('%s: centering is not defined for `dbm_first` / `dbm_last` models (one conditional doubled)' % name)
+        if self.dropout is not None:
+            raise NotImplementedError('%s: centering is not combined with dropout' % name)
+
+    def _engine_set_centering(self, on, nus):
+        self._engine.set_centering(on, nus[0], nus[1])
+
+    def set_centering(self, enabled=True, nu_v=0.01, nu_h=0.01, offset_v=None, offset_h=None):
+        """Centred updates in `fit` (the centering trick: Montavon & Mueller 2012; Melchior, Fischer & Wiskott 2016).
+
+        The weight gradient is taken between units minus running offsets, <(v - o_v)(h - o_h)^T>, and the bias gradients are
+        corrected accordingly; the model itself stays in the standard parameters W, vb, hb, so everything but the update is
+        unchanged.  Learning becomes invariant to flips of the data's coding.  Every update first moves the offsets,
+        o <- (1 - nu) o + nu * mean of the positive phase, with the sliding factors `nu_v`, `nu_h` in [0, 1].
+
+        offset_v, offset_h : the offsets to start from; None: at the first update of the next `fit(X)` the mean of X
+        (float64 sum, rounded to float32) for the visible layer and 0.5 for the hidden layer.
+        Works with both negative phases of `set_negative_phase`.  The offsets are optimiser state like the momentum buffers:
+        while centering is on they are written to model.npz (`centering_ov`, `centering_oh`, `centering_nu`) and
+        `load_model` re-enables the mode from them; params.json keeps the reference's schema.  BernoulliRBM in float32 only:
+        GaussianRBM, MultinomialRBM, float64, `dbm_first` / `dbm_last`, dropout and BM355_DATA_PARALLEL jobs raise
+        NotImplementedError.  Returns self."""
+        return self._set_centering(enabled, [nu_v, nu_h], [offset_v, offset_h])
+
+    @classmethod
+    def load_model(cls, model_path):
+        model = super(BaseRBM, cls).load_model(model_path)
+        model._centering_restore(model._pending_vars)
+        return model
+
     # ---- tempered negative phase (no counterpart in the reference; DESIGN.md 3.14) --------------
     _PT_MIN_CHAINS = 'batch_size'
 
@@ -472,6 +518,7 @@ class BaseRBM(TemperedNegativePhase, EngineModel):
 
     def _fit(self, X, X_val=None, *args, **kwargs):
         self._on_device()
+        self._centering_begin_fit(X)
         self._pt_fresh = True          # a tempered negative phase builds its ensemble at this call's first update
         if self._neg_phase is not None:
             self._check_tempered_fit()

@@ -603,6 +603,25 @@ int bm_dbm_set_ais_literal(bm_dbm *h, int32_t on);
  * reference's mean-field trip counts - the loop of dbm.py:449-452 at mf_tol = 1e-7 is decided in the last bits of the
  * means (784-512-1024: 5 - 6 sweeps per update with the literal form, 7 - 8 with the default). */
 int bm_dbm_set_sigmoid_literal(bm_dbm *h, int32_t on);
+/* ---- Centred training (Montavon & Mueller 2012; Melchior, Fischer & Wiskott 2016) -------------------
+ * The model stays in standard parameters (W, vb, hb); only the update changes.  With layers x_0 = v, x_1 .. x_L, offsets o_l
+ * (one vector per layer) and sliding factors nu_l, one update runs, in this order:
+ *   o_l  <- (1 - nu_l) o_l + nu_l colmean_pos(x_l)
+ *   g_l   = colsum_pos(x_l) / N - colsum_neg(x_l) / M                        (the plain bias gradient)
+ *   dW_l  = pos / N - neg / M - o_{l-1} g_l^T - g_{l-1} o_l^T                 (then l2, sparsity, momentum, lr, max-norm as ever)
+ *   a_lb  = (x_lb - o_l) . o_l                                               (one scalar per row and layer, both phases)
+ *   r_l   = (1/N) sum_pos (x_lb - o_l)(a_{l-1,b} + a_{l+1,b}) - (1/M) sum_neg (same);   bias gradient g_l - r_l
+ * which is the gradient of the centred parameterisation expressed in the standard one.  The mode is a property of the
+ * handle: while it is on, every fused update entry takes the centred update - bm_rbm_train_step, _metrics, _metrics_async,
+ * bm_rbm_train_epoch, bm_rbm_train_step_pt, bm_rbm_train_epoch_pt; bm_dbm_train_step, bm_dbm_train_step_pt.  Sampling,
+ * mean-field, AIS, tempering and the metrics are untouched.  With all offsets and sliding factors zero the update is the plain
+ * one, bit for bit.  The offsets are variables of bm_*_set_param / get_param: "ov", "oh" (RBM); "ov", "oh", "oh_1", ...
+ * (DBM); they are zero until set.  Sliding factors lie in [0, 1].
+ * Refused (the error names centering): switching it on for Gaussian visible units, Multinomial hidden units, dbm_first /
+ * dbm_last handles or handles with dropout; and, while it is on, the split and exchange paths - bm_*_grad_step,
+ * bm_*_apply_step, bm_*_exchange_apply_direct.  The float64 engines have no centred update. */
+int bm_rbm_set_centering(bm_rbm *h, int32_t on, float nu_v, float nu_h);
+int bm_dbm_set_centering(bm_dbm *h, int32_t on, const float *nu /* [n_layers + 1]: v, h_1, ...; read when on != 0 */);
 /* ---- float64 DBM path ----------------------------------------------------------------------
  * DBM(dtype='float64') (base/mixin.py:14-25; the DBM graph is built "all in model dtype", dbm.py:294-383): the fetch sites
  * of the float32 entry points above with every buffer, hyper-parameter and random draw in double, on the FP64 tile engine of
