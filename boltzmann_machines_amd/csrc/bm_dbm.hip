@@ -8,6 +8,7 @@
 #include "../../include/bm355.h"
 #include "bm_common.h"
 #include "bm_kernels.h"
+#include "bm_pass.h"
 #include "bm_pt.h"
 #include "bm_center.h"
 
@@ -184,41 +185,9 @@ static bool dbm_xm() {
     return on;
 }
 
-// ---- a layer pass as a value (layer_pass() describes it, issue() launches it): out = act(mult * (below.W_lo [+ above.W_hi^T]) + bmult * bias)
+// ---- a layer pass as a value (bm_pass.h: layer_pass() describes it, issue() launches it): out = act(mult * (below.W_lo [+ above.W_hi^T]) + bmult * bias)
 //   below [J][n_lo] (pitch ldb) with W_lo = W[lo] ([n_lo][I]);  above [J][n_hi] with Wt[lo+1] ([n_hi][I])
-struct LayerIn { const float *p; int ld; };
-static constexpr LayerIn NO_IN{nullptr, 0};
-static LayerIn in_of(const Mat &m) { return LayerIn{m.p, m.ld}; }
-// what a pass writes (either pointer may be null) and draws with
-struct LayerOut { int sample; float *means, *states; int ld; PhiloxKey key; int64_t row0; };
-// the layer's value: its sample, or - without sampling - its mean, written as `means` only
-static LayerOut value_out(int sample, float *p, int ld, const PhiloxKey &key, int64_t row0) {
-    return LayerOut{sample, sample ? nullptr : p, sample ? p : nullptr, ld, key, row0};
-}
 static LayerOut mean_out(const bm_dbm *h, float *p, int ld) { return LayerOut{0, p, nullptr, ld, dkey(h, 0, 0, h->seed, h->call), 0}; }
-
-struct LayerPass {
-    ActArgs a;
-    int layer;                        // hidden layer index, -1 = visible
-    const float *below, *above;       // the state matrices the segments read (fast-binary: their shadows)
-    // ---- optional parts of the request
-    LayerPass &raw() { a.kind = 2; return *this; }                       // the raw pre-activation mult * z (mean-field hoist)
-    // mean-field residual max |out - prev| into the atomic cell and / or the workgroups' slots
-    LayerPass &residual(const float *prev, unsigned *cell, float *slots) { a.prev = prev; a.maxdiff = cell; a.maxdiff_blk = slots; return *this; }
-    LayerPass &skip_if(const int *skip) { a.skip = skip; return *this; }             // device int != 0: the launch returns at once
-    // the first kernel of a sweep evaluates the loop control of the previous sweep from the slots it left
-    LayerPass &check(MfCtl *ctl, const float *slots, int n, float tol) { a.chk_ctl = ctl; a.chk_slots = slots; a.chk_n = n; a.chk_tol = tol; return *this; }
-    // row-reduction epilogues into slot partials of pitch ldp: softplus(beta_b .) - softplus(beta_a .), or softplus(beta_b .)
-    // alone (single); states . vec; z . mat
-    LayerPass &softplus_rows(float *out, int ldp, float beta_a, float beta_b, int single) {
-        a.rowacc = out; a.ld_part = ldp; a.beta_a = beta_a; a.beta_b = beta_b; a.rowacc_single = single;
-        return *this;
-    }
-    LayerPass &statedot_rows(float *out, int ldp, const float *vec) { a.rowdot_out = out; a.ld_part = ldp; a.dot_vec = vec; return *this; }
-    LayerPass &zdot_rows(float *out, int ldp, const Mat &mat) { a.rowacc = out; a.ld_part = ldp; a.dot_mat = mat.p; a.ld_dot = mat.ld; return *this; }
-    // conditional sampling: outputs with a non-zero mask entry hold `val` (both [J][I], pitch ld; ActArgs::clamp_mask)
-    LayerPass &clamp(const float *val, const float *mask, int ld) { a.clamp_val = val; a.clamp_mask = mask; a.ld_clamp = ld; return *this; }
-};
 // the clamp of a call's visible-layer passes (null mask: none)
 struct Clamp { const float *val, *mask; int ld; };
 
@@ -292,7 +261,7 @@ static void fast_substitute(bm_dbm *h, LayerPass &p) {
 
 // MultinomialLayer inside the stack (layers.py:54-70): the GEMM writes the logits mult*z + bmult*b, then one
 // wave per row does the softmax (activation = n_samples * softmax) and, when sampling, the n_samples
-// categorical draws (counts); same two kernels as the MultinomialRBM hidden layer (bm_rbm.hip launch_up)
+// categorical draws (counts); same two kernels as the MultinomialRBM hidden layer (bm_rbm.hip issue)
 static void issue_multinomial(bm_dbm *h, ActArgs a, int layer) {
     float *lg = a.means; int ldl = a.ldo;
     if (!lg) {                                 // sampled sweep: the means are not kept, they pass through a row store
@@ -316,9 +285,10 @@ static void issue_multinomial(bm_dbm *h, ActArgs a, int layer) {
 
 // everything that is about launching a pass, on h->cur
 static void issue(bm_dbm *h, LayerPass p) {
-    if (h->cur == h->stream2 && h->pcd_geo_now) p.a.geo_hint = h->pcd_geo_now;   // a pass that runs beside the mean-field loop
+    const bool tempered = p.a.row_mult != nullptr;      // a plain fp32 launch, always (the RT launcher has no other flavour)
+    if (h->cur == h->stream2 && h->pcd_geo_now && !tempered) p.a.geo_hint = h->pcd_geo_now;   // a pass that runs beside the mean-field loop
     const bool act = p.a.kind != 2, multinomial = h->multinomial(p.layer);
-    if (h->fast_now && act && !multinomial && !p.a.clamp_mask) fast_substitute(h, p);      // (a clamped pass is fp32, always)
+    if (h->fast_now && act && !multinomial && !p.a.clamp_mask && !tempered) fast_substitute(h, p);      // (a clamped pass is fp32, always)
     if (act && multinomial) issue_multinomial(h, p.a, p.layer);
     else launch_act(p.a, h->cur);
 }
@@ -1284,10 +1254,9 @@ static void pt_pass(bm_dbm *h, int layer, int t) {
     const PhiloxKey key = dkey(h, layer < 0 ? SITE_DBM_V : SITE_DBM_H + layer, t, h->seed, h->call);
     LayerPass p = layer_pass(h, layer, e.nrows(), below, above, 1.f, 1.f,
                              value_out(1, out.x.p, out.x.ld, key, e.row0()));   // (mult: not read)
-    if (layer == 0) { p.a.rowen_out = out.part.p; p.a.ld_part = e.rows; }
+    if (layer == 0) p.energy_rows(out.part.p, e.rows);
     else p.statedot_rows(out.part.p, e.rows, layer == 1 ? h->hb[1].p : h->vb.p);
-    p.a.row_mult = e.mult.p;
-    launch_act(p.a, h->stream);
+    issue(h, p.row_tempered(e.mult.p));     // (h->cur is the main stream here: only enqueue_particles_stream2 moves it, and back)
 }
 
 // step t of a tempered call, in gibbs_sweep's order with every layer sampled: h1 from (v, OLD h2); the swap of the parity of the

@@ -8,6 +8,7 @@
 #include "bm_common.h"
 #include "bm_kernels.h"
 #include "bm_chain.h"
+#include "bm_pass.h"
 #include "bm_pt.h"
 #include "bm_center.h"
 
@@ -90,7 +91,7 @@ struct bm_rbm {
     uint64_t seed = 0;
     uint32_t call = 0;
     int64_t row0 = 0;
-    // input of the last run_chain() (after /sigma and dropout) and its pitch
+    // input of the last run_chain() (after prep_input: /sigma and dropout) and its pitch
     const float *Xin = nullptr;
     int Xin_ld = 0;
     bool hm_is_neg = false;    // the last run_chain() wrote -h_k (hneg) instead of h_k (hm)
@@ -135,7 +136,7 @@ struct bm_rbm {
     struct Rec { int cls; Event a, b; };
     std::vector<Rec> recs;
     size_t grad_tail() const { return (size_t)V * W.ld; }
-    // a run of dependent propagation passes recorded by launch_up / launch_down and issued as ONE launch (bm_chain.h)
+    // a run of dependent propagation passes recorded by issue() and launched as ONE launch (bm_chain.h)
     ChainState chain;
 };
 
@@ -170,18 +171,7 @@ static PhiloxKey make_key(const bm_rbm *h, uint32_t site, int t) {
     return k;
 }
 
-// a propagation pass: launched now, or recorded while a chained run is open (chain_begin .. chain_end)
-static void act_pass(bm_rbm *h, const ActArgs &a, const Operand *alt_p = nullptr) {
-    if (h->chain.on) {
-        h->chain.rec.push_back(a);
-        h->chain.alt_p.resize(h->chain.rec.size(), Operand{nullptr, 0, 0, 0});
-        if (alt_p) h->chain.alt_p.back() = *alt_p;
-    } else if (alt_p) {
-        ActArgs b = a;
-        b.P1 = *alt_p; b.p_xm = 1;
-        launch_act(b, h->stream);
-    } else launch_act(a, h->stream);
-}
+// a chained run (bm_chain.h): the passes issue() sees between chain_begin and chain_end are recorded and launched as one
 static void chain_begin(bm_rbm *h) {
     // per-class event timing, Multinomial hidden units (a softmax launch between the passes) and the fast-binary sweep
     // keep their per-pass launches
@@ -202,135 +192,149 @@ static void ensure_wt(bm_rbm *h) {
     h->wt_valid = true;
 }
 
-// E[h|v] (+ sample): base_rbm.py:339-351.  v [B][V] pitch ldv
-static void launch_up(bm_rbm *h, const float *v, int ldv, int B, float *means, float *states, int ldo,
-                      int sample, uint32_t site, int t, float *negmeans = nullptr, bool fe = false) {
-    ProfScope _ps(h, KC_UP);
-    ActArgs a;
-    memset(&a, 0, sizeof(a));
-    a.P1 = make_operand(h->W.p, h->W.ld, h->H);   // W[k=v][i=h], KM
-    a.Q1 = make_operand(v, ldv, B);               // v[j=b][k=v], XM
-    a.K1 = h->V;
-    a.I = h->H; a.J = B;
-    a.bias = h->hb.p; a.sigma = nullptr;
-    a.mult = 1.0f + (h->cfg.dbm_first ? 1.0f : 0.0f);
-    a.bmult = a.mult;
-    a.kind = BM_UNIT_BERNOULLI;
-    a.sample = states ? sample : 0;               // no consumer of the states: no draw
-    a.means = means; a.states = states; a.negmeans = negmeans; a.ldo = ldo;
-    a.key = make_key(h, site, t);
-    a.row0 = h->row0;
-    if (fe) {                                    // metric fetch: the free-energy row sums from this pass's pre-activations
-        const int nslot = (h->H + 15) / 16, rm = (nslot + 3) & ~3;
-        a.rowacc = h->fe_part.p; a.rowacc_single = 1; a.beta_b = 1.f; a.ld_part = h->maxB; a.fe_rm = rm;
-        a.fe_rowacc2 = h->fe_part.p + (size_t)rm * h->maxB;
-        // the flip columns straight from their Philox stream and the zeroing of the six accumulators ride on this pass: the
-        // fused fetch has no prep launch
-        a.fe_flip = FE_FLIP_FROM_KEY; a.fe_key = make_key(h, SITE_PLL, 0); a.fe_zero = h->scal.p;
-        a.fe_x = v; a.fe_ldx = ldv; a.fe_w = h->W.p; a.fe_ldw = h->W.ld;
+// ---- a propagation pass as a value (bm_pass.h): rbm_pass() describes it, issue() launches it.  The RBM is the one-layer stack:
+//   up   (layer 0):  E[h|v] (+ sample), base_rbm.py:339-351, from in = v [J][V]
+//   down (layer -1): E[v|h] (+ sample), base_rbm.py:353-365, from in = h [J][H]
+// Queues nothing, allocates nothing.  mult multiplies z and the bias: the handle's own (below) or a temperature (AIS).
+static LayerPass rbm_pass(const bm_rbm *h, bool up, int J, LayerIn in, const LayerOut &out, float mult) {
+    LayerPass p;
+    ActArgs &a = p.a;
+    memset(&a, 0, sizeof(ActArgs));
+    p.layer = up ? 0 : -1; p.below = up ? in.p : nullptr; p.above = up ? nullptr : in.p;
+    if (up) {
+        a.P1 = make_operand(h->W.p, h->W.ld, h->H);   // W[k=v][i=h], k-major (issue() reads W^T x-major where the handle keeps it)
+        a.K1 = h->V; a.I = h->H;
+        a.bias = h->hb.p; a.kind = BM_UNIT_BERNOULLI;  // (Multinomial hidden units: issue() turns the pass into the logits pair)
+    } else {
+        a.P1 = make_operand(h->W.p, h->W.ld, h->V);   // W[i=v][k=h], x-major P
+        a.p_xm = 1;
+        a.K1 = h->H; a.I = h->V;
+        a.bias = h->vb.p; a.sigma = h->sigma.p; a.kind = h->cfg.v_unit;
     }
-    if (h->fast_now && v == h->vs.p) {           // fast-binary: W^T planes x the bf16 shadow of the visible bitmap
-        a.b3.P1 = Bf3Operand{h->W3t.p, h->W3t.plane_stride(), h->W3t.ld, h->H};
-        a.b3.Q1 = Bf3Operand{h->vs16.p, 0, h->vs16.ld, B};
-        a.b3.K1 = h->vs16.ld;
-        if (states == h->hs.p) { a.states16 = h->hs16.p; a.ld16 = h->hs16.ld; }
-    }
-    if (h->multinomial()) {
-        // MultinomialLayer (layers.py:54-70): logits from the GEMM, then one wave per row for the
-        // softmax (activation) and the multinomial counts (sample)
-        if (!means) { means = h->hm.p; ldo = h->hm.ld; }     // pure sampling sweep: hm is the scratch row store
-        a.kind = 3; a.sample = 0; a.means = means; a.ldo = ldo; a.states = nullptr; a.negmeans = nullptr;
-        launch_act(a, h->stream);
-        SmArgs m;
-        memset(&m, 0, sizeof(m));
-        m.L = means; m.ld = ldo; m.I = h->H; m.J = B; m.M = h->cfg.n_samples; m.sample = sample;
-        m.states = states; m.negmeans = negmeans; m.key = a.key; m.row0 = h->row0;
-        hipLaunchKernelGGL(softmax_multinomial_kernel, dim3(B), dim3(64), 2 * (size_t)h->H * sizeof(float), h->stream, m);
-        return;
-    }
-    if (h->use_wt && h->wt_valid && !(h->fast_now && v == h->vs.p)) {
-        const Operand wt = make_operand(h->Wt.p, h->Wt.ld, h->H);      // W^T[i=h][k=v], x-major: the per-pass launch's P
-        act_pass(h, a, &wt);
-    } else act_pass(h, a);
+    a.Q1 = make_operand(in.p, in.ld, J);              // in[j=b][k], x-major
+    a.J = J;
+    a.mult = mult; a.bmult = mult;
+    a.sample = out.states ? out.sample : 0;           // no consumer of the states: no draw
+    a.means = out.means; a.states = out.states; a.ldo = out.ld; a.key = out.key; a.row0 = out.row0;
+    return p;
+}
+// the handle's own conditionals: the doubled pre-activation of a dbm_first (up) / dbm_last (down) layer
+static LayerPass rbm_pass(const bm_rbm *h, bool up, int J, LayerIn in, const LayerOut &out) {
+    return rbm_pass(h, up, J, in, out, 1.0f + ((up ? h->cfg.dbm_first : h->cfg.dbm_last) ? 1.0f : 0.0f));
+}
+// outputs drawn at the handle's seed, call counter and row offset
+static LayerOut rbm_out(const bm_rbm *h, int sample, float *means, float *states, int ld, uint32_t site, int t) {
+    return LayerOut{sample, means, states, ld, make_key(h, site, t), h->row0};
 }
 
-// E[v|h] (+ sample): base_rbm.py:353-365.  hs [B][H] pitch ldh
-// clamp_mask / clamp_val (dense [B][V], or null): outputs with a non-zero mask entry are held at clamp_val (ActArgs::clamp_mask)
-static void launch_down(bm_rbm *h, const float *hs, int ldh, int B, float *means, float *states, int ldo,
-                        int sample, uint32_t site, int t, const float *clamp_val = nullptr, const float *clamp_mask = nullptr) {
-    ProfScope _ps(h, KC_DOWN);
-    ActArgs a;
-    memset(&a, 0, sizeof(a));
-    a.P1 = make_operand(h->W.p, h->W.ld, h->V);    // W[i=v][k=h], x-major P
-    a.p_xm = 1;
-    a.Q1 = make_operand(hs, ldh, B);               // h[j=b][k=h], XM
-    a.K1 = h->H;
-    a.I = h->V; a.J = B;
-    a.bias = h->vb.p; a.sigma = h->sigma.p;
-    a.mult = 1.0f + (h->cfg.dbm_last ? 1.0f : 0.0f);
-    a.bmult = a.mult;
-    a.kind = h->cfg.v_unit;
-    a.sample = sample;
-    a.means = means; a.states = states; a.ldo = ldo;
-    a.key = make_key(h, site, t);
-    a.row0 = h->row0;
-    a.clamp_val = clamp_val; a.clamp_mask = clamp_mask; a.ld_clamp = h->V;
-    if (h->fast_now && hs == h->hs.p) {          // fast-binary: W planes x the bf16 shadow of the hidden bitmap
-        a.b3.P1 = Bf3Operand{h->W3.p, h->W3.plane_stride(), h->W3.ld, h->V};
-        a.b3.Q1 = Bf3Operand{h->hs16.p, 0, h->hs16.ld, B};
-        a.b3.K1 = h->hs16.ld;
-        if (states == h->vs.p) { a.states16 = h->vs16.p; a.ld16 = h->vs16.ld; }
+// everything that is about launching a pass, on h->stream: the one place that launches a propagation pass or records one
+// into an open chained run
+static void issue(bm_rbm *h, LayerPass p) {
+    const bool up = p.layer == 0;
+    ProfScope _ps(h, up ? KC_UP : KC_DOWN);
+    ActArgs &a = p.a;
+    // fast-binary: the bf16 planes of W^T (up) / W (down) x the bf16 shadow of the input bitmap, when that is the workspace
+    // that carries one; the shadow of the output when the states go to the other workspace
+    const bool fast = h->fast_now && (up ? p.below == h->vs.p : p.above == h->hs.p);
+    if (fast) {
+        const Mat16 &w3 = up ? h->W3t : h->W3, &in16 = up ? h->vs16 : h->hs16, &out16 = up ? h->hs16 : h->vs16;
+        a.b3.P1 = Bf3Operand{w3.p, w3.plane_stride(), w3.ld, a.I};
+        a.b3.Q1 = Bf3Operand{in16.p, 0, in16.ld, a.J};
+        a.b3.K1 = in16.ld;
+        if (a.states == (up ? h->hs.p : h->vs.p)) { a.states16 = out16.p; a.ld16 = out16.ld; }
     }
-    act_pass(h, a);
+    if (up && h->multinomial()) {
+        // MultinomialLayer (layers.py:54-70): logits from the GEMM, then one wave per row for the
+        // softmax (activation) and the multinomial counts (sample)
+        if (!a.means) { a.means = h->hm.p; a.ldo = h->hm.ld; }     // pure sampling sweep: hm is the scratch row store
+        SmArgs m;
+        memset(&m, 0, sizeof(m));
+        m.L = a.means; m.ld = a.ldo; m.I = a.I; m.J = a.J; m.M = h->cfg.n_samples; m.sample = a.sample;
+        m.states = a.states; m.negmeans = a.negmeans; m.key = a.key; m.row0 = a.row0;
+        a.kind = 3; a.sample = 0; a.states = nullptr; a.negmeans = nullptr;
+        launch_act(a, h->stream);
+        hipLaunchKernelGGL(softmax_multinomial_kernel, dim3(a.J), dim3(64), 2 * (size_t)h->H * sizeof(float), h->stream, m);
+        return;
+    }
+    // the prop-up's weights x-major: W^T where the handle keeps a valid one (ensure_wt), never beside the bf16 planes
+    const bool xm = up && h->use_wt && h->wt_valid && !fast;
+    const Operand wt = xm ? make_operand(h->Wt.p, h->Wt.ld, h->H) : Operand{nullptr, 0, 0, 0};     // W^T[i=h][k=v]
+    if (h->chain.on) {          // a chained run is open: recorded with W k-major, W^T as the per-pass launch's alternative
+        h->chain.rec.push_back(a);
+        h->chain.alt_p.push_back(wt);
+        return;
+    }
+    if (xm) { a.P1 = wt; a.p_xm = 1; }
+    launch_act(a, h->stream);
+}
+
+// Gaussian visibles: X / sigma (rbm.py:107); then dropout (base_rbm.py:417-418).  *Xin / *ldx: what the passes read
+static void prep_input(bm_rbm *h, const float *X_dev, int B, const float **Xin, int *ldx, bool *dropped) {
+    *Xin = X_dev; *ldx = h->V; *dropped = false;
+    if (h->cfg.v_unit == BM_UNIT_GAUSSIAN) {
+        hipLaunchKernelGGL(div_cols_kernel, dim3(256), dim3(256), 0, h->stream, *Xin, *ldx, h->sigma.p, h->Xs.p,
+                           h->Xs.ld, B, h->V);
+        *Xin = h->Xs.p; *ldx = h->Xs.ld;
+    }
+    if (h->cfg.dropout >= 0.f) {
+        hipLaunchKernelGGL(dropout_kernel, dim3(256), dim3(256), 0, h->stream, *Xin, *ldx, h->Xd.p, h->Xd.ld, B, h->V,
+                           h->cfg.dropout, make_key(h, SITE_DROPOUT, 0),
+                           (unsigned long long)h->row0 * (unsigned long long)h->V);
+        *Xin = h->Xd.p; *ldx = h->Xd.ld;
+        *dropped = true;
+    }
 }
 
 // input preprocessing + h0 + k Gibbs steps (base_rbm.py:417-426). Leaves
 // h0m/h0s, vm/vs (last step), hm/hs (last step) and Xin in the handle.
-// If hm_out != null the last step's h_means are written there (dense, pitch H).
-// need_vm: the last step's visible MEANS are wanted (msre metric); a plain update only consumes the
-// visible states, and nothing consumes the hidden STATES of the last step: those stores (and their
-// share of the kernel-boundary L2 writeback) are skipped.
+struct ChainOpts {
+    // the last step's visible MEANS are wanted (msre metric); a plain update only consumes the
+    // visible states, and nothing consumes the hidden STATES of the last step: those stores (and their
+    // share of the kernel-boundary L2 writeback) are skipped.
+    bool need_vm = true;
+    bool split_step = false;      // the data-parallel step: W^T is not rebuilt (ensure_wt)
+    bool fetch = false;           // a metrics iteration (metrics_from_chain follows)
+    float *hm_out = nullptr;      // the last step's h_means are written there (dense, pitch H)
+};
 static bool metrics_fused_ok(const bm_rbm *h);
 static void metrics_prep(bm_rbm *h, int B);
-static int run_chain(bm_rbm *h, const float *X_dev, int B, int k, float *hm_out, bool need_vm = true, bool for_update = false,
-                     bool split_step = false, bool fetch = false) {
+static int run_chain(bm_rbm *h, const float *X_dev, int B, int k, const ChainOpts &o) {
     BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
     BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", k);
-    if (!split_step) ensure_wt(h);
-    const float *Xin = X_dev;
-    int ldx = h->V;
-    if (h->cfg.v_unit == BM_UNIT_GAUSSIAN) {   // rbm.py:107
-        hipLaunchKernelGGL(div_cols_kernel, dim3(256), dim3(256), 0, h->stream, Xin, ldx, h->sigma.p, h->Xs.p,
-                           h->Xs.ld, B, h->V);
-        Xin = h->Xs.p; ldx = h->Xs.ld;
-    }
-    if (h->cfg.dropout >= 0.f) {               // base_rbm.py:417-418
-        hipLaunchKernelGGL(dropout_kernel, dim3(256), dim3(256), 0, h->stream, Xin, ldx, h->Xd.p, h->Xd.ld, B, h->V,
-                           h->cfg.dropout, make_key(h, SITE_DROPOUT, 0),
-                           (unsigned long long)h->row0 * (unsigned long long)h->V);
-        Xin = h->Xd.p; ldx = h->Xd.ld;
-    }
+    if (!o.split_step) ensure_wt(h);
+    const float *Xin;
+    int ldx;
+    bool dropped;
+    prep_input(h, X_dev, B, &Xin, &ldx, &dropped);
     h->Xin = Xin; h->Xin_ld = ldx;
     // a metrics iteration: the flip columns and the zeroed accumulators first, then the h0 pass adds the free-energy row
     // sums of x and of its PLL partner from its own pre-activations (ActArgs::fe_flip) - no GEMM of their own
-    const bool fe = fetch && metrics_fused_ok(h);
-    if (fe && !h->fe_part.p) BM_TRY(h->fe_part.alloc((size_t)2 * ((((h->H + 15) / 16) + 3) & ~3) * h->maxB));
+    const bool fe = o.fetch && metrics_fused_ok(h);
+    const int fe_rm = (((h->H + 15) / 16) + 3) & ~3;
+    if (fe && !h->fe_part.p) BM_TRY(h->fe_part.alloc((size_t)2 * fe_rm * h->maxB));
     h->fe_in_chain = fe;
-    if (fetch && !fe) metrics_prep(h, B);
+    if (o.fetch && !fe) metrics_prep(h, B);
     chain_begin(h);               // h0 and the k Gibbs steps: one launch where the shape allows it (bm_chain.h)
-    launch_up(h, Xin, ldx, B, h->h0m.p, h->h0s.p, h->h0m.ld, 1, SITE_H0, 0, nullptr, fe);      // :421-422
-    const float *hstate = h->cfg.sample_h_states ? h->h0s.p : h->h0m.p;           // :423
+    LayerPass h0 = rbm_pass(h, true, B, LayerIn{Xin, ldx}, rbm_out(h, 1, h->h0m.p, h->h0s.p, h->h0m.ld, SITE_H0, 0));     // :421-422
+    // the flip columns straight from their Philox stream and the zeroing of the six accumulators ride on this pass: the
+    // fused fetch has no prep launch
+    if (fe) h0.free_energy_fetch(h->fe_part.p, fe_rm, h->maxB, make_key(h, SITE_PLL, 0), h->scal.p, Xin, ldx, h->W.p, h->W.ld);
+    issue(h, h0);
+    LayerIn hstate = in_of(h->cfg.sample_h_states ? h->h0s : h->h0m);             // :423
     for (int t = 0; t < k; ++t) {                                                 // :367-378
         const bool last = t == k - 1;
-        launch_down(h, hstate, h->hs.ld, B, (need_vm && last) ? h->vm.p : nullptr, h->vs.p, h->vm.ld,
-                    h->cfg.sample_v_states, SITE_V, t);
-        const bool last_out = hm_out && last;
+        issue(h, rbm_pass(h, false, B, hstate, rbm_out(h, h->cfg.sample_v_states, (o.need_vm && last) ? h->vm.p : nullptr, h->vs.p,
+                                                       h->vs.ld, SITE_V, t)));
+        const bool last_out = o.hm_out && last;
         // plain update, last step: only -h_k is consumed (outer products and column sums)
-        const bool neg_only = last && !hm_out && !need_vm && !h->multinomial();
+        const bool neg_only = last && !o.hm_out && !o.need_vm && !h->multinomial();
         h->hm_is_neg = neg_only;
-        launch_up(h, h->vs.p, h->vs.ld, B, last_out ? hm_out : (neg_only ? nullptr : h->hm.p), last ? nullptr : h->hs.p,
-                  last_out ? h->H : h->hm.ld, h->cfg.sample_h_states, SITE_H, t, (!hm_out && last) ? h->hneg.p : nullptr);
-        hstate = h->hs.p;
+        LayerPass up = rbm_pass(h, true, B, in_of(h->vs),
+                                rbm_out(h, h->cfg.sample_h_states, last_out ? o.hm_out : (neg_only ? nullptr : h->hm.p),
+                                        last ? nullptr : h->hs.p, last_out ? h->H : h->hm.ld, SITE_H, t));
+        if (!o.hm_out && last) up.negmeans_out(h->hneg.p);
+        issue(h, up);
+        hstate = in_of(h->hs);
     }
     BM_TRY(chain_end(h));
     return 0;
@@ -354,11 +358,7 @@ static int fill_bias_fused(bm_rbm *h, int B, float lr, float mom, RbmBiasFusedAr
     if (h->hm_is_neg) { a.hm = h->hneg.p; a.ldh = h->hneg.ld; a.hm_negated = 1; }
     else              { a.hm = h->hm.p; a.ldh = h->hm.ld; }
     a.raw_tail = h->grad.p + h->grad_tail();
-    RbmBiasArgs &b = a.u;
-    b.vb = h->vb.p; b.dvb = h->dvb.p; b.hb = h->hb.p; b.dhb = h->dhb.p; b.q = h->q.p; b.pen = h->pen.p;
-    b.V = h->V; b.H = h->H;
-    b.N = (float)B; b.lr = lr; b.mom = mom;
-    b.damping = h->cfg.sparsity_damping; b.cost = h->cfg.sparsity_cost; b.target = h->cfg.sparsity_target;
+    fill_bias(h, (float)B, lr, mom, a.u);     // (sv / sh / sq are not read: the kernel forms the sums itself, into raw_tail)
     return (h->V + 63) / 64 + (h->H + 63) / 64;
 }
 
@@ -621,87 +621,40 @@ static PhiloxKey ais_key(uint64_t seed, uint32_t site, int t, uint32_t step) {
     return k;
 }
 
-// the weights as the prop-up's P operand: W^T x-major where the handle keeps it, else W k-major (launch_up)
-static void up_weights(const bm_rbm *h, ActArgs &a) {
-    if (h->use_wt && h->wt_valid) { a.P1 = make_operand(h->Wt.p, h->Wt.ld, h->H); a.p_xm = 1; }
-    else a.P1 = make_operand(h->W.p, h->W.ld, h->H);
-}
-
 // h ~ Ber(sigmoid(beta z)), z = v W + hb, from the chain state av into ah; score: the same pass leaves the slot partials of
 // sum_j softplus(beta z_j) - softplus(beta_a z_j) in apart_h.  sample = 0: the score alone (the last beta)
 static void ais_up(bm_rbm *h, int R, float beta, int sample, const PhiloxKey &key, int64_t chain0, bool score, float beta_a) {
-    ActArgs a;
-    memset(&a, 0, sizeof(a));
-    up_weights(h, a);
-    a.Q1 = make_operand(h->av.p, h->av.ld, R);
-    a.K1 = h->V; a.I = h->H; a.J = R;
-    a.bias = h->hb.p; a.mult = beta; a.bmult = beta;
-    a.kind = BM_UNIT_BERNOULLI;
-    a.sample = sample; a.states = sample ? h->ah.p : nullptr; a.ldo = h->ah.ld;
-    a.key = key; a.row0 = chain0;
-    if (score) { a.rowacc = h->apart_h.p; a.ld_part = h->ais_rows; a.beta_a = beta_a; a.beta_b = beta; }
-    launch_act(a, h->stream);
+    LayerPass p = rbm_pass(h, true, R, in_of(h->av), LayerOut{sample, nullptr, sample ? h->ah.p : nullptr, h->ah.ld, key, chain0}, beta);
+    if (score) p.softplus_rows(h->apart_h.p, h->ais_rows, beta_a, beta, 0);
+    issue(h, p);
 }
 // v ~ Ber(sigmoid(beta h W^T + a + beta (vb - a))) from ah into av, the mixed bias from row `kbeta` of the table; dot: the pass
 // leaves the slot partials of v.(vb - a) in apart_v for the next score
 static void ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &key, int64_t chain0, bool dot) {
-    ActArgs a;
-    memset(&a, 0, sizeof(a));
-    a.P1 = make_operand(h->W.p, h->W.ld, h->V); a.p_xm = 1;
-    a.Q1 = make_operand(h->ah.p, h->ah.ld, R);
-    a.K1 = h->H; a.I = h->V; a.J = R;
-    a.bias = h->atable.p + (size_t)kbeta * h->V; a.mult = beta; a.bmult = 1.0f;
-    a.kind = BM_UNIT_BERNOULLI;
-    a.sample = 1; a.states = h->av.p; a.ldo = h->av.ld;
-    a.key = key; a.row0 = chain0;
-    if (dot) { a.rowdot_out = h->apart_v.p; a.ld_part = h->ais_rows; a.dot_vec = h->adot.p; }
-    launch_act(a, h->stream);
+    LayerPass p = rbm_pass(h, false, R, in_of(h->ah), LayerOut{1, nullptr, h->av.p, h->av.ld, key, chain0}, beta)
+                      .bias(h->atable.p + (size_t)kbeta * h->V, 1.0f);
+    if (dot) p.statedot_rows(h->apart_v.p, h->ais_rows, h->adot.p);
+    issue(h, p);
 }
 
 // ---- parallel tempering (bm355.h: bm_rbm_pt_init / _sweep / _read)
 
 // (the ensemble, its start, the replica exchange, the rescore and the gather: bm_pt.h, shared with bm_dbm_pt_*)
 
-// one row-tempered pass of the ensemble (the RT flavour of act_kernel): up = h ~ Ber(sigmoid(beta_row (vW + hb))) from pt.v into
-// pt.h1, leaving the slot partials of h.(vW + hb); down = v ~ Ber(sigmoid(beta_row (hW^T + vb))) from pt.h1 into pt.v, leaving those
-// of v.vb
-// sel_rows > 0 (down only): the beta = 1 row of every chain c < sel_rows is also left in vs[c] (ActArgs::sel_out)
-static void pt_pass(bm_rbm *h, bool up, const PhiloxKey &key, int sel_rows = 0) {
+// step t of a tempered call: the RT prop-up, the swap of the parity of the global step number, the RT prop-down.  The passes are
+// row-tempered (the RT flavour of act_kernel): up = h ~ Ber(sigmoid(beta_row (vW + hb))) from pt.v into pt.h1, leaving the slot
+// partials of h.(vW + hb); down = v ~ Ber(sigmoid(beta_row (hW^T + vb))) from pt.h1 into pt.v, leaving those of v.vb
+// sel_rows > 0: the prop-down also leaves the beta = 1 row of every chain c < sel_rows in vs[c] (ActArgs::sel_out)
+static void pt_step(bm_rbm *h, int t, int sel_rows = 0) {
     PtEnsemble &e = h->pt;
     const int rows = e.nrows();
-    ActArgs a;
-    memset(&a, 0, sizeof(a));
-    if (up) {
-        up_weights(h, a);
-        a.Q1 = make_operand(e.v.x.p, e.v.x.ld, rows);
-        a.K1 = h->V; a.I = h->H; a.bias = h->hb.p;
-        a.states = e.h1.x.p; a.ldo = e.h1.x.ld;
-        a.rowen_out = e.h1.part.p;
-    } else {
-        a.P1 = make_operand(h->W.p, h->W.ld, h->V); a.p_xm = 1;
-        a.Q1 = make_operand(e.h1.x.p, e.h1.x.ld, rows);
-        a.K1 = h->H; a.I = h->V; a.bias = h->vb.p;
-        a.states = e.v.x.p; a.ldo = e.v.x.ld;
-        a.rowdot_out = e.v.part.p; a.dot_vec = h->vb.p;
-    }
-    a.J = rows;
-    a.mult = 1.0f; a.bmult = 1.0f;                // (not read: row_mult replaces them)
-    a.row_mult = e.mult.p;
-    a.ld_part = e.rows;
-    a.kind = BM_UNIT_BERNOULLI;
-    a.sample = 1;
-    a.key = key;
-    a.row0 = e.row0();
-    if (sel_rows > 0 && !up) { a.sel_out = h->vs.p; a.sel_ld = h->vs.ld; a.sel_R = e.R; a.sel_rows = sel_rows; }
-    launch_act(a, h->stream);
-}
-
-// step t of a tempered call: the RT prop-up, the swap of the parity of the global step number, the RT prop-down (which hands the
-// beta = 1 rows of the chains [0, sel_rows) over to vs, if asked)
-static void pt_step(bm_rbm *h, int t, int sel_rows = 0) {
-    pt_pass(h, true, make_key(h, SITE_H, t));
+    issue(h, rbm_pass(h, true, rows, in_of(e.v.x), value_out(1, e.h1.x.p, e.h1.x.ld, make_key(h, SITE_H, t), e.row0()))   // (mult: not read)
+                 .energy_rows(e.h1.part.p, e.rows).row_tempered(e.mult.p));
     pt_launch_swap(h->pt, h->stream, t, make_key(h, SITE_PT_SWAP, t));
-    pt_pass(h, false, make_key(h, SITE_V, t), sel_rows);
+    LayerPass down = rbm_pass(h, false, rows, in_of(e.h1.x), value_out(1, e.v.x.p, e.v.x.ld, make_key(h, SITE_V, t), e.row0()))
+                         .statedot_rows(e.v.part.p, e.rows, h->vb.p).row_tempered(e.mult.p);
+    if (sel_rows > 0) down.select_rows(h->vs.p, h->vs.ld, e.R, sel_rows);
+    issue(h, down);
 }
 
 extern "C" {
@@ -1037,7 +990,9 @@ int bm_rbm_set_row_offset(bm_rbm *h, int64_t row0) { h->row0 = row0; return 0; }
 
 int bm_rbm_train_step(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
     BM_TRY(check_dw(h, "bm_rbm_train_step"));
-    BM_TRY(run_chain(h, X_dev, B, k, nullptr, false, true));
+    ChainOpts o;
+    o.need_vm = false;
+    BM_TRY(run_chain(h, X_dev, B, k, o));
     launch_update_fused(h, B, lr, mom);
     h->call++;
     BM_HIP(hipGetLastError());
@@ -1047,7 +1002,9 @@ int bm_rbm_train_step(bm_rbm *h, const float *X_dev, int32_t B, float lr, float 
 int bm_rbm_train_step_metrics(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k,
                               float *out4) {
     BM_TRY(check_dw(h, "bm_rbm_train_step_metrics"));
-    BM_TRY(run_chain(h, X_dev, B, k, nullptr, true, false, false, true));
+    ChainOpts o;
+    o.fetch = true;
+    BM_TRY(run_chain(h, X_dev, B, k, o));
     BM_TRY(metrics_from_chain(h, B, out4));
     launch_update_fused(h, B, lr, mom);
     h->call++;
@@ -1071,7 +1028,9 @@ int bm_rbm_train_step_metrics_async(bm_rbm *h, const float *X_dev, int32_t B, fl
     }
     BM_CHECK(h->mring_n < bm_rbm::MRING, "%d metric fetches are pending: call bm_rbm_collect_metrics", h->mring_n);
     BM_TRY(check_dw(h, "bm_rbm_train_step_metrics_async"));
-    BM_TRY(run_chain(h, X_dev, B, k, nullptr, true, false, false, true));
+    ChainOpts o;
+    o.fetch = true;
+    BM_TRY(run_chain(h, X_dev, B, k, o));
     BM_TRY(metrics_from_chain(h, B, nullptr));
     hipLaunchKernelGGL(scal_to_host_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)h->scal.p,
                        h->mring_dev + (size_t)h->mring_n * 6);
@@ -1117,7 +1076,9 @@ int bm_rbm_train_epoch(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, 
 
 int bm_rbm_grad_step(bm_rbm *h, const float *X_dev, int32_t B, int32_t k) {
     BM_CHECK(!h->cen_on, "bm_rbm_grad_step: the split step has no centred form; switch centering off (bm_rbm_set_centering)");
-    BM_TRY(run_chain(h, X_dev, B, k, nullptr, false, false, true));
+    ChainOpts o;
+    o.need_vm = false; o.split_step = true;
+    BM_TRY(run_chain(h, X_dev, B, k, o));
     rbm_grad(h, B, 0, (float)B, 0.f, 0.f, true);     // raw outer products + raw column sums, one launch
     h->call++;
     BM_HIP(hipGetLastError());
@@ -1187,14 +1148,18 @@ int bm_rbm_apply_step(bm_rbm *h, int32_t B_global, float lr, float mom) {
 
 int bm_rbm_transform(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float *H_dev) {
     BM_CHECK(H_dev, "null output");
-    BM_TRY(run_chain(h, X_dev, B, k, H_dev));
+    ChainOpts o;
+    o.hm_out = H_dev;
+    BM_TRY(run_chain(h, X_dev, B, k, o));
     h->call++;
     BM_HIP(hipGetLastError());
     return 0;
 }
 
 int bm_rbm_metrics(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float *out4) {
-    BM_TRY(run_chain(h, X_dev, B, k, nullptr, true, false, false, true));
+    ChainOpts o;
+    o.fetch = true;
+    BM_TRY(run_chain(h, X_dev, B, k, o));
     BM_TRY(metrics_from_chain(h, B, out4));
     h->call++;
     return 0;
@@ -1202,23 +1167,12 @@ int bm_rbm_metrics(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float *o
 
 int bm_rbm_free_energy(bm_rbm *h, const float *X_dev, int32_t B, float *out1) {
     BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
-    const float *Xin = X_dev;
-    int ldx = h->V;
-    if (h->cfg.v_unit == BM_UNIT_GAUSSIAN) {
-        hipLaunchKernelGGL(div_cols_kernel, dim3(256), dim3(256), 0, h->stream, Xin, ldx, h->sigma.p, h->Xs.p,
-                           h->Xs.ld, B, h->V);
-        Xin = h->Xs.p; ldx = h->Xs.ld;
-    }
-    bool dropped = false;
-    if (h->cfg.dropout >= 0.f) {
-        // free_energy_op is built from self._X_batch AFTER tf.nn.dropout replaced it (base_rbm.py:417-418,
-        // :516): the `feg` metric sees the dropped input like msre / pll do
-        hipLaunchKernelGGL(dropout_kernel, dim3(256), dim3(256), 0, h->stream, Xin, ldx, h->Xd.p, h->Xd.ld, B, h->V,
-                           h->cfg.dropout, make_key(h, SITE_DROPOUT, 0),
-                           (unsigned long long)h->row0 * (unsigned long long)h->V);
-        Xin = h->Xd.p; ldx = h->Xd.ld;
-        dropped = true;
-    }
+    // free_energy_op is built from self._X_batch AFTER tf.nn.dropout replaced it (base_rbm.py:417-418,
+    // :516): the `feg` metric sees the dropped input like msre / pll do
+    const float *Xin;
+    int ldx;
+    bool dropped;
+    prep_input(h, X_dev, B, &Xin, &ldx, &dropped);
     BM_HIP(hipMemsetAsync(h->scal.p, 0, 6 * sizeof(double), h->stream));
     BM_HIP(hipMemsetAsync(h->rowacc.p, 0, 3 * (size_t)h->maxB * sizeof(float), h->stream));
     launch_fe(h, Xin, ldx, B, false);
@@ -1242,16 +1196,8 @@ int bm_rbm_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, float *out
         h->fer_rows = B;
     }
     ensure_wt(h);
-    ActArgs a;
-    memset(&a, 0, sizeof(a));
-    up_weights(h, a);
-    a.Q1 = make_operand(X_dev, h->V, B);
-    a.K1 = h->V; a.I = h->H; a.J = B;
-    a.bias = h->hb.p; a.mult = 1.0f; a.bmult = 1.0f;
-    a.kind = BM_UNIT_BERNOULLI;
-    a.ldo = pad_ld(h->H);
-    a.rowacc = h->fer_part.p; a.rowacc_single = 1; a.beta_b = 1.0f; a.ld_part = h->fer_rows;
-    launch_act(a, h->stream);
+    issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, LayerOut{0, nullptr, nullptr, pad_ld(h->H), PhiloxKey{0, 0, 0, 0}, 0})
+                 .softplus_rows(h->fer_part.p, h->fer_rows, 0.f, 1.0f, 1));
     hipLaunchKernelGGL(rbm_fe_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, h->stream, X_dev, h->V, (int)B, h->V, (const float *)h->vb.p,
                        (const float *)h->fer_part.p, h->fer_rows, nslots(h->H), h->fer_out.p);
     BM_HIP(hipGetLastError());
@@ -1335,10 +1281,11 @@ int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_ste
         chain_begin(h);
         for (int t = 0; t < n_steps; ++t) {
             const bool first = t == 0, last = t == n_steps - 1;
-            launch_down(h, first ? H_dev : h->hs.p, first ? h->H : h->hs.ld, B, nullptr, last ? V_dev : h->vs.p,
-                        last ? h->V : h->vs.ld, h->cfg.sample_v_states, SITE_V, t);
-            launch_up(h, last ? V_dev : h->vs.p, last ? h->V : h->vs.ld, B, nullptr, last ? H_dev : h->hs.p,
-                      last ? h->H : h->hs.ld, h->cfg.sample_h_states, SITE_H, t);
+            const LayerIn hin = first ? LayerIn{H_dev, h->H} : in_of(h->hs);
+            float *vnew = last ? V_dev : h->vs.p, *hnew = last ? H_dev : h->hs.p;
+            const int ldv = last ? h->V : h->vs.ld, ldh = last ? h->H : h->hs.ld;
+            issue(h, rbm_pass(h, false, B, hin, rbm_out(h, h->cfg.sample_v_states, nullptr, vnew, ldv, SITE_V, t)));
+            issue(h, rbm_pass(h, true, B, LayerIn{vnew, ldv}, rbm_out(h, h->cfg.sample_h_states, nullptr, hnew, ldh, SITE_H, t)));
         }
         BM_TRY(chain_end(h));
         h->call++;
@@ -1365,8 +1312,8 @@ int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_ste
         h->fast_now = true;
     }
     for (int t = 0; t < n_steps; ++t) {
-        launch_down(h, h->hs.p, h->hs.ld, B, nullptr, h->vs.p, h->vs.ld, h->cfg.sample_v_states, SITE_V, t);
-        launch_up(h, h->vs.p, h->vs.ld, B, nullptr, h->hs.p, h->hs.ld, h->cfg.sample_h_states, SITE_H, t);
+        issue(h, rbm_pass(h, false, B, in_of(h->hs), rbm_out(h, h->cfg.sample_v_states, nullptr, h->vs.p, h->vs.ld, SITE_V, t)));
+        issue(h, rbm_pass(h, true, B, in_of(h->vs), rbm_out(h, h->cfg.sample_h_states, nullptr, h->hs.p, h->hs.ld, SITE_H, t)));
     }
     hipLaunchKernelGGL(copy2d_kernel, dim3(256), dim3(256), 0, h->stream, (const float *)h->hs.p, h->hs.ld, H_dev, h->H, B, h->H);
     hipLaunchKernelGGL(copy2d_kernel, dim3(256), dim3(256), 0, h->stream, (const float *)h->vs.p, h->vs.ld, V_dev, h->V, B, h->V);
@@ -1392,10 +1339,12 @@ int bm_rbm_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev
     hipLaunchKernelGGL(clamp_apply_kernel, dim3(256), dim3(256), 0, h->stream, V_dev, h->V, clamp_val_dev, clamp_mask_dev, h->V, B, h->V);
     for (int t = 0; t < n_steps; ++t) {
         const bool first = t == 0, last = t == n_steps - 1;
-        launch_up(h, first ? V_dev : h->vs.p, first ? h->V : h->vs.ld, B, nullptr, last ? H_dev : h->hs.p,
-                  last ? h->H : h->hs.ld, 1, SITE_H, t);
-        launch_down(h, last ? H_dev : h->hs.p, last ? h->H : h->hs.ld, B, last ? Vmean_dev : nullptr, last ? V_dev : h->vs.p,
-                    last ? h->V : h->vs.ld, 1, SITE_V, t, clamp_val_dev, clamp_mask_dev);
+        const LayerIn vin = first ? LayerIn{V_dev, h->V} : in_of(h->vs);
+        float *hnew = last ? H_dev : h->hs.p, *vnew = last ? V_dev : h->vs.p;
+        const int ldh = last ? h->H : h->hs.ld, ldv = last ? h->V : h->vs.ld;
+        issue(h, rbm_pass(h, true, B, vin, rbm_out(h, 1, nullptr, hnew, ldh, SITE_H, t)));
+        issue(h, rbm_pass(h, false, B, LayerIn{hnew, ldh}, rbm_out(h, 1, last ? Vmean_dev : nullptr, vnew, ldv, SITE_V, t))
+                     .clamp(clamp_val_dev, clamp_mask_dev, h->V));
     }
     h->call++;
     BM_HIP(hipGetLastError());
@@ -1451,7 +1400,7 @@ int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, flo
     // 2. positive phase: the h0 means alone
     h->Xin = X_dev; h->Xin_ld = h->V;
     h->fe_in_chain = false;
-    launch_up(h, X_dev, h->V, B, h->h0m.p, nullptr, h->h0m.ld, 0, SITE_H0, 0);
+    issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, rbm_out(h, 0, h->h0m.p, nullptr, h->h0m.ld, SITE_H0, 0)));
     // 3. + 4. the tempered steps; the last prop-down leaves the beta = 1 rows of the chains [0, B) in vs
     for (int t = 0; t < k; ++t) pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
     if (!sel_in_pass) {
@@ -1460,7 +1409,7 @@ int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, flo
         pt_launch_gather(h->pt, h->stream, B, dst, ldd);
     }
     // 5. negative means: only -h is consumed (run_chain's neg_only form)
-    launch_up(h, h->vs.p, h->vs.ld, B, nullptr, nullptr, h->hm.ld, 0, SITE_H, 0, h->hneg.p);
+    issue(h, rbm_pass(h, true, B, in_of(h->vs), rbm_out(h, 0, nullptr, nullptr, h->hm.ld, SITE_H, 0)).negmeans_out(h->hneg.p));
     h->hm_is_neg = true;
     // 6. + 7.
     launch_update_fused(h, B, lr, mom);

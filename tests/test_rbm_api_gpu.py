@@ -196,3 +196,27 @@ def test_staged_checkpoints_hold_epoch_end_states(gpu_lib, dirs, monkeypatch):
     assert np.array_equal(runs['staged'][0], runs['host'][0])
     with np.load(os.path.join(dirs[0], 'model.npz')) as z:
         assert np.array_equal(z['W'], runs['staged'][0])
+
+
+@pytest.mark.parametrize('sparsity_cost,expected', [
+    (0.0, dict(act_up=3, act_down=2, grad=1, colsum=0, bias=0, other=0)),
+    (0.1, dict(act_up=3, act_down=2, grad=1, colsum=1, bias=0, other=0)),
+])
+def test_profile_counts_the_launches_of_one_update_by_class(gpu_lib, sparsity_cost, expected):
+    """with profile(True) every pass of a CD-2 update is a launch of its own (no chained launch), event-timed under its
+    class: k + 1 prop-ups, k prop-downs, one outer-product launch that carries the bias update - or, with a sparsity
+    penalty, the column-sum / bias launch in front of it.  V % 4 == 0 (W^T exists), H is no multiple of 16."""
+    from boltzmann_machines_amd.engine import RbmEngine, as_device
+    V, H, B, k = 72, 40, 24, 2
+    eng = RbmEngine(V, H, max_batch=B, sample_v_states=True, sample_h_states=True, sparsity_cost=sparsity_cost)
+    try:
+        eng.set('W', RNG(seed=7).randn(V, H).astype(np.float32) * 0.01)
+        eng.seed(1337)
+        Xd = as_device((RNG(seed=8).rand(B, V) < 0.3).astype(np.float32))
+        eng.profile(True)
+        eng.train_step(Xd, B, 0.05, 0.9, k)
+        counts = {name: n for name, (ms, n) in eng.kernel_times().items()}
+        eng.profile(False)
+    finally:
+        eng.close()
+    assert counts == expected
