@@ -143,6 +143,10 @@ SIGNATURES = {
     'bm_rbm_free_energy': [_vp, _vp, _i32, _fp],
     'bm_rbm_free_energy_rows': [_vp, _vp, _i32, _vp],
     'bm_rbm_ais': [_vp, _i32, _i32, _i32, _vp, _u64, _i64, _vp],
+    'bm_rbm_set_classes': [_vp, _i32],
+    'bm_rbm_class_log_proba': [_vp, _vp, _i32, _vp],
+    'bm_rbm_class_train_step': [_vp, _vp, _vp, _i32, _f32, _f32, _fp],
+    'bm_rbm_class_train_epoch': [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _fp],
     'bm_rbm_gibbs': [_vp, _vp, _vp, _i32, _i32],
     'bm_rbm_gibbs_clamped': [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     'bm_rbm_pt_init': [_vp, _i32, _i32, _vp, _vp, _i64],

@@ -1,0 +1,241 @@
+"""Class head of a BernoulliRBM: the Python side.
+
+Larochelle & Bengio 2008, "Classification using discriminative restricted Boltzmann machines".  A head of C classes on the
+hidden layer - U [C, H], yb [C] beside the RBM's own W, hb, vb - gives the exact class posterior
+
+    z = x W + hb,   s_c = yb_c + sum_i softplus(z_i + U[c, i]),   log p(c|x) = s_c - logsumexp_c' s_c'
+
+and `fit_discriminative` ascends the batch mean of log p(t|x) with the exact gradient (no sampling), through the update rules
+of `fit` (bm_rbm_set_classes / bm_rbm_class_*, include/bm355.h).  The workflow: `fit(X)` unsupervised, `set_classes(C)`,
+`fit_discriminative(X, y)`, `predict(X)`.  The head is model state like the momentum buffers: U, yb, dU, dyb go into model.npz
+(`class_U`, `class_yb`, `class_dU`, `class_dyb`) and `n_classes` into params.json only while a head is attached; a model
+without a head is saved exactly as before.
+"""
+import os
+
+import numpy as np
+
+from .base import run_on_engine
+from .utils import make_list_from, write_during_training
+
+_CLASS_VARS = ('U', 'yb', 'dU', 'dyb')
+_PREDICT_ROWS = 4096          # rows per engine call of predict_log_proba (bounds the workspaces, not the input)
+
+
+def validate_labels(y, n_rows, n_classes):
+    """labels for `n_rows` rows of a head of `n_classes` classes -> contiguous int32 [n_rows]; ValueError for anything that is not
+    a one-dimensional integer array of that length with every entry in [0, n_classes)"""
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise ValueError('`y` has invalid shape {0}: expected [{1}]'.format(y.shape, n_rows))
+    if len(y) != n_rows:
+        raise ValueError('`y` has {0} labels for {1} rows of `X`'.format(len(y), n_rows))
+    if not (np.issubdtype(y.dtype, np.integer) or y.dtype == np.bool_):
+        raise ValueError('`y` must hold integer class labels (got dtype {0})'.format(y.dtype))
+    if len(y) and (y.min() < 0 or y.max() >= n_classes):
+        bad = y[(y < 0) | (y >= n_classes)][0]
+        raise ValueError('`y` holds the label {0} outside [0, n_classes={1})'.format(int(bad), n_classes))
+    return np.ascontiguousarray(y, dtype=np.int32)
+
+
+class ClassHead(object):
+    """`self._class_head` is None (no head) or dict(C=n_classes, pending=None | {name: array}): `pending` holds the head's
+    variables while no engine has them (before the engine is built, across a rebuild, after load_model).  `n_classes` is an
+    INSTANCE attribute only while a head is attached, so that params.json of a model without one keeps its schema."""
+    _class_head = None
+    n_classes = None
+
+    # ---- checks that need no device
+    def _check_class_head(self, what, train=False):
+        name = '%s.%s' % (self.__class__.__name__, what)
+        from . import _ffi
+        if self._V_UNIT != _ffi.UNIT_BERNOULLI:
+            raise ValueError('%s: a class head needs Bernoulli visible units (Gaussian visible units are not supported)' % name)
+        if self._H_UNIT != _ffi.UNIT_BERNOULLI:
+            raise ValueError('%s: a class head needs Bernoulli hidden units (Multinomial hidden units are not supported)' % name)
+        if np.dtype(self.dtype) != np.float32:
+            raise ValueError("%s: the class head runs in float32 only (dtype=%r)" % (name, self.dtype))
+        if self.dbm_first or self.dbm_last:
+            raise ValueError('%s: a dbm_first / dbm_last model (one conditional doubled) takes no class head' % name)
+        if what != 'set_classes' and self._class_head is None:
+            raise ValueError('%s: no class head is attached; call set_classes(n_classes) first' % name)
+        if train:
+            if self.dropout is not None:
+                raise ValueError('%s is not combined with dropout (dropout=%r)' % (name, self.dropout))
+            if self.sparsity_cost != 0.:
+                raise ValueError('%s is not combined with the sparsity penalty (sparsity_cost=%r)' % (name, self.sparsity_cost))
+            if self._centering is not None:
+                raise ValueError('%s is not combined with centering; call set_centering(False) first' % name)
+            if os.environ.get('BM355_DATA_PARALLEL', '0') == '1' or getattr(self, '_dp', None) is not None:
+                raise ValueError('%s is not combined with data parallelism (BM355_DATA_PARALLEL)' % name)
+        return name
+
+    def _check_class_X(self, X, name='X'):
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.n_visible:
+            raise ValueError('`{0}` has invalid shape {1}: expected [N, {2}]'.format(name, X.shape, self.n_visible))
+        return X
+
+    # ---- the head
+    def set_classes(self, n_classes, U=None, yb=None, U_std=0.01):
+        """Attach a head of `n_classes` >= 2 classes to this BernoulliRBM, or detach it (`n_classes=None`).
+
+        U : [n_classes, n_hidden] class weights; None: a normal draw of standard deviation `U_std` from the model's seeded host
+            stream (the stream `make_random_seed` draws from).  yb : [n_classes] class biases; None: zeros.  The momentum
+        buffers start at zero.  An attached head is replaced.  BernoulliRBM in float32 only: GaussianRBM, MultinomialRBM,
+        float64 and `dbm_first` / `dbm_last` models raise ValueError.  Nothing else about the model changes.  Returns self."""
+        if n_classes is None:
+            was, self._class_head = self._class_head, None
+            self.__dict__.pop('n_classes', None)
+            if was is not None and self._engine is not None and was['pending'] is None:
+                self._engine.set_classes(0)
+            return self
+        self._check_class_head('set_classes')
+        C, H = int(n_classes), self.n_hidden
+        if C != n_classes or C < 2:
+            raise ValueError('set_classes: n_classes must be an integer >= 2 or None (got {0!r})'.format(n_classes))
+        if U is None:
+            U = self._rng.normal(0., float(U_std), (C, H))
+        U = np.ascontiguousarray(U, dtype=np.float32)
+        yb = np.zeros(C, dtype=np.float32) if yb is None else np.ascontiguousarray(yb, dtype=np.float32)
+        if U.shape != (C, H):
+            raise ValueError('`U` has invalid shape {0} != {1}'.format(U.shape, (C, H)))
+        if yb.shape != (C,):
+            raise ValueError('`yb` has invalid shape {0} != {1}'.format(yb.shape, (C,)))
+        self.n_classes = C
+        self._class_head = dict(C=C, pending=dict(U=U, yb=yb, dU=np.zeros_like(U), dyb=np.zeros_like(yb)))
+        if self._engine is not None:
+            self._apply_class_head()
+        return self
+
+    def _apply_class_head(self):
+        """the engine exists: attach the head to it and hand over the variables that wait for it"""
+        c = self._class_head
+        if c is None or c['pending'] is None:
+            return
+        self._check_class_head('fit')
+        self._engine.set_classes(c['C'])
+        for name in _CLASS_VARS:
+            self._engine.set(name, c['pending'][name])
+        c['pending'] = None
+
+    def _class_detach(self):
+        """the engine is about to be closed (a rebuild after set_params): the head's variables wait on the host"""
+        c = self._class_head
+        if c is not None and c['pending'] is None and self._engine is not None:
+            c['pending'] = {name: np.array(self._engine.get(name), dtype=np.float32) for name in _CLASS_VARS}
+
+    def class_variables(self):
+        """dict(U, yb, dU, dyb) of float32 arrays; None without a head"""
+        c = self._class_head
+        if c is None:
+            return None
+        if c['pending'] is not None:
+            return {name: np.array(c['pending'][name], dtype=np.float32) for name in _CLASS_VARS}
+        return {name: np.array(self._engine.get(name), dtype=np.float32) for name in _CLASS_VARS}
+
+    # ---- checkpoints
+    def _class_variables(self):
+        """what model.npz additionally holds while a head is attached"""
+        v = self.class_variables()
+        return {} if v is None else {'class_' + name: v[name] for name in _CLASS_VARS}
+
+    def _class_restore(self, d):
+        """load_model only: takes the class_* arrays out of `d` and re-attaches the head they describe"""
+        taken = {k: d.pop(k) for k in [k for k in d if k.startswith('class_')]}
+        self.__dict__.pop('n_classes', None)
+        if 'class_U' not in taken:
+            return
+        U = np.ascontiguousarray(taken['class_U'], dtype=np.float32)
+        self.set_classes(U.shape[0], U=U, yb=taken['class_yb'])
+        for name in ('dU', 'dyb'):
+            self._class_head['pending'][name] = np.ascontiguousarray(taken['class_' + name], dtype=np.float32)
+
+    # ---- discriminative training
+    def fit_discriminative(self, X, y, X_val=None, y_val=None, n_epochs=10, learning_rate=0.1, momentum=0.5, batch_size=None,
+                           verbose=None):
+        """Ascend the mean of log p(y|x) over (X, y) with the exact gradient: W, hb, U, yb move, vb sees a zero gradient.
+
+        y : integer labels in [0, n_classes), one per row of X (checked on the host before anything is uploaded).
+        learning_rate, momentum : a number or one value per epoch (the last one repeats), like the schedules of `fit`; `l2` is
+        the model's.  batch_size : None = the model's; at most the model's.  Batches are consecutive rows, the last one may be
+        short.  X_val, y_val : evaluated after every epoch.  Returns dict(log_proba=[..], accuracy=[..]) with one entry per
+        epoch - the mean log p(y|x) and the accuracy over the epoch's rows, each batch's taken before its update - plus
+        val_log_proba / val_accuracy when validation data is given.  Touches neither `epoch_` / `iter_`, the schedules of
+        `fit`, the RNG streams nor the persistent chains.  Not combined with dropout, a sparsity penalty, centering or data
+        parallelism (ValueError)."""
+        self._check_class_head('fit_discriminative', train=True)
+        X = self._check_class_X(X)
+        y = validate_labels(y, len(X), self._class_head['C'])
+        if (X_val is None) != (y_val is None):
+            raise ValueError('fit_discriminative: `X_val` and `y_val` go together')
+        if X_val is not None:
+            X_val = self._check_class_X(X_val, 'X_val')
+            y_val = validate_labels(y_val, len(X_val), self._class_head['C'])
+        bs = self.batch_size if batch_size is None else int(batch_size)
+        if not 1 <= bs <= self.batch_size:
+            raise ValueError('fit_discriminative: batch_size {0} outside [1, the model\'s batch_size = {1}]'.format(bs, self.batch_size))
+        if len(X) < 1 or int(n_epochs) < 0:
+            raise ValueError('fit_discriminative: needs at least one row and n_epochs >= 0')
+        return self._fit_discriminative(X, y, X_val, y_val, int(n_epochs), make_list_from(learning_rate), make_list_from(momentum),
+                                        bs, self.verbose if verbose is None else verbose)
+
+    @run_on_engine(check_initialized=False)
+    def _fit_discriminative(self, X, y, X_val, y_val, n_epochs, lrs, moms, bs, verbose):
+        from . import _ffi
+        self.initialized_ = True
+        eng = self._on_device()
+        Xd = self._to_device(X, 'fit_X')
+        yd = _ffi.DeviceArray.from_numpy(y, np.int32)
+        names = ['log_proba', 'accuracy'] + (['val_log_proba', 'val_accuracy'] if X_val is not None else [])
+        out = {name: [] for name in names}
+        for epoch in range(n_epochs):
+            lr, mom = float(lrs[min(epoch, len(lrs) - 1)]), float(moms[min(epoch, len(moms) - 1)])
+            lp, acc = eng.class_train_epoch(Xd, yd, len(X), bs, lr, mom)
+            out['log_proba'].append(lp)
+            out['accuracy'].append(acc)
+            if X_val is not None:
+                L = self._class_log_proba(X_val)
+                out['val_log_proba'].append(float(L[np.arange(len(y_val)), y_val].astype(np.float64).mean()))
+                out['val_accuracy'].append(float((L.argmax(axis=1) == y_val).mean()))
+            if verbose:
+                parts = ['epoch: %*d/%d' % (len(str(n_epochs)), epoch + 1, n_epochs)]
+                parts += ['%s: %s' % (m.replace('val_', 'val.'), format(out[m][-1], '.4f')) for m in names]
+                write_during_training('; '.join(parts))
+        eng.sync()
+        self._save_model()
+        return out
+
+    # ---- prediction
+    def _class_log_proba(self, X):
+        eng = self._on_device()
+        Xd = self._to_device(X)
+        L = np.empty((len(X), self._class_head['C']), dtype=np.float32)
+        for start in range(0, len(X), _PREDICT_ROWS):
+            B = min(_PREDICT_ROWS, len(X) - start)
+            L[start:start + B] = eng.class_log_proba(Xd, B, row=start)
+        return L
+
+    def predict_log_proba(self, X):
+        """[N, n_classes] float32: the exact log p(c|x) per row of X.  Draws nothing."""
+        self._check_class_head('predict_log_proba')
+        return self._predict_log_proba(self._check_class_X(X))
+
+    @run_on_engine()
+    def _predict_log_proba(self, X):
+        return self._class_log_proba(X)
+
+    def predict_proba(self, X):
+        """[N, n_classes]: p(c|x) per row of X"""
+        return np.exp(self.predict_log_proba(X))
+
+    def predict(self, X):
+        """[N] int64: argmax_c p(c|x) per row of X (the lowest class among equals)"""
+        return self.predict_log_proba(X).argmax(axis=1)
+
+    def score(self, X, y):
+        """the accuracy of `predict(X)` against the labels `y`"""
+        self._check_class_head('score')
+        X = self._check_class_X(X)
+        y = validate_labels(y, len(X), self._class_head['C'])
+        return float((self.predict(X) == y).mean())

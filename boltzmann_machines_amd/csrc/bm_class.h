@@ -1,0 +1,54 @@
+// bm_class.h — the class head of a Bernoulli RBM (Larochelle & Bengio 2008, "Classification using discriminative
+// restricted Boltzmann machines"): the arguments and launchers of its kernels.  The kernels themselves, and the CR flavour of
+// act_kernel that feeds them, are compiled in bm_class.hip.  Host code only.
+//
+//   z_i        = (x W)_i + hb_i
+//   s_c        = yb_c + sum_i softplus(z_i + U[c][i])
+//   log p(c|x) = s_c - logsumexp_c' s_c'
+//
+// One discriminative update (ascent of the batch mean of log p(t|x)), in stream order:
+//   1. act_kernel, CR flavour      t = z + hb as [B][H]; per class the slot partials of sum_i softplus(t_i + U[c][i])
+//   2. class_row_kernel            s_c, logsumexp, log p, p, coef = 1[c == t] - p; the row's log p(t|x) and hit      (double sums)
+//   3. class_hidden_kernel         pos = sigmoid(t + U[t_j]),  negm = -sum_c p_c sigmoid(t + U[c])  ->  the h0 / -h_k buffers
+//   4. class_head_update_kernel    dU, dyb from coef and the recomputed sigmoids; the U and yb update rules
+//   5. grad_kernel form 0 + bias tail, unchanged, with the input as its negative-phase visible operand: W, W^T, hb, vb
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace bm {
+
+struct ClassRowArgs {
+    const float *part;        // [C][nslots][ldp] slot partials (ActArgs::cr_part)
+    int ldp, nslots, C, B;
+    const float *yb;          // [C]
+    const int *y;             // [B] labels or null (prediction: logp / prob only)
+    float *logp, *prob;       // [B][C] dense
+    float *coef;              // [B][C]: 1[c == t] - p(c|x); a row whose label is outside [0, C): zeros
+    int *tl;                  // [B]: the label, -1 where it is outside [0, C)
+    float *rowlp, *rowhit;    // [B]: log p(t|x) and 1[argmax == t] (0 for a bad label)
+    int *bad;                 // device flag raised by a label outside [0, C)
+};
+struct ClassHiddenArgs {
+    const float *T;           // [B][H] pitch ldt: t = z + hb
+    const float *U;           // [C][H] pitch ldu
+    const float *prob;        // [B][C]
+    const int *tl;            // [B]
+    float *pos, *negm;        // [B][H] pitch ld
+    int ldt, ldu, ld, B, H, C;
+};
+struct ClassHeadArgs {
+    const float *T;           // [B][H] pitch ldt
+    const float *coef;        // [B][C]
+    float *U, *dU;            // [C][H] pitch ldu
+    float *yb, *dyb;          // [C]
+    int ldt, ldu, B, H, C;
+    float N, l2, lr, mom;
+};
+
+void launch_class_row(const ClassRowArgs &a, hipStream_t st);
+void launch_class_hidden(const ClassHiddenArgs &a, hipStream_t st);
+void launch_class_head_update(const ClassHeadArgs &a, hipStream_t st);
+// acc[0] += sum_j rowlp[j], acc[1] += sum_j rowhit[j], in double, in an order that depends on B alone
+void launch_class_sum(const float *rowlp, const float *rowhit, int B, double *acc, hipStream_t st);
+
+}  // namespace bm

@@ -119,6 +119,13 @@ struct ActArgs {
     // dense negative particles of the update that follows.  The lane holds row_mult[j] already; no further load.  Null: off.
     float *sel_out;
     int sel_ld, sel_R, sel_rows;
+    // Class head (the CR flavour, act_kernel<..., CR = true>; launch_act_cr): the hidden prop-up of a
+    // classification RBM.  The pass stores t = z + b as `means` (kind 3, mult == bmult == 1) and leaves, for every class
+    // c < cr_C, the slot partials of sum_i softplus(t_i + cr_U[c][i]) at cr_part[(c * cr_nslots + slot) * ld_part + j] - the
+    // quad order and slot rule of `rowacc`, one class at a time (one accumulator live: cr_C costs no registers).  Null: off.
+    float *cr_part;
+    const float *cr_U;                   // [cr_C][I], pitch cr_ldu
+    int cr_ldu, cr_C, cr_nslots;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -342,7 +349,8 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // act_kernel's epilogue for the lane's outputs of ONE output tile (i0, j0): activation, draw, stores, the per-row
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
-template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false>
+template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false,
+          bool CR = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -545,13 +553,40 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
             }
         }
     }
+    // CR: the class rows of a classification RBM's prop-up (ActArgs::cr_part) - for every class the slot partials of
+    // sum_i softplus(t_i + U[c][i]), t = z + b as the stores above rounded it (mult == bmult == 1), in rowacc's quad order and
+    // slot rule; the accurate softplus (these sums feed gradients).  The loop over the classes is wave-uniform
+    if constexpr (CR) {
+        const bool writer = (G::MI == 1) ? (g == 0) : ((g & 1) == 0);
+        const int slot = (i0 + wi * (16 * G::MI)) / 16 + ((G::MI == 2) ? (g >> 1) : 0);
+        for (int c = 0; c < a.cr_C; ++c) {
+            const float *u = a.cr_U + (size_t)c * a.cr_ldu;
+            float racc = 0.f;
+            if (j < a.J) {
+#pragma unroll
+                for (int hlf = 0; hlf < NH; ++hlf) {
+                    float qa = 0.f;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int e = 4 * hlf + r, i = ib0 + e;
+                        if (i >= a.I) break;
+                        qa += softplus((z[e] + bs[e]) + u[i]);
+                    }
+                    racc = (hlf == 0) ? qa : racc + qa;
+                }
+            }
+            racc += __shfl_xor(racc, 16);
+            if (G::MI == 1) racc += __shfl_xor(racc, 32);
+            if (writer && j < a.J && slot * 16 < a.I) a.cr_part[((size_t)c * a.cr_nslots + slot) * a.ld_part + j] = racc;
+        }
+    }
     return dmax;
 }
 
 // MINB: HIP's second __launch_bounds__ argument = WAVES PER SIMD the register budget must allow (for the 4-wave
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
-          bool CL = false, bool RT = false>
+          bool CL = false, bool RT = false, bool CR = false>
 BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -627,7 +662,7 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];
@@ -2050,6 +2085,6 @@ BM_KERNEL __launch_bounds__(256) void ais_score_kernel(double *logw, int J, int 
 
 }  // namespace bm
 
-#ifndef BM_KERNELS_ONLY       // (bm_grad_cen.hip: a unit that launches ONE kernel family does not pay for every instantiation)
-#include "bm_launch.h"      // the host side: launchers and the launch tuner
-#endif
+// the host side: launchers and the launch tuner.  (BM_KERNELS_ONLY - bm_grad_cen.hip, bm_class.hip: a unit that launches ONE
+// kernel family does not pay for every instantiation - keeps the templates of the flavour dispatcher and nothing that names a kernel)
+#include "bm_launch.h"

@@ -49,6 +49,12 @@ struct LayerPass {
     LayerPass &row_tempered(const float *row_mult) { a.row_mult = row_mult; return *this; }
     // ... and, rows grouped in runs of R, the row_mult == 1 row of every group c < rows also stores its states at out + c * ld
     LayerPass &select_rows(float *out, int ld, int R, int rows) { a.sel_out = out; a.sel_ld = ld; a.sel_R = R; a.sel_rows = rows; return *this; }
+    // class head: the slot partials, per class c < C, of sum_i softplus(t_i + U[c][i]) at part[(c * nslots(I) + slot) * ldp + j], of a
+    // logits pass (kind 3, mult 1: t = z + bias is what it stores); the CR flavour (ActArgs::cr_part)
+    LayerPass &class_rows(float *part, int ldp, const float *U, int ldu, int C) {
+        a.cr_part = part; a.ld_part = ldp; a.cr_U = U; a.cr_ldu = ldu; a.cr_C = C; a.cr_nslots = nslots(a.I);
+        return *this;
+    }
     // metric fetch riding on a prop-up of x [J][K] (pitch ldx) through w [K][I] (pitch ldw): the row-major slot partials
     // ([ldp][rm] each) of sum softplus(z + b) for x and, behind them, for its PLL partner - the flip column drawn from
     // `flip_key`; the pass also zeroes the fetch's accumulators `zero` (ActArgs::fe_flip)

@@ -11,6 +11,7 @@
 #include "bm_pass.h"
 #include "bm_pt.h"
 #include "bm_center.h"
+#include "bm_class.h"
 
 #include <math.h>
 #include <atomic>
@@ -116,6 +117,17 @@ struct bm_rbm {
     bool fast_now = false;
     Mat16 W3, W3t, hs16, vs16;
     DevArray<int> nonbinary;   // device flag: a state handed to the fast path was not a {0,1} bitmap
+    // class head (bm_rbm_set_classes; bm_class.h): U [C][H] (dense), yb [C] and their momentum buffers are
+    // variables; the rest is workspace for cls_rows rows (max_batch at set_classes, grown on demand by class_log_proba)
+    int n_classes = 0, cls_rows = 0;
+    DevBuf U, dU, yb, dyb;
+    DevBuf cls_part;                   // [C][ceil(H/16)][cls_rows] slot partials of sum softplus(t + U[c])
+    DevBuf cls_logp, cls_prob, cls_coef, cls_rowlp, cls_rowhit;      // [cls_rows][C] x 3, [cls_rows] x 2
+    DevArray<int> cls_tl, cls_bad;     // [cls_rows] checked labels; the device flag a label outside [0, C) raises
+    DevArray<double> cls_acc;          // [2] sums of log p(t|x) and of the hits
+    // the negative-phase visible operand of the fused update: vs, or - the class head's update - the input itself
+    const float *neg_v = nullptr;
+    int neg_v_ld = 0;
     // bm_rbm_stage / bm_rbm_get_staged: device-side copies of every variable taken in stream order (a checkpoint
     // snapshot that does not stop the stream), read back on their own stream by whoever writes the checkpoint
     struct Stage { Mat W, dW; DevBuf vb, hb, dvb, dhb, q, sigma; Event ev; bool ready = false;
@@ -352,7 +364,8 @@ static void fill_bias(bm_rbm *h, float N, float lr, float mom, RbmBiasArgs &b) {
 // single-GPU path: column sums + bias/q update in ONE launch (or inside the grad launch)
 static int fill_bias_fused(bm_rbm *h, int B, float lr, float mom, RbmBiasFusedArgs &a) {
     memset(&a, 0, sizeof(a));
-    a.X = h->Xin; a.ldx = h->Xin_ld; a.vs = h->vs.p; a.ldv = h->vs.ld;
+    a.X = h->Xin; a.ldx = h->Xin_ld;
+    a.vs = h->neg_v ? h->neg_v : h->vs.p; a.ldv = h->neg_v ? h->neg_v_ld : h->vs.ld;
     a.h0m = h->h0m.p; a.ldh0 = h->h0m.ld; a.B = B;
     // the last up-pass of a plain update leaves only -h_k behind (run_chain)
     if (h->hm_is_neg) { a.hm = h->hneg.p; a.ldh = h->hneg.ld; a.hm_negated = 1; }
@@ -389,7 +402,8 @@ static void fill_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom,
     g.Qpos = make_operand(h->Xin, h->Xin_ld, h->V);     // X        [k=b][j=v]
     g.Kpos = B;
     g.Pneg = make_operand(h->hneg.p, h->hneg.ld, h->H); // -(h_k means): the chain subtracts  :448
-    g.Qneg = make_operand(h->vs.p, h->vs.ld, h->V);     // v_k states
+    g.Qneg = h->neg_v ? make_operand(h->neg_v, h->neg_v_ld, h->V)      // (the class head's update: the input itself)
+                      : make_operand(h->vs.p, h->vs.ld, h->V);         // v_k states
     g.Kneg = B;
     g.I = h->H; g.J = h->V;
     g.form = 0; g.fused = fused;
@@ -789,6 +803,19 @@ static int check_device_status(bm_rbm *h) {
     return 0;
 }
 
+// the class head's label flag (class_row_kernel): reported ONCE, then cleared.  The stream is idle when this is called
+static int check_class_labels(bm_rbm *h) {
+    if (!h->cls_bad.p) return 0;
+    int bad = 0;
+    BM_HIP(hipMemcpy(&bad, h->cls_bad.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) {
+        BM_HIP(hipMemset(h->cls_bad.p, 0, sizeof(int)));
+        BM_CHECK(false, "class head: a label outside [0, n_classes=%d) reached bm_rbm_class_train_step / _epoch; its row was left "
+                 "out of the update", h->n_classes);
+    }
+    return 0;
+}
+
 int bm_rbm_sync(bm_rbm *h) {
     BM_HIP(hipStreamSynchronize(h->stream));
     BM_TRY(check_device_status(h));
@@ -800,6 +827,7 @@ int bm_rbm_sync(bm_rbm *h) {
             BM_CHECK(false, "fast-binary mode: bm_rbm_gibbs was given hidden states that are not a {0,1} bitmap");
         }
     }
+    BM_TRY(check_class_labels(h));
     return 0;
 }
 
@@ -844,6 +872,12 @@ static DevBuf *find_vec(bm_rbm *h, const std::string &n) {
     if (n == "sigma") return &h->sigma;
     if (n == "ov") return &h->ov;             // centering offsets (bm_rbm_set_centering)
     if (n == "oh") return &h->oh;
+    if (h->n_classes) {                       // the class head's variables (bm_rbm_set_classes), dense [C][H] and [C]
+        if (n == "U") return &h->U;
+        if (n == "dU") return &h->dU;
+        if (n == "yb") return &h->yb;
+        if (n == "dyb") return &h->dyb;
+    }
     return nullptr;
 }
 
@@ -1204,6 +1238,149 @@ int bm_rbm_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, float *out
     BM_HIP(hipMemcpyAsync(out_host, h->fer_out.p, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// ---- class head (bm355.h; bm_class.h lists the launches)
+static int ensure_class_rows(bm_rbm *h, int rows) {
+    if (rows <= h->cls_rows) return 0;
+    const size_t C = (size_t)h->n_classes;
+    h->cls_rows = 0;                               // (set again once every buffer exists: a failure leaves none counted)
+    BM_TRY(h->cls_part.alloc(C * nslots(h->H) * rows));
+    BM_TRY(h->cls_logp.alloc(C * rows)); BM_TRY(h->cls_prob.alloc(C * rows)); BM_TRY(h->cls_coef.alloc(C * rows));
+    BM_TRY(h->cls_rowlp.alloc(rows)); BM_TRY(h->cls_rowhit.alloc(rows)); BM_TRY(h->cls_tl.alloc(rows));
+    h->cls_rows = rows;
+    return 0;
+}
+
+int bm_rbm_set_classes(bm_rbm *h, int32_t n_classes) {
+    BM_CHECK(h, "null argument");
+    BM_CHECK(n_classes == 0 || n_classes >= 2, "bm_rbm_set_classes: n_classes must be 0 (detach) or >= 2 (got %d)", (int)n_classes);
+    BM_HIP(hipStreamSynchronize(h->stream));
+    if (n_classes == 0) {
+        h->n_classes = 0; h->cls_rows = 0;
+        for (DevBuf *b : {&h->U, &h->dU, &h->yb, &h->dyb, &h->cls_part, &h->cls_logp, &h->cls_prob, &h->cls_coef, &h->cls_rowlp, &h->cls_rowhit})
+            *b = DevBuf();
+        h->cls_tl = DevArray<int>();
+        return 0;
+    }
+    BM_TRY(check_single_joint(h, "bm_rbm_set_classes"));
+    const size_t C = (size_t)n_classes;
+    h->n_classes = 0; h->cls_rows = 0;
+    BM_TRY(h->U.alloc(C * h->H)); BM_TRY(h->dU.alloc(C * h->H)); BM_TRY(h->yb.alloc(C)); BM_TRY(h->dyb.alloc(C));
+    if (!h->cls_bad.p) BM_TRY(h->cls_bad.alloc(1));
+    if (!h->cls_acc.p) BM_TRY(h->cls_acc.alloc(2));
+    h->n_classes = n_classes;
+    if (ensure_class_rows(h, h->maxB)) { h->n_classes = 0; return 1; }
+    return 0;
+}
+
+// the forward pass of B rows (B <= cls_rows): the CR prop-up (t into `T` when it is wanted) and the row kernel
+static void class_forward(bm_rbm *h, const float *X_dev, int B, float *T, int ldt, const int *y_dev) {
+    ensure_wt(h);
+    LayerPass p = rbm_pass(h, true, B, LayerIn{X_dev, h->V}, LayerOut{0, T, nullptr, ldt, PhiloxKey{0, 0, 0, 0}, 0}, 1.0f);
+    p.a.kind = 3;                                  // stores t = z + hb
+    issue(h, p.class_rows(h->cls_part.p, h->cls_rows, h->U.p, h->H, h->n_classes));
+    ProfScope _ps(h, KC_OTHER);
+    ClassRowArgs r;
+    memset(&r, 0, sizeof(r));
+    r.part = h->cls_part.p; r.ldp = h->cls_rows; r.nslots = nslots(h->H); r.C = h->n_classes; r.B = B;
+    r.yb = h->yb.p; r.y = y_dev;
+    r.logp = h->cls_logp.p; r.prob = h->cls_prob.p; r.coef = h->cls_coef.p; r.tl = h->cls_tl.p;
+    r.rowlp = h->cls_rowlp.p; r.rowhit = h->cls_rowhit.p; r.bad = h->cls_bad.p;
+    launch_class_row(r, h->stream);
+}
+
+int bm_rbm_class_log_proba(bm_rbm *h, const float *X_dev, int32_t B, float *logp_host) {
+    BM_CHECK(h && X_dev && logp_host, "null argument");
+    BM_CHECK(h->n_classes, "bm_rbm_class_log_proba: no class head is attached (bm_rbm_set_classes)");
+    BM_TRY(check_single_joint(h, "bm_rbm_class_log_proba"));
+    BM_CHECK(B >= 1, "bad row count %d", (int)B);
+    BM_TRY(ensure_class_rows(h, B));
+    class_forward(h, X_dev, B, nullptr, pad_ld(h->H), nullptr);
+    BM_HIP(hipGetLastError());
+    BM_HIP(hipMemcpyAsync(logp_host, h->cls_logp.p, (size_t)B * h->n_classes * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+static int check_class_train(const bm_rbm *h, const char *what, int B) {
+    BM_CHECK(h->n_classes, "%s: no class head is attached (bm_rbm_set_classes)", what);
+    BM_TRY(check_single_joint(h, what));
+    BM_CHECK(h->cfg.dropout < 0.f, "%s does not combine with dropout (this handle's is %g)", what, (double)h->cfg.dropout);
+    BM_CHECK(h->cfg.sparsity_cost == 0.f, "%s does not combine with the sparsity penalty (this handle's sparsity_cost is %g)", what,
+             (double)h->cfg.sparsity_cost);
+    BM_CHECK(!h->cen_on, "%s has no centred form; switch centering off (bm_rbm_set_centering)", what);
+    BM_CHECK(!h->xchg_used && !h->comm_stream && !h->dw_sharded && h->grad_slot == 0,
+             "%s: this handle takes part in a data-parallel run; the discriminative update has no split form", what);
+    BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
+    return 0;
+}
+// one discriminative update; `sum`: the batch's sums of log p(t|x) and of the hits are added to cls_acc (taken from the forward
+// pass, before the update).  Queues only
+static int class_update(bm_rbm *h, const float *X_dev, const int *y_dev, int B, float lr, float mom, bool sum) {
+    class_forward(h, X_dev, B, h->hm.p, h->hm.ld, y_dev);
+    {   // (event timing, bm_rbm_profile: the classes this update leaves unused tell its kernels apart - the CR pass counts as
+        //  KC_UP, class_row_kernel as KC_OTHER, class_hidden_kernel as KC_COLSUM, class_head_update_kernel as KC_BIAS)
+        ProfScope _ps(h, KC_COLSUM);
+        ClassHiddenArgs c;
+        memset(&c, 0, sizeof(c));
+        c.T = h->hm.p; c.ldt = h->hm.ld; c.U = h->U.p; c.ldu = h->H; c.prob = h->cls_prob.p; c.tl = h->cls_tl.p;
+        c.pos = h->h0m.p; c.negm = h->hneg.p; c.ld = h->h0m.ld; c.B = B; c.H = h->H; c.C = h->n_classes;
+        launch_class_hidden(c, h->stream);
+        if (sum) launch_class_sum(h->cls_rowlp.p, h->cls_rowhit.p, B, h->cls_acc.p, h->stream);
+    }
+    {
+        ProfScope _ps(h, KC_BIAS);
+        ClassHeadArgs u;
+        memset(&u, 0, sizeof(u));
+        u.T = h->hm.p; u.ldt = h->hm.ld; u.coef = h->cls_coef.p; u.U = h->U.p; u.dU = h->dU.p; u.yb = h->yb.p; u.dyb = h->dyb.p;
+        u.ldu = h->H; u.B = B; u.H = h->H; u.C = h->n_classes;
+        u.N = (float)B; u.l2 = h->cfg.l2; u.lr = lr; u.mom = mom;
+        launch_class_head_update(u, h->stream);
+    }
+    // W, W^T, hb, vb: the fused update as it is, on pos (h0m), negm (hneg, "already negated") and the input on both sides -
+    // dvb = colsum(X - X) / B = 0 by construction
+    h->Xin = X_dev; h->Xin_ld = h->V;
+    h->hm_is_neg = true;
+    h->neg_v = X_dev; h->neg_v_ld = h->V;
+    launch_update_fused(h, B, lr, mom);
+    h->neg_v = nullptr; h->neg_v_ld = 0;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+static int class_fetch(bm_rbm *h, double rows, float *out2) {
+    double host[2];
+    BM_HIP(hipMemcpyAsync(host, h->cls_acc.p, sizeof(host), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_TRY(check_device_status(h));
+    BM_TRY(check_class_labels(h));
+    out2[0] = (float)(host[0] / rows); out2[1] = (float)(host[1] / rows);
+    return 0;
+}
+
+int bm_rbm_class_train_step(bm_rbm *h, const float *X_dev, const int32_t *y_dev, int32_t B, float lr, float mom, float *out2) {
+    BM_CHECK(h && X_dev && y_dev, "null argument");
+    BM_TRY(check_class_train(h, "bm_rbm_class_train_step", B));
+    BM_TRY(check_dw(h, "bm_rbm_class_train_step"));
+    if (out2) BM_HIP(hipMemsetAsync(h->cls_acc.p, 0, 2 * sizeof(double), h->stream));
+    BM_TRY(class_update(h, X_dev, y_dev, B, lr, mom, out2 != nullptr));
+    return out2 ? class_fetch(h, (double)B, out2) : 0;
+}
+
+// N rows as consecutive minibatches of `batch` rows, driven from C: the launches of the caller's own loop over
+// bm_rbm_class_train_step, no host wait between the batches
+int bm_rbm_class_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev, int64_t N, int32_t batch, float lr, float mom,
+                             float *out2) {
+    BM_CHECK(h && X_dev && y_dev, "null argument");
+    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
+    BM_TRY(check_class_train(h, "bm_rbm_class_train_epoch", (int)((N < batch) ? N : batch)));
+    BM_TRY(check_dw(h, "bm_rbm_class_train_epoch"));
+    if (out2) BM_HIP(hipMemsetAsync(h->cls_acc.p, 0, 2 * sizeof(double), h->stream));
+    for (int64_t s = 0; s < N; s += batch) {
+        const int B = (int)((N - s < batch) ? (N - s) : batch);
+        BM_TRY(class_update(h, X_dev + (size_t)s * h->V, y_dev + s, B, lr, mom, out2 != nullptr));
+    }
+    return out2 ? class_fetch(h, (double)N, out2) : 0;
 }
 
 // AIS from the base-rate model p_0(v) ~ exp(a.v) to the RBM, the hidden layer summed out (Salakhutdinov & Murray 2008):

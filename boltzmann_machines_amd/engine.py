@@ -93,11 +93,15 @@ class RbmEngine(_PtCalls):
 
     # -- variables
     def _size(self, name):
+        C_ = getattr(self, 'n_classes', 0)
         return {'W': self.V * self.H, 'dW': self.V * self.H, 'vb': self.V, 'dvb': self.V, 'sigma': self.V,
                 'hb': self.H, 'dhb': self.H, 'q_means': self.H, 'ov': self.V, 'oh': self.H,
-                'grad': self.V * self.H + self.V + 2 * self.H}[name]
+                'grad': self.V * self.H + self.V + 2 * self.H,
+                'U': C_ * self.H, 'dU': C_ * self.H, 'yb': C_, 'dyb': C_}[name]
 
     def _shape(self, name):
+        if name in ('U', 'dU'):          # the class head's weights (set_classes)
+            return (getattr(self, 'n_classes', 0), self.H)
         return (self.V, self.H) if name in ('W', 'dW') else (self._size(name),)
 
     def set(self, name, value):
@@ -209,6 +213,36 @@ class RbmEngine(_PtCalls):
         out = np.empty(B, dtype=np.float32)
         check(self.lib.bm_rbm_free_energy_rows(self._h, Xd.offset_ptr(row * self.V), B, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    # class head (bm355.h: bm_rbm_set_classes / _class_log_proba / _class_train_step / _class_train_epoch)
+    n_classes = 0
+
+    def set_classes(self, n_classes):
+        """attach a head of n_classes >= 2 classes (the variables 'U' [C, H], 'yb' [C], 'dU', 'dyb', all zero), or detach it (0)"""
+        check(self.lib.bm_rbm_set_classes(self._h, int(n_classes)))
+        self.n_classes = int(n_classes)
+
+    def class_log_proba(self, Xd, B, row=0):
+        """[B, C] float32: log p(c|x) of rows [row, row + B) of Xd (any B)"""
+        out = np.empty((B, self.n_classes), dtype=np.float32)
+        check(self.lib.bm_rbm_class_log_proba(self._h, Xd.offset_ptr(row * self.V), B, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def class_train_step(self, Xd, yd, B, lr, momentum, row=0, fetch=True):
+        """one discriminative update from rows [row, row + B) of Xd and of the int32 labels yd; fetch: returns the batch's
+        (mean log p(t|x), accuracy) of the forward pass before the update, else only queues and returns None"""
+        out = (C.c_float * 2)()
+        check(self.lib.bm_rbm_class_train_step(self._h, Xd.offset_ptr(row * self.V), yd.offset_ptr(row), B, lr, momentum,
+                                               out if fetch else None))
+        return (float(out[0]), float(out[1])) if fetch else None
+
+    def class_train_epoch(self, Xd, yd, N, batch, lr, momentum, row=0, fetch=True):
+        """N rows starting at `row` as consecutive batches of `batch` rows, driven from C; fetch: (mean log p(t|x), accuracy)
+        over the N rows, each batch's taken before its update"""
+        out = (C.c_float * 2)()
+        check(self.lib.bm_rbm_class_train_epoch(self._h, Xd.offset_ptr(row * self.V), yd.offset_ptr(row), N, batch, lr, momentum,
+                                                out if fetch else None))
+        return (float(out[0]), float(out[1])) if fetch else None
 
     def ais(self, n_betas, n_runs, k, seed, chain0=0, base_bias=None):
         """[n_runs] float32 per-chain AIS estimates of the RBM's log Z (bm_rbm_ais); base_bias [V]: the bias `a` of the

@@ -19,6 +19,7 @@ import numpy as np
 from . import _ffi
 from .base import EngineModel, is_attribute_name, run_on_engine
 from .centering import CenteredTraining
+from .classification import ClassHead
 from .engine import RbmEngine, RbmEngine64
 from .tempering import TemperedNegativePhase, resolve_ladder, run_tempered_sampler
 from .utils import epoch_iter, make_list_from, write_during_training
@@ -57,7 +58,7 @@ def clampable_only(f):
     return checked
 
 
-class BaseRBM(CenteredTraining, TemperedNegativePhase, EngineModel):
+class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
     """Restricted Boltzmann machine trained with CD-k (reference base_rbm.py:14-94)."""
 
     _V_UNIT = _ffi.UNIT_BERNOULLI
@@ -74,6 +75,9 @@ class BaseRBM(CenteredTraining, TemperedNegativePhase, EngineModel):
                  metrics_config=None, verbose=True, save_after_each_epoch=True,
                  display_filters=0, display_hidden_activations=0, v_shape=(28, 28),
                  model_path='rbm_model/', *args, **kwargs):
+        # (`n_classes` is no keyword of the reference: params.json carries it while a class head is attached, and load_model hands
+        #  it back here; the head itself is re-attached from model.npz, ClassHead._class_restore)
+        kwargs.pop('n_classes', None)
         super(BaseRBM, self).__init__(model_path=model_path, *args, **kwargs)
         self.n_visible = n_visible
         self.n_hidden = n_hidden
@@ -204,6 +208,7 @@ class BaseRBM(CenteredTraining, TemperedNegativePhase, EngineModel):
                 self._dp = parallel.DataParallelRBM(self._engine, self._rank, self._world, self.batch_size,
                                                     parallel.native_allreduce_on_engine_stream(self._engine, self._comm))
             self._apply_centering()
+            self._apply_class_head()
         else:
             raise NotImplementedError("%s: dtype must be 'float32' or 'float64' (got %r)" % (self.__class__.__name__, self.dtype))
 
@@ -237,6 +242,7 @@ class BaseRBM(CenteredTraining, TemperedNegativePhase, EngineModel):
     def _variables(self):
         out = {name: self._engine.get(name) for name, _ in self._VAR_SCOPES}
         out.update(self._centering_variables())       # (nothing unless centering is on)
+        out.update(self._class_variables())           # (nothing unless a class head is attached)
         return out
 
     def _scoped_variables(self):
@@ -250,8 +256,10 @@ class BaseRBM(CenteredTraining, TemperedNegativePhase, EngineModel):
         """checkpoint snapshot without stopping the stream (bm_rbm_stage): float32 engine only; BM355_STAGED_SAVE=0
         restores the host-side snapshot"""
         eng = self._engine
-        if not isinstance(eng, RbmEngine) or os.environ.get('BM355_STAGED_SAVE', '1') == '0' or self._centering is not None:
-            return None          # (the staged slots hold the reference's variables only: a centred model snapshots on the host)
+        if (not isinstance(eng, RbmEngine) or os.environ.get('BM355_STAGED_SAVE', '1') == '0' or self._centering is not None
+                or self._class_head is not None):
+            return None          # (the staged slots hold the reference's variables only: a centred model, or one with a class
+                                 #  head, snapshots on the host)
         eng.stage(slot)
         names = [name for name, _ in self._VAR_SCOPES]
         return lambda: {name: eng.get_staged(slot, name) for name in names}
@@ -264,6 +272,7 @@ class BaseRBM(CenteredTraining, TemperedNegativePhase, EngineModel):
         if self._engine is not None and isinstance(self._engine, (RbmEngine, RbmEngine64)) and rebuild & set(params):
             self._pending_vars = {name: self._engine.get(name) for name, _ in self._VAR_SCOPES}
             self._centering_detach()          # (the offsets wait on the host for the next engine: _apply_centering)
+            self._class_detach()              # (so do the class head's variables: _apply_class_head)
             self._engine.close()
             self._engine = None
         return self
@@ -421,6 +430,7 @@ class BaseRBM(CenteredTraining, TemperedNegativePhase, EngineModel):
     def load_model(cls, model_path):
         model = super(BaseRBM, cls).load_model(model_path)
         model._centering_restore(model._pending_vars)
+        model._class_restore(model._pending_vars)
         return model
 
     # ---- tempered negative phase (no counterpart in the reference) --------------

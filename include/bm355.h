@@ -622,6 +622,36 @@ int bm_dbm_set_sigmoid_literal(bm_dbm *h, int32_t on);
  * bm_*_apply_step, bm_*_exchange_apply_direct.  The float64 engines have no centred update. */
 int bm_rbm_set_centering(bm_rbm *h, int32_t on, float nu_v, float nu_h);
 int bm_dbm_set_centering(bm_dbm *h, int32_t on, const float *nu /* [n_layers + 1]: v, h_1, ...; read when on != 0 */);
+/* ---- Class head of a Bernoulli RBM (Larochelle & Bengio 2008, classification RBMs) ---------------------
+ * A head of C classes on the RBM's hidden layer: U [C][H] and yb [C] beside the RBM's own W, hb, vb, with
+ *   z_i = (x W)_i + hb_i,   s_c = yb_c + sum_i softplus(z_i + U[c][i]),   log p(c|x) = s_c - logsumexp_c' s_c'
+ * - the exact class posterior of the RBM over (x, one-hot y) - and the exact gradient of the batch mean of log p(t|x), which
+ * the train entries ascend (no sampling, no RNG: the call counter of the handle's streams is not touched):
+ *   coef[j][c] = 1[c == t_j] - p(c|x_j),   S[j][c][i] = sigmoid(z_ji + U[c][i]),   g = S[., t, .] - sum_c p(c|x) S[., c, .]
+ *   dW = X^T g / B,  dhb = colmean(g),  dvb = 0,  dU[c][i] = sum_j coef[j][c] S[j][c][i] / B,  dyb[c] = colmean(coef[:, c])
+ * with the update rules of bm_rbm_train_step: W and U take l2, momentum and the learning rate as W does there, hb and yb the
+ * bias rule; vb sees a zero gradient (its momentum buffer decays under the ordinary rule).  q_means follows the rule of
+ * bm_rbm_train_step on the model's class-averaged hidden means.
+ * bm_rbm_set_classes: C >= 2 attaches a head - U, yb and the momentum buffers dU, dyb, all zero, and workspaces for max_batch
+ * rows; an attached head is replaced.  C == 0 detaches it.  While a head is attached "U", "dU" ([C][H], dense, row-major), "yb",
+ * "dyb" are variables of bm_rbm_set_param / get_param / dev_ptr.  Everything else the handle does is unchanged by a head.
+ * bm_rbm_class_log_proba: log p(c|x) [B][C] of B rows (any B: the workspaces grow on demand) to the host; synchronises.
+ * bm_rbm_class_train_step: one update from X_dev [B][V] and the labels y_dev (int32 [B], device), B <= max_batch.  out2
+ * (nullable): the batch mean of log p(t|x) and the accuracy, both of the forward pass BEFORE the update; with out2 the call
+ * synchronises, without it it only queues.  bm_rbm_class_train_epoch: N rows as consecutive batches of `batch` rows, the same
+ * launches as the caller's own loop over the step entry, no host wait between batches; out2 averaged over the N rows.
+ * Every sum runs in a fixed order: the results do not depend on the run or on the tile geometry.
+ * A label outside [0, C) never indexes memory: its row contributes nothing to the update (the divisor stays B), and the
+ * next bm_rbm_sync, or the out2 fetch, returns an error once and clears the flag.
+ * Refused with an error: no head attached; Gaussian visible or Multinomial hidden units; dbm_first / dbm_last handles; and for
+ * the train entries dropout, sparsity_cost != 0, centering switched on, a handle that takes part in a data-parallel run,
+ * B > max_batch.  The float64 engines have no class head. */
+int bm_rbm_set_classes(bm_rbm *h, int32_t n_classes);
+int bm_rbm_class_log_proba(bm_rbm *h, const float *X_dev, int32_t B, float *logp_host /* [B][n_classes] */);
+int bm_rbm_class_train_step(bm_rbm *h, const float *X_dev, const int32_t *y_dev /* [B] */, int32_t B, float learning_rate,
+                            float momentum, float *out2 /* nullable */);
+int bm_rbm_class_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev /* [N] */, int64_t N, int32_t batch,
+                             float learning_rate, float momentum, float *out2 /* nullable */);
 /* ---- float64 DBM path ----------------------------------------------------------------------
  * DBM(dtype='float64') (base/mixin.py:14-25; the DBM graph is built "all in model dtype", dbm.py:294-383): the fetch sites
  * of the float32 entry points above with every buffer, hyper-parameter and random draw in double, on the FP64 tile engine of
