@@ -64,6 +64,9 @@ def lib():
         L.orc_philox_words.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
         L.orc_uniform.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, f32p]
         L.orc_normal.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, f32p]
+        L.orc_pin_log_unit_n.argtypes = [f32p, C.c_uint64, f32p]
+        L.orc_pin_sincos_2pi_n.argtypes = [f32p, C.c_uint64, f32p, f32p]
+        L.orc_box_muller_words.argtypes = [u32p, u32p, C.c_uint64, f32p, f32p]
         L.orc_rbm_chain.argtypes = [C.POINTER(RbmCfg), C.POINTER(RbmState), f32p, C.c_int, C.c_int,
                                     C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(RbmWork)]
         L.orc_rbm_raw_grads.argtypes = [C.POINTER(RbmCfg), C.POINTER(RbmWork), C.c_int, f32p]
@@ -315,6 +318,32 @@ def normal(seed, site, call, n, idx0=0):
     out = np.zeros(n, dtype=np.float32)
     lib().orc_normal(seed, site, call, idx0, n, out)
     return out
+
+
+def pin_log_unit(u):
+    """pin_log_unit elementwise (float32 in, float32 out, same shape)"""
+    u = np.ascontiguousarray(u, dtype=np.float32)
+    out = np.zeros(u.shape, dtype=np.float32)
+    lib().orc_pin_log_unit_n(u.reshape(-1), u.size, out.reshape(-1))
+    return out
+
+
+def pin_sincos_2pi(u):
+    """pin_sincos_2pi elementwise -> (sin, cos), float32, same shape"""
+    u = np.ascontiguousarray(u, dtype=np.float32)
+    sn, cs = np.zeros(u.shape, dtype=np.float32), np.zeros(u.shape, dtype=np.float32)
+    lib().orc_pin_sincos_2pi_n(u.reshape(-1), u.size, sn.reshape(-1), cs.reshape(-1))
+    return sn, cs
+
+
+def box_muller_words(x0, x1):
+    """the pair function of a Normal draw on raw Philox words (clamp included) -> (n0, n1), float32, same shape"""
+    x0 = np.ascontiguousarray(x0, dtype=np.uint32)
+    x1 = np.ascontiguousarray(x1, dtype=np.uint32)
+    assert x0.shape == x1.shape
+    n0, n1 = np.zeros(x0.shape, dtype=np.float32), np.zeros(x0.shape, dtype=np.float32)
+    lib().orc_box_muller_words(x0.reshape(-1), x1.reshape(-1), x0.size, n0.reshape(-1), n1.reshape(-1))
+    return n0, n1
 
 
 # ------------------------------------------------------------------------------ DBM
