@@ -7,7 +7,9 @@ hidden layer - U [C, H], yb [C] beside the RBM's own W, hb, vb - gives the exact
 
 and `fit_discriminative` ascends the batch mean of log p(t|x) with the exact gradient (no sampling), through the update rules
 of `fit` (bm_rbm_set_classes / bm_rbm_class_*, include/bm355.h).  The workflow: `fit(X)` unsupervised, `set_classes(C)`,
-`fit_discriminative(X, y)`, `predict(X)`.  The head is model state like the momentum buffers: U, yb, dU, dyb go into model.npz
+`fit_discriminative(X, y)`, `predict(X)`.  `fit_joint(X, y)` trains the joint p(x, y) of the same model with CD-k instead (or,
+with `discriminative_weight`, both objectives in one update) and `sample_v_given_class(y)` draws x given a class (DESIGN.md
+3.19; bm_rbm_class_joint_* / bm_rbm_class_gibbs).  The head is model state like the momentum buffers: U, yb, dU, dyb go into model.npz
 (`class_U`, `class_yb`, `class_dU`, `class_dyb`) and `n_classes` into params.json only while a head is attached; a model
 without a head is saved exactly as before.
 """
@@ -205,6 +207,110 @@ class ClassHead(object):
         eng.sync()
         self._save_model()
         return out
+
+    # ---- joint training of p(x, y)
+    def fit_joint(self, X, y, X_val=None, y_val=None, n_epochs=10, n_gibbs_steps=1, learning_rate=0.05, momentum=0.5,
+                  discriminative_weight=0., batch_size=None, verbose=None):
+        """Train the classification RBM over (x, one-hot y) with CD-k on the joint: h0 from (x, y), every Gibbs step draws v and
+        y from the hidden layer, W, hb, vb, U, yb all move.  `discriminative_weight` > 0 adds that multiple of the gradient of
+        log p(y|x) (`fit_discriminative`'s objective) in the same update: the hybrid objective of Larochelle & Bengio 2008,
+        L_disc + alpha L_gen, with discriminative_weight = 1 / alpha folded into the learning rate.
+
+        Labels, schedules, batches, validation data and the returned dict are those of `fit_discriminative` (the epoch's
+        log_proba / accuracy are taken before each update).  n_gibbs_steps : the k of CD-k, >= 1.  One seed is drawn from the
+        model's host stream, as by every stochastic public call.  Touches neither `epoch_` / `iter_`, the schedules of `fit`
+        nor the persistent chains.  Not combined with dropout, a sparsity penalty, centering or data parallelism (ValueError)."""
+        self._check_class_head('fit_joint', train=True)
+        X = self._check_class_X(X)
+        y = validate_labels(y, len(X), self._class_head['C'])
+        if (X_val is None) != (y_val is None):
+            raise ValueError('fit_joint: `X_val` and `y_val` go together')
+        if X_val is not None:
+            X_val = self._check_class_X(X_val, 'X_val')
+            y_val = validate_labels(y_val, len(X_val), self._class_head['C'])
+        bs = self.batch_size if batch_size is None else int(batch_size)
+        if not 1 <= bs <= self.batch_size:
+            raise ValueError('fit_joint: batch_size {0} outside [1, the model\'s batch_size = {1}]'.format(bs, self.batch_size))
+        if len(X) < 1 or int(n_epochs) < 0:
+            raise ValueError('fit_joint: needs at least one row and n_epochs >= 0')
+        if int(n_gibbs_steps) != n_gibbs_steps or int(n_gibbs_steps) < 1:
+            raise ValueError('fit_joint: `n_gibbs_steps` must be an integer >= 1 (got {0!r})'.format(n_gibbs_steps))
+        if not float(discriminative_weight) >= 0.:
+            raise ValueError('fit_joint: `discriminative_weight` must be >= 0 (got {0!r})'.format(discriminative_weight))
+        return self._fit_joint(X, y, X_val, y_val, int(n_epochs), int(n_gibbs_steps), make_list_from(learning_rate),
+                               make_list_from(momentum), float(discriminative_weight), bs, self.verbose if verbose is None else verbose)
+
+    @run_on_engine(check_initialized=False, update_seed=True)
+    def _fit_joint(self, X, y, X_val, y_val, n_epochs, k, lrs, moms, gamma, bs, verbose):
+        from . import _ffi
+        self.initialized_ = True
+        eng = self._on_device()
+        Xd = self._to_device(X, 'fit_X')
+        yd = _ffi.DeviceArray.from_numpy(y, np.int32)
+        names = ['log_proba', 'accuracy'] + (['val_log_proba', 'val_accuracy'] if X_val is not None else [])
+        out = {name: [] for name in names}
+        for epoch in range(n_epochs):
+            lr, mom = float(lrs[min(epoch, len(lrs) - 1)]), float(moms[min(epoch, len(moms) - 1)])
+            lp, acc = eng.class_joint_train_epoch(Xd, yd, len(X), bs, k, lr, mom, gamma)
+            out['log_proba'].append(lp)
+            out['accuracy'].append(acc)
+            if X_val is not None:
+                L = self._class_log_proba(X_val)
+                out['val_log_proba'].append(float(L[np.arange(len(y_val)), y_val].astype(np.float64).mean()))
+                out['val_accuracy'].append(float((L.argmax(axis=1) == y_val).mean()))
+            if verbose:
+                parts = ['epoch: %*d/%d' % (len(str(n_epochs)), epoch + 1, n_epochs)]
+                parts += ['%s: %s' % (m.replace('val_', 'val.'), format(out[m][-1], '.4f')) for m in names]
+                write_during_training('; '.join(parts))
+        eng.sync()
+        self._save_model()
+        return out
+
+    def sample_v_given_class(self, y, n_gibbs_steps=None, V_init=None, return_means=False):
+        """Class-conditional sampling ("show me a 7"): one chain per entry of `y`, block-Gibbs h ~ p(h | v, y), v ~ p(v | h) with
+        the class clamped.
+
+        y : [N] integer labels in [0, n_classes).  n_gibbs_steps : sweeps; None: the model's `n_gibbs_steps` of the current
+        epoch.  V_init : [N, n_visible] start of the chains; None: v_0 ~ Ber(1/2).  Returns the visible states [N, n_visible]
+        after the last sweep (with `return_means`: a pair, states and the means of the last visible pass).
+        Both layers are always sampled.  The rows are processed in slices of at most `batch_size`, every row drawing from its
+        own position of the call's random stream: the result does not depend on the slicing.  One seed is drawn from the
+        model's host stream; no parameter is changed."""
+        self._check_class_head('sample_v_given_class')
+        y = np.asarray(y)
+        y = validate_labels(y, len(y) if y.ndim == 1 else -1, self._class_head['C'])
+        if len(y) < 1:
+            raise ValueError('sample_v_given_class: `y` is empty')
+        if V_init is not None:
+            V_init = self._check_class_X(V_init, 'V_init')
+            if len(V_init) != len(y):
+                raise ValueError('`V_init` has {0} rows for {1} labels'.format(len(V_init), len(y)))
+        if n_gibbs_steps is not None and int(n_gibbs_steps) < 1:
+            raise ValueError('`n_gibbs_steps` must be >= 1 (got {0})'.format(n_gibbs_steps))
+        return self._sample_v_given_class(y, n_gibbs_steps, V_init, return_means)
+
+    @run_on_engine(update_seed=True)
+    def _sample_v_given_class(self, y, n_gibbs_steps, V_init, return_means):
+        from . import _ffi
+        eng = self._on_device()
+        k = int(n_gibbs_steps) if n_gibbs_steps is not None else self._feed()[2]
+        if k < 1:
+            raise ValueError('`n_gibbs_steps` must be >= 1 (got {0})'.format(k))
+        N = len(y)
+        yd = _ffi.DeviceArray.from_numpy(y, np.int32)
+        V0 = self._to_device(V_init) if V_init is not None else None
+        Vd = _ffi.DeviceArray((N, self.n_visible), np.float32)
+        Pd = _ffi.DeviceArray((N, self.n_visible), np.float32) if return_means else None
+        try:
+            for start in range(0, N, self.batch_size):
+                # every slice at call 0 of the call's seed and at its own rows of the stream: a row's draws depend on its index alone
+                eng.seed(self._graph_seed)
+                eng.set_row_offset(start)
+                eng.class_gibbs(V0, yd, min(self.batch_size, N - start), k, Vd, Pd, row=start)
+            eng.sync()
+        finally:
+            eng.set_row_offset(0)
+        return (Vd.numpy(), Pd.numpy()) if return_means else Vd.numpy()
 
     # ---- prediction
     def _class_log_proba(self, X):

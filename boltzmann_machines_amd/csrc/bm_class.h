@@ -14,6 +14,7 @@
 //   5. grad_kernel form 0 + bias tail, unchanged, with the input as its negative-phase visible operand: W, W^T, hb, vb
 #pragma once
 #include <hip/hip_runtime.h>
+#include "bm_rng.h"
 
 namespace bm {
 
@@ -44,6 +45,40 @@ struct ClassHeadArgs {
     int ldt, ldu, B, H, C;
     float N, l2, lr, mom;
 };
+
+// ---- joint training of p(x, y): the CD-k chain on (x, y) and the U / yb update behind it; these kernels and
+// the CB flavour of act_kernel are compiled in bm_class_joint.hip
+//   p(h_i = 1 | x, y) = sigmoid((x W)_i + hb_i + U[y][i])      act_kernel, CB flavour (LayerPass::class_bias)
+//   p(y = c | h)      = softmax_c(yb_c + sum_i h_i U[c][i])     class_draw_kernel
+//   dU[c][i] = (1/B) sum_j (1[y_j = c] h0m_ji - 1[yk_j = c] hk_ji + gamma coef_jc sigmoid(t_ji + U[c][i])),  dyb alike
+struct ClassDrawArgs {
+    const float *h;           // [B][H] pitch ldh: what the chain feeds downward (states or means)
+    const float *U;           // [C][H] pitch ldu
+    const float *yb;          // [C]
+    int *y;                   // [B] out
+    int ldh, ldu, B, H, C;
+    PhiloxKey key;            // one uniform per row, at flat index row0 + j
+    long long row0;
+};
+struct ClassJointArgs {
+    const int *y, *yk;        // [B] the labels (outside [0, C): the row is out of every sum) and the chain's last class draws
+    const float *h0m;         // [B][H] pitch ldh0: E[h | x, y]
+    const float *hk;          // [B][H] pitch ldhk: E[h | v_k, y_k], or its negation (hk_neg)
+    int ldh0, ldhk, hk_neg;
+    float gamma;              // the discriminative weight; 0: coef and T are not read
+    const float *coef;        // [B][C]
+    const float *T;           // [B][H] pitch ldt: t = x W + hb
+    float *U, *dU;            // [C][H] pitch ldu
+    float *yb, *dyb;          // [C]
+    int ldt, ldu, B, H, C;
+    float N, l2, lr, mom;
+};
+void launch_class_draw(const ClassDrawArgs &a, hipStream_t st);
+void launch_class_joint_update(const ClassJointArgs &a, hipStream_t st);
+// h0m := fma(gamma, pos + negm, h0m), elementwise over [B][H] (pitch ld each)
+void launch_class_mix(float *h0m, const float *pos, const float *negm, int ld, int B, int H, float gamma, hipStream_t st);
+// v [B][V] (pitch ld) := Ber(1/2), u < 0.5 at flat index (row0 + j) V + i
+void launch_class_v0(float *v, int ld, int B, int V, const PhiloxKey &key, long long row0, hipStream_t st);
 
 void launch_class_row(const ClassRowArgs &a, hipStream_t st);
 void launch_class_hidden(const ClassHiddenArgs &a, hipStream_t st);

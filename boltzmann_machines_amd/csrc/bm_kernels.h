@@ -126,6 +126,14 @@ struct ActArgs {
     float *cr_part;
     const float *cr_U;                   // [cr_C][I], pitch cr_ldu
     int cr_ldu, cr_C, cr_nslots;
+    // Joint training of the classification RBM (the CB flavour, act_kernel<..., CB = true>; launch_act_cb): the
+    // hidden prop-up given (x, y).  Row j takes the bias b' = __fadd_rn(bias[i], cb_U[cb_y[j]][i]) - one rounded add - where
+    // the plain pass takes bias[i] (mult == bmult == 1); everything behind it is the plain epilogue.  A label outside [0, cb_C)
+    // indexes nothing: its row takes the plain bias and *cb_bad is raised.  Null cb_y: off.
+    const int *cb_y;                     // [J]
+    const float *cb_U;                   // [cb_C][I], pitch cb_ldu
+    int cb_ldu, cb_C;
+    int *cb_bad;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -350,7 +358,7 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
 template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false,
-          bool CR = false>
+          bool CR = false, bool CB = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -399,6 +407,35 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 #pragma unroll
         for (int e = 0; e < E; ++e) sv[e] = 0.f;
     }
+    // CB: the row's class and the lane's quads of U[y_j], requested at epilogue entry like the clamp arrays (one 16-byte load per
+    // group of 4 where pitch and base allow it); a label outside [0, cb_C) loads nothing and raises the flag (every lane that
+    // sees it stores the same 1)
+    float cu[NH][4];
+    bool cb_ok = false;
+    (void)cu; (void)cb_ok;
+    if constexpr (CB) {
+        const int yj = (j < a.J) ? a.cb_y[j] : -1;
+        cb_ok = (unsigned)yj < (unsigned)a.cb_C;
+        if (j < a.J && !cb_ok && ib0 == 0) *a.cb_bad = 1;
+        const bool al_cb = ((a.cb_ldu & 3) == 0) && (((uintptr_t)a.cb_U & 15u) == 0);
+#pragma unroll
+        for (int hlf = 0; hlf < NH; ++hlf) {
+            const int ib = ib0 + 4 * hlf;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) cu[hlf][r] = 0.f;
+            if (cb_ok && ib < a.I) {
+                const float *u = a.cb_U + (size_t)yj * a.cb_ldu + ib;
+                if (al_cb && ib + 3 < a.I && (ib & 3) == 0) {
+                    const float4 tu = *reinterpret_cast<const float4 *>(u);
+                    cu[hlf][0] = tu.x; cu[hlf][1] = tu.y; cu[hlf][2] = tu.z; cu[hlf][3] = tu.w;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (ib + r < a.I) cu[hlf][r] = u[r];
+                }
+            }
+        }
+    }
     float z[E];
     lane_outputs<G>(acc, 0, z);
     float dmax = 0.f;
@@ -418,7 +455,9 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float x = (RT ? rm : a.mult) * z[4 * hlf + r];
-                const float b = (RT ? rm : a.bmult) * bs[4 * hlf + r];
+                float bv = bs[4 * hlf + r];
+                if constexpr (CB) { if (cb_ok) bv = __fadd_rn(bv, cu[hlf][r]); }       // b' = b + U[y_j][i], one rounded add
+                const float b = (RT ? rm : a.bmult) * bv;
                 m[r] = (a.kind == 0) ? (LIT ? sigmoid_literal(x + b) : (HWMATH ? sigmoid_hw(x + b) : sigmoid(x + b)))
                                      : (a.kind == 1 ? (x * sg[4 * hlf + r] + b) : (a.kind == 3 ? x + b : x));
                 s[r] = m[r];
@@ -586,7 +625,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 // MINB: HIP's second __launch_bounds__ argument = WAVES PER SIMD the register budget must allow (for the 4-wave
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
-          bool CL = false, bool RT = false, bool CR = false>
+          bool CL = false, bool RT = false, bool CR = false, bool CB = false>
 BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -662,7 +701,7 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];
@@ -2085,6 +2124,6 @@ BM_KERNEL __launch_bounds__(256) void ais_score_kernel(double *logw, int J, int 
 
 }  // namespace bm
 
-// the host side: launchers and the launch tuner.  (BM_KERNELS_ONLY - bm_grad_cen.hip, bm_class.hip: a unit that launches ONE
+// the host side: launchers and the launch tuner.  (BM_KERNELS_ONLY - bm_grad_cen.hip, bm_class.hip, bm_class_joint.hip: a unit that launches ONE
 // kernel family does not pay for every instantiation - keeps the templates of the flavour dispatcher and nothing that names a kernel)
 #include "bm_launch.h"

@@ -55,6 +55,12 @@ struct LayerPass {
         a.cr_part = part; a.ld_part = ldp; a.cr_U = U; a.cr_ldu = ldu; a.cr_C = C; a.cr_nslots = nslots(a.I);
         return *this;
     }
+    // joint chain of the classification RBM: row j's bias is bias[i] + U[y[j]][i] (one rounded add; mult == bmult == 1); a label
+    // outside [0, C) keeps the plain bias and raises *bad; the CB flavour (ActArgs::cb_y)
+    LayerPass &class_bias(const int *y, const float *U, int ldu, int C, int *bad) {
+        a.cb_y = y; a.cb_U = U; a.cb_ldu = ldu; a.cb_C = C; a.cb_bad = bad;
+        return *this;
+    }
     // metric fetch riding on a prop-up of x [J][K] (pitch ldx) through w [K][I] (pitch ldw): the row-major slot partials
     // ([ldp][rm] each) of sum softplus(z + b) for x and, behind them, for its PLL partner - the flip column drawn from
     // `flip_key`; the pass also zeroes the fetch's accumulators `zero` (ActArgs::fe_flip)

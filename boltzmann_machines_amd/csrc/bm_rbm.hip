@@ -33,6 +33,9 @@ enum : uint32_t { SITE_DROPOUT = 1, SITE_H0 = 2, SITE_V = 3, SITE_H = 4, SITE_PL
 enum : uint32_t { SITE_AIS_V0 = 7, SITE_AIS_V = 8, SITE_AIS_H = 9 };
 // bm_rbm_pt_* (bm355.h): the swap uniforms (flat index = global chain * (R - 1) + ladder pair) and the random start v_0
 enum : uint32_t { SITE_PT_SWAP = 10, SITE_PT_V0 = 11 };
+// joint training of the classification RBM: the class draw of a Gibbs step (one uniform per global row), the
+// Ber(1/2) start of bm_rbm_class_gibbs
+enum : uint32_t { SITE_CLASS_Y = 12, SITE_CLASS_V0 = 13 };
 
 }  // namespace bm
 
@@ -125,6 +128,10 @@ struct bm_rbm {
     DevBuf cls_logp, cls_prob, cls_coef, cls_rowlp, cls_rowhit;      // [cls_rows][C] x 3, [cls_rows] x 2
     DevArray<int> cls_tl, cls_bad;     // [cls_rows] checked labels; the device flag a label outside [0, C) raises
     DevArray<double> cls_acc;          // [2] sums of log p(t|x) and of the hits
+    // joint training of p(x, y), allocated at the first joint call: the chain's class draws and - the hybrid
+    // objective's discriminative launches - workspaces of their own for t, pos and negm
+    DevArray<int> cj_yk;               // [maxB]
+    Mat cj_T, cj_pos, cj_negm;         // [maxB][H]
     // the negative-phase visible operand of the fused update: vs, or - the class head's update - the input itself
     const float *neg_v = nullptr;
     int neg_v_ld = 0;
@@ -272,6 +279,7 @@ static void issue(bm_rbm *h, LayerPass p) {
     const bool xm = up && h->use_wt && h->wt_valid && !fast;
     const Operand wt = xm ? make_operand(h->Wt.p, h->Wt.ld, h->H) : Operand{nullptr, 0, 0, 0};     // W^T[i=h][k=v]
     if (h->chain.on) {          // a chained run is open: recorded with W k-major, W^T as the per-pass launch's alternative
+        if (a.cb_y) { fprintf(stderr, "bm355: a class-bias pass does not ride in a chained launch (no such kernel)\n"); abort(); }
         h->chain.rec.push_back(a);
         h->chain.alt_p.push_back(wt);
         return;
@@ -1381,6 +1389,166 @@ int bm_rbm_class_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev
         BM_TRY(class_update(h, X_dev + (size_t)s * h->V, y_dev + s, B, lr, mom, out2 != nullptr));
     }
     return out2 ? class_fetch(h, (double)N, out2) : 0;
+}
+
+// ---- joint training of p(x, y) and sampling by class (bm355.h; bm_class.h)
+static int ensure_class_joint(bm_rbm *h, bool disc) {
+    if (!h->cj_yk.p) BM_TRY(h->cj_yk.alloc(h->maxB));
+    if (disc && !h->cj_negm.p) {
+        BM_TRY(h->cj_T.alloc(h->maxB, h->H)); BM_TRY(h->cj_pos.alloc(h->maxB, h->H)); BM_TRY(h->cj_negm.alloc(h->maxB, h->H));
+    }
+    return 0;
+}
+static int check_class_joint(const bm_rbm *h, const char *what, int B, int k, float gamma) {
+    BM_TRY(check_class_train(h, what, B));
+    BM_CHECK(k >= 1, "%s: n_gibbs_steps must be >= 1 (got %d)", what, k);
+    BM_CHECK(gamma >= 0.f, "%s: disc_weight must be >= 0 (got %g)", what, (double)gamma);
+    return 0;
+}
+// the prop-up given (x, y): the hidden pass with the class bias of row j's label
+static LayerPass class_up(bm_rbm *h, int B, LayerIn vin, const int *y_dev, const LayerOut &out) {
+    return rbm_pass(h, true, B, vin, out, 1.0f).class_bias(y_dev, h->U.p, h->H, h->n_classes, h->cls_bad.p);
+}
+// y ~ p(y | h) of B rows at Gibbs step t
+static void class_draw(bm_rbm *h, LayerIn hin, int B, int t, int *y_out) {
+    ProfScope _ps(h, KC_OTHER);
+    ClassDrawArgs d;
+    memset(&d, 0, sizeof(d));
+    d.h = hin.p; d.ldh = hin.ld; d.U = h->U.p; d.ldu = h->H; d.yb = h->yb.p; d.y = y_out;
+    d.B = B; d.H = h->H; d.C = h->n_classes;
+    d.key = make_key(h, SITE_CLASS_Y, t); d.row0 = h->row0;
+    launch_class_draw(d, h->stream);
+}
+// The CD-k chain on (x, y), run_chain as per-pass launches: h0 from (X, y); per step the plain visible pass and the class draw
+// from the same hidden input, then the prop-up given (v_k, y_k).  Leaves h0m / h0s, vs, cj_yk and - last step - hneg = -h_k
+// (keep_hm: hm = h_k instead), and Xin, as run_chain does
+static int class_joint_chain(bm_rbm *h, const float *X_dev, const int *y_dev, int B, int k, bool keep_hm) {
+    ensure_wt(h);
+    h->Xin = X_dev; h->Xin_ld = h->V;
+    h->fe_in_chain = false;
+    issue(h, class_up(h, B, LayerIn{X_dev, h->V}, y_dev, rbm_out(h, 1, h->h0m.p, h->h0s.p, h->h0m.ld, SITE_H0, 0)));
+    LayerIn hstate = in_of(h->cfg.sample_h_states ? h->h0s : h->h0m);
+    for (int t = 0; t < k; ++t) {
+        const bool last = t == k - 1, neg_only = last && !keep_hm;
+        issue(h, rbm_pass(h, false, B, hstate, rbm_out(h, h->cfg.sample_v_states, nullptr, h->vs.p, h->vs.ld, SITE_V, t)));
+        class_draw(h, hstate, B, t, h->cj_yk.p);
+        LayerPass up = class_up(h, B, in_of(h->vs), h->cj_yk.p,
+                                rbm_out(h, h->cfg.sample_h_states, neg_only ? nullptr : h->hm.p, last ? nullptr : h->hs.p, h->hm.ld, SITE_H, t));
+        if (neg_only) up.negmeans_out(h->hneg.p);         // the last step as the plain update has it: only -h_k is consumed
+        h->hm_is_neg = neg_only;
+        issue(h, up);
+        hstate = in_of(h->hs);
+    }
+    return 0;
+}
+// one update of L_gen + gamma L_disc; `sum`: the batch's sums of log p(t|x) and of the hits, taken before the update, are added
+// to cls_acc.  Queues only
+static int class_joint_update(bm_rbm *h, const float *X_dev, const int *y_dev, int B, int k, float lr, float mom, float gamma, bool sum) {
+    const bool disc = gamma > 0.f;
+    BM_TRY(ensure_class_joint(h, disc));
+    if (disc || sum) {      // launches 1 - 3 of the discriminative update (3.18) into workspaces of their own; gamma == 0: 1 - 2, metric only
+        class_forward(h, X_dev, B, disc ? h->cj_T.p : nullptr, disc ? h->cj_T.ld : pad_ld(h->H), y_dev);
+        ProfScope _ps(h, KC_COLSUM);
+        if (disc) {
+            ClassHiddenArgs c;
+            memset(&c, 0, sizeof(c));
+            c.T = h->cj_T.p; c.ldt = h->cj_T.ld; c.U = h->U.p; c.ldu = h->H; c.prob = h->cls_prob.p; c.tl = h->cls_tl.p;
+            c.pos = h->cj_pos.p; c.negm = h->cj_negm.p; c.ld = h->cj_pos.ld; c.B = B; c.H = h->H; c.C = h->n_classes;
+            launch_class_hidden(c, h->stream);
+        }
+        if (sum) launch_class_sum(h->cls_rowlp.p, h->cls_rowhit.p, B, h->cls_acc.p, h->stream);
+    }
+    BM_TRY(class_joint_chain(h, X_dev, y_dev, B, k, false));
+    {   // U, yb: from the chain's own h0m (before the hybrid objective rewrites it) and -h_k, the OLD U throughout
+        ProfScope _ps(h, KC_BIAS);
+        ClassJointArgs u;
+        memset(&u, 0, sizeof(u));
+        u.y = y_dev; u.yk = h->cj_yk.p; u.h0m = h->h0m.p; u.ldh0 = h->h0m.ld; u.hk = h->hneg.p; u.ldhk = h->hneg.ld; u.hk_neg = 1;
+        u.gamma = gamma;
+        if (disc) { u.coef = h->cls_coef.p; u.T = h->cj_T.p; u.ldt = h->cj_T.ld; }
+        u.U = h->U.p; u.dU = h->dU.p; u.yb = h->yb.p; u.dyb = h->dyb.p; u.ldu = h->H; u.B = B; u.H = h->H; u.C = h->n_classes;
+        u.N = (float)B; u.l2 = h->cfg.l2; u.lr = lr; u.mom = mom;
+        launch_class_joint_update(u, h->stream);
+        // dW = X^T (h0m + gamma g) - v_k^T h_k: the positive-phase operand takes the discriminative part, the fused update stays as it is
+        if (disc) launch_class_mix(h->h0m.p, h->cj_pos.p, h->cj_negm.p, h->h0m.ld, B, h->H, gamma, h->stream);
+    }
+    launch_update_fused(h, B, lr, mom);
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+int bm_rbm_class_joint_train_step(bm_rbm *h, const float *X_dev, const int32_t *y_dev, int32_t B, int32_t k, float lr, float mom,
+                                  float disc_weight, float *out2) {
+    BM_CHECK(h && X_dev && y_dev, "null argument");
+    BM_TRY(check_class_joint(h, "bm_rbm_class_joint_train_step", B, k, disc_weight));
+    BM_TRY(check_dw(h, "bm_rbm_class_joint_train_step"));
+    if (out2) BM_HIP(hipMemsetAsync(h->cls_acc.p, 0, 2 * sizeof(double), h->stream));
+    BM_TRY(class_joint_update(h, X_dev, y_dev, B, k, lr, mom, disc_weight, out2 != nullptr));
+    return out2 ? class_fetch(h, (double)B, out2) : 0;
+}
+
+// N rows as consecutive minibatches of `batch` rows, driven from C: the launches of the caller's own loop over
+// bm_rbm_class_joint_train_step, no host wait between the batches
+int bm_rbm_class_joint_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev, int64_t N, int32_t batch, int32_t k, float lr,
+                                   float mom, float disc_weight, float *out2) {
+    BM_CHECK(h && X_dev && y_dev, "null argument");
+    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
+    BM_TRY(check_class_joint(h, "bm_rbm_class_joint_train_epoch", (int)((N < batch) ? N : batch), k, disc_weight));
+    BM_TRY(check_dw(h, "bm_rbm_class_joint_train_epoch"));
+    if (out2) BM_HIP(hipMemsetAsync(h->cls_acc.p, 0, 2 * sizeof(double), h->stream));
+    for (int64_t s = 0; s < N; s += batch) {
+        const int B = (int)((N - s < batch) ? (N - s) : batch);
+        BM_TRY(class_joint_update(h, X_dev + (size_t)s * h->V, y_dev + s, B, k, lr, mom, disc_weight, out2 != nullptr));
+    }
+    return out2 ? class_fetch(h, (double)N, out2) : 0;
+}
+
+// the chain of one joint update without the update, its states to the host (any pointer may be null); synchronises
+int bm_rbm_class_joint_chain(bm_rbm *h, const float *X_dev, const int32_t *y_dev, int32_t B, int32_t k, float *h0m_host, float *h0s_host,
+                             float *vk_host, int32_t *yk_host, float *hk_host) {
+    BM_CHECK(h && X_dev && y_dev, "null argument");
+    BM_TRY(check_class_joint(h, "bm_rbm_class_joint_chain", B, k, 0.f));
+    BM_TRY(ensure_class_joint(h, false));
+    BM_TRY(class_joint_chain(h, X_dev, y_dev, B, k, true));
+    h->call++;
+    BM_HIP(hipGetLastError());
+    const struct { float *dst; const Mat *src; int cols; } out[4] = {{h0m_host, &h->h0m, h->H}, {h0s_host, &h->h0s, h->H}, {vk_host, &h->vs, h->V},
+                                                                    {hk_host, &h->hm, h->H}};
+    for (const auto &o : out)
+        if (o.dst)
+            BM_HIP(hipMemcpy2DAsync(o.dst, (size_t)o.cols * sizeof(float), o.src->p, (size_t)o.src->ld * sizeof(float), (size_t)o.cols * sizeof(float),
+                                    (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (yk_host) BM_HIP(hipMemcpyAsync(yk_host, h->cj_yk.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_TRY(check_device_status(h));
+    return check_class_labels(h);
+}
+
+// Class-conditional sampling: n_steps of h ~ p(h | v, y), v ~ p(v | h) with y clamped, from V_dev (dense [B][V]) or - null - from
+// v_0 ~ Ber(1/2).  Per-pass fp32 launches, both layers sampled, rows drawn by global position (bm_rbm_set_row_offset)
+int bm_rbm_class_gibbs(bm_rbm *h, const float *V_dev, const int32_t *y_dev, int32_t B, int32_t n_steps, float *out_v, float *out_vmeans) {
+    BM_CHECK(h && y_dev && out_v, "null argument");
+    BM_CHECK(h->n_classes, "bm_rbm_class_gibbs: no class head is attached (bm_rbm_set_classes)");
+    BM_TRY(check_single_joint(h, "bm_rbm_class_gibbs"));
+    BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
+    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
+    ensure_wt(h);
+    LayerIn vin{V_dev, h->V};
+    if (!V_dev) {
+        launch_class_v0(h->vs.p, h->vs.ld, B, h->V, make_key(h, SITE_CLASS_V0, 0), h->row0, h->stream);
+        vin = in_of(h->vs);
+    }
+    for (int t = 0; t < n_steps; ++t) {
+        const bool last = t == n_steps - 1;
+        issue(h, class_up(h, B, vin, y_dev, rbm_out(h, 1, nullptr, h->hs.p, h->hs.ld, SITE_H, t)));
+        issue(h, rbm_pass(h, false, B, in_of(h->hs), rbm_out(h, 1, last ? out_vmeans : nullptr, last ? out_v : h->vs.p, last ? h->V : h->vs.ld, SITE_V, t),
+                          1.0f));
+        vin = in_of(h->vs);
+    }
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
 }
 
 // AIS from the base-rate model p_0(v) ~ exp(a.v) to the RBM, the hidden layer summed out (Salakhutdinov & Murray 2008):

@@ -244,6 +244,36 @@ class RbmEngine(_PtCalls):
                                                 out if fetch else None))
         return (float(out[0]), float(out[1])) if fetch else None
 
+    # joint training of p(x, y) and sampling by class (bm355.h: bm_rbm_class_joint_* / bm_rbm_class_gibbs)
+    def class_joint_train_step(self, Xd, yd, B, k, lr, momentum, disc_weight=0., row=0, fetch=True):
+        """one update of L_gen + disc_weight * L_disc (CD-k on (x, y)) from rows [row, row + B) of Xd and of the int32 labels yd;
+        fetch: the batch's (mean log p(t|x), accuracy) before the update, else only queues and returns None"""
+        out = (C.c_float * 2)()
+        check(self.lib.bm_rbm_class_joint_train_step(self._h, Xd.offset_ptr(row * self.V), yd.offset_ptr(row), B, k, lr, momentum,
+                                                     disc_weight, out if fetch else None))
+        return (float(out[0]), float(out[1])) if fetch else None
+
+    def class_joint_train_epoch(self, Xd, yd, N, batch, k, lr, momentum, disc_weight=0., row=0, fetch=True):
+        """N rows starting at `row` as consecutive batches of `batch` rows, driven from C; fetch as class_train_epoch"""
+        out = (C.c_float * 2)()
+        check(self.lib.bm_rbm_class_joint_train_epoch(self._h, Xd.offset_ptr(row * self.V), yd.offset_ptr(row), N, batch, k, lr,
+                                                      momentum, disc_weight, out if fetch else None))
+        return (float(out[0]), float(out[1])) if fetch else None
+
+    def class_joint_chain(self, Xd, yd, B, k, row=0):
+        """the chain of one joint update without the update: dict(h0m, h0s, vk, yk, hk) of host arrays"""
+        out = dict(h0m=np.empty((B, self.H), np.float32), h0s=np.empty((B, self.H), np.float32), vk=np.empty((B, self.V), np.float32),
+                   yk=np.empty(B, np.int32), hk=np.empty((B, self.H), np.float32))
+        check(self.lib.bm_rbm_class_joint_chain(self._h, Xd.offset_ptr(row * self.V), yd.offset_ptr(row), B, k,
+                                                *[out[n].ctypes.data_as(C.c_void_p) for n in ('h0m', 'h0s', 'vk', 'yk', 'hk')]))
+        return out
+
+    def class_gibbs(self, Vd, yd, B, n_steps, out_v, out_vmeans=None, row=0):
+        """n_steps of h ~ p(h | v, y), v ~ p(v | h) for rows [row, row + B): from Vd (None: Ber(1/2)) into out_v / out_vmeans"""
+        check(self.lib.bm_rbm_class_gibbs(self._h, Vd.offset_ptr(row * self.V) if Vd is not None else None, yd.offset_ptr(row), B,
+                                          n_steps, out_v.offset_ptr(row * self.V),
+                                          out_vmeans.offset_ptr(row * self.V) if out_vmeans is not None else None))
+
     def ais(self, n_betas, n_runs, k, seed, chain0=0, base_bias=None):
         """[n_runs] float32 per-chain AIS estimates of the RBM's log Z (bm_rbm_ais); base_bias [V]: the bias `a` of the
         base model p_0(v) ~ exp(a.v), None: the uniform base"""

@@ -652,6 +652,39 @@ int bm_rbm_class_train_step(bm_rbm *h, const float *X_dev, const int32_t *y_dev 
                             float momentum, float *out2 /* nullable */);
 int bm_rbm_class_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev /* [N] */, int64_t N, int32_t batch,
                              float learning_rate, float momentum, float *out2 /* nullable */);
+/* ---- joint training of the classification RBM and sampling by class --------
+ * The RBM over (x, one-hot y) with the head's own parameters, nothing new is stored:
+ *   p(h_i = 1 | x, y) = sigmoid((x W)_i + hb_i + U[y][i]),   p(x | h) = the RBM's visible pass,
+ *   p(y = c | h) = softmax_c(yb_c + sum_i h_i U[c][i])
+ * bm_rbm_class_joint_train_step: one update of L_gen + disc_weight * L_disc from X_dev [B][V] and y_dev (int32 [B], device).
+ * L_gen is the CD-k estimate of the gradient of log p(x, y): h0 from (x, y), per Gibbs step the visible pass and a class draw
+ * from the same hidden input, then the prop-up given (v_k, y_k); W, hb, vb take the update of bm_rbm_train_step on
+ * (X, h0) and (v_k, h_k), U and yb the rules of bm_rbm_class_train_step on
+ *   dU[c][i] = (1/B) sum_j (1[y_j = c] h0_ji - 1[yk_j = c] hk_ji + disc_weight coef_jc sigmoid(t_ji + U[c][i])),
+ *   dyb[c]   = (1/B) sum_j (1[y_j = c] - 1[yk_j = c] + disc_weight coef_jc).
+ * L_disc is the objective of bm_rbm_class_train_step (Larochelle & Bengio's hybrid objective L_disc + alpha L_gen with
+ * disc_weight = 1 / alpha folded into the learning rate); with disc_weight == 0 none of its launches run unless out2 is asked
+ * for.  One application of the update rules per batch; the call counter of the handle's streams advances by one per update,
+ * as in bm_rbm_train_step.  out2 as in bm_rbm_class_train_step.  bm_rbm_class_joint_train_epoch: N rows as consecutive
+ * batches, no host wait between them.  Every sum runs in a fixed order: two runs give identical bits.
+ * bm_rbm_class_joint_chain: the chain of one such update without the update (one call of the streams), its states to the
+ * host, dense - E[h | x, y] and its draw, v_k, y_k, E[h | v_k, y_k]; any pointer may be null; synchronises.
+ * bm_rbm_class_gibbs: class-conditional sampling.  n_steps of h ~ p(h | v, y), v ~ p(v | h) with y (int32 [B], device)
+ * clamped, from V_dev (dense [B][V]) or - null - from v_0 ~ Ber(1/2); the last states to out_v, the last visible means to
+ * out_vmeans (nullable), both dense device buffers.  Both layers are always sampled; rows draw by global position
+ * (bm_rbm_set_row_offset): the result does not depend on how the rows are sliced.  One call of the streams.
+ * A label outside [0, C) never indexes memory: its row takes the plain hidden bias, is out of the U / yb sums, and the next
+ * bm_rbm_sync or out2 fetch returns an error once.
+ * Refused with an error: what bm_rbm_class_train_step refuses; n_gibbs_steps < 1; disc_weight < 0. */
+int bm_rbm_class_joint_train_step(bm_rbm *h, const float *X_dev, const int32_t *y_dev /* [B] */, int32_t B, int32_t n_gibbs_steps,
+                                  float learning_rate, float momentum, float disc_weight, float *out2 /* nullable */);
+int bm_rbm_class_joint_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev /* [N] */, int64_t N, int32_t batch,
+                                   int32_t n_gibbs_steps, float learning_rate, float momentum, float disc_weight,
+                                   float *out2 /* nullable */);
+int bm_rbm_class_joint_chain(bm_rbm *h, const float *X_dev, const int32_t *y_dev, int32_t B, int32_t n_gibbs_steps,
+                             float *h0_means_host, float *h0_states_host, float *vk_host, int32_t *yk_host, float *hk_means_host);
+int bm_rbm_class_gibbs(bm_rbm *h, const float *V_dev /* nullable */, const int32_t *y_dev /* [B] */, int32_t B, int32_t n_steps,
+                       float *out_v, float *out_vmeans /* nullable */);
 /* ---- float64 DBM path ----------------------------------------------------------------------
  * DBM(dtype='float64') (base/mixin.py:14-25; the DBM graph is built "all in model dtype", dbm.py:294-383): the fetch sites
  * of the float32 entry points above with every buffer, hyper-parameter and random draw in double, on the FP64 tile engine of
