@@ -150,6 +150,9 @@ SIGNATURES = {
     'bm_rbm_class_joint_train_step': [_vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _fp],
     'bm_rbm_class_joint_train_epoch': [_vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _fp],
     'bm_rbm_class_joint_chain': [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    'bm_rbm_class_unsup_train_step': [_vp, _vp, _i32, _i32, _f32, _f32, _fp],
+    'bm_rbm_class_unsup_chain': [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    'bm_rbm_class_semi_train_epoch': [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _fp],
     'bm_rbm_class_gibbs': [_vp, _vp, _vp, _i32, _i32, _vp, _vp],
     'bm_rbm_gibbs': [_vp, _vp, _vp, _i32, _i32],
     'bm_rbm_gibbs_clamped': [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],

@@ -9,7 +9,9 @@ and `fit_discriminative` ascends the batch mean of log p(t|x) with the exact gra
 of `fit` (bm_rbm_set_classes / bm_rbm_class_*, include/bm355.h).  The workflow: `fit(X)` unsupervised, `set_classes(C)`,
 `fit_discriminative(X, y)`, `predict(X)`.  `fit_joint(X, y)` trains the joint p(x, y) of the same model with CD-k instead (or,
 with `discriminative_weight`, both objectives in one update) and `sample_v_given_class(y)` draws x given a class (DESIGN.md
-3.19; bm_rbm_class_joint_* / bm_rbm_class_gibbs).  The head is model state like the momentum buffers: U, yb, dU, dyb go into model.npz
+3.19; bm_rbm_class_joint_* / bm_rbm_class_gibbs); `fit_semi_supervised(X, y, X_unlabelled)` interleaves it with updates on unlabelled
+rows, which train the same parameters through log p(x) = log sum_y p(x, y) (bm_rbm_class_unsup_* /
+bm_rbm_class_semi_train_epoch).  The head is model state like the momentum buffers: U, yb, dU, dyb go into model.npz
 (`class_U`, `class_yb`, `class_dU`, `class_dyb`) and `n_classes` into params.json only while a head is attached; a model
 without a head is saved exactly as before.
 """
@@ -254,6 +256,82 @@ class ClassHead(object):
             lp, acc = eng.class_joint_train_epoch(Xd, yd, len(X), bs, k, lr, mom, gamma)
             out['log_proba'].append(lp)
             out['accuracy'].append(acc)
+            if X_val is not None:
+                L = self._class_log_proba(X_val)
+                out['val_log_proba'].append(float(L[np.arange(len(y_val)), y_val].astype(np.float64).mean()))
+                out['val_accuracy'].append(float((L.argmax(axis=1) == y_val).mean()))
+            if verbose:
+                parts = ['epoch: %*d/%d' % (len(str(n_epochs)), epoch + 1, n_epochs)]
+                parts += ['%s: %s' % (m.replace('val_', 'val.'), format(out[m][-1], '.4f')) for m in names]
+                write_during_training('; '.join(parts))
+        eng.sync()
+        self._save_model()
+        return out
+
+    # ---- semi-supervised training
+    def fit_semi_supervised(self, X, y, X_unlabelled, X_val=None, y_val=None, n_epochs=10, n_gibbs_steps=1, learning_rate=0.05,
+                            momentum=0.5, discriminative_weight=0., unlabelled_weight=1., batch_size=None, verbose=None):
+        """`fit_joint` on the labelled rows (X, y) with the unlabelled rows `X_unlabelled` training the same W, U, hb, vb, yb
+        through log p(x) = log sum_y p(x, y): behind every labelled batch's update one update on the next batch of unlabelled
+        rows - its positive phase over y exact (the class posterior of `predict_proba`), its negative phase the CD-k chain of
+        `fit_joint` started at a class drawn from that posterior - with the learning rate `learning_rate * unlabelled_weight`.
+        That is stochastic gradient ascent on L_sup + unlabelled_weight * L_unsup with alternating minibatches (Larochelle &
+        Bengio 2008, section 6); `unlabelled_weight = 0` is `fit_joint`.
+
+        The unlabelled rows are taken as consecutive batches of `batch_size` rows (a short last one), cyclically; the cursor
+        carries over from epoch to epoch within the call and starts at the first batch.  Everything else - labels, schedules,
+        validation data, `discriminative_weight`, the seed drawn from the model's host stream, the saved model - is
+        `fit_joint`'s.  The returned dict adds `unlabelled_entropy` and `unlabelled_confidence` per epoch: the mean entropy of
+        p(.|x) and the mean max_c p(c|x) over the epoch's unlabelled rows, each batch's taken before its update (nan for an
+        epoch without unlabelled updates).  Touches neither `epoch_` / `iter_`, the schedules of `fit` nor the persistent
+        chains.  Not combined with dropout, a sparsity penalty, centering or data parallelism (ValueError)."""
+        self._check_class_head('fit_semi_supervised', train=True)
+        X = self._check_class_X(X)
+        y = validate_labels(y, len(X), self._class_head['C'])
+        if not float(unlabelled_weight) >= 0.:
+            raise ValueError('fit_semi_supervised: `unlabelled_weight` must be >= 0 (got {0!r})'.format(unlabelled_weight))
+        X_unlabelled = self._check_class_X(X_unlabelled, 'X_unlabelled')
+        if len(X_unlabelled) < 1:
+            raise ValueError('fit_semi_supervised: `X_unlabelled` has no rows')
+        if (X_val is None) != (y_val is None):
+            raise ValueError('fit_semi_supervised: `X_val` and `y_val` go together')
+        if X_val is not None:
+            X_val = self._check_class_X(X_val, 'X_val')
+            y_val = validate_labels(y_val, len(X_val), self._class_head['C'])
+        bs = self.batch_size if batch_size is None else int(batch_size)
+        if not 1 <= bs <= self.batch_size:
+            raise ValueError('fit_semi_supervised: batch_size {0} outside [1, the model\'s batch_size = {1}]'.format(bs, self.batch_size))
+        if len(X) < 1 or int(n_epochs) < 0:
+            raise ValueError('fit_semi_supervised: needs at least one row and n_epochs >= 0')
+        if int(n_gibbs_steps) != n_gibbs_steps or int(n_gibbs_steps) < 1:
+            raise ValueError('fit_semi_supervised: `n_gibbs_steps` must be an integer >= 1 (got {0!r})'.format(n_gibbs_steps))
+        if not float(discriminative_weight) >= 0.:
+            raise ValueError('fit_semi_supervised: `discriminative_weight` must be >= 0 (got {0!r})'.format(discriminative_weight))
+        return self._fit_semi_supervised(X, y, X_unlabelled, X_val, y_val, int(n_epochs), int(n_gibbs_steps), make_list_from(learning_rate),
+                                         make_list_from(momentum), float(discriminative_weight), float(unlabelled_weight), bs,
+                                         self.verbose if verbose is None else verbose)
+
+    @run_on_engine(check_initialized=False, update_seed=True)
+    def _fit_semi_supervised(self, X, y, Xu, X_val, y_val, n_epochs, k, lrs, moms, gamma, beta, bs, verbose):
+        from . import _ffi
+        self.initialized_ = True
+        eng = self._on_device()
+        Xd = self._to_device(X, 'fit_X')
+        Xud = self._to_device(Xu, 'fit_X_unlabelled')
+        yd = _ffi.DeviceArray.from_numpy(y, np.int32)
+        names = ['log_proba', 'accuracy', 'unlabelled_entropy', 'unlabelled_confidence']
+        names += ['val_log_proba', 'val_accuracy'] if X_val is not None else []
+        out = {name: [] for name in names}
+        n_batches, n_slices, cursor = (len(X) + bs - 1) // bs, (len(Xu) + bs - 1) // bs, 0
+        for epoch in range(n_epochs):
+            lr, mom = float(lrs[min(epoch, len(lrs) - 1)]), float(moms[min(epoch, len(moms) - 1)])
+            lp, acc, ent, conf = eng.class_semi_train_epoch(Xd, yd, len(X), Xud, len(Xu), cursor, bs, k, lr, mom, gamma, beta)
+            if beta > 0.:
+                cursor = (cursor + n_batches) % n_slices
+            else:
+                ent = conf = float('nan')
+            for name, v in zip(names, (lp, acc, ent, conf)):
+                out[name].append(v)
             if X_val is not None:
                 L = self._class_log_proba(X_val)
                 out['val_log_proba'].append(float(L[np.arange(len(y_val)), y_val].astype(np.float64).mean()))

@@ -80,6 +80,44 @@ void launch_class_mix(float *h0m, const float *pos, const float *negm, int ld, i
 // v [B][V] (pitch ld) := Ber(1/2), u < 0.5 at flat index (row0 + j) V + i
 void launch_class_v0(float *v, int ld, int B, int V, const PhiloxKey &key, long long row0, hipStream_t st);
 
+// ---- semi-supervised training: one update on unlabelled rows ascends the batch mean of log p(x) = log sum_y
+// p(x, y) - the positive phase over y exact, the negative phase the CD-k chain of 3.19 started at y0 ~ p(y | x).  These kernels
+// are compiled in bm_class_semi.hip.  In stream order:
+//   1. act_kernel CR + class_row_kernel, no labels     t (the cj_T workspace), prob
+//   2. class_posterior_kernel                           y0, the row's posterior entropy and max_c p(c|x)
+//   3. the joint chain on (X, y0)                       h0s, v_k, y_k, -h_k            (its h0 pass writes h0m)
+//   4. class_marginal_kernel                            h0m := em = sum_c p_c sigmoid(t + U[c])
+//   5. class_unsup_update_kernel                        dU[c][i] = (1/B) sum_j (p_jc sigmoid(t_ji + U[c][i]) - 1[yk_j = c] hk_ji), dyb alike
+//   6. the fused update on (X, em) and (v_k, h_k)       W, W^T, hb, vb
+struct ClassPosteriorArgs {
+    const float *prob;        // [B][C]
+    int *y0;                  // [B] out: y0 ~ p(y | x)
+    float *ent, *conf;        // [B] out: -sum_c p_c log p_c, max_c p_c
+    int B, C;
+    PhiloxKey key;            // one uniform per row, at flat index row0 + j
+    long long row0;
+};
+struct ClassMarginalArgs {
+    const float *T;           // [B][H] pitch ldt
+    const float *U;           // [C][H] pitch ldu
+    const float *prob;        // [B][C]
+    float *em;                // [B][H] pitch ld
+    int ldt, ldu, ld, B, H, C;
+};
+struct ClassUnsupArgs {
+    const int *yk;            // [B] the chain's last class draws
+    const float *prob;        // [B][C]
+    const float *T;           // [B][H] pitch ldt
+    const float *hkneg;       // [B][H] pitch ldhk: -E[h | v_k, y_k] (added)
+    float *U, *dU;            // [C][H] pitch ldu
+    float *yb, *dyb;          // [C]
+    int ldt, ldhk, ldu, B, H, C;
+    float N, l2, lr, mom;
+};
+void launch_class_posterior(const ClassPosteriorArgs &a, hipStream_t st);
+void launch_class_marginal(const ClassMarginalArgs &a, hipStream_t st);
+void launch_class_unsup_update(const ClassUnsupArgs &a, hipStream_t st);
+
 void launch_class_row(const ClassRowArgs &a, hipStream_t st);
 void launch_class_hidden(const ClassHiddenArgs &a, hipStream_t st);
 void launch_class_head_update(const ClassHeadArgs &a, hipStream_t st);

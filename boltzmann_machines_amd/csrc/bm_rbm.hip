@@ -36,6 +36,8 @@ enum : uint32_t { SITE_PT_SWAP = 10, SITE_PT_V0 = 11 };
 // joint training of the classification RBM: the class draw of a Gibbs step (one uniform per global row), the
 // Ber(1/2) start of bm_rbm_class_gibbs
 enum : uint32_t { SITE_CLASS_Y = 12, SITE_CLASS_V0 = 13 };
+// semi-supervised training: the start class y0 ~ p(y | x) of an unlabelled row's chain (one uniform per global row)
+enum : uint32_t { SITE_CLASS_Y0 = 14 };
 
 }  // namespace bm
 
@@ -132,6 +134,11 @@ struct bm_rbm {
     // objective's discriminative launches - workspaces of their own for t, pos and negm
     DevArray<int> cj_yk;               // [maxB]
     Mat cj_T, cj_pos, cj_negm;         // [maxB][H]
+    // semi-supervised training, allocated at the first unlabelled call: the chain's start classes, the rows'
+    // posterior entropy and max_c p(c|x), and their sums (t lives in cj_T)
+    DevArray<int> cs_y0;               // [maxB]
+    DevBuf cs_ent, cs_conf;            // [maxB]
+    DevArray<double> cs_acc;           // [2]
     // the negative-phase visible operand of the fused update: vs, or - the class head's update - the input itself
     const float *neg_v = nullptr;
     int neg_v_ld = 0;
@@ -1395,7 +1402,8 @@ int bm_rbm_class_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev
 static int ensure_class_joint(bm_rbm *h, bool disc) {
     if (!h->cj_yk.p) BM_TRY(h->cj_yk.alloc(h->maxB));
     if (disc && !h->cj_negm.p) {
-        BM_TRY(h->cj_T.alloc(h->maxB, h->H)); BM_TRY(h->cj_pos.alloc(h->maxB, h->H)); BM_TRY(h->cj_negm.alloc(h->maxB, h->H));
+        if (!h->cj_T.p) BM_TRY(h->cj_T.alloc(h->maxB, h->H));       // (the unlabelled update may have allocated it)
+        BM_TRY(h->cj_pos.alloc(h->maxB, h->H)); BM_TRY(h->cj_negm.alloc(h->maxB, h->H));
     }
     return 0;
 }
@@ -1523,6 +1531,141 @@ int bm_rbm_class_joint_chain(bm_rbm *h, const float *X_dev, const int32_t *y_dev
     BM_HIP(hipStreamSynchronize(h->stream));
     BM_TRY(check_device_status(h));
     return check_class_labels(h);
+}
+
+// ---- semi-supervised training: the update on unlabelled rows and the interleaved epoch (bm355.h; bm_class.h)
+static int ensure_class_semi(bm_rbm *h) {
+    BM_TRY(ensure_class_joint(h, false));
+    if (!h->cj_T.p) BM_TRY(h->cj_T.alloc(h->maxB, h->H));
+    if (!h->cs_acc.p) {
+        BM_TRY(h->cs_y0.alloc(h->maxB)); BM_TRY(h->cs_ent.alloc(h->maxB)); BM_TRY(h->cs_conf.alloc(h->maxB));
+        BM_TRY(h->cs_acc.alloc(2));
+    }
+    return 0;
+}
+// launches 1 - 4 of the unlabelled update: the forward pass, the posterior draw, the chain on (X, y0), then h0m := em (AFTER the
+// chain, whose h0 pass writes h0m).  `sum`: the batch's sums of the posterior entropy and of max_c p(c|x) are added to cs_acc
+static int class_unsup_chain(bm_rbm *h, const float *X_dev, int B, int k, bool keep_hm, bool sum) {
+    class_forward(h, X_dev, B, h->cj_T.p, h->cj_T.ld, nullptr);
+    {
+        ProfScope _ps(h, KC_OTHER);
+        ClassPosteriorArgs q;
+        memset(&q, 0, sizeof(q));
+        q.prob = h->cls_prob.p; q.y0 = h->cs_y0.p; q.ent = h->cs_ent.p; q.conf = h->cs_conf.p; q.B = B; q.C = h->n_classes;
+        q.key = make_key(h, SITE_CLASS_Y0, 0); q.row0 = h->row0;
+        launch_class_posterior(q, h->stream);
+        if (sum) launch_class_sum(h->cs_ent.p, h->cs_conf.p, B, h->cs_acc.p, h->stream);
+    }
+    BM_TRY(class_joint_chain(h, X_dev, h->cs_y0.p, B, k, keep_hm));
+    ProfScope _ps(h, KC_COLSUM);
+    ClassMarginalArgs m;
+    memset(&m, 0, sizeof(m));
+    m.T = h->cj_T.p; m.ldt = h->cj_T.ld; m.U = h->U.p; m.ldu = h->H; m.prob = h->cls_prob.p;
+    m.em = h->h0m.p; m.ld = h->h0m.ld; m.B = B; m.H = h->H; m.C = h->n_classes;
+    launch_class_marginal(m, h->stream);
+    return 0;
+}
+// one update on B unlabelled rows.  Queues only
+static int class_unsup_update(bm_rbm *h, const float *X_dev, int B, int k, float lr, float mom, bool sum) {
+    BM_TRY(class_unsup_chain(h, X_dev, B, k, false, sum));
+    {   // U, yb: from prob, t and -h_k, the OLD U throughout
+        ProfScope _ps(h, KC_BIAS);
+        ClassUnsupArgs u;
+        memset(&u, 0, sizeof(u));
+        u.yk = h->cj_yk.p; u.prob = h->cls_prob.p; u.T = h->cj_T.p; u.ldt = h->cj_T.ld; u.hkneg = h->hneg.p; u.ldhk = h->hneg.ld;
+        u.U = h->U.p; u.dU = h->dU.p; u.yb = h->yb.p; u.dyb = h->dyb.p; u.ldu = h->H; u.B = B; u.H = h->H; u.C = h->n_classes;
+        u.N = (float)B; u.l2 = h->cfg.l2; u.lr = lr; u.mom = mom;
+        launch_class_unsup_update(u, h->stream);
+    }
+    launch_update_fused(h, B, lr, mom);                   // dW = (X^T em - v_k^T h_k) / B, dhb, dvb: the fused update as it is
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+// the sums of cls_acc / cs_acc to the host as means over their own rows (a null target or no rows: skipped); synchronises
+static int class_semi_fetch(bm_rbm *h, double rows, float *out_l, double rows_u, float *out_u) {
+    double hl[2] = {0.0, 0.0}, hu[2] = {0.0, 0.0};
+    if (out_l) BM_HIP(hipMemcpyAsync(hl, h->cls_acc.p, sizeof(hl), hipMemcpyDeviceToHost, h->stream));
+    if (out_u && rows_u > 0) BM_HIP(hipMemcpyAsync(hu, h->cs_acc.p, sizeof(hu), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_TRY(check_device_status(h));
+    BM_TRY(check_class_labels(h));
+    if (out_l) { out_l[0] = (float)(hl[0] / rows); out_l[1] = (float)(hl[1] / rows); }
+    if (out_u) { out_u[0] = rows_u > 0 ? (float)(hu[0] / rows_u) : 0.f; out_u[1] = rows_u > 0 ? (float)(hu[1] / rows_u) : 0.f; }
+    return 0;
+}
+
+int bm_rbm_class_unsup_train_step(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float lr, float mom, float *out2) {
+    BM_CHECK(h && X_dev, "null argument");
+    BM_TRY(check_class_joint(h, "bm_rbm_class_unsup_train_step", B, k, 0.f));
+    BM_TRY(check_dw(h, "bm_rbm_class_unsup_train_step"));
+    BM_TRY(ensure_class_semi(h));
+    if (out2) BM_HIP(hipMemsetAsync(h->cs_acc.p, 0, 2 * sizeof(double), h->stream));
+    BM_TRY(class_unsup_update(h, X_dev, B, k, lr, mom, out2 != nullptr));
+    return out2 ? class_semi_fetch(h, 0.0, nullptr, (double)B, out2) : 0;
+}
+
+// the chain and the positive operand of one unlabelled update without the update, to the host (any pointer may be null);
+// synchronises
+int bm_rbm_class_unsup_chain(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, int32_t *y0_host, float *em_host, float *h0s_host,
+                             float *vk_host, int32_t *yk_host, float *hk_host) {
+    BM_CHECK(h && X_dev, "null argument");
+    BM_TRY(check_class_joint(h, "bm_rbm_class_unsup_chain", B, k, 0.f));
+    BM_TRY(ensure_class_semi(h));
+    BM_TRY(class_unsup_chain(h, X_dev, B, k, true, false));
+    h->call++;
+    BM_HIP(hipGetLastError());
+    const struct { float *dst; const Mat *src; int cols; } out[4] = {{em_host, &h->h0m, h->H}, {h0s_host, &h->h0s, h->H}, {vk_host, &h->vs, h->V},
+                                                                    {hk_host, &h->hm, h->H}};
+    for (const auto &o : out)
+        if (o.dst)
+            BM_HIP(hipMemcpy2DAsync(o.dst, (size_t)o.cols * sizeof(float), o.src->p, (size_t)o.src->ld * sizeof(float), (size_t)o.cols * sizeof(float),
+                                    (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (y0_host) BM_HIP(hipMemcpyAsync(y0_host, h->cs_y0.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (yk_host) BM_HIP(hipMemcpyAsync(yk_host, h->cj_yk.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_TRY(check_device_status(h));
+    return check_class_labels(h);
+}
+
+// One semi-supervised epoch, driven from C with no host wait between the batches: per labelled batch the joint update with lr,
+// then one unlabelled update with lr * unl_weight on the next slice of `batch` rows of Xu (a short last slice; cyclic, from slice
+// u_slice).  unl_weight == 0: bm_rbm_class_joint_train_epoch's launches and nothing else
+int bm_rbm_class_semi_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev, int64_t N, const float *Xu_dev, int64_t Nu,
+                                  int64_t u_slice, int32_t batch, int32_t k, float lr, float mom, float disc_weight, float unl_weight,
+                                  float *out4) {
+    const char *what = "bm_rbm_class_semi_train_epoch";
+    BM_CHECK(h && X_dev && y_dev, "null argument");
+    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
+    BM_TRY(check_class_joint(h, what, (int)((N < batch) ? N : batch), k, disc_weight));
+    BM_CHECK(unl_weight >= 0.f, "%s: unl_weight must be >= 0 (got %g)", what, (double)unl_weight);
+    const bool unl = unl_weight > 0.f;
+    if (unl) {
+        BM_CHECK(Xu_dev && Nu >= 1, "%s: unl_weight > 0 needs unlabelled rows (Xu %s, Nu = %lld)", what, Xu_dev ? "given" : "null", (long long)Nu);
+        BM_CHECK(((Nu < batch) ? Nu : batch) <= h->maxB, "batch %d outside [1, max_batch=%d]", batch, h->maxB);
+    }
+    const int64_t n_slices = Nu >= 1 ? (Nu + batch - 1) / batch : 0;
+    BM_CHECK(u_slice >= 0 && u_slice < (n_slices > 1 ? n_slices : 1), "%s: u_slice %lld outside [0, %lld slices of Xu)", what, (long long)u_slice,
+             (long long)(n_slices > 1 ? n_slices : 1));
+    BM_TRY(check_dw(h, what));
+    if (unl) BM_TRY(ensure_class_semi(h));
+    const float lr_u = lr * unl_weight;
+    if (out4) {
+        BM_HIP(hipMemsetAsync(h->cls_acc.p, 0, 2 * sizeof(double), h->stream));
+        if (unl) BM_HIP(hipMemsetAsync(h->cs_acc.p, 0, 2 * sizeof(double), h->stream));
+    }
+    int64_t u = u_slice, rows_u = 0;
+    for (int64_t s = 0; s < N; s += batch) {
+        const int B = (int)((N - s < batch) ? (N - s) : batch);
+        BM_TRY(class_joint_update(h, X_dev + (size_t)s * h->V, y_dev + s, B, k, lr, mom, disc_weight, out4 != nullptr));
+        if (!unl) continue;
+        const int64_t r = u * batch;
+        const int Bu = (int)((Nu - r < batch) ? (Nu - r) : batch);
+        BM_TRY(class_unsup_update(h, Xu_dev + (size_t)r * h->V, Bu, k, lr_u, mom, out4 != nullptr));
+        rows_u += Bu;
+        u = (u + 1) % n_slices;
+    }
+    return out4 ? class_semi_fetch(h, (double)N, out4, (double)rows_u, out4 + 2) : 0;
 }
 
 // Class-conditional sampling: n_steps of h ~ p(h | v, y), v ~ p(v | h) with y clamped, from V_dev (dense [B][V]) or - null - from

@@ -268,6 +268,32 @@ class RbmEngine(_PtCalls):
                                                 *[out[n].ctypes.data_as(C.c_void_p) for n in ('h0m', 'h0s', 'vk', 'yk', 'hk')]))
         return out
 
+    # semi-supervised training (bm355.h: bm_rbm_class_unsup_* / bm_rbm_class_semi_train_epoch)
+    def class_unsup_train_step(self, Xd, B, k, lr, momentum, row=0, fetch=True):
+        """one update on the unlabelled rows [row, row + B) of Xd (exact positive phase over y, CD-k from y0 ~ p(y | x)); fetch:
+        the batch's (mean posterior entropy, mean max_c p(c|x)) before the update, else only queues and returns None"""
+        out = (C.c_float * 2)()
+        check(self.lib.bm_rbm_class_unsup_train_step(self._h, Xd.offset_ptr(row * self.V), B, k, lr, momentum, out if fetch else None))
+        return (float(out[0]), float(out[1])) if fetch else None
+
+    def class_unsup_chain(self, Xd, B, k, row=0):
+        """the chain and the positive operand of one unlabelled update without the update: dict(y0, em, h0s, vk, yk, hk)"""
+        out = dict(y0=np.empty(B, np.int32), em=np.empty((B, self.H), np.float32), h0s=np.empty((B, self.H), np.float32),
+                   vk=np.empty((B, self.V), np.float32), yk=np.empty(B, np.int32), hk=np.empty((B, self.H), np.float32))
+        check(self.lib.bm_rbm_class_unsup_chain(self._h, Xd.offset_ptr(row * self.V), B, k,
+                                                *[out[n].ctypes.data_as(C.c_void_p) for n in ('y0', 'em', 'h0s', 'vk', 'yk', 'hk')]))
+        return out
+
+    def class_semi_train_epoch(self, Xd, yd, N, Xud, Nu, u_slice, batch, k, lr, momentum, disc_weight=0., unl_weight=1., row=0, fetch=True):
+        """N labelled rows starting at `row` as consecutive batches, one unlabelled update with lr * unl_weight behind each on the
+        next slice of `batch` rows of Xud [Nu, V] (cyclic, from slice u_slice; Xud may be None while unl_weight == 0); fetch:
+        (mean log p(t|x), accuracy, mean posterior entropy, mean max_c p(c|x)), each over its own rows and before its update"""
+        out = (C.c_float * 4)()
+        check(self.lib.bm_rbm_class_semi_train_epoch(self._h, Xd.offset_ptr(row * self.V), yd.offset_ptr(row), N,
+                                                     Xud.ptr if Xud is not None else None, Nu, u_slice, batch, k, lr, momentum,
+                                                     disc_weight, unl_weight, out if fetch else None))
+        return tuple(float(v) for v in out) if fetch else None
+
     def class_gibbs(self, Vd, yd, B, n_steps, out_v, out_vmeans=None, row=0):
         """n_steps of h ~ p(h | v, y), v ~ p(v | h) for rows [row, row + B): from Vd (None: Ber(1/2)) into out_v / out_vmeans"""
         check(self.lib.bm_rbm_class_gibbs(self._h, Vd.offset_ptr(row * self.V) if Vd is not None else None, yd.offset_ptr(row), B,

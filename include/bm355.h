@@ -685,6 +685,36 @@ int bm_rbm_class_joint_chain(bm_rbm *h, const float *X_dev, const int32_t *y_dev
                              float *h0_means_host, float *h0_states_host, float *vk_host, int32_t *yk_host, float *hk_means_host);
 int bm_rbm_class_gibbs(bm_rbm *h, const float *V_dev /* nullable */, const int32_t *y_dev /* [B] */, int32_t B, int32_t n_steps,
                        float *out_v, float *out_vmeans /* nullable */);
+/* ---- semi-supervised training of the classification RBM --------------------
+ * bm_rbm_class_unsup_train_step: one update on B UNLABELLED rows X_dev [B][V]: ascent of the batch mean of
+ * log p(x) = log sum_y p(x, y) of the joint model.  The positive phase over y is exact - with p_jc = p(c | x_j) of
+ * bm_rbm_class_log_proba, t = x W + hb and S_jci = sigmoid(t_ji + U[c][i]): em_ji = sum_c p_jc S_jci = E[h_i | x_j] - the
+ * negative phase is the CD-k chain of bm_rbm_class_joint_train_step started at y0_j ~ p(y | x_j):
+ *   dW = (X^T em - v_k^T h_k) / B,  dhb = colmean(em - h_k),  dvb = colmean(X - v_k),
+ *   dU[c][i] = (1/B) sum_j (p_jc S_jci - 1[yk_j = c] hk_ji),   dyb[c] = (1/B) sum_j (p_jc - 1[yk_j = c]),
+ * all from the OLD parameters, through the update rules of bm_rbm_class_joint_train_step.  The call counter advances by one.
+ * out2 (nullable): the mean posterior entropy -sum_c p_jc log p_jc and the mean max_c p_jc of the forward pass before the
+ * update.  Every sum runs in a fixed order: two runs give identical bits.
+ * bm_rbm_class_unsup_chain: the chain and the positive operand of one such update without the update (one call of the
+ * streams), to the host, dense - y0, em, the draw of h0 ~ p(h | x, y0), v_k, y_k, E[h | v_k, y_k]; any pointer may be null;
+ * synchronises.
+ * bm_rbm_class_semi_train_epoch: N labelled rows as consecutive batches, no host wait between them; behind every labelled
+ * batch's joint update (learning_rate, disc_weight) one unlabelled update with learning_rate * unl_weight (one float product)
+ * on the next slice of Xu_dev [Nu][V]: its consecutive slices of `batch` rows (a short last one) are taken cyclically,
+ * starting at slice u_slice.  This is stochastic gradient ascent on L_sup + unl_weight * L_unsup with alternating minibatches
+ * (DESIGN.md 3.20 says why it is not one combined update).  out4 (nullable): out2 of bm_rbm_class_joint_train_epoch, then the
+ * unlabelled pair, each a mean over its own rows.  unl_weight == 0: no unlabelled launch, Xu_dev may be null, the result is
+ * bm_rbm_class_joint_train_epoch's bit for bit.
+ * Refused with an error: what bm_rbm_class_joint_train_step refuses; unl_weight < 0; Nu < 1 or a null Xu_dev while
+ * unl_weight > 0; u_slice outside [0, ceil(Nu / batch)). */
+int bm_rbm_class_unsup_train_step(bm_rbm *h, const float *X_dev, int32_t B, int32_t n_gibbs_steps, float learning_rate, float momentum,
+                                  float *out2 /* nullable */);
+int bm_rbm_class_unsup_chain(bm_rbm *h, const float *X_dev, int32_t B, int32_t n_gibbs_steps, int32_t *y0_host, float *em_host,
+                             float *h0_states_host, float *vk_host, int32_t *yk_host, float *hk_means_host);
+int bm_rbm_class_semi_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev /* [N] */, int64_t N,
+                                  const float *Xu_dev /* [Nu][V], nullable */, int64_t Nu, int64_t u_slice, int32_t batch,
+                                  int32_t n_gibbs_steps, float learning_rate, float momentum, float disc_weight, float unl_weight,
+                                  float *out4 /* nullable */);
 /* ---- float64 DBM path ----------------------------------------------------------------------
  * DBM(dtype='float64') (base/mixin.py:14-25; the DBM graph is built "all in model dtype", dbm.py:294-383): the fetch sites
  * of the float32 entry points above with every buffer, hyper-parameter and random draw in double, on the FP64 tile engine of
