@@ -5,6 +5,7 @@ package never falls back to a CPU implementation."""
 from .rbm import BernoulliRBM, MultinomialRBM, GaussianRBM, BaseRBM, logit_mean          # noqa: F401
 from .base import EngineModel, BaseModel                                  # noqa: F401
 from .utils import RNG                                                    # noqa: F401
+from .finetune import StackClassifier                                     # noqa: F401
 
 try:                                                                      # DBM lands after the RBM path
     from .dbm import DBM                                                  # noqa: F401

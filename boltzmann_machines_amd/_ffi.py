@@ -147,6 +147,12 @@ SIGNATURES = {
     'bm_rbm_class_log_proba': [_vp, _vp, _i32, _vp],
     'bm_rbm_class_train_step': [_vp, _vp, _vp, _i32, _f32, _f32, _fp],
     'bm_rbm_class_train_epoch': [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _fp],
+    'bm_rbm_backprop_down': [_vp, _vp, _i32, _vp, _i32, _vp, _i32],
+    'bm_rbm_delta_update': [_vp, _vp, _vp, _i32, _f32, _f32],
+    'bm_rbm_class_stack_train_step': [_vp, _vp, _i32, _vp, _vp, _i32, _fp, _f32, _fp],
+    'bm_rbm_class_stack_train_epoch': [_vp, _vp, _i32, _vp, _vp, _i64, _i32, _fp, _f32, _fp],
+    'bm_rbm_class_stack_log_proba': [_vp, _vp, _i32, _vp, _i32, _vp],
+    'bm_rbm_stack_transform': [_vp, _i32, _vp, _i32, _vp],
     'bm_rbm_class_joint_train_step': [_vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _fp],
     'bm_rbm_class_joint_train_epoch': [_vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _fp],
     'bm_rbm_class_joint_chain': [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],

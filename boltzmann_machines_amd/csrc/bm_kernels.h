@@ -134,6 +134,14 @@ struct ActArgs {
     const float *cb_U;                   // [cb_C][I], pitch cb_ldu
     int cb_ldu, cb_C;
     int *cb_bad;
+    // Back-propagation through a sigmoid layer (the BP flavour, act_kernel<..., BP = true>; launch_act_bp): the
+    // prop-down of a delta.  A single-segment raw pass (kind 2, mult == 1, no bias, no draw) whose stored value is
+    //   out[j][i] = __fmul_rn(__fmul_rn(z, a), __fsub_rn(1.0f, a)),   a = bp_act[j][i]       - (z * a) * (1 - a), three rounded steps
+    // with bp_act a [J][I] activation matrix of pitch bp_ld, read the way dot_mat is; a null bp_act stores z itself.  (`bias` still
+    // points at [I] floats: the side loads of every pass read it, kind 2 does not use it.)  bp == 0: off.
+    int bp;
+    const float *bp_act;
+    int bp_ld;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -358,7 +366,7 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
 template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false,
-          bool CR = false, bool CB = false>
+          bool CR = false, bool CB = false, bool BP = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -436,6 +444,30 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
             }
         }
     }
+    // BP: the lane's quads of the activation matrix, requested at epilogue entry like the clamp arrays (one 16-byte load per group
+    // of 4 where pitch and base allow it, scalar loads at ragged edges); without a matrix nothing is loaded
+    float ba[NH][4];
+    (void)ba;
+    if constexpr (BP) {
+        const bool al_bp = ((a.bp_ld & 3) == 0) && (((uintptr_t)a.bp_act & 15u) == 0);
+#pragma unroll
+        for (int hlf = 0; hlf < NH; ++hlf) {
+            const int ib = ib0 + 4 * hlf;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ba[hlf][r] = 0.f;
+            if (a.bp_act && j < a.J && ib < a.I) {
+                const float *p = a.bp_act + (size_t)j * a.bp_ld + ib;
+                if (al_bp && ib + 3 < a.I) {
+                    const float4 t = *reinterpret_cast<const float4 *>(p);
+                    ba[hlf][0] = t.x; ba[hlf][1] = t.y; ba[hlf][2] = t.z; ba[hlf][3] = t.w;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (ib + r < a.I) ba[hlf][r] = p[r];
+                }
+            }
+        }
+    }
     float z[E];
     lane_outputs<G>(acc, 0, z);
     float dmax = 0.f;
@@ -454,6 +486,12 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
             float m[4], s[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
+                if constexpr (BP) {            // delta = (z * a) * (1 - a), every step rounded once; no matrix: z itself
+                    const float zv = z[4 * hlf + r], av = ba[hlf][r];
+                    m[r] = a.bp_act ? __fmul_rn(__fmul_rn(zv, av), __fsub_rn(1.0f, av)) : zv;
+                    s[r] = m[r];
+                    continue;
+                }
                 const float x = (RT ? rm : a.mult) * z[4 * hlf + r];
                 float bv = bs[4 * hlf + r];
                 if constexpr (CB) { if (cb_ok) bv = __fadd_rn(bv, cu[hlf][r]); }       // b' = b + U[y_j][i], one rounded add
@@ -462,7 +500,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                                      : (a.kind == 1 ? (x * sg[4 * hlf + r] + b) : (a.kind == 3 ? x + b : x));
                 s[r] = m[r];
             }
-            if (a.sample) {
+            if (!BP && a.sample) {
                 if (rng_fast) {          // the 4 outputs are exactly one (precomputed) Philox block
                     const uint32_t *wds = rng.words(hlf);
                     if (a.kind == 0) {
@@ -534,6 +572,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
     if constexpr (FE) { if (a.fe_zero && i0 == 0 && j0 == 0 && tid < 6) a.fe_zero[tid] = 0.0; }     // the first tile zeroes the fetch's accumulators
     bool row_sums = a.rowacc || a.rowdot_out;
     if constexpr (RT) row_sums = row_sums || a.rowen_out;
+    if constexpr (BP) row_sums = false;
     if (row_sums) {                           // wave-uniform
         // per-lane quads (4 consecutive i, left to right); MI == 2: the lane's two quads are added
         float racc = 0.f, rdot = 0.f, racc2 = 0.f, ren = 0.f;
@@ -625,7 +664,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 // MINB: HIP's second __launch_bounds__ argument = WAVES PER SIMD the register budget must allow (for the 4-wave
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
-          bool CL = false, bool RT = false, bool CR = false, bool CB = false>
+          bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false>
 BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -701,7 +740,7 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];

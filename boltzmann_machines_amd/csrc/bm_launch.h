@@ -25,6 +25,10 @@
 //   CB   the class bias of a classification RBM's prop-up given (x, y) (ActArgs::cb_y): single-segment Bernoulli
 //        passes with mult == bmult == 1 whose row j adds U[y_j] to the bias; geometry and tile map as CR; its instantiations
 //        live in bm_class_joint.hip (launch_act_cb_as); combined with no other flavour
+//   BP   the prop-down of a delta through a sigmoid layer (ActArgs::bp / bp_act): single-segment raw passes (kind 2)
+//        with mult == 1, an x-major P (W itself), no draw and no row sums, whose epilogue multiplies by a (1 - a) of an activation
+//        matrix; geometry and tile map as CR (the plain prop-down's memo entry for the shape); its instantiations - the x-major
+//        ones only - live in bm_stack.hip (launch_act_bp_as); combined with no other flavour
 // FE, LIT and MF stage through LDS-DMA in the slab order.  dispatch_act walks the one ladder they share with the plain flavour:
 // x-major P / two K segments / one, each as the `fast` kernel (16-byte loads) or the one that passes every chunk through
 // registers (STG_DMA whatever the geometry's staging: shapes without 16-byte loads have ONE flavour).
@@ -144,14 +148,14 @@ template <class Args, class F> static inline int tune_tile_map(TuneTimer &tm, Ar
 static inline bool tune_log() { static const bool on = dbg("tune_log") != nullptr; return on; }
 
 // ---- act_kernel: one dispatcher for every flavour
-enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
+enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
 template <class G, int MINB, int STG, unsigned FL, bool SEG2, int PL>
 static inline void launch_act_kernel(bool fast, unsigned dyn_lds, hipStream_t st, const ActArgs &a, const TileMap &tmap) {
     const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
     constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0, CL = (FL & FL_CL) != 0,
-                   RT = (FL & FL_RT) != 0, CR = (FL & FL_CR) != 0, CB = (FL & FL_CB) != 0;
-    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB>), grid, blk, dyn_lds, st, a, tmap);
-    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB>), grid, blk, dyn_lds, st, a, tmap);
+                   RT = (FL & FL_RT) != 0, CR = (FL & FL_CR) != 0, CB = (FL & FL_CB) != 0, BP = (FL & FL_BP) != 0;
+    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP>), grid, blk, dyn_lds, st, a, tmap);
+    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP>), grid, blk, dyn_lds, st, a, tmap);
 }
 template <class G, int MINB, int STG, unsigned FL>
 static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, unsigned dyn_lds = 0) {
@@ -437,7 +441,33 @@ static inline void launch_act_cb(const ActArgs &a, hipStream_t st) {
     }
     launch_act_cb_as(T.geo, a, st);
 }
+// the prop-down of a delta: the geometry `geo` of the BP flavour.  Defined in bm_stack.hip, a translation unit of
+// its own for the reason bm_class.hip is one
+void launch_act_bp_as(int geo, const ActArgs &a, hipStream_t st);
+// ... per-pass fp32 launches always, on the plain flavour's memo entry for the shape (measured with the plain kernels)
+static inline void launch_act_bp(const ActArgs &a, hipStream_t st) {
+    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.row_mult || a.cr_part ||
+        a.cb_y || a.b3.K1 > 0 || a.lit || a.kind != 2 || a.mult != 1.0f || a.sample || a.rowacc || a.rowdot_out || a.negmeans ||
+        a.states || !a.means || !a.p_xm || !a.bias) {
+        fprintf(stderr, "bm355: a back-propagation pass is a single-segment raw prop-down of its own flavour (no such kernel)\n");
+        abort();
+    }
+    static const int geo_env = dbg_int("act_geo");
+    const int ov = geo_env ? geo_env : a.geo_hint;
+    if (ov) { launch_act_bp_as(ov, a, st); return; }
+    ActArgs plain = a;
+    plain.bp = 0; plain.bp_act = nullptr; plain.bp_ld = 0;
+    const Tuned T = tuned_act(plain, st);
+    if (T.xi != XI_MODEL && !a.map_xi) {
+        ActArgs a2 = a;
+        a2.map_xi = T.xi;
+        launch_act_bp_as(T.geo, a2, st);
+        return;
+    }
+    launch_act_bp_as(T.geo, a, st);
+}
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
+    if (a.bp) { launch_act_bp(a, st); return; }
     if (a.cb_y) { launch_act_cb(a, st); return; }
     if (a.cr_part) { launch_act_cr(a, st); return; }
     if (a.row_mult) { launch_act_rt(a, st); return; }

@@ -12,6 +12,7 @@
 #include "bm_pt.h"
 #include "bm_center.h"
 #include "bm_class.h"
+#include "bm_stack.h"
 
 #include <math.h>
 #include <atomic>
@@ -142,6 +143,10 @@ struct bm_rbm {
     // the negative-phase visible operand of the fused update: vs, or - the class head's update - the input itself
     const float *neg_v = nullptr;
     int neg_v_ld = 0;
+    // ... and its positive-phase hidden operand: h0m, or - the update of a layer below a class head - a delta
+    const float *pos_h = nullptr;
+    int pos_h_ld = 0;
+    Event ev_stack;                    // the hand-over of a stack's launches from this handle's stream to the next handle's
     // bm_rbm_stage / bm_rbm_get_staged: device-side copies of every variable taken in stream order (a checkpoint
     // snapshot that does not stop the stream), read back on their own stream by whoever writes the checkpoint
     struct Stage { Mat W, dW; DevBuf vb, hb, dvb, dhb, q, sigma; Event ev; bool ready = false;
@@ -381,7 +386,7 @@ static int fill_bias_fused(bm_rbm *h, int B, float lr, float mom, RbmBiasFusedAr
     memset(&a, 0, sizeof(a));
     a.X = h->Xin; a.ldx = h->Xin_ld;
     a.vs = h->neg_v ? h->neg_v : h->vs.p; a.ldv = h->neg_v ? h->neg_v_ld : h->vs.ld;
-    a.h0m = h->h0m.p; a.ldh0 = h->h0m.ld; a.B = B;
+    a.h0m = h->pos_h ? h->pos_h : h->h0m.p; a.ldh0 = h->pos_h ? h->pos_h_ld : h->h0m.ld; a.B = B;
     // the last up-pass of a plain update leaves only -h_k behind (run_chain)
     if (h->hm_is_neg) { a.hm = h->hneg.p; a.ldh = h->hneg.ld; a.hm_negated = 1; }
     else              { a.hm = h->hm.p; a.ldh = h->hm.ld; }
@@ -413,7 +418,8 @@ static void launch_update_fused(bm_rbm *h, int B, float lr, float mom) {
 
 static void fill_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom, GradArgs &g) {
     memset(&g, 0, sizeof(g));
-    g.Ppos = make_operand(h->h0m.p, h->h0m.ld, h->H);   // h0 means [k=b][i=h]           :447
+    g.Ppos = h->pos_h ? make_operand(h->pos_h, h->pos_h_ld, h->H)      // (a layer below a class head: its delta)
+                      : make_operand(h->h0m.p, h->h0m.ld, h->H);       // h0 means [k=b][i=h]           :447
     g.Qpos = make_operand(h->Xin, h->Xin_ld, h->V);     // X        [k=b][j=v]
     g.Kpos = B;
     g.Pneg = make_operand(h->hneg.p, h->hneg.ld, h->H); // -(h_k means): the chain subtracts  :448
@@ -1290,9 +1296,9 @@ int bm_rbm_set_classes(bm_rbm *h, int32_t n_classes) {
 }
 
 // the forward pass of B rows (B <= cls_rows): the CR prop-up (t into `T` when it is wanted) and the row kernel
-static void class_forward(bm_rbm *h, const float *X_dev, int B, float *T, int ldt, const int *y_dev) {
+static void class_forward(bm_rbm *h, const float *X_dev, int B, float *T, int ldt, const int *y_dev, int ldx = 0) {
     ensure_wt(h);
-    LayerPass p = rbm_pass(h, true, B, LayerIn{X_dev, h->V}, LayerOut{0, T, nullptr, ldt, PhiloxKey{0, 0, 0, 0}, 0}, 1.0f);
+    LayerPass p = rbm_pass(h, true, B, LayerIn{X_dev, ldx ? ldx : h->V}, LayerOut{0, T, nullptr, ldt, PhiloxKey{0, 0, 0, 0}, 0}, 1.0f);
     p.a.kind = 3;                                  // stores t = z + hb
     issue(h, p.class_rows(h->cls_part.p, h->cls_rows, h->U.p, h->H, h->n_classes));
     ProfScope _ps(h, KC_OTHER);
@@ -1332,8 +1338,14 @@ static int check_class_train(const bm_rbm *h, const char *what, int B) {
 }
 // one discriminative update; `sum`: the batch's sums of log p(t|x) and of the hits are added to cls_acc (taken from the forward
 // pass, before the update).  Queues only
-static int class_update(bm_rbm *h, const float *X_dev, const int *y_dev, int B, float lr, float mom, bool sum) {
-    class_forward(h, X_dev, B, h->hm.p, h->hm.ld, y_dev);
+struct StackBelow;
+static void stack_backward(bm_rbm *top, const StackBelow &below, int B);
+// `ldx`: the pitch of the input (0: dense); `below`: the layers under the head - their backward passes are queued
+// behind class_hidden_kernel, ahead of every update
+static int class_update(bm_rbm *h, const float *X_dev, const int *y_dev, int B, float lr, float mom, bool sum, int ldx = 0,
+                        const StackBelow *below = nullptr) {
+    if (!ldx) ldx = h->V;
+    class_forward(h, X_dev, B, h->hm.p, h->hm.ld, y_dev, ldx);
     {   // (event timing, bm_rbm_profile: the classes this update leaves unused tell its kernels apart - the CR pass counts as
         //  KC_UP, class_row_kernel as KC_OTHER, class_hidden_kernel as KC_COLSUM, class_head_update_kernel as KC_BIAS)
         ProfScope _ps(h, KC_COLSUM);
@@ -1344,6 +1356,7 @@ static int class_update(bm_rbm *h, const float *X_dev, const int *y_dev, int B, 
         launch_class_hidden(c, h->stream);
         if (sum) launch_class_sum(h->cls_rowlp.p, h->cls_rowhit.p, B, h->cls_acc.p, h->stream);
     }
+    if (below) stack_backward(h, *below, B);
     {
         ProfScope _ps(h, KC_BIAS);
         ClassHeadArgs u;
@@ -1355,9 +1368,9 @@ static int class_update(bm_rbm *h, const float *X_dev, const int *y_dev, int B, 
     }
     // W, W^T, hb, vb: the fused update as it is, on pos (h0m), negm (hneg, "already negated") and the input on both sides -
     // dvb = colsum(X - X) / B = 0 by construction
-    h->Xin = X_dev; h->Xin_ld = h->V;
+    h->Xin = X_dev; h->Xin_ld = ldx;
     h->hm_is_neg = true;
-    h->neg_v = X_dev; h->neg_v_ld = h->V;
+    h->neg_v = X_dev; h->neg_v_ld = ldx;
     launch_update_fused(h, B, lr, mom);
     h->neg_v = nullptr; h->neg_v_ld = 0;
     BM_HIP(hipGetLastError());
@@ -1396,6 +1409,231 @@ int bm_rbm_class_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev
         BM_TRY(class_update(h, X_dev + (size_t)s * h->V, y_dev + s, B, lr, mom, out2 != nullptr));
     }
     return out2 ? class_fetch(h, (double)N, out2) : 0;
+}
+
+// ---- fine-tuning a stack of sigmoid layers below the head by back-propagation (bm355.h; bm_stack.h)
+// Every layer is a handle of its own with a stream of its own.  The launches of a stack are ordered with EVENTS: whenever the
+// work moves from one handle to another, hand_over() records the giver's ev_stack on its stream and makes the taker's stream
+// wait for it.  One update, in issue order (L_1 .. L_D the layers below, T the top):
+//   L_1 .. L_D   the deterministic prop-up a_l = sigmoid(a_{l-1} W_l + hb_l) into the handle's hm         -> next handle
+//   T            act_kernel CR, class_row_kernel, class_hidden_kernel (class_update)
+//   T            stack_g_kernel: g = pos + negm into hs;  act_kernel BP: delta_D into L_D's h0m            -> L_D
+//   L_D .. L_2   act_kernel BP: delta_{l-1} into L_{l-1}'s h0m                                            -> L_{l-1}
+//   T            class_head_update_kernel, the fused update (class_update)                                -> L_D
+//   L_D .. L_1   the zero fill of hneg, the fused update on (a_{l-1}, delta_l) against (a_{l-1}, 0)       -> L_{l-1}
+// A backward pass reads W of the handle whose stream it runs on, and that handle's update is queued behind it on the same
+// stream: no backward pass sees a weight written in its own step.  The closing hand-overs, top down, end on L_1's stream, where
+// the next step begins: whatever that step overwrites (a_l in hm, delta_l in h0m) has been read by then.
+struct StackBelow { bm_rbm *const *l; int n; };
+
+static void hand_over(bm_rbm *from, bm_rbm *to) {
+    if (from == to) return;
+    (void)hipEventRecord(from->ev_stack, from->stream);
+    (void)hipStreamWaitEvent(to->stream, from->ev_stack, 0);
+}
+// what a layer of a stack must be (the top as well: `head`); creates the hand-over event
+static int check_stack_layer(bm_rbm *h, const char *what, int B, bool head) {
+    if (head) BM_CHECK(h->n_classes, "%s: no class head is attached to the top handle (bm_rbm_set_classes)", what);
+    BM_TRY(check_single_joint(h, what));
+    BM_CHECK(h->cfg.dropout < 0.f, "%s does not combine with dropout (this handle's is %g)", what, (double)h->cfg.dropout);
+    BM_CHECK(h->cfg.sparsity_cost == 0.f, "%s does not combine with the sparsity penalty (this handle's sparsity_cost is %g)", what,
+             (double)h->cfg.sparsity_cost);
+    BM_CHECK(!h->cen_on, "%s has no centred form; switch centering off (bm_rbm_set_centering)", what);
+    BM_CHECK(!h->xchg_used && !h->comm_stream && !h->dw_sharded && h->grad_slot == 0,
+             "%s: this handle takes part in a data-parallel run; back-propagation has no split form", what);
+    BM_CHECK(B >= 1 && B <= h->maxB, "%s: batch %d outside [1, max_batch=%d]", what, B, h->maxB);
+    BM_TRY(check_dw(h, what));
+    if (!h->ev_stack) BM_TRY(create(h->ev_stack, hipEventDisableTiming));
+    return 0;
+}
+static int check_stack(bm_rbm *top, bm_rbm *const *below, int n_below, const char *what, int B) {
+    BM_CHECK(top && n_below >= 0 && (n_below == 0 || below), "null argument");
+    for (int l = 0; l < n_below; ++l) {
+        BM_CHECK(below[l], "null argument");
+        BM_CHECK(below[l] != top, "%s: the same handle twice (layer %d is the top)", what, l);
+        for (int m = 0; m < l; ++m) BM_CHECK(below[l] != below[m], "%s: the same handle twice (layers %d and %d)", what, m, l);
+        bm_rbm *above = (l + 1 < n_below) ? below[l + 1] : top;
+        BM_CHECK(below[l]->H == above->V, "%s: the widths do not chain (layer %d has %d hidden units, the layer above it %d visible)",
+                 what, l, below[l]->H, above->V);
+        BM_TRY(check_stack_layer(below[l], what, B, false));
+    }
+    return check_stack_layer(top, what, B, true);
+}
+// the deterministic prop-up of a layer below the head: means only, into hm
+static void stack_up(bm_rbm *h, const float *in, int ldin, int B) {
+    ensure_wt(h);
+    issue(h, rbm_pass(h, true, B, LayerIn{in, ldin}, LayerOut{0, h->hm.p, nullptr, h->hm.ld, PhiloxKey{0, 0, 0, 0}, 0}, 1.0f));
+}
+// the BP pass of handle h: out = (delta W^T) .* A .* (1 - A), or delta W^T itself without A.  (vb stands in for the bias the raw
+// pass loads and does not use)
+static void stack_down(bm_rbm *h, const float *delta, int ldd, int B, const float *A, int lda, float *out, int ldo) {
+    LayerPass p = rbm_pass(h, false, B, LayerIn{delta, ldd}, LayerOut{0, out, nullptr, ldo, PhiloxKey{0, 0, 0, 0}, 0}, 1.0f);
+    p.raw();
+    p.a.bp = 1; p.a.bp_act = A; p.a.bp_ld = lda;
+    issue(h, p);
+}
+// the backward passes of one update, top down, queued behind the top's class_hidden_kernel: every delta_l lands in L_l's h0m
+static void stack_backward(bm_rbm *top, const StackBelow &s, int B) {
+    if (s.n == 0) return;
+    {
+        ProfScope _ps(top, KC_OTHER);
+        launch_stack_g(top->h0m.p, top->hneg.p, top->hs.p, top->h0m.ld, B, top->H, top->stream);
+    }
+    bm_rbm *src = top;
+    const float *delta = top->hs.p;
+    int ldd = top->hs.ld;
+    for (int l = s.n - 1; l >= 0; --l) {
+        bm_rbm *lay = s.l[l];
+        stack_down(src, delta, ldd, B, lay->hm.p, lay->hm.ld, lay->h0m.p, lay->h0m.ld);
+        hand_over(src, lay);
+        src = lay; delta = lay->h0m.p; ldd = lay->h0m.ld;
+    }
+}
+// W, W^T, hb of a layer from its input and its delta: the fused update as it is, with the delta as the positive hidden operand,
+// zeros as the negative one and the input on both visible sides - dvb = colsum(X - X) / B = 0 by construction.  Queues only
+static int delta_update(bm_rbm *h, const float *X_dev, int ldx, const float *delta, int ldd, int B, float lr, float mom) {
+    BM_HIP(hipMemsetAsync(h->hneg.p, 0, (size_t)B * h->hneg.ld * sizeof(float), h->stream));
+    h->Xin = X_dev; h->Xin_ld = ldx;
+    h->hm_is_neg = true;
+    h->neg_v = X_dev; h->neg_v_ld = ldx;
+    h->pos_h = delta; h->pos_h_ld = ldd;
+    launch_update_fused(h, B, lr, mom);
+    h->neg_v = nullptr; h->neg_v_ld = 0;
+    h->pos_h = nullptr; h->pos_h_ld = 0;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+// one update of the whole stack (the table above).  Queues only
+static int stack_update(bm_rbm *top, const StackBelow &s, const float *X_dev, const int *y_dev, int B, const float *lr, float mom, bool sum) {
+    const float *in = X_dev;
+    int ldin = s.n ? s.l[0]->V : top->V;
+    for (int l = 0; l < s.n; ++l) {
+        stack_up(s.l[l], in, ldin, B);
+        hand_over(s.l[l], (l + 1 < s.n) ? s.l[l + 1] : top);
+        in = s.l[l]->hm.p; ldin = s.l[l]->hm.ld;
+    }
+    BM_TRY(class_update(top, in, y_dev, B, lr[s.n], mom, sum, ldin, &s));
+    bm_rbm *src = top;
+    for (int l = s.n - 1; l >= 0; --l) {
+        bm_rbm *lay = s.l[l];
+        hand_over(src, lay);
+        const float *x = l ? s.l[l - 1]->hm.p : X_dev;
+        BM_TRY(delta_update(lay, x, l ? s.l[l - 1]->hm.ld : lay->V, lay->h0m.p, lay->h0m.ld, B, lr[l], mom));
+        src = lay;
+    }
+    return 0;
+}
+// the fetch of a stack's train entries: the top's, after every layer's stream has drained
+static int stack_fetch(bm_rbm *top, const StackBelow &s, double rows, float *out2) {
+    for (int l = 0; l < s.n; ++l) {
+        BM_HIP(hipStreamSynchronize(s.l[l]->stream));
+        BM_TRY(check_device_status(s.l[l]));
+    }
+    return class_fetch(top, rows, out2);
+}
+
+int bm_rbm_backprop_down(bm_rbm *h, const float *Delta_dev, int32_t B, const float *A_dev, int32_t lda, float *Out_dev, int32_t ldo) {
+    BM_CHECK(h && Delta_dev && Out_dev, "null argument");
+    BM_TRY(check_stack_layer(h, "bm_rbm_backprop_down", B, false));
+    BM_CHECK(ldo >= h->V && (!A_dev || lda >= h->V), "bm_rbm_backprop_down: a pitch below the row length %d (lda=%d, ldo=%d)", h->V,
+             (int)lda, (int)ldo);
+    stack_down(h, Delta_dev, h->H, B, A_dev, lda, Out_dev, ldo);
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+int bm_rbm_delta_update(bm_rbm *h, const float *X_dev, const float *Delta_dev, int32_t B, float lr, float mom) {
+    BM_CHECK(h && X_dev && Delta_dev, "null argument");
+    BM_TRY(check_stack_layer(h, "bm_rbm_delta_update", B, false));
+    return delta_update(h, X_dev, h->V, Delta_dev, h->H, B, lr, mom);
+}
+
+int bm_rbm_class_stack_train_step(bm_rbm *top, bm_rbm *const *below, int32_t n_below, const float *X_dev, const int32_t *y_dev, int32_t B,
+                                  const float *lr, float mom, float *out2) {
+    BM_CHECK(top && X_dev && y_dev && lr, "null argument");
+    BM_TRY(check_stack(top, below, n_below, "bm_rbm_class_stack_train_step", B));
+    const StackBelow s{below, n_below};
+    if (out2) BM_HIP(hipMemsetAsync(top->cls_acc.p, 0, 2 * sizeof(double), top->stream));
+    BM_TRY(stack_update(top, s, X_dev, y_dev, B, lr, mom, out2 != nullptr));
+    return out2 ? stack_fetch(top, s, (double)B, out2) : 0;
+}
+
+// N rows as consecutive minibatches of `batch` rows, driven from C: the launches of the caller's own loop over
+// bm_rbm_class_stack_train_step, no host wait between the batches
+int bm_rbm_class_stack_train_epoch(bm_rbm *top, bm_rbm *const *below, int32_t n_below, const float *X_dev, const int32_t *y_dev, int64_t N,
+                                   int32_t batch, const float *lr, float mom, float *out2) {
+    BM_CHECK(top && X_dev && y_dev && lr, "null argument");
+    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
+    BM_TRY(check_stack(top, below, n_below, "bm_rbm_class_stack_train_epoch", (int)((N < batch) ? N : batch)));
+    const StackBelow s{below, n_below};
+    const int V0 = n_below ? below[0]->V : top->V;
+    if (out2) BM_HIP(hipMemsetAsync(top->cls_acc.p, 0, 2 * sizeof(double), top->stream));
+    for (int64_t r = 0; r < N; r += batch) {
+        const int B = (int)((N - r < batch) ? (N - r) : batch);
+        BM_TRY(stack_update(top, s, X_dev + (size_t)r * V0, y_dev + r, B, lr, mom, out2 != nullptr));
+    }
+    return out2 ? stack_fetch(top, s, (double)N, out2) : 0;
+}
+
+// log p(c|x) of B rows through the stack (any B): slices of at most the smallest max_batch among the layers below go up the
+// stack one after the other - the hm workspaces of the layers are never outgrown, the top's grow to the slice
+int bm_rbm_class_stack_log_proba(bm_rbm *top, bm_rbm *const *below, int32_t n_below, const float *X_dev, int32_t B, float *logp_host) {
+    BM_CHECK(top && X_dev && logp_host, "null argument");
+    BM_CHECK(B >= 1, "bad row count %d", (int)B);
+    BM_TRY(check_stack(top, below, n_below, "bm_rbm_class_stack_log_proba", 1));
+    if (n_below == 0) return bm_rbm_class_log_proba(top, X_dev, B, logp_host);
+    int slice = B;
+    for (int l = 0; l < n_below; ++l) slice = std::min(slice, below[l]->maxB);
+    BM_TRY(ensure_class_rows(top, slice));
+    const size_t C = (size_t)top->n_classes;
+    for (int r = 0; r < B; r += slice) {
+        const int n = std::min(slice, B - r);
+        const float *in = X_dev + (size_t)r * below[0]->V;
+        int ldin = below[0]->V;
+        for (int l = 0; l < n_below; ++l) {
+            stack_up(below[l], in, ldin, n);
+            hand_over(below[l], (l + 1 < n_below) ? below[l + 1] : top);
+            in = below[l]->hm.p; ldin = below[l]->hm.ld;
+        }
+        class_forward(top, in, n, nullptr, pad_ld(top->H), nullptr, ldin);
+        BM_HIP(hipGetLastError());
+        BM_HIP(hipMemcpyAsync(logp_host + (size_t)r * C, top->cls_logp.p, (size_t)n * C * sizeof(float), hipMemcpyDeviceToHost, top->stream));
+        hand_over(top, below[0]);          // the next slice overwrites hm of every layer: behind this slice's readers
+    }
+    BM_HIP(hipStreamSynchronize(top->stream));
+    return 0;
+}
+
+// a_D of B rows (any B) to the device matrix A_dev [B][H_D] (dense): the prop-ups of bm_rbm_class_stack_log_proba, in its slices
+int bm_rbm_stack_transform(bm_rbm *const *below, int32_t n_below, const float *X_dev, int32_t B, float *A_dev) {
+    BM_CHECK(below && n_below >= 1 && X_dev && A_dev, "null argument");
+    BM_CHECK(B >= 1, "bad row count %d", (int)B);
+    int slice = B;
+    for (int l = 0; l < n_below; ++l) {
+        BM_CHECK(below[l], "null argument");
+        for (int m = 0; m < l; ++m) BM_CHECK(below[l] != below[m], "bm_rbm_stack_transform: the same handle twice (layers %d and %d)", m, l);
+        if (l) BM_CHECK(below[l - 1]->H == below[l]->V, "bm_rbm_stack_transform: the widths do not chain (layer %d has %d hidden units, "
+                        "the layer above it %d visible)", l - 1, below[l - 1]->H, below[l]->V);
+        BM_TRY(check_stack_layer(below[l], "bm_rbm_stack_transform", 1, false));
+        slice = std::min(slice, below[l]->maxB);
+    }
+    bm_rbm *last = below[n_below - 1];
+    for (int r = 0; r < B; r += slice) {
+        const int n = std::min(slice, B - r);
+        const float *in = X_dev + (size_t)r * below[0]->V;
+        int ldin = below[0]->V;
+        for (int l = 0; l < n_below; ++l) {
+            stack_up(below[l], in, ldin, n);
+            if (l + 1 < n_below) hand_over(below[l], below[l + 1]);
+            in = below[l]->hm.p; ldin = below[l]->hm.ld;
+        }
+        BM_HIP(hipGetLastError());
+        BM_HIP(hipMemcpy2DAsync(A_dev + (size_t)r * last->H, (size_t)last->H * sizeof(float), last->hm.p, (size_t)last->hm.ld * sizeof(float),
+                                (size_t)last->H * sizeof(float), n, hipMemcpyDeviceToDevice, last->stream));
+        hand_over(last, below[0]);
+    }
+    BM_HIP(hipStreamSynchronize(last->stream));
+    return 0;
 }
 
 // ---- joint training of p(x, y) and sampling by class (bm355.h; bm_class.h)

@@ -244,6 +244,17 @@ class RbmEngine(_PtCalls):
                                                 out if fetch else None))
         return (float(out[0]), float(out[1])) if fetch else None
 
+    # back-propagation below a class head (bm355.h: bm_rbm_backprop_down / bm_rbm_delta_update; StackEngine drives whole stacks)
+    def backprop_down(self, Dd, B, Od, Ad=None, lda=None, ldo=None):
+        """Od [B, V] (pitch ldo, default V) = (Dd [B, H] W^T) * Ad * (1 - Ad), Ad [B, V] (pitch lda, default V) an activation
+        matrix; Ad=None: Dd W^T itself.  Queues only"""
+        check(self.lib.bm_rbm_backprop_down(self._h, Dd.ptr, B, Ad.ptr if Ad is not None else None,
+                                            self.V if lda is None else int(lda), Od.ptr, self.V if ldo is None else int(ldo)))
+
+    def delta_update(self, Xd, Dd, B, lr, momentum):
+        """W, W^T, hb from the input Xd [B, V] and the delta Dd [B, H] through the fused update (dvb = 0).  Queues only"""
+        check(self.lib.bm_rbm_delta_update(self._h, Xd.ptr, Dd.ptr, B, lr, momentum))
+
     # joint training of p(x, y) and sampling by class (bm355.h: bm_rbm_class_joint_* / bm_rbm_class_gibbs)
     def class_joint_train_step(self, Xd, yd, B, k, lr, momentum, disc_weight=0., row=0, fetch=True):
         """one update of L_gen + disc_weight * L_disc (CD-k on (x, y)) from rows [row, row + B) of Xd and of the int32 labels yd;
@@ -368,6 +379,60 @@ class RbmEngine(_PtCalls):
         ms = C.c_float()
         check(self.lib.bm_rbm_timer_elapsed(self._h, C.byref(ms)))
         return float(ms.value)
+
+
+class StackEngine(object):
+    """A stack of RbmEngine handles, bottom first, the last one carrying a class head: the bm_rbm_class_stack_* entries
+    (include/bm355.h).  Owns nothing: the engines stay their owners'."""
+
+    def __init__(self, engines):
+        engines = list(engines)
+        if not engines:
+            raise ValueError('StackEngine needs at least one engine (the top)')
+        self.engines, self.top, self.below = engines, engines[-1], engines[:-1]
+        self.lib = self.top.lib
+        self.n_below = len(self.below)
+        self._below = (C.c_void_p * self.n_below)(*[e._h.value for e in self.below]) if self.n_below else None
+        self.V = engines[0].V
+
+    def _lrs(self, lr):
+        lr = [float(lr)] * len(self.engines) if np.isscalar(lr) else [float(v) for v in lr]
+        if len(lr) != len(self.engines):
+            raise ValueError('one learning rate per layer, the top last: %d values for %d layers' % (len(lr), len(self.engines)))
+        return (C.c_float * len(lr))(*lr)
+
+    def train_step(self, Xd, yd, B, lr, momentum, row=0, fetch=True):
+        """one update of the whole stack from rows [row, row + B); lr: a number or one value per layer, the top last; fetch as
+        RbmEngine.class_train_step (without it the call only queues: sync() before reading variables)"""
+        out = (C.c_float * 2)()
+        check(self.lib.bm_rbm_class_stack_train_step(self.top._h, self._below, self.n_below, Xd.offset_ptr(row * self.V),
+                                                     yd.offset_ptr(row), B, self._lrs(lr), momentum, out if fetch else None))
+        return (float(out[0]), float(out[1])) if fetch else None
+
+    def train_epoch(self, Xd, yd, N, batch, lr, momentum, row=0, fetch=True):
+        """N rows starting at `row` as consecutive batches of `batch` rows, driven from C"""
+        out = (C.c_float * 2)()
+        check(self.lib.bm_rbm_class_stack_train_epoch(self.top._h, self._below, self.n_below, Xd.offset_ptr(row * self.V),
+                                                      yd.offset_ptr(row), N, batch, self._lrs(lr), momentum, out if fetch else None))
+        return (float(out[0]), float(out[1])) if fetch else None
+
+    def log_proba(self, Xd, B, row=0):
+        """[B, C] float32: log p(c|x) of rows [row, row + B) of Xd through the stack (any B)"""
+        out = np.empty((B, self.top.n_classes), dtype=np.float32)
+        check(self.lib.bm_rbm_class_stack_log_proba(self.top._h, self._below, self.n_below, Xd.offset_ptr(row * self.V), B,
+                                                    out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def transform(self, Xd, B, Ad, row=0):
+        """a_D of rows [row, row + B) of Xd into the DeviceArray Ad [B, V of the top] (a stack without layers below: a copy)"""
+        if not self.n_below:
+            raise ValueError('a stack without layers below the top has a_D = x')
+        check(self.lib.bm_rbm_stack_transform(self._below, self.n_below, Xd.offset_ptr(row * self.V), B, Ad.ptr))
+
+    def sync(self):
+        """every layer's stream; the top last (it reports a label outside [0, C))"""
+        for e in self.engines:
+            e.sync()
 
 
 class RbmEngine64(object):

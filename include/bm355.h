@@ -652,6 +652,45 @@ int bm_rbm_class_train_step(bm_rbm *h, const float *X_dev, const int32_t *y_dev 
                             float momentum, float *out2 /* nullable */);
 int bm_rbm_class_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *y_dev /* [N] */, int64_t N, int32_t batch,
                              float learning_rate, float momentum, float *out2 /* nullable */);
+/* ---- Fine-tuning a stack of layers below the head by back-propagation -------
+ * D >= 0 feature layers under a classification RBM, every layer a bm_rbm handle of its own (Bernoulli-Bernoulli, float32):
+ *   a_0 = x,   a_l = sigmoid(a_{l-1} W_l + hb_l)  (l = 1..D; means only, nothing is sampled)
+ *   log p(c|x) = the exact posterior above of the top handle on the input a_D
+ * The train entries ascend the batch mean of log p(t|x).  With g = pos + negm of the top handle and ' marking pre-update values:
+ *   delta_D = (g W_top'^T) .* a_D .* (1 - a_D),      delta_l = (delta_{l+1} W_{l+1}'^T) .* a_l .* (1 - a_l)
+ *   layer l:  dW_l = a_{l-1}^T delta_l / B,  dhb_l = colmean(delta_l),  dvb_l = 0;   top: bm_rbm_class_train_step on the input a_D
+ * W, W^T, hb and their momentum buffers of a layer go through that handle's own fused update (its l2, its rules); its vb sees a
+ * zero gradient.  Every backward pass reads pre-update weights.  The handles keep their streams; the launches are ordered across
+ * them with events, so the caller needs no synchronisation between the handles.
+ * bm_rbm_backprop_down: Out [B][V] (pitch ldo) = (Delta [B][H] W^T) .* A .* (1 - A) of handle h, A [B][V] (pitch lda) an activation
+ *   matrix; A_dev == NULL stores Delta W^T itself.  Each product and the difference are rounded once: (z * a) * (1 - a).  Any
+ *   B <= max_batch.  Queues only.
+ * bm_rbm_delta_update: W, W^T, hb of handle h from its input X [B][V] and a delta [B][H] (both dense): dW = X^T Delta / B,
+ *   dhb = colmean(Delta), dvb = 0, through the fused update of bm_rbm_train_step.  Queues only.
+ * bm_rbm_class_stack_train_step: one update of the whole stack.  `below`: the n_below handles under the top, bottom first;
+ *   learning_rate [n_below + 1]: one value per layer, the top's last.  out2 as in bm_rbm_class_train_step: with it the call waits
+ *   for every layer's stream, without it it only queues (then synchronise EVERY handle before reading its variables).  n_below == 0
+ *   issues exactly the launches of bm_rbm_class_train_step.  bm_rbm_class_stack_train_epoch: N rows as consecutive batches of
+ *   `batch` rows, the same launches as the caller's loop over the step entry, no host wait between the batches.
+ * bm_rbm_class_stack_log_proba: log p(c|x) [B][C] of B rows (any B: rows go up the stack in slices no longer than the smallest
+ *   max_batch below the top) to the host; synchronises.
+ * A label outside [0, C) behaves as above: its row has zero g, hence a zero delta in every layer, and the flag is raised.
+ * Refused with an error, for every handle of the stack: what bm_rbm_class_train_step refuses (Gaussian, Multinomial, dbm_first /
+ * dbm_last, dropout, sparsity_cost != 0, centering, a data-parallel handle, B > max_batch); widths that do not chain
+ * (H of a layer != V of the one above); the same handle twice; no head on the top. */
+int bm_rbm_backprop_down(bm_rbm *h, const float *Delta_dev, int32_t B, const float *A_dev /* nullable */, int32_t lda, float *Out_dev,
+                         int32_t ldo);
+int bm_rbm_delta_update(bm_rbm *h, const float *X_dev, const float *Delta_dev, int32_t B, float learning_rate, float momentum);
+int bm_rbm_class_stack_train_step(bm_rbm *top, bm_rbm *const *below /* [n_below], bottom first */, int32_t n_below, const float *X_dev,
+                                  const int32_t *y_dev /* [B] */, int32_t B, const float *learning_rate /* [n_below + 1] */,
+                                  float momentum, float *out2 /* nullable */);
+int bm_rbm_class_stack_train_epoch(bm_rbm *top, bm_rbm *const *below, int32_t n_below, const float *X_dev, const int32_t *y_dev /* [N] */,
+                                   int64_t N, int32_t batch, const float *learning_rate /* [n_below + 1] */, float momentum,
+                                   float *out2 /* nullable */);
+int bm_rbm_class_stack_log_proba(bm_rbm *top, bm_rbm *const *below, int32_t n_below, const float *X_dev, int32_t B,
+                                 float *logp_host /* [B][n_classes] */);
+/* a_D of B rows (any B, in the same slices) into the DEVICE matrix A_dev [B][H_D] (dense); n_below >= 1; synchronises */
+int bm_rbm_stack_transform(bm_rbm *const *below, int32_t n_below, const float *X_dev, int32_t B, float *A_dev);
 /* ---- joint training of the classification RBM and sampling by class --------
  * The RBM over (x, one-hot y) with the head's own parameters, nothing new is stored:
  *   p(h_i = 1 | x, y) = sigmoid((x W)_i + hb_i + U[y][i]),   p(x | h) = the RBM's visible pass,
