@@ -92,6 +92,7 @@ SIGNATURES = {
     'bm_rbm_set_fast_binary': [_vp, _i32],
     'bm_rbm_set_centering': [_vp, _i32, C.c_float, C.c_float],
     'bm_dbm_set_centering': [_vp, _i32, C.POINTER(C.c_float)],
+    'bm_rbm_set_fast_weights': [_vp, _i32, C.c_float, C.c_float],
     'bm_rbm64_create': [C.POINTER(RbmConfig), C.POINTER(C.c_double), C.POINTER(_vp)],
     'bm_rbm_multinomial_limit': [C.POINTER(C.c_int64)],
     'bm_rbm64_multinomial_limit': [C.POINTER(C.c_int64)],

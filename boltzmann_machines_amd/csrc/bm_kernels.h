@@ -12,6 +12,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include "bm_gemm.h"
 #include "bm_bf3.h"
 #include "bm_numerics.h"
@@ -1129,10 +1130,19 @@ __device__ __forceinline__ const GradCen &grad_cen_of(const GradCen &c) { return
 // The flavour is compile-time, as FE / LIT / MF / CL / RT are for act_kernel: the plain instantiations (CENP empty) carry none
 // of the centred code and keep their kernel arguments; the centred ones (CENP = GradCen) take a GradCen behind them.  The
 // fused-bias tail (nbias) does not exist in the centred flavour: the tiles need the bias gradients before the tail would form them.
+// The fast-weights flavour (CENP = GradFast): beside the regular update of W the epilogue moves the fast set,
+// wf <- decay * wf + fast_lr * g0 with g0 the normalised gradient before l2 and penalty, and stores the effective weights
+// we = w_new + wf and, where Wet is not null, their transpose (the pairing of the W^T write).  Wf and We share the pitch ldf.
+// Wf is read in the epilogue, next to its use: the lane already holds 2 x 16 values of W / dW from the side fetch, and the
+// eight values of one j live only from their load to their store.  The fused bias tail stays legal: the tiles need nothing of it.
+struct GradFast { float *Wf, *We, *Wet; int ldf, ldet; float fast_lr, fast_decay; };
+__device__ __forceinline__ const GradFast &grad_fast_of(const GradFast &f) { return f; }
+template <class T, class... P> struct grad_has { static constexpr int value = 0; };
+template <class T, class P0, class... P> struct grad_has<T, P0, P...> { static constexpr int value = (std::is_same<T, P0>::value ? 1 : 0) + grad_has<T, P...>::value; };
 template <class G, bool FAST, int ABL = 0, int STG = STG_DMA, int MINB = 1, class... CENP>
 BM_KERNEL __launch_bounds__(G::NT, MINB) void grad_kernel(GradArgs a, TileMap tmap, CENP... cenp) {
-    constexpr int CEN = (int)sizeof...(CENP);
-    static_assert(CEN <= 1, "grad_kernel: at most one GradCen");
+    constexpr int CEN = grad_has<GradCen, CENP...>::value, FW = grad_has<GradFast, CENP...>::value;
+    static_assert(sizeof...(CENP) <= 1 && CEN + FW == (int)sizeof...(CENP), "grad_kernel: at most one GradCen or one GradFast");
     constexpr int TI = G::TI, NJ = G::NJ;
     static_assert(G::MI == 2 && G::TI == 64 && G::TJ == 64, "grad_kernel: 64 x 64 tiles, 8 consecutive outputs per lane");
     __shared__ __attribute__((aligned(16))) float smem[G::SMEM_FLOATS];
@@ -1208,6 +1218,7 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void grad_kernel(GradArgs a, TileMap tm
     if (!a.fetch_at_fill) { side.on = a.fused != 0; side.fetch(); }
     const DivBy divN(a.N), divM(a.M);
     float wt[NJ][8];                // updated W values of the lane's j (NJ == 2: adjacent columns of Wt)
+    float et[FW ? NJ : 1][FW ? 8 : 1];      // fast-weights flavour: the effective values, for Wet
     bool jok[NJ];
     float coi[CEN ? 8 : 1], cgi[CEN ? 8 : 1];
     if constexpr (CEN != 0) {
@@ -1256,6 +1267,20 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void grad_kernel(GradArgs a, TileMap tm
 #pragma unroll
             for (int e = 0; e < 8; ++e) gr[e] = __fsub_rn(gr[e], __fadd_rn(__fmul_rn(oj, cgi[e]), __fmul_rn(gj, coi[e])));
         }
+        float fv[FW ? 8 : 1];
+        if constexpr (FW != 0) {            // wf <- decay * wf + fast_lr * g0, from the gradient before l2 and penalty
+            const GradFast &f = grad_fast_of(cenp...);
+            const size_t of = (size_t)j * f.ldf + ib0;
+            if (side.vec8 && (f.ldf & 3) == 0) {
+                const float4 f0 = *reinterpret_cast<const float4 *>(f.Wf + of), f1 = *reinterpret_cast<const float4 *>(f.Wf + of + 4);
+                fv[0] = f0.x; fv[1] = f0.y; fv[2] = f0.z; fv[3] = f0.w; fv[4] = f1.x; fv[5] = f1.y; fv[6] = f1.z; fv[7] = f1.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) fv[e] = (ib0 + e < a.I) ? f.Wf[of + e] : 0.f;
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) fv[e] = __fadd_rn(__fmul_rn(f.fast_decay, fv[e]), __fmul_rn(f.fast_lr, gr[e]));
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             apply_w_update(gr[e], pe[e], a.l2, a.lr, a.mom, wv[e], dv[e]);
@@ -1270,6 +1295,40 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void grad_kernel(GradArgs a, TileMap tm
 #pragma unroll
             for (int e = 0; e < 8; ++e)
                 if (ib0 + e < a.I) { a.W[o + e] = wv[e]; a.dW[o + e] = dv[e]; }
+        }
+        if constexpr (FW != 0) {            // we = w_new + wf
+            const GradFast &f = grad_fast_of(cenp...);
+            const size_t of = (size_t)j * f.ldf + ib0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) et[n][e] = __fadd_rn(wv[e], fv[e]);
+            if (side.vec8 && (f.ldf & 3) == 0) {
+                stream_store4(f.Wf + of, fv[0], fv[1], fv[2], fv[3]);
+                stream_store4(f.Wf + of + 4, fv[4], fv[5], fv[6], fv[7]);
+                stream_store4(f.We + of, et[n][0], et[n][1], et[n][2], et[n][3]);
+                stream_store4(f.We + of + 4, et[n][4], et[n][5], et[n][6], et[n][7]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (ib0 + e < a.I) { f.Wf[of + e] = fv[e]; f.We[of + e] = et[n][e]; }
+            }
+        }
+    }
+    if constexpr (FW != 0) {
+        const GradFast &f = grad_fast_of(cenp...);
+        if (a.fused && f.Wet) {                       // the effective transpose: the pairing of the W^T write below
+            const int ja = side.jb[0];
+            const bool pair = NJ == 2 && jok[0] && jok[NJ - 1] && ((f.ldet & 1) == 0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                if (ib0 + e >= a.I) break;
+                float *dst = f.Wet + (size_t)(ib0 + e) * f.ldet + ja;
+                if (pair) {
+                    stream_store2(dst, et[0][e], et[NJ - 1][e]);
+                } else {
+                    if (jok[0]) dst[0] = et[0][e];
+                    if (NJ == 2 && jok[NJ - 1]) dst[1] = et[NJ - 1][e];
+                }
+            }
         }
     }
     if (a.fused && a.Wt) {                            // maintained transpose (prop-down P operand)

@@ -542,18 +542,28 @@ static inline Tuned tune_grad_shape(const GradArgs &g, hipStream_t st) {
                 g.I, g.J, g.Kpos, g.Kneg, g.form, g.fused, T.geo, us[0], us[1], us[2], us[3], us[4], T.xi == XI_SLAB ? 9 : T.xi, xi_us[4], xi_us[0], xi_us[1], xi_us[2], xi_us[3]);
     return T;
 }
-// cen: the centred flavour (fused, no bias tail - its callers see to both)
-static inline void launch_grad(const GradArgs &g_in, hipStream_t st, const GradCen *cen = nullptr) {
+// fast-weights flavour (grad_kernel<..., GradFast>): as the centred one, the geometries 4 and 8 with DMA staging in
+// a translation unit of its own (bm_grad_fast.hip); the bias tail and the penalty are both legal in it
+void launch_grad_fast(int geo, const GradArgs &g, const GradFast &f, hipStream_t st);
+// cen: the centred flavour (fused, no bias tail - its callers see to both); fw: the fast-weights flavour (fused); never both
+static inline void launch_grad(const GradArgs &g_in, hipStream_t st, const GradCen *cen = nullptr, const GradFast *fw = nullptr) {
     static const int fetch_env = std::max(0, dbg_int("grad_fetch")), geo_env = dbg_int("grad_geo");   // overrides (experiments)
     GradArgs g = g_in;
     g.fetch_at_fill = fetch_env;      // measured (same box, 784x1024x512): epilogue 66.6 us/update, fill 67.5
-    if (geo_env) { if (cen) launch_grad_cen(geo_env, g, *cen, st); else launch_grad_as(geo_env, g, st); return; }
+    if (geo_env) {
+        if (fw) launch_grad_fast(geo_env, g, *fw, st);
+        else if (cen) launch_grad_cen(geo_env, g, *cen, st);
+        else launch_grad_as(geo_env, g, st);
+        return;
+    }
     static TuneMemo<6> memo;
     // (the centred flavour shares the plain flavour's entry for the shape, as CL and RT do for act_kernel)
     const Tuned T = memo.get({g.I, g.J, g.Kpos, g.Kneg, g.form | (g.fused << 1), g.ldw}, [&] { return tune_grad_shape(g, st); });
     if (T.xi != XI_MODEL && !g.map_xi) g.map_xi = T.xi;
     // (a tuned 8-wave geometry - 8, 9, 108, 208 - takes the centred 8-wave kernel, the others the 4-wave one)
-    if (cen) launch_grad_cen((T.geo == 8 || T.geo == 9 || T.geo == 108 || T.geo == 208) ? 8 : 4, g, *cen, st);
+    const int geo48 = (T.geo == 8 || T.geo == 9 || T.geo == 108 || T.geo == 208) ? 8 : 4;
+    if (fw) launch_grad_fast(geo48, g, *fw, st);
+    else if (cen) launch_grad_cen(geo48, g, *cen, st);
     else launch_grad_as(T.geo, g, st);
 }
 

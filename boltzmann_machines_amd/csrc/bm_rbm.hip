@@ -5,12 +5,14 @@
 // (train op + metrics), :329-413 (propagations, Gibbs chain), rbm/rbm.py:17-22,
 // :101-116 (free energies, Gaussian input scaling), layers.py:39-51,73-89.
 #include "../../include/bm355.h"
+#include <cmath>
 #include "bm_common.h"
 #include "bm_kernels.h"
 #include "bm_chain.h"
 #include "bm_pass.h"
 #include "bm_pt.h"
 #include "bm_center.h"
+#include "bm_fast.h"
 #include "bm_class.h"
 #include "bm_stack.h"
 
@@ -90,6 +92,15 @@ struct bm_rbm {
     DevBuf ov, oh;            // [V], [H]
     DevBuf cen_gv, cen_gh;    // [V], [H] plain bias gradients of the running update
     DevBuf cen_a;             // [4][maxB] row scalars: X, v_k, h0, h_k
+    // fast-weights PCD (bm_rbm_set_fast_weights; bm_fast.h): the fast set and the effective copies We = W + Wf,
+    // We^T (where the handle keeps W^T), vbe, hbe, allocated when the mode is first switched on and released when it goes off.
+    // eff_valid is to the effective copies what wt_valid is to W^T: set by the fast-weights update, cleared by every other
+    // writer of W, vb or hb; ensure_eff rebuilds them.  eff_now: the passes described and issued now read the effective set
+    // (EffScope: bm_rbm_train_step_pt's tempered steps and negative means; nothing else ever does)
+    bool fw_on = false, eff_valid = false, eff_now = false;
+    float fw_lr = 0.f, fw_decay = 0.f;
+    Mat Wf, We, Wet;
+    DevBuf vbf, hbf, vbe, hbe;
     DevBuf rowacc;    // [3*maxB]
     DevBuf hhat;      // [3*H] MultinomialRBM free-energy h_hat vectors (rbm.py:58)
     DevArray<int> flip;
@@ -223,6 +234,31 @@ static void ensure_wt(bm_rbm *h) {
     h->wt_valid = true;
 }
 
+// fast-weights PCD: the effective copies We, We^T, vbe, hbe when something else than the fast-weights update last wrote W, vb
+// or hb (or the fast set): one elementwise launch and - where the handle keeps W^T - one transpose, valid until the next such write
+static void ensure_eff(bm_rbm *h) {
+    if (!h->fw_on || h->eff_valid) return;
+    FastRefreshArgs r;
+    memset(&r, 0, sizeof(r));
+    r.W = h->W.p; r.Wf = h->Wf.p; r.We = h->We.p; r.Wet = h->use_wt ? h->Wet.p : nullptr;
+    r.V = h->V; r.H = h->H; r.ldw = h->W.ld; r.ldf = h->Wf.ld; r.ldet = h->Wet.ld;
+    r.vb = h->vb.p; r.vbf = h->vbf.p; r.hb = h->hb.p; r.hbf = h->hbf.p; r.vbe = h->vbe.p; r.hbe = h->hbe.p;
+    ProfScope _ps(h, KC_OTHER);
+    launch_fast_refresh(r, h->stream);
+    h->eff_valid = true;
+}
+// while one lives, rbm_pass() describes and issue() launches passes under the effective set of a fast-weights handle
+// (a handle without the mode: no effect)
+struct EffScope {
+    bm_rbm *h;
+    explicit EffScope(bm_rbm *h_) : h(h_) { h->eff_now = h->fw_on; }
+    ~EffScope() { h->eff_now = false; }
+};
+// the parameter set the passes of now read
+static const Mat &pass_w(const bm_rbm *h) { return h->eff_now ? h->We : h->W; }
+static const float *pass_vb(const bm_rbm *h) { return h->eff_now ? h->vbe.p : h->vb.p; }
+static const float *pass_hb(const bm_rbm *h) { return h->eff_now ? h->hbe.p : h->hb.p; }
+
 // ---- a propagation pass as a value (bm_pass.h): rbm_pass() describes it, issue() launches it.  The RBM is the one-layer stack:
 //   up   (layer 0):  E[h|v] (+ sample), base_rbm.py:339-351, from in = v [J][V]
 //   down (layer -1): E[v|h] (+ sample), base_rbm.py:353-365, from in = h [J][H]
@@ -233,14 +269,14 @@ static LayerPass rbm_pass(const bm_rbm *h, bool up, int J, LayerIn in, const Lay
     memset(&a, 0, sizeof(ActArgs));
     p.layer = up ? 0 : -1; p.below = up ? in.p : nullptr; p.above = up ? nullptr : in.p;
     if (up) {
-        a.P1 = make_operand(h->W.p, h->W.ld, h->H);   // W[k=v][i=h], k-major (issue() reads W^T x-major where the handle keeps it)
+        a.P1 = make_operand(pass_w(h).p, pass_w(h).ld, h->H);   // W[k=v][i=h], k-major (issue() reads W^T x-major where the handle keeps it)
         a.K1 = h->V; a.I = h->H;
-        a.bias = h->hb.p; a.kind = BM_UNIT_BERNOULLI;  // (Multinomial hidden units: issue() turns the pass into the logits pair)
+        a.bias = pass_hb(h); a.kind = BM_UNIT_BERNOULLI;  // (Multinomial hidden units: issue() turns the pass into the logits pair)
     } else {
-        a.P1 = make_operand(h->W.p, h->W.ld, h->V);   // W[i=v][k=h], x-major P
+        a.P1 = make_operand(pass_w(h).p, pass_w(h).ld, h->V);   // W[i=v][k=h], x-major P
         a.p_xm = 1;
         a.K1 = h->H; a.I = h->V;
-        a.bias = h->vb.p; a.sigma = h->sigma.p; a.kind = h->cfg.v_unit;
+        a.bias = pass_vb(h); a.sigma = h->sigma.p; a.kind = h->cfg.v_unit;
     }
     a.Q1 = make_operand(in.p, in.ld, J);              // in[j=b][k], x-major
     a.J = J;
@@ -288,8 +324,10 @@ static void issue(bm_rbm *h, LayerPass p) {
         return;
     }
     // the prop-up's weights x-major: W^T where the handle keeps a valid one (ensure_wt), never beside the bf16 planes
-    const bool xm = up && h->use_wt && h->wt_valid && !fast;
-    const Operand wt = xm ? make_operand(h->Wt.p, h->Wt.ld, h->H) : Operand{nullptr, 0, 0, 0};     // W^T[i=h][k=v]
+    // (a pass under the effective set of a fast-weights handle, EffScope: We^T, valid with the effective copies)
+    const bool xm = up && h->use_wt && (h->eff_now ? h->eff_valid : h->wt_valid) && !fast;
+    const Mat &wtm = h->eff_now ? h->Wet : h->Wt;
+    const Operand wt = xm ? make_operand(wtm.p, wtm.ld, h->H) : Operand{nullptr, 0, 0, 0};     // W^T[i=h][k=v]
     if (h->chain.on) {          // a chained run is open: recorded with W k-major, W^T as the per-pass launch's alternative
         if (a.cb_y) { fprintf(stderr, "bm355: a class-bias pass does not ride in a chained launch (no such kernel)\n"); abort(); }
         h->chain.rec.push_back(a);
@@ -402,8 +440,9 @@ static void launch_bias_fused(bm_rbm *h, int B, float lr, float mom) {
     hipLaunchKernelGGL(rbm_bias_fused_kernel, dim3(nw), dim3(NT), 0, h->stream, a);
 }
 
-static void rbm_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom, bool with_bias);
+static void rbm_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom, bool with_bias, bool fast_weights = false);
 static void launch_update_centred(bm_rbm *h, int B, float lr, float mom);
+static void launch_update_fast(bm_rbm *h, int B, float lr, float mom);
 
 // whole parameter update of the fused single-GPU step (base_rbm.py:443-478)
 static void launch_update_fused(bm_rbm *h, int B, float lr, float mom) {
@@ -414,6 +453,26 @@ static void launch_update_fused(bm_rbm *h, int B, float lr, float mom) {
     } else {                                // penalty == 0: run both in one launch
         rbm_grad(h, B, 1, (float)B, lr, mom, true);
     }
+}
+
+// The fast-weights form of launch_update_fused: the regular update exactly as there, its grad launch in the
+// fast-weights flavour (Wf, We, We^T ride on it); behind it the fast bias update from the raw column sums the update published
+static void launch_update_fast(bm_rbm *h, int B, float lr, float mom) {
+    if (h->cfg.sparsity_cost != 0.f) {
+        launch_bias_fused(h, B, lr, mom);
+        rbm_grad(h, B, 1, (float)B, lr, mom, false, true);
+    } else {
+        rbm_grad(h, B, 1, (float)B, lr, mom, true, true);
+    }
+    ProfScope _ps(h, KC_BIAS);
+    FastBiasArgs b;
+    memset(&b, 0, sizeof(b));
+    const float *tail = h->grad.p + h->grad_tail();
+    b.sv = tail; b.sh = tail + h->V;
+    b.vb = h->vb.p; b.hb = h->hb.p; b.vbf = h->vbf.p; b.hbf = h->hbf.p; b.vbe = h->vbe.p; b.hbe = h->hbe.p;
+    b.V = h->V; b.H = h->H; b.N = (float)B; b.fast_lr = h->fw_lr; b.fast_decay = h->fw_decay;
+    launch_fast_bias(b, h->stream);
+    h->eff_valid = true;
 }
 
 static void fill_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom, GradArgs &g) {
@@ -434,7 +493,7 @@ static void fill_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom,
     if (h->use_wt && fused) { g.Wt = h->Wt.p; g.ldwt = h->Wt.ld; }
     g.N = N; g.M = N; g.l2 = h->cfg.l2; g.lr = lr; g.mom = mom;
 }
-static void rbm_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom, bool with_bias) {
+static void rbm_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom, bool with_bias, bool fast_weights) {
     ProfScope _ps(h, KC_GRAD);
     GradArgs g;
     fill_grad(h, B, fused, N, lr, mom, g);
@@ -443,10 +502,14 @@ static void rbm_grad(bm_rbm *h, int B, int fused, float N, float lr, float mom, 
         g.nbias = fill_bias_fused(h, B, lr, mom, g.bias);
         g.bias.raw_only = fused ? 0 : 1;      // split (data-parallel) step: raw column sums only
     }
-    if (h->cen_on && fused) {
+    if (fast_weights) {           // (fused, never centred: bm_rbm_set_fast_weights refuses a centred handle)
+        const GradFast f{h->Wf.p, h->We.p, h->use_wt ? h->Wet.p : nullptr, h->Wf.ld, h->Wet.ld, h->fw_lr, h->fw_decay};
+        bm::launch_grad(g, h->stream, nullptr, &f);
+    } else if (h->cen_on && fused) {
         const GradCen cen{h->ov.p, h->cen_gv.p, h->oh.p, h->cen_gh.p};
         bm::launch_grad(g, h->stream, &cen);
     } else bm::launch_grad(g, h->stream);
+    h->eff_valid = false;         // (launch_update_fast sets it once the fast bias update is queued as well)
     if (fused && h->use_wt) h->wt_valid = true;      // the fused update wrote W and W^T together (every other writer of W
                                                      // clears the flag: set_param, apply_step, the exchange)
 }
@@ -687,7 +750,7 @@ static void pt_step(bm_rbm *h, int t, int sel_rows = 0) {
                  .energy_rows(e.h1.part.p, e.rows).row_tempered(e.mult.p));
     pt_launch_swap(h->pt, h->stream, t, make_key(h, SITE_PT_SWAP, t));
     LayerPass down = rbm_pass(h, false, rows, in_of(e.h1.x), value_out(1, e.v.x.p, e.v.x.ld, make_key(h, SITE_V, t), e.row0()))
-                         .statedot_rows(e.v.part.p, e.rows, h->vb.p).row_tempered(e.mult.p);
+                         .statedot_rows(e.v.part.p, e.rows, pass_vb(h)).row_tempered(e.mult.p);
     if (sel_rows > 0) down.select_rows(h->vs.p, h->vs.ld, e.R, sel_rows);
     issue(h, down);
 }
@@ -869,6 +932,7 @@ int bm_rbm_set_fast_binary(bm_rbm *h, int32_t on) {
 int bm_rbm_set_centering(bm_rbm *h, int32_t on, float nu_v, float nu_h) {
     BM_CHECK(h, "null argument");
     if (!on) { h->cen_on = false; return 0; }
+    BM_CHECK(!h->fw_on, "centering is not combined with fast weights (two flavours of the update kernel; bm_rbm_set_fast_weights(off) first)");
     BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "centering needs Bernoulli visible units (this handle's are Gaussian)");
     BM_CHECK(!h->multinomial(), "centering needs Bernoulli hidden units (this handle's are Multinomial)");
     BM_CHECK(!h->cfg.dbm_first && !h->cfg.dbm_last, "centering: a dbm_first / dbm_last handle (one conditional doubled) is not centred");
@@ -881,6 +945,46 @@ int bm_rbm_set_centering(bm_rbm *h, int32_t on, float nu_v, float nu_h) {
     h->cen_nu_v = nu_v; h->cen_nu_h = nu_h;
     h->cen_on = true;
     return 0;
+}
+
+// Fast-weights PCD (bm355.h).  A property of the handle that only bm_rbm_train_step_pt / _train_epoch_pt read.
+int bm_rbm_set_fast_weights(bm_rbm *h, int32_t on, float fast_learning_rate, float fast_decay) {
+    BM_CHECK(h, "null argument");
+    if (!on) {          // released: the handle is what it was before the mode was ever switched on
+        h->fw_on = h->eff_valid = false;
+        h->fw_lr = h->fw_decay = 0.f;
+        BM_HIP(hipStreamSynchronize(h->stream));
+        h->Wf = Mat(); h->We = Mat(); h->Wet = Mat();
+        h->vbf = DevBuf(); h->hbf = DevBuf(); h->vbe = DevBuf(); h->hbe = DevBuf();
+        return 0;
+    }
+    BM_TRY(check_single_joint(h, "bm_rbm_set_fast_weights"));
+    BM_CHECK(h->cfg.dropout < 0.f, "fast weights: the tempered family has no dropout (this handle's is %g)", (double)h->cfg.dropout);
+    BM_CHECK(!h->cen_on, "fast weights are not combined with centering (two flavours of the update kernel; bm_rbm_set_centering(off) first)");
+    BM_CHECK(std::isfinite(fast_learning_rate) && fast_learning_rate >= 0.f, "fast weights: fast_learning_rate %g is not a finite number >= 0",
+             (double)fast_learning_rate);
+    BM_CHECK(fast_decay >= 0.f && fast_decay < 1.f, "fast weights: fast_decay %g outside [0, 1)", (double)fast_decay);
+    if (!h->fw_on) {    // off -> on: a zero fast set (alloc zeroes); on -> on: the two scalars only
+        BM_TRY(h->Wf.alloc(h->V, h->H)); BM_TRY(h->We.alloc(h->V, h->H));
+        if (h->use_wt) BM_TRY(h->Wet.alloc(h->H, h->V));
+        BM_TRY(h->vbf.alloc(h->V)); BM_TRY(h->hbf.alloc(h->H)); BM_TRY(h->vbe.alloc(h->V)); BM_TRY(h->hbe.alloc(h->H));
+        h->eff_valid = false;
+    }
+    h->fw_lr = fast_learning_rate; h->fw_decay = fast_decay;
+    h->fw_on = true;
+    return 0;
+}
+
+// name -> matrix / vector of the fast-weights mode (null: no such name, or the mode is off); *ro: an effective copy (get only)
+static Mat *find_fast_mat(bm_rbm *h, const std::string &n, bool *ro) {
+    if (!h->fw_on) return nullptr;
+    *ro = n == "W_eff";
+    return n == "W_fast" ? &h->Wf : n == "W_eff" ? &h->We : nullptr;
+}
+static DevBuf *find_fast_vec(bm_rbm *h, const std::string &n, bool *ro) {
+    if (!h->fw_on) return nullptr;
+    *ro = n == "vb_eff" || n == "hb_eff";
+    return n == "vb_fast" ? &h->vbf : n == "hb_fast" ? &h->hbf : n == "vb_eff" ? &h->vbe : n == "hb_eff" ? &h->hbe : nullptr;
 }
 
 // name -> vector variable
@@ -905,6 +1009,19 @@ static DevBuf *find_vec(bm_rbm *h, const std::string &n) {
 int bm_rbm_set_param(bm_rbm *h, const char *name, const float *host, size_t n) {
     const std::string nm(name ? name : "");
     BM_HIP(hipStreamSynchronize(h->stream));
+    h->eff_valid = false;       // (whatever is written: the effective copies of a fast-weights handle are rebuilt before their next use)
+    bool ro = false;
+    if (Mat *fm = find_fast_mat(h, nm, &ro)) {
+        BM_CHECK(!ro, "variable '%s' is a derived copy (W + W_fast): get only", name);
+        BM_CHECK(n == (size_t)h->V * h->H, "variable '%s' has %zu elements, got %zu", name, (size_t)h->V * h->H, n);
+        return fm->upload(host);
+    }
+    if (DevBuf *fb = find_fast_vec(h, nm, &ro)) {
+        BM_CHECK(!ro, "variable '%s' is a derived copy (bias + fast bias): get only", name);
+        BM_CHECK(n == fb->n, "variable '%s' has %zu elements, got %zu", name, fb->n, n);
+        BM_HIP(hipMemcpy(fb->p, host, n * sizeof(float), hipMemcpyHostToDevice));
+        return 0;
+    }
     if (nm == "W" || nm == "dW") {
         BM_CHECK(n == (size_t)h->V * h->H, "variable '%s' has %zu elements, got %zu", name, (size_t)h->V * h->H, n);
         BM_TRY((nm == "W" ? h->W : h->dW).upload(host));
@@ -924,6 +1041,7 @@ int bm_rbm_set_param(bm_rbm *h, const char *name, const float *host, size_t n) {
 int bm_rbm_set_param_dev(bm_rbm *h, const char *name, const float *src_dev, size_t n) {
     const std::string nm(name ? name : "");
     BM_CHECK(h && src_dev, "null argument");
+    h->eff_valid = false;
     if (nm == "W" || nm == "dW") {
         BM_CHECK(n == (size_t)h->V * h->H, "variable '%s' has %zu elements, got %zu", name, (size_t)h->V * h->H, n);
         Mat &m = nm == "W" ? h->W : h->dW;
@@ -944,6 +1062,20 @@ int bm_rbm_get_param(bm_rbm *h, const char *name, float *host, size_t n) {
     const std::string nm(name ? name : "");
     BM_HIP(hipStreamSynchronize(h->stream));
     BM_TRY(check_device_status(h));        // never hand out variables computed from invalid tiles / a lost rank's sums
+    bool ro = false;
+    Mat *fm = find_fast_mat(h, nm, &ro);
+    DevBuf *fb = fm ? nullptr : find_fast_vec(h, nm, &ro);
+    if (fm || fb) {
+        if (ro) {               // a stale effective copy is rebuilt first
+            ensure_eff(h);
+            BM_HIP(hipStreamSynchronize(h->stream));
+        }
+        const size_t want = fm ? (size_t)h->V * h->H : fb->n;
+        BM_CHECK(n == want, "variable '%s' has %zu elements, got %zu", name, want, n);
+        if (fm) return fm->download(host);
+        BM_HIP(hipMemcpy(host, fb->p, n * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
     if (nm == "W" || nm == "dW") {
         BM_CHECK(n == (size_t)h->V * h->H, "variable '%s' has %zu elements, got %zu", name, (size_t)h->V * h->H, n);
         if (nm == "dW") BM_TRY(check_dw(h, "bm_rbm_get_param(dW)"));
@@ -1187,6 +1319,7 @@ int bm_rbm_apply_step(bm_rbm *h, int32_t B_global, float lr, float mom) {
     a.raw = h->grad.p; a.raw2 = nullptr;
     a.W = h->W.p; a.dW = h->dW.p; a.Wt = nullptr;
     h->wt_valid = false;
+    h->eff_valid = false;
     a.I = h->H; a.J = h->V; a.ldw = h->W.ld; a.ldwt = 0; a.form = 0;
     a.N = (float)B_global; a.M = a.N; a.l2 = h->cfg.l2; a.lr = lr; a.mom = mom;
     if (h->cfg.sparsity_cost != 0.f) {      // the W update needs the penalty: bias update first
@@ -2121,24 +2254,29 @@ int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, flo
     BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
     static const bool sel_in_pass = !dbg("pt_sel") || atoi(dbg("pt_sel")) != 0;     // BM355_DEBUG=pt_sel=0: a gather launch instead
     ensure_wt(h);
-    // 1. the v.vb partials of the swap energy under the vb of NOW (the previous update changed it)
-    pt_launch_rescore(h->pt, h->stream, h->vb.p, nullptr);
+    ensure_eff(h);
+    // 1. the v.vb partials of the swap energy under the vb of NOW (the previous update changed it; fast weights: the effective vb)
+    pt_launch_rescore(h->pt, h->stream, h->fw_on ? h->vbe.p : h->vb.p, nullptr);
     // 2. positive phase: the h0 means alone
     h->Xin = X_dev; h->Xin_ld = h->V;
     h->fe_in_chain = false;
     issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, rbm_out(h, 0, h->h0m.p, nullptr, h->h0m.ld, SITE_H0, 0)));
-    // 3. + 4. the tempered steps; the last prop-down leaves the beta = 1 rows of the chains [0, B) in vs
-    for (int t = 0; t < k; ++t) pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
-    if (!sel_in_pass) {
-        float *const dst[3] = {h->vs.p, nullptr, nullptr};
-        const int ldd[3] = {h->vs.ld, 0, 0};
-        pt_launch_gather(h->pt, h->stream, B, dst, ldd);
+    {
+        EffScope eff(h);      // fast weights: the whole negative phase lives under the effective set
+        // 3. + 4. the tempered steps; the last prop-down leaves the beta = 1 rows of the chains [0, B) in vs
+        for (int t = 0; t < k; ++t) pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
+        if (!sel_in_pass) {
+            float *const dst[3] = {h->vs.p, nullptr, nullptr};
+            const int ldd[3] = {h->vs.ld, 0, 0};
+            pt_launch_gather(h->pt, h->stream, B, dst, ldd);
+        }
+        // 5. negative means: only -h is consumed (run_chain's neg_only form)
+        issue(h, rbm_pass(h, true, B, in_of(h->vs), rbm_out(h, 0, nullptr, nullptr, h->hm.ld, SITE_H, 0)).negmeans_out(h->hneg.p));
+        h->hm_is_neg = true;
     }
-    // 5. negative means: only -h is consumed (run_chain's neg_only form)
-    issue(h, rbm_pass(h, true, B, in_of(h->vs), rbm_out(h, 0, nullptr, nullptr, h->hm.ld, SITE_H, 0)).negmeans_out(h->hneg.p));
-    h->hm_is_neg = true;
-    // 6. + 7.
-    launch_update_fused(h, B, lr, mom);
+    // 6. + 7. (fast weights: the fast and effective sets move in the same launches)
+    if (h->fw_on) launch_update_fast(h, B, lr, mom);
+    else launch_update_fused(h, B, lr, mom);
     h->pt.step += k;
     h->call++;
     BM_HIP(hipGetLastError());

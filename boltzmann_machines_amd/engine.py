@@ -96,13 +96,15 @@ class RbmEngine(_PtCalls):
         C_ = getattr(self, 'n_classes', 0)
         return {'W': self.V * self.H, 'dW': self.V * self.H, 'vb': self.V, 'dvb': self.V, 'sigma': self.V,
                 'hb': self.H, 'dhb': self.H, 'q_means': self.H, 'ov': self.V, 'oh': self.H,
+                'W_fast': self.V * self.H, 'W_eff': self.V * self.H, 'vb_fast': self.V, 'vb_eff': self.V,
+                'hb_fast': self.H, 'hb_eff': self.H,
                 'grad': self.V * self.H + self.V + 2 * self.H,
                 'U': C_ * self.H, 'dU': C_ * self.H, 'yb': C_, 'dyb': C_}[name]
 
     def _shape(self, name):
         if name in ('U', 'dU'):          # the class head's weights (set_classes)
             return (getattr(self, 'n_classes', 0), self.H)
-        return (self.V, self.H) if name in ('W', 'dW') else (self._size(name),)
+        return (self.V, self.H) if name in ('W', 'dW', 'W_fast', 'W_eff') else (self._size(name),)
 
     def set(self, name, value):
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(value, dtype=np.float32), self._shape(name)))
@@ -132,6 +134,13 @@ class RbmEngine(_PtCalls):
         """centred update (bm_rbm_set_centering): while on, every fused update entry of this handle takes it; the offsets are
         the variables 'ov' / 'oh'"""
         check(self.lib.bm_rbm_set_centering(self._h, int(bool(on)), float(nu_v), float(nu_h)))
+
+    def set_fast_weights(self, on, fast_learning_rate=0.0, fast_decay=0.95):
+        """fast-weights PCD (bm_rbm_set_fast_weights): while on, train_step_pt / train_epoch_pt run their negative phase under
+        W + W_fast, vb + vb_fast, hb + hb_fast and move the fast set with every update; off -> on starts from a zero fast set,
+        on -> on changes the two scalars only, off releases the set.  Variables while on: 'W_fast', 'vb_fast', 'hb_fast'
+        (get / set), 'W_eff', 'vb_eff', 'hb_eff' (get)"""
+        check(self.lib.bm_rbm_set_fast_weights(self._h, int(bool(on)), float(fast_learning_rate), float(fast_decay)))
 
     def set_from_device(self, name, darr):
         """variable <- dense DeviceArray, asynchronously on the engine's stream (bm_rbm_set_param_dev)"""

@@ -152,6 +152,8 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
         # the negative phase of fit(): None = CD-k from the batch, else (betas, n_chains) of the tempered ensemble
         # (set_negative_phase; not a constructor keyword and not written to checkpoints)
         self._neg_phase = None
+        # fast weights of the tempered negative phase: None or (fast_learning_rate, fast_decay) (set_negative_phase; as _neg_phase)
+        self._fast_weights = None
 
     # ---- variables -----------------------------------------------------------------
     def _sigma_vector(self):
@@ -423,7 +425,10 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
         while centering is on they are written to model.npz (`centering_ov`, `centering_oh`, `centering_nu`) and
         `load_model` re-enables the mode from them; params.json keeps the reference's schema.  BernoulliRBM in float32 only:
         GaussianRBM, MultinomialRBM, float64, `dbm_first` / `dbm_last`, dropout and BM355_DATA_PARALLEL jobs raise
-        NotImplementedError.  Returns self."""
+        NotImplementedError, and so does switching it on while `set_negative_phase` has fast weights on.  Returns self."""
+        if enabled and self._fast_weights is not None:
+            raise NotImplementedError('%s.set_centering: centering is not combined with fast weights (set_negative_phase(..., '
+                                      'fast_learning_rate=0) first)' % self.__class__.__name__)
         return self._set_centering(enabled, [nu_v, nu_h], [offset_v, offset_h])
 
     @classmethod
@@ -446,7 +451,7 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
             raise NotImplementedError('%s: a tempered negative phase is not combined with BM355_DATA_PARALLEL (chains are '
                                       'not sharded over ranks)' % name)
 
-    def set_negative_phase(self, kind='cd', n_temperatures=10, betas=None, n_chains=None):
+    def set_negative_phase(self, kind='cd', n_temperatures=10, betas=None, n_chains=None, fast_learning_rate=0.0, fast_decay=0.95):
         """Where the negative particles of `fit` come from.
 
         kind='cd' (the default, the reference's training graph): a k-step Gibbs chain started at the minibatch.
@@ -465,8 +470,59 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
         loaded model trains with CD until this method is called again, and a resumed fit starts a fresh ensemble.
         A train-metrics iteration reports the metrics of the CD reconstruction (as `kind='cd'` would) and then makes its
         tempered update.  BernoulliRBM in float32 only: GaussianRBM, MultinomialRBM, float64, `dbm_first` / `dbm_last`,
-        dropout and BM355_DATA_PARALLEL jobs raise NotImplementedError.  Returns self."""
-        return self._set_negative_phase(kind, n_temperatures, betas, n_chains)
+        dropout and BM355_DATA_PARALLEL jobs raise NotImplementedError.
+
+        fast_learning_rate > 0 (kind='tempered' only): fast weights (FPCD, Tieleman & Hinton 2009).  A second parameter set
+        W_fast, vb_fast, hb_fast learns from every update's gradient at this rate and decays by `fast_decay` in [0, 1) per
+        update; the ensemble and the negative means run under model + fast set, which raises the energy wherever the chains sit
+        and pushes them out of their modes at once, while the model itself is updated as before.  n_temperatures=1 is FPCD
+        proper; more temperatures run the whole ladder under model + fast set.  The fast set starts at zero whenever the
+        ensemble is built (so at the first update of every `fit()` call), is read by `fast_weights()` and is not written to
+        checkpoints; calling this method again between `fit()` calls changes the rate.  Not combined with `set_centering`
+        (NotImplementedError, whichever is set second).  Returns self."""
+        rate, decay = float(fast_learning_rate), float(fast_decay)
+        if not (np.isfinite(rate) and rate >= 0.):
+            raise ValueError('`fast_learning_rate` must be a finite number >= 0 (got {0!r})'.format(fast_learning_rate))
+        if not 0. <= decay < 1.:
+            raise ValueError('`fast_decay` must lie in [0, 1) (got {0!r})'.format(fast_decay))
+        if rate > 0.:
+            if kind != 'tempered':
+                raise ValueError("`fast_learning_rate` > 0 needs kind='tempered' (got kind={0!r})".format(kind))
+            if self._centering is not None:
+                raise NotImplementedError('%s.set_negative_phase: fast weights are not combined with centering '
+                                          '(set_centering(False) first)' % self.__class__.__name__)
+        self._set_negative_phase(kind, n_temperatures, betas, n_chains)
+        self._fast_weights = (rate, decay) if rate > 0. else None
+        if self._fast_weights is None:
+            self._engine_fast_weights_off()
+        return self
+
+    def _engine_fast_weights_off(self):
+        eng = self._engine
+        if eng is not None and getattr(eng, '_fast_on', False):
+            eng.set_fast_weights(False)
+            eng._fast_on = False
+
+    def _ensure_train_ensemble(self, eng):
+        """... and the engine's fast-weights mode as set_negative_phase left it: a zero fast set wherever the ensemble is built"""
+        built = getattr(self, '_pt_fresh', True) or getattr(eng, '_pt_train_key', None) != self._neg_phase
+        super(BaseRBM, self)._ensure_train_ensemble(eng)
+        if self._fast_weights is None:
+            self._engine_fast_weights_off()
+            return
+        if built:
+            self._engine_fast_weights_off()               # (off -> on starts from zero)
+        eng.set_fast_weights(True, *self._fast_weights)
+        eng._fast_on = True
+
+    def fast_weights(self):
+        """The fast parameter set of the tempered negative phase, dict(W=[n_visible, n_hidden], vb=, hb=) in float32.  Raises
+        RuntimeError where there is none (fast weights off, or no update made yet)."""
+        eng = self._engine
+        if self._fast_weights is None or eng is None or not getattr(eng, '_fast_on', False):
+            raise RuntimeError('`fast_weights`: no fast weights (call set_negative_phase(\'tempered\', fast_learning_rate=...) '
+                               'and fit first)')
+        return dict(W=eng.get('W_fast'), vb=eng.get('vb_fast'), hb=eng.get('hb_fast'))
 
     def _check_tempered_fit(self):
         """what may have changed since set_negative_phase (set_params): refused before an epoch starts"""

@@ -253,6 +253,30 @@ int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, i
 int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t n_gibbs_steps);
 int bm_rbm_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t n_gibbs_steps);
 
+/* ---- Fast-weights PCD (FPCD, Tieleman & Hinton 2009) ---------------------------------------------------
+ * A second, quickly decaying parameter set Wf [V][H], vbf [V], hbf [H] (float32) that learns from the gradient of every
+ * tempered update at its own rate.  While the mode is on, bm_rbm_train_step_pt / _train_epoch_pt run their whole negative
+ * phase - the v.vb rescore, the n_gibbs_steps tempered steps of all rows with their swap energies, the negative means of the
+ * selected rows - under the effective set We = W + Wf, vbe = vb + vbf, hbe = hb + hbf (one float32 addition per element); the
+ * positive phase and the regular update (momentum, l2, sparsity, q_means) are exactly those of the mode off.  In the update's
+ * launches, with g0 the gradient the regular rule starts from (raw / N, before l2 and penalty; biases: the column sums / N)
+ * and every product and sum rounded once:
+ *   f <- fast_decay * f + fast_learning_rate * g0;      effective <- regular_new + f
+ * No random number is drawn for it: an update with fast weights draws what the plain tempered update draws.  With one
+ * temperature this is FPCD proper; with more, the whole ladder runs under the effective set.  Nothing else reads the fast or
+ * effective parameters: bm_rbm_pt_sweep, sampling, the metrics, transform, AIS, the class head and the CD updates see the
+ * regular model.  Any other writer of W, vb or hb (bm_rbm_set_param[_dev], the CD updates, bm_rbm_apply_step, the exchanges)
+ * leaves the effective copies stale; the next tempered update or read of them rebuilds them first, so such calls between two
+ * fast-weights updates are legal.
+ * on = 1 from off: allocates the sets and starts from a zero fast set; on = 1 while on: only changes the two scalars;
+ * on = 0: releases the sets (the scalars are not read) - the handle is then what it was before.
+ * Variables of bm_rbm_set_param / get_param while the mode is on: "W_fast", "vb_fast", "hb_fast" (get and set), "W_eff",
+ * "vb_eff", "hb_eff" (get only).
+ * Refused (the error names fast weights): what bm_rbm_pt_init refuses, a handle with dropout, a centred handle - and
+ * bm_rbm_set_centering(on) while fast weights are on -, fast_learning_rate negative or not finite, fast_decay outside
+ * [0, 1).  Float32 only; not combined with the class head's training, the DBM or data parallelism (none of them reads it). */
+int bm_rbm_set_fast_weights(bm_rbm *h, int32_t on, float fast_learning_rate, float fast_decay);
+
 /* the handle's hipStream_t (as void*), so a host can enqueue collectives on
  * the same stream (torch.cuda.ExternalStream) without host synchronisation. */
 int bm_rbm_stream(bm_rbm *h, void **out_stream);
