@@ -13,6 +13,7 @@ from . import build as _build
 
 MAX_LAYERS = 4
 UNIT_BERNOULLI, UNIT_GAUSSIAN, UNIT_MULTINOMIAL = 0, 1, 2
+UNIT_NRELU = 3          # noisy rectified-linear hidden units (BM_UNIT_NRELU)
 
 
 class Bm355Error(RuntimeError):
@@ -140,6 +141,7 @@ SIGNATURES = {
     'bm_rbm_grad_step': [_vp, _vp, _i32, _i32],
     'bm_rbm_apply_step': [_vp, _i32, _f32, _f32],
     'bm_rbm_transform': [_vp, _vp, _i32, _i32, _vp],
+    'bm_rbm_sample_h': [_vp, _vp, _i32, _vp, _vp],
     'bm_rbm_metrics': [_vp, _vp, _i32, _i32, _fp],
     'bm_rbm_free_energy': [_vp, _vp, _i32, _fp],
     'bm_rbm_free_energy_rows': [_vp, _vp, _i32, _vp],

@@ -128,6 +128,7 @@ int bm_comm_allgather(bm_comm *c, const float *send_dev, float *recv_dev, size_t
 
 int bm_rbm_allreduce_grads(bm_rbm *h, bm_comm *c) {
     BM_CHECK(h && c, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_allreduce_grads"));
     void *p = nullptr, *st = nullptr;
     size_t n = 0;
     BM_TRY(bm_rbm_dev_ptr(h, "grad", &p, &n));

@@ -143,6 +143,13 @@ struct ActArgs {
     int bp;
     const float *bp_act;
     int bp_ld;
+    // Noisy rectified-linear hidden units (the NR flavour, act_kernel<..., NR = true>; launch_act_nr): a
+    // single-segment prop-up with mult == bmult == 1 whose pre-activation t = z + b is formed as kind 3 forms it and whose outputs are
+    //   mean  m = (t > 0) ? t : 0                                      - a comparison: +0 for t <= 0, for -0 and for NaN
+    //   state s = (u > 0) ? u : 0,  u = __fadd_rn(t, __fmul_rn(n, sqrt_rn(sigmoid(t))))          - every step rounded once
+    // with n the standard normal draw of the output's flat index on the pass's key (the Gaussian layer's word-to-draw mapping);
+    // a pass that does not sample stores s = m.  nrelu == 0: off.
+    int nrelu;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -194,6 +201,32 @@ __device__ __forceinline__ void draw4(const ActArgs &a, const PhiloxKey &key, un
                 s[r] = ((idx & 1) ? n1 : n0) * a.sigma[ib + r] + m[r];
             }
         }
+    }
+}
+
+// NR flavour: the state of one output from its pre-activation t and its normal draw n (ActArgs::nrelu) - sigmoid, square root,
+// multiply, add, each rounded once (no fused multiply-add), then the comparison.  The square root is sqrtf, the correctly
+// rounded one box_muller uses (hipcc's default for fp32 sqrt): __fsqrt_rn is the NATIVE approximation in this toolchain's headers
+// unless OCML_BASIC_ROUNDED_OPERATIONS is defined, and differed from the IEEE root in the last bit of one draw in ten
+__device__ __forceinline__ float nrelu_state(float t, float n) {
+    const float sd = sqrtf(sigmoid(t));
+    const float u = __fadd_rn(t, __fmul_rn(n, sd));
+    return (u > 0.0f) ? u : 0.0f;
+}
+// ... and the normal draws of up to 4 consecutive outputs from flat index `flat` on the generic path (I % 4 != 0): per element, the
+// draw the aligned path gives the same flat index (draw4's mapping)
+__device__ __forceinline__ void nrelu_normals(const PhiloxKey &key, unsigned long long flat, int nvalid, float *n) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        n[r] = 0.f;
+        if (r >= nvalid) continue;
+        const unsigned long long idx = flat + r;
+        uint32_t wds[4];
+        philox_block(key, idx >> 2, wds);
+        float n0, n1;
+        const int pr = (int)(idx & 3) >> 1;
+        box_muller(wds[2 * pr], wds[2 * pr + 1], n0, n1);
+        n[r] = (idx & 1) ? n1 : n0;
     }
 }
 
@@ -367,7 +400,7 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
 template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false,
-          bool CR = false, bool CB = false, bool BP = false>
+          bool CR = false, bool CB = false, bool BP = false, bool NR = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -484,7 +517,8 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
             const int ib = ib0 + 4 * hlf;
             if (ib >= a.I) break;
             const int nvalid = (a.I - ib < 4) ? a.I - ib : 4;
-            float m[4], s[4];
+            float m[4], s[4], nt[4];
+            (void)nt;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if constexpr (BP) {            // delta = (z * a) * (1 - a), every step rounded once; no matrix: z itself
@@ -497,12 +531,29 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                 float bv = bs[4 * hlf + r];
                 if constexpr (CB) { if (cb_ok) bv = __fadd_rn(bv, cu[hlf][r]); }       // b' = b + U[y_j][i], one rounded add
                 const float b = (RT ? rm : a.bmult) * bv;
+                if constexpr (NR) {            // t = z + b as kind 3 forms it; the mean is the rectified t
+                    nt[r] = x + b;
+                    m[r] = (nt[r] > 0.0f) ? nt[r] : 0.0f;
+                    s[r] = m[r];
+                    continue;
+                }
                 m[r] = (a.kind == 0) ? (LIT ? sigmoid_literal(x + b) : (HWMATH ? sigmoid_hw(x + b) : sigmoid(x + b)))
                                      : (a.kind == 1 ? (x * sg[4 * hlf + r] + b) : (a.kind == 3 ? x + b : x));
                 s[r] = m[r];
             }
             if (!BP && a.sample) {
-                if (rng_fast) {          // the 4 outputs are exactly one (precomputed) Philox block
+                if constexpr (NR) {      // one normal per output: the lane's Philox block, or per element where I % 4 != 0
+                    float n[4];
+                    if (rng_fast) {
+                        const uint32_t *wds = rng.words(hlf);
+                        box_muller(wds[0], wds[1], n[0], n[1]);
+                        box_muller(wds[2], wds[3], n[2], n[3]);
+                    } else {
+                        nrelu_normals(key, (unsigned long long)(a.row0 + j) * (unsigned long long)a.I + ib, nvalid, n);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s[r] = nrelu_state(nt[r], n[r]);
+                } else if (rng_fast) {   // the 4 outputs are exactly one (precomputed) Philox block
                     const uint32_t *wds = rng.words(hlf);
                     if (a.kind == 0) {
 #pragma unroll
@@ -665,7 +716,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 // MINB: HIP's second __launch_bounds__ argument = WAVES PER SIMD the register budget must allow (for the 4-wave
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
-          bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false>
+          bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false, bool NR = false>
 BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -741,7 +792,7 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP, NR>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];

@@ -29,6 +29,10 @@
 //        with mult == 1, an x-major P (W itself), no draw and no row sums, whose epilogue multiplies by a (1 - a) of an activation
 //        matrix; geometry and tile map as CR (the plain prop-down's memo entry for the shape); its instantiations - the x-major
 //        ones only - live in bm_stack.hip (launch_act_bp_as); combined with no other flavour
+//   NR   noisy rectified-linear hidden units (ActArgs::nrelu): single-segment prop-ups with mult == bmult == 1, in
+//        either operand layout (W k-major, W^T x-major), whose epilogue rectifies t = z + b and draws one normal per output;
+//        geometry and tile map as CR (the plain prop-up's memo entry for the shape); its instantiations live in bm_nrelu.hip
+//        (launch_act_nr_as); combined with no other flavour
 // FE, LIT and MF stage through LDS-DMA in the slab order.  dispatch_act walks the one ladder they share with the plain flavour:
 // x-major P / two K segments / one, each as the `fast` kernel (16-byte loads) or the one that passes every chunk through
 // registers (STG_DMA whatever the geometry's staging: shapes without 16-byte loads have ONE flavour).
@@ -148,14 +152,14 @@ template <class Args, class F> static inline int tune_tile_map(TuneTimer &tm, Ar
 static inline bool tune_log() { static const bool on = dbg("tune_log") != nullptr; return on; }
 
 // ---- act_kernel: one dispatcher for every flavour
-enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
+enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512, FL_NR = 1024 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
 template <class G, int MINB, int STG, unsigned FL, bool SEG2, int PL>
 static inline void launch_act_kernel(bool fast, unsigned dyn_lds, hipStream_t st, const ActArgs &a, const TileMap &tmap) {
     const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
     constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0, CL = (FL & FL_CL) != 0,
-                   RT = (FL & FL_RT) != 0, CR = (FL & FL_CR) != 0, CB = (FL & FL_CB) != 0, BP = (FL & FL_BP) != 0;
-    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP>), grid, blk, dyn_lds, st, a, tmap);
-    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP>), grid, blk, dyn_lds, st, a, tmap);
+                   RT = (FL & FL_RT) != 0, CR = (FL & FL_CR) != 0, CB = (FL & FL_CB) != 0, BP = (FL & FL_BP) != 0, NR = (FL & FL_NR) != 0;
+    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP, NR>), grid, blk, dyn_lds, st, a, tmap);
+    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP, NR>), grid, blk, dyn_lds, st, a, tmap);
 }
 template <class G, int MINB, int STG, unsigned FL>
 static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, unsigned dyn_lds = 0) {
@@ -172,12 +176,12 @@ static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, un
         if (seg2) { launch_act_kernel<G, MINB, STG, FL, true, KM>(fast, dyn_lds, st, a, tmap); return; }
     launch_act_kernel<G, MINB, STG, FL, false, KM>(fast, dyn_lds, st, a, tmap);
 }
-// the plain flavour (FLX == 0) and RT (FLX == FL_RT) have two-segment kernels, CL (FLX == FL_CL), CR (FLX == FL_CR) and CB
-// (FLX == FL_CB) have none;
+// the plain flavour (FLX == 0) and RT (FLX == FL_RT) have two-segment kernels, CL (FLX == FL_CL), CR (FLX == FL_CR), CB
+// (FLX == FL_CB) and NR (FLX == FL_NR) have none;
 // x-major P exists for the geometries with MI == 1
 template <class G, int MINB, int STG, unsigned FLX = 0>
 static inline void launch_act_geo(const ActArgs &a, hipStream_t st) {
-    dispatch_act<G, MINB, STG, FLX | ((FLX == FL_CL || FLX == FL_CR || FLX == FL_CB) ? 0 : FL_SEG2) | (G::MI == 1 ? FL_XM : 0)>(a, st, a.map_xi);
+    dispatch_act<G, MINB, STG, FLX | ((FLX == FL_CL || FLX == FL_CR || FLX == FL_CB || FLX == FL_NR) ? 0 : FL_SEG2) | (G::MI == 1 ? FL_XM : 0)>(a, st, a.map_xi);
 }
 #ifndef BM_KERNELS_ONLY
 static inline void launch_act_fe(const ActArgs &a, hipStream_t st) { dispatch_act<GeoAct8, 1, STG_DMA, FL_FE | FL_XM>(a, st, XI_SLAB); }
@@ -236,8 +240,9 @@ static inline void launch_act_as(int geo, const ActArgs &a, hipStream_t st) {
     if (geo == 9 && !a.p_xm) { launch_act_geo<GeoGrad8h, 4, STG_DMA, FLX>(a, st); return; }
     if (geo == 9) geo = 8;
     // 5: 64 x 32 tile with BK = 32, three workgroups per CU (k-major P only)
-    // (CR, CB: their epilogues do not fit the 168 registers of three workgroups per CU without scratch - the same tile as 7)
-    if constexpr (FLX != FL_CR && FLX != FL_CB) { if (geo == 5 && !a.p_xm) { launch_act_geo<GeoAct32, 3, STG_DMA, FLX>(a, st); return; } }
+    // (CR, CB: their epilogues do not fit the 168 registers of three workgroups per CU without scratch - the same tile as 7;
+    //  NR takes that tile as well)
+    if constexpr (FLX != FL_CR && FLX != FL_CB && FLX != FL_NR) { if (geo == 5 && !a.p_xm) { launch_act_geo<GeoAct32, 3, STG_DMA, FLX>(a, st); return; } }
     else if (geo == 5 && !a.p_xm) geo = 7;
     // 7: the same with two workgroups per CU (256 registers per wave: the two-segment variant spills 140 bytes at 168)
     if (geo == 7 && !a.p_xm) { launch_act_geo<GeoAct32, 2, STG_DMA, FLX>(a, st); return; }
@@ -466,7 +471,32 @@ static inline void launch_act_bp(const ActArgs &a, hipStream_t st) {
     }
     launch_act_bp_as(T.geo, a, st);
 }
+// the noisy rectified-linear prop-up: the geometry `geo` of the NR flavour.  Defined in bm_nrelu.hip, a translation
+// unit of its own for the reason bm_class.hip is one
+void launch_act_nr_as(int geo, const ActArgs &a, hipStream_t st);
+// ... per-pass fp32 launches always, on the plain flavour's memo entry for the shape (measured with the plain kernels)
+static inline void launch_act_nr(const ActArgs &a, hipStream_t st) {
+    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.row_mult || a.cr_part ||
+        a.cb_y || a.bp || a.b3.K1 > 0 || a.lit || a.kind != 3 || a.mult != 1.0f || a.bmult != 1.0f || a.rowacc || a.rowdot_out) {
+        fprintf(stderr, "bm355: a noisy rectified-linear pass is a single-segment prop-up of its own flavour (no such kernel)\n");
+        abort();
+    }
+    static const int geo_env = dbg_int("act_geo");
+    const int ov = geo_env ? geo_env : a.geo_hint;
+    if (ov) { launch_act_nr_as(ov, a, st); return; }
+    ActArgs plain = a;
+    plain.nrelu = 0; plain.kind = 0;        // (the Bernoulli prop-up of the shape: the same contraction, a draw per output)
+    const Tuned T = tuned_act(plain, st);
+    if (T.xi != XI_MODEL && !a.map_xi) {
+        ActArgs a2 = a;
+        a2.map_xi = T.xi;
+        launch_act_nr_as(T.geo, a2, st);
+        return;
+    }
+    launch_act_nr_as(T.geo, a, st);
+}
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
+    if (a.nrelu) { launch_act_nr(a, st); return; }
     if (a.bp) { launch_act_bp(a, st); return; }
     if (a.cb_y) { launch_act_cb(a, st); return; }
     if (a.cr_part) { launch_act_cr(a, st); return; }

@@ -106,6 +106,7 @@ struct bm_rbm {
     DevArray<int> flip;
     DevArray<double> scal;    // [6] device accumulators: msre, l2, F(x), F(x~), F'(x) (multinomial), spare
     bool multinomial() const { return cfg.h_unit == BM_UNIT_MULTINOMIAL; }
+    bool nrelu() const { return cfg.h_unit == BM_UNIT_NRELU; }      // noisy rectified-linear hidden units
     uint64_t seed = 0;
     uint32_t call = 0;
     int64_t row0 = 0;
@@ -191,6 +192,13 @@ static int check_dw(const bm_rbm *h, const char *what) {
     return 0;
 }
 
+// what a handle with noisy rectified-linear hidden units does not do (DESIGN.md 3.23 says why, entry by entry)
+static int refuse_nrelu(const bm_rbm *h, const char *what) {
+    BM_CHECK(!h || !h->nrelu(), "%s is not available for NReLU hidden units (noisy rectified-linear, BM_UNIT_NRELU): the unit has no "
+             "closed-form free energy and real-valued hidden states; see DESIGN.md 3.23", what);
+    return 0;
+}
+
 struct ProfScope {
     bm_rbm *h; hipEvent_t b = nullptr;
     ProfScope(bm_rbm *h_, int cls) : h(h_) {
@@ -217,7 +225,8 @@ static PhiloxKey make_key(const bm_rbm *h, uint32_t site, int t) {
 static void chain_begin(bm_rbm *h) {
     // per-class event timing, Multinomial hidden units (a softmax launch between the passes) and the fast-binary sweep
     // keep their per-pass launches
-    h->chain.on = !h->prof && !h->multinomial() && !h->fast_now && chain_mode(h->chain) > 0;
+    // (noisy rectified-linear hidden units: their prop-up is a flavour of its own, never chained)
+    h->chain.on = !h->prof && !h->multinomial() && !h->nrelu() && !h->fast_now && chain_mode(h->chain) > 0;
 }
 static int chain_end(bm_rbm *h) {
     BM_CHECK(chain_flush(h->chain, h->stream, h->maxB) == 0, "chained launch: %s", hipGetErrorString(hipGetLastError()));
@@ -323,6 +332,8 @@ static void issue(bm_rbm *h, LayerPass p) {
         hipLaunchKernelGGL(softmax_multinomial_kernel, dim3(a.J), dim3(64), 2 * (size_t)h->H * sizeof(float), h->stream, m);
         return;
     }
+    // noisy rectified-linear hidden units: the NR flavour rectifies t = z + b (formed as kind 3 forms it) and draws a normal
+    if (up && h->nrelu()) { a.kind = 3; a.nrelu = 1; }
     // the prop-up's weights x-major: W^T where the handle keeps a valid one (ensure_wt), never beside the bf16 planes
     // (a pass under the effective set of a fast-weights handle, EffScope: We^T, valid with the effective copies)
     const bool xm = up && h->use_wt && (h->eff_now ? h->eff_valid : h->wt_valid) && !fast;
@@ -600,7 +611,7 @@ static void metrics_to_out4(const bm_rbm *h, const double *host, int B, float *o
 // units are Bernoulli and the epilogue in use is act_kernel's (not the fast-binary strip kernel)
 static bool metrics_fused_ok(const bm_rbm *h) {
     static const bool off = bm::dbg("metrics_fused") && atoi(bm::dbg("metrics_fused")) == 0;
-    return !off && !h->multinomial() && !h->cfg.dbm_first && !h->fast_now && (h->W.ld & 3) == 0;
+    return !off && !h->multinomial() && !h->nrelu() && !h->cfg.dbm_first && !h->fast_now && (h->W.ld & 3) == 0;
 }
 static void metrics_prep(bm_rbm *h, int B) {
     MetricsPrepArgs mp;
@@ -624,7 +635,7 @@ static int metrics_from_chain(bm_rbm *h, int B, float *out4) {
         hipLaunchKernelGGL(metrics_tail_kernel, dim3(nb_sq + nb_fe), dim3(256), 0, h->stream, msre, l2, r, nb_sq);
     } else {
         hipLaunchKernelGGL(sqdiff2_kernel, dim3(256), dim3(256), 0, h->stream, msre, l2);
-        launch_fe(h, h->Xin, h->Xin_ld, B, true);
+        if (!h->nrelu()) launch_fe(h, h->Xin, h->Xin_ld, B, true);      // (NReLU: no free energy in closed form, pll / feg are NaN)
     }
     if (!out4) return 0;                                    // asynchronous caller: the sums stay in h->scal
     double host[6];
@@ -644,6 +655,7 @@ static void metrics_to_out4(const bm_rbm *h, const double *host, int B, float *o
     out4[1] = (float)h->V * ls;
     out4[2] = h->cfg.l2 * (float)(0.5 * host[1]);               // l2_loss       :483
     out4[3] = (float)fe;                                        // free energy   :516
+    if (h->nrelu()) out4[1] = out4[3] = nanf("");               // noisy rectified-linear hidden units: neither exists in closed form
 }
 
 // ---- AIS log Z of the RBM itself and per-row free energies (bm355.h: bm_rbm_ais, bm_rbm_free_energy_rows)
@@ -694,6 +706,7 @@ __global__ __launch_bounds__(256) void rbm_fe_rows_kernel(const float *X, int ld
 
 // the two entry points are about the joint p(v, h) of ONE Bernoulli-Bernoulli RBM
 static int check_single_joint(const bm_rbm *h, const char *what) {
+    BM_TRY(refuse_nrelu(h, what));
     BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "%s needs Bernoulli visible units (this handle's are Gaussian)", what);
     BM_CHECK(!h->multinomial(), "%s needs Bernoulli hidden units (this handle's are Multinomial)", what);
     BM_CHECK(!h->cfg.dbm_first && !h->cfg.dbm_last, "%s: the conditionals of a dbm_first / dbm_last handle (one of them doubled) "
@@ -815,7 +828,15 @@ int bm_rbm_create(const bm_rbm_config *cfg, bm_rbm **out) {
     BM_CHECK(cfg->n_visible >= 1 && cfg->n_hidden >= 1, "bad layer sizes %d x %d", cfg->n_visible, cfg->n_hidden);
     BM_CHECK(cfg->max_batch >= 1, "max_batch must be >= 1");
     BM_CHECK(cfg->v_unit == BM_UNIT_BERNOULLI || cfg->v_unit == BM_UNIT_GAUSSIAN, "unknown visible unit %d", cfg->v_unit);
-    BM_CHECK(cfg->h_unit == BM_UNIT_BERNOULLI || cfg->h_unit == BM_UNIT_MULTINOMIAL, "unknown hidden unit %d", cfg->h_unit);
+    BM_CHECK(cfg->h_unit == BM_UNIT_BERNOULLI || cfg->h_unit == BM_UNIT_MULTINOMIAL || cfg->h_unit == BM_UNIT_NRELU, "unknown hidden unit %d",
+             cfg->h_unit);
+    if (cfg->h_unit == BM_UNIT_NRELU) {
+        BM_CHECK(!cfg->dbm_first && !cfg->dbm_last, "NReLU hidden units: no dbm_first / dbm_last handle (a doubled pre-activation is not the "
+                 "unit's conditional, and the DBM has no such layer)");
+        BM_CHECK(cfg->sparsity_cost == 0.f, "NReLU hidden units do not combine with the sparsity penalty (sparsity_cost %g: the target is a "
+                 "probability, the unit's mean is not)", (double)cfg->sparsity_cost);
+        BM_CHECK(cfg->dropout < 0.f, "NReLU hidden units do not combine with dropout (this configuration's is %g)", (double)cfg->dropout);
+    }
     if (cfg->h_unit == BM_UNIT_MULTINOMIAL) {
         BM_CHECK(cfg->n_samples >= 1, "MultinomialRBM: n_samples must be >= 1 (got %d)", cfg->n_samples);
     }
@@ -932,6 +953,7 @@ int bm_rbm_set_fast_binary(bm_rbm *h, int32_t on) {
 int bm_rbm_set_centering(bm_rbm *h, int32_t on, float nu_v, float nu_h) {
     BM_CHECK(h, "null argument");
     if (!on) { h->cen_on = false; return 0; }
+    BM_TRY(refuse_nrelu(h, "bm_rbm_set_centering"));
     BM_CHECK(!h->fw_on, "centering is not combined with fast weights (two flavours of the update kernel; bm_rbm_set_fast_weights(off) first)");
     BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "centering needs Bernoulli visible units (this handle's are Gaussian)");
     BM_CHECK(!h->multinomial(), "centering needs Bernoulli hidden units (this handle's are Multinomial)");
@@ -1262,6 +1284,7 @@ int bm_rbm_train_epoch(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, 
 }
 
 int bm_rbm_grad_step(bm_rbm *h, const float *X_dev, int32_t B, int32_t k) {
+    BM_TRY(refuse_nrelu(h, "bm_rbm_grad_step"));
     BM_CHECK(!h->cen_on, "bm_rbm_grad_step: the split step has no centred form; switch centering off (bm_rbm_set_centering)");
     ChainOpts o;
     o.need_vm = false; o.split_step = true;
@@ -1286,6 +1309,7 @@ static int ensure_delayed(bm_rbm *h) {
 }
 int bm_rbm_set_grad_slot(bm_rbm *h, int32_t slot) {
     BM_CHECK(h && (slot == 0 || slot == 1), "slot must be 0 or 1");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_set_grad_slot"));
     if (slot == h->grad_slot) return 0;
     BM_TRY(ensure_delayed(h));
     std::swap(h->grad, h->grad_alt);
@@ -1294,6 +1318,7 @@ int bm_rbm_set_grad_slot(bm_rbm *h, int32_t slot) {
 }
 int bm_rbm_allreduce_grads_async(bm_rbm *h, bm_comm *c) {
     BM_CHECK(h && c, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_allreduce_grads_async"));
     BM_TRY(ensure_delayed(h));
     const int s = h->grad_slot;
     BM_HIP(hipEventRecord(h->ev_ready[s], h->stream));
@@ -1309,6 +1334,7 @@ int bm_rbm_wait_grads(bm_rbm *h, int32_t slot) {
 }
 
 int bm_rbm_apply_step(bm_rbm *h, int32_t B_global, float lr, float mom) {
+    BM_TRY(refuse_nrelu(h, "bm_rbm_apply_step"));
     BM_CHECK(!h->cen_on, "bm_rbm_apply_step: the split step has no centred form; switch centering off (bm_rbm_set_centering)");
     BM_TRY(check_dw(h, "bm_rbm_apply_step"));
     ProfScope _ps(h, KC_BIAS);
@@ -1344,6 +1370,24 @@ int bm_rbm_transform(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float 
     return 0;
 }
 
+// One prop-up of the handle's own hidden conditional from X_dev [B][V] (dense), the input taken as given - no division by sigma,
+// no dropout: means and / or states to dense [B][H] outputs, drawn at SITE_H0, step 0, the handle's seed, call counter and row
+// offset (bm355.h).  Every hidden unit type.  The counter advances by one
+int bm_rbm_sample_h(bm_rbm *h, const float *X_dev, int32_t B, float *Hmean_dev, float *Hstate_dev) {
+    BM_CHECK(h && X_dev, "null argument");
+    BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
+    ensure_wt(h);
+    // (Multinomial units without a means output: the softmax pair stages its logits in hm and shares one pitch between means
+    //  and states - through the pitched workspaces, then one copy)
+    const bool staged = h->multinomial() && Hstate_dev && !Hmean_dev;
+    issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, staged ? rbm_out(h, 1, h->hm.p, h->hs.p, h->hm.ld, SITE_H0, 0)
+                                                              : rbm_out(h, 1, Hmean_dev, Hstate_dev, h->H, SITE_H0, 0)));
+    if (staged) hipLaunchKernelGGL(copy2d_kernel, dim3(256), dim3(256), 0, h->stream, (const float *)h->hs.p, h->hs.ld, Hstate_dev, h->H, B, h->H);
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
 int bm_rbm_metrics(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float *out4) {
     ChainOpts o;
     o.fetch = true;
@@ -1354,6 +1398,7 @@ int bm_rbm_metrics(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float *o
 }
 
 int bm_rbm_free_energy(bm_rbm *h, const float *X_dev, int32_t B, float *out1) {
+    BM_TRY(refuse_nrelu(h, "bm_rbm_free_energy"));
     BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
     // free_energy_op is built from self._X_batch AFTER tf.nn.dropout replaced it (base_rbm.py:417-418,
     // :516): the `feg` metric sees the dropped input like msre / pll do
@@ -1446,6 +1491,7 @@ static void class_forward(bm_rbm *h, const float *X_dev, int B, float *T, int ld
 
 int bm_rbm_class_log_proba(bm_rbm *h, const float *X_dev, int32_t B, float *logp_host) {
     BM_CHECK(h && X_dev && logp_host, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_class_log_proba"));
     BM_CHECK(h->n_classes, "bm_rbm_class_log_proba: no class head is attached (bm_rbm_set_classes)");
     BM_TRY(check_single_joint(h, "bm_rbm_class_log_proba"));
     BM_CHECK(B >= 1, "bad row count %d", (int)B);
@@ -1458,6 +1504,7 @@ int bm_rbm_class_log_proba(bm_rbm *h, const float *X_dev, int32_t B, float *logp
 }
 
 static int check_class_train(const bm_rbm *h, const char *what, int B) {
+    BM_TRY(refuse_nrelu(h, what));
     BM_CHECK(h->n_classes, "%s: no class head is attached (bm_rbm_set_classes)", what);
     BM_TRY(check_single_joint(h, what));
     BM_CHECK(h->cfg.dropout < 0.f, "%s does not combine with dropout (this handle's is %g)", what, (double)h->cfg.dropout);
@@ -1566,6 +1613,7 @@ static void hand_over(bm_rbm *from, bm_rbm *to) {
 }
 // what a layer of a stack must be (the top as well: `head`); creates the hand-over event
 static int check_stack_layer(bm_rbm *h, const char *what, int B, bool head) {
+    BM_TRY(refuse_nrelu(h, what));
     if (head) BM_CHECK(h->n_classes, "%s: no class head is attached to the top handle (bm_rbm_set_classes)", what);
     BM_TRY(check_single_joint(h, what));
     BM_CHECK(h->cfg.dropout < 0.f, "%s does not combine with dropout (this handle's is %g)", what, (double)h->cfg.dropout);
@@ -2043,6 +2091,7 @@ int bm_rbm_class_semi_train_epoch(bm_rbm *h, const float *X_dev, const int32_t *
 // v_0 ~ Ber(1/2).  Per-pass fp32 launches, both layers sampled, rows drawn by global position (bm_rbm_set_row_offset)
 int bm_rbm_class_gibbs(bm_rbm *h, const float *V_dev, const int32_t *y_dev, int32_t B, int32_t n_steps, float *out_v, float *out_vmeans) {
     BM_CHECK(h && y_dev && out_v, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_class_gibbs"));
     BM_CHECK(h->n_classes, "bm_rbm_class_gibbs: no class head is attached (bm_rbm_set_classes)");
     BM_TRY(check_single_joint(h, "bm_rbm_class_gibbs"));
     BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
@@ -2130,7 +2179,7 @@ int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_ste
     BM_CHECK(H_dev && V_dev, "null state pointer");
     BM_CHECK(n_steps >= 1, "n_steps must be >= 1");
     struct FastScope { bm_rbm *h; ~FastScope() { h->fast_now = false; } } fast_scope{h};
-    const bool fast = h->fast && h->cfg.v_unit == BM_UNIT_BERNOULLI && !h->multinomial() && h->cfg.sample_v_states &&
+    const bool fast = h->fast && h->cfg.v_unit == BM_UNIT_BERNOULLI && !h->multinomial() && !h->nrelu() && h->cfg.sample_v_states &&
                       h->cfg.sample_h_states && h->cfg.dropout < 0.f;
     if (!fast && !h->multinomial()) {
         // The sweeps read and write the caller's dense buffers IN PLACE: the first prop-down takes H_dev (pitch H) as its
@@ -2189,6 +2238,7 @@ int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_ste
 int bm_rbm_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev, int32_t B, int32_t n_steps,
                          const float *clamp_val_dev, const float *clamp_mask_dev) {
     BM_CHECK(h, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_gibbs_clamped"));
     BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
     BM_CHECK(V_dev && H_dev && clamp_val_dev && clamp_mask_dev, "null state or clamp pointer");
     BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
@@ -2223,6 +2273,7 @@ int bm_rbm_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *be
 
 int bm_rbm_pt_sweep(bm_rbm *h, int32_t n_steps) {
     BM_CHECK(h, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_pt_sweep"));
     BM_CHECK(h->pt.M > 0, "bm_rbm_pt_sweep: no ensemble (call bm_rbm_pt_init first)");
     BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
     ensure_wt(h);
@@ -2235,6 +2286,7 @@ int bm_rbm_pt_sweep(bm_rbm *h, int32_t n_steps) {
 
 int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
     BM_CHECK(h, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_pt_read"));
     BM_CHECK(h->pt.M > 0, "bm_rbm_pt_read: no ensemble (call bm_rbm_pt_init first)");
     BM_CHECK(V_dev || !H_dev, "bm_rbm_pt_read: H_dev without V_dev");
     float *const dst[3] = {V_dev, H_dev, nullptr};
@@ -2246,6 +2298,7 @@ int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, i
 // One update whose negative phase is the tempered ensemble (bm355.h).  No host synchronisation.
 int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
     BM_CHECK(h && X_dev, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_train_step_pt"));
     BM_TRY(check_dw(h, "bm_rbm_train_step_pt"));
     BM_CHECK(h->pt.M > 0, "bm_rbm_train_step_pt: no ensemble (call bm_rbm_pt_init first)");
     BM_CHECK(h->cfg.dropout < 0.f, "bm_rbm_train_step_pt: the tempered family has no dropout (this handle's is %g)", (double)h->cfg.dropout);
@@ -2286,6 +2339,7 @@ int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, flo
 // the native batch loop of bm_rbm_train_step_pt (as bm_rbm_train_epoch is to bm_rbm_train_step)
 int bm_rbm_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t k) {
     BM_CHECK(h && X_dev, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_train_epoch_pt"));
     BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
     for (int64_t s = 0; s < N; s += batch) {
         const int B = (int)((N - s < batch) ? (N - s) : batch);

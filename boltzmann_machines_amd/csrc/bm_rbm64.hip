@@ -799,6 +799,7 @@ int bm_rbm64_create(const bm_rbm_config *cfg, const double *hyper5, bm_rbm64 **o
     BM_CHECK(cfg->n_visible >= 1 && cfg->n_hidden >= 1, "bad layer sizes %d x %d", cfg->n_visible, cfg->n_hidden);
     BM_CHECK(cfg->max_batch >= 1, "max_batch must be >= 1");
     BM_CHECK(cfg->v_unit == BM_UNIT_BERNOULLI || cfg->v_unit == BM_UNIT_GAUSSIAN, "unknown visible unit %d", cfg->v_unit);
+    BM_CHECK(cfg->h_unit != BM_UNIT_NRELU, "bm_rbm64_create: NReLU hidden units (noisy rectified-linear) exist on the float32 path only");
     BM_CHECK(cfg->h_unit == BM_UNIT_BERNOULLI || cfg->h_unit == BM_UNIT_MULTINOMIAL, "unknown hidden unit %d", cfg->h_unit);
     BM_CHECK(cfg->h_unit != BM_UNIT_MULTINOMIAL || cfg->n_samples >= 1, "MultinomialRBM needs n_samples >= 1 (got %d)", cfg->n_samples);
     BM_CHECK(bm_device_count() > 0, "no HIP device visible: libbm355 has no CPU fallback");

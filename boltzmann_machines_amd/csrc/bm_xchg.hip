@@ -879,6 +879,7 @@ static int xchg_launch_apply(bm_rbm *h, bm_xchg *x, float N_global, float lr, fl
 // holds ITS slice (bm_rbm_exchange_gather_dw completes the replicas, e.g. before a checkpoint).
 int bm_rbm_exchange_apply_direct(bm_rbm *h, bm_xchg *x, int32_t B_global, float lr, float mom) {
     BM_CHECK(!h || !h->cen_on, "bm_rbm_exchange_apply_direct: the exchange's fused apply has no centred form; switch centering off");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_exchange_apply_direct"));
     BM_CHECK(h && x, "null argument");
     BM_CHECK(B_global > 0, "bm_rbm_exchange_apply_direct: B_global = %d must be positive", B_global);
     BM_TRY(xchg_launch_apply(h, x, (float)B_global, lr, mom, 0));
@@ -892,6 +893,7 @@ int bm_rbm_exchange_apply_direct(bm_rbm *h, bm_xchg *x, int32_t B_global, float 
 // data-parallel job must be made on every rank: the gather keeps each OWNER's slice.
 int bm_rbm_exchange_gather_dw(bm_rbm *h, bm_xchg *x) {
     BM_CHECK(h && x, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_exchange_gather_dw"));
     if (x->nranks == 1 || (!x->dw_stale && !(h->H % 4 == 0 && h->W.ld % 4 == 0 && h->W.ld == h->dW.ld))) {
         x->dw_stale = false; h->dw_sharded = false; return 0;
     }
@@ -904,6 +906,7 @@ int bm_rbm_exchange_gather_dw(bm_rbm *h, bm_xchg *x) {
 // the exchange step of data-parallel training over the direct path (bm_*_allreduce_grads over RCCL is the other)
 int bm_rbm_xchg_create(bm_rbm *h, int32_t rank, int32_t nranks, bm_xchg **out) {
     BM_CHECK(h && out, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_xchg_create"));
     void *p = nullptr; size_t n = 0;
     BM_TRY(bm_rbm_dev_ptr(h, "grad", &p, &n));
     return bm_xchg_create(rank, nranks, (float *)p, n, out);
@@ -1099,6 +1102,7 @@ int bm_dbm_ais_sharded_direct(bm_dbm *h, bm_xchg *x, int32_t n_betas, int32_t n_
 
 int bm_rbm_allreduce_grads_direct(bm_rbm *h, bm_xchg *x) {
     BM_CHECK(h && x, "null argument");
+    BM_TRY(refuse_nrelu(h, "bm_rbm_allreduce_grads_direct"));
     void *p = nullptr, *st = nullptr; size_t n = 0;
     BM_TRY(bm_rbm_dev_ptr(h, "grad", &p, &n));
     BM_CHECK(p == (void *)x->buf && n == x->count, "the exchange was created for another buffer (gradient slots are not supported)");

@@ -112,6 +112,10 @@ class DBM(CenteredTraining, TemperedNegativePhase, EngineModel):
     # ---- composition from pre-trained RBMs (reference dbm.py:207-231) ------------------
     def load_rbms(self, rbms):
         if rbms is not None:
+            for i, rbm in enumerate(rbms):
+                if int(getattr(rbm, '_H_UNIT', _ffi.UNIT_BERNOULLI)) == _ffi.UNIT_NRELU:
+                    raise ValueError('DBM.load_rbms: layer %d (%s) has noisy rectified-linear (NReLU) hidden units; the DBM has no '
+                                     'such layer (its mean-field and AIS need Bernoulli or Multinomial units)' % (i, type(rbm).__name__))
             self._rbms = rbms
             # `self._h_layers = [rbm._h_layer for rbm in self._rbms]` (dbm.py:226): the hidden layer of every RBM
             self.h_units_ = [int(getattr(rbm, '_H_UNIT', _ffi.UNIT_BERNOULLI)) for rbm in rbms]

@@ -207,6 +207,13 @@ class RbmEngine(_PtCalls):
     def transform(self, Xd, B, k, Hd, row=0, out_row=0):
         check(self.lib.bm_rbm_transform(self._h, Xd.offset_ptr(row * self.V), B, k, Hd.offset_ptr(out_row * self.H)))
 
+    def sample_h(self, Xd, B, Hmean_d=None, Hstate_d=None, row=0, out_row=0):
+        """one prop-up of the handle's own hidden conditional from rows [row, row + B) of Xd, the input taken as given
+        (bm_rbm_sample_h): means and / or states into rows [out_row, out_row + B) of the dense DeviceArrays"""
+        check(self.lib.bm_rbm_sample_h(self._h, Xd.offset_ptr(row * self.V), B,
+                                       Hmean_d.offset_ptr(out_row * self.H) if Hmean_d is not None else None,
+                                       Hstate_d.offset_ptr(out_row * self.H) if Hstate_d is not None else None))
+
     def metrics(self, Xd, B, k, row=0):
         out = (C.c_float * 4)()
         check(self.lib.bm_rbm_metrics(self._h, Xd.offset_ptr(row * self.V), B, k, out))

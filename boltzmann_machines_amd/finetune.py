@@ -77,6 +77,9 @@ class StackClassifier(object):
                 raise ValueError('%s is the same model as an earlier layer (the same handle twice)' % name)
             if m._V_UNIT != _ffi.UNIT_BERNOULLI:
                 raise ValueError('%s has Gaussian visible units; a stack takes Bernoulli layers only' % name)
+            if m._H_UNIT == _ffi.UNIT_NRELU:
+                raise ValueError('%s (%s) has noisy rectified-linear (NReLU) hidden units; a stack (from_rbms) takes Bernoulli layers '
+                                 'only' % (name, type(m).__name__))
             if m._H_UNIT != _ffi.UNIT_BERNOULLI:
                 raise ValueError('%s has Multinomial hidden units; a stack takes Bernoulli layers only' % name)
             if np.dtype(m.dtype) != np.float32:
@@ -257,6 +260,9 @@ class StackClassifier(object):
         if isinstance(dbm, dict):
             params = dbm
         else:
+            if any(int(u) == _ffi.UNIT_NRELU for u in dbm.h_units_):
+                raise ValueError('StackClassifier.from_dbm: a layer with noisy rectified-linear (NReLU) hidden units; stacks of '
+                                 'Bernoulli layers only')
             if dbm.v_unit_ != _ffi.UNIT_BERNOULLI or any(int(u) != _ffi.UNIT_BERNOULLI for u in dbm.h_units_):
                 raise ValueError('StackClassifier.from_dbm: stacks of Bernoulli layers only (this DBM has Gaussian or Multinomial units)')
             if np.dtype(dbm.dtype) != np.float32:

@@ -707,6 +707,38 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
         eng.sync()
         return Hd.numpy().astype(np_dtype)
 
+    @run_on_engine(update_seed=True)
+    def sample_h(self, X, return_means=False):
+        """One draw of the hidden units given X, h ~ p(h | v = X), by a single prop-up of the model's own hidden conditional
+        (no counterpart in the reference).
+
+        X : [N, n_visible], taken as given: a GaussianRBM's input is NOT divided by `sigma` here, dropout is not applied.
+        Returns the hidden states [N, n_hidden] (with `return_means`: a pair, states and means).  The layer is always sampled,
+        whatever `sample_h_states` says.  The rows are processed in slices of at most `batch_size`, every row drawing from its
+        own position of the call's random stream: the result does not depend on the slicing.  One seed is drawn from the
+        model's host stream, as by every stochastic public call.  No parameter is changed.  float32 models only."""
+        eng = self._on_device()
+        if not isinstance(eng, RbmEngine):
+            raise NotImplementedError("%s.sample_h: dtype='%s' models are not supported (float32 only)"
+                                      % (self.__class__.__name__, np.dtype(self.dtype).name))
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.n_visible:
+            raise ValueError('`X` has invalid shape {0}: expected [N, {1}]'.format(X.shape, self.n_visible))
+        N = len(X)
+        Xd = self._to_device(X)
+        Sd = _ffi.DeviceArray((N, self.n_hidden), np.float32)
+        Md = _ffi.DeviceArray((N, self.n_hidden), np.float32) if return_means else None
+        home = self._rank * self.batch_size if getattr(self, '_dp', None) is not None else 0
+        try:
+            for start in range(0, N, self.batch_size):
+                # every slice at call 0 of the call's seed and at its own rows of the stream, as sample_v_given
+                eng.seed(self._graph_seed)
+                eng.set_row_offset(start)
+                eng.sample_h(Xd, min(self.batch_size, N - start), Md, Sd, row=start, out_row=start)
+            eng.sync()
+        finally:
+            eng.set_row_offset(home)
+        return (Sd.numpy(), Md.numpy()) if return_means else Sd.numpy()
 
     # ---- conditional sampling (no counterpart in the reference) ------------------------------------
     def _check_clampable(self, what):
@@ -911,6 +943,93 @@ class GaussianRBM(BaseRBM):
 
     def _sigma_vector(self):
         return np.asarray(self._sigma_tmp, dtype=self._np_dtype)
+
+
+class NReLUHidden(object):
+    """Noisy rectified-linear hidden units (NReLU; Nair & Hinton 2010), mixed in in front of an RBM class.
+
+    With t = vW + hb: hidden means max(0, t), hidden states max(0, t + n * sqrt(sigmoid(t))), n ~ N(0, 1).  `fit`, `transform`,
+    `sample_h`, `load_model`, checkpoints and `init_from` work as for the other classes; the update consumes the means and
+    states exactly as the Bernoulli update does.  The unit has no closed-form free energy and real-valued hidden states, so
+    everything built on either is refused with a ValueError before the engine is touched: the `pll` / `feg` metrics,
+    `sparsity_cost`, `dropout`, `dbm_first` / `dbm_last`, dtype='float64', `set_negative_phase('tempered')`, `set_centering`,
+    `set_classes`, `sample_v`, `sample_v_given`, `log_Z`, `log_proba`, BM355_DATA_PARALLEL jobs, and use as a layer of a `DBM`
+    or a `StackClassifier`."""
+
+    _H_UNIT = _ffi.UNIT_NRELU
+    _UNIT_NAME = 'noisy rectified-linear (NReLU) hidden units'
+
+    def _nrelu_refuse(self, what, why):
+        raise ValueError('%s.%s: %s with %s' % (self.__class__.__name__, what, why, self._UNIT_NAME))
+
+    def _check_nrelu_config(self, what):
+        """the constructor keywords the unit does not combine with (set_params may change them: checked again before the
+        engine is built)"""
+        for m in ('pll', 'feg'):
+            if self.metrics_config.get(m):
+                self._nrelu_refuse(what, "metrics_config['%s'] needs a free energy in closed form, which does not exist" % m)
+        if self.sparsity_cost != 0.:
+            self._nrelu_refuse(what, 'the sparsity penalty (sparsity_cost=%r) targets a probability; it is not combined' % (self.sparsity_cost,))
+        if self.dropout is not None:
+            self._nrelu_refuse(what, 'dropout (dropout=%r) is not combined' % (self.dropout,))
+        if self.dbm_first or self.dbm_last:
+            self._nrelu_refuse(what, 'dbm_first / dbm_last (a doubled conditional, a DBM layer) is not defined')
+        if np.dtype(self.dtype) != np.float32:
+            self._nrelu_refuse(what, "dtype='%s' is not supported (float32 only)" % np.dtype(self.dtype).name)
+
+    def __init__(self, *args, **kwargs):
+        super(NReLUHidden, self).__init__(*args, **kwargs)
+        self._check_nrelu_config('__init__')
+
+    def _ensure_engine(self):
+        if self._engine is None:
+            self._check_nrelu_config('fit')
+            if os.environ.get('BM355_DATA_PARALLEL', '0') == '1':
+                self._nrelu_refuse('fit', 'data-parallel mode (BM355_DATA_PARALLEL) is not combined: the split step has no such form')
+        return super(NReLUHidden, self)._ensure_engine()
+
+    def set_negative_phase(self, kind='cd', *args, **kwargs):
+        if kind != 'cd':
+            self._nrelu_refuse('set_negative_phase', 'a %r negative phase (the tempered family needs an energy) is not defined' % (kind,))
+        return super(NReLUHidden, self).set_negative_phase(kind, *args, **kwargs)
+
+    def set_centering(self, enabled=True, *args, **kwargs):
+        if enabled:
+            self._nrelu_refuse('set_centering', 'centering is not combined')
+        return super(NReLUHidden, self).set_centering(enabled, *args, **kwargs)
+
+    def set_classes(self, n_classes, *args, **kwargs):
+        if n_classes is not None:
+            self._nrelu_refuse('set_classes', 'a class head (exact p(y|x) sums softplus terms over Bernoulli units) is not defined')
+        return super(NReLUHidden, self).set_classes(n_classes, *args, **kwargs)
+
+    def sample_v(self, *args, **kwargs):
+        self._nrelu_refuse('sample_v', 'parallel tempering (it needs an energy) is not defined')
+
+    def sample_v_given(self, *args, **kwargs):
+        self._nrelu_refuse('sample_v_given', 'the clamped sweep is not built')
+
+    def log_Z(self, *args, **kwargs):
+        self._nrelu_refuse('log_Z', 'AIS (it needs a free energy in closed form) is not defined')
+
+    def log_proba(self, *args, **kwargs):
+        self._nrelu_refuse('log_proba', 'the likelihood (it needs a free energy in closed form) is not defined')
+
+
+class ReLURBM(NReLUHidden, BaseRBM):
+    """RBM with Bernoulli visible and noisy rectified-linear hidden units (Nair & Hinton 2010; no counterpart in the
+    reference).  See `NReLUHidden` for the unit and for what is refused."""
+
+    def __init__(self, model_path='relu_rbm_model/', *args, **kwargs):
+        super(ReLURBM, self).__init__(model_path=model_path, *args, **kwargs)
+
+
+class GaussianReLURBM(NReLUHidden, GaussianRBM):
+    """RBM with Gaussian visible (fixed `sigma`) and noisy rectified-linear hidden units: the usual model for real-valued data
+    (Nair & Hinton 2010; no counterpart in the reference).  See `NReLUHidden` for the unit and for what is refused."""
+
+    def __init__(self, learning_rate=1e-4, model_path='g_relu_rbm_model/', *args, **kwargs):
+        super(GaussianReLURBM, self).__init__(learning_rate=learning_rate, model_path=model_path, *args, **kwargs)
 
 
 def logit_mean(X):

@@ -53,7 +53,17 @@ int bm_debug_tile_map(int32_t tiles_i, int32_t tiles_j, double bytes_i, double b
 /* ------------------------------------------------------------------- RBM */
 typedef struct bm_rbm bm_rbm;
 
-enum { BM_UNIT_BERNOULLI = 0, BM_UNIT_GAUSSIAN = 1, BM_UNIT_MULTINOMIAL = 2 };
+/* BM_UNIT_NRELU: noisy rectified-linear HIDDEN units (Nair & Hinton 2010; no counterpart in the reference).  With
+ * t = v W + hb in float32: mean max(0, t), state max(0, t + n sqrt(sigmoid(t))), n a standard normal draw by position - the
+ * sigmoid of csrc/bm_numerics.h, a correctly rounded square root, one rounded multiply and one rounded add (no fused
+ * multiply-add).  bm_rbm_config.h_unit only, with Bernoulli or Gaussian visible units.  Such a handle trains (train_step,
+ * _metrics, _metrics_async, _epoch), transforms, runs bm_rbm_gibbs / bm_rbm_metrics / bm_rbm_sample_h and is staged like any
+ * other; out4[1] (pll) and out4[3] (free energy) of the metric calls are NaN - the unit has no closed-form free energy.  Refused,
+ * with a message that names NReLU: dbm_first / dbm_last, sparsity_cost != 0 and dropout (at create); bm_rbm_free_energy(_rows),
+ * bm_rbm_ais, bm_rbm_pt_*, bm_rbm_train_step_pt / _epoch_pt, bm_rbm_set_fast_weights, bm_rbm_set_centering, bm_rbm_set_classes
+ * and every bm_rbm_class_* entry, bm_rbm_gibbs_clamped, bm_rbm_grad_step / _apply_step and the gradient exchange entries,
+ * bm_rbm_backprop_down / _delta_update / the stack entries, bm_rbm64_create.  bm_rbm_set_fast_binary is accepted and runs fp32. */
+enum { BM_UNIT_BERNOULLI = 0, BM_UNIT_GAUSSIAN = 1, BM_UNIT_MULTINOMIAL = 2, BM_UNIT_NRELU = 3 };
 
 /* ctor kwargs of BaseRBM.__init__ that influence the device graph
  * (rbm/base_rbm.py:95-105, :244-327). */
@@ -145,6 +155,13 @@ int bm_rbm_apply_step(bm_rbm *h, int32_t B_global, float learning_rate, float mo
  * chain (base_rbm.py:426,438-440).  H_dev [B, n_hidden]. */
 int bm_rbm_transform(bm_rbm *h, const float *X_dev, int32_t B, int32_t n_gibbs_steps,
                      float *H_dev);
+
+/* One prop-up of the handle's OWN hidden conditional (every hidden unit type) from X_dev [B, n_visible], the input taken as
+ * given: no division by sigma, no dropout.  Hmean_dev / Hstate_dev [B, n_hidden] dense, either may be NULL (no states: no
+ * draw).  The states are drawn at site SITE_H0 (2), step 0, with the handle's seed, call counter and row offset - what the h0
+ * pass of bm_rbm_train_step draws for the same input - whatever sample_h_states says.  The call counter advances by one.
+ * B <= max_batch. */
+int bm_rbm_sample_h(bm_rbm *h, const float *X_dev, int32_t B, float *Hmean_dev, float *Hstate_dev);
 
 /* Metric fetches of base_rbm.py:554-564,578,605,612: out[0]=msre (:486-488),
  * out[1]=pll (:496-513), out[2]=l2_loss (:482-484), out[3]=free_energy
