@@ -150,6 +150,14 @@ struct ActArgs {
     // with n the standard normal draw of the output's flat index on the pass's key (the Gaussian layer's word-to-draw mapping);
     // a pass that does not sample stores s = m.  nrelu == 0: off.
     int nrelu;
+    // Softmax visible units (the SM flavour, act_kernel<..., SM = true>; launch_act_sm): a single-segment prop-down
+    // from W itself (x-major P) with mult == bmult == 1 whose logits l = z + b are formed as kind 3 forms them and whose I outputs
+    // are I / sm_k one-hot groups of sm_k in {2, 4, 8, 16} consecutive units, I % 4 == 0.  Per row and group, sequentially left to
+    // right: mx = max l; e[k] = exp_neg(min(mx - l[k], 80)); c[k] = c[k-1] + e[k]; S = c[sm_k-1]; mean[k] = e[k] / S; state[k] =
+    // (c[k] > t) && !(c[k-1] > t) with t = u * S, u the uniform of the group's first unit on the pass's key - the operation
+    // sequence of softmax_groups_kernel (bm_softmax_v.hip), which serves every other width.  A pass that does not sample stores
+    // state = mean.  sm_k == 0: off.
+    int sm_k;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -400,7 +408,7 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
 template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false,
-          bool CR = false, bool CB = false, bool BP = false, bool NR = false>
+          bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -537,11 +545,66 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                     s[r] = m[r];
                     continue;
                 }
+                if constexpr (SM) {            // l = z + b as kind 3 forms it; means and states below, once the quad is complete
+                    nt[r] = x + b;
+                    continue;
+                }
                 m[r] = (a.kind == 0) ? (LIT ? sigmoid_literal(x + b) : (HWMATH ? sigmoid_hw(x + b) : sigmoid(x + b)))
                                      : (a.kind == 1 ? (x * sg[4 * hlf + r] + b) : (a.kind == 3 ? x + b : x));
                 s[r] = m[r];
             }
-            if (!BP && a.sample) {
+            if constexpr (SM) {
+                // A group never straddles a tile, a wave or a 16-column slot: i0 and the wave's columns start at multiples of 16,
+                // the lane's quad at a multiple of 4, I % 4 == 0 makes the quad whole and I % sm_k == 0 makes the lanes of a group
+                // valid together (same row j, same l15: the shuffles below only ever read lanes that run this branch).  sm_k <= 4
+                // is local to the quad; sm_k = 8 / 16 spans the nl = 2 / 4 lanes g that share l15, in the order of g
+                static_assert(G::MI == 1, "the SM flavour exists for the geometries with one quad per lane");
+                const int Ks = a.sm_k, nl = (Ks >= 8) ? (Ks >> 2) : 1, pos = g & (nl - 1);
+                float mxa = fmaxf(nt[0], nt[1]), mxb = fmaxf(nt[2], nt[3]);
+                if (Ks > 2) {
+                    mxa = fmaxf(mxa, mxb);
+                    if (Ks >= 8) mxa = fmaxf(mxa, __shfl_xor(mxa, 16));
+                    if (Ks == 16) mxa = fmaxf(mxa, __shfl_xor(mxa, 32));
+                    mxb = mxa;
+                }
+                float ev[4], cc[4], cpv[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float d = ((r < 2) ? mxa : mxb) - nt[r];
+                    if (d > 80.0f) d = 80.0f;
+                    ev[r] = exp_neg(d);
+                }
+                // the running sum enters the lane at `start`: 0 for the first lane of a group, the preceding lane's last c otherwise
+                float start = 0.0f;
+                for (int step = 0; step < nl; ++step) {            // wave-uniform trip count
+                    if (step > 0) {
+                        const float recv = __shfl(cc[3], (lane + 48) & 63);
+                        if (pos == step) start = recv;
+                    }
+                    cpv[0] = start;          cc[0] = start + ev[0];
+                    cpv[1] = cc[0];          cc[1] = cc[0] + ev[1];
+                    cpv[2] = (Ks == 2) ? 0.0f : cc[1];
+                    cc[2] = cpv[2] + ev[2];
+                    cpv[3] = cc[2];          cc[3] = cc[2] + ev[3];
+                }
+                float Sa = cc[3], Sb = cc[3];
+                if (Ks == 2) Sa = cc[1];
+                if (Ks >= 8) { Sa = __shfl(cc[3], l15 + 16 * (g | (nl - 1))); Sb = Sa; }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { m[r] = ev[r] / ((r < 2) ? Sa : Sb); s[r] = m[r]; }
+                if (a.sample) {              // (I % 4 == 0: the lane's quad is one precomputed Philox block)
+                    const uint32_t *wds = rng.words(hlf);
+                    float ua = u32_to_uniform(wds[0]), ub = (Ks == 2) ? u32_to_uniform(wds[2]) : ua;
+                    if (Ks >= 8) { ua = __shfl(ua, l15 + 16 * (g & ~(nl - 1))); ub = ua; }
+                    const float ta = ua * Sa, tb = ub * Sb;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float t = (r < 2) ? ta : tb;
+                        s[r] = (cc[r] > t && !(cpv[r] > t)) ? 1.f : 0.f;
+                    }
+                }
+            }
+            if (!BP && !SM && a.sample) {
                 if constexpr (NR) {      // one normal per output: the lane's Philox block, or per element where I % 4 != 0
                     float n[4];
                     if (rng_fast) {
@@ -716,7 +779,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 // MINB: HIP's second __launch_bounds__ argument = WAVES PER SIMD the register budget must allow (for the 4-wave
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
-          bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false, bool NR = false>
+          bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false>
 BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -792,7 +855,7 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP, NR>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP, NR, SM>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];

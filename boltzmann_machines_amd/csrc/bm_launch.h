@@ -33,6 +33,10 @@
 //        either operand layout (W k-major, W^T x-major), whose epilogue rectifies t = z + b and draws one normal per output;
 //        geometry and tile map as CR (the plain prop-up's memo entry for the shape); its instantiations live in bm_nrelu.hip
 //        (launch_act_nr_as); combined with no other flavour
+//   SM   softmax visible units (ActArgs::sm_k): single-segment prop-downs with mult == bmult == 1 and an x-major P
+//        (W itself) whose epilogue turns every group of sm_k in {2, 4, 8, 16} logits into its means and its one-hot state; geometry
+//        and tile map as BP (the plain prop-down's memo entry for the shape); its instantiations - the x-major ones only - live
+//        in bm_softmax_v.hip (launch_act_sm_as); combined with no other flavour
 // FE, LIT and MF stage through LDS-DMA in the slab order.  dispatch_act walks the one ladder they share with the plain flavour:
 // x-major P / two K segments / one, each as the `fast` kernel (16-byte loads) or the one that passes every chunk through
 // registers (STG_DMA whatever the geometry's staging: shapes without 16-byte loads have ONE flavour).
@@ -152,14 +156,15 @@ template <class Args, class F> static inline int tune_tile_map(TuneTimer &tm, Ar
 static inline bool tune_log() { static const bool on = dbg("tune_log") != nullptr; return on; }
 
 // ---- act_kernel: one dispatcher for every flavour
-enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512, FL_NR = 1024 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
+enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512, FL_NR = 1024, FL_SM = 2048 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
 template <class G, int MINB, int STG, unsigned FL, bool SEG2, int PL>
 static inline void launch_act_kernel(bool fast, unsigned dyn_lds, hipStream_t st, const ActArgs &a, const TileMap &tmap) {
     const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
     constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0, CL = (FL & FL_CL) != 0,
-                   RT = (FL & FL_RT) != 0, CR = (FL & FL_CR) != 0, CB = (FL & FL_CB) != 0, BP = (FL & FL_BP) != 0, NR = (FL & FL_NR) != 0;
-    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP, NR>), grid, blk, dyn_lds, st, a, tmap);
-    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP, NR>), grid, blk, dyn_lds, st, a, tmap);
+                   RT = (FL & FL_RT) != 0, CR = (FL & FL_CR) != 0, CB = (FL & FL_CB) != 0, BP = (FL & FL_BP) != 0, NR = (FL & FL_NR) != 0,
+                   SM = (FL & FL_SM) != 0;
+    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM>), grid, blk, dyn_lds, st, a, tmap);
+    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM>), grid, blk, dyn_lds, st, a, tmap);
 }
 template <class G, int MINB, int STG, unsigned FL>
 static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, unsigned dyn_lds = 0) {
@@ -495,7 +500,34 @@ static inline void launch_act_nr(const ActArgs &a, hipStream_t st) {
     }
     launch_act_nr_as(T.geo, a, st);
 }
+// the prop-down of softmax visible units: the geometry `geo` of the SM flavour.  Defined in bm_softmax_v.hip, a
+// translation unit of its own for the reason bm_class.hip is one
+void launch_act_sm_as(int geo, const ActArgs &a, hipStream_t st);
+// ... per-pass fp32 launches always, on the plain flavour's memo entry for the shape (measured with the plain kernels)
+static inline void launch_act_sm(const ActArgs &a, hipStream_t st) {
+    const bool width_ok = a.sm_k == 2 || a.sm_k == 4 || a.sm_k == 8 || a.sm_k == 16;
+    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.row_mult || a.cr_part ||
+        a.cb_y || a.bp || a.nrelu || a.b3.K1 > 0 || a.lit || a.kind != 3 || a.mult != 1.0f || a.bmult != 1.0f || a.rowacc || a.rowdot_out ||
+        a.negmeans || !a.p_xm || !width_ok || (a.I & 3) != 0 || a.I % a.sm_k != 0) {
+        fprintf(stderr, "bm355: a softmax-group pass is a single-segment prop-down of its own flavour, groups of 2, 4, 8 or 16 (no such kernel)\n");
+        abort();
+    }
+    static const int geo_env = dbg_int("act_geo");
+    const int ov = geo_env ? geo_env : a.geo_hint;
+    if (ov) { launch_act_sm_as(ov, a, st); return; }
+    ActArgs plain = a;
+    plain.sm_k = 0; plain.kind = 0;         // (the Bernoulli prop-down of the shape: the same contraction, a draw per output)
+    const Tuned T = tuned_act(plain, st);
+    if (T.xi != XI_MODEL && !a.map_xi) {
+        ActArgs a2 = a;
+        a2.map_xi = T.xi;
+        launch_act_sm_as(T.geo, a2, st);
+        return;
+    }
+    launch_act_sm_as(T.geo, a, st);
+}
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
+    if (a.sm_k) { launch_act_sm(a, st); return; }
     if (a.nrelu) { launch_act_nr(a, st); return; }
     if (a.bp) { launch_act_bp(a, st); return; }
     if (a.cb_y) { launch_act_cb(a, st); return; }

@@ -15,6 +15,7 @@
 #include "bm_fast.h"
 #include "bm_class.h"
 #include "bm_stack.h"
+#include "bm_softmax_v.h"
 
 #include <math.h>
 #include <atomic>
@@ -107,6 +108,9 @@ struct bm_rbm {
     DevArray<double> scal;    // [6] device accumulators: msre, l2, F(x), F(x~), F'(x) (multinomial), spare
     bool multinomial() const { return cfg.h_unit == BM_UNIT_MULTINOMIAL; }
     bool nrelu() const { return cfg.h_unit == BM_UNIT_NRELU; }      // noisy rectified-linear hidden units
+    // softmax visible units (bm_rbm_set_visible_groups): the visible layer is V / v_groups one-hot groups of
+    // v_groups units each; 0: off (Bernoulli visible units)
+    int v_groups = 0;
     uint64_t seed = 0;
     uint32_t call = 0;
     int64_t row0 = 0;
@@ -192,8 +196,16 @@ static int check_dw(const bm_rbm *h, const char *what) {
     return 0;
 }
 
-// what a handle with noisy rectified-linear hidden units does not do (DESIGN.md 3.23 says why, entry by entry)
-static int refuse_nrelu(const bm_rbm *h, const char *what) {
+// what a handle with softmax visible units does not do (DESIGN.md 3.24 says why, entry by entry)
+static int refuse_softmax_v(const bm_rbm *h, const char *what) {
+    BM_CHECK(!h || !h->v_groups, "%s is not available for softmax visible units (bm_rbm_set_visible_groups: %d groups of %d): not "
+             "built for one-hot groups; see DESIGN.md 3.24", what, h->V / h->v_groups, h->v_groups);
+    return 0;
+}
+// what a handle with noisy rectified-linear hidden units does not do (DESIGN.md 3.23 says why, entry by entry) - and, at the
+// same entries but the free energies (groups_ok), one with softmax visible units
+static int refuse_nrelu(const bm_rbm *h, const char *what, bool groups_ok = false) {
+    if (!groups_ok) BM_TRY(refuse_softmax_v(h, what));
     BM_CHECK(!h || !h->nrelu(), "%s is not available for NReLU hidden units (noisy rectified-linear, BM_UNIT_NRELU): the unit has no "
              "closed-form free energy and real-valued hidden states; see DESIGN.md 3.23", what);
     return 0;
@@ -226,7 +238,8 @@ static void chain_begin(bm_rbm *h) {
     // per-class event timing, Multinomial hidden units (a softmax launch between the passes) and the fast-binary sweep
     // keep their per-pass launches
     // (noisy rectified-linear hidden units: their prop-up is a flavour of its own, never chained)
-    h->chain.on = !h->prof && !h->multinomial() && !h->nrelu() && !h->fast_now && chain_mode(h->chain) > 0;
+    // (softmax visible units: a softmax launch between the passes, as for Multinomial hidden units)
+    h->chain.on = !h->prof && !h->multinomial() && !h->nrelu() && !h->v_groups && !h->fast_now && chain_mode(h->chain) > 0;
 }
 static int chain_end(bm_rbm *h) {
     BM_CHECK(chain_flush(h->chain, h->stream, h->maxB) == 0, "chained launch: %s", hipGetErrorString(hipGetLastError()));
@@ -330,6 +343,28 @@ static void issue(bm_rbm *h, LayerPass p) {
         a.kind = 3; a.sample = 0; a.states = nullptr; a.negmeans = nullptr;
         launch_act(a, h->stream);
         hipLaunchKernelGGL(softmax_multinomial_kernel, dim3(a.J), dim3(64), 2 * (size_t)h->H * sizeof(float), h->stream, m);
+        return;
+    }
+    if (!up && h->v_groups) {
+        // softmax visible units.  Groups of 2, 4, 8 or 16 in a layer of V % 4 == 0: the SM flavour of the
+        // prop-down, one launch (BM355_DEBUG=sm_fused=0 sends these shapes down the generic path as well: the same bits)
+        static const bool fused_off = bm::dbg("sm_fused") && atoi(bm::dbg("sm_fused")) == 0;
+        const int K = h->v_groups;
+        if (!fused_off && (K == 2 || K == 4 || K == 8 || K == 16) && (a.I & 3) == 0) {
+            a.kind = 3; a.sm_k = K;
+            launch_act(a, h->stream);
+            return;
+        }
+        // every other shape: logits from the GEMM, in place of the means, then a lane per group for the softmax and the
+        // one-hot draw
+        SgArgs g;
+        memset(&g, 0, sizeof(g));
+        g.states = a.states; g.ld_states = a.ldo;
+        if (!a.means) { a.means = h->vm.p; a.ldo = h->vm.ld; }     // pure sampling sweep: vm is the scratch row store
+        g.L = a.means; g.ld = a.ldo; g.V = a.I; g.K = h->v_groups; g.J = a.J; g.sample = a.sample; g.key = a.key; g.row0 = a.row0;
+        a.kind = 3; a.sample = 0; a.states = nullptr;
+        launch_act(a, h->stream);
+        launch_softmax_groups(g, h->stream);
         return;
     }
     // noisy rectified-linear hidden units: the NR flavour rectifies t = z + b (formed as kind 3 forms it) and draws a normal
@@ -656,6 +691,7 @@ static void metrics_to_out4(const bm_rbm *h, const double *host, int B, float *o
     out4[2] = h->cfg.l2 * (float)(0.5 * host[1]);               // l2_loss       :483
     out4[3] = (float)fe;                                        // free energy   :516
     if (h->nrelu()) out4[1] = out4[3] = nanf("");               // noisy rectified-linear hidden units: neither exists in closed form
+    if (h->v_groups) out4[1] = nanf("");                        // softmax visible units: a row with one bit flipped is no state of the model
 }
 
 // ---- AIS log Z of the RBM itself and per-row free energies (bm355.h: bm_rbm_ais, bm_rbm_free_energy_rows)
@@ -705,8 +741,8 @@ __global__ __launch_bounds__(256) void rbm_fe_rows_kernel(const float *X, int ld
 }
 
 // the two entry points are about the joint p(v, h) of ONE Bernoulli-Bernoulli RBM
-static int check_single_joint(const bm_rbm *h, const char *what) {
-    BM_TRY(refuse_nrelu(h, what));
+static int check_single_joint(const bm_rbm *h, const char *what, bool groups_ok = false) {
+    BM_TRY(refuse_nrelu(h, what, groups_ok));
     BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "%s needs Bernoulli visible units (this handle's are Gaussian)", what);
     BM_CHECK(!h->multinomial(), "%s needs Bernoulli hidden units (this handle's are Multinomial)", what);
     BM_CHECK(!h->cfg.dbm_first && !h->cfg.dbm_last, "%s: the conditionals of a dbm_first / dbm_last handle (one of them doubled) "
@@ -1388,6 +1424,38 @@ int bm_rbm_sample_h(bm_rbm *h, const float *X_dev, int32_t B, float *Hmean_dev, 
     return 0;
 }
 
+// The visible counterpart: one prop-down of the handle's own visible conditional from H_dev [B][H] (dense), taken as given:
+// means and / or states to dense [B][V] outputs, drawn at SITE_V, step 0, the handle's seed, call counter and row offset (bm355.h).
+// Every visible unit type.  The counter advances by one
+int bm_rbm_sample_v_from_h(bm_rbm *h, const float *H_dev, int32_t B, float *Vmean_dev, float *Vstate_dev) {
+    BM_CHECK(h && H_dev, "null argument");
+    BM_CHECK(Vmean_dev || Vstate_dev, "bm_rbm_sample_v_from_h: no output (means and states are both null)");
+    BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
+    issue(h, rbm_pass(h, false, B, LayerIn{H_dev, h->H}, rbm_out(h, 1, Vmean_dev, Vstate_dev, h->V, SITE_V, 0)));
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// Softmax visible units (bm355.h).  A property of the handle that issue() reads at every prop-down
+int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K) {
+    BM_CHECK(h, "null argument");
+    if (K == 0) { h->v_groups = 0; return 0; }
+    BM_CHECK(K >= 2, "softmax visible units: the group width must be 0 (off) or >= 2 (got %d)", (int)K);
+    BM_CHECK(h->V % K == 0, "softmax visible units: n_visible = %d is no multiple of the group width %d", h->V, (int)K);
+    BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "softmax visible units replace Bernoulli visible units (this handle's are Gaussian)");
+    BM_CHECK(h->cfg.h_unit == BM_UNIT_BERNOULLI, "softmax visible units need Bernoulli hidden units (this handle's are %s)",
+             h->multinomial() ? "Multinomial" : "NReLU");
+    BM_CHECK(!h->cfg.dbm_first && !h->cfg.dbm_last, "softmax visible units: no dbm_first / dbm_last handle (the DBM has no such layer)");
+    BM_CHECK(h->cfg.dropout < 0.f, "softmax visible units do not combine with dropout (this handle's is %g)", (double)h->cfg.dropout);
+    BM_CHECK(!h->cen_on, "softmax visible units do not combine with centering (bm_rbm_set_centering(off) first)");
+    BM_CHECK(!h->n_classes, "softmax visible units do not combine with a class head (bm_rbm_set_classes(0) first)");
+    BM_CHECK(!h->fw_on, "softmax visible units do not combine with fast weights (bm_rbm_set_fast_weights(off) first)");
+    BM_CHECK(h->pt.M == 0, "softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
+    h->v_groups = K;
+    return 0;
+}
+
 int bm_rbm_metrics(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float *out4) {
     ChainOpts o;
     o.fetch = true;
@@ -1398,7 +1466,7 @@ int bm_rbm_metrics(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float *o
 }
 
 int bm_rbm_free_energy(bm_rbm *h, const float *X_dev, int32_t B, float *out1) {
-    BM_TRY(refuse_nrelu(h, "bm_rbm_free_energy"));
+    BM_TRY(refuse_nrelu(h, "bm_rbm_free_energy", true));
     BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
     // free_energy_op is built from self._X_batch AFTER tf.nn.dropout replaced it (base_rbm.py:417-418,
     // :516): the `feg` metric sees the dropped input like msre / pll do
@@ -1421,7 +1489,7 @@ int bm_rbm_free_energy(bm_rbm *h, const float *X_dev, int32_t B, float *out1) {
 // change of the RNG call counter): one prop-up that only leaves its softplus slot partials, one row kernel
 int bm_rbm_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, float *out_host) {
     BM_CHECK(h && X_dev && out_host, "null argument");
-    BM_TRY(check_single_joint(h, "bm_rbm_free_energy_rows"));
+    BM_TRY(check_single_joint(h, "bm_rbm_free_energy_rows", true));
     BM_CHECK(B >= 1, "bad row count %d", (int)B);
     if (B > h->fer_rows) {
         h->fer_rows = 0;
@@ -2179,7 +2247,7 @@ int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_ste
     BM_CHECK(H_dev && V_dev, "null state pointer");
     BM_CHECK(n_steps >= 1, "n_steps must be >= 1");
     struct FastScope { bm_rbm *h; ~FastScope() { h->fast_now = false; } } fast_scope{h};
-    const bool fast = h->fast && h->cfg.v_unit == BM_UNIT_BERNOULLI && !h->multinomial() && !h->nrelu() && h->cfg.sample_v_states &&
+    const bool fast = h->fast && h->cfg.v_unit == BM_UNIT_BERNOULLI && !h->multinomial() && !h->nrelu() && !h->v_groups && h->cfg.sample_v_states &&
                       h->cfg.sample_h_states && h->cfg.dropout < 0.f;
     if (!fast && !h->multinomial()) {
         // The sweeps read and write the caller's dense buffers IN PLACE: the first prop-down takes H_dev (pitch H) as its

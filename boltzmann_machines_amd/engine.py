@@ -68,7 +68,7 @@ class RbmEngine(_PtCalls):
     def __init__(self, n_visible, n_hidden, v_unit=_ffi.UNIT_BERNOULLI, sample_v_states=False,
                  sample_h_states=True, dbm_first=False, dbm_last=False, max_batch=10, l2=1e-4,
                  sparsity_target=0.1, sparsity_cost=0., sparsity_damping=0.9, dropout=None,
-                 h_unit=_ffi.UNIT_BERNOULLI, n_samples=0):
+                 h_unit=_ffi.UNIT_BERNOULLI, n_samples=0, v_groups=0):
         self.lib = _ffi.load()
         self.V, self.H, self.max_batch = int(n_visible), int(n_hidden), int(max_batch)
         cfg = _ffi.RbmConfig(self.V, self.H, int(v_unit), int(bool(sample_v_states)),
@@ -78,6 +78,12 @@ class RbmEngine(_PtCalls):
                              int(h_unit), int(n_samples))
         self._h = C.c_void_p()
         check(self.lib.bm_rbm_create(C.byref(cfg), C.byref(self._h)))
+        if v_groups:          # softmax visible units: n_visible / v_groups one-hot groups (bm_rbm_set_visible_groups)
+            try:
+                self.set_visible_groups(v_groups)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifetime
     def close(self):
@@ -213,6 +219,17 @@ class RbmEngine(_PtCalls):
         check(self.lib.bm_rbm_sample_h(self._h, Xd.offset_ptr(row * self.V), B,
                                        Hmean_d.offset_ptr(out_row * self.H) if Hmean_d is not None else None,
                                        Hstate_d.offset_ptr(out_row * self.H) if Hstate_d is not None else None))
+
+    def sample_v_from_h(self, Hd, B, Vmean_d=None, Vstate_d=None, row=0, out_row=0):
+        """one prop-down of the handle's own visible conditional from rows [row, row + B) of Hd, taken as given
+        (bm_rbm_sample_v_from_h): means and / or states into rows [out_row, out_row + B) of the dense DeviceArrays"""
+        check(self.lib.bm_rbm_sample_v_from_h(self._h, Hd.offset_ptr(row * self.H), B,
+                                              Vmean_d.offset_ptr(out_row * self.V) if Vmean_d is not None else None,
+                                              Vstate_d.offset_ptr(out_row * self.V) if Vstate_d is not None else None))
+
+    def set_visible_groups(self, K):
+        """softmax visible units (bm_rbm_set_visible_groups): n_visible / K one-hot groups of K units; 0: Bernoulli units again"""
+        check(self.lib.bm_rbm_set_visible_groups(self._h, int(K)))
 
     def metrics(self, Xd, B, k, row=0):
         out = (C.c_float * 4)()

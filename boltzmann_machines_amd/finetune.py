@@ -77,6 +77,9 @@ class StackClassifier(object):
                 raise ValueError('%s is the same model as an earlier layer (the same handle twice)' % name)
             if m._V_UNIT != _ffi.UNIT_BERNOULLI:
                 raise ValueError('%s has Gaussian visible units; a stack takes Bernoulli layers only' % name)
+            if getattr(m, '_V_GROUP_WIDTH', 0):
+                raise ValueError('%s (%s) has softmax visible units; a stack (from_rbms) takes Bernoulli layers only'
+                                 % (name, type(m).__name__))
             if m._H_UNIT == _ffi.UNIT_NRELU:
                 raise ValueError('%s (%s) has noisy rectified-linear (NReLU) hidden units; a stack (from_rbms) takes Bernoulli layers '
                                  'only' % (name, type(m).__name__))

@@ -63,6 +63,7 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
 
     _V_UNIT = _ffi.UNIT_BERNOULLI
     _H_UNIT = _ffi.UNIT_BERNOULLI
+    _V_GROUP_WIDTH = 0           # softmax visible units (CategoricalRBM): the width of a one-hot group; 0: none
 
     def __init__(self,
                  n_visible=784, v_layer_cls=None, v_layer_params=None,
@@ -192,8 +193,10 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
         variables = self._initial_variables()
         f64 = np.dtype(self.dtype) == np.float64
         if np.dtype(self.dtype) == np.float32 or f64:
+            # (softmax visible units, CategoricalRBM: a property of the float32 handle)
+            groups = {} if f64 or not self._V_GROUP_WIDTH else dict(v_groups=int(self._V_GROUP_WIDTH))
             self._engine = (RbmEngine64 if f64 else RbmEngine)(
-                                     self.n_visible, self.n_hidden, v_unit=self._V_UNIT,
+                                     self.n_visible, self.n_hidden, v_unit=self._V_UNIT, **groups,
                                      sample_v_states=self.sample_v_states, sample_h_states=self.sample_h_states,
                                      dbm_first=self.dbm_first, dbm_last=self.dbm_last, max_batch=self.batch_size,
                                      l2=self.l2, sparsity_target=self.sparsity_target,
@@ -740,6 +743,38 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
             eng.set_row_offset(home)
         return (Sd.numpy(), Md.numpy()) if return_means else Sd.numpy()
 
+    @run_on_engine(update_seed=True)
+    def sample_v_from_h(self, H, return_means=False):
+        """One draw of the visible units given H, v ~ p(v | h = H), by a single prop-down of the model's own visible conditional
+        (no counterpart in the reference): the visible counterpart of `sample_h`.
+
+        H : [N, n_hidden], taken as given.  Returns the visible states [N, n_visible] (with `return_means`: a pair, states and
+        means) - for a GaussianRBM in the units of the chain (the input divided by `sigma`).  The layer is always sampled,
+        whatever `sample_v_states` says.  The rows are processed in slices of at most `batch_size`, every row drawing from its
+        own position of the call's random stream: the result does not depend on the slicing.  One seed is drawn from the
+        model's host stream, as by every stochastic public call.  No parameter is changed.  float32 models only."""
+        eng = self._on_device()
+        if not isinstance(eng, RbmEngine):
+            raise NotImplementedError("%s.sample_v_from_h: dtype='%s' models are not supported (float32 only)"
+                                      % (self.__class__.__name__, np.dtype(self.dtype).name))
+        H = np.ascontiguousarray(H, dtype=np.float32)
+        if H.ndim != 2 or H.shape[1] != self.n_hidden:
+            raise ValueError('`H` has invalid shape {0}: expected [N, {1}]'.format(H.shape, self.n_hidden))
+        N = len(H)
+        Hd = self._to_device(H)
+        Sd = _ffi.DeviceArray((N, self.n_visible), np.float32)
+        Md = _ffi.DeviceArray((N, self.n_visible), np.float32) if return_means else None
+        home = self._rank * self.batch_size if getattr(self, '_dp', None) is not None else 0
+        try:
+            for start in range(0, N, self.batch_size):
+                eng.seed(self._graph_seed)
+                eng.set_row_offset(start)
+                eng.sample_v_from_h(Hd, min(self.batch_size, N - start), Md, Sd, row=start, out_row=start)
+            eng.sync()
+        finally:
+            eng.set_row_offset(home)
+        return (Sd.numpy(), Md.numpy()) if return_means else Sd.numpy()
+
     # ---- conditional sampling (no counterpart in the reference) ------------------------------------
     def _check_clampable(self, what):
         name = '%s.%s' % (self.__class__.__name__, what)
@@ -1030,6 +1065,149 @@ class GaussianReLURBM(NReLUHidden, GaussianRBM):
 
     def __init__(self, learning_rate=1e-4, model_path='g_relu_rbm_model/', *args, **kwargs):
         super(GaussianReLURBM, self).__init__(learning_rate=learning_rate, model_path=model_path, *args, **kwargs)
+
+
+class SoftmaxVisible(object):
+    """Softmax (categorical) visible units (Salakhutdinov, Mnih & Hinton 2007), mixed in in front of an RBM
+    class: the visible layer is `n_groups` groups of `n_categories` mutually exclusive units, one-hot per group.
+
+    p(v_{gK+k} = 1 | h) = softmax_k((hW^T + vb)_{gK..gK+K-1}) independently per group; the hidden conditional, the update and
+    the free energy are the Bernoulli ones.  `fit`, `transform`, `sample_h`, `sample_v_from_h`, `log_proba`, `load_model`,
+    checkpoints and `init_from` work as for the other classes.  What is not built for one-hot groups is refused with a
+    ValueError before the engine is touched: the `pll` metric, `dropout`, `dbm_first` / `dbm_last`, dtype='float64',
+    `set_negative_phase` other than 'cd', `set_centering`, `set_classes`, `sample_v_given`, `log_Z`, BM355_DATA_PARALLEL jobs,
+    and use as a layer of a `DBM` or a `StackClassifier`."""
+
+    _UNIT_NAME = 'softmax visible units'
+
+    @property
+    def _V_GROUP_WIDTH(self):
+        return int(self.n_categories)
+
+    def _softmax_refuse(self, what, why):
+        raise ValueError('%s.%s: %s with %s' % (self.__class__.__name__, what, why, self._UNIT_NAME))
+
+    def _check_softmax_config(self, what):
+        """the constructor keywords the unit does not combine with (set_params may change them: checked again before the
+        engine is built)"""
+        if int(self.n_groups) < 1 or int(self.n_categories) < 2:
+            raise ValueError('%s.%s: n_groups must be >= 1 and n_categories >= 2 (got %r, %r)'
+                             % (self.__class__.__name__, what, self.n_groups, self.n_categories))
+        if self.n_visible != int(self.n_groups) * int(self.n_categories):
+            raise ValueError('%s.%s: n_visible = %r is not n_groups x n_categories = %d x %d'
+                             % (self.__class__.__name__, what, self.n_visible, self.n_groups, self.n_categories))
+        if self.metrics_config.get('pll'):
+            self._softmax_refuse(what, "metrics_config['pll'] flips single bits, which leaves the one-hot states; it is not defined")
+        if self.dropout is not None:
+            self._softmax_refuse(what, 'dropout (dropout=%r) is not combined' % (self.dropout,))
+        if self.dbm_first or self.dbm_last:
+            self._softmax_refuse(what, 'dbm_first / dbm_last (a doubled conditional, a DBM layer) is not built')
+        if np.dtype(self.dtype) != np.float32:
+            self._softmax_refuse(what, "dtype='%s' is not supported (float32 only)" % np.dtype(self.dtype).name)
+
+    def __init__(self, *args, **kwargs):
+        super(SoftmaxVisible, self).__init__(*args, **kwargs)
+        self._check_softmax_config('__init__')
+
+    def _ensure_engine(self):
+        if self._engine is None:
+            self._check_softmax_config('fit')
+            if os.environ.get('BM355_DATA_PARALLEL', '0') == '1':
+                self._softmax_refuse('fit', 'data-parallel mode (BM355_DATA_PARALLEL) is not combined: the split step is not built')
+        return super(SoftmaxVisible, self)._ensure_engine()
+
+    def set_negative_phase(self, kind='cd', *args, **kwargs):
+        if kind != 'cd':
+            self._softmax_refuse('set_negative_phase', 'a %r negative phase (the tempered sweep has no softmax pass) is not built' % (kind,))
+        return super(SoftmaxVisible, self).set_negative_phase(kind, *args, **kwargs)
+
+    def set_centering(self, enabled=True, *args, **kwargs):
+        if enabled:
+            self._softmax_refuse('set_centering', 'centering is not combined')
+        return super(SoftmaxVisible, self).set_centering(enabled, *args, **kwargs)
+
+    def set_classes(self, n_classes, *args, **kwargs):
+        if n_classes is not None:
+            self._softmax_refuse('set_classes', 'a class head is not built')
+        return super(SoftmaxVisible, self).set_classes(n_classes, *args, **kwargs)
+
+    def sample_v_given(self, *args, **kwargs):
+        self._softmax_refuse('sample_v_given', 'the clamped sweep (clamped groups) is not built')
+
+    def log_Z(self, *args, **kwargs):
+        self._softmax_refuse('log_Z', 'AIS (its base model and its sweeps are Bernoulli) is not built')
+
+    # ---- one-hot coding
+    def encode(self, C):
+        """integer categories [N, n_groups] with entries in [0, n_categories) -> one-hot float32 [N, n_groups * n_categories]"""
+        C = np.asarray(C)
+        if C.ndim != 2 or C.shape[1] != self.n_groups:
+            raise ValueError('`C` has invalid shape {0}: expected [N, {1}]'.format(C.shape, self.n_groups))
+        Ci = C.astype(np.int64)
+        if C.size and (np.any(Ci != C) or Ci.min() < 0 or Ci.max() >= self.n_categories):
+            raise ValueError('`C` has entries outside the categories 0 .. {0}'.format(self.n_categories - 1))
+        X = np.zeros((len(C), self.n_groups, self.n_categories), dtype=np.float32)
+        np.put_along_axis(X, Ci[:, :, None], 1.0, axis=2)
+        return X.reshape(len(C), self.n_visible)
+
+    def decode(self, X):
+        """[N, n_groups * n_categories] (states or means) -> the argmax per group, int64 [N, n_groups]"""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != self.n_visible:
+            raise ValueError('`X` has invalid shape {0}: expected [N, {1}]'.format(X.shape, self.n_visible))
+        return X.reshape(len(X), self.n_groups, self.n_categories).argmax(axis=2)
+
+    @run_on_engine(update_seed=True)
+    def sample_v(self, n_samples, n_gibbs_steps=1000, V_init=None):
+        """Unconditional samples of the visible units by single-temperature block-Gibbs: `n_samples` independent chains run
+        `n_gibbs_steps` steps of (v ~ p(v|h), h ~ p(h|v)) from h ~ p(h | v_0); the one-hot states of the last step are returned,
+        [n_samples, n_visible].
+
+        V_init : [n_samples, n_visible] one-hot start of every chain; None: uniform categories drawn under the call's seed.
+        Both layers are always sampled (`sample_v_states` / `sample_h_states` do not apply): every pass is a
+        `bm_rbm_sample_v_from_h` / `bm_rbm_sample_h` call, which draw whatever the flags say, where `bm_rbm_gibbs` would follow
+        them.  The rows are processed in slices of at most `batch_size`, every row drawing from its own position of the call's
+        random stream: the result does not depend on the slicing.  One seed is drawn from the model's host stream; no
+        parameter is changed."""
+        eng = self._on_device()
+        n_samples, n_gibbs_steps = int(n_samples), int(n_gibbs_steps)
+        if n_samples < 1 or n_gibbs_steps < 1:
+            raise ValueError('`n_samples` and `n_gibbs_steps` must be >= 1 (got {0}, {1})'.format(n_samples, n_gibbs_steps))
+        if V_init is None:
+            V0 = self.encode(np.random.RandomState(self._graph_seed).randint(0, self.n_categories, (n_samples, self.n_groups)))
+        else:
+            V0 = np.ascontiguousarray(V_init, dtype=np.float32)
+            if V0.shape != (n_samples, self.n_visible):
+                raise ValueError('`V_init` has invalid shape {0}: expected [{1}, {2}]'.format(V0.shape, n_samples, self.n_visible))
+        Vd = self._to_device(V0)
+        Hd = _ffi.DeviceArray((n_samples, self.n_hidden), np.float32)
+        try:
+            for start in range(0, n_samples, self.batch_size):
+                B = min(self.batch_size, n_samples - start)
+                eng.seed(self._graph_seed)
+                eng.set_row_offset(start)
+                eng.sample_h(Vd, B, None, Hd, row=start, out_row=start)
+                for _ in range(n_gibbs_steps):
+                    eng.sample_v_from_h(Hd, B, None, Vd, row=start, out_row=start)
+                    eng.sample_h(Vd, B, None, Hd, row=start, out_row=start)
+            eng.sync()
+        finally:
+            eng.set_row_offset(0)
+        return Vd.numpy()
+
+
+class CategoricalRBM(SoftmaxVisible, BaseRBM):
+    """RBM with softmax (categorical) visible units and Bernoulli hidden units: `n_groups` one-hot groups of `n_categories`
+    units each, n_visible = n_groups * n_categories (no counterpart in the reference).  The model for ratings, quantised pixels,
+    characters, categorical table columns.  See `SoftmaxVisible` for the unit and for what is refused."""
+
+    def __init__(self, n_groups=1, n_categories=2, n_hidden=256, model_path='c_rbm_model/', *args, **kwargs):
+        self.n_groups, self.n_categories = n_groups, n_categories
+        n_visible = kwargs.pop('n_visible', None)          # (params.json carries it: load_model hands it back)
+        if n_visible is not None and int(n_visible) != int(n_groups) * int(n_categories):
+            raise ValueError('CategoricalRBM: n_visible = %r is not n_groups x n_categories = %r x %r' % (n_visible, n_groups, n_categories))
+        super(CategoricalRBM, self).__init__(n_visible=int(n_groups) * int(n_categories), n_hidden=n_hidden, model_path=model_path,
+                                             *args, **kwargs)
 
 
 def logit_mean(X):

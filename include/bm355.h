@@ -163,6 +163,29 @@ int bm_rbm_transform(bm_rbm *h, const float *X_dev, int32_t B, int32_t n_gibbs_s
  * B <= max_batch. */
 int bm_rbm_sample_h(bm_rbm *h, const float *X_dev, int32_t B, float *Hmean_dev, float *Hstate_dev);
 
+/* The visible counterpart of bm_rbm_sample_h: one prop-down of the handle's OWN visible conditional (every visible unit type,
+ * softmax groups included) from H_dev [B, n_hidden], taken as given.  Vmean_dev / Vstate_dev [B, n_visible] dense, either may
+ * be NULL (no states: no draw), not both.  The states are drawn at site SITE_V (3), step 0, with the handle's seed, call counter
+ * and row offset - what the first prop-down of bm_rbm_gibbs draws for the same input - whatever sample_v_states says.  The call
+ * counter advances by one.  B <= max_batch. */
+int bm_rbm_sample_v_from_h(bm_rbm *h, const float *H_dev, int32_t B, float *Vmean_dev, float *Vstate_dev);
+
+/* Softmax (categorical) visible units (no counterpart in the reference): turns the visible layer of a
+ * Bernoulli-visible, Bernoulli-hidden float32 handle into n_visible / K groups of K mutually exclusive units, one-hot per group;
+ * K = 0 turns it off again.  bm_rbm_config is unchanged.  With l = h W^T + vb, per row and group, sequentially left to right in
+ * float32: mx = max l; e[k] = exp_neg(min(mx - l[k], 80)); c[k] = c[k-1] + e[k]; S = c[K-1]; mean[k] = e[k] / S; the state is
+ * the first k with c[k] > u S, u the uniform of the layer's per-element stream at the group's first unit (site and call counter
+ * of a Bernoulli handle's visible pass).  The prop-up, the update and the free energy are the Bernoulli ones.  Such a handle
+ * trains (train_step, _metrics, _metrics_async, _epoch), transforms, runs bm_rbm_gibbs / bm_rbm_metrics / bm_rbm_sample_h /
+ * bm_rbm_sample_v_from_h / bm_rbm_free_energy(_rows) and is staged like any other; out4[1] (pll) of the metric calls is NaN,
+ * out4[3] the ordinary free energy.  Refused, with a message that contains "softmax visible" and leaves the handle usable - here:
+ * n_visible % K != 0, K == 1, K < 0, Gaussian visible units, Multinomial or NReLU hidden units, dbm_first / dbm_last, dropout, a
+ * handle with centering, a class head, fast weights or a tempered ensemble; on such a handle: bm_rbm_ais, bm_rbm_pt_*,
+ * bm_rbm_train_step_pt / _epoch_pt, bm_rbm_set_fast_weights, bm_rbm_set_centering, bm_rbm_set_classes and every bm_rbm_class_*
+ * entry, bm_rbm_gibbs_clamped, bm_rbm_grad_step / _apply_step and the gradient exchange entries, bm_rbm_backprop_down /
+ * _delta_update / the stack entries.  bm_rbm_set_fast_binary is accepted and runs fp32. */
+int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K);
+
 /* Metric fetches of base_rbm.py:554-564,578,605,612: out[0]=msre (:486-488),
  * out[1]=pll (:496-513), out[2]=l2_loss (:482-484), out[3]=free_energy
  * (:516-517; rbm.py:17-22 / :109-116).  Runs the same chain as train_step
