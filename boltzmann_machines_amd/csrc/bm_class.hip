@@ -1,4 +1,4 @@
-// bm_class.hip - the class head of a Bernoulli RBM: the CR flavour of act_kernel with its launcher, and the
+// bm_class.hip - the class head of a Bernoulli RBM: the instantiations of act_kernel's CR flavour, and the
 // three fixed-order kernels behind it (bm_class.h lists the launches of one update).  A translation unit of its own, as
 // bm_grad_cen.hip is: the kernels of the plain update are compiled exactly as before.  Compiled into libbm355.so next to bm355.hip.
 #define BM_KERNELS_ONLY

@@ -1,5 +1,5 @@
-// bm_class_joint.hip - joint training of the classification RBM and sampling by class: the CB flavour of
-// act_kernel with its launcher, and the small fixed-order kernels of the chain and the update (bm_class.h lists them).  A
+// bm_class_joint.hip - joint training of the classification RBM and sampling by class: the instantiations of
+// act_kernel's CB flavour, and the small fixed-order kernels of the chain and the update (bm_class.h lists them).  A
 // translation unit of its own, as bm_grad_cen.hip and bm_class.hip are: beside the CB instantiations the compiler allocates the
 // registers of some CR instantiations differently, and the kernels that exist are to stay exactly what they were
 // (profiles/class_joint_resources.md).  Compiled into libbm355.so next to bm355.hip.

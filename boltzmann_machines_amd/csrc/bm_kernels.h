@@ -100,13 +100,13 @@ struct ActArgs {
     const int *fe_flip;
     const float *fe_x; int fe_ldx;       // the pass's own input rows [J][K] (for x[j][fc])
     const float *fe_w; int fe_ldw;       // W [K][I] row-major (row fc)
-    // Conditional sampling (the CL flavour, act_kernel<..., CL = true>; launch_act_cl): outputs whose mask entry
+    // Conditional sampling (the CL flavour, act_kernel<..., CL = true>; FL_CL): outputs whose mask entry
     // is non-zero are CLAMPED - mean and state are replaced by clamp_val AFTER the draw (a clamped output's Philox words are
     // consumed by position like any other's: the free outputs get the bits of an unclamped pass), before the stores and
     // before the rowdot_out read-back.  Both arrays are [J][I] with the common pitch ld_clamp.  Null mask: off.
     const float *clamp_val, *clamp_mask;
     int ld_clamp;
-    // Parallel tempering (the RT flavour, act_kernel<..., RT = true>; launch_act_rt): a temperature PER ROW.
+    // Parallel tempering (the RT flavour, act_kernel<..., RT = true>; FL_RT): a temperature PER ROW.
     // row_mult [J]: the multiplier of z and of the bias of row j is row_mult[j] - it replaces mult / bmult,
     // m = sigmoid(row_mult[j] * z + row_mult[j] * b): the same two multiplies and one add.  Null: off.
     // rowen_out [ceil(I/16)][ld_part] (or null): slot partials of sum_i s_i * (z_i + b_i), s the state just drawn and z + b the
@@ -120,14 +120,14 @@ struct ActArgs {
     // dense negative particles of the update that follows.  The lane holds row_mult[j] already; no further load.  Null: off.
     float *sel_out;
     int sel_ld, sel_R, sel_rows;
-    // Class head (the CR flavour, act_kernel<..., CR = true>; launch_act_cr): the hidden prop-up of a
+    // Class head (the CR flavour, act_kernel<..., CR = true>; FL_CR): the hidden prop-up of a
     // classification RBM.  The pass stores t = z + b as `means` (kind 3, mult == bmult == 1) and leaves, for every class
     // c < cr_C, the slot partials of sum_i softplus(t_i + cr_U[c][i]) at cr_part[(c * cr_nslots + slot) * ld_part + j] - the
     // quad order and slot rule of `rowacc`, one class at a time (one accumulator live: cr_C costs no registers).  Null: off.
     float *cr_part;
     const float *cr_U;                   // [cr_C][I], pitch cr_ldu
     int cr_ldu, cr_C, cr_nslots;
-    // Joint training of the classification RBM (the CB flavour, act_kernel<..., CB = true>; launch_act_cb): the
+    // Joint training of the classification RBM (the CB flavour, act_kernel<..., CB = true>; FL_CB): the
     // hidden prop-up given (x, y).  Row j takes the bias b' = __fadd_rn(bias[i], cb_U[cb_y[j]][i]) - one rounded add - where
     // the plain pass takes bias[i] (mult == bmult == 1); everything behind it is the plain epilogue.  A label outside [0, cb_C)
     // indexes nothing: its row takes the plain bias and *cb_bad is raised.  Null cb_y: off.
@@ -135,7 +135,7 @@ struct ActArgs {
     const float *cb_U;                   // [cb_C][I], pitch cb_ldu
     int cb_ldu, cb_C;
     int *cb_bad;
-    // Back-propagation through a sigmoid layer (the BP flavour, act_kernel<..., BP = true>; launch_act_bp): the
+    // Back-propagation through a sigmoid layer (the BP flavour, act_kernel<..., BP = true>; FL_BP): the
     // prop-down of a delta.  A single-segment raw pass (kind 2, mult == 1, no bias, no draw) whose stored value is
     //   out[j][i] = __fmul_rn(__fmul_rn(z, a), __fsub_rn(1.0f, a)),   a = bp_act[j][i]       - (z * a) * (1 - a), three rounded steps
     // with bp_act a [J][I] activation matrix of pitch bp_ld, read the way dot_mat is; a null bp_act stores z itself.  (`bias` still
@@ -143,14 +143,14 @@ struct ActArgs {
     int bp;
     const float *bp_act;
     int bp_ld;
-    // Noisy rectified-linear hidden units (the NR flavour, act_kernel<..., NR = true>; launch_act_nr): a
+    // Noisy rectified-linear hidden units (the NR flavour, act_kernel<..., NR = true>; FL_NR): a
     // single-segment prop-up with mult == bmult == 1 whose pre-activation t = z + b is formed as kind 3 forms it and whose outputs are
     //   mean  m = (t > 0) ? t : 0                                      - a comparison: +0 for t <= 0, for -0 and for NaN
     //   state s = (u > 0) ? u : 0,  u = __fadd_rn(t, __fmul_rn(n, sqrt_rn(sigmoid(t))))          - every step rounded once
     // with n the standard normal draw of the output's flat index on the pass's key (the Gaussian layer's word-to-draw mapping);
     // a pass that does not sample stores s = m.  nrelu == 0: off.
     int nrelu;
-    // Softmax visible units (the SM flavour, act_kernel<..., SM = true>; launch_act_sm): a single-segment prop-down
+    // Softmax visible units (the SM flavour, act_kernel<..., SM = true>; FL_SM): a single-segment prop-down
     // from W itself (x-major P) with mult == bmult == 1 whose logits l = z + b are formed as kind 3 forms them and whose I outputs
     // are I / sm_k one-hot groups of sm_k in {2, 4, 8, 16} consecutive units, I % 4 == 0.  Per row and group, sequentially left to
     // right: mx = max l; e[k] = exp_neg(min(mx - l[k], 80)); c[k] = c[k-1] + e[k]; S = c[sm_k-1]; mean[k] = e[k] / S; state[k] =

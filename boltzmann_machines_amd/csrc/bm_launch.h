@@ -12,31 +12,29 @@
 //   MF   mean-field passes (ActArgs::prev / maxdiff / skip / chk_ctl / acc_init; ActSide<.., MF>).  Two tiles, by rule: 32 x 64
 //        (8 waves, one workgroup per CU) where that gives every CU a tile, else 32 x 32 (4 waves) - what the tuner picked for
 //        these passes at 784-512-1024 x 512 (profiles/r5_dbm_kernel_stats.csv); BM355_DEBUG=mf_geo=8|1 forces one
-//   CL   clamped outputs (ActArgs::clamp_mask / clamp_val; conditional sampling): single-segment passes.  NOT a
-//        tile of its own: the geometry and the block -> tile map are the ones the tuner chose (or now chooses, with the plain
-//        kernels) for the same shape in the plain flavour - one memo, no tuning run with the clamp loads; act_geo forces it
-//        like any pass.  With `lit`: the 32 x 32 parity tile of LIT.  Never the chained launch or the bf16 x 3 strip kernel
-//   RT   a temperature per row (ActArgs::row_mult / rowen_out; parallel tempering): passes of one or two
-//        K segments (the interior layer of a DBM: below first, above chained onto the same accumulator) on the geometry and
-//        tile map of the plain flavour's memo for the shape, exactly as CL; combined with no other flavour
-//   CR   the class rows of a classification RBM's prop-up (ActArgs::cr_part): single-segment kind-3 passes with
-//        mult == 1 on the geometry and tile map of the plain flavour's memo for the shape, exactly as CL; combined with no other
-//        flavour.  Its instantiations live in bm_class.hip, a translation unit of their own (launch_act_cr_as)
-//   CB   the class bias of a classification RBM's prop-up given (x, y) (ActArgs::cb_y): single-segment Bernoulli
-//        passes with mult == bmult == 1 whose row j adds U[y_j] to the bias; geometry and tile map as CR; its instantiations
-//        live in bm_class_joint.hip (launch_act_cb_as); combined with no other flavour
-//   BP   the prop-down of a delta through a sigmoid layer (ActArgs::bp / bp_act): single-segment raw passes (kind 2)
-//        with mult == 1, an x-major P (W itself), no draw and no row sums, whose epilogue multiplies by a (1 - a) of an activation
-//        matrix; geometry and tile map as CR (the plain prop-down's memo entry for the shape); its instantiations - the x-major
-//        ones only - live in bm_stack.hip (launch_act_bp_as); combined with no other flavour
-//   NR   noisy rectified-linear hidden units (ActArgs::nrelu): single-segment prop-ups with mult == bmult == 1, in
-//        either operand layout (W k-major, W^T x-major), whose epilogue rectifies t = z + b and draws one normal per output;
-//        geometry and tile map as CR (the plain prop-up's memo entry for the shape); its instantiations live in bm_nrelu.hip
-//        (launch_act_nr_as); combined with no other flavour
-//   SM   softmax visible units (ActArgs::sm_k): single-segment prop-downs with mult == bmult == 1 and an x-major P
-//        (W itself) whose epilogue turns every group of sm_k in {2, 4, 8, 16} logits into its means and its one-hot state; geometry
-//        and tile map as BP (the plain prop-down's memo entry for the shape); its instantiations - the x-major ones only - live
-//        in bm_softmax_v.hip (launch_act_sm_as); combined with no other flavour
+//   CL, RT, CR, CB, BP, NR, SM   the flavours of the table below (ActFlavour): each is selected by one field of ActArgs, admits a
+//        narrow kind of pass and is combined with NO other selector of a pass - another flavour's, the bf16 range, FE, the
+//        mean-field plumbing, `lit`, a second K segment - except those its entry tolerates (act_route; anything else: "no such
+//        kernel", abort).  None is a tile of its own: a pass runs on the geometry and the block -> tile map that the tuner chose
+//        (or now chooses, with the plain kernels) for the same shape in the plain flavour - one memo, keyed on the pass stripped
+//        of the flavour's fields, no tuning run with the flavour's loads; act_geo forces it like any pass
+//        (launch_act_flavoured).  Always per-pass fp32 launches: never the chained launch or the bf16 x 3 strip kernel.  What differs:
+//          CL   clamped outputs (conditional sampling): any single-segment pass; with `lit`, the 32 x 32 parity tile
+//               of LIT; a bf16 range on the pass is ignored, not refused
+//          RT   a temperature per row (parallel tempering): Bernoulli passes of one or two K segments (the
+//               interior layer of a DBM: below first, above chained onto the same accumulator; k-major P)
+//          CR   the class rows of a classification RBM's prop-up: logits passes (kind 3) without draw or row sums
+//          CB   the class bias of a classification RBM's prop-up given (x, y): Bernoulli passes whose row j adds
+//               U[y_j] to the bias
+//          BP   the prop-down of a delta through a sigmoid layer: raw passes (kind 2) from W itself, means only,
+//               whose epilogue multiplies by a (1 - a) of an activation matrix
+//          NR   noisy rectified-linear hidden units: logits prop-ups in either operand layout whose epilogue
+//               rectifies t = z + b and draws one normal per output
+//          SM   softmax visible units: logits prop-downs from W itself whose epilogue turns every group of sm_k in
+//               {2, 4, 8, 16} logits into its means and its one-hot state
+//        CR to SM take mult == bmult == 1 (BP: mult) and one K segment.  The instantiations of CL and RT live in bm355.hip, those of
+//        the other five in translation units of their own (ActFlavour::as) so that the kernels of every other unit are compiled
+//        exactly as before; BP and SM have the x-major kernels only (launch_act_xm_as)
 // FE, LIT and MF stage through LDS-DMA in the slab order.  dispatch_act walks the one ladder they share with the plain flavour:
 // x-major P / two K segments / one, each as the `fast` kernel (16-byte loads) or the one that passes every chunk through
 // registers (STG_DMA whatever the geometry's staging: shapes without 16-byte loads have ONE flavour).
@@ -63,6 +61,7 @@
 #include <array>
 #include <map>
 #include <mutex>
+#include <utility>
 #include "bm_common.h"
 
 namespace bm {
@@ -181,12 +180,138 @@ static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, un
         if (seg2) { launch_act_kernel<G, MINB, STG, FL, true, KM>(fast, dyn_lds, st, a, tmap); return; }
     launch_act_kernel<G, MINB, STG, FL, false, KM>(fast, dyn_lds, st, a, tmap);
 }
-// the plain flavour (FLX == 0) and RT (FLX == FL_RT) have two-segment kernels, CL (FLX == FL_CL), CR (FLX == FL_CR), CB
-// (FLX == FL_CB) and NR (FLX == FL_NR) have none;
-// x-major P exists for the geometries with MI == 1
+// ---- the flavours that run on the plain flavour's tuner entry: one table entry each, most specific first (act_route takes the
+// first entry whose selector the pass carries)
+constexpr unsigned FT_BF16 = 1u << 16;      // act_features: the pass carries a bf16 range (the strip kernel: no act_kernel flavour)
+using ActAsFn = void (*)(int geo, const ActArgs &a, hipStream_t st);
+// The geometry `geo` (launch_act_as codes) of the five flavours whose instantiations live in translation units of their own, as
+// those of bm_grad_cen.hip do: bm_class.hip (CR; the plain kernels are to stay exactly what they were), bm_class_joint.hip (CB;
+// beside the CB instantiations the compiler allocates the registers of a dozen CR instantiations differently, 1 - 4 VGPRs, and
+// those are to stay exactly what they were as well), bm_stack.hip (BP), bm_nrelu.hip (NR), bm_softmax_v.hip (SM).  Each is
+// launch_act_as<FL> and nothing else
+void launch_act_cr_as(int, const ActArgs &, hipStream_t), launch_act_cb_as(int, const ActArgs &, hipStream_t),
+     launch_act_bp_as(int, const ActArgs &, hipStream_t), launch_act_nr_as(int, const ActArgs &, hipStream_t),
+     launch_act_sm_as(int, const ActArgs &, hipStream_t);
+// An entry states
+//   seg2, xm_only, geo5   its kernel set: two-segment kernels exist / only the x-major-P kernels exist (a prop-down from W itself) /
+//                         geometry 5 exists (else the pass takes 7, the same tile at two workgroups per CU: the epilogues of CR and
+//                         CB do not fit the 168 registers of three workgroups per CU without scratch; NR takes that tile as well)
+// and, where it differs from ActFlavourDefaults,
+//   lit_tile              a Bernoulli pass with `lit` takes the 32 x 32 parity tile of LIT in this flavour (tolerates FL_LIT then)
+//   tolerates             the foreign selectors (act_features) a pass may carry; every other one refuses it
+//   as                    the geometry entry point in the flavour's own unit; null: launch_act_as<FL>, instantiated by the caller
+//   no_kernel             what a refused pass prints before it aborts
+//   selects / admits      the field that selects the flavour / what else the pass must look like
+//   strip                 the flavour's fields taken out: the plain pass of the same shape, which the tuner memo is keyed on
+struct ActFlavourDefaults {
+    static constexpr bool lit_tile = false;
+    static constexpr unsigned tolerates = 0;
+    static constexpr ActAsFn as = nullptr;
+};
+template <unsigned FL> struct ActFlavour;
+template <> struct ActFlavour<0> : ActFlavourDefaults { static constexpr bool seg2 = true, xm_only = false, geo5 = true; };      // plain: its kernel set only
+template <> struct ActFlavour<FL_CL> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = false, geo5 = true, lit_tile = true;
+    static constexpr unsigned tolerates = FL_LIT | FT_BF16;      // (clamp values may be grey levels: no bf16 shadow is written either)
+    static constexpr const char *no_kernel = "bm355: a clamped pass has one K segment and no metric-fetch or mean-field plumbing (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.clamp_mask != nullptr; }
+    static bool admits(const ActArgs &) { return true; }
+    static void strip(ActArgs &p) { p.clamp_mask = p.clamp_val = nullptr; p.ld_clamp = 0; }
+};
+template <> struct ActFlavour<FL_RT> : ActFlavourDefaults {
+    static constexpr bool seg2 = true, xm_only = false, geo5 = true;
+    static constexpr unsigned tolerates = FL_SEG2;
+    static constexpr const char *no_kernel = "bm355: a row-tempered pass is a Bernoulli pass of its own flavour (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.row_mult != nullptr; }
+    static bool admits(const ActArgs &a) { return a.kind == 0 && !(a.K2 > 0 && a.p_xm); }
+    static void strip(ActArgs &p) {      // (the clamp fields as well: no flavour reads them without a mask, the memo's tuning run sees none)
+        p.clamp_mask = p.clamp_val = nullptr; p.ld_clamp = 0;
+        p.row_mult = nullptr; p.rowen_out = nullptr; p.sel_out = nullptr; p.mult = p.bmult = 1.0f;
+    }
+};
+template <> struct ActFlavour<FL_CR> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = false, geo5 = false;
+    static constexpr ActAsFn as = launch_act_cr_as;
+    static constexpr const char *no_kernel = "bm355: a class-rows pass is a single-segment logits pass of its own flavour (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.cr_part != nullptr; }
+    static bool admits(const ActArgs &a) { return a.kind == 3 && a.mult == 1.0f && a.bmult == 1.0f && !a.sample && !a.rowacc && !a.rowdot_out; }
+    static void strip(ActArgs &p) { p.cr_part = nullptr; p.cr_U = nullptr; p.cr_ldu = p.cr_C = p.cr_nslots = 0; p.ld_part = 0; }
+};
+template <> struct ActFlavour<FL_CB> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = false, geo5 = false;
+    static constexpr ActAsFn as = launch_act_cb_as;
+    static constexpr const char *no_kernel = "bm355: a class-bias pass is a single-segment Bernoulli prop-up of its own flavour (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.cb_y != nullptr; }
+    static bool admits(const ActArgs &a) { return a.kind == 0 && a.mult == 1.0f && a.bmult == 1.0f && !a.rowacc && !a.rowdot_out && a.cb_U && a.cb_bad; }
+    static void strip(ActArgs &p) { p.cb_y = nullptr; p.cb_U = nullptr; p.cb_ldu = p.cb_C = 0; p.cb_bad = nullptr; }
+};
+template <> struct ActFlavour<FL_BP> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = true, geo5 = false;
+    static constexpr ActAsFn as = launch_act_bp_as;
+    static constexpr const char *no_kernel = "bm355: a back-propagation pass is a single-segment raw prop-down of its own flavour (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.bp != 0; }
+    static bool admits(const ActArgs &a) {
+        return a.kind == 2 && a.mult == 1.0f && !a.sample && !a.rowacc && !a.rowdot_out && !a.negmeans && !a.states && a.means && a.p_xm && a.bias;
+    }
+    static void strip(ActArgs &p) { p.bp = 0; p.bp_act = nullptr; p.bp_ld = 0; }
+};
+template <> struct ActFlavour<FL_NR> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = false, geo5 = false;
+    static constexpr ActAsFn as = launch_act_nr_as;
+    static constexpr const char *no_kernel = "bm355: a noisy rectified-linear pass is a single-segment prop-up of its own flavour (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.nrelu != 0; }
+    static bool admits(const ActArgs &a) { return a.kind == 3 && a.mult == 1.0f && a.bmult == 1.0f && !a.rowacc && !a.rowdot_out; }
+    static void strip(ActArgs &p) { p.nrelu = 0; p.kind = 0; }      // (the Bernoulli prop-up of the shape: the same contraction, a draw per output)
+};
+template <> struct ActFlavour<FL_SM> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = true, geo5 = false;
+    static constexpr ActAsFn as = launch_act_sm_as;
+    static constexpr const char *no_kernel = "bm355: a softmax-group pass is a single-segment prop-down of its own flavour, groups of 2, 4, 8 or 16 (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.sm_k != 0; }
+    static bool admits(const ActArgs &a) {
+        const bool width_ok = a.sm_k == 2 || a.sm_k == 4 || a.sm_k == 8 || a.sm_k == 16;
+        return a.kind == 3 && a.mult == 1.0f && a.bmult == 1.0f && !a.rowacc && !a.rowdot_out && !a.negmeans && a.p_xm && width_ok && (a.I & 3) == 0 &&
+               a.I % a.sm_k == 0;
+    }
+    static void strip(ActArgs &p) { p.sm_k = 0; p.kind = 0; }       // (the Bernoulli prop-down of the shape: the same contraction, a draw per output)
+};
+
+// the table's order: most specific first.  first(f): f(std::integral_constant<unsigned, FL>) for each flavour until one returns true
+template <unsigned... FL> struct ActFlavoursOf {
+    static unsigned selected(const ActArgs &a) { return ((ActFlavour<FL>::selects(a) ? FL : 0u) | ...); }
+    template <class F> static bool first(F &&f) { return (f(std::integral_constant<unsigned, FL>{}) || ...); }
+};
+using ActFlavours = ActFlavoursOf<FL_SM, FL_NR, FL_BP, FL_CB, FL_CR, FL_RT, FL_CL>;
+// every selector the pass carries: the FL_ bits of the table's flavours, FL_FE, FL_MF, FL_LIT, FL_SEG2 (K2 > 0) and FT_BF16
+static inline unsigned act_features(const ActArgs &a) {
+    return ActFlavours::selected(a) | (a.b3.K1 > 0 ? FT_BF16 : 0u) | (a.fe_flip ? FL_FE : 0u) |
+           ((a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init) ? FL_MF : 0u) | (a.lit ? FL_LIT : 0u) | (a.K2 > 0 ? FL_SEG2 : 0u);
+}
+// Where a pass goes: fl = the first flavour of the table that the pass selects (0: none - FE, MF, LIT, bf16 or plain), refusal =
+// null if that flavour has a kernel for the pass, else its message.  The rule of exclusivity: a flavour's pass carries no selector
+// but its own and those its entry tolerates.  No launch, no abort
+struct ActRoute { unsigned fl; const char *refusal; };
+static inline ActRoute act_route(const ActArgs &a) {
+    const unsigned f = act_features(a);
+    ActRoute r{0, nullptr};
+    ActFlavours::first([&](auto fl) {
+        using F = ActFlavour<decltype(fl)::value>;
+        if (!(f & fl.value)) return false;
+        r = {fl.value, (f & ~(fl.value | F::tolerates)) == 0 && F::admits(a) ? nullptr : F::no_kernel};
+        return true;
+    });
+    return r;
+}
+// what the tuner memo of the fp32 passes keys on besides I, J, K1 and K2 (tuned_act), of a plain pass
+static inline long long act_memo_flags(const ActArgs &a) {
+    return (long long)((a.sample ? 1 : 0) | (a.kind << 1) | (a.prev ? 16 : 0) | (a.rowacc ? 32 : 0) | (a.acc_init ? 64 : 0) | (a.p_xm ? 128 : 0) |
+                       (a.rowdot_out ? 256 : 0) | (a.dot_mat ? 512 : 0) | (a.negmeans ? 1024 : 0));
+}
+
+// (x-major P exists for the geometries with MI == 1)
 template <class G, int MINB, int STG, unsigned FLX = 0>
 static inline void launch_act_geo(const ActArgs &a, hipStream_t st) {
-    dispatch_act<G, MINB, STG, FLX | ((FLX == FL_CL || FLX == FL_CR || FLX == FL_CB || FLX == FL_NR) ? 0 : FL_SEG2) | (G::MI == 1 ? FL_XM : 0)>(a, st, a.map_xi);
+    dispatch_act<G, MINB, STG, FLX | (ActFlavour<FLX>::seg2 ? FL_SEG2 : 0) | (G::MI == 1 ? FL_XM : 0)>(a, st, a.map_xi);
 }
 #ifndef BM_KERNELS_ONLY
 static inline void launch_act_fe(const ActArgs &a, hipStream_t st) { dispatch_act<GeoAct8, 1, STG_DMA, FL_FE | FL_XM>(a, st, XI_SLAB); }
@@ -230,10 +355,40 @@ static inline void launch_act_bf3_as(int geo, const ActArgs &a, hipStream_t st) 
 }
 #endif  // BM_KERNELS_ONLY
 
+// The ladder of a flavour with the x-major kernels only (ActFlavour::xm_only: its passes are prop-downs from W itself).  geo: the
+// codes of launch_act_as, resolved as that ladder resolves them for an x-major P (6, 9, 4 -> 8; 5, 7 -> 3): every code lands on a
+// geometry with MI == 1 - one quad per lane, no scratch (profiles/stack_resources.md, softmax_v_resources.md).  The tile map and
+// the 16-byte / generic choice are dispatch_act's
+template <class G, int MINB, int STG, unsigned FLX>
+static inline void launch_act_xm_geo(const ActArgs &a, hipStream_t st) {
+    const double kt = (double)a.K1;
+    const TileMap tmap = make_tile_map((a.I + G::TI - 1) / G::TI, (a.J + G::TJ - 1) / G::TJ, kt * G::TI * 4.0, kt * G::TJ * 4.0, a.map_xi);
+    const bool fast = operand_fast(a.P1, XM, a.K1) && operand_fast(a.Q1, XM, a.K1);
+    launch_act_kernel<G, MINB, STG, FLX, false, XM>(fast, 0, st, a, tmap);
+}
+template <unsigned FLX>
+static inline void launch_act_xm_as(int geo, const ActArgs &a, hipStream_t st) {
+    static_assert(ActFlavour<FLX>::xm_only, "this flavour's ladder is launch_act_as");
+    if (geo == 208) { launch_act_xm_geo<GeoAct8, 1, STG_DMAH, FLX>(a, st); return; }
+    if (geo == 6 || geo == 9) geo = 8;
+    if (geo == 5 || geo == 7) geo = 3;
+    const bool reg = geo >= 100;
+    geo %= 100;
+    if (reg) {
+        if (geo == 1)      launch_act_xm_geo<GeoActS, 2, STG_REG, FLX>(a, st);
+        else if (geo == 3) launch_act_xm_geo<GeoActS32, 4, STG_REG, FLX>(a, st);
+        else               launch_act_xm_geo<GeoAct8, 1, STG_REG, FLX>(a, st);
+    } else {
+        if (geo == 1)      launch_act_xm_geo<GeoActS, 2, STG_DMA, FLX>(a, st);
+        else if (geo == 3) launch_act_xm_geo<GeoActS32, 4, STG_DMA, FLX>(a, st);
+        else               launch_act_xm_geo<GeoAct8, 1, STG_DMA, FLX>(a, st);
+    }
+}
 // geo: tile geometry 8 | 4 | 1 | 3, + 100 for register staging of the full chunks (default: LDS-DMA), or one of the specials
-// FLX: the flavour of the ladder's kernels (0 plain, FL_CL, FL_RT)
+// FLX: the flavour of the ladder's kernels (0 plain, or an entry of the table: what this instantiates follows its kernel-set facts)
 template <unsigned FLX = 0>
 static inline void launch_act_as(int geo, const ActArgs &a, hipStream_t st) {
+    static_assert(!ActFlavour<FLX>::xm_only, "this flavour's ladder is launch_act_xm_as");
     // 208: 8 waves, DMA issued by waves 0-3 only (not a tuner candidate: within noise of 8 on every shape measured)
     if (geo == 208) { launch_act_geo<GeoAct8, 1, STG_DMAH, FLX>(a, st); return; }
     // 6: 64 x 64 tile, 8 waves of 32 x 16 (the outer-product geometry): half the operand traffic per flop of the
@@ -245,9 +400,8 @@ static inline void launch_act_as(int geo, const ActArgs &a, hipStream_t st) {
     if (geo == 9 && !a.p_xm) { launch_act_geo<GeoGrad8h, 4, STG_DMA, FLX>(a, st); return; }
     if (geo == 9) geo = 8;
     // 5: 64 x 32 tile with BK = 32, three workgroups per CU (k-major P only)
-    // (CR, CB: their epilogues do not fit the 168 registers of three workgroups per CU without scratch - the same tile as 7;
-    //  NR takes that tile as well)
-    if constexpr (FLX != FL_CR && FLX != FL_CB && FLX != FL_NR) { if (geo == 5 && !a.p_xm) { launch_act_geo<GeoAct32, 3, STG_DMA, FLX>(a, st); return; } }
+    // (a flavour without it, ActFlavour::geo5, takes the same tile as 7)
+    if constexpr (ActFlavour<FLX>::geo5) { if (geo == 5 && !a.p_xm) { launch_act_geo<GeoAct32, 3, STG_DMA, FLX>(a, st); return; } }
     else if (geo == 5 && !a.p_xm) geo = 7;
     // 7: the same with two workgroups per CU (256 registers per wave: the two-segment variant spills 140 bytes at 168)
     if (geo == 7 && !a.p_xm) { launch_act_geo<GeoAct32, 2, STG_DMA, FLX>(a, st); return; }
@@ -356,189 +510,44 @@ static inline void launch_act_bf3(const ActArgs &a, hipStream_t st) {
     const Tuned T = memo.get({a.I, a.J, a.b3.K1, a.b3.K2, flags}, [&] { return tune_bf3_shape(a, st, flags); });
     launch_act_bf3_as(T.geo, a, st);
 }
-// the tuner's decision for the shape of `a` (ONE memo for the plain flavour, CL and RT; measured with the plain kernels)
+// the tuner's decision for the shape of the PLAIN pass `a` (ONE memo for the plain flavour and every flavour of the table, which
+// hands in its pass stripped; measured with the plain kernels)
 static inline Tuned tuned_act(const ActArgs &a, hipStream_t st) {
     static TuneMemo<5> memo;
-    const long long flags = (long long)((a.sample ? 1 : 0) | (a.kind << 1) | (a.prev ? 16 : 0) | (a.rowacc ? 32 : 0) |
-                                        (a.acc_init ? 64 : 0) | (a.p_xm ? 128 : 0) | (a.rowdot_out ? 256 : 0) |
-                                        (a.dot_mat ? 512 : 0) | (a.negmeans ? 1024 : 0));
-    return memo.get({a.I, a.J, a.K1, a.K2, flags}, [&] {
-        if (!a.clamp_mask && !a.row_mult) return tune_act_shape(a, st, flags);
-        ActArgs plain = a;
-        plain.clamp_mask = plain.clamp_val = nullptr; plain.ld_clamp = 0;
-        if (a.row_mult) { plain.row_mult = nullptr; plain.rowen_out = nullptr; plain.sel_out = nullptr; plain.mult = plain.bmult = 1.0f; }
-        return tune_act_shape(plain, st, flags);
-    });
+    const long long flags = act_memo_flags(a);
+    return memo.get({a.I, a.J, a.K1, a.K2, flags}, [&] { return tune_act_shape(a, st, flags); });
 }
-template <unsigned FLX = 0>
-static inline void launch_act_f32(const ActArgs &a, hipStream_t st) {
+// a per-pass fp32 launch of flavour FL (0: plain) on the geometry that is forced (act_geo, geo_hint) or tuned for the plain pass of
+// the shape, with the tuned tile map unless the caller chose one
+template <unsigned FL>
+static inline void launch_act_flavoured(const ActArgs &a, hipStream_t st) {
+    using F = ActFlavour<FL>;
+    const auto as = [&](int geo, const ActArgs &x) { if constexpr (F::as != nullptr) F::as(geo, x, st); else launch_act_as<FL>(geo, x, st); };
+    if constexpr (F::lit_tile)
+        if (a.lit && a.kind == 0) { dispatch_act<GeoActS, 2, STG_DMA, FL | FL_LIT | FL_XM>(a, st, XI_SLAB); return; }
     static const int geo_env = dbg_int("act_geo");
     const int ov = geo_env ? geo_env : a.geo_hint;
-    if (ov) { launch_act_as<FLX>(ov, a, st); return; }
-    const Tuned T = tuned_act(a, st);
+    if (ov) { as(ov, a); return; }
+    Tuned T;
+    if constexpr (FL == 0) T = tuned_act(a, st);        // (nothing to strip, no copy)
+    else { ActArgs plain = a; F::strip(plain); T = tuned_act(plain, st); }
     if (T.xi != XI_MODEL && !a.map_xi) {
         ActArgs a2 = a;
         a2.map_xi = T.xi;
-        launch_act_as<FLX>(T.geo, a2, st);
+        as(T.geo, a2);
         return;
     }
-    launch_act_as<FLX>(T.geo, a, st);
-}
-// clamped outputs: per-pass fp32 launches always (clamp values may be grey levels: no bf16 shadow is written either)
-static inline void launch_act_cl(const ActArgs &a, hipStream_t st) {
-    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init) {
-        fprintf(stderr, "bm355: a clamped pass has one K segment and no metric-fetch or mean-field plumbing (no such kernel)\n");
-        abort();
-    }
-    if (a.lit && a.kind == 0) { dispatch_act<GeoActS, 2, STG_DMA, FL_CL | FL_LIT | FL_XM>(a, st, XI_SLAB); return; }
-    launch_act_f32<FL_CL>(a, st);
-}
-// a temperature per row: per-pass fp32 launches always, one or two K segments, combined with nothing else (no such kernel)
-static inline void launch_act_rt(const ActArgs &a, hipStream_t st) {
-    if ((a.K2 > 0 && a.p_xm) || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.b3.K1 > 0 || a.lit ||
-        a.kind != 0) {
-        fprintf(stderr, "bm355: a row-tempered pass is a Bernoulli pass of its own flavour (no such kernel)\n");
-        abort();
-    }
-    launch_act_f32<FL_RT>(a, st);
-}
-// the class rows of a classification RBM's prop-up: the geometry `geo` (launch_act_as codes) of the CR flavour.  Defined in
-// bm_class.hip, a translation unit of its own as bm_grad_cen.hip is: the plain kernels are to stay exactly what they were
-void launch_act_cr_as(int geo, const ActArgs &a, hipStream_t st);
-// ... per-pass fp32 launches always, on the plain flavour's memo entry for the shape (measured with the plain kernels)
-static inline void launch_act_cr(const ActArgs &a, hipStream_t st) {
-    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.row_mult || a.b3.K1 > 0 ||
-        a.lit || a.kind != 3 || a.mult != 1.0f || a.bmult != 1.0f || a.sample || a.rowacc || a.rowdot_out) {
-        fprintf(stderr, "bm355: a class-rows pass is a single-segment logits pass of its own flavour (no such kernel)\n");
-        abort();
-    }
-    static const int geo_env = dbg_int("act_geo");
-    const int ov = geo_env ? geo_env : a.geo_hint;
-    if (ov) { launch_act_cr_as(ov, a, st); return; }
-    ActArgs plain = a;
-    plain.cr_part = nullptr; plain.cr_U = nullptr; plain.cr_ldu = plain.cr_C = plain.cr_nslots = 0; plain.ld_part = 0;
-    const Tuned T = tuned_act(plain, st);
-    if (T.xi != XI_MODEL && !a.map_xi) {
-        ActArgs a2 = a;
-        a2.map_xi = T.xi;
-        launch_act_cr_as(T.geo, a2, st);
-        return;
-    }
-    launch_act_cr_as(T.geo, a, st);
-}
-// the class-bias prop-up of the joint chain: the geometry `geo` of the CB flavour.  Defined in
-// bm_class_joint.hip, again a translation unit of its own: beside the CB instantiations the compiler allocates the registers of
-// a dozen CR instantiations differently (1 - 4 VGPRs), and those are to stay exactly what they were as well
-void launch_act_cb_as(int geo, const ActArgs &a, hipStream_t st);
-// ... per-pass fp32 launches always, on the plain flavour's memo entry for the shape (measured with the plain kernels)
-static inline void launch_act_cb(const ActArgs &a, hipStream_t st) {
-    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.row_mult || a.cr_part ||
-        a.b3.K1 > 0 || a.lit || a.kind != 0 || a.mult != 1.0f || a.bmult != 1.0f || a.rowacc || a.rowdot_out || !a.cb_U || !a.cb_bad) {
-        fprintf(stderr, "bm355: a class-bias pass is a single-segment Bernoulli prop-up of its own flavour (no such kernel)\n");
-        abort();
-    }
-    static const int geo_env = dbg_int("act_geo");
-    const int ov = geo_env ? geo_env : a.geo_hint;
-    if (ov) { launch_act_cb_as(ov, a, st); return; }
-    ActArgs plain = a;
-    plain.cb_y = nullptr; plain.cb_U = nullptr; plain.cb_ldu = plain.cb_C = 0; plain.cb_bad = nullptr;
-    const Tuned T = tuned_act(plain, st);
-    if (T.xi != XI_MODEL && !a.map_xi) {
-        ActArgs a2 = a;
-        a2.map_xi = T.xi;
-        launch_act_cb_as(T.geo, a2, st);
-        return;
-    }
-    launch_act_cb_as(T.geo, a, st);
-}
-// the prop-down of a delta: the geometry `geo` of the BP flavour.  Defined in bm_stack.hip, a translation unit of
-// its own for the reason bm_class.hip is one
-void launch_act_bp_as(int geo, const ActArgs &a, hipStream_t st);
-// ... per-pass fp32 launches always, on the plain flavour's memo entry for the shape (measured with the plain kernels)
-static inline void launch_act_bp(const ActArgs &a, hipStream_t st) {
-    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.row_mult || a.cr_part ||
-        a.cb_y || a.b3.K1 > 0 || a.lit || a.kind != 2 || a.mult != 1.0f || a.sample || a.rowacc || a.rowdot_out || a.negmeans ||
-        a.states || !a.means || !a.p_xm || !a.bias) {
-        fprintf(stderr, "bm355: a back-propagation pass is a single-segment raw prop-down of its own flavour (no such kernel)\n");
-        abort();
-    }
-    static const int geo_env = dbg_int("act_geo");
-    const int ov = geo_env ? geo_env : a.geo_hint;
-    if (ov) { launch_act_bp_as(ov, a, st); return; }
-    ActArgs plain = a;
-    plain.bp = 0; plain.bp_act = nullptr; plain.bp_ld = 0;
-    const Tuned T = tuned_act(plain, st);
-    if (T.xi != XI_MODEL && !a.map_xi) {
-        ActArgs a2 = a;
-        a2.map_xi = T.xi;
-        launch_act_bp_as(T.geo, a2, st);
-        return;
-    }
-    launch_act_bp_as(T.geo, a, st);
-}
-// the noisy rectified-linear prop-up: the geometry `geo` of the NR flavour.  Defined in bm_nrelu.hip, a translation
-// unit of its own for the reason bm_class.hip is one
-void launch_act_nr_as(int geo, const ActArgs &a, hipStream_t st);
-// ... per-pass fp32 launches always, on the plain flavour's memo entry for the shape (measured with the plain kernels)
-static inline void launch_act_nr(const ActArgs &a, hipStream_t st) {
-    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.row_mult || a.cr_part ||
-        a.cb_y || a.bp || a.b3.K1 > 0 || a.lit || a.kind != 3 || a.mult != 1.0f || a.bmult != 1.0f || a.rowacc || a.rowdot_out) {
-        fprintf(stderr, "bm355: a noisy rectified-linear pass is a single-segment prop-up of its own flavour (no such kernel)\n");
-        abort();
-    }
-    static const int geo_env = dbg_int("act_geo");
-    const int ov = geo_env ? geo_env : a.geo_hint;
-    if (ov) { launch_act_nr_as(ov, a, st); return; }
-    ActArgs plain = a;
-    plain.nrelu = 0; plain.kind = 0;        // (the Bernoulli prop-up of the shape: the same contraction, a draw per output)
-    const Tuned T = tuned_act(plain, st);
-    if (T.xi != XI_MODEL && !a.map_xi) {
-        ActArgs a2 = a;
-        a2.map_xi = T.xi;
-        launch_act_nr_as(T.geo, a2, st);
-        return;
-    }
-    launch_act_nr_as(T.geo, a, st);
-}
-// the prop-down of softmax visible units: the geometry `geo` of the SM flavour.  Defined in bm_softmax_v.hip, a
-// translation unit of its own for the reason bm_class.hip is one
-void launch_act_sm_as(int geo, const ActArgs &a, hipStream_t st);
-// ... per-pass fp32 launches always, on the plain flavour's memo entry for the shape (measured with the plain kernels)
-static inline void launch_act_sm(const ActArgs &a, hipStream_t st) {
-    const bool width_ok = a.sm_k == 2 || a.sm_k == 4 || a.sm_k == 8 || a.sm_k == 16;
-    if (a.K2 > 0 || a.fe_flip || a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init || a.clamp_mask || a.row_mult || a.cr_part ||
-        a.cb_y || a.bp || a.nrelu || a.b3.K1 > 0 || a.lit || a.kind != 3 || a.mult != 1.0f || a.bmult != 1.0f || a.rowacc || a.rowdot_out ||
-        a.negmeans || !a.p_xm || !width_ok || (a.I & 3) != 0 || a.I % a.sm_k != 0) {
-        fprintf(stderr, "bm355: a softmax-group pass is a single-segment prop-down of its own flavour, groups of 2, 4, 8 or 16 (no such kernel)\n");
-        abort();
-    }
-    static const int geo_env = dbg_int("act_geo");
-    const int ov = geo_env ? geo_env : a.geo_hint;
-    if (ov) { launch_act_sm_as(ov, a, st); return; }
-    ActArgs plain = a;
-    plain.sm_k = 0; plain.kind = 0;         // (the Bernoulli prop-down of the shape: the same contraction, a draw per output)
-    const Tuned T = tuned_act(plain, st);
-    if (T.xi != XI_MODEL && !a.map_xi) {
-        ActArgs a2 = a;
-        a2.map_xi = T.xi;
-        launch_act_sm_as(T.geo, a2, st);
-        return;
-    }
-    launch_act_sm_as(T.geo, a, st);
+    as(T.geo, a);
 }
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
-    if (a.sm_k) { launch_act_sm(a, st); return; }
-    if (a.nrelu) { launch_act_nr(a, st); return; }
-    if (a.bp) { launch_act_bp(a, st); return; }
-    if (a.cb_y) { launch_act_cb(a, st); return; }
-    if (a.cr_part) { launch_act_cr(a, st); return; }
-    if (a.row_mult) { launch_act_rt(a, st); return; }
-    if (a.clamp_mask) { launch_act_cl(a, st); return; }
+    const ActRoute r = act_route(a);
+    if (r.refusal) { fputs(r.refusal, stderr); abort(); }
+    if (ActFlavours::first([&](auto fl) { return r.fl == fl.value && (launch_act_flavoured<decltype(fl)::value>(a, st), true); })) return;
     if (a.b3.K1 > 0) { launch_act_bf3(a, st); return; }
     if (a.fe_flip) { launch_act_fe(a, st); return; }
     if (a.prev || a.maxdiff || a.skip || a.chk_ctl || a.acc_init) { launch_act_mf(a, st); return; }
     if (a.lit && a.kind == 0) { launch_act_lit(a, st); return; }
-    launch_act_f32(a, st);
+    launch_act_flavoured<0>(a, st);
     // fast-binary mode, an fp32 launch whose sampled states the NEXT launches read as a bf16 shadow: converted here (the
     // strip kernel writes its shadow itself; keeping the branch out of the fp32 epilogue is worth ~0.2 us per launch)
     if (a.states16 && a.states)

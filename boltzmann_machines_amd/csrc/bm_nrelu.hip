@@ -1,4 +1,4 @@
-// bm_nrelu.hip - noisy rectified-linear hidden units: the NR flavour of act_kernel with its launcher.  A
+// bm_nrelu.hip - noisy rectified-linear hidden units: the instantiations of act_kernel's NR flavour.  A
 // translation unit of its own, as bm_class.hip and bm_stack.hip are: the kernels of the other units are compiled exactly as
 // before.  Compiled into libbm355.so next to bm355.hip.
 #define BM_KERNELS_ONLY

@@ -2,7 +2,7 @@
 // bm_softmax_v.hip.  Host code only.
 //
 // A visible layer of G = V / K groups of K mutually exclusive units, one-hot per group.  Groups of 2, 4, 8 or 16 in a layer of
-// V % 4 == 0 are served by the SM flavour of act_kernel in one launch (ActArgs::sm_k; launch_act_sm, bm_launch.h).  For every
+// V % 4 == 0 are served by the SM flavour of act_kernel in one launch (ActArgs::sm_k; ActFlavour<FL_SM>, bm_launch.h).  For every
 // other shape the prop-down is a pair of launches, as the Multinomial hidden layer's prop-up is: a kind-3 pass of act_kernel leaves
 // the logits l = h W^T + vb, then softmax_groups_kernel turns every group of a row into its means and its one-hot state, in place.
 // Both produce the same bits.

@@ -1,4 +1,4 @@
-// bm_softmax_v.hip - softmax (categorical) visible units: the SM flavour of act_kernel with its launcher (groups
+// bm_softmax_v.hip - softmax (categorical) visible units: the instantiations of act_kernel's SM flavour (groups
 // of 2, 4, 8 or 16 units in a layer of V % 4 == 0), and softmax_groups_kernel, the generic path behind a logits pass for every
 // other shape.  A translation unit of its own, as bm_stack.hip and bm_nrelu.hip are: the kernels of the other units are compiled
 // exactly as before.  Compiled into libbm355.so next to bm355.hip.
@@ -9,33 +9,9 @@
 
 namespace bm {
 
-// An SM pass is a prop-down from W itself (x-major P): only those kernels are instantiated, as for the BP flavour (bm_stack.hip).
-// The tile map and the 16-byte / generic choice are dispatch_act's
-template <class G, int MINB, int STG>
-static inline void launch_act_sm_geo(const ActArgs &a, hipStream_t st) {
-    const double kt = (double)a.K1;
-    const TileMap tmap = make_tile_map((a.I + G::TI - 1) / G::TI, (a.J + G::TJ - 1) / G::TJ, kt * G::TI * 4.0, kt * G::TJ * 4.0, a.map_xi);
-    const bool fast = operand_fast(a.P1, XM, a.K1) && operand_fast(a.Q1, XM, a.K1);
-    launch_act_kernel<G, MINB, STG, FL_SM, false, XM>(fast, 0, st, a, tmap);
-}
-// geo: the codes of launch_act_as, resolved as that ladder resolves them for an x-major P (6, 9, 4 -> 8; 5, 7 -> 3): every code
-// lands on a geometry with MI == 1 (one quad per lane: the epilogue's group logic is written for it)
-void launch_act_sm_as(int geo, const ActArgs &a, hipStream_t st) {
-    if (geo == 208) { launch_act_sm_geo<GeoAct8, 1, STG_DMAH>(a, st); return; }
-    if (geo == 6 || geo == 9) geo = 8;
-    if (geo == 5 || geo == 7) geo = 3;
-    const bool reg = geo >= 100;
-    geo %= 100;
-    if (reg) {
-        if (geo == 1)      launch_act_sm_geo<GeoActS, 2, STG_REG>(a, st);
-        else if (geo == 3) launch_act_sm_geo<GeoActS32, 4, STG_REG>(a, st);
-        else               launch_act_sm_geo<GeoAct8, 1, STG_REG>(a, st);
-    } else {
-        if (geo == 1)      launch_act_sm_geo<GeoActS, 2, STG_DMA>(a, st);
-        else if (geo == 3) launch_act_sm_geo<GeoActS32, 4, STG_DMA>(a, st);
-        else               launch_act_sm_geo<GeoAct8, 1, STG_DMA>(a, st);
-    }
-}
+// An SM pass is a prop-down from W itself (x-major P): only those kernels are instantiated, as for the BP flavour (bm_launch.h:
+// ActFlavour<FL_SM>::xm_only) - one quad per lane, which the epilogue's group logic is written for
+void launch_act_sm_as(int geo, const ActArgs &a, hipStream_t st) { launch_act_xm_as<FL_SM>(geo, a, st); }
 
 // ---- softmax_groups_kernel: every width the SM flavour does not cover (3, 5, 10, 26, ...) and every layer with V % 4 != 0.
 // One wave per row (four rows per workgroup), a lane per group in turn; the K units of a group are walked three times in the
