@@ -105,7 +105,9 @@ __device__ __forceinline__ void t64_fetch(double2 (&r)[ROWS * COLS / 512], const
     constexpr int NV = ROWS * COLS / 512, CP = COLS / 2;
     // branch-free: clamped addresses, unconditional loads (all of a chunk's loads are in flight together),
     // out-of-range elements selected to zero afterwards
-    const bool vec = ((ld & 1) == 0) && (((uintptr_t)p & 15u) == 0) && ncols >= 2;      // wave-uniform (col is even)
+    // wave-uniform (col is even).  An odd ncols under an even ld would make the clamped pair of the last column the
+    // pair BEFORE it; every caller passes ld == ncols, so the extra term moves no reachable launch to the other branch
+    const bool vec = ((ld & 1) == 0) && ((ncols & 1) == 0) && (((uintptr_t)p & 15u) == 0) && ncols >= 2;
 #pragma unroll
     for (int n = 0; n < NV; ++n) {
         const int f = tid + n * 256;
