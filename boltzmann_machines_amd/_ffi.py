@@ -144,6 +144,9 @@ SIGNATURES = {
     'bm_rbm_sample_h': [_vp, _vp, _i32, _vp, _vp],
     'bm_rbm_sample_v_from_h': [_vp, _vp, _i32, _vp, _vp],
     'bm_rbm_set_visible_groups': [_vp, _i32],
+    'bm_rbm_groups_set_missing': [_vp, _i32],
+    'bm_rbm_groups_gibbs_clamped': [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    'bm_rbm_groups_scores': [_vp, _vp, _i32, _vp],
     'bm_rbm_metrics': [_vp, _vp, _i32, _i32, _fp],
     'bm_rbm_free_energy': [_vp, _vp, _i32, _fp],
     'bm_rbm_free_energy_rows': [_vp, _vp, _i32, _vp],

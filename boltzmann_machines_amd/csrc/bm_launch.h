@@ -32,6 +32,9 @@
 //               rectifies t = z + b and draws one normal per output
 //          SM   softmax visible units: logits prop-downs from W itself whose epilogue turns every group of sm_k in
 //               {2, 4, 8, 16} logits into its means and its one-hot state
+//        SM + CL is the one combination of two of them, and no entry of the table: act_route refuses a softmax-group pass with a clamp
+//        mask as it always did; the caller that means clamped groups (a mask constant within every group) says so by
+//        calling launch_act_sm_clamped, which runs the kernels of bm_softmax_cl.hip - the CL block behind the SM block
 //        CR to SM take mult == bmult == 1 (BP: mult) and one K segment.  The instantiations of CL and RT live in bm355.hip, those of
 //        the other five in translation units of their own (ActFlavour::as) so that the kernels of every other unit are compiled
 //        exactly as before; BP and SM have the x-major kernels only (launch_act_xm_as)
@@ -274,6 +277,18 @@ template <> struct ActFlavour<FL_SM> : ActFlavourDefaults {
                a.I % a.sm_k == 0;
     }
     static void strip(ActArgs &p) { p.sm_k = 0; p.kind = 0; }       // (the Bernoulli prop-down of the shape: the same contraction, a draw per output)
+};
+// SM + CL, clamped groups of softmax visible units: not an entry of the table - act_route never yields it - but
+// described like one, so that launch_act_sm_clamped runs it through launch_act_flavoured.  The kernel set is SM's, in a unit of its
+// own (bm_softmax_cl.hip); the pass is an SM pass that carries clamp values and a mask and no other selector; the strip is SM's and CL's
+void launch_act_smcl_as(int, const ActArgs &, hipStream_t);
+template <> struct ActFlavour<FL_SM | FL_CL> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = true, geo5 = false;
+    static constexpr ActAsFn as = launch_act_smcl_as;
+    static constexpr const char *no_kernel = "bm355: a clamped softmax-group pass is a softmax-group pass with clamp values and a mask and nothing else (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.sm_k != 0 && a.clamp_mask != nullptr; }
+    static bool admits(const ActArgs &a) { return ActFlavour<FL_SM>::admits(a) && a.clamp_val != nullptr; }
+    static void strip(ActArgs &p) { ActFlavour<FL_SM>::strip(p); ActFlavour<FL_CL>::strip(p); }
 };
 
 // the table's order: most specific first.  first(f): f(std::integral_constant<unsigned, FL>) for each flavour until one returns true
@@ -538,6 +553,12 @@ static inline void launch_act_flavoured(const ActArgs &a, hipStream_t st) {
         return;
     }
     as(T.geo, a);
+}
+// a clamped softmax-group pass (ActFlavour<FL_SM | FL_CL>): the caller's explicit choice, not a route of launch_act
+static inline void launch_act_sm_clamped(const ActArgs &a, hipStream_t st) {
+    using F = ActFlavour<FL_SM | FL_CL>;
+    if (!F::selects(a) || (act_features(a) & ~(FL_SM | FL_CL)) != 0 || !F::admits(a)) { fputs(F::no_kernel, stderr); abort(); }
+    launch_act_flavoured<FL_SM | FL_CL>(a, st);
 }
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
     const ActRoute r = act_route(a);

@@ -111,6 +111,14 @@ struct bm_rbm {
     // softmax visible units (bm_rbm_set_visible_groups): the visible layer is V / v_groups one-hot groups of
     // v_groups units each; 0: off (Bernoulli visible units)
     int v_groups = 0;
+    // incomplete rows (bm_rbm_groups_set_missing): run_chain() holds the empty groups of its input at zero.  gmask:
+    // the clamp mask of the running chain, dense [maxB][V], allocated when the mode is first used
+    bool groups_missing = false;
+    DevBuf gmask;
+    // bm_rbm_groups_scores: pre-activations [maxB][pad_ld(H)] and scores [maxB][V] of a slice, allocated at the first call;
+    // nothing else in the handle reads or writes them
+    Mat gs_z;
+    DevArray<double> gs_out;
     uint64_t seed = 0;
     uint32_t call = 0;
     int64_t row0 = 0;
@@ -352,7 +360,9 @@ static void issue(bm_rbm *h, LayerPass p) {
         const int K = h->v_groups;
         if (!fused_off && (K == 2 || K == 4 || K == 8 || K == 16) && (a.I & 3) == 0) {
             a.kind = 3; a.sm_k = K;
-            launch_act(a, h->stream);
+            // (clamped groups, DESIGN.md 3.25: the SM + CL kernels are asked for by name; launch_act refuses the combination)
+            if (a.clamp_mask) launch_act_sm_clamped(a, h->stream);
+            else              launch_act(a, h->stream);
             return;
         }
         // every other shape: logits from the GEMM, in place of the means, then a lane per group for the softmax and the
@@ -360,6 +370,9 @@ static void issue(bm_rbm *h, LayerPass p) {
         SgArgs g;
         memset(&g, 0, sizeof(g));
         g.states = a.states; g.ld_states = a.ldo;
+        // clamped groups: the clamp moves from the logits pass to the softmax kernel
+        g.clamp_val = a.clamp_val; g.clamp_mask = a.clamp_mask; g.ld_clamp = a.ld_clamp;
+        a.clamp_val = a.clamp_mask = nullptr; a.ld_clamp = 0;
         if (!a.means) { a.means = h->vm.p; a.ldo = h->vm.ld; }     // pure sampling sweep: vm is the scratch row store
         g.L = a.means; g.ld = a.ldo; g.V = a.I; g.K = h->v_groups; g.J = a.J; g.sample = a.sample; g.key = a.key; g.row0 = a.row0;
         a.kind = 3; a.sample = 0; a.states = nullptr;
@@ -430,6 +443,14 @@ static int run_chain(bm_rbm *h, const float *X_dev, int B, int k, const ChainOpt
     if (fe && !h->fe_part.p) BM_TRY(h->fe_part.alloc((size_t)2 * fe_rm * h->maxB));
     h->fe_in_chain = fe;
     if (o.fetch && !fe) metrics_prep(h, B);
+    // incomplete rows: the mask of the input's empty groups; every prop-down of the chain holds them at the
+    // input's own zeros (one pitch for values and mask: V, the input's).  The training and metric chains only: bm_rbm_transform
+    // (hm_out) runs the plain chain
+    const bool missing = h->groups_missing && h->v_groups && !o.hm_out;
+    if (missing) {
+        if (!h->gmask.p) BM_TRY(h->gmask.alloc((size_t)h->maxB * h->V));
+        launch_group_missing_mask(Xin, ldx, h->gmask.p, h->V, B, h->V, h->v_groups, h->stream);
+    }
     chain_begin(h);               // h0 and the k Gibbs steps: one launch where the shape allows it (bm_chain.h)
     LayerPass h0 = rbm_pass(h, true, B, LayerIn{Xin, ldx}, rbm_out(h, 1, h->h0m.p, h->h0s.p, h->h0m.ld, SITE_H0, 0));     // :421-422
     // the flip columns straight from their Philox stream and the zeroing of the six accumulators ride on this pass: the
@@ -439,8 +460,10 @@ static int run_chain(bm_rbm *h, const float *X_dev, int B, int k, const ChainOpt
     LayerIn hstate = in_of(h->cfg.sample_h_states ? h->h0s : h->h0m);             // :423
     for (int t = 0; t < k; ++t) {                                                 // :367-378
         const bool last = t == k - 1;
-        issue(h, rbm_pass(h, false, B, hstate, rbm_out(h, h->cfg.sample_v_states, (o.need_vm && last) ? h->vm.p : nullptr, h->vs.p,
-                                                       h->vs.ld, SITE_V, t)));
+        LayerPass down = rbm_pass(h, false, B, hstate, rbm_out(h, h->cfg.sample_v_states, (o.need_vm && last) ? h->vm.p : nullptr, h->vs.p,
+                                                               h->vs.ld, SITE_V, t));
+        if (missing) down.clamp(Xin, h->gmask.p, h->V);
+        issue(h, down);
         const bool last_out = o.hm_out && last;
         // plain update, last step: only -h_k is consumed (outer products and column sums)
         const bool neg_only = last && !o.hm_out && !o.need_vm && !h->multinomial();
@@ -1440,7 +1463,7 @@ int bm_rbm_sample_v_from_h(bm_rbm *h, const float *H_dev, int32_t B, float *Vmea
 // Softmax visible units (bm355.h).  A property of the handle that issue() reads at every prop-down
 int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K) {
     BM_CHECK(h, "null argument");
-    if (K == 0) { h->v_groups = 0; return 0; }
+    if (K == 0) { h->v_groups = 0; h->groups_missing = false; return 0; }
     BM_CHECK(K >= 2, "softmax visible units: the group width must be 0 (off) or >= 2 (got %d)", (int)K);
     BM_CHECK(h->V % K == 0, "softmax visible units: n_visible = %d is no multiple of the group width %d", h->V, (int)K);
     BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "softmax visible units replace Bernoulli visible units (this handle's are Gaussian)");
@@ -2325,6 +2348,75 @@ int bm_rbm_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev
     }
     h->call++;
     BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- softmax visible units: incomplete rows, clamped groups, exact group conditionals (bm355.h)
+static int need_groups(const bm_rbm *h, const char *what) {
+    BM_CHECK(h, "null argument");
+    BM_CHECK(h->v_groups, "%s needs a handle with visible groups (softmax visible units: bm_rbm_set_visible_groups); this handle has none", what);
+    return 0;
+}
+
+int bm_rbm_groups_set_missing(bm_rbm *h, int32_t on) {
+    BM_TRY(need_groups(h, "bm_rbm_groups_set_missing"));
+    h->groups_missing = on != 0;
+    return 0;
+}
+
+// bm_rbm_gibbs_clamped for a handle with visible groups: the mask is constant within every group (the caller's guarantee).  The
+// same launches, sites, call counter and row offset; the prop-down is the clamped softmax pass (SM + CL, or the generic pair)
+int bm_rbm_groups_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev, int32_t B, int32_t n_steps,
+                                const float *clamp_val_dev, const float *clamp_mask_dev) {
+    BM_TRY(need_groups(h, "bm_rbm_groups_gibbs_clamped"));
+    BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
+    BM_CHECK(V_dev && H_dev && clamp_val_dev && clamp_mask_dev, "null state or clamp pointer");
+    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
+    ensure_wt(h);
+    hipLaunchKernelGGL(clamp_apply_kernel, dim3(256), dim3(256), 0, h->stream, V_dev, h->V, clamp_val_dev, clamp_mask_dev, h->V, B, h->V);
+    for (int t = 0; t < n_steps; ++t) {
+        const bool first = t == 0, last = t == n_steps - 1;
+        const LayerIn vin = first ? LayerIn{V_dev, h->V} : in_of(h->vs);
+        float *hnew = last ? H_dev : h->hs.p, *vnew = last ? V_dev : h->vs.p;
+        const int ldh = last ? h->H : h->hs.ld, ldv = last ? h->V : h->vs.ld;
+        issue(h, rbm_pass(h, true, B, vin, rbm_out(h, 1, nullptr, hnew, ldh, SITE_H, t)));
+        issue(h, rbm_pass(h, false, B, LayerIn{hnew, ldh}, rbm_out(h, 1, last ? Vmean_dev : nullptr, vnew, ldv, SITE_V, t))
+                     .clamp(clamp_val_dev, clamp_mask_dev, h->V));
+    }
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// S [B][V] (host, double) of GsArgs: per slice of at most max_batch rows one kind-3 prop-up into a workspace of its own (z = x W +
+// hb in float32) and one group_scores_kernel launch.  No RNG call, no parameter and no shared workspace is touched
+int bm_rbm_groups_scores(bm_rbm *h, const float *X_dev, int32_t B, double *scores_host) {
+    BM_TRY(need_groups(h, "bm_rbm_groups_scores"));
+    BM_CHECK(X_dev && scores_host, "null argument");
+    BM_CHECK(B >= 1, "bad row count %d", (int)B);
+    if (!h->gs_out.p) {
+        BM_TRY(h->gs_z.alloc(h->maxB, h->H));
+        BM_TRY(h->gs_out.alloc((size_t)h->maxB * h->V));
+    }
+    ensure_wt(h);
+    for (int s = 0; s < B; s += h->maxB) {
+        const int n = (B - s < h->maxB) ? B - s : h->maxB;
+        const float *Xs = X_dev + (size_t)s * h->V;
+        LayerPass p = rbm_pass(h, true, n, LayerIn{Xs, h->V}, LayerOut{0, h->gs_z.p, nullptr, h->gs_z.ld, PhiloxKey{0, 0, 0, 0}, 0}, 1.0f);
+        p.a.kind = 3;                                  // stores z + hb
+        issue(h, p);
+        GsArgs g;
+        memset(&g, 0, sizeof(g));
+        g.X = Xs; g.ldx = h->V; g.Z = h->gs_z.p; g.ldz = h->gs_z.ld; g.W = h->W.p; g.ldw = h->W.ld; g.vb = h->vb.p;
+        g.S = h->gs_out.p; g.B = n; g.V = h->V; g.H = h->H; g.K = h->v_groups;
+        {
+            ProfScope _ps(h, KC_OTHER);
+            launch_group_scores(g, h->stream);
+        }
+        BM_HIP(hipGetLastError());
+        BM_HIP(hipMemcpyAsync(scores_host + (size_t)s * h->V, h->gs_out.p, (size_t)n * h->V * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        BM_HIP(hipStreamSynchronize(h->stream));
+    }
     return 0;
 }
 

@@ -231,6 +231,25 @@ class RbmEngine(_PtCalls):
         """softmax visible units (bm_rbm_set_visible_groups): n_visible / K one-hot groups of K units; 0: Bernoulli units again"""
         check(self.lib.bm_rbm_set_visible_groups(self._h, int(K)))
 
+    # softmax visible units: incomplete rows, clamped groups, exact group conditionals (bm355.h: bm_rbm_groups_*; DESIGN.md 3.25)
+    def groups_set_missing(self, on):
+        """while on, an all-zero group of a training row is a missing group, held at zero by every prop-down of the chain"""
+        check(self.lib.bm_rbm_groups_set_missing(self._h, int(bool(on))))
+
+    def groups_gibbs_clamped(self, Vd, Hd, B, n_steps, clamp_val_d, clamp_mask_d, Vmean_d=None, row=0):
+        """gibbs_clamped for a handle with visible groups; the mask must be constant within every group
+        (bm_rbm_groups_gibbs_clamped)"""
+        ov, oh = row * self.V, row * self.H
+        check(self.lib.bm_rbm_groups_gibbs_clamped(self._h, Vd.offset_ptr(ov), Hd.offset_ptr(oh),
+                                                   Vmean_d.offset_ptr(ov) if Vmean_d is not None else None, B, n_steps,
+                                                   clamp_val_d.offset_ptr(ov), clamp_mask_d.offset_ptr(ov)))
+
+    def groups_scores(self, Xd, B, row=0):
+        """[B, V] float64: S of rows [row, row + B) of Xd (bm_rbm_groups_scores); B is not bounded by max_batch"""
+        out = np.empty((B, self.V), dtype=np.float64)
+        check(self.lib.bm_rbm_groups_scores(self._h, Xd.offset_ptr(row * self.V), B, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def metrics(self, Xd, B, k, row=0):
         out = (C.c_float * 4)()
         check(self.lib.bm_rbm_metrics(self._h, Xd.offset_ptr(row * self.V), B, k, out))

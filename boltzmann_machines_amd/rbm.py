@@ -1076,7 +1076,12 @@ class SoftmaxVisible(object):
     checkpoints and `init_from` work as for the other classes.  What is not built for one-hot groups is refused with a
     ValueError before the engine is touched: the `pll` metric, `dropout`, `dbm_first` / `dbm_last`, dtype='float64',
     `set_negative_phase` other than 'cd', `set_centering`, `set_classes`, `sample_v_given`, `log_Z`, BM355_DATA_PARALLEL jobs,
-    and use as a layer of a `DBM` or a `StackClassifier`."""
+    and use as a layer of a `DBM` or a `StackClassifier`.
+
+    Incomplete rows: with `missing_values=True` a group of all zeros is a missing value - `fit` accepts rows
+    whose groups are one-hot or empty and trains each row's observed units only.  `group_log_proba`, `predict_proba`, `predict`
+    and `pseudo_log_likelihood` give the exact conditionals of the groups with the hidden layer summed out, and
+    `sample_groups_given` draws the empty groups of a row given its observed ones; these work whatever `missing_values` says."""
 
     _UNIT_NAME = 'softmax visible units'
 
@@ -1114,7 +1119,10 @@ class SoftmaxVisible(object):
             self._check_softmax_config('fit')
             if os.environ.get('BM355_DATA_PARALLEL', '0') == '1':
                 self._softmax_refuse('fit', 'data-parallel mode (BM355_DATA_PARALLEL) is not combined: the split step is not built')
-        return super(SoftmaxVisible, self)._ensure_engine()
+        out = super(SoftmaxVisible, self)._ensure_engine()
+        if hasattr(self._engine, 'groups_set_missing'):       # incomplete rows: a property of the handle, read by every training chain
+            self._engine.groups_set_missing(bool(self.missing_values))
+        return out
 
     def set_negative_phase(self, kind='cd', *args, **kwargs):
         if kind != 'cd':
@@ -1138,24 +1146,119 @@ class SoftmaxVisible(object):
         self._softmax_refuse('log_Z', 'AIS (its base model and its sweeps are Bernoulli) is not built')
 
     # ---- one-hot coding
-    def encode(self, C):
-        """integer categories [N, n_groups] with entries in [0, n_categories) -> one-hot float32 [N, n_groups * n_categories]"""
+    def encode(self, C, missing=None):
+        """integer categories [N, n_groups] with entries in [0, n_categories) -> one-hot float32 [N, n_groups * n_categories];
+        entries equal to `missing` (when one is given, e.g. -1) become empty - all-zero - groups"""
         C = np.asarray(C)
         if C.ndim != 2 or C.shape[1] != self.n_groups:
             raise ValueError('`C` has invalid shape {0}: expected [N, {1}]'.format(C.shape, self.n_groups))
-        Ci = C.astype(np.int64)
-        if C.size and (np.any(Ci != C) or Ci.min() < 0 or Ci.max() >= self.n_categories):
+        gone = np.zeros(C.shape, dtype=bool) if missing is None else (C == missing)
+        Ci = np.where(gone, 0, C).astype(np.int64)
+        if C.size and (np.any(Ci != np.where(gone, 0, C)) or Ci.min() < 0 or Ci.max() >= self.n_categories):
             raise ValueError('`C` has entries outside the categories 0 .. {0}'.format(self.n_categories - 1))
         X = np.zeros((len(C), self.n_groups, self.n_categories), dtype=np.float32)
         np.put_along_axis(X, Ci[:, :, None], 1.0, axis=2)
+        X[gone] = 0.0
         return X.reshape(len(C), self.n_visible)
 
-    def decode(self, X):
-        """[N, n_groups * n_categories] (states or means) -> the argmax per group, int64 [N, n_groups]"""
+    def decode(self, X, missing=None):
+        """[N, n_groups * n_categories] (states or means) -> the argmax per group, int64 [N, n_groups]; with `missing` given,
+        empty - all-zero - groups decode to it"""
         X = np.asarray(X)
         if X.ndim != 2 or X.shape[1] != self.n_visible:
             raise ValueError('`X` has invalid shape {0}: expected [N, {1}]'.format(X.shape, self.n_visible))
-        return X.reshape(len(X), self.n_groups, self.n_categories).argmax(axis=2)
+        X3 = X.reshape(len(X), self.n_groups, self.n_categories)
+        C = X3.argmax(axis=2)
+        if missing is not None:
+            C = np.where(np.any(X3 != 0, axis=2), C, missing)
+        return C
+
+    # ---- incomplete rows, clamped groups, exact group conditionals (DESIGN.md 3.25)
+    def _groups_of(self, X, what):
+        """X as float32 [N, n_visible], every group of every row one-hot or empty (else ValueError) -> (X, observed [N, n_groups])"""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.n_visible:
+            raise ValueError('`X` has invalid shape {0}: expected [N, {1}]'.format(X.shape, self.n_visible))
+        X3 = X.reshape(len(X), self.n_groups, self.n_categories)
+        ones, total = (X3 == 1).sum(axis=2), (X3 != 0).sum(axis=2)
+        if np.any((total > 1) | (ones != total)):
+            b, g = np.argwhere((total > 1) | (ones != total))[0]
+            raise ValueError('%s.%s: group %d of row %d is neither one-hot nor empty (all zeros: a missing value)'
+                             % (self.__class__.__name__, what, g, b))
+        return X, total == 1
+
+    def fit(self, X, X_val=None, *args, **kwargs):
+        if self.missing_values:
+            self._groups_of(X, 'fit')
+            if X_val is not None:
+                self._groups_of(X_val, 'fit')
+        return super(SoftmaxVisible, self).fit(X, X_val, *args, **kwargs)
+
+    @run_on_engine()
+    def group_log_proba(self, X):
+        """log p(v_g = k | v_-g) for every row, group and category, [N, n_groups, n_categories] float64, the hidden layer summed
+        out exactly.  X : [N, n_visible], every group one-hot or empty.  For an observed group the conditioning set is every
+        other observed group of the row (the term of the pseudo-likelihood over groups); for an empty group it is every
+        observed group, the other empty groups being absent from the row's model: the exact prediction of a missing value.
+        Draws nothing, changes nothing."""
+        eng = self._on_device()
+        X, _ = self._groups_of(X, 'group_log_proba')
+        if not len(X):
+            return np.zeros((0, self.n_groups, self.n_categories))
+        S = eng.groups_scores(self._to_device(X), len(X)).reshape(len(X), self.n_groups, self.n_categories)
+        S = S - S.max(axis=2, keepdims=True)
+        return S - np.log(np.exp(S).sum(axis=2, keepdims=True))
+
+    def predict_proba(self, X):
+        """exp(group_log_proba(X)): [N, n_groups, n_categories]"""
+        return np.exp(self.group_log_proba(X))
+
+    def predict(self, X):
+        """categories [N, n_groups] int64: an observed group keeps its category, an empty group takes the most probable one
+        given the row's observed groups"""
+        X, observed = self._groups_of(X, 'predict')
+        X3 = X.reshape(len(X), self.n_groups, self.n_categories)
+        return np.where(observed, X3.argmax(axis=2), self.group_log_proba(X).argmax(axis=2)).astype(np.int64)
+
+    def pseudo_log_likelihood(self, X):
+        """[N] float64: the sum over a row's observed groups of log p(v_g | v_-g), the pseudo-likelihood over groups"""
+        X, _ = self._groups_of(X, 'pseudo_log_likelihood')
+        X3 = X.reshape(len(X), self.n_groups, self.n_categories)
+        return (self.group_log_proba(X) * X3).sum(axis=(1, 2))
+
+    @run_on_engine(update_seed=True)
+    def sample_groups_given(self, X, n_gibbs_steps=1000, return_means=False):
+        """Conditional sampling over groups: the empty groups of every row of X are drawn jointly from p(v_free | v_observed)
+        by block-Gibbs with the observed groups clamped (imputation of missing values).
+
+        X : [N, n_visible], every group one-hot (observed) or empty (to be drawn).  The free groups start at uniform
+        categories drawn under the call's seed.  Returns one-hot rows [N, n_visible] after `n_gibbs_steps` sweeps (with
+        `return_means`: a pair, states and the means of the last visible pass); observed groups hold X in both.  Both layers
+        are always sampled.  The rows are processed in slices of at most `batch_size`, every row drawing from its own position
+        of the call's random stream: the result does not depend on the slicing.  One seed is drawn from the model's host
+        stream; no parameter is changed."""
+        eng = self._on_device()
+        X, observed = self._groups_of(X, 'sample_groups_given')
+        k = int(n_gibbs_steps)
+        if k < 1:
+            raise ValueError('`n_gibbs_steps` must be >= 1 (got {0})'.format(k))
+        N = len(X)
+        start_cats = np.random.RandomState(self._graph_seed).randint(0, self.n_categories, (N, self.n_groups))
+        obs_units = np.repeat(observed, self.n_categories, axis=1)
+        V0 = np.where(obs_units, X, self.encode(start_cats))
+        Vd, Cd = self._to_device(V0), self._to_device(X)
+        Md = self._to_device(obs_units.astype(np.float32))
+        Hd = _ffi.DeviceArray((N, self.n_hidden), np.float32)
+        Pd = _ffi.DeviceArray((N, self.n_visible), np.float32) if return_means else None
+        try:
+            for start in range(0, N, self.batch_size):
+                eng.seed(self._graph_seed)
+                eng.set_row_offset(start)
+                eng.groups_gibbs_clamped(Vd, Hd, min(self.batch_size, N - start), k, Cd, Md, Pd, row=start)
+            eng.sync()
+        finally:
+            eng.set_row_offset(0)
+        return (Vd.numpy(), Pd.numpy()) if return_means else Vd.numpy()
 
     @run_on_engine(update_seed=True)
     def sample_v(self, n_samples, n_gibbs_steps=1000, V_init=None):
@@ -1201,8 +1304,10 @@ class CategoricalRBM(SoftmaxVisible, BaseRBM):
     units each, n_visible = n_groups * n_categories (no counterpart in the reference).  The model for ratings, quantised pixels,
     characters, categorical table columns.  See `SoftmaxVisible` for the unit and for what is refused."""
 
-    def __init__(self, n_groups=1, n_categories=2, n_hidden=256, model_path='c_rbm_model/', *args, **kwargs):
+    def __init__(self, n_groups=1, n_categories=2, n_hidden=256, model_path='c_rbm_model/', *args, missing_values=False, **kwargs):
         self.n_groups, self.n_categories = n_groups, n_categories
+        # incomplete rows (DESIGN.md 3.25): an all-zero group of a training row is a missing value, absent from the row's model
+        self.missing_values = missing_values
         n_visible = kwargs.pop('n_visible', None)          # (params.json carries it: load_model hands it back)
         if n_visible is not None and int(n_visible) != int(n_groups) * int(n_categories):
             raise ValueError('CategoricalRBM: n_visible = %r is not n_groups x n_categories = %r x %r' % (n_visible, n_groups, n_categories))

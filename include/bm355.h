@@ -186,6 +186,36 @@ int bm_rbm_sample_v_from_h(bm_rbm *h, const float *H_dev, int32_t B, float *Vmea
  * _delta_update / the stack entries.  bm_rbm_set_fast_binary is accepted and runs fp32. */
 int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K);
 
+/* Softmax visible units with incomplete rows, clamped groups and exact group conditionals.  All three entries
+ * need a handle with visible groups (bm_rbm_set_visible_groups); on any other handle they are refused with a message that names
+ * visible groups, and the handle stays usable.  V = G K, W [V][H].
+ *
+ * bm_rbm_groups_set_missing(h, on): while on, a group of an input row that is all zeros is a MISSING group: the model of that row
+ * has the observed units only (shared weights).  Everything that runs the training chain - bm_rbm_train_step, _metrics,
+ * _metrics_async, _epoch, bm_rbm_metrics - builds the mask of the input's empty groups first and holds those groups at zero in
+ * every prop-down (visible means and states exactly 0 there); the prop-up, the update with N = B, the sparsity terms and the free
+ * energy are unchanged (a zero row of v contributes nothing).  With complete rows every result equals the mode-off result bit for
+ * bit.  bm_rbm_gibbs, bm_rbm_sample_v_from_h and bm_rbm_transform do not look at the mode.  Off by default;
+ * bm_rbm_set_visible_groups(h, 0) turns it off.
+ *
+ * bm_rbm_groups_gibbs_clamped: bm_rbm_gibbs_clamped (same arguments, launches, sites, call counter, row offset; both layers always
+ * sampled; Vmean_dev may be NULL) for a handle with visible groups.  clamp_mask_dev must be constant within every group - the
+ * caller's guarantee, not checked: a clamped group holds clamp_val (a one-hot group, or zeros for a group that is absent), a free
+ * group gets exactly the means, the uniform and the state of the unclamped pass from the same input; a clamped group's uniform is
+ * consumed by position and not used.  An all-zero mask reproduces the unclamped sweep bit for bit.  B <= max_batch.
+ *
+ * bm_rbm_groups_scores: scores_host [B][V] (double).  For a row x whose groups are each one-hot or empty, group g with current
+ * unit c (none if empty) and category k:  S[g K + k] = vb[gK+k] + sum_j softplus(a_j + W[gK+k][j]),  a_j = z_j - W[c][j] (a_j = z_j
+ * for an empty group), z = x W + hb; then log p(v_g = k | v_-g) = S[gK+k] - logsumexp_k' S[gK+k'] - for an empty group the
+ * posterior given the observed groups alone (the other empty groups absent).  z, a_j and the argument of the softplus are rounded
+ * float32 operations, the softplus terms float32 on the hardware transcendentals (as the default AIS path), their sum and the
+ * bias accumulated in double in a fixed order that depends on the shape alone.  The softmax over k is left to the caller.  B is
+ * not bounded by max_batch (sliced internally); no RNG call is consumed, no parameter changes. */
+int bm_rbm_groups_set_missing(bm_rbm *h, int32_t on);
+int bm_rbm_groups_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev, int32_t B, int32_t n_steps,
+                                const float *clamp_val_dev, const float *clamp_mask_dev);
+int bm_rbm_groups_scores(bm_rbm *h, const float *X_dev, int32_t B, double *scores_host);
+
 /* Metric fetches of base_rbm.py:554-564,578,605,612: out[0]=msre (:486-488),
  * out[1]=pll (:496-513), out[2]=l2_loss (:482-484), out[3]=free_energy
  * (:516-517; rbm.py:17-22 / :109-116).  Runs the same chain as train_step
