@@ -158,6 +158,15 @@ struct ActArgs {
     // sequence of softmax_groups_kernel (bm_softmax_v.hip), which serves every other width.  A pass that does not sample stores
     // state = mean.  sm_k == 0: off.
     int sm_k;
+    // AIS over softmax visible units (the SA flavour on top of SM, act_kernel<..., SM = true, SA = true>; FL_SM | FL_SA):
+    // a softmax-group pass at a temperature - logits l = mult * z + bmult * b with free mult / bmult, formed as kind 3 forms them -
+    // that always samples, stores its states and leaves the slot partials of state . dot_vec in rowdot_out (the quad order and slot
+    // rule of the plain epilogue, from the lane's registers: no read-back of the states).  sm_absent [I] (or null: every group is
+    // there): a unit whose entry is non-zero belongs to a group that is ABSENT from the model of this run - the same pattern for
+    // every row, constant within a group (the caller's guarantee): mean and state are zero, its uniform is consumed by position, not
+    // used.  Asked for by name (launch_act_sm_ais), never a route of launch_act.  sm_ais == 0: off.
+    int sm_ais;
+    const float *sm_absent;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -408,7 +417,7 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
 template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false,
-          bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false>
+          bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false, bool SA = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -506,6 +515,33 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (ib + r < a.I) ba[hlf][r] = p[r];
+                }
+            }
+        }
+    }
+    // SA: the lane's quad of the absent pattern and of dot_vec, requested at epilogue entry like the clamp arrays (I % 4 == 0: the
+    // quad is whole; one 16-byte load per vector where its base allows it); sa_q keeps the quad's state . dot_vec for the slot partials
+    float sab[4], sdv[4], sa_q = 0.f;
+    (void)sab; (void)sdv; (void)sa_q;
+    if constexpr (SA) {
+        static_assert(SM && G::MI == 1, "the SA flavour sits on top of the SM flavour");
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { sab[r] = 0.f; sdv[r] = 0.f; }
+        if (j < a.J && ib0 + 3 < a.I) {
+            if (((uintptr_t)a.dot_vec & 15u) == 0) {
+                const float4 t = *reinterpret_cast<const float4 *>(a.dot_vec + ib0);
+                sdv[0] = t.x; sdv[1] = t.y; sdv[2] = t.z; sdv[3] = t.w;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sdv[r] = a.dot_vec[ib0 + r];
+            }
+            if (a.sm_absent) {                 // wave-uniform
+                if (((uintptr_t)a.sm_absent & 15u) == 0) {
+                    const float4 t = *reinterpret_cast<const float4 *>(a.sm_absent + ib0);
+                    sab[0] = t.x; sab[1] = t.y; sab[2] = t.z; sab[3] = t.w;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sab[r] = a.sm_absent[ib0 + r];
                 }
             }
         }
@@ -638,6 +674,15 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                 for (int r = 0; r < 4; ++r)
                     if (cm[hlf][r] != 0.f) { m[r] = cv[hlf][r]; s[r] = cv[hlf][r]; }
             }
+            if constexpr (SA) {                // absent groups hold zero; the quad's state . dot_vec, left to right as the read-back sums it
+                float qd = 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (sab[r] != 0.f) { m[r] = 0.f; s[r] = 0.f; }
+                    qd += s[r] * sdv[r];
+                }
+                sa_q = qd;
+            }
             if constexpr (RT) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sv[4 * hlf + r] = s[r];
@@ -688,6 +733,14 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
     bool row_sums = a.rowacc || a.rowdot_out;
     if constexpr (RT) row_sums = row_sums || a.rowen_out;
     if constexpr (BP) row_sums = false;
+    if constexpr (SA) {                       // the slot partials of state . dot_vec from the lanes' registers: (q0+q1)+(q2+q3), lanes g = 0..3
+        row_sums = false;
+        float rdot = sa_q;
+        rdot += __shfl_xor(rdot, 16);
+        rdot += __shfl_xor(rdot, 32);
+        const int slot = (i0 + wi * 16) / 16;
+        if (g == 0 && j < a.J && slot * 16 < a.I) a.rowdot_out[(size_t)slot * a.ld_part + j] = rdot;
+    }
     if (row_sums) {                           // wave-uniform
         // per-lane quads (4 consecutive i, left to right); MI == 2: the lane's two quads are added
         float racc = 0.f, rdot = 0.f, racc2 = 0.f, ren = 0.f;
@@ -779,7 +832,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 // MINB: HIP's second __launch_bounds__ argument = WAVES PER SIMD the register budget must allow (for the 4-wave
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
-          bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false>
+          bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false, bool SA = false>
 BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -855,7 +908,7 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP, NR, SM>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP, NR, SM, SA>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];

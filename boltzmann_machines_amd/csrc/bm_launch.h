@@ -35,6 +35,8 @@
 //        SM + CL is the one combination of two of them, and no entry of the table: act_route refuses a softmax-group pass with a clamp
 //        mask as it always did; the caller that means clamped groups (a mask constant within every group) says so by
 //        calling launch_act_sm_clamped, which runs the kernels of bm_softmax_cl.hip - the CL block behind the SM block
+//        SM + SA is the other flavour asked for by name (launch_act_sm_ais; bm_softmax_ais.hip): the softmax-group pass of the AIS over
+//        softmax visible units - free mult / bmult, absent groups held at zero, state . dot_vec from registers
 //        CR to SM take mult == bmult == 1 (BP: mult) and one K segment.  The instantiations of CL and RT live in bm355.hip, those of
 //        the other five in translation units of their own (ActFlavour::as) so that the kernels of every other unit are compiled
 //        exactly as before; BP and SM have the x-major kernels only (launch_act_xm_as)
@@ -158,15 +160,15 @@ template <class Args, class F> static inline int tune_tile_map(TuneTimer &tm, Ar
 static inline bool tune_log() { static const bool on = dbg("tune_log") != nullptr; return on; }
 
 // ---- act_kernel: one dispatcher for every flavour
-enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512, FL_NR = 1024, FL_SM = 2048 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
+enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512, FL_NR = 1024, FL_SM = 2048, FL_SA = 4096 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
 template <class G, int MINB, int STG, unsigned FL, bool SEG2, int PL>
 static inline void launch_act_kernel(bool fast, unsigned dyn_lds, hipStream_t st, const ActArgs &a, const TileMap &tmap) {
     const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
     constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0, CL = (FL & FL_CL) != 0,
                    RT = (FL & FL_RT) != 0, CR = (FL & FL_CR) != 0, CB = (FL & FL_CB) != 0, BP = (FL & FL_BP) != 0, NR = (FL & FL_NR) != 0,
-                   SM = (FL & FL_SM) != 0;
-    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM>), grid, blk, dyn_lds, st, a, tmap);
-    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM>), grid, blk, dyn_lds, st, a, tmap);
+                   SM = (FL & FL_SM) != 0, SA = (FL & FL_SA) != 0;
+    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA>), grid, blk, dyn_lds, st, a, tmap);
+    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA>), grid, blk, dyn_lds, st, a, tmap);
 }
 template <class G, int MINB, int STG, unsigned FL>
 static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, unsigned dyn_lds = 0) {
@@ -289,6 +291,24 @@ template <> struct ActFlavour<FL_SM | FL_CL> : ActFlavourDefaults {
     static bool selects(const ActArgs &a) { return a.sm_k != 0 && a.clamp_mask != nullptr; }
     static bool admits(const ActArgs &a) { return ActFlavour<FL_SM>::admits(a) && a.clamp_val != nullptr; }
     static void strip(ActArgs &p) { ActFlavour<FL_SM>::strip(p); ActFlavour<FL_CL>::strip(p); }
+};
+// SM + SA, the tempered softmax-group pass of the AIS over softmax visible units: like SM + CL no entry of the table -
+// act_route sends a softmax-group pass with a temperature or row dots to SM, which refuses it, as it always did - but described like
+// one, so that launch_act_sm_ais runs it through launch_act_flavoured.  The kernel set is SM's, in a unit of its own
+// (bm_softmax_ais.hip); the pass is an SM pass with free mult / bmult that samples, stores its states and leaves state . dot_vec; ONE
+// flavour serves runs with and without a pattern of absent groups (a null sm_absent is a wave-uniform branch around one 16-byte load)
+void launch_act_smais_as(int, const ActArgs &, hipStream_t);
+template <> struct ActFlavour<FL_SM | FL_SA> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = true, geo5 = false;
+    static constexpr ActAsFn as = launch_act_smais_as;
+    static constexpr const char *no_kernel = "bm355: a tempered softmax-group pass (AIS) is a sampled softmax-group pass that leaves state . dot_vec and nothing else (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.sm_k != 0 && a.sm_ais != 0; }
+    static bool admits(const ActArgs &a) {
+        const bool width_ok = a.sm_k == 2 || a.sm_k == 4 || a.sm_k == 8 || a.sm_k == 16;
+        return a.kind == 3 && !a.rowacc && !a.negmeans && a.p_xm && width_ok && (a.I & 3) == 0 && a.I % a.sm_k == 0 && a.sample && a.states &&
+               a.rowdot_out && a.dot_vec && a.ld_part >= a.J;
+    }
+    static void strip(ActArgs &p) { ActFlavour<FL_SM>::strip(p); p.sm_ais = 0; p.sm_absent = nullptr; p.mult = p.bmult = 1.0f; }
 };
 
 // the table's order: most specific first.  first(f): f(std::integral_constant<unsigned, FL>) for each flavour until one returns true
@@ -560,7 +580,14 @@ static inline void launch_act_sm_clamped(const ActArgs &a, hipStream_t st) {
     if (!F::selects(a) || (act_features(a) & ~(FL_SM | FL_CL)) != 0 || !F::admits(a)) { fputs(F::no_kernel, stderr); abort(); }
     launch_act_flavoured<FL_SM | FL_CL>(a, st);
 }
+// a tempered softmax-group pass (ActFlavour<FL_SM | FL_SA>): the caller's explicit choice, not a route of launch_act
+static inline void launch_act_sm_ais(const ActArgs &a, hipStream_t st) {
+    using F = ActFlavour<FL_SM | FL_SA>;
+    if (!F::selects(a) || (act_features(a) & ~FL_SM) != 0 || !F::admits(a)) { fputs(F::no_kernel, stderr); abort(); }
+    launch_act_flavoured<FL_SM | FL_SA>(a, st);
+}
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
+    if (a.sm_ais) { fputs("bm355: a tempered softmax-group pass (AIS) is asked for by name, launch_act_sm_ais (no such route)\n", stderr); abort(); }
     const ActRoute r = act_route(a);
     if (r.refusal) { fputs(r.refusal, stderr); abort(); }
     if (ActFlavours::first([&](auto fl) { return r.fl == fl.value && (launch_act_flavoured<decltype(fl)::value>(a, st), true); })) return;

@@ -16,6 +16,7 @@
 #include "bm_class.h"
 #include "bm_stack.h"
 #include "bm_softmax_v.h"
+#include "bm_softmax_ais.h"
 
 #include <math.h>
 #include <atomic>
@@ -135,6 +136,11 @@ struct bm_rbm {
     DevBuf apart_h, apart_v;           // slot partials (ActArgs::rowacc / rowdot_out): [ceil(H/16)][ais_rows], [ceil(V/16)][ais_rows]
     DevArray<double> alogw;            // [ais_rows] log-weights, accumulated in double in a fixed order
     DevBuf abase, adot, abeta, atable; // a [V], vb - a [V], beta [n_betas], the mixed biases a + beta_k (vb - a) [n_betas][V]
+    // bm_rbm_groups_ais, allocated at the first call: the run's pattern of absent groups and a row of zeros [V]
+    // each, and - the generic route only - the logits / means [ga_rows][V] of its prop-down; nothing else reads or writes them
+    DevBuf ga_absent, ga_zero;
+    int ga_rows = 0;
+    Mat ga_l;
     // bm_rbm_pt_*: the tempered ensemble (bm_pt.h; layers v and h1), allocated on demand - max_batch does not bound it; nothing
     // else in the handle reads or writes it
     PtEnsemble pt;
@@ -2417,6 +2423,130 @@ int bm_rbm_groups_scores(bm_rbm *h, const float *X_dev, int32_t B, double *score
         BM_HIP(hipMemcpyAsync(scores_host + (size_t)s * h->V, h->gs_out.p, (size_t)n * h->V * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         BM_HIP(hipStreamSynchronize(h->stream));
     }
+    return 0;
+}
+
+// ---- AIS over softmax visible units (bm355.h: bm_rbm_groups_ais)
+
+// the two routes of issue()'s softmax prop-down; BM355_DEBUG=sm_fused=0 forces the generic one
+static bool groups_fused(const bm_rbm *h) {
+    static const bool fused_off = bm::dbg("sm_fused") && atoi(bm::dbg("sm_fused")) == 0;
+    const int K = h->v_groups;
+    return !fused_off && (K == 2 || K == 4 || K == 8 || K == 16) && (h->V & 3) == 0;
+}
+// the workspaces of bm_rbm_ais for `rows` chains and, on the generic route, the logits of the prop-down; a failed allocation leaves
+// nothing counted (ensure_ais_rows)
+static int ensure_groups_ais_rows(bm_rbm *h, int rows) {
+    BM_TRY(ensure_ais_rows(h, rows));
+    if (!h->ga_zero.p) {
+        BM_TRY(h->ga_absent.alloc(h->V)); BM_TRY(h->ga_zero.alloc(h->V));
+        BM_HIP(hipMemset(h->ga_zero.p, 0, (size_t)h->V * sizeof(float)));
+    }
+    if (groups_fused(h) || rows <= h->ga_rows) return 0;
+    h->ga_rows = 0;
+    BM_TRY(h->ga_l.alloc(rows, h->V));
+    h->ga_rows = rows;
+    return 0;
+}
+// v_g ~ softmax_k(beta (h W^T)_{gK+k} + a + beta (vb - a)) for the groups that are there, zeros elsewhere, from ah into av, the mixed
+// bias from row `kbeta` of the table; dot: the slot partials of v.(vb - a) in apart_v for the next score.  Fused route: ONE launch,
+// the SM + SA flavour (which leaves the partials whether they are read or not); generic route: the logits pass, softmax_groups_kernel
+// with the pattern as its clamp mask (pitch 0: every row reads the same [V] vectors) and - dot - the row-dot kernel
+static void groups_ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &key, int64_t chain0, bool dot, const float *absent) {
+    LayerPass p = rbm_pass(h, false, R, in_of(h->ah), LayerOut{1, nullptr, h->av.p, h->av.ld, key, chain0}, beta)
+                      .bias(h->atable.p + (size_t)kbeta * h->V, 1.0f);
+    ActArgs &a = p.a;
+    if (groups_fused(h)) {
+        ProfScope _ps(h, KC_DOWN);
+        p.statedot_rows(h->apart_v.p, h->ais_rows, h->adot.p);
+        a.kind = 3; a.sm_k = h->v_groups; a.sm_ais = 1; a.sm_absent = absent;
+        launch_act_sm_ais(a, h->stream);
+        return;
+    }
+    SgArgs g;
+    memset(&g, 0, sizeof(g));
+    g.L = h->ga_l.p; g.ld = h->ga_l.ld; g.states = h->av.p; g.ld_states = h->av.ld;
+    g.V = h->V; g.K = h->v_groups; g.J = R; g.sample = 1; g.key = key; g.row0 = chain0;
+    if (absent) { g.clamp_val = h->ga_zero.p; g.clamp_mask = absent; g.ld_clamp = 0; }
+    a.kind = 3; a.sample = 0; a.states = nullptr; a.means = h->ga_l.p; a.ldo = h->ga_l.ld;
+    {
+        ProfScope _ps(h, KC_DOWN);
+        launch_act(a, h->stream);
+    }
+    ProfScope _ps(h, KC_OTHER);                        // (per-class event timing: the route's extra launches are the class `other`)
+    launch_softmax_groups(g, h->stream);
+    if (dot) launch_softmax_ais_dot(h->av.p, h->av.ld, R, h->V, h->adot.p, h->apart_v.p, h->ais_rows, h->stream);
+}
+
+// bm_rbm_ais with a categorical base model and softmax transitions over the observed groups; the host loop, the prop-up with its
+// softplus partials, the score kernel and the double accumulation are bm_rbm_ais's own
+int bm_rbm_groups_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t k, const float *base_bias_host, const uint8_t *observed_host,
+                      uint64_t seed, int64_t chain0, float *values_host) {
+    BM_TRY(need_groups(h, "bm_rbm_groups_ais"));
+    BM_CHECK(values_host, "null argument");
+    BM_CHECK(n_betas >= 2 && n_runs >= 1 && k >= 1, "bad AIS arguments (n_betas %d >= 2, n_runs %d >= 1, n_gibbs_steps %d >= 1)",
+             (int)n_betas, (int)n_runs, (int)k);
+    const int R = n_runs, V = h->V, H = h->H, K = h->v_groups, G = V / K;
+    int n_obs = G;
+    if (observed_host) { n_obs = 0; for (int g = 0; g < G; ++g) n_obs += observed_host[g] != 0; }
+    BM_CHECK(n_obs >= 1, "bm_rbm_groups_ais: the pattern observes none of the %d groups (a model without visible units has no chain)", G);
+    BM_TRY(ensure_groups_ais_rows(h, R));
+    if (!h->abase.p) { BM_TRY(h->adot.alloc(V)); BM_TRY(h->abase.alloc(V)); }
+    if (h->atable.n < (size_t)n_betas * V) { BM_TRY(h->abeta.alloc(n_betas)); BM_TRY(h->atable.alloc((size_t)n_betas * V)); }
+    // beta_k as float(np.linspace(0, 1, n_betas)[k]); log Z_0 = H log 2 + sum over the observed groups of logsumexp_k a, in double
+    std::vector<float> beta(n_betas);
+    const double step = 1.0 / (double)(n_betas - 1);
+    for (int b = 0; b < n_betas; ++b) beta[b] = (float)((double)b * step);
+    beta[n_betas - 1] = 1.0f;
+    double logZ0 = (double)H * log(2.0);
+    std::vector<float> absent_host(observed_host ? V : 0);
+    for (int g = 0; g < G; ++g) {
+        const bool there = !observed_host || observed_host[g] != 0;
+        if (observed_host) for (int q = 0; q < K; ++q) absent_host[(size_t)g * K + q] = there ? 0.f : 1.f;
+        if (!there) continue;
+        double mx = -INFINITY, se = 0.0;
+        for (int q = 0; q < K; ++q) mx = fmax(mx, base_bias_host ? (double)base_bias_host[(size_t)g * K + q] : 0.0);
+        for (int q = 0; q < K; ++q) se += exp((base_bias_host ? (double)base_bias_host[(size_t)g * K + q] : 0.0) - mx);
+        logZ0 += mx + log(se);
+    }
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_HIP(hipMemcpy(h->abeta.p, beta.data(), (size_t)n_betas * sizeof(float), hipMemcpyHostToDevice));
+    if (base_bias_host) BM_HIP(hipMemcpy(h->abase.p, base_bias_host, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
+    else BM_HIP(hipMemset(h->abase.p, 0, (size_t)V * sizeof(float)));
+    if (observed_host) BM_HIP(hipMemcpy(h->ga_absent.p, absent_host.data(), (size_t)V * sizeof(float), hipMemcpyHostToDevice));
+    const float *absent = observed_host ? h->ga_absent.p : nullptr;
+    ensure_wt(h);
+    hipLaunchKernelGGL(rbm_ais_prep_kernel, dim3(512), dim3(256), 0, h->stream, (const float *)h->vb.p, (const float *)h->abase.p,
+                       (const float *)h->abeta.p, (int)n_betas, V, h->adot.p, h->atable.p);
+    BM_HIP(hipMemsetAsync(h->alogw.p, 0, (size_t)R * sizeof(double), h->stream));
+    const int ldp = h->ais_rows;
+    SaStartArgs s0;
+    memset(&s0, 0, sizeof(s0));
+    s0.v = h->av.p; s0.ld = h->av.ld; s0.rows = R; s0.V = V; s0.K = K;
+    s0.abase = h->abase.p; s0.dvec = h->adot.p; s0.absent = absent;
+    s0.key = ais_key(seed, SITE_AIS_V0, 0, 0); s0.row0 = (unsigned long long)chain0;
+    s0.part = h->apart_v.p; s0.ld_part = ldp; s0.nslot = nslots(V);
+    launch_softmax_ais_start(s0, h->stream);
+    AisScoreArgs sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.ne = 1; sc.pe[0] = h->apart_h.p; sc.ne_slots[0] = nslots(H);
+    sc.no = 1; sc.po[0] = h->apart_v.p; sc.no_slots[0] = nslots(V);
+    for (int b = 1; b < n_betas; ++b) {
+        const bool last = b == n_betas - 1;            // no transition behind the last score
+        const float ba = beta[b - 1], bb = beta[b];
+        ais_up(h, R, bb, last ? 0 : 1, ais_key(seed, SITE_AIS_H, 0, (uint32_t)b), chain0, true, ba);
+        hipLaunchKernelGGL(ais_score_kernel, dim3((R + 31) / 32), dim3(256), 0, h->stream, h->alogw.p, R, ldp, sc, bb - ba);
+        if (last) break;
+        for (int t = 0; t < k; ++t) {
+            if (t > 0) ais_up(h, R, bb, 1, ais_key(seed, SITE_AIS_H, t, (uint32_t)b), chain0, false, 0.f);
+            groups_ais_down(h, R, bb, b, ais_key(seed, SITE_AIS_V, t, (uint32_t)b), chain0, t == k - 1, absent);
+        }
+    }
+    BM_HIP(hipGetLastError());
+    std::vector<double> w(R);
+    BM_HIP(hipMemcpyAsync(w.data(), h->alogw.p, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    for (int r = 0; r < R; ++r) values_host[r] = (float)(w[r] + logZ0);
     return 0;
 }
 

@@ -230,6 +230,7 @@ class RbmEngine(_PtCalls):
     def set_visible_groups(self, K):
         """softmax visible units (bm_rbm_set_visible_groups): n_visible / K one-hot groups of K units; 0: Bernoulli units again"""
         check(self.lib.bm_rbm_set_visible_groups(self._h, int(K)))
+        self.v_groups = int(K)
 
     # softmax visible units: incomplete rows, clamped groups, exact group conditionals (bm355.h: bm_rbm_groups_*; DESIGN.md 3.25)
     def groups_set_missing(self, on):
@@ -248,6 +249,25 @@ class RbmEngine(_PtCalls):
         """[B, V] float64: S of rows [row, row + B) of Xd (bm_rbm_groups_scores); B is not bounded by max_batch"""
         out = np.empty((B, self.V), dtype=np.float64)
         check(self.lib.bm_rbm_groups_scores(self._h, Xd.offset_ptr(row * self.V), B, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def groups_ais(self, n_betas, n_runs, k, seed, chain0=0, base_bias=None, observed=None):
+        """[n_runs] float32 per-chain AIS estimates of log Z of a handle with visible groups (bm_rbm_groups_ais; DESIGN.md 3.26);
+        base_bias [V]: the base logits `a`, None: the uniform base; observed [n_groups] bool: the groups the model has, None: all"""
+        out = np.empty(n_runs, dtype=np.float32)
+        a = o = None
+        if base_bias is not None:
+            a = np.ascontiguousarray(base_bias, dtype=np.float32)
+            if a.shape != (self.V,):
+                raise ValueError('base_bias has shape %r, expected (%d,)' % (a.shape, self.V))
+        if observed is not None:
+            o = np.ascontiguousarray(np.asarray(observed) != 0, dtype=np.uint8)
+            K = getattr(self, 'v_groups', 0)
+            if K and o.shape != (self.V // K,):
+                raise ValueError('observed has shape %r, expected (%d,)' % (o.shape, self.V // K))
+        check(self.lib.bm_rbm_groups_ais(self._h, n_betas, n_runs, k, a.ctypes.data_as(C.c_void_p) if a is not None else None,
+                                         o.ctypes.data_as(C.c_void_p) if o is not None else None, int(seed), int(chain0),
+                                         out.ctypes.data_as(C.c_void_p)))
         return out
 
     def metrics(self, Xd, B, k, row=0):

@@ -1081,7 +1081,11 @@ class SoftmaxVisible(object):
     Incomplete rows: with `missing_values=True` a group of all zeros is a missing value - `fit` accepts rows
     whose groups are one-hot or empty and trains each row's observed units only.  `group_log_proba`, `predict_proba`, `predict`
     and `pseudo_log_likelihood` give the exact conditionals of the groups with the hidden layer summed out, and
-    `sample_groups_given` draws the empty groups of a row given its observed ones; these work whatever `missing_values` says."""
+    `sample_groups_given` draws the empty groups of a row given its observed ones; these work whatever `missing_values` says.
+
+    Density evaluation: `ais_log_Z` estimates the log partition function of the model, or of the sub-model over
+    one pattern of observed groups, by AIS from a categorical base model; `ais_log_Z_rows(X)` does so for every pattern of
+    incomplete rows, so that `log_proba(X, ais_log_Z_rows(X))` is their log-likelihood."""
 
     _UNIT_NAME = 'softmax visible units'
 
@@ -1143,7 +1147,90 @@ class SoftmaxVisible(object):
         self._softmax_refuse('sample_v_given', 'the clamped sweep (clamped groups) is not built')
 
     def log_Z(self, *args, **kwargs):
-        self._softmax_refuse('log_Z', 'AIS (its base model and its sweeps are Bernoulli) is not built')
+        self._softmax_refuse('log_Z', 'AIS (its base model and its sweeps are Bernoulli) is not built; `ais_log_Z` is the estimator')
+
+    # ---- AIS log Z and held-out log-likelihood
+    def _base_group_logits(self, X_base):
+        """the base logits `a` of the AIS base model p_0(v) = prod_g softmax(a_g)[v_g]: None (uniform), `a` itself [V], or data
+        [N][V] of one-hot-or-empty groups -> a_{gK+k} = log((count_{g,k} + 1) / (N_g + K)), N_g the rows that observe g (Laplace
+        smoothing; float64, handed over as float32)"""
+        if X_base is None:
+            return None
+        X = np.asarray(X_base, dtype=np.float64)
+        if X.ndim == 2 and X.shape[1] == self.n_visible:
+            X, observed = self._groups_of(X, 'ais_log_Z')
+            G, K = int(self.n_groups), int(self.n_categories)
+            count = X.astype(np.float64).sum(axis=0).reshape(G, K)
+            n_g = observed.sum(axis=0).astype(np.float64)
+            return np.log((count + 1.) / (n_g[:, None] + K)).reshape(self.n_visible).astype(np.float32)
+        if X.shape != (self.n_visible,):
+            raise ValueError('`X_base` has invalid shape {0}: expected [N, {1}] or [{1}]'.format(X.shape, self.n_visible))
+        return X.astype(np.float32)
+
+    def _observed_pattern(self, observed, what):
+        if observed is None:
+            return None
+        o = np.asarray(observed)
+        if o.shape != (int(self.n_groups),) or o.dtype != np.bool_:
+            raise ValueError('%s.%s: `observed` must be a boolean array of shape [%d] (got %s %r)'
+                             % (self.__class__.__name__, what, self.n_groups, o.dtype, o.shape))
+        if not o.any():
+            raise ValueError('%s.%s: `observed` names no group (a model without visible units)' % (self.__class__.__name__, what))
+        return o
+
+    def ais_log_Z(self, n_betas=100, n_runs=100, n_gibbs_steps=5, X_base=None, observed=None):
+        """AIS estimate of the log partition function of this model - or, with `observed`, of the sub-model that has the named
+        groups only (the model of a row whose other groups are missing).  Returns log_mean, (log_low, log_high),
+        values - as `BernoulliRBM.log_Z`.
+
+        `n_runs` chains run from the base model p_0(v) = prod_g softmax(a_g)[v_g] through `n_betas` temperatures
+        linspace(0, 1, n_betas) with `n_gibbs_steps` transitions each, the hidden layer summed out:
+        log p*_beta(v) = (1 - beta) a.v + beta vb.v + sum_j softplus(beta (vW + hb)_j).
+        X_base : None - the uniform base (a = 0); an [N, n_visible] array of one-hot-or-empty groups - the smoothed base rates of
+        that data, a_{gK+k} = log((count_{g,k} + 1) / (N_g + K)) with N_g the rows that observe group g; an [n_visible] array -
+        the logits `a` themselves.
+        observed : None - every group; a boolean [n_groups] array - the groups the model has.
+        Both layers are always sampled.  One seed is drawn from the model's host stream; no parameter is changed."""
+        n_betas, n_runs, n_gibbs_steps = int(n_betas), int(n_runs), int(n_gibbs_steps)
+        if n_betas < 2 or n_runs < 1 or n_gibbs_steps < 1:
+            raise ValueError('%s.ais_log_Z: n_betas must be >= 2, n_runs and n_gibbs_steps >= 1 (got %d, %d, %d)'
+                             % (self.__class__.__name__, n_betas, n_runs, n_gibbs_steps))
+        a = self._base_group_logits(X_base)
+        o = self._observed_pattern(observed, 'ais_log_Z')
+        return self._ais_log_Z_checked(n_betas, n_runs, n_gibbs_steps, a, o)
+
+    @run_on_engine(update_seed=True)
+    def _ais_log_Z_checked(self, n_betas, n_runs, n_gibbs_steps, a, o):
+        values = self._on_device().groups_ais(n_betas, n_runs, n_gibbs_steps, seed=self._graph_seed, base_bias=a, observed=o)
+        log_mean = log_mean_exp(values)
+        log_std = log_std_exp(values, log_mean_exp_x=log_mean)
+        log_high = log_sum_exp([log_std, log_mean])
+        log_low = log_diff_exp([log_std, log_mean])[0]
+        return log_mean, (log_low, log_high), values
+
+    def observed_patterns(self, X):
+        """(patterns [P, n_groups] bool, index [N] int64): the distinct patterns of observed groups among the rows of X (every
+        group one-hot or empty) and, for every row, the position of its pattern - X's row n observes patterns[index[n]]"""
+        _, observed = self._groups_of(X, 'observed_patterns')
+        if not len(observed):
+            return np.zeros((0, int(self.n_groups)), dtype=bool), np.zeros(0, dtype=np.int64)
+        patterns, index = np.unique(observed, axis=0, return_inverse=True)
+        return patterns.astype(bool), np.asarray(index, dtype=np.int64).reshape(len(observed))
+
+    def ais_log_Z_rows(self, X, **ais_kwargs):
+        """[N] float64: for every row of X (every group one-hot or empty) the AIS log Z of the sub-model over the row's observed
+        groups, so that `log_proba(X, ais_log_Z_rows(X))` is the log-likelihood of incomplete rows.  One `ais_log_Z` run per
+        DISTINCT pattern of X, its log_mean scattered to the rows of that pattern: the cost is P runs for P patterns (see
+        `observed_patterns`), each drawing one seed from the model's host stream.  A row with no observed group is refused
+        (ValueError): it belongs to no model.  `ais_kwargs`: n_betas, n_runs, n_gibbs_steps, X_base."""
+        if 'observed' in ais_kwargs:
+            raise ValueError('%s.ais_log_Z_rows: the patterns come from `X`; `observed` is not an argument' % self.__class__.__name__)
+        patterns, index = self.observed_patterns(X)
+        empty = ~patterns.any(axis=1)
+        if empty.any():
+            raise ValueError('%s.ais_log_Z_rows: row %d observes no group' % (self.__class__.__name__, int(np.argmax(empty[index]))))
+        per_pattern = np.array([self.ais_log_Z(observed=p, **ais_kwargs)[0] for p in patterns], dtype=np.float64)
+        return per_pattern[index] if len(index) else np.zeros(0)
 
     # ---- one-hot coding
     def encode(self, C, missing=None):

@@ -215,6 +215,31 @@ int bm_rbm_groups_set_missing(bm_rbm *h, int32_t on);
 int bm_rbm_groups_gibbs_clamped(bm_rbm *h, float *V_dev, float *H_dev, float *Vmean_dev, int32_t B, int32_t n_steps,
                                 const float *clamp_val_dev, const float *clamp_mask_dev);
 int bm_rbm_groups_scores(bm_rbm *h, const float *X_dev, int32_t B, double *scores_host);
+/* AIS estimate of the log partition function of an RBM with softmax visible units, or of one of its sub-models:
+ * bm_rbm_ais with a categorical base model and softmax transitions.  V = G K; O = the observed groups, observed_host [G] (0 =
+ * absent; NULL: all of them).  A group outside O is absent from the model - the missing_values semantics of 3.25 - and every
+ * chain state is zero there.  a = base_bias_host [V] are the base logits (NULL: a = 0, the uniform base), z = v W + hb:
+ *   p_0(v) = prod_{g in O} softmax(a_g)[v_g],   log Z_0 = n_hidden log 2 + sum_{g in O} logsumexp_k a_{gK+k}   (host, double)
+ *   log p*_beta(v) = (1 - beta) a.v + beta vb.v + sum_j softplus(beta z_j),   beta_k = float32(linspace(0, 1, n_betas))[k]
+ * v_0: every group in O gets one categorical draw from the logits a_g by the softmax-group rule (mx, e, sequential c, S, the first
+ * k with c[k] > u S); for k = 1 .. n_betas - 1: logw += log p*_{beta_k}(v_{k-1}) - log p*_{beta_{k-1}}(v_{k-1}), then n_gibbs_steps
+ * transitions h ~ Ber(sigmoid(beta_k z)), v_g ~ softmax_k(beta_k (h W^T)_{gK+k} + a + beta_k (vb - a)) for g in O and zeros
+ * elsewhere - both layers always sampled; none behind the last score.  values_host [n_runs] receives logw + log Z_0 per chain.
+ * RNG sites as bm_rbm_ais (Philox key = seed, counter word site + 16 t, call = beta step, row offset = chain0 + row): 7 for v_0
+ * (call 0), 8 for v, 9 for h; a group's uniform is the visible layer's per-element stream read at the group's first unit, flat
+ * index (chain0 + row) V + g K; an absent group's uniform is consumed by position, not used.  Chains [c, c + n) of a larger run
+ * are the run of n chains at chain0 = c, bit for bit.
+ * The per-beta terms are fp32 (softplus on the hardware transcendentals); the sums over the 16-column slots and over the betas
+ * are DOUBLE in a fixed order: the values depend neither on the tile geometry nor on which softmax route ran (the fused SM + SA
+ * flavour for groups of 2, 4, 8 or 16 in a layer of V % 4 == 0, the logits / softmax / row-dot triple for every other shape;
+ * BM355_DEBUG=sm_fused=0 forces the latter).  A pattern that observes every group gives the bits of the run without a pattern.
+ * Needs a handle with visible groups; refused otherwise, like the entries above.  Refused too: bad arguments (as bm_rbm_ais), a
+ * pattern with no observed group.  The call draws from its own streams: it does not advance the handle's call counter, changes no
+ * parameter, momentum buffer or workspace that another entry reads (the AIS workspaces are shared with bm_rbm_ais only), and does
+ * not look at bm_rbm_groups_set_missing - the pattern is explicit.  Workspaces for n_runs rows are allocated on demand: max_batch
+ * does not bound the number of chains. */
+int bm_rbm_groups_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t n_gibbs_steps, const float *base_bias_host,
+                      const uint8_t *observed_host, uint64_t seed, int64_t chain0, float *values_host);
 
 /* Metric fetches of base_rbm.py:554-564,578,605,612: out[0]=msre (:486-488),
  * out[1]=pll (:496-513), out[2]=l2_loss (:482-484), out[3]=free_energy
