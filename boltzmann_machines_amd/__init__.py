@@ -5,6 +5,7 @@ package never falls back to a CPU implementation."""
 from .rbm import BernoulliRBM, MultinomialRBM, GaussianRBM, BaseRBM, logit_mean          # noqa: F401
 from .rbm import ReLURBM, GaussianReLURBM                                 # noqa: F401
 from .rbm import CategoricalRBM                                           # noqa: F401
+from .rbm import ReplicatedSoftmaxRBM                                     # noqa: F401
 from .base import EngineModel, BaseModel                                  # noqa: F401
 from .utils import RNG                                                    # noqa: F401
 from .finetune import StackClassifier                                     # noqa: F401

@@ -144,6 +144,8 @@ SIGNATURES = {
     'bm_rbm_sample_h': [_vp, _vp, _i32, _vp, _vp],
     'bm_rbm_sample_v_from_h': [_vp, _vp, _i32, _vp, _vp],
     'bm_rbm_set_visible_groups': [_vp, _i32],
+    'bm_rbm_set_replicated_softmax': [_vp, _i32],
+    'bm_rbm_set_row_lengths': [_vp, _vp, _i32],
     'bm_rbm_groups_set_missing': [_vp, _i32],
     'bm_rbm_groups_gibbs_clamped': [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     'bm_rbm_groups_scores': [_vp, _vp, _i32, _vp],

@@ -167,6 +167,12 @@ struct ActArgs {
     // used.  Asked for by name (launch_act_sm_ais), never a route of launch_act.  sm_ais == 0: off.
     int sm_ais;
     const float *sm_absent;
+    // Replicated softmax (the DB flavour, act_kernel<..., DB = true>; FL_DB): the hidden prop-up of a word-count
+    // visible layer.  A single-segment Bernoulli pass with mult == bmult == 1 whose row j scales the BIAS ALONE by its document
+    // length: t = __fadd_rn(z, __fmul_rn(row_bmult[j], bias[i])) - two rounded steps, no contraction - where the plain pass takes
+    // z + bias[i]; everything behind it is the plain epilogue (sigmoid, draw, negmeans, the softplus slot partials of `rowacc`,
+    // which sum softplus(t) of the same t).  row_bmult [J].  Null: off.
+    const float *row_bmult;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
@@ -417,7 +423,7 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
 template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false,
-          bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false, bool SA = false>
+          bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false, bool SA = false, bool DB = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -466,6 +472,10 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 #pragma unroll
         for (int e = 0; e < E; ++e) sv[e] = 0.f;
     }
+    // DB: the row's document length, requested at epilogue entry like the row's temperature of RT
+    float dbm = 1.f;
+    (void)dbm;
+    if constexpr (DB) dbm = (j < a.J) ? a.row_bmult[j] : 0.f;
     // CB: the row's class and the lane's quads of U[y_j], requested at epilogue entry like the clamp arrays (one 16-byte load per
     // group of 4 where pitch and base allow it); a label outside [0, cb_C) loads nothing and raises the flag (every lane that
     // sees it stores the same 1)
@@ -574,7 +584,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                 const float x = (RT ? rm : a.mult) * z[4 * hlf + r];
                 float bv = bs[4 * hlf + r];
                 if constexpr (CB) { if (cb_ok) bv = __fadd_rn(bv, cu[hlf][r]); }       // b' = b + U[y_j][i], one rounded add
-                const float b = (RT ? rm : a.bmult) * bv;
+                const float b = DB ? __fmul_rn(dbm, bv) : (RT ? rm : a.bmult) * bv;      // (DB: the length scales the bias alone; mult == 1)
                 if constexpr (NR) {            // t = z + b as kind 3 forms it; the mean is the rectified t
                     nt[r] = x + b;
                     m[r] = (nt[r] > 0.0f) ? nt[r] : 0.0f;
@@ -763,7 +773,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                         if (a.dot_mat) {
                             qa += z[e] * a.dot_mat[(size_t)j * a.ld_dot + i];
                         } else {
-                            const float t = z[e] + bs[e];
+                            const float t = z[e] + (DB ? __fmul_rn(dbm, bs[e]) : bs[e]);
                             if constexpr (FE) qa2 += softplus(t + delta * a.fe_w[(size_t)fc * a.fe_ldw + i]);    // the PLL partner's row (beta_b == 1)
                             if (a.rowacc_single) qa += HWMATH ? softplus_hw(a.beta_b * t) : softplus(a.beta_b * t);
                             else qa += softplus_hw(a.beta_b * t) - softplus_hw(a.beta_a * t);
@@ -832,7 +842,8 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 // MINB: HIP's second __launch_bounds__ argument = WAVES PER SIMD the register budget must allow (for the 4-wave
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
-          bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false, bool SA = false>
+          bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false, bool SA = false,
+          bool DB = false>
 BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -908,7 +919,7 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP, NR, SM, SA>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP, NR, SM, SA, DB>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];

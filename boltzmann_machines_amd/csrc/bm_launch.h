@@ -12,7 +12,7 @@
 //   MF   mean-field passes (ActArgs::prev / maxdiff / skip / chk_ctl / acc_init; ActSide<.., MF>).  Two tiles, by rule: 32 x 64
 //        (8 waves, one workgroup per CU) where that gives every CU a tile, else 32 x 32 (4 waves) - what the tuner picked for
 //        these passes at 784-512-1024 x 512 (profiles/r5_dbm_kernel_stats.csv); BM355_DEBUG=mf_geo=8|1 forces one
-//   CL, RT, CR, CB, BP, NR, SM   the flavours of the table below (ActFlavour): each is selected by one field of ActArgs, admits a
+//   CL, RT, CR, CB, BP, NR, SM, DB   the flavours of the table below (ActFlavour): each is selected by one field of ActArgs, admits a
 //        narrow kind of pass and is combined with NO other selector of a pass - another flavour's, the bf16 range, FE, the
 //        mean-field plumbing, `lit`, a second K segment - except those its entry tolerates (act_route; anything else: "no such
 //        kernel", abort).  None is a tile of its own: a pass runs on the geometry and the block -> tile map that the tuner chose
@@ -32,6 +32,8 @@
 //               rectifies t = z + b and draws one normal per output
 //          SM   softmax visible units: logits prop-downs from W itself whose epilogue turns every group of sm_k in
 //               {2, 4, 8, 16} logits into its means and its one-hot state
+//          DB   replicated softmax: Bernoulli prop-ups whose row j multiplies the bias ALONE by row_bmult[j], the
+//               document length; the softplus slot partials of `rowacc` (single) ride on it; bm_rsm.hip
 //        SM + CL is the one combination of two of them, and no entry of the table: act_route refuses a softmax-group pass with a clamp
 //        mask as it always did; the caller that means clamped groups (a mask constant within every group) says so by
 //        calling launch_act_sm_clamped, which runs the kernels of bm_softmax_cl.hip - the CL block behind the SM block
@@ -160,15 +162,15 @@ template <class Args, class F> static inline int tune_tile_map(TuneTimer &tm, Ar
 static inline bool tune_log() { static const bool on = dbg("tune_log") != nullptr; return on; }
 
 // ---- act_kernel: one dispatcher for every flavour
-enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512, FL_NR = 1024, FL_SM = 2048, FL_SA = 4096 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
+enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512, FL_NR = 1024, FL_SM = 2048, FL_SA = 4096, FL_DB = 8192 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
 template <class G, int MINB, int STG, unsigned FL, bool SEG2, int PL>
 static inline void launch_act_kernel(bool fast, unsigned dyn_lds, hipStream_t st, const ActArgs &a, const TileMap &tmap) {
     const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
     constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0, CL = (FL & FL_CL) != 0,
                    RT = (FL & FL_RT) != 0, CR = (FL & FL_CR) != 0, CB = (FL & FL_CB) != 0, BP = (FL & FL_BP) != 0, NR = (FL & FL_NR) != 0,
-                   SM = (FL & FL_SM) != 0, SA = (FL & FL_SA) != 0;
-    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA>), grid, blk, dyn_lds, st, a, tmap);
-    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA>), grid, blk, dyn_lds, st, a, tmap);
+                   SM = (FL & FL_SM) != 0, SA = (FL & FL_SA) != 0, DB = (FL & FL_DB) != 0;
+    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA, DB>), grid, blk, dyn_lds, st, a, tmap);
+    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA, DB>), grid, blk, dyn_lds, st, a, tmap);
 }
 template <class G, int MINB, int STG, unsigned FL>
 static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, unsigned dyn_lds = 0) {
@@ -192,11 +194,11 @@ using ActAsFn = void (*)(int geo, const ActArgs &a, hipStream_t st);
 // The geometry `geo` (launch_act_as codes) of the five flavours whose instantiations live in translation units of their own, as
 // those of bm_grad_cen.hip do: bm_class.hip (CR; the plain kernels are to stay exactly what they were), bm_class_joint.hip (CB;
 // beside the CB instantiations the compiler allocates the registers of a dozen CR instantiations differently, 1 - 4 VGPRs, and
-// those are to stay exactly what they were as well), bm_stack.hip (BP), bm_nrelu.hip (NR), bm_softmax_v.hip (SM).  Each is
+// those are to stay exactly what they were as well), bm_stack.hip (BP), bm_nrelu.hip (NR), bm_softmax_v.hip (SM), bm_rsm.hip (DB).  Each is
 // launch_act_as<FL> and nothing else
 void launch_act_cr_as(int, const ActArgs &, hipStream_t), launch_act_cb_as(int, const ActArgs &, hipStream_t),
      launch_act_bp_as(int, const ActArgs &, hipStream_t), launch_act_nr_as(int, const ActArgs &, hipStream_t),
-     launch_act_sm_as(int, const ActArgs &, hipStream_t);
+     launch_act_sm_as(int, const ActArgs &, hipStream_t), launch_act_db_as(int, const ActArgs &, hipStream_t);
 // An entry states
 //   seg2, xm_only, geo5   its kernel set: two-segment kernels exist / only the x-major-P kernels exist (a prop-down from W itself) /
 //                         geometry 5 exists (else the pass takes 7, the same tile at two workgroups per CU: the epilogues of CR and
@@ -280,6 +282,16 @@ template <> struct ActFlavour<FL_SM> : ActFlavourDefaults {
     }
     static void strip(ActArgs &p) { p.sm_k = 0; p.kind = 0; }       // (the Bernoulli prop-down of the shape: the same contraction, a draw per output)
 };
+template <> struct ActFlavour<FL_DB> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = false, geo5 = false;
+    static constexpr ActAsFn as = launch_act_db_as;
+    static constexpr const char *no_kernel = "bm355: a length-scaled-bias pass is a single-segment Bernoulli prop-up of its own flavour (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.row_bmult != nullptr; }
+    static bool admits(const ActArgs &a) {
+        return a.kind == 0 && a.mult == 1.0f && a.bmult == 1.0f && !a.rowdot_out && (!a.rowacc || (a.rowacc_single && !a.dot_mat));
+    }
+    static void strip(ActArgs &p) { p.row_bmult = nullptr; }
+};
 // SM + CL, clamped groups of softmax visible units: not an entry of the table - act_route never yields it - but
 // described like one, so that launch_act_sm_clamped runs it through launch_act_flavoured.  The kernel set is SM's, in a unit of its
 // own (bm_softmax_cl.hip); the pass is an SM pass that carries clamp values and a mask and no other selector; the strip is SM's and CL's
@@ -316,7 +328,7 @@ template <unsigned... FL> struct ActFlavoursOf {
     static unsigned selected(const ActArgs &a) { return ((ActFlavour<FL>::selects(a) ? FL : 0u) | ...); }
     template <class F> static bool first(F &&f) { return (f(std::integral_constant<unsigned, FL>{}) || ...); }
 };
-using ActFlavours = ActFlavoursOf<FL_SM, FL_NR, FL_BP, FL_CB, FL_CR, FL_RT, FL_CL>;
+using ActFlavours = ActFlavoursOf<FL_DB, FL_SM, FL_NR, FL_BP, FL_CB, FL_CR, FL_RT, FL_CL>;
 // every selector the pass carries: the FL_ bits of the table's flavours, FL_FE, FL_MF, FL_LIT, FL_SEG2 (K2 > 0) and FT_BF16
 static inline unsigned act_features(const ActArgs &a) {
     return ActFlavours::selected(a) | (a.b3.K1 > 0 ? FT_BF16 : 0u) | (a.fe_flip ? FL_FE : 0u) |

@@ -16,6 +16,7 @@
 #include "bm_class.h"
 #include "bm_stack.h"
 #include "bm_softmax_v.h"
+#include "bm_rsm.h"
 #include "bm_softmax_ais.h"
 
 #include <math.h>
@@ -120,6 +121,14 @@ struct bm_rbm {
     // nothing else in the handle reads or writes them
     Mat gs_z;
     DevArray<double> gs_out;
+    // replicated softmax visible units (bm_rbm_set_replicated_softmax; bm_rsm.h): the visible layer is one softmax
+    // over the V units drawn D_j times for row j; rsm_len = max_length, 0: off.  rsm_cur: the lengths [J] of the rows the passes
+    // described now run on (issue() reads it) - rsm_D (computed from a batch by row_lengths_kernel), rsm_user (the caller's,
+    // bm_rbm_set_row_lengths; rsm_user_n of them) or fer_len (bm_rbm_free_energy_rows).  rsm_bad: row_lengths_kernel's flag
+    int rsm_len = 0, rsm_user_n = 0;
+    const float *rsm_cur = nullptr;
+    DevBuf rsm_D, rsm_user, fer_len;
+    DevArray<int> rsm_bad;
     uint64_t seed = 0;
     uint32_t call = 0;
     int64_t row0 = 0;
@@ -212,6 +221,9 @@ static int check_dw(const bm_rbm *h, const char *what) {
 
 // what a handle with softmax visible units does not do (DESIGN.md 3.24 says why, entry by entry)
 static int refuse_softmax_v(const bm_rbm *h, const char *what) {
+    // ... and, at the same entries, one with replicated softmax visible units
+    BM_CHECK(!h || !h->rsm_len, "%s is not available for replicated softmax visible units (bm_rbm_set_replicated_softmax: max_length %d): "
+             "not built for word-count rows; see DESIGN.md 3.27", what, h->rsm_len);
     BM_CHECK(!h || !h->v_groups, "%s is not available for softmax visible units (bm_rbm_set_visible_groups: %d groups of %d): not "
              "built for one-hot groups; see DESIGN.md 3.24", what, h->V / h->v_groups, h->v_groups);
     return 0;
@@ -253,7 +265,8 @@ static void chain_begin(bm_rbm *h) {
     // keep their per-pass launches
     // (noisy rectified-linear hidden units: their prop-up is a flavour of its own, never chained)
     // (softmax visible units: a softmax launch between the passes, as for Multinomial hidden units)
-    h->chain.on = !h->prof && !h->multinomial() && !h->nrelu() && !h->v_groups && !h->fast_now && chain_mode(h->chain) > 0;
+    // (replicated softmax visible units: the DB flavour and the count kernel, never chained)
+    h->chain.on = !h->prof && !h->multinomial() && !h->nrelu() && !h->v_groups && !h->rsm_len && !h->fast_now && chain_mode(h->chain) > 0;
 }
 static int chain_end(bm_rbm *h) {
     BM_CHECK(chain_flush(h->chain, h->stream, h->maxB) == 0, "chained launch: %s", hipGetErrorString(hipGetLastError()));
@@ -386,6 +399,22 @@ static void issue(bm_rbm *h, LayerPass p) {
         launch_softmax_groups(g, h->stream);
         return;
     }
+    if (!up && h->rsm_len) {
+        // replicated softmax visible units: logits from the GEMM, in place of the means, then a workgroup per
+        // row for the softmax over the whole layer and the row's D_j draws (bm_rsm.h)
+        McArgs m;
+        memset(&m, 0, sizeof(m));
+        m.states = a.states; m.ld_states = a.ldo;
+        if (!a.means) { a.means = h->vm.p; a.ldo = h->vm.ld; }     // pure sampling sweep: vm is the scratch row store
+        m.L = a.means; m.ld = a.ldo; m.lengths = h->rsm_cur; m.V = a.I; m.J = a.J; m.sample = a.sample; m.max_length = h->rsm_len;
+        m.key = a.key; m.row0 = a.row0;
+        a.kind = 3; a.sample = 0; a.states = nullptr;
+        launch_act(a, h->stream);
+        if (launch_multinomial_counts(m, h->stream)) abort();      // (bm_rbm_set_replicated_softmax checked the width)
+        return;
+    }
+    // ... and their prop-up: the DB flavour scales the bias alone by the row's length
+    if (up && h->rsm_len) a.row_bmult = h->rsm_cur;
     // noisy rectified-linear hidden units: the NR flavour rectifies t = z + b (formed as kind 3 forms it) and draws a normal
     if (up && h->nrelu()) { a.kind = 3; a.nrelu = 1; }
     // the prop-up's weights x-major: W^T where the handle keeps a valid one (ensure_wt), never beside the bf16 planes
@@ -433,6 +462,13 @@ struct ChainOpts {
 };
 static bool metrics_fused_ok(const bm_rbm *h);
 static void metrics_prep(bm_rbm *h, int B);
+// replicated softmax: the lengths D [B] of the count rows X (pitch ldx) into `D`, which the passes issued from
+// now on read; a row that is no count vector of 1 .. max_length tokens raises the handle's flag (check_row_lengths)
+static void rsm_lengths_of(bm_rbm *h, const float *X, int ldx, int B, float *D) {
+    RowLenArgs r{X, ldx, h->V, B, D, h->rsm_len, h->rsm_bad.p};
+    launch_row_lengths(r, h->stream);
+    h->rsm_cur = D;
+}
 static int run_chain(bm_rbm *h, const float *X_dev, int B, int k, const ChainOpts &o) {
     BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
     BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", k);
@@ -442,6 +478,8 @@ static int run_chain(bm_rbm *h, const float *X_dev, int B, int k, const ChainOpt
     bool dropped;
     prep_input(h, X_dev, B, &Xin, &ldx, &dropped);
     h->Xin = Xin; h->Xin_ld = ldx;
+    // replicated softmax: the batch's lengths, once; every pass of the chain keeps them (each prop-down draws exactly D_b tokens)
+    if (h->rsm_len) rsm_lengths_of(h, Xin, ldx, B, h->rsm_D.p);
     // a metrics iteration: the flip columns and the zeroed accumulators first, then the h0 pass adds the free-energy row
     // sums of x and of its PLL partner from its own pre-activations (ActArgs::fe_flip) - no GEMM of their own
     const bool fe = o.fetch && metrics_fused_ok(h);
@@ -522,6 +560,18 @@ static void launch_update_fast(bm_rbm *h, int B, float lr, float mom);
 // whole parameter update of the fused single-GPU step (base_rbm.py:443-478)
 static void launch_update_fused(bm_rbm *h, int B, float lr, float mom) {
     if (h->cen_on) { launch_update_centred(h, B, lr, mom); return; }
+    if (h->rsm_len) {
+        // replicated softmax: the bias block with the hidden sums weighted by the batch's lengths in front, then
+        // the unchanged grad_kernel without its bias tail - the launch order of a handle with a sparsity penalty (pen is zero)
+        {
+            ProfScope _ps(h, KC_COLSUM);
+            RbmBiasFusedArgs a;
+            fill_bias_fused(h, B, lr, mom, a);
+            launch_rsm_bias(a, h->rsm_D.p, h->stream);
+        }
+        rbm_grad(h, B, 1, (float)B, lr, mom, false);
+        return;
+    }
     if (h->cfg.sparsity_cost != 0.f) {      // W update needs the penalty: bias kernel first
         launch_bias_fused(h, B, lr, mom);
         rbm_grad(h, B, 1, (float)B, lr, mom, false);
@@ -675,7 +725,8 @@ static void metrics_to_out4(const bm_rbm *h, const double *host, int B, float *o
 // units are Bernoulli and the epilogue in use is act_kernel's (not the fast-binary strip kernel)
 static bool metrics_fused_ok(const bm_rbm *h) {
     static const bool off = bm::dbg("metrics_fused") && atoi(bm::dbg("metrics_fused")) == 0;
-    return !off && !h->multinomial() && !h->nrelu() && !h->cfg.dbm_first && !h->fast_now && (h->W.ld & 3) == 0;
+    // (replicated softmax: the h0 pass is a DB pass, which carries no metric fetch)
+    return !off && !h->multinomial() && !h->nrelu() && !h->rsm_len && !h->cfg.dbm_first && !h->fast_now && (h->W.ld & 3) == 0;
 }
 static void metrics_prep(bm_rbm *h, int B) {
     MetricsPrepArgs mp;
@@ -699,7 +750,8 @@ static int metrics_from_chain(bm_rbm *h, int B, float *out4) {
         hipLaunchKernelGGL(metrics_tail_kernel, dim3(nb_sq + nb_fe), dim3(256), 0, h->stream, msre, l2, r, nb_sq);
     } else {
         hipLaunchKernelGGL(sqdiff2_kernel, dim3(256), dim3(256), 0, h->stream, msre, l2);
-        if (!h->nrelu()) launch_fe(h, h->Xin, h->Xin_ld, B, true);      // (NReLU: no free energy in closed form, pll / feg are NaN)
+        // (NReLU: no free energy in closed form, pll / feg are NaN; replicated softmax: fe_hidden_kernel has no length-scaled bias)
+        if (!h->nrelu() && !h->rsm_len) launch_fe(h, h->Xin, h->Xin_ld, B, true);
     }
     if (!out4) return 0;                                    // asynchronous caller: the sums stay in h->scal
     double host[6];
@@ -721,6 +773,7 @@ static void metrics_to_out4(const bm_rbm *h, const double *host, int B, float *o
     out4[3] = (float)fe;                                        // free energy   :516
     if (h->nrelu()) out4[1] = out4[3] = nanf("");               // noisy rectified-linear hidden units: neither exists in closed form
     if (h->v_groups) out4[1] = nanf("");                        // softmax visible units: a row with one bit flipped is no state of the model
+    if (h->rsm_len) out4[1] = out4[3] = nanf("");               // replicated softmax: the same; the free energy is bm_rbm_free_energy_rows'
 }
 
 // ---- AIS log Z of the RBM itself and per-row free energies (bm355.h: bm_rbm_ais, bm_rbm_free_energy_rows)
@@ -986,6 +1039,7 @@ static int check_class_labels(bm_rbm *h) {
     return 0;
 }
 
+static int check_row_lengths(bm_rbm *h);      // (replicated softmax: row_lengths_kernel's flag, below)
 int bm_rbm_sync(bm_rbm *h) {
     BM_HIP(hipStreamSynchronize(h->stream));
     BM_TRY(check_device_status(h));
@@ -998,6 +1052,7 @@ int bm_rbm_sync(bm_rbm *h) {
         }
     }
     BM_TRY(check_class_labels(h));
+    BM_TRY(check_row_lengths(h));
     return 0;
 }
 
@@ -1445,11 +1500,22 @@ int bm_rbm_sample_h(bm_rbm *h, const float *X_dev, int32_t B, float *Hmean_dev, 
     // (Multinomial units without a means output: the softmax pair stages its logits in hm and shares one pitch between means
     //  and states - through the pitched workspaces, then one copy)
     const bool staged = h->multinomial() && Hstate_dev && !Hmean_dev;
+    if (h->rsm_len) rsm_lengths_of(h, X_dev, h->V, B, h->rsm_D.p);      // replicated softmax: the lengths of the input rows
     issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, staged ? rbm_out(h, 1, h->hm.p, h->hs.p, h->hm.ld, SITE_H0, 0)
                                                               : rbm_out(h, 1, Hmean_dev, Hstate_dev, h->H, SITE_H0, 0)));
     if (staged) hipLaunchKernelGGL(copy2d_kernel, dim3(256), dim3(256), 0, h->stream, (const float *)h->hs.p, h->hs.ld, Hstate_dev, h->H, B, h->H);
     h->call++;
     BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// replicated softmax: the entries that start from hidden states take the rows' lengths from the caller
+// (bm_rbm_set_row_lengths), exactly B of them; a handle without the unit: nothing to do
+static int rsm_use_row_lengths(bm_rbm *h, const char *what, int B) {
+    if (!h->rsm_len) return 0;
+    BM_CHECK(h->rsm_user_n == B, "%s on a handle with replicated softmax visible units needs the lengths of its %d rows: call "
+             "bm_rbm_set_row_lengths(h, D_dev, %d) first (%d lengths are set)", what, B, B, h->rsm_user_n);
+    h->rsm_cur = h->rsm_user.p;
     return 0;
 }
 
@@ -1460,6 +1526,7 @@ int bm_rbm_sample_v_from_h(bm_rbm *h, const float *H_dev, int32_t B, float *Vmea
     BM_CHECK(h && H_dev, "null argument");
     BM_CHECK(Vmean_dev || Vstate_dev, "bm_rbm_sample_v_from_h: no output (means and states are both null)");
     BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
+    BM_TRY(rsm_use_row_lengths(h, "bm_rbm_sample_v_from_h", B));
     issue(h, rbm_pass(h, false, B, LayerIn{H_dev, h->H}, rbm_out(h, 1, Vmean_dev, Vstate_dev, h->V, SITE_V, 0)));
     h->call++;
     BM_HIP(hipGetLastError());
@@ -1481,7 +1548,68 @@ int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K) {
     BM_CHECK(!h->n_classes, "softmax visible units do not combine with a class head (bm_rbm_set_classes(0) first)");
     BM_CHECK(!h->fw_on, "softmax visible units do not combine with fast weights (bm_rbm_set_fast_weights(off) first)");
     BM_CHECK(h->pt.M == 0, "softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
+    BM_CHECK(!h->rsm_len, "softmax visible units do not combine with replicated softmax visible units (bm_rbm_set_replicated_softmax(0) first)");
     h->v_groups = K;
+    return 0;
+}
+
+// Replicated softmax visible units (bm355.h).  A property of the handle that issue() reads at every pass
+int bm_rbm_set_replicated_softmax(bm_rbm *h, int32_t max_length) {
+    BM_CHECK(h, "null argument");
+    if (max_length == 0) { h->rsm_len = 0; h->rsm_user_n = 0; h->rsm_cur = nullptr; return 0; }
+    BM_CHECK(max_length >= 1 && max_length < (1 << 24), "replicated softmax visible units: max_length must be 0 (off) or in [1, 2^24) "
+             "(got %d): the lengths are exact in float32", (int)max_length);
+    BM_CHECK(h->V >= 2 && h->V <= RSM_MAX_V, "replicated softmax visible units: n_visible = %d is outside [2, %d] (a row's prefix sums and "
+             "counts live in LDS)", h->V, RSM_MAX_V);
+    BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "replicated softmax visible units replace Bernoulli visible units (this handle's are Gaussian)");
+    BM_CHECK(h->cfg.h_unit == BM_UNIT_BERNOULLI, "replicated softmax visible units need Bernoulli hidden units (this handle's are %s)",
+             h->multinomial() ? "Multinomial" : "NReLU");
+    BM_CHECK(!h->cfg.dbm_first && !h->cfg.dbm_last, "replicated softmax visible units: no dbm_first / dbm_last handle (the DBM has no such layer)");
+    BM_CHECK(h->cfg.dropout < 0.f, "replicated softmax visible units do not combine with dropout (this handle's is %g)", (double)h->cfg.dropout);
+    BM_CHECK(h->cfg.sparsity_cost == 0.f, "replicated softmax visible units do not combine with a sparsity penalty (this handle's "
+             "sparsity_cost is %g)", (double)h->cfg.sparsity_cost);
+    BM_CHECK(!h->cen_on, "replicated softmax visible units do not combine with centering (bm_rbm_set_centering(off) first)");
+    BM_CHECK(!h->n_classes, "replicated softmax visible units do not combine with a class head (bm_rbm_set_classes(0) first)");
+    BM_CHECK(!h->fw_on, "replicated softmax visible units do not combine with fast weights (bm_rbm_set_fast_weights(off) first)");
+    BM_CHECK(h->pt.M == 0, "replicated softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
+    BM_CHECK(!h->v_groups, "replicated softmax visible units do not combine with visible groups (bm_rbm_set_visible_groups(0) first)");
+    if (!h->rsm_bad.p) {          // (allocated last: the workspaces are complete once the flag exists)
+        BM_TRY(h->rsm_D.alloc(h->maxB)); BM_TRY(h->rsm_user.alloc(h->maxB));
+        DevArray<int> flag;
+        BM_TRY(flag.alloc(1));
+        BM_HIP(hipMemset(flag.p, 0, sizeof(int)));
+        h->rsm_bad = std::move(flag);
+    }
+    h->rsm_len = max_length;
+    h->rsm_user_n = 0;
+    h->rsm_cur = nullptr;
+    return 0;
+}
+
+// ... and the lengths of the rows that bm_rbm_sample_v_from_h and bm_rbm_gibbs run on next: D_dev [B] float32 on the device,
+// integers in [1, max_length], copied into the handle in stream order
+int bm_rbm_set_row_lengths(bm_rbm *h, const float *D_dev, int32_t B) {
+    BM_CHECK(h && D_dev, "null argument");
+    BM_CHECK(h->rsm_len, "bm_rbm_set_row_lengths needs a handle with replicated softmax visible units (bm_rbm_set_replicated_softmax); "
+             "this handle has none");
+    BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
+    BM_HIP(hipMemcpyAsync(h->rsm_user.p, D_dev, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    h->rsm_user_n = B;
+    return 0;
+}
+
+// row_lengths_kernel's flag: reported ONCE, then cleared.  The stream is idle when this is called
+static int check_row_lengths(bm_rbm *h) {
+    if (!h->rsm_bad.p) return 0;
+    int bad = 0;
+    BM_HIP(hipMemcpy(&bad, h->rsm_bad.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) {
+        BM_HIP(hipMemset(h->rsm_bad.p, 0, sizeof(int)));
+        BM_CHECK(false, "replicated softmax visible units: a row that is no count vector of 1 to max_length = %d tokens reached the "
+                 "engine:%s%s%s%s", h->rsm_len, (bad & RSM_BAD_NEGATIVE) ? " [a negative entry]" : "",
+                 (bad & RSM_BAD_FRACTION) ? " [a non-integer entry]" : "", (bad & RSM_BAD_EMPTY) ? " [an empty row, length 0]" : "",
+                 (bad & RSM_BAD_LONG) ? " [a row longer than max_length]" : "");
+    }
     return 0;
 }
 
@@ -1496,6 +1624,8 @@ int bm_rbm_metrics(bm_rbm *h, const float *X_dev, int32_t B, int32_t k, float *o
 
 int bm_rbm_free_energy(bm_rbm *h, const float *X_dev, int32_t B, float *out1) {
     BM_TRY(refuse_nrelu(h, "bm_rbm_free_energy", true));
+    BM_CHECK(!h->rsm_len, "bm_rbm_free_energy (the feg metric) is not available for replicated softmax visible units: its hidden kernel "
+             "has no length-scaled bias; bm_rbm_free_energy_rows gives the rows' free energies (DESIGN.md 3.27)");
     BM_CHECK(B >= 1 && B <= h->maxB, "batch %d outside [1, max_batch=%d]", B, h->maxB);
     // free_energy_op is built from self._X_batch AFTER tf.nn.dropout replaced it (base_rbm.py:417-418,
     // :516): the `feg` metric sees the dropped input like msre / pll do
@@ -1518,14 +1648,18 @@ int bm_rbm_free_energy(bm_rbm *h, const float *X_dev, int32_t B, float *out1) {
 // change of the RNG call counter): one prop-up that only leaves its softplus slot partials, one row kernel
 int bm_rbm_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, float *out_host) {
     BM_CHECK(h && X_dev && out_host, "null argument");
+    // (replicated softmax is served: F(v) = -v.vb - sum_j softplus(D hb_j + (vW)_j), the DB pass's own slot partials)
     BM_TRY(check_single_joint(h, "bm_rbm_free_energy_rows", true));
     BM_CHECK(B >= 1, "bad row count %d", (int)B);
-    if (B > h->fer_rows) {
+    if (B > h->fer_rows || (h->rsm_len && !h->fer_len.p)) {
+        const int rows = std::max((int)B, h->fer_rows);
         h->fer_rows = 0;
-        BM_TRY(h->fer_part.alloc((size_t)nslots(h->H) * B)); BM_TRY(h->fer_out.alloc(B));
-        h->fer_rows = B;
+        BM_TRY(h->fer_part.alloc((size_t)nslots(h->H) * rows)); BM_TRY(h->fer_out.alloc(rows));
+        if (h->rsm_len) BM_TRY(h->fer_len.alloc(rows));
+        h->fer_rows = rows;
     }
     ensure_wt(h);
+    if (h->rsm_len) rsm_lengths_of(h, X_dev, h->V, B, h->fer_len.p);     // the lengths of the input rows
     issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, LayerOut{0, nullptr, nullptr, pad_ld(h->H), PhiloxKey{0, 0, 0, 0}, 0})
                  .softplus_rows(h->fer_part.p, h->fer_rows, 0.f, 1.0f, 1));
     hipLaunchKernelGGL(rbm_fe_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, h->stream, X_dev, h->V, (int)B, h->V, (const float *)h->vb.p,
@@ -1533,6 +1667,7 @@ int bm_rbm_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, float *out
     BM_HIP(hipGetLastError());
     BM_HIP(hipMemcpyAsync(out_host, h->fer_out.p, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
+    BM_TRY(check_row_lengths(h));
     return 0;
 }
 
@@ -2276,8 +2411,9 @@ int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_ste
     BM_CHECK(H_dev && V_dev, "null state pointer");
     BM_CHECK(n_steps >= 1, "n_steps must be >= 1");
     struct FastScope { bm_rbm *h; ~FastScope() { h->fast_now = false; } } fast_scope{h};
-    const bool fast = h->fast && h->cfg.v_unit == BM_UNIT_BERNOULLI && !h->multinomial() && !h->nrelu() && !h->v_groups && h->cfg.sample_v_states &&
-                      h->cfg.sample_h_states && h->cfg.dropout < 0.f;
+    const bool fast = h->fast && h->cfg.v_unit == BM_UNIT_BERNOULLI && !h->multinomial() && !h->nrelu() && !h->v_groups && !h->rsm_len &&
+                      h->cfg.sample_v_states && h->cfg.sample_h_states && h->cfg.dropout < 0.f;
+    BM_TRY(rsm_use_row_lengths(h, "bm_rbm_gibbs", B));
     if (!fast && !h->multinomial()) {
         // The sweeps read and write the caller's dense buffers IN PLACE: the first prop-down takes H_dev (pitch H) as its
         // operand, the last sweep's launches store straight into V_dev / H_dev - no copy kernels (round 3 moved the

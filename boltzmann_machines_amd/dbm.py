@@ -119,6 +119,9 @@ class DBM(CenteredTraining, TemperedNegativePhase, EngineModel):
                 if getattr(rbm, '_V_GROUP_WIDTH', 0):
                     raise ValueError('DBM.load_rbms: layer %d (%s) has softmax visible units; the DBM has no such layer (its '
                                      'sweeps, mean-field and AIS are not built for one-hot groups)' % (i, type(rbm).__name__))
+                if getattr(rbm, '_RSM_MAX_LENGTH', 0):
+                    raise ValueError('DBM.load_rbms: layer %d (%s) has replicated softmax visible units; the DBM has no such layer '
+                                     '(its sweeps, mean-field and AIS are not built for word counts)' % (i, type(rbm).__name__))
             self._rbms = rbms
             # `self._h_layers = [rbm._h_layer for rbm in self._rbms]` (dbm.py:226): the hidden layer of every RBM
             self.h_units_ = [int(getattr(rbm, '_H_UNIT', _ffi.UNIT_BERNOULLI)) for rbm in rbms]

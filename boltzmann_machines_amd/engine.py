@@ -68,7 +68,7 @@ class RbmEngine(_PtCalls):
     def __init__(self, n_visible, n_hidden, v_unit=_ffi.UNIT_BERNOULLI, sample_v_states=False,
                  sample_h_states=True, dbm_first=False, dbm_last=False, max_batch=10, l2=1e-4,
                  sparsity_target=0.1, sparsity_cost=0., sparsity_damping=0.9, dropout=None,
-                 h_unit=_ffi.UNIT_BERNOULLI, n_samples=0, v_groups=0):
+                 h_unit=_ffi.UNIT_BERNOULLI, n_samples=0, v_groups=0, rsm_max_length=0):
         self.lib = _ffi.load()
         self.V, self.H, self.max_batch = int(n_visible), int(n_hidden), int(max_batch)
         cfg = _ffi.RbmConfig(self.V, self.H, int(v_unit), int(bool(sample_v_states)),
@@ -81,6 +81,12 @@ class RbmEngine(_PtCalls):
         if v_groups:          # softmax visible units: n_visible / v_groups one-hot groups (bm_rbm_set_visible_groups)
             try:
                 self.set_visible_groups(v_groups)
+            except Exception:
+                self.close()
+                raise
+        if rsm_max_length:    # replicated softmax visible units: one softmax over the layer, drawn D times per row
+            try:
+                self.set_replicated_softmax(rsm_max_length)
             except Exception:
                 self.close()
                 raise
@@ -231,6 +237,17 @@ class RbmEngine(_PtCalls):
         """softmax visible units (bm_rbm_set_visible_groups): n_visible / K one-hot groups of K units; 0: Bernoulli units again"""
         check(self.lib.bm_rbm_set_visible_groups(self._h, int(K)))
         self.v_groups = int(K)
+
+    def set_replicated_softmax(self, max_length):
+        """replicated softmax visible units (bm_rbm_set_replicated_softmax): rows are count vectors of 1 .. max_length tokens;
+        0: Bernoulli units again"""
+        check(self.lib.bm_rbm_set_replicated_softmax(self._h, int(max_length)))
+        self.rsm_max_length = int(max_length)
+
+    def set_row_lengths(self, Dd, B, row=0):
+        """the lengths of the B rows that the next sample_v_from_h / gibbs calls run on: entries [row, row + B) of the float32
+        DeviceArray Dd (bm_rbm_set_row_lengths)"""
+        check(self.lib.bm_rbm_set_row_lengths(self._h, Dd.offset_ptr(row), B))
 
     # softmax visible units: incomplete rows, clamped groups, exact group conditionals (bm355.h: bm_rbm_groups_*; DESIGN.md 3.25)
     def groups_set_missing(self, on):

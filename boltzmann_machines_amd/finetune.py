@@ -80,6 +80,9 @@ class StackClassifier(object):
             if getattr(m, '_V_GROUP_WIDTH', 0):
                 raise ValueError('%s (%s) has softmax visible units; a stack (from_rbms) takes Bernoulli layers only'
                                  % (name, type(m).__name__))
+            if getattr(m, '_RSM_MAX_LENGTH', 0):
+                raise ValueError('%s (%s) has replicated softmax visible units; a stack (from_rbms) takes Bernoulli layers only'
+                                 % (name, type(m).__name__))
             if m._H_UNIT == _ffi.UNIT_NRELU:
                 raise ValueError('%s (%s) has noisy rectified-linear (NReLU) hidden units; a stack (from_rbms) takes Bernoulli layers '
                                  'only' % (name, type(m).__name__))

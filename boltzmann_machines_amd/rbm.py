@@ -64,6 +64,7 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
     _V_UNIT = _ffi.UNIT_BERNOULLI
     _H_UNIT = _ffi.UNIT_BERNOULLI
     _V_GROUP_WIDTH = 0           # softmax visible units (CategoricalRBM): the width of a one-hot group; 0: none
+    _RSM_MAX_LENGTH = 0          # replicated softmax visible units (ReplicatedSoftmaxRBM): the longest document; 0: none
 
     def __init__(self,
                  n_visible=784, v_layer_cls=None, v_layer_params=None,
@@ -195,6 +196,8 @@ class BaseRBM(CenteredTraining, ClassHead, TemperedNegativePhase, EngineModel):
         if np.dtype(self.dtype) == np.float32 or f64:
             # (softmax visible units, CategoricalRBM: a property of the float32 handle)
             groups = {} if f64 or not self._V_GROUP_WIDTH else dict(v_groups=int(self._V_GROUP_WIDTH))
+            if not f64 and self._RSM_MAX_LENGTH:      # (replicated softmax visible units: likewise)
+                groups['rsm_max_length'] = int(self._RSM_MAX_LENGTH)
             self._engine = (RbmEngine64 if f64 else RbmEngine)(
                                      self.n_visible, self.n_hidden, v_unit=self._V_UNIT, **groups,
                                      sample_v_states=self.sample_v_states, sample_h_states=self.sample_h_states,
@@ -1400,6 +1403,230 @@ class CategoricalRBM(SoftmaxVisible, BaseRBM):
             raise ValueError('CategoricalRBM: n_visible = %r is not n_groups x n_categories = %r x %r' % (n_visible, n_groups, n_categories))
         super(CategoricalRBM, self).__init__(n_visible=int(n_groups) * int(n_categories), n_hidden=n_hidden, model_path=model_path,
                                              *args, **kwargs)
+
+
+class ReplicatedSoftmaxVisible(object):
+    """Replicated softmax visible units (Salakhutdinov & Hinton 2009), mixed in in front of an RBM class: the
+    visible layer is ONE softmax over the whole vocabulary of `n_visible` words, drawn D times per document and summed into a
+    count vector; the hidden bias is scaled by the document length D.  The RBM for bag-of-words data.
+
+    Rows of X are count vectors: non-negative integers whose sum D = X.sum(axis=1) lies in [1, max_length].
+    p(h_j = 1 | v) = sigmoid(D hb_j + (vW)_j);  v | h ~ Multinomial(D, softmax(vb + W h)), means D * softmax;
+    F(v) = -v.vb - sum_j softplus(D hb_j + (vW)_j).  The update is the Bernoulli one with the hidden-bias gradient
+    (1/N) sum_b D_b (h0_b - hk_b).  `fit`, `transform`, `sample_h`, checkpoints, `load_model` and `init_from` work as for the
+    other classes; `sample_v_from_h` and `sample_v` take the documents' lengths; `free_energy` gives F per row; `encode` turns
+    lists of token ids into count rows.  What is not built for word counts is refused with a ValueError before the engine is
+    touched: the `pll` and `feg` metrics, `dropout`, a non-zero `sparsity_cost`, `dbm_first` / `dbm_last`, dtype='float64',
+    `set_negative_phase` other than 'cd', `set_centering`, `set_classes`, `sample_v_given`, `log_Z` / `log_proba`,
+    BM355_DATA_PARALLEL jobs, and use as a layer of a `DBM` or a `StackClassifier`."""
+
+    _UNIT_NAME = 'replicated softmax visible units'
+    _MAX_VISIBLE = 16384         # csrc/bm_rsm.h: RSM_MAX_V
+
+    @property
+    def _RSM_MAX_LENGTH(self):
+        return int(self.max_length)
+
+    def _rsm_refuse(self, what, why):
+        raise ValueError('%s.%s: %s with %s' % (self.__class__.__name__, what, why, self._UNIT_NAME))
+
+    def _check_rsm_config(self, what):
+        """the constructor keywords the unit does not combine with (set_params may change them: checked again before the
+        engine is built)"""
+        name = self.__class__.__name__
+        if not 1 <= int(self.max_length) < (1 << 24):
+            raise ValueError('%s.%s: max_length must be in [1, 2^24) for %s (got %r)' % (name, what, self._UNIT_NAME, self.max_length))
+        if not 2 <= int(self.n_visible) <= self._MAX_VISIBLE:
+            raise ValueError('%s.%s: n_visible must be in [2, %d] for %s (got %r)' % (name, what, self._MAX_VISIBLE, self._UNIT_NAME,
+                                                                                   self.n_visible))
+        if self.metrics_config.get('pll'):
+            self._rsm_refuse(what, "metrics_config['pll'] flips single bits, which leaves the count vectors; it is not defined")
+        if self.metrics_config.get('feg'):
+            self._rsm_refuse(what, "metrics_config['feg'] (the batch free energy has no length-scaled bias) is not built; "
+                                   "`free_energy` gives the rows' free energies")
+        if self.dropout is not None:
+            self._rsm_refuse(what, 'dropout (dropout=%r) is not combined' % (self.dropout,))
+        if self.sparsity_cost != 0:
+            self._rsm_refuse(what, 'a sparsity penalty (sparsity_cost=%r) is not combined' % (self.sparsity_cost,))
+        if self.dbm_first or self.dbm_last:
+            self._rsm_refuse(what, 'dbm_first / dbm_last (a doubled conditional, a DBM layer) is not built')
+        if np.dtype(self.dtype) != np.float32:
+            self._rsm_refuse(what, "dtype='%s' is not supported (float32 only)" % np.dtype(self.dtype).name)
+
+    def __init__(self, *args, **kwargs):
+        super(ReplicatedSoftmaxVisible, self).__init__(*args, **kwargs)
+        self._check_rsm_config('__init__')
+
+    def _ensure_engine(self):
+        if self._engine is None:
+            self._check_rsm_config('fit')
+            if os.environ.get('BM355_DATA_PARALLEL', '0') == '1':
+                self._rsm_refuse('fit', 'data-parallel mode (BM355_DATA_PARALLEL) is not combined: the split step is not built')
+        return super(ReplicatedSoftmaxVisible, self)._ensure_engine()
+
+    def set_negative_phase(self, kind='cd', *args, **kwargs):
+        if kind != 'cd':
+            self._rsm_refuse('set_negative_phase', 'a %r negative phase (the tempered sweep has no count sampler) is not built' % (kind,))
+        return super(ReplicatedSoftmaxVisible, self).set_negative_phase(kind, *args, **kwargs)
+
+    def set_centering(self, enabled=True, *args, **kwargs):
+        if enabled:
+            self._rsm_refuse('set_centering', 'centering is not combined')
+        return super(ReplicatedSoftmaxVisible, self).set_centering(enabled, *args, **kwargs)
+
+    def set_classes(self, n_classes, *args, **kwargs):
+        if n_classes is not None:
+            self._rsm_refuse('set_classes', 'a class head is not built')
+        return super(ReplicatedSoftmaxVisible, self).set_classes(n_classes, *args, **kwargs)
+
+    def sample_v_given(self, *args, **kwargs):
+        self._rsm_refuse('sample_v_given', 'the clamped sweep is not built')
+
+    def log_Z(self, *args, **kwargs):
+        self._rsm_refuse('log_Z', 'AIS (its base model and its sweeps are Bernoulli) is not built')
+
+    def log_proba(self, *args, **kwargs):
+        self._rsm_refuse('log_proba', 'the log-likelihood (it needs log Z per document length) is not built')
+
+    # ---- count rows
+    def _counts_of(self, X, what):
+        """X as float32 [N, n_visible] with its lengths [N] int64; ValueError names the condition a row fails"""
+        name = self.__class__.__name__
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.n_visible:
+            raise ValueError('`X` has invalid shape {0}: expected [N, {1}]'.format(X.shape, self.n_visible))
+        if not np.all(np.isfinite(X)) or np.any(X != np.trunc(X)):
+            b = int(np.argwhere(~(np.isfinite(X) & (X == np.trunc(X))))[0][0])
+            raise ValueError('%s.%s: row %d is not integer-valued (%s take word counts)' % (name, what, b, self._UNIT_NAME))
+        if np.any(X < 0):
+            raise ValueError('%s.%s: row %d has a negative entry (%s take word counts)'
+                             % (name, what, int(np.argwhere(X < 0)[0][0]), self._UNIT_NAME))
+        D = X.astype(np.float64).sum(axis=1)
+        if np.any(D < 1):
+            raise ValueError('%s.%s: row %d is empty (length 0; %s need at least one token)'
+                             % (name, what, int(np.argwhere(D < 1)[0][0]), self._UNIT_NAME))
+        if np.any(D > int(self.max_length)):
+            b = int(np.argwhere(D > int(self.max_length))[0][0])
+            raise ValueError('%s.%s: row %d has length %d > max_length = %d (%s)' % (name, what, b, int(D[b]), int(self.max_length),
+                                                                                  self._UNIT_NAME))
+        return X, D.astype(np.int64)
+
+    def lengths(self, X):
+        """document lengths D = X.sum(axis=1), [N] int64, of count rows X (validated as `fit` validates them)"""
+        return self._counts_of(X, 'lengths')[1]
+
+    def encode(self, docs):
+        """documents (sequences of token ids in [0, n_visible)) -> count rows [N, n_visible] float32"""
+        X = np.zeros((len(docs), self.n_visible), dtype=np.float32)
+        for b, doc in enumerate(docs):
+            ids = np.asarray(doc, dtype=np.int64).reshape(-1)
+            if ids.size and (ids.min() < 0 or ids.max() >= self.n_visible):
+                raise ValueError('%s.encode: document %d has a token id outside [0, %d)' % (self.__class__.__name__, b, self.n_visible))
+            np.add.at(X[b], ids, 1.0)
+        return X
+
+    def _lengths_arg(self, lengths, N, what):
+        D = np.asarray(lengths)
+        D = np.repeat(D.reshape(1), N) if D.ndim == 0 else D.reshape(-1)
+        if len(D) != N or np.any(D != np.trunc(D)) or np.any(D < 1) or np.any(D > int(self.max_length)):
+            raise ValueError('%s.%s: `lengths` must be one integer in [1, max_length = %d] per row (%d rows)'
+                             % (self.__class__.__name__, what, int(self.max_length), N))
+        return np.ascontiguousarray(D, dtype=np.float32)
+
+    def fit(self, X, X_val=None, *args, **kwargs):
+        self._counts_of(X, 'fit')
+        if X_val is not None:
+            self._counts_of(X_val, 'fit')
+        return super(ReplicatedSoftmaxVisible, self).fit(X, X_val, *args, **kwargs)
+
+    @run_on_engine()
+    def free_energy(self, X):
+        """F(v) = -v.vb - sum_j softplus(D hb_j + (vW)_j) of every count row of X, [N] float32.  Draws nothing, changes nothing."""
+        eng = self._on_device()
+        X, _ = self._counts_of(X, 'free_energy')
+        if not len(X):
+            return np.zeros(0, dtype=np.float32)
+        return eng.free_energy_rows(self._to_device(X), len(X))
+
+    @run_on_engine(update_seed=True)
+    def sample_v_from_h(self, H, lengths, return_means=False):
+        """One draw of the count vectors given H, v ~ Multinomial(D, softmax(vb + W h)), by a single prop-down.
+
+        H : [N, n_hidden], taken as given; lengths : the documents' lengths D, one integer or [N].  Returns the counts
+        [N, n_visible] (with `return_means`: a pair, counts and the expected counts D * softmax); every row sums to its D.  The
+        rows are processed in slices of at most `batch_size`; draw d of row r reads position r * max_length + d of the call's
+        random stream: the result does not depend on the slicing.  One seed is drawn from the model's host stream; no parameter
+        is changed."""
+        eng = self._on_device()
+        H = np.ascontiguousarray(H, dtype=np.float32)
+        if H.ndim != 2 or H.shape[1] != self.n_hidden:
+            raise ValueError('`H` has invalid shape {0}: expected [N, {1}]'.format(H.shape, self.n_hidden))
+        N = len(H)
+        Dd = self._to_device(self._lengths_arg(lengths, N, 'sample_v_from_h'))
+        Hd = self._to_device(H)
+        Sd = _ffi.DeviceArray((N, self.n_visible), np.float32)
+        Md = _ffi.DeviceArray((N, self.n_visible), np.float32) if return_means else None
+        try:
+            for start in range(0, N, self.batch_size):
+                B = min(self.batch_size, N - start)
+                eng.seed(self._graph_seed)
+                eng.set_row_offset(start)
+                eng.set_row_lengths(Dd, B, row=start)
+                eng.sample_v_from_h(Hd, B, Md, Sd, row=start, out_row=start)
+            eng.sync()
+        finally:
+            eng.set_row_offset(0)
+        return (Sd.numpy(), Md.numpy()) if return_means else Sd.numpy()
+
+    @run_on_engine(update_seed=True)
+    def sample_v(self, n_samples, lengths, n_gibbs_steps=1000, V_init=None):
+        """Unconditional documents of given lengths by single-temperature block-Gibbs: `n_samples` independent chains run
+        `n_gibbs_steps` steps of (v ~ p(v|h), h ~ p(h|v)) from h ~ p(h | v_0); the count rows of the last step are returned,
+        [n_samples, n_visible].
+
+        lengths : the documents' lengths D, one integer or [n_samples]; every step draws exactly D tokens per row.
+        V_init : [n_samples, n_visible] count rows of those lengths; None: D tokens drawn uniformly over the vocabulary under
+        the call's seed.  Both layers are always sampled.  The rows are processed in slices of at most `batch_size`, every row
+        drawing from its own position of the call's random stream: the result does not depend on the slicing.  One seed is
+        drawn from the model's host stream; no parameter is changed."""
+        eng = self._on_device()
+        n_samples, n_gibbs_steps = int(n_samples), int(n_gibbs_steps)
+        if n_samples < 1 or n_gibbs_steps < 1:
+            raise ValueError('`n_samples` and `n_gibbs_steps` must be >= 1 (got {0}, {1})'.format(n_samples, n_gibbs_steps))
+        D = self._lengths_arg(lengths, n_samples, 'sample_v')
+        if V_init is None:
+            rng = np.random.RandomState(self._graph_seed)
+            V0 = self.encode([rng.randint(0, self.n_visible, int(d)) for d in D])
+        else:
+            V0, D0 = self._counts_of(V_init, 'sample_v')
+            if V0.shape != (n_samples, self.n_visible) or np.any(D0 != D):
+                raise ValueError('`V_init` must be [{0}, {1}] count rows of the given lengths'.format(n_samples, self.n_visible))
+        Vd, Dd = self._to_device(V0), self._to_device(D)
+        Hd = _ffi.DeviceArray((n_samples, self.n_hidden), np.float32)
+        try:
+            for start in range(0, n_samples, self.batch_size):
+                B = min(self.batch_size, n_samples - start)
+                eng.seed(self._graph_seed)
+                eng.set_row_offset(start)
+                eng.set_row_lengths(Dd, B, row=start)
+                eng.sample_h(Vd, B, None, Hd, row=start, out_row=start)
+                for _ in range(n_gibbs_steps):
+                    eng.sample_v_from_h(Hd, B, None, Vd, row=start, out_row=start)
+                    eng.sample_h(Vd, B, None, Hd, row=start, out_row=start)
+            eng.sync()
+        finally:
+            eng.set_row_offset(0)
+        return Vd.numpy()
+
+
+class ReplicatedSoftmaxRBM(ReplicatedSoftmaxVisible, BaseRBM):
+    """RBM with a replicated softmax (word-count) visible layer and Bernoulli hidden units: `n_visible` is the vocabulary size,
+    `max_length` the longest document the model will see (no counterpart in the reference).  The model for bag-of-words data.
+    See `ReplicatedSoftmaxVisible` for the unit and for what is refused."""
+
+    def __init__(self, n_visible=2000, n_hidden=256, max_length=1000, model_path='rs_rbm_model/', *args, **kwargs):
+        self.max_length = max_length
+        super(ReplicatedSoftmaxRBM, self).__init__(n_visible=n_visible, n_hidden=n_hidden, model_path=model_path, *args, **kwargs)
 
 
 def logit_mean(X):

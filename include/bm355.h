@@ -186,6 +186,32 @@ int bm_rbm_sample_v_from_h(bm_rbm *h, const float *H_dev, int32_t B, float *Vmea
  * _delta_update / the stack entries.  bm_rbm_set_fast_binary is accepted and runs fp32. */
 int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K);
 
+/* Replicated softmax visible units (Salakhutdinov & Hinton 2009; no counterpart in the reference): turns the
+ * visible layer of a Bernoulli-visible, Bernoulli-hidden float32 handle into ONE softmax over the n_visible units (2 to 16384),
+ * drawn D times per row and summed into a count vector; max_length = 0 turns it off again.  Rows are count vectors: non-negative
+ * integers in float32 with D_b = sum_i X[b][i] in [1, max_length], max_length < 2^24.  bm_rbm_config is unchanged.
+ *   E(v, h) = -v W h - v.vb - D h.hb;   p(h_j = 1 | v) = sigmoid(D hb_j + (v W)_j), formed as z + fl(D hb_j);
+ *   v | h ~ Multinomial(D, softmax(vb + W h)), means D * softmax;   F(v) = -v.vb - sum_j softplus(D hb_j + (v W)_j).
+ * The softmax and the draws are multinomial_counts_kernel's (csrc/bm_rsm.h: the prefix order, draw d of global row r reads the
+ * uniform at flat index r * max_length + d of the visible pass's stream).  The update is the Bernoulli one except for the hidden
+ * bias, whose gradient is (1/N) sum_b D_b (h0_b - hk_b).  Where the lengths come from: the training, metric and transform chains,
+ * bm_rbm_sample_h and bm_rbm_free_energy_rows compute them from their input rows; bm_rbm_sample_v_from_h and bm_rbm_gibbs take
+ * them from bm_rbm_set_row_lengths.  A row that is no such count vector raises a device flag, reported once by bm_rbm_sync and
+ * bm_rbm_free_energy_rows with a message that names the kind (negative entry, non-integer entry, empty row, row longer than
+ * max_length).  Such a handle trains (train_step, _metrics, _metrics_async, _epoch), transforms, runs bm_rbm_metrics (out4[0] the
+ * msre on counts; out4[1] pll and out4[3] are NaN), bm_rbm_sample_h and is staged like any other; always per-pass fp32 launches
+ * (no chained launch; bm_rbm_set_fast_binary is accepted and runs fp32).  Refused, with a message that contains "replicated
+ * softmax" and leaves the handle usable - here: max_length outside [1, 2^24), n_visible outside [2, 16384], Gaussian visible
+ * units, Multinomial or NReLU hidden units, dbm_first / dbm_last, dropout, a non-zero sparsity_cost, a handle with centering, a
+ * class head, fast weights, a tempered ensemble or visible groups; on such a handle: bm_rbm_free_energy (the feg metric) and every
+ * entry bm_rbm_set_visible_groups lists for its handles. */
+int bm_rbm_set_replicated_softmax(bm_rbm *h, int32_t max_length);
+
+/* The lengths of the rows that the next bm_rbm_sample_v_from_h / bm_rbm_gibbs calls of a replicated-softmax handle run on:
+ * D_dev [B] float32 on the device, integers in [1, max_length]; copied into the handle in stream order.  Those calls need
+ * exactly B rows. */
+int bm_rbm_set_row_lengths(bm_rbm *h, const float *D_dev, int32_t B);
+
 /* Softmax visible units with incomplete rows, clamped groups and exact group conditionals.  All three entries
  * need a handle with visible groups (bm_rbm_set_visible_groups); on any other handle they are refused with a message that names
  * visible groups, and the handle stays usable.  V = G K, W [V][H].
