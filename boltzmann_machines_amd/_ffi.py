@@ -150,6 +150,7 @@ SIGNATURES = {
     'bm_rbm_groups_gibbs_clamped': [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     'bm_rbm_groups_scores': [_vp, _vp, _i32, _vp],
     'bm_rbm_groups_ais': [_vp, _i32, _i32, _i32, _vp, _vp, _u64, _i64, _vp],
+    'bm_rbm_rsm_ais': [_vp, _i32, _i32, _i32, _vp, _vp, _u64, _i64, _vp],
     'bm_rbm_metrics': [_vp, _vp, _i32, _i32, _fp],
     'bm_rbm_free_energy': [_vp, _vp, _i32, _fp],
     'bm_rbm_free_energy_rows': [_vp, _vp, _i32, _vp],

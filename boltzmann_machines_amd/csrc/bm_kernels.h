@@ -172,6 +172,10 @@ struct ActArgs {
     // length: t = __fadd_rn(z, __fmul_rn(row_bmult[j], bias[i])) - two rounded steps, no contraction - where the plain pass takes
     // z + bias[i]; everything behind it is the plain epilogue (sigmoid, draw, negmeans, the softplus slot partials of `rowacc`,
     // which sum softplus(t) of the same t).  row_bmult [J].  Null: off.
+    // Tempered (the AIS per document length): mult == bmult == beta, uniform over the launch, multiplies the WHOLE
+    // pre-activation - the draw is from sigmoid(x), x = __fmul_rn(beta, t) with the t above: three rounded steps; `rowacc` takes the
+    // two-beta slot partials softplus_hw(__fmul_rn(beta_b, t)) - softplus_hw(__fmul_rn(beta_a, t)) of the same t.  beta == 1 is the
+    // untempered pass bit for bit (1 * t == t).
     const float *row_bmult;
 #ifdef BM_PROBE
     long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
@@ -593,6 +597,11 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                 }
                 if constexpr (SM) {            // l = z + b as kind 3 forms it; means and states below, once the quad is complete
                     nt[r] = x + b;
+                    continue;
+                }
+                if constexpr (DB) {            // beta (z + D hb): t as the row sums below form it, then ONE rounded product
+                    m[r] = sigmoid(__fmul_rn(a.mult, __fadd_rn(z[4 * hlf + r], b)));      // (mult == 1: t itself, the untempered pass)
+                    s[r] = m[r];
                     continue;
                 }
                 m[r] = (a.kind == 0) ? (LIT ? sigmoid_literal(x + b) : (HWMATH ? sigmoid_hw(x + b) : sigmoid(x + b)))

@@ -33,7 +33,8 @@
 //          SM   softmax visible units: logits prop-downs from W itself whose epilogue turns every group of sm_k in
 //               {2, 4, 8, 16} logits into its means and its one-hot state
 //          DB   replicated softmax: Bernoulli prop-ups whose row j multiplies the bias ALONE by row_bmult[j], the
-//               document length; the softplus slot partials of `rowacc` (single) ride on it; bm_rsm.hip
+//               document length; the softplus slot partials of `rowacc` ride on it; mult == bmult is 1 or the beta of a tempered
+//               pass, which multiplies the whole pre-activation; bm_rsm.hip
 //        SM + CL is the one combination of two of them, and no entry of the table: act_route refuses a softmax-group pass with a clamp
 //        mask as it always did; the caller that means clamped groups (a mask constant within every group) says so by
 //        calling launch_act_sm_clamped, which runs the kernels of bm_softmax_cl.hip - the CL block behind the SM block
@@ -287,10 +288,9 @@ template <> struct ActFlavour<FL_DB> : ActFlavourDefaults {
     static constexpr ActAsFn as = launch_act_db_as;
     static constexpr const char *no_kernel = "bm355: a length-scaled-bias pass is a single-segment Bernoulli prop-up of its own flavour (no such kernel)\n";
     static bool selects(const ActArgs &a) { return a.row_bmult != nullptr; }
-    static bool admits(const ActArgs &a) {
-        return a.kind == 0 && a.mult == 1.0f && a.bmult == 1.0f && !a.rowdot_out && (!a.rowacc || (a.rowacc_single && !a.dot_mat));
-    }
-    static void strip(ActArgs &p) { p.row_bmult = nullptr; }
+    // (mult == bmult: 1, or the launch-uniform beta of a tempered pass; the slot partials are softplus terms, single or two-beta)
+    static bool admits(const ActArgs &a) { return a.kind == 0 && a.mult == a.bmult && !a.rowdot_out && (!a.rowacc || !a.dot_mat); }
+    static void strip(ActArgs &p) { p.row_bmult = nullptr; p.mult = p.bmult = 1.0f; }
 };
 // SM + CL, clamped groups of softmax visible units: not an entry of the table - act_route never yields it - but
 // described like one, so that launch_act_sm_clamped runs it through launch_act_flavoured.  The kernel set is SM's, in a unit of its

@@ -21,6 +21,7 @@
 
 #include <math.h>
 #include <atomic>
+#include <functional>
 #include <memory>
 
 namespace bm {
@@ -150,6 +151,12 @@ struct bm_rbm {
     DevBuf ga_absent, ga_zero;
     int ga_rows = 0;
     Mat ga_l;
+    // bm_rbm_rsm_ais, allocated with the AIS workspaces at ra_rows == ais_rows rows: the logits of the run's
+    // prop-downs [ra_rows][V], the chains' lengths [ra_rows] and the float32 pair of v.dvec [2][ra_rows]; nothing else reads or
+    // writes them
+    int ra_rows = 0;
+    Mat ra_l;
+    DevBuf ra_len, ra_dot;
     // bm_rbm_pt_*: the tempered ensemble (bm_pt.h; layers v and h1), allocated on demand - max_batch does not bound it; nothing
     // else in the handle reads or writes it
     PtEnsemble pt;
@@ -413,8 +420,9 @@ static void issue(bm_rbm *h, LayerPass p) {
         if (launch_multinomial_counts(m, h->stream)) abort();      // (bm_rbm_set_replicated_softmax checked the width)
         return;
     }
-    // ... and their prop-up: the DB flavour scales the bias alone by the row's length
-    if (up && h->rsm_len) a.row_bmult = h->rsm_cur;
+    // ... and their prop-up: the DB flavour scales the bias alone by the row's length (a pass that brings lengths of its own - the
+    // chains of bm_rbm_rsm_ais - keeps them)
+    if (up && h->rsm_len && !a.row_bmult) a.row_bmult = h->rsm_cur;
     // noisy rectified-linear hidden units: the NR flavour rectifies t = z + b (formed as kind 3 forms it) and draws a normal
     if (up && h->nrelu()) { a.kind = 3; a.nrelu = 1; }
     // the prop-up's weights x-major: W^T where the handle keeps a valid one (ensure_wt), never beside the bf16 planes
@@ -852,9 +860,12 @@ static PhiloxKey ais_key(uint64_t seed, uint32_t site, int t, uint32_t step) {
 
 // h ~ Ber(sigmoid(beta z)), z = v W + hb, from the chain state av into ah; score: the same pass leaves the slot partials of
 // sum_j softplus(beta z_j) - softplus(beta_a z_j) in apart_h.  sample = 0: the score alone (the last beta)
-static void ais_up(bm_rbm *h, int R, float beta, int sample, const PhiloxKey &key, int64_t chain0, bool score, float beta_a) {
+// lengths (replicated softmax, bm_rbm_rsm_ais): the chains' own document lengths [R], z = v W + D hb - the tempered DB pass
+static void ais_up(bm_rbm *h, int R, float beta, int sample, const PhiloxKey &key, int64_t chain0, bool score, float beta_a,
+                   const float *lengths = nullptr) {
     LayerPass p = rbm_pass(h, true, R, in_of(h->av), LayerOut{sample, nullptr, sample ? h->ah.p : nullptr, h->ah.ld, key, chain0}, beta);
     if (score) p.softplus_rows(h->apart_h.p, h->ais_rows, beta_a, beta, 0);
+    p.a.row_bmult = lengths;
     issue(h, p);
 }
 // v ~ Ber(sigmoid(beta h W^T + a + beta (vb - a))) from ah into av, the mixed bias from row `kbeta` of the table; dot: the pass
@@ -2352,26 +2363,24 @@ int bm_rbm_class_gibbs(bm_rbm *h, const float *V_dev, const int32_t *y_dev, int3
 // beta_k from the same pre-activation; the score kernel adds them and (beta_k - beta_{k-1}) v_{k-1}.(vb - a) - the slot partials
 // the prop-down that made v_{k-1} left - to the double log-weights; then the prop-down, and n_gibbs_steps - 1 more up / down
 // pairs.  Between the uploads in front of the loop and the download behind it the host only enqueues.  fp32 path always.
-int bm_rbm_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t k, const float *base_bias_host, uint64_t seed, int64_t chain0,
-               float *values_host) {
-    BM_CHECK(h && values_host, "null argument");
-    BM_TRY(check_single_joint(h, "bm_rbm_ais"));
-    BM_CHECK(n_betas >= 2 && n_runs >= 1 && k >= 1, "bad AIS arguments (n_betas %d >= 2, n_runs %d >= 1, n_gibbs_steps %d >= 1)",
-             (int)n_betas, (int)n_runs, (int)k);
-    const int R = n_runs, V = h->V, H = h->H;
-    BM_TRY(ensure_ais_rows(h, R));
+//
+// What the AIS entries of the handle share (bm_rbm_ais, bm_rbm_groups_ais, bm_rbm_rsm_ais): the beta ladder, the upload of the base
+// logits, the table of mixed biases, the host loop with its seeds, the prop-up with its softplus partials, the score and the double
+// log-weights.  An entry brings log Z_0 of its base model (one number, or logZ0_rows [R] where it differs by chain), start() - v_0
+// into av and the partials of v_0.(vb - a) - and down(beta, kbeta, key, dot) - its visible transition from ah into av, which with
+// `dot` leaves the partials of v.(vb - a); vdot [vdot_slots][ais_rows] is where those partials are; lengths: ais_up's.  The AIS
+// workspaces for R rows exist (ensure_ais_rows)
+static int ais_run(bm_rbm *h, int n_betas, int R, int k, const float *base_bias_host, uint64_t seed, int64_t chain0, const float *lengths,
+                   const float *vdot, int vdot_slots, double logZ0, const double *logZ0_rows, float *values_host,
+                   const std::function<void()> &start, const std::function<void(float, int, const PhiloxKey &, bool)> &down) {
+    const int V = h->V, H = h->H;
     if (!h->abase.p) { BM_TRY(h->adot.alloc(V)); BM_TRY(h->abase.alloc(V)); }
     if (h->atable.n < (size_t)n_betas * V) { BM_TRY(h->abeta.alloc(n_betas)); BM_TRY(h->atable.alloc((size_t)n_betas * V)); }
-    // beta_k as float(np.linspace(0, 1, n_betas)[k]); log Z_0 = H log 2 + sum_i softplus(a_i) in double
+    // beta_k as float(np.linspace(0, 1, n_betas)[k])
     std::vector<float> beta(n_betas);
     const double step = 1.0 / (double)(n_betas - 1);
     for (int b = 0; b < n_betas; ++b) beta[b] = (float)((double)b * step);
     beta[n_betas - 1] = 1.0f;
-    double logZ0 = (double)H * log(2.0);
-    for (int i = 0; i < V; ++i) {
-        const double ai = base_bias_host ? (double)base_bias_host[i] : 0.0;
-        logZ0 += fmax(ai, 0.0) + log1p(exp(-fabs(ai)));
-    }
     BM_HIP(hipStreamSynchronize(h->stream));
     BM_HIP(hipMemcpy(h->abeta.p, beta.data(), (size_t)n_betas * sizeof(float), hipMemcpyHostToDevice));
     if (base_bias_host) BM_HIP(hipMemcpy(h->abase.p, base_bias_host, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
@@ -2381,29 +2390,53 @@ int bm_rbm_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t k, const floa
                        (const float *)h->abeta.p, (int)n_betas, V, h->adot.p, h->atable.p);
     BM_HIP(hipMemsetAsync(h->alogw.p, 0, (size_t)R * sizeof(double), h->stream));
     const int ldp = h->ais_rows;
-    hipLaunchKernelGGL(rbm_ais_init_kernel, dim3((R + 3) / 4), dim3(256), 0, h->stream, h->av.p, h->av.ld, R, V, (const float *)h->abase.p,
-                       (const float *)h->adot.p, ais_key(seed, SITE_AIS_V0, 0, 0), (unsigned long long)chain0, h->apart_v.p, ldp, nslots(V));
+    start();
     AisScoreArgs sc;
     memset(&sc, 0, sizeof(sc));
     sc.ne = 1; sc.pe[0] = h->apart_h.p; sc.ne_slots[0] = nslots(H);
-    sc.no = 1; sc.po[0] = h->apart_v.p; sc.no_slots[0] = nslots(V);
+    sc.no = 1; sc.po[0] = vdot; sc.no_slots[0] = vdot_slots;
     for (int b = 1; b < n_betas; ++b) {
         const bool last = b == n_betas - 1;            // no transition behind the last score
         const float ba = beta[b - 1], bb = beta[b];
-        ais_up(h, R, bb, last ? 0 : 1, ais_key(seed, SITE_AIS_H, 0, (uint32_t)b), chain0, true, ba);
+        ais_up(h, R, bb, last ? 0 : 1, ais_key(seed, SITE_AIS_H, 0, (uint32_t)b), chain0, true, ba, lengths);
         hipLaunchKernelGGL(ais_score_kernel, dim3((R + 31) / 32), dim3(256), 0, h->stream, h->alogw.p, R, ldp, sc, bb - ba);
         if (last) break;
         for (int t = 0; t < k; ++t) {
-            if (t > 0) ais_up(h, R, bb, 1, ais_key(seed, SITE_AIS_H, t, (uint32_t)b), chain0, false, 0.f);
-            ais_down(h, R, bb, b, ais_key(seed, SITE_AIS_V, t, (uint32_t)b), chain0, t == k - 1);
+            if (t > 0) ais_up(h, R, bb, 1, ais_key(seed, SITE_AIS_H, t, (uint32_t)b), chain0, false, 0.f, lengths);
+            down(bb, b, ais_key(seed, SITE_AIS_V, t, (uint32_t)b), t == k - 1);
         }
     }
     BM_HIP(hipGetLastError());
     std::vector<double> w(R);
     BM_HIP(hipMemcpyAsync(w.data(), h->alogw.p, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
-    for (int r = 0; r < R; ++r) values_host[r] = (float)(w[r] + logZ0);
+    for (int r = 0; r < R; ++r) values_host[r] = (float)(w[r] + (logZ0_rows ? logZ0_rows[r] : logZ0));
     return 0;
+}
+
+int bm_rbm_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t k, const float *base_bias_host, uint64_t seed, int64_t chain0,
+               float *values_host) {
+    BM_CHECK(h && values_host, "null argument");
+    BM_CHECK(!h->rsm_len, "bm_rbm_ais is not available for replicated softmax visible units (bm_rbm_set_replicated_softmax: max_length %d): "
+             "log Z depends on the document length there, bm_rbm_rsm_ais estimates it; see DESIGN.md 3.28", h->rsm_len);
+    BM_TRY(check_single_joint(h, "bm_rbm_ais"));
+    BM_CHECK(n_betas >= 2 && n_runs >= 1 && k >= 1, "bad AIS arguments (n_betas %d >= 2, n_runs %d >= 1, n_gibbs_steps %d >= 1)",
+             (int)n_betas, (int)n_runs, (int)k);
+    const int R = n_runs, V = h->V, H = h->H;
+    BM_TRY(ensure_ais_rows(h, R));
+    // log Z_0 = H log 2 + sum_i softplus(a_i) in double
+    double logZ0 = (double)H * log(2.0);
+    for (int i = 0; i < V; ++i) {
+        const double ai = base_bias_host ? (double)base_bias_host[i] : 0.0;
+        logZ0 += fmax(ai, 0.0) + log1p(exp(-fabs(ai)));
+    }
+    return ais_run(h, n_betas, R, k, base_bias_host, seed, chain0, nullptr, h->apart_v.p, nslots(V), logZ0, nullptr, values_host,
+                   [&] {
+                       hipLaunchKernelGGL(rbm_ais_init_kernel, dim3((R + 3) / 4), dim3(256), 0, h->stream, h->av.p, h->av.ld, R, V,
+                                          (const float *)h->abase.p, (const float *)h->adot.p, ais_key(seed, SITE_AIS_V0, 0, 0),
+                                          (unsigned long long)chain0, h->apart_v.p, h->ais_rows, nslots(V));
+                   },
+                   [&](float bb, int b, const PhiloxKey &key, bool dot) { ais_down(h, R, bb, b, key, chain0, dot); });
 }
 
 int bm_rbm_gibbs(bm_rbm *h, float *H_dev, float *V_dev, int32_t B, int32_t n_steps) {
@@ -2627,13 +2660,7 @@ int bm_rbm_groups_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t k, con
     if (observed_host) { n_obs = 0; for (int g = 0; g < G; ++g) n_obs += observed_host[g] != 0; }
     BM_CHECK(n_obs >= 1, "bm_rbm_groups_ais: the pattern observes none of the %d groups (a model without visible units has no chain)", G);
     BM_TRY(ensure_groups_ais_rows(h, R));
-    if (!h->abase.p) { BM_TRY(h->adot.alloc(V)); BM_TRY(h->abase.alloc(V)); }
-    if (h->atable.n < (size_t)n_betas * V) { BM_TRY(h->abeta.alloc(n_betas)); BM_TRY(h->atable.alloc((size_t)n_betas * V)); }
-    // beta_k as float(np.linspace(0, 1, n_betas)[k]); log Z_0 = H log 2 + sum over the observed groups of logsumexp_k a, in double
-    std::vector<float> beta(n_betas);
-    const double step = 1.0 / (double)(n_betas - 1);
-    for (int b = 0; b < n_betas; ++b) beta[b] = (float)((double)b * step);
-    beta[n_betas - 1] = 1.0f;
+    // log Z_0 = H log 2 + sum over the observed groups of logsumexp_k a, in double
     double logZ0 = (double)H * log(2.0);
     std::vector<float> absent_host(observed_host ? V : 0);
     for (int g = 0; g < G; ++g) {
@@ -2645,45 +2672,92 @@ int bm_rbm_groups_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t k, con
         for (int q = 0; q < K; ++q) se += exp((base_bias_host ? (double)base_bias_host[(size_t)g * K + q] : 0.0) - mx);
         logZ0 += mx + log(se);
     }
-    BM_HIP(hipStreamSynchronize(h->stream));
-    BM_HIP(hipMemcpy(h->abeta.p, beta.data(), (size_t)n_betas * sizeof(float), hipMemcpyHostToDevice));
-    if (base_bias_host) BM_HIP(hipMemcpy(h->abase.p, base_bias_host, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
-    else BM_HIP(hipMemset(h->abase.p, 0, (size_t)V * sizeof(float)));
-    if (observed_host) BM_HIP(hipMemcpy(h->ga_absent.p, absent_host.data(), (size_t)V * sizeof(float), hipMemcpyHostToDevice));
-    const float *absent = observed_host ? h->ga_absent.p : nullptr;
-    ensure_wt(h);
-    hipLaunchKernelGGL(rbm_ais_prep_kernel, dim3(512), dim3(256), 0, h->stream, (const float *)h->vb.p, (const float *)h->abase.p,
-                       (const float *)h->abeta.p, (int)n_betas, V, h->adot.p, h->atable.p);
-    BM_HIP(hipMemsetAsync(h->alogw.p, 0, (size_t)R * sizeof(double), h->stream));
-    const int ldp = h->ais_rows;
-    SaStartArgs s0;
-    memset(&s0, 0, sizeof(s0));
-    s0.v = h->av.p; s0.ld = h->av.ld; s0.rows = R; s0.V = V; s0.K = K;
-    s0.abase = h->abase.p; s0.dvec = h->adot.p; s0.absent = absent;
-    s0.key = ais_key(seed, SITE_AIS_V0, 0, 0); s0.row0 = (unsigned long long)chain0;
-    s0.part = h->apart_v.p; s0.ld_part = ldp; s0.nslot = nslots(V);
-    launch_softmax_ais_start(s0, h->stream);
-    AisScoreArgs sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.ne = 1; sc.pe[0] = h->apart_h.p; sc.ne_slots[0] = nslots(H);
-    sc.no = 1; sc.po[0] = h->apart_v.p; sc.no_slots[0] = nslots(V);
-    for (int b = 1; b < n_betas; ++b) {
-        const bool last = b == n_betas - 1;            // no transition behind the last score
-        const float ba = beta[b - 1], bb = beta[b];
-        ais_up(h, R, bb, last ? 0 : 1, ais_key(seed, SITE_AIS_H, 0, (uint32_t)b), chain0, true, ba);
-        hipLaunchKernelGGL(ais_score_kernel, dim3((R + 31) / 32), dim3(256), 0, h->stream, h->alogw.p, R, ldp, sc, bb - ba);
-        if (last) break;
-        for (int t = 0; t < k; ++t) {
-            if (t > 0) ais_up(h, R, bb, 1, ais_key(seed, SITE_AIS_H, t, (uint32_t)b), chain0, false, 0.f);
-            groups_ais_down(h, R, bb, b, ais_key(seed, SITE_AIS_V, t, (uint32_t)b), chain0, t == k - 1, absent);
-        }
+    if (observed_host) {
+        BM_HIP(hipStreamSynchronize(h->stream));
+        BM_HIP(hipMemcpy(h->ga_absent.p, absent_host.data(), (size_t)V * sizeof(float), hipMemcpyHostToDevice));
     }
-    BM_HIP(hipGetLastError());
-    std::vector<double> w(R);
-    BM_HIP(hipMemcpyAsync(w.data(), h->alogw.p, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    BM_HIP(hipStreamSynchronize(h->stream));
-    for (int r = 0; r < R; ++r) values_host[r] = (float)(w[r] + logZ0);
+    const float *absent = observed_host ? h->ga_absent.p : nullptr;
+    return ais_run(h, n_betas, R, k, base_bias_host, seed, chain0, nullptr, h->apart_v.p, nslots(V), logZ0, nullptr, values_host,
+                   [&] {
+                       SaStartArgs s0;
+                       memset(&s0, 0, sizeof(s0));
+                       s0.v = h->av.p; s0.ld = h->av.ld; s0.rows = R; s0.V = V; s0.K = K;
+                       s0.abase = h->abase.p; s0.dvec = h->adot.p; s0.absent = absent;
+                       s0.key = ais_key(seed, SITE_AIS_V0, 0, 0); s0.row0 = (unsigned long long)chain0;
+                       s0.part = h->apart_v.p; s0.ld_part = h->ais_rows; s0.nslot = nslots(V);
+                       launch_softmax_ais_start(s0, h->stream);
+                   },
+                   [&](float bb, int b, const PhiloxKey &key, bool dot) { groups_ais_down(h, R, bb, b, key, chain0, dot, absent); });
+}
+
+// ---- AIS per document length over replicated softmax visible units (bm355.h: bm_rbm_rsm_ais)
+
+// the workspaces of bm_rbm_ais for `rows` chains and the run's own logits, lengths and v.dvec pair at the same pitch; a failed
+// allocation leaves nothing counted (ensure_ais_rows)
+static int ensure_rsm_ais_rows(bm_rbm *h, int rows) {
+    BM_TRY(ensure_ais_rows(h, rows));
+    if (h->ra_rows == h->ais_rows) return 0;
+    h->ra_rows = 0;
+    BM_TRY(h->ra_l.alloc(h->ais_rows, h->V)); BM_TRY(h->ra_len.alloc(h->ais_rows)); BM_TRY(h->ra_dot.alloc(2 * (size_t)h->ais_rows));
+    h->ra_rows = h->ais_rows;
     return 0;
+}
+// the rows of ra_l, logits, become the chains' counts in av - D_r draws each at (chain0 + r) max_length + d of `key` - and leave
+// the pair of v.(vb - a) in ra_dot: the AIS flavour of multinomial_counts_kernel (bm_rsm.h)
+static void rsm_ais_counts(bm_rbm *h, int R, const PhiloxKey &key, int64_t chain0) {
+    McAisArgs m;
+    memset(&m, 0, sizeof(m));
+    m.L = h->ra_l.p; m.ld = h->ra_l.ld; m.states = h->av.p; m.ld_states = h->av.ld; m.lengths = h->ra_len.p;
+    m.V = h->V; m.J = R; m.sample = 1; m.max_length = h->rsm_len; m.key = key; m.row0 = chain0;
+    m.dvec = h->adot.p; m.part = h->ra_dot.p; m.ld_part = h->ais_rows;
+    if (launch_multinomial_counts_ais(m, h->stream)) abort();      // (bm_rbm_set_replicated_softmax checked the width)
+}
+// v ~ Multinomial(D, softmax(beta h W^T + a + beta (vb - a))) from ah into av: the kind-3 logits pass with the mixed bias from row
+// `kbeta` of the table into ra_l, then the count kernel on it in place
+static void rsm_ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &key, int64_t chain0) {
+    LayerPass p = rbm_pass(h, false, R, in_of(h->ah), LayerOut{0, h->ra_l.p, nullptr, h->ra_l.ld, key, chain0}, beta)
+                      .bias(h->atable.p + (size_t)kbeta * h->V, 1.0f);
+    p.a.kind = 3;
+    {
+        ProfScope _ps(h, KC_DOWN);
+        launch_act(p.a, h->stream);
+    }
+    ProfScope _ps(h, KC_OTHER);
+    rsm_ais_counts(h, R, key, chain0);
+}
+
+// bm_rbm_ais with a multinomial base model, count transitions and a length per chain; the host loop, the score kernel and the double
+// accumulation are bm_rbm_ais's own (ais_run), the prop-up is the DB pass at mult == bmult == beta
+int bm_rbm_rsm_ais(bm_rbm *h, int32_t n_betas, int32_t n_rows, int32_t k, const float *base_logits_host, const float *lengths_host,
+                   uint64_t seed, int64_t chain0, float *values_host) {
+    BM_CHECK(h && lengths_host && values_host, "bm_rbm_rsm_ais: null argument");
+    BM_CHECK(h->rsm_len, "bm_rbm_rsm_ais needs a handle with replicated softmax visible units (bm_rbm_set_replicated_softmax): log Z per "
+             "document length is defined for word-count rows only; bm_rbm_ais / bm_rbm_groups_ais serve the other units");
+    BM_CHECK(n_betas >= 2 && n_rows >= 1 && k >= 1 && chain0 >= 0, "bm_rbm_rsm_ais: bad AIS arguments (n_betas %d >= 2, n_rows %d >= 1, "
+             "n_gibbs_steps %d >= 1, chain0 %lld >= 0)", (int)n_betas, (int)n_rows, (int)k, (long long)chain0);
+    const int R = n_rows, V = h->V, H = h->H;
+    for (int r = 0; r < R; ++r) {
+        const float D = lengths_host[r];
+        BM_CHECK(D >= 1.0f && D <= (float)h->rsm_len && D == truncf(D), "bm_rbm_rsm_ais: lengths_host[%d] = %g is no integer in "
+                 "[1, max_length = %d]", r, (double)D, h->rsm_len);
+    }
+    BM_TRY(ensure_rsm_ais_rows(h, R));
+    // log Z_0(D) = H log 2 + D logsumexp(a) in double
+    double mx = -INFINITY, se = 0.0;
+    for (int i = 0; i < V; ++i) mx = fmax(mx, base_logits_host ? (double)base_logits_host[i] : 0.0);
+    for (int i = 0; i < V; ++i) se += exp((base_logits_host ? (double)base_logits_host[i] : 0.0) - mx);
+    const double lse = mx + log(se);
+    std::vector<double> logZ0(R);
+    for (int r = 0; r < R; ++r) logZ0[r] = (double)H * log(2.0) + (double)lengths_host[r] * lse;
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_HIP(hipMemcpy(h->ra_len.p, lengths_host, (size_t)R * sizeof(float), hipMemcpyHostToDevice));
+    return ais_run(h, n_betas, R, k, base_logits_host, seed, chain0, h->ra_len.p, h->ra_dot.p, 2, 0.0, logZ0.data(), values_host,
+                   [&] {
+                       ProfScope _ps(h, KC_OTHER);
+                       launch_rsm_fill_rows(h->ra_l.p, h->ra_l.ld, R, V, h->abase.p, h->stream);
+                       rsm_ais_counts(h, R, ais_key(seed, SITE_AIS_V0, 0, 0), chain0);
+                   },
+                   [&](float bb, int b, const PhiloxKey &key, bool) { rsm_ais_down(h, R, bb, b, key, chain0); });
 }
 
 // Parallel tempering (replica exchange).  The ensemble lives in the handle; see bm355.h for the contract.

@@ -7,6 +7,7 @@
 // l = h W^T + vb, then multinomial_counts_kernel turns every row into its expected counts and its drawn counts, in place.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "bm_rng.h"
 
 namespace bm {
@@ -59,6 +60,26 @@ struct McArgs {
     PhiloxKey key; long long row0;
 };
 int launch_multinomial_counts(const McArgs &a, hipStream_t st);
+
+// ---- the AIS flavour of multinomial_counts_kernel (a template parameter: the instantiations above carry none of it; bm_rbm_rsm_ais,
+// DESIGN.md 3.28).  Everything above, with sample == 1 and states; behind the draws the row also leaves its state . dvec for the
+// next AIS score, from the counts in LDS (nothing is read back from memory):
+//   s = sum_i (double)count[i] * (double)dvec[i]  - every product exact (counts are integers below 2^24, dvec is float32) - summed
+//       in double by the three levels of the prefix order: within each aligned run of 16 units sequentially from 0; within each
+//       aligned block of 16 runs the run totals sequentially from 0; the block totals in ascending order from 0.  The padding
+//       past V adds exact zeros: the order is a function of V alone
+//   part[row] = hi = (float)s;   part[ld_part + row] = lo = (float)(s - (double)hi)
+// A float32 pair in two "slots" of pitch ld_part: ais_score_kernel adds slots in double, hi + lo, which is s to 2^-48 |s| (s - hi
+// is exact in double, |s - hi| <= 2^-24 |s|, and lo rounds it to 2^-24 of that).  The tempered hidden pass that goes with it is the
+// DB flavour at mult == bmult == beta (bm_kernels.h: ActArgs::row_bmult).
+struct McAisArgs : McArgs {
+    const float *dvec;               // [V]
+    float *part; int ld_part;        // [2][ld_part], ld_part >= J
+};
+int launch_multinomial_counts_ais(const McAisArgs &a, hipStream_t st);
+
+// ---- rsm_fill_rows_kernel: L[j][i] = a[i] for j < J, i < V - the logits rows of the AIS start, v_0 ~ Multinomial(D_j, softmax(a))
+void launch_rsm_fill_rows(float *L, int ld, int J, int V, const float *a, hipStream_t st);
 
 // ---- rsm_bias_kernel: the bias block of the update with the hidden-bias sums weighted by the document lengths; launched in
 // front of the unchanged grad_kernel (which then runs without its bias tail, as it does for a handle with a sparsity penalty).

@@ -1,6 +1,7 @@
 // bm_rsm.hip - replicated softmax visible units: the instantiations of act_kernel's DB flavour (the prop-up
 // with a length-scaled bias), row_lengths_kernel, multinomial_counts_kernel (the prop-down's count sampler for vocabulary-wide
-// rows) and rsm_bias_kernel (the bias block with length-weighted hidden sums).  A translation unit of its own, as bm_nrelu.hip
+// rows, and its AIS flavour with rsm_fill_rows_kernel: DESIGN.md 3.28) and rsm_bias_kernel (the bias block with length-weighted
+// hidden sums).  A translation unit of its own, as bm_nrelu.hip
 // and bm_softmax_v.hip are: the kernels of the other units are compiled exactly as before.  Compiled into libbm355.so next to
 // bm355.hip.  bm_rsm.h fixes the operation sequences.
 #define BM_KERNELS_ONLY
@@ -44,8 +45,9 @@ void launch_row_lengths(const RowLenArgs &a, hipStream_t st) {
 // A run is four 16-byte loads where the row is 16-byte aligned and the run lies inside it; scalar loads at the ragged end and
 // for unaligned rows.  Level 1 of the prefix order runs in the 16-lane groups of a wave (15 dependent shuffle steps, every group
 // of the workgroup at once), level 2 in thread 0 over at most 64 block totals.
-template <int RPT>
-__global__ __launch_bounds__(256) void multinomial_counts_kernel(McArgs a) {
+// AIS (bm_rsm.h: McAisArgs): behind the draws the row's state . dvec from the counts in LDS, in double, as a float32 pair.
+template <int RPT, bool AIS = false>
+__global__ __launch_bounds__(256) void multinomial_counts_kernel(std::conditional_t<AIS, McAisArgs, McArgs> a) {
     constexpr int CAP = RPT * 4096;
     __shared__ __attribute__((aligned(16))) float s_c[CAP];
     __shared__ __attribute__((aligned(16))) int s_cnt[CAP];
@@ -185,6 +187,63 @@ __global__ __launch_bounds__(256) void multinomial_counts_kernel(McArgs a) {
             for (int k = 0; k < 16; ++k) if (i0 + k < V) st[i0 + k] = (float)s_cnt[i0 + k];
         }
     }
+    if constexpr (AIS) {
+        // state . dvec in double, by the three levels of the prefix order (bm_rsm.h): every product is exact, the padding adds zeros
+        __shared__ double s_dr[RPT * 256], s_db[RPT * 16];
+#pragma unroll
+        for (int p = 0; p < RPT; ++p) {
+            const int i0 = (p * 256 + tid) * 16;
+            double r = 0.0;
+            if (i0 < V) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (i0 + k < V) r = r + (double)s_cnt[i0 + k] * (double)a.dvec[i0 + k];
+            }
+            s_dr[p * 256 + tid] = r;
+        }
+        __syncthreads();
+        if (tid < RPT * 16) {                           // level 1: the 16 runs of block `tid` in ascending order
+            double b = 0.0;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) b = b + s_dr[tid * 16 + q];
+            s_db[tid] = b;
+        }
+        __syncthreads();
+        if (tid == 0) {                                 // level 2: the blocks in ascending order
+            double s = 0.0;
+            for (int b = 0; b < RPT * 16; ++b) s = s + s_db[b];
+            const float hi = (float)s, lo = (float)(s - (double)hi);
+            a.part[row] = hi;
+            a.part[(size_t)a.ld_part + row] = lo;
+        }
+    }
+}
+
+int launch_multinomial_counts_ais(const McAisArgs &a, hipStream_t st) {
+    if (a.V < 2 || a.V > RSM_MAX_V || !a.sample || !a.states || !a.dvec || !a.part || a.ld_part < a.J) {
+        fprintf(stderr, "bm355: the AIS flavour of multinomial_counts_kernel draws the counts of rows of 2 to %d units (got %d) and leaves "
+                "their state . dvec: it needs states, dvec and partials of pitch >= J\n", RSM_MAX_V, a.V);
+        return 1;
+    }
+    if (a.J < 1) return 0;
+    if (a.V <= 4096) hipLaunchKernelGGL((multinomial_counts_kernel<1, true>), dim3(a.J), dim3(256), 0, st, a);
+    else             hipLaunchKernelGGL((multinomial_counts_kernel<4, true>), dim3(a.J), dim3(256), 0, st, a);
+    return 0;
+}
+
+// ---- rsm_fill_rows_kernel (bm_rsm.h): L[j][i] = a[i]
+__global__ __launch_bounds__(256) void rsm_fill_rows_kernel(float *L, int ld, int J, int V, const float *a) {
+    const size_t n = (size_t)J * (size_t)V;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t j = e / (size_t)V, i = e % (size_t)V;
+        L[j * (size_t)ld + i] = a[i];
+    }
+}
+void launch_rsm_fill_rows(float *L, int ld, int J, int V, const float *a, hipStream_t st) {
+    if (J < 1) return;
+    const size_t n = (size_t)J * (size_t)V;
+    const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    hipLaunchKernelGGL(rsm_fill_rows_kernel, dim3(grid), dim3(256), 0, st, L, ld, J, V, a);
 }
 
 int launch_multinomial_counts(const McArgs &a, hipStream_t st) {

@@ -287,6 +287,21 @@ class RbmEngine(_PtCalls):
                                          out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def rsm_ais(self, n_betas, lengths, k, seed, chain0=0, base_logits=None):
+        """[len(lengths)] float32 per-chain AIS estimates of log Z_D of a handle with replicated softmax visible units, chain r
+        over count vectors of lengths[r] tokens (bm_rbm_rsm_ais); base_logits [V]: the base logits `a`, None: the
+        uniform base"""
+        D = np.ascontiguousarray(lengths, dtype=np.float32).reshape(-1)
+        out = np.empty(len(D), dtype=np.float32)
+        a = None
+        if base_logits is not None:
+            a = np.ascontiguousarray(base_logits, dtype=np.float32)
+            if a.shape != (self.V,):
+                raise ValueError('base_logits has shape %r, expected (%d,)' % (a.shape, self.V))
+        check(self.lib.bm_rbm_rsm_ais(self._h, n_betas, len(D), k, a.ctypes.data_as(C.c_void_p) if a is not None else None,
+                                      D.ctypes.data_as(C.c_void_p), int(seed), int(chain0), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def metrics(self, Xd, B, k, row=0):
         out = (C.c_float * 4)()
         check(self.lib.bm_rbm_metrics(self._h, Xd.offset_ptr(row * self.V), B, k, out))

@@ -1415,7 +1415,8 @@ class ReplicatedSoftmaxVisible(object):
     F(v) = -v.vb - sum_j softplus(D hb_j + (vW)_j).  The update is the Bernoulli one with the hidden-bias gradient
     (1/N) sum_b D_b (h0_b - hk_b).  `fit`, `transform`, `sample_h`, checkpoints, `load_model` and `init_from` work as for the
     other classes; `sample_v_from_h` and `sample_v` take the documents' lengths; `free_energy` gives F per row; `encode` turns
-    lists of token ids into count rows.  What is not built for word counts is refused with a ValueError before the engine is
+    lists of token ids into count rows; `ais_log_Z` / `ais_log_Z_rows` estimate log Z per document length by AIS, and
+    `log_likelihood` / `perplexity` score held-out documents with it.  What is not built for word counts is refused with a ValueError before the engine is
     touched: the `pll` and `feg` metrics, `dropout`, a non-zero `sparsity_cost`, `dbm_first` / `dbm_last`, dtype='float64',
     `set_negative_phase` other than 'cd', `set_centering`, `set_classes`, `sample_v_given`, `log_Z` / `log_proba`,
     BM355_DATA_PARALLEL jobs, and use as a layer of a `DBM` or a `StackClassifier`."""
@@ -1483,10 +1484,130 @@ class ReplicatedSoftmaxVisible(object):
         self._rsm_refuse('sample_v_given', 'the clamped sweep is not built')
 
     def log_Z(self, *args, **kwargs):
-        self._rsm_refuse('log_Z', 'AIS (its base model and its sweeps are Bernoulli) is not built')
+        self._rsm_refuse('log_Z', 'AIS (its base model and its sweeps are Bernoulli) is not built; log Z depends on the document '
+                                  'length here: `ais_log_Z` / `ais_log_Z_rows` are the estimators')
 
     def log_proba(self, *args, **kwargs):
-        self._rsm_refuse('log_proba', 'the log-likelihood (it needs log Z per document length) is not built')
+        self._rsm_refuse('log_proba', 'the log-likelihood (it needs log Z per document length) is not built; `log_likelihood` and '
+                                      '`perplexity` take the rows\' log Z from `ais_log_Z_rows`')
+
+    # ---- AIS log Z per document length, log-likelihood, perplexity
+    _AIS_MAX_ROWS = 1 << 16      # chains of one engine call; longer runs go through chain0 in chunks (the slice property)
+
+    def _base_logits(self, X_base):
+        """the logits `a` of the AIS base model p_0(v) = Multinomial(D, softmax(a)): None (uniform), `a` itself [V], or count
+        rows [N][V] -> the smoothed unigram a_i = log((sum_n X[n,i] + 1) / (sum_n D_n + V)) (float64, handed over as float32)"""
+        if X_base is None:
+            return None
+        X = np.asarray(X_base, dtype=np.float64)
+        if X.ndim == 2 and X.shape[1] == self.n_visible:
+            X, D = self._counts_of(X, 'ais_log_Z')
+            count = X.astype(np.float64).sum(axis=0)
+            return np.log((count + 1.) / (float(D.sum()) + self.n_visible)).astype(np.float32)
+        if X.shape != (self.n_visible,) or not np.all(np.isfinite(X)):
+            raise ValueError('`X_base` has invalid shape {0} or entries: expected count rows [N, {1}] or finite logits [{1}]'
+                             .format(X.shape, self.n_visible))
+        return X.astype(np.float32)
+
+    def _ais_lengths(self, lengths, what):
+        """(lengths as int64 [L], scalar?) - integers in [1, max_length], a scalar or a 1-D array"""
+        D = np.asarray(lengths)
+        scalar = D.ndim == 0
+        D = D.reshape(1) if scalar else D
+        ok = D.ndim == 1 and len(D) >= 1 and D.dtype.kind in 'iuf'
+        ok = ok and bool(np.all(np.isfinite(D)) and np.all(D == np.trunc(D)) and np.all(D >= 1) and np.all(D <= int(self.max_length)))
+        if not ok:
+            raise ValueError('%s.%s: `lengths` must be an integer or a 1-D array of integers in [1, max_length = %d]'
+                             % (self.__class__.__name__, what, int(self.max_length)))
+        return D.astype(np.int64), scalar
+
+    def ais_log_Z(self, lengths, n_betas=100, n_runs=100, n_gibbs_steps=5, X_base=None):
+        """AIS estimates of log Z_D, the log partition function over the count vectors of D tokens, for every D in `lengths`:
+        Z_D = sum_h exp(D h.hb) (sum_i exp(vb_i + (W h)_i))^D depends on the document length, so a held-out set needs one
+        estimate per distinct length.  All of them come from ONE run whose chains have different lengths.
+
+        lengths : an integer or a 1-D array of L integers in [1, max_length]; duplicates get chains of their own.
+        Returns log_mean, (log_low, log_high), values - per length what `BernoulliRBM.log_Z` returns - of shapes [L], ([L], [L])
+        and [L, n_runs]; a scalar `lengths` gives scalars and [n_runs].
+        `n_runs` chains per length run from the base model p_0(v) = Multinomial(D, softmax(a)) through `n_betas` temperatures
+        linspace(0, 1, n_betas) with `n_gibbs_steps` transitions each, the hidden layer summed out:
+        log p*_beta(v) = log(D!/prod v_i!) + (1 - beta) a.v + beta vb.v + sum_j softplus(beta (D hb + vW)_j).
+        X_base : None - the uniform base (a = 0); [N, n_visible] count rows - their smoothed unigram,
+        a_i = log((sum_n X[n,i] + 1) / (sum_n D_n + n_visible)); an [n_visible] array - the logits `a` themselves.
+        The chain of length lengths[l] and run r has index l * n_runs + r in the call's random streams, whatever the chunking.
+        Both layers are always sampled.  One seed is drawn from the model's host stream; no parameter is changed."""
+        n_betas, n_runs, n_gibbs_steps = int(n_betas), int(n_runs), int(n_gibbs_steps)
+        if n_betas < 2 or n_runs < 1 or n_gibbs_steps < 1:
+            raise ValueError('%s.ais_log_Z: n_betas must be >= 2, n_runs and n_gibbs_steps >= 1 (got %d, %d, %d)'
+                             % (self.__class__.__name__, n_betas, n_runs, n_gibbs_steps))
+        D, scalar = self._ais_lengths(lengths, 'ais_log_Z')
+        a = self._base_logits(X_base)
+        values = self._rsm_ais_checked(n_betas, np.repeat(D, n_runs), n_gibbs_steps, a).reshape(len(D), n_runs)
+        log_mean, log_low, log_high = (np.zeros(len(D)) for _ in range(3))
+        for l in range(len(D)):
+            log_mean[l] = log_mean_exp(values[l])
+            log_std = log_std_exp(values[l], log_mean_exp_x=log_mean[l])
+            log_high[l] = log_sum_exp([log_std, log_mean[l]])
+            log_low[l] = log_diff_exp([log_std, log_mean[l]])[0]
+        if scalar:
+            return log_mean[0], (log_low[0], log_high[0]), values[0]
+        return log_mean, (log_low, log_high), values
+
+    @run_on_engine(update_seed=True)
+    def _rsm_ais_checked(self, n_betas, D_rows, n_gibbs_steps, a):
+        """[len(D_rows)] float32: chain c has length D_rows[c]; chunks of at most _AIS_MAX_ROWS chains through chain0"""
+        eng = self._on_device()
+        out = np.empty(len(D_rows), dtype=np.float32)
+        for c0 in range(0, len(D_rows), self._AIS_MAX_ROWS):
+            c1 = min(len(D_rows), c0 + self._AIS_MAX_ROWS)
+            out[c0:c1] = eng.rsm_ais(n_betas, D_rows[c0:c1], n_gibbs_steps, seed=self._graph_seed, chain0=c0, base_logits=a)
+        return out
+
+    def ais_log_Z_rows(self, X, **ais_kwargs):
+        """[N] float64: for every count row of X the AIS log Z of its length, so that `log_likelihood(X, ais_log_Z_rows(X))` is
+        the held-out log-likelihood.  The DISTINCT lengths of X go through one `ais_log_Z` call - one run, one seed - and every
+        row gets the log_mean of its length.  `ais_kwargs`: n_betas, n_runs, n_gibbs_steps, X_base."""
+        if 'lengths' in ais_kwargs:
+            raise ValueError('%s.ais_log_Z_rows: the lengths come from `X`; `lengths` is not an argument' % self.__class__.__name__)
+        _, D = self._counts_of(X, 'ais_log_Z_rows')
+        if not len(D):
+            return np.zeros(0)
+        distinct, index = np.unique(D, return_inverse=True)
+        return np.asarray(self.ais_log_Z(distinct, **ais_kwargs)[0], dtype=np.float64)[index.reshape(-1)]
+
+    @staticmethod
+    def _log_coefficient(X):
+        """log(D! / prod_i v_i!) per count row, float64"""
+        from math import lgamma
+        Xi = np.asarray(X).astype(np.int64)
+        D = Xi.sum(axis=1)
+        vals = np.unique(np.concatenate([Xi.reshape(-1), D]))          # lgamma once per distinct integer
+        lg = np.array([lgamma(v + 1.) for v in vals], dtype=np.float64)
+        return lg[np.searchsorted(vals, D)] - lg[np.searchsorted(vals, Xi)].sum(axis=1)
+
+    def log_likelihood(self, X, log_Z_rows, ordered=False):
+        """[N] float64 log-probabilities of the count rows of X given the log partition function of every row's length
+        (`ais_log_Z_rows(X)`, or exact values).
+        ordered=False : log p(v) = log(D!/prod_i v_i!) - F(v) - log Z_D, the probability of the COUNT VECTOR (these sum to one over
+        the count vectors of a length); the coefficient is computed in float64 on the host.
+        ordered=True : -F(v) - log Z_D, the probability of ONE token sequence with those counts (the coefficient left out)."""
+        X, D = self._counts_of(X, 'log_likelihood')
+        lz = np.asarray(log_Z_rows, dtype=np.float64)
+        if lz.shape != (len(X),):
+            raise ValueError('`log_Z_rows` has invalid shape {0}: expected [{1}], one value per row'.format(lz.shape, len(X)))
+        if not len(X):
+            return np.zeros(0)
+        lp = -np.asarray(self.free_energy(X), dtype=np.float64) - lz
+        return lp if ordered else lp + self._log_coefficient(X)
+
+    def perplexity(self, X, log_Z_rows):
+        """exp(-mean_n(log p_ordered(v_n) / D_n)): the per-word perplexity of Salakhutdinov & Hinton (2009), from the probability
+        of a document as a token SEQUENCE (`log_likelihood(..., ordered=True)`: no multinomial coefficient), so that it compares
+        with a unigram model's exp(-mean_n (1/D_n) sum_i v_ni log q_i) and with the uniform model's n_visible."""
+        X, D = self._counts_of(X, 'perplexity')
+        if not len(X):
+            raise ValueError('`X` has no rows')
+        return float(np.exp(-np.mean(self.log_likelihood(X, log_Z_rows, ordered=True) / D.astype(np.float64))))
 
     # ---- count rows
     def _counts_of(self, X, what):

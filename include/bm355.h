@@ -266,6 +266,29 @@ int bm_rbm_groups_scores(bm_rbm *h, const float *X_dev, int32_t B, double *score
  * does not bound the number of chains. */
 int bm_rbm_groups_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t n_gibbs_steps, const float *base_bias_host,
                       const uint8_t *observed_host, uint64_t seed, int64_t chain0, float *values_host);
+/* AIS estimates of the log partition functions of an RBM with replicated softmax visible units.  The partition
+ * function depends on the document length, Z_D = sum_h exp(D h.hb) (sum_i exp(vb_i + (W h)_i))^D, so every chain has a length of
+ * its own: row r is ONE chain over count vectors of lengths_host[r] tokens, an integer in [1, max_length]; chains of different
+ * lengths run side by side in the same launches.  a = base_logits_host [V] (NULL: a = 0, the uniform base), t = D hb + v W:
+ *   p_0(v) = Multinomial(D, softmax(a)),   log Z_0(D) = n_hidden log 2 + D logsumexp(a)   (host, double)
+ *   log p*_beta(v) = log(D! / prod v_i!) + (1 - beta) a.v + beta vb.v + sum_j softplus(beta t_j),  beta_k = float32(linspace(0, 1, n_betas))[k]
+ * v_0 ~ p_0; for k = 1 .. n_betas - 1: logw += (beta_k - beta_{k-1}) v.(vb - a) + sum_j [softplus(beta_k t_j) - softplus(beta_{k-1} t_j)]
+ * (the coefficient cancels), then n_gibbs_steps transitions h ~ Ber(sigmoid(beta_k t)), v ~ Multinomial(D, softmax(a + beta_k (vb - a)
+ * + beta_k W h)) - both layers always sampled; none behind the last score.  values_host [n_rows] receives logw + log Z_0(D_r).
+ * The hidden pass forms x = fl(beta fl(z + fl(D hb_j))), three rounded steps; the counts are multinomial_counts_kernel's (csrc/bm_rsm.h:
+ * the prefix order).  RNG sites as bm_rbm_ais (Philox key = seed, counter word site + 16 t, call = beta step): 7 for v_0 (call 0), 8
+ * for v, 9 for h; draw d of row r reads the uniform at flat index (chain0 + r) max_length + d of the visible pass's stream, hidden unit
+ * j the one at (chain0 + r) n_hidden + j.  Rows [c, c + n) of a larger run are the run of those n lengths at chain0 = c, bit for bit.
+ * The per-beta softplus terms are fp32 (hardware transcendentals); v.(vb - a) is summed in DOUBLE from the counts (every product
+ * exact) and handed to the score as a float32 pair (hi, lo), exact to 2^-48 of its value; the sums over the slots and over the betas
+ * are double in a fixed order.  Needs a handle with replicated softmax visible units; refused otherwise, and for bad arguments
+ * (n_betas < 2, n_rows or n_gibbs_steps < 1, chain0 < 0, a length that is no integer in [1, max_length], null pointers), with a
+ * message that names bm_rbm_rsm_ais, before anything is enqueued; the handle stays usable.  The call draws from its own streams: it
+ * does not advance the handle's call counter, changes no parameter or momentum buffer, and touches no workspace that another entry
+ * reads - the lengths of bm_rbm_set_row_lengths and of the last batch included (the AIS workspaces are shared with bm_rbm_ais
+ * only).  Workspaces for n_rows rows are allocated on demand: max_batch does not bound the number of chains. */
+int bm_rbm_rsm_ais(bm_rbm *h, int32_t n_betas, int32_t n_rows, int32_t n_gibbs_steps, const float *base_logits_host,
+                   const float *lengths_host, uint64_t seed, int64_t chain0, float *values_host);
 
 /* Metric fetches of base_rbm.py:554-564,578,605,612: out[0]=msre (:486-488),
  * out[1]=pll (:496-513), out[2]=l2_loss (:482-484), out[3]=free_energy
