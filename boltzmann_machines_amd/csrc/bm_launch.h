@@ -322,6 +322,22 @@ template <> struct ActFlavour<FL_SM | FL_SA> : ActFlavourDefaults {
     }
     static void strip(ActArgs &p) { ActFlavour<FL_SM>::strip(p); p.sm_ais = 0; p.sm_absent = nullptr; p.mult = p.bmult = 1.0f; }
 };
+// SM + SA + RT, the softmax-group prop-down of parallel tempering over softmax visible units: the SM + SA pass with a
+// temperature PER ROW - row_mult[j] takes the place of mult and bmult in the logits, l = fl(fl(beta_j z) + fl(beta_j b)), the two
+// multiplies and one add of RT - and RT's hand-over of the beta = 1 rows (sel_out).  Like SM + SA no entry of the table and asked for
+// by name (launch_act_sm_pt; bm_softmax_pt.hip); the kernel set is SM's.  The pass carries no pattern of absent groups (an ensemble
+// row has none) and no rowen_out (the hidden half of the swap energy is the prop-up's); row_mult == 1 gives the plain SM pass bit for bit
+void launch_act_smpt_as(int, const ActArgs &, hipStream_t);
+template <> struct ActFlavour<FL_SM | FL_SA | FL_RT> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = true, geo5 = false;
+    static constexpr ActAsFn as = launch_act_smpt_as;
+    static constexpr const char *no_kernel = "bm355: a row-tempered softmax-group pass is a sampled softmax-group pass with a temperature per row that leaves state . dot_vec and nothing else (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.sm_k != 0 && a.sm_ais != 0 && a.row_mult != nullptr; }
+    static bool admits(const ActArgs &a) {
+        return ActFlavour<FL_SM | FL_SA>::admits(a) && !a.sm_absent && !a.rowen_out && (!a.sel_out || (a.sel_R >= 1 && a.sel_rows >= 0));
+    }
+    static void strip(ActArgs &p) { ActFlavour<FL_SM | FL_SA>::strip(p); ActFlavour<FL_RT>::strip(p); }
+};
 
 // the table's order: most specific first.  first(f): f(std::integral_constant<unsigned, FL>) for each flavour until one returns true
 template <unsigned... FL> struct ActFlavoursOf {
@@ -597,6 +613,12 @@ static inline void launch_act_sm_ais(const ActArgs &a, hipStream_t st) {
     using F = ActFlavour<FL_SM | FL_SA>;
     if (!F::selects(a) || (act_features(a) & ~FL_SM) != 0 || !F::admits(a)) { fputs(F::no_kernel, stderr); abort(); }
     launch_act_flavoured<FL_SM | FL_SA>(a, st);
+}
+// a row-tempered softmax-group pass (ActFlavour<FL_SM | FL_SA | FL_RT>): the caller's explicit choice, not a route of launch_act
+static inline void launch_act_sm_pt(const ActArgs &a, hipStream_t st) {
+    using F = ActFlavour<FL_SM | FL_SA | FL_RT>;
+    if (!F::selects(a) || (act_features(a) & ~(FL_SM | FL_RT)) != 0 || !F::admits(a)) { fputs(F::no_kernel, stderr); abort(); }
+    launch_act_flavoured<FL_SM | FL_SA | FL_RT>(a, st);
 }
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
     if (a.sm_ais) { fputs("bm355: a tempered softmax-group pass (AIS) is asked for by name, launch_act_sm_ais (no such route)\n", stderr); abort(); }

@@ -27,6 +27,7 @@ __device__ __forceinline__ float pt_vb_slot(int slot, int V, const float *vb, F 
     return (q[0] + q[1]) + (q[2] + q[3]);
 }
 
+#ifndef BM_KERNELS_ONLY      // (a unit that only needs the slot order above - bm_softmax_pt.hip - compiles none of the kernels below)
 // Start of the ensemble: one thread per row and 16-column slot of the visible layer, then of h2 (nH2 == 0: the model has none - an
 // RBM, a one-layer stack - and every thread is a visible slot).  v_0 ~ Ber(1/2) at its flat index of the global row (V0 null) or
 // the chain's row of V0 [M][V] for all its R replicas; h2_0 ~ Ber(1/2) always (key_h2); the slot's partial of v_0.vb / h2_0.b2
@@ -184,24 +185,33 @@ static inline int pt_check_ladder(int32_t n_chains, int32_t n_temps, const float
     return 0;
 }
 
-// Start an ensemble of M chains x R replicas of the widths {V, n1, n2} (n2 == 0: no h2) from a checked ladder: v_0 from V0_dev
-// (null: Ber(1/2) under key_v), h2_0 ~ Ber(1/2) under key_h2; vb / b2: the biases the first partials are scored with.
-static inline int pt_begin(PtEnsemble &e, hipStream_t stream, const int widths[3], int M, int R, int64_t chain0,
-                           const float *betas_host, const float *V0_dev, const float *vb, const float *b2, PhiloxKey key_v,
-                           PhiloxKey key_h2) {
+// Start an ensemble of M chains x R replicas of the widths {V, n1, n2} (n2 == 0: no h2) from a checked ladder; start(e, rows): the
+// engine's own start launch on `stream` - it fills e.v.x (and e.h2.x), the first v.vb (h2.b2) partials, e.mult from e.beta and e.idx
+template <class StartFn>
+static inline int pt_begin_with(PtEnsemble &e, hipStream_t stream, const int widths[3], int M, int R, int64_t chain0,
+                                const float *betas_host, StartFn &&start) {
     const int rows = M * R;
     e.M = 0;                                       // (an ensemble exists once everything below went through)
     BM_TRY(e.ensure(rows, R, widths));
     BM_HIP(hipStreamSynchronize(stream));
     BM_HIP(hipMemcpy(e.beta.p, betas_host, (size_t)R * sizeof(float), hipMemcpyHostToDevice));
     BM_HIP(hipMemsetAsync(e.cnt.p, 0, (size_t)2 * std::max(R - 1, 1) * sizeof(unsigned long long), stream));
-    const long long nthr = (long long)rows * (nslots(e.v.n) + nslots(e.h2.n));
-    hipLaunchKernelGGL(pt_init_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, e.v.x.p, e.v.x.ld, rows, R, e.v.n,
-                       V0_dev, vb, e.h2.x.p, e.h2.x.ld, e.h2.n, b2, (const float *)e.beta.p, key_v, key_h2,
-                       (unsigned long long)chain0 * (unsigned long long)R, e.v.part.p, e.h2.part.p, e.rows, e.mult.p, e.idx.p);
+    start(e, rows);
     BM_HIP(hipGetLastError());
     e.M = M; e.R = R; e.chain0 = chain0; e.step = 0;
     return 0;
+}
+// ... with pt_init_kernel as the start: v_0 from V0_dev (null: Ber(1/2) under key_v), h2_0 ~ Ber(1/2) under key_h2; vb / b2: the
+// biases the first partials are scored with.
+static inline int pt_begin(PtEnsemble &e, hipStream_t stream, const int widths[3], int M, int R, int64_t chain0,
+                           const float *betas_host, const float *V0_dev, const float *vb, const float *b2, PhiloxKey key_v,
+                           PhiloxKey key_h2) {
+    return pt_begin_with(e, stream, widths, M, R, chain0, betas_host, [&](PtEnsemble &en, int rows) {
+        const long long nthr = (long long)rows * (nslots(en.v.n) + nslots(en.h2.n));
+        hipLaunchKernelGGL(pt_init_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, en.v.x.p, en.v.x.ld, rows, R, en.v.n,
+                           V0_dev, vb, en.h2.x.p, en.h2.x.ld, en.h2.n, b2, (const float *)en.beta.p, key_v, key_h2,
+                           (unsigned long long)chain0 * (unsigned long long)R, en.v.part.p, en.h2.part.p, en.rows, en.mult.p, en.idx.p);
+    });
 }
 
 // The replica exchange of step t of a call (parity of the global step number e.step + t); nothing to launch at R == 1 or where
@@ -250,5 +260,7 @@ static inline int pt_read_host(PtEnsemble &e, hipStream_t stream, int64_t *swaps
     if (ladder_idx_host) BM_HIP(hipMemcpy(ladder_idx_host, e.idx.p, (size_t)e.nrows() * sizeof(int32_t), hipMemcpyDeviceToHost));
     return 0;
 }
+
+#endif  // BM_KERNELS_ONLY
 
 }  // namespace bm

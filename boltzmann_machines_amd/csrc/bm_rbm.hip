@@ -18,6 +18,7 @@
 #include "bm_softmax_v.h"
 #include "bm_rsm.h"
 #include "bm_softmax_ais.h"
+#include "bm_softmax_pt.h"
 
 #include <math.h>
 #include <atomic>
@@ -160,6 +161,10 @@ struct bm_rbm {
     // bm_rbm_pt_*: the tempered ensemble (bm_pt.h; layers v and h1), allocated on demand - max_batch does not bound it; nothing
     // else in the handle reads or writes it
     PtEnsemble pt;
+    // bm_rbm_groups_pt_* (DESIGN.md 3.29), the generic route only: the raw z = h W^T [gp_rows][V] of the ensemble's prop-down,
+    // allocated with the ensemble; nothing else reads or writes it
+    int gp_rows = 0;
+    Mat gp_z;
     int fer_rows = 0;
     DevBuf fer_part, fer_out;          // bm_rbm_free_energy_rows: slot partials [ceil(H/16)][fer_rows] of sum softplus, F [fer_rows]
     // fast-binary mode (bm_bf3.h, bm_rbm_set_fast_binary): bf16 planes of W ([V][H]: the prop-down operand) and of
@@ -1211,10 +1216,30 @@ int bm_rbm_set_param_dev(bm_rbm *h, const char *name, const float *src_dev, size
     return 0;
 }
 
+// The whole tempered ensemble, read only, dense (tests and tools; bm_rbm_pt_read / bm_rbm_groups_pt_read hand out the beta = 1 rows):
+// "pt_v" [M R][V], "pt_h" [M R][H], "pt_part_v" [ceil(V/16)][M R], "pt_part_h" [ceil(H/16)][M R], "pt_mult" [M R]
+static int pt_get_param(bm_rbm *h, const std::string &nm, float *host, size_t n) {
+    PtEnsemble &e = h->pt;
+    BM_CHECK(e.M > 0, "variable '%s': no ensemble (bm_rbm_pt_init / bm_rbm_groups_pt_init)", nm.c_str());
+    const size_t rows = (size_t)e.nrows();
+    const float *src = nullptr;
+    size_t pitch = 0, width = 0, height = 0;
+    if (nm == "pt_v")           { src = e.v.x.p; pitch = e.v.x.ld; width = h->V; height = rows; }
+    else if (nm == "pt_h")      { src = e.h1.x.p; pitch = e.h1.x.ld; width = h->H; height = rows; }
+    else if (nm == "pt_part_v") { src = e.v.part.p; pitch = e.rows; width = rows; height = nslots(h->V); }
+    else if (nm == "pt_part_h") { src = e.h1.part.p; pitch = e.rows; width = rows; height = nslots(h->H); }
+    else if (nm == "pt_mult")   { src = e.mult.p; pitch = rows; width = rows; height = 1; }
+    BM_CHECK(src, "unknown RBM variable '%s'", nm.c_str());
+    BM_CHECK(n == width * height, "variable '%s' has %zu elements, got %zu", nm.c_str(), width * height, n);
+    BM_HIP(hipMemcpy2D(host, width * sizeof(float), src, pitch * sizeof(float), width * sizeof(float), height, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int bm_rbm_get_param(bm_rbm *h, const char *name, float *host, size_t n) {
     const std::string nm(name ? name : "");
     BM_HIP(hipStreamSynchronize(h->stream));
     BM_TRY(check_device_status(h));        // never hand out variables computed from invalid tiles / a lost rank's sums
+    if (nm.compare(0, 3, "pt_") == 0) return pt_get_param(h, nm, host, n);
     bool ro = false;
     Mat *fm = find_fast_mat(h, nm, &ro);
     DevBuf *fb = fm ? nullptr : find_fast_vec(h, nm, &ro);
@@ -1547,7 +1572,12 @@ int bm_rbm_sample_v_from_h(bm_rbm *h, const float *H_dev, int32_t B, float *Vmea
 // Softmax visible units (bm355.h).  A property of the handle that issue() reads at every prop-down
 int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K) {
     BM_CHECK(h, "null argument");
-    if (K == 0) { h->v_groups = 0; h->groups_missing = false; return 0; }
+    if (K == 0) {
+        // (an ensemble of one-hot rows goes with the groups, DESIGN.md 3.29: a Bernoulli sweep never runs over it)
+        if (h->v_groups) h->pt.M = 0;
+        h->v_groups = 0; h->groups_missing = false;
+        return 0;
+    }
     BM_CHECK(K >= 2, "softmax visible units: the group width must be 0 (off) or >= 2 (got %d)", (int)K);
     BM_CHECK(h->V % K == 0, "softmax visible units: n_visible = %d is no multiple of the group width %d", h->V, (int)K);
     BM_CHECK(h->cfg.v_unit == BM_UNIT_BERNOULLI, "softmax visible units replace Bernoulli visible units (this handle's are Gaussian)");
@@ -1558,7 +1588,8 @@ int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K) {
     BM_CHECK(!h->cen_on, "softmax visible units do not combine with centering (bm_rbm_set_centering(off) first)");
     BM_CHECK(!h->n_classes, "softmax visible units do not combine with a class head (bm_rbm_set_classes(0) first)");
     BM_CHECK(!h->fw_on, "softmax visible units do not combine with fast weights (bm_rbm_set_fast_weights(off) first)");
-    BM_CHECK(h->pt.M == 0, "softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
+    // (the ensemble of a handle that has this width already is bm_rbm_groups_pt_init's, DESIGN.md 3.29: nothing changes)
+    BM_CHECK(h->pt.M == 0 || h->v_groups == K, "softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
     BM_CHECK(!h->rsm_len, "softmax visible units do not combine with replicated softmax visible units (bm_rbm_set_replicated_softmax(0) first)");
     h->v_groups = K;
     return 0;
@@ -2844,6 +2875,153 @@ int bm_rbm_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batc
     for (int64_t s = 0; s < N; s += batch) {
         const int B = (int)((N - s < batch) ? (N - s) : batch);
         BM_TRY(bm_rbm_train_step_pt(h, X_dev + (size_t)s * h->V, B, lr, mom, k));
+    }
+    return 0;
+}
+
+// ---- parallel tempering over softmax visible units (bm355.h: bm_rbm_groups_pt_* / _train_step_pt).  The ensemble
+// is the handle's one PtEnsemble: a handle with visible groups holds no other (bm_rbm_pt_init refuses it, bm_rbm_set_visible_groups
+// refuses a handle that holds a Bernoulli one), and turning the groups off discards it.
+static int check_groups_pt(const bm_rbm *h, const char *what) {
+    BM_TRY(need_groups(h, what));
+    BM_CHECK(!h->groups_missing, "%s: not built for incomplete rows (bm_rbm_groups_set_missing is on): a row of the tempered ensemble "
+             "has no pattern of observed groups; see DESIGN.md 3.29", what);
+    return 0;
+}
+// the generic route's raw z for `rows` ensemble rows; a failed allocation leaves nothing counted
+static int ensure_groups_pt_rows(bm_rbm *h, int rows) {
+    if (groups_fused(h) || rows <= h->gp_rows) return 0;
+    h->gp_rows = 0;
+    BM_TRY(h->gp_z.alloc(rows, h->V));
+    h->gp_rows = rows;
+    return 0;
+}
+// The prop-down of step t: v_g ~ softmax_k(beta_row (h W^T + vb)_{gK+k}) from pt.h1 into pt.v, leaving the slot partials of v.vb.
+// Fused route: ONE launch, the SM + SA + RT flavour; sel_rows > 0: it also leaves the beta = 1 row of every chain c < sel_rows in
+// vs[c].  Generic route: a raw pass (z = h W^T, the plain kernels), the tempered groups kernel, the row-dot kernel - the same bits;
+// its hand-over is the caller's gather launch
+static void groups_pt_down(bm_rbm *h, int t, int sel_rows) {
+    PtEnsemble &e = h->pt;
+    const int rows = e.nrows();
+    const PhiloxKey key = make_key(h, SITE_V, t);
+    LayerPass p = rbm_pass(h, false, rows, in_of(e.h1.x), value_out(1, e.v.x.p, e.v.x.ld, key, e.row0()));
+    ActArgs &a = p.a;
+    if (groups_fused(h)) {
+        ProfScope _ps(h, KC_DOWN);
+        p.statedot_rows(e.v.part.p, e.rows, h->vb.p).row_tempered(e.mult.p);
+        if (sel_rows > 0) p.select_rows(h->vs.p, h->vs.ld, e.R, sel_rows);
+        a.kind = 3; a.sm_k = h->v_groups; a.sm_ais = 1; a.sm_absent = nullptr;
+        launch_act_sm_pt(a, h->stream);
+        return;
+    }
+    a.kind = 2; a.sample = 0; a.states = nullptr; a.means = h->gp_z.p; a.ldo = h->gp_z.ld;
+    {
+        ProfScope _ps(h, KC_DOWN);
+        launch_act(a, h->stream);
+    }
+    ProfScope _ps(h, KC_OTHER);                        // (per-class event timing: the route's extra launches are the class `other`)
+    SpGroupsArgs g;
+    memset(&g, 0, sizeof(g));
+    g.Z = h->gp_z.p; g.ldz = h->gp_z.ld; g.states = e.v.x.p; g.ld_states = e.v.x.ld;
+    g.V = h->V; g.K = h->v_groups; g.J = rows; g.bias = h->vb.p; g.row_mult = e.mult.p; g.key = key; g.row0 = e.row0();
+    launch_softmax_pt_groups(g, h->stream);
+    launch_softmax_ais_dot(e.v.x.p, e.v.x.ld, rows, h->V, h->vb.p, e.v.part.p, e.rows, h->stream);
+}
+// step t of a tempered call: the RT prop-up and the swap of pt_step, unchanged - for one-hot v they are this model's - then the
+// tempered softmax prop-down
+static void groups_pt_step(bm_rbm *h, int t, int sel_rows = 0) {
+    PtEnsemble &e = h->pt;
+    issue(h, rbm_pass(h, true, e.nrows(), in_of(e.v.x), value_out(1, e.h1.x.p, e.h1.x.ld, make_key(h, SITE_H, t), e.row0()))   // (mult: not read)
+                 .energy_rows(e.h1.part.p, e.rows).row_tempered(e.mult.p));
+    pt_launch_swap(e, h->stream, t, make_key(h, SITE_PT_SWAP, t));
+    groups_pt_down(h, t, sel_rows);
+}
+
+int bm_rbm_groups_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0) {
+    BM_TRY(check_groups_pt(h, "bm_rbm_groups_pt_init"));
+    BM_TRY(pt_check_ladder(n_chains, n_temps, betas_host, chain0));
+    h->pt.M = 0;
+    BM_TRY(ensure_groups_pt_rows(h, n_chains * n_temps));
+    const int widths[3] = {h->V, h->H, 0};
+    const PhiloxKey key = make_key(h, SITE_PT_V0, 0);
+    return pt_begin_with(h->pt, h->stream, widths, n_chains, n_temps, chain0, betas_host, [&](PtEnsemble &e, int rows) {
+        SpStartArgs s0;
+        memset(&s0, 0, sizeof(s0));
+        s0.v = e.v.x.p; s0.ld = e.v.x.ld; s0.rows = rows; s0.R = n_temps; s0.V = h->V; s0.K = h->v_groups;
+        s0.V0 = V0_dev; s0.vb = h->vb.p; s0.beta = e.beta.p;
+        s0.key = key; s0.row0 = (unsigned long long)chain0 * (unsigned long long)n_temps;
+        s0.part = e.v.part.p; s0.ld_part = e.rows; s0.row_mult = e.mult.p; s0.idx = e.idx.p;
+        launch_softmax_pt_init(s0, h->stream);
+    });
+}
+
+int bm_rbm_groups_pt_sweep(bm_rbm *h, int32_t n_steps) {
+    BM_TRY(check_groups_pt(h, "bm_rbm_groups_pt_sweep"));
+    BM_CHECK(h->pt.M > 0, "bm_rbm_groups_pt_sweep: no ensemble (call bm_rbm_groups_pt_init first)");
+    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
+    ensure_wt(h);
+    for (int t = 0; t < n_steps; ++t) groups_pt_step(h, t);
+    h->pt.step += n_steps;
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+int bm_rbm_groups_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
+    BM_TRY(check_groups_pt(h, "bm_rbm_groups_pt_read"));
+    BM_CHECK(h->pt.M > 0, "bm_rbm_groups_pt_read: no ensemble (call bm_rbm_groups_pt_init first)");
+    BM_CHECK(V_dev || !H_dev, "bm_rbm_groups_pt_read: H_dev without V_dev");
+    float *const dst[3] = {V_dev, H_dev, nullptr};
+    const int ldd[3] = {h->V, h->H, 0};
+    pt_launch_gather(h->pt, h->stream, h->pt.M, dst, ldd);
+    return pt_read_host(h->pt, h->stream, swaps_host, ladder_idx_host);
+}
+
+// bm_rbm_train_step_pt for a handle with visible groups: the same seven steps (a handle with visible groups has no dropout, no
+// fast weights and no centering: bm_rbm_set_visible_groups).  No host synchronisation.
+int bm_rbm_groups_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
+    BM_TRY(check_groups_pt(h, "bm_rbm_groups_train_step_pt"));
+    BM_CHECK(X_dev, "null argument");
+    BM_TRY(check_dw(h, "bm_rbm_groups_train_step_pt"));
+    BM_CHECK(h->pt.M > 0, "bm_rbm_groups_train_step_pt: no ensemble (call bm_rbm_groups_pt_init first)");
+    const int Bmax = std::min(h->maxB, h->pt.M);
+    BM_CHECK(B >= 1 && B <= Bmax, "bm_rbm_groups_train_step_pt: batch %d outside [1, min(max_batch=%d, n_chains=%d)]", (int)B, h->maxB, h->pt.M);
+    BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
+    static const bool sel_env = !dbg("pt_sel") || atoi(dbg("pt_sel")) != 0;          // BM355_DEBUG=pt_sel=0: a gather launch instead
+    const bool sel_in_pass = sel_env && groups_fused(h);                             // (the generic route always gathers)
+    ensure_wt(h);
+    // 1. the v.vb partials of the swap energy under the vb of NOW (the previous update changed it)
+    pt_launch_rescore(h->pt, h->stream, h->vb.p, nullptr);
+    // 2. positive phase: the h0 means alone
+    h->Xin = X_dev; h->Xin_ld = h->V;
+    h->fe_in_chain = false;
+    issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, rbm_out(h, 0, h->h0m.p, nullptr, h->h0m.ld, SITE_H0, 0)));
+    // 3. + 4. the tempered steps; the beta = 1 rows of the chains [0, B) go to vs
+    for (int t = 0; t < k; ++t) groups_pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
+    if (!sel_in_pass) {
+        float *const dst[3] = {h->vs.p, nullptr, nullptr};
+        const int ldd[3] = {h->vs.ld, 0, 0};
+        pt_launch_gather(h->pt, h->stream, B, dst, ldd);
+    }
+    // 5. negative means: only -h is consumed (run_chain's neg_only form)
+    issue(h, rbm_pass(h, true, B, in_of(h->vs), rbm_out(h, 0, nullptr, nullptr, h->hm.ld, SITE_H, 0)).negmeans_out(h->hneg.p));
+    h->hm_is_neg = true;
+    // 6. + 7.
+    launch_update_fused(h, B, lr, mom);
+    h->pt.step += k;
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// the native batch loop of bm_rbm_groups_train_step_pt
+int bm_rbm_groups_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t k) {
+    BM_TRY(check_groups_pt(h, "bm_rbm_groups_train_epoch_pt"));
+    BM_CHECK(X_dev, "null argument");
+    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
+    for (int64_t s = 0; s < N; s += batch) {
+        const int B = (int)((N - s < batch) ? (N - s) : batch);
+        BM_TRY(bm_rbm_groups_train_step_pt(h, X_dev + (size_t)s * h->V, B, lr, mom, k));
     }
     return 0;
 }

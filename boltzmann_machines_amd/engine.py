@@ -61,6 +61,50 @@ class _PtCalls(object):
         return swaps, idx
 
 
+class RbmGroupsPt(_PtCalls):
+    """The tempered ensemble of an RbmEngine with visible groups (bm355.h: bm_rbm_groups_pt_* / _train_step_pt / _train_epoch_pt;
+    DESIGN.md 3.29): pt_init / pt_sweep / pt_read and the two tempered updates under the prefix 'bm_rbm_groups', on the engine's
+    handle.  Every other attribute is the engine's, so that the tempered sampler and the tempered epoch of tempering.py / rbm.py
+    run on it as they run on an engine."""
+    _pt_prefix, _pt_n_hidden = 'bm_rbm_groups', 1
+
+    def __init__(self, engine):
+        self._engine = engine
+        self.lib, self.V = engine.lib, engine.V
+
+    @property
+    def _h(self):
+        return self._engine._h
+
+    def __getattr__(self, name):                  # (only what this object does not define itself)
+        if name == '_engine':
+            raise AttributeError(name)
+        return getattr(self._engine, name)
+
+    def pt_state(self):
+        """the whole ensemble as NumPy arrays (tests, tools): v [M R, V], h [M R, H], part_v [ceil(V/16), M R], part_h
+        [ceil(H/16), M R], mult [M R], idx [M R] int32, swaps [2, R - 1] int64 (bm_rbm_get_param 'pt_*' and pt_read); waits for
+        the device"""
+        M, R = self._pt_shape
+        rows, eng = M * R, self._engine
+        shapes = dict(v=(rows, eng.V), h=(rows, eng.H), part_v=((eng.V + 15) // 16, rows), part_h=((eng.H + 15) // 16, rows), mult=(rows,))
+        out = {}
+        for name, shape in shapes.items():
+            a = np.empty(shape, dtype=np.float32)
+            check(self.lib.bm_rbm_get_param(self._h, ('pt_' + name).encode(), a.ctypes.data_as(C.c_void_p), a.size))
+            out[name] = a
+        swaps, idx = self.pt_read()
+        out.update(idx=idx.reshape(-1), swaps=swaps)
+        return out
+
+    def train_step_pt(self, Xd, B, lr, momentum, k, row=0):
+        check(self.lib.bm_rbm_groups_train_step_pt(self._h, Xd.offset_ptr(row * self.V), B, lr, momentum, k))
+
+    def train_epoch_pt(self, Xd, N, batch, lr, momentum, k, row=0):
+        """N rows starting at `row`, consecutive batches of `batch` rows, one tempered update each, driven from C"""
+        check(self.lib.bm_rbm_groups_train_epoch_pt(self._h, Xd.offset_ptr(row * self.V), N, batch, lr, momentum, k))
+
+
 class RbmEngine(_PtCalls):
     dtype = np.float32
     _pt_prefix, _pt_n_hidden = 'bm_rbm', 1
@@ -286,6 +330,14 @@ class RbmEngine(_PtCalls):
                                          o.ctypes.data_as(C.c_void_p) if o is not None else None, int(seed), int(chain0),
                                          out.ctypes.data_as(C.c_void_p)))
         return out
+
+    @property
+    def groups_pt(self):
+        """the tempered ensemble of a handle with visible groups and its calls (RbmGroupsPt), one object per engine"""
+        view = self.__dict__.get('_groups_pt')
+        if view is None:
+            view = self.__dict__['_groups_pt'] = RbmGroupsPt(self)
+        return view
 
     def rsm_ais(self, n_betas, lengths, k, seed, chain0=0, base_logits=None):
         """[len(lengths)] float32 per-chain AIS estimates of log Z_D of a handle with replicated softmax visible units, chain r

@@ -21,7 +21,7 @@ from .base import EngineModel, is_attribute_name, run_on_engine
 from .centering import CenteredTraining
 from .classification import ClassHead
 from .engine import RbmEngine, RbmEngine64
-from .tempering import TemperedNegativePhase, resolve_ladder, run_tempered_sampler
+from .tempering import TemperedNegativePhase, acceptance_rates, resolve_ladder, run_tempered_sampler
 from .utils import epoch_iter, make_list_from, write_during_training
 from .utils import log_sum_exp, log_mean_exp, log_diff_exp, log_std_exp
 from .utils import philox
@@ -1387,6 +1387,83 @@ class SoftmaxVisible(object):
         finally:
             eng.set_row_offset(0)
         return Vd.numpy()
+
+    # ---- parallel tempering and the tempered negative phase
+    def sample_v_tempered(self, n_samples, n_gibbs_steps=1000, n_temperatures=10, betas=None, V_init=None, return_stats=False):
+        """Unconditional samples of the visible units by parallel tempering (replica exchange), as `BernoulliRBM.sample_v`:
+        `n_samples` independent chains, each with one replica per temperature of the ladder 0 < betas[0] < ... < betas[-1] = 1,
+        run `n_gibbs_steps` steps of (h ~ p_beta(h|v), exchange of neighbouring temperatures, v_g ~ softmax(beta (hW^T + vb)_g)
+        per group); the replica at beta = 1 of every chain is returned as one-hot rows [n_samples, n_visible].  The hot replicas
+        cross between modes the single-temperature `sample_v` stays in.
+
+        betas : the ladder; None: float32(linspace(0, 1, n_temperatures + 1)[1:]).  `n_temperatures=1` is plain Gibbs.
+        V_init : [n_samples, n_visible] complete one-hot start of every chain (all its replicas); None: uniform categories
+        drawn on the device under the call's seed.
+        With `return_stats` also the acceptance rate of every neighbouring pair of temperatures, [n_temperatures - 1].
+        Both layers are always sampled; `missing_values` does not apply (every row of the ensemble is complete).  One seed is
+        drawn from the model's host stream; no parameter is changed.  It replaces the ensemble of `set_group_tempering`, which
+        the next `fit` builds again."""
+        n_samples, n_gibbs_steps = int(n_samples), int(n_gibbs_steps)
+        if n_samples < 1 or n_gibbs_steps < 1:
+            raise ValueError('`n_samples` and `n_gibbs_steps` must be >= 1 (got {0}, {1})'.format(n_samples, n_gibbs_steps))
+        ladder = resolve_ladder(n_temperatures, betas)
+        if V_init is not None:
+            V_init = np.ascontiguousarray(V_init, dtype=np.float32)
+            if V_init.shape != (n_samples, self.n_visible):
+                raise ValueError('`V_init` has invalid shape {0}: expected [{1}, {2}]'.format(V_init.shape, n_samples, self.n_visible))
+            _, observed = self._groups_of(V_init, 'sample_v_tempered')
+            if not observed.all():
+                b, g = np.argwhere(~observed)[0]
+                raise ValueError('%s.sample_v_tempered: group %d of row %d of `V_init` is empty (the rows of a tempered ensemble '
+                                 'are complete one-hot rows)' % (self.__class__.__name__, g, b))
+        return self._sample_v_tempered_checked(n_samples, n_gibbs_steps, ladder, V_init, return_stats)
+
+    @run_on_engine(update_seed=True)
+    def _sample_v_tempered_checked(self, n_samples, n_gibbs_steps, ladder, V_init, return_stats):
+        eng = self._on_device()
+        try:
+            eng.groups_set_missing(False)             # (the ensemble's rows are complete whatever `missing_values` says)
+            return run_tempered_sampler(eng.groups_pt, n_samples, n_gibbs_steps, ladder, V_init, self.n_visible, return_stats)
+        finally:
+            eng.groups_set_missing(bool(self.missing_values))
+
+    def _check_tempered_setting(self, what):
+        if self.missing_values:
+            self._softmax_refuse(what, 'a tempered negative phase with missing_values=True (a row of the tempered ensemble has no '
+                                       'pattern of observed groups) is not built')
+        return super(SoftmaxVisible, self)._check_tempered_setting(what)
+
+    def set_group_tempering(self, enabled=True, n_temperatures=10, betas=None, n_chains=None):
+        """Where the negative particles of `fit` come from: `enabled=True` - the beta = 1 replicas of a persistent tempered
+        ensemble of `n_chains` chains (None: `batch_size`; at least `batch_size`) over the ladder `betas` (None:
+        float32(linspace(0, 1, n_temperatures + 1)[1:])), every update sweeping all of it for `n_gibbs_steps` tempered steps -
+        `BernoulliRBM.set_negative_phase('tempered')` with the softmax prop-down of `sample_v_tempered`; `enabled=False` - CD-k
+        from the batch again.  The ensemble starts at uniform categories at the first update of every `fit()` call and again
+        whenever the ladder or `n_chains` changed; `tempering_stats()` reports its swap acceptance.  Neither the ensemble nor
+        this setting is written to checkpoints.  Refused with `missing_values=True` (ValueError, before the engine is touched),
+        and wherever `BernoulliRBM.set_negative_phase('tempered')` is (BM355_DATA_PARALLEL).  `set_negative_phase('tempered')`
+        itself stays refused for this class.  Returns self."""
+        self._fast_weights = None
+        if not enabled:
+            self._neg_phase = None
+            return self
+        self._check_tempered_setting('set_group_tempering')
+        self._set_negative_phase('tempered', n_temperatures, betas, n_chains)
+        return self
+
+    def _train_epoch_tempered(self, eng, *args, **kwargs):
+        # (the ensemble and its updates live under the engine's groups prefix; everything else the epoch calls is the engine's)
+        return super(SoftmaxVisible, self)._train_epoch_tempered(eng.groups_pt, *args, **kwargs)
+
+    def tempering_stats(self):
+        """Acceptance rate (accepts / attempts) of every neighbouring pair of temperatures, [n_temperatures - 1], since the
+        ensemble of `set_group_tempering` was built.  Waits for the device; copies no states."""
+        eng = self._engine
+        view = eng.groups_pt if eng is not None and hasattr(eng, 'groups_pt') else None
+        if view is None or getattr(view, '_pt_train_key', None) is None:
+            raise RuntimeError('`tempering_stats`: no tempered ensemble (call set_group_tempering() and fit first)')
+        swaps, _ = view.pt_read()
+        return acceptance_rates(swaps)
 
 
 class CategoricalRBM(SoftmaxVisible, BaseRBM):

@@ -98,6 +98,8 @@ int bm_rbm_set_param(bm_rbm *h, const char *name, const float *host, size_t n);
 /* the same from DEVICE memory (dense, row-major), asynchronously on the handle's stream - no host synchronisation
  * (re-initialising between runs, `init_from` another handle: base_rbm.py:668-685 without a host round trip) */
 int bm_rbm_set_param_dev(bm_rbm *h, const char *name, const float *src_dev, size_t n);
+/* get only, while the handle holds a tempered ensemble of M chains x R replicas (tests and tools; dense): "pt_v" [M R * V],
+ * "pt_h" [M R * H], the slot partials "pt_part_v" [ceil(V/16) * M R] and "pt_part_h" [ceil(H/16) * M R], "pt_mult" [M R] */
 int bm_rbm_get_param(bm_rbm *h, const char *name, float *host, size_t n);
 /* device pointer of a variable / workspace for zero-copy interop (RCCL):
  * the variables above plus "grad" (fused [V*H + V + H + H] raw-sum buffer). */
@@ -266,6 +268,31 @@ int bm_rbm_groups_scores(bm_rbm *h, const float *X_dev, int32_t B, double *score
  * does not bound the number of chains. */
 int bm_rbm_groups_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t n_gibbs_steps, const float *base_bias_host,
                       const uint8_t *observed_host, uint64_t seed, int64_t chain0, float *values_host);
+/* Parallel tempering and the tempered negative phase over softmax visible units: bm_rbm_pt_init / _sweep / _read
+ * and bm_rbm_train_step_pt / _train_epoch_pt for a handle with visible groups, under names of their own (those entries keep
+ * refusing such a handle).  The contracts are theirs - the ensemble, its chain-major rows, the ladder checks, the swap step, the
+ * counters, the seven steps of an update, the call counter (once per sweep or update) and the step parity (continued across calls),
+ * chain0 and the chain-slice property, BM355_DEBUG=pt_sel=0 - with these differences:
+ *   start      v_0 is one uniform category per group: the softmax-group rule with zero logits (e = 1, c[k] = k + 1, the first k with
+ *              c[k] > u K), u the uniform at flat index ((chain0 + c) R + r) V + g K of site 11; with V0_dev [n_chains, n_visible]
+ *              (complete one-hot rows: the caller's guarantee) every chain's R replicas start from its row.
+ *   prop-down  v_g ~ softmax_k(l_{gK..gK+K-1}) with the logits l = fl(fl(beta_row z) + fl(beta_row vb)), z = h W^T: two rounded
+ *              multiplies and one rounded add, never an FMA, so that beta_row = 1 is the plain softmax pass bit for bit; means, draw
+ *              and Philox index are those of bm_rbm_set_visible_groups (site SITE_V + 16 t, the group's first unit).  One launch (the
+ *              SM + SA + RT flavour of act_kernel) for groups of 2, 4, 8 or 16 in a layer of n_visible % 4 == 0, a raw pass, a groups
+ *              kernel and a row-dot kernel for every other shape (BM355_DEBUG=sm_fused=0 forces the latter): the same bits.
+ *   prop-up, swap   unchanged: for one-hot v the Bernoulli hidden conditional and E = -v.vb - h.hb - vWh are this model's.
+ * An update takes its negative particles from the beta = 1 rows of the chains [0, B) - in the last prop-down's epilogue on the
+ * one-launch route, by a gather launch on the other - and ends in the fused update of bm_rbm_train_step.
+ * Refused, the handle staying usable: a handle without visible groups (the message of the entries above), a handle with
+ * bm_rbm_groups_set_missing on (an ensemble row has no pattern of observed groups: not built), sweep / read / update before init,
+ * B outside [1, min(max_batch, n_chains)], n_steps or n_gibbs_steps < 1, a bad ladder.  bm_rbm_set_visible_groups(h, 0) discards
+ * the ensemble.  bm_rbm_train_step, bm_rbm_groups_ais and every other entry neither read nor write it.  Float32, one process. */
+int bm_rbm_groups_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0);
+int bm_rbm_groups_pt_sweep(bm_rbm *h, int32_t n_steps);
+int bm_rbm_groups_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host);
+int bm_rbm_groups_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t n_gibbs_steps);
+int bm_rbm_groups_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t n_gibbs_steps);
 /* AIS estimates of the log partition functions of an RBM with replicated softmax visible units.  The partition
  * function depends on the document length, Z_D = sum_h exp(D h.hb) (sum_i exp(vb_i + (W h)_i))^D, so every chain has a length of
  * its own: row r is ONE chain over count vectors of lengths_host[r] tokens, an integer in [1, max_length]; chains of different
