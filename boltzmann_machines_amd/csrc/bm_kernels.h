@@ -177,8 +177,19 @@ struct ActArgs {
     // two-beta slot partials softplus_hw(__fmul_rn(beta_b, t)) - softplus_hw(__fmul_rn(beta_a, t)) of the same t.  beta == 1 is the
     // untempered pass bit for bit (1 * t == t).
     const float *row_bmult;
+    // Parallel tempering over Gaussian visible units (the GT flavour on top of RT, act_kernel<..., RT = true, GT = true>;
+    // FL_RT | FL_GT): a single-segment prop-down from W itself whose row j holds ladder index gt_idx[j] and draws
+    //   m = __fadd_rn(z, bias[i]),   s = __fadd_rn(m, __fmul_rn(n, gt_sd[gt_idx[j]]))          - every step rounded once
+    // with n the standard normal draw of the output's flat index on the pass's key (the Gaussian layer's word-to-draw mapping): the
+    // temperature scales the VARIANCE of a tempered Gaussian conditional, not its mean - mult, bmult and row_mult multiply nothing.
+    // The pass always samples, stores its states and leaves in rowdot_out the slot partials of -1/2 (s - bias)^2, from the lane's
+    // registers: d = __fsub_rn(s, bias[i]), term __fmul_rn(__fmul_rn(-0.5f, d), d), quads left to right, then (q0 + q1) + (q2 + q3).
+    // gt_sd [R]: the ladder's standard deviations, float32(1 / sqrt(double(beta_r))), exactly 1 at beta = 1.  Asked for by name
+    // (launch_act_gauss_pt), never a route of launch_act.  Null gt_sd: off.
+    const float *gt_sd;
+    const int *gt_idx;
 #ifdef BM_PROBE
-    long long *dbg;              // [grid][4] s_memtime stamps (tools/probe_act.hip only)
+    long long *dbg;             // [grid][4] s_memtime stamps (tools/probe_act.hip only)
 #endif
 };
 #ifdef BM_PROBE
@@ -427,7 +438,8 @@ template <int E, class Rng, bool MF = false, int NTH = 256> struct ActSide {
 // partial sums.  Returns the lane's mean-field residual max|m - prev| (0 without a.prev).  A function so that the
 // persistent fast-binary kernel (act_bf3_kernel) can call it once per tile of its strip.
 template <class G, int ABL, class SideT, bool HWMATH = false, bool FE = false, bool LIT = false, bool CL = false, bool RT = false,
-          bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false, bool SA = false, bool DB = false>
+          bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false, bool SA = false, bool DB = false,
+          bool GT = false>
 __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey &key, const f32x4 (&acc)[G::MI][1], const SideT &side,
                                               int i0, int j0) {
     constexpr int E = G::E, NH = G::MI;            // NH = Philox blocks (groups of 4 outputs) per lane
@@ -480,6 +492,14 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
     float dbm = 1.f;
     (void)dbm;
     if constexpr (DB) dbm = (j < a.J) ? a.row_bmult[j] : 0.f;
+    // GT: the standard deviation of the row's temperature, requested at epilogue entry like the row's temperature of RT (two dependent
+    // scalars per lane); gt_q keeps the quad's -1/2 (s - c)^2 for the slot partials
+    float gsd = 0.f, gt_q = 0.f;
+    (void)gsd; (void)gt_q;
+    if constexpr (GT) {
+        static_assert(RT && G::MI == 1, "the GT flavour sits on top of the RT flavour, on the geometries with one quad per lane");
+        gsd = (j < a.J) ? a.gt_sd[a.gt_idx[j]] : 0.f;
+    }
     // CB: the row's class and the lane's quads of U[y_j], requested at epilogue entry like the clamp arrays (one 16-byte load per
     // group of 4 where pitch and base allow it); a label outside [0, cb_C) loads nothing and raises the flag (every lane that
     // sees it stores the same 1)
@@ -585,6 +605,11 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                     s[r] = m[r];
                     continue;
                 }
+                if constexpr (GT) {            // m = z + c, one rounded add: the temperature does not scale the mean
+                    m[r] = __fadd_rn(z[4 * hlf + r], bs[4 * hlf + r]);
+                    s[r] = m[r];
+                    continue;
+                }
                 const float x = (RT ? rm : a.mult) * z[4 * hlf + r];
                 float bv = bs[4 * hlf + r];
                 if constexpr (CB) { if (cb_ok) bv = __fadd_rn(bv, cu[hlf][r]); }       // b' = b + U[y_j][i], one rounded add
@@ -660,7 +685,18 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                 }
             }
             if (!BP && !SM && a.sample) {
-                if constexpr (NR) {      // one normal per output: the lane's Philox block, or per element where I % 4 != 0
+                if constexpr (GT) {      // one normal per output, as NR draws it; s = m + n sd, two rounded steps
+                    float n[4];
+                    if (rng_fast) {
+                        const uint32_t *wds = rng.words(hlf);
+                        box_muller(wds[0], wds[1], n[0], n[1]);
+                        box_muller(wds[2], wds[3], n[2], n[3]);
+                    } else {
+                        nrelu_normals(key, (unsigned long long)(a.row0 + j) * (unsigned long long)a.I + ib, nvalid, n);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s[r] = __fadd_rn(m[r], __fmul_rn(n[r], gsd));
+                } else if constexpr (NR) {      // one normal per output: the lane's Philox block, or per element where I % 4 != 0
                     float n[4];
                     if (rng_fast) {
                         const uint32_t *wds = rng.words(hlf);
@@ -701,6 +737,16 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                     qd += s[r] * sdv[r];
                 }
                 sa_q = qd;
+            }
+            if constexpr (GT) {                // the quad's -1/2 (s - c)^2 from the registers, left to right
+                float qd = 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (r >= nvalid) break;
+                    const float d = __fsub_rn(s[r], bs[4 * hlf + r]);
+                    qd = __fadd_rn(qd, __fmul_rn(__fmul_rn(-0.5f, d), d));
+                }
+                gt_q = qd;
             }
             if constexpr (RT) {
 #pragma unroll
@@ -759,6 +805,14 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
         rdot += __shfl_xor(rdot, 32);
         const int slot = (i0 + wi * 16) / 16;
         if (g == 0 && j < a.J && slot * 16 < a.I) a.rowdot_out[(size_t)slot * a.ld_part + j] = rdot;
+    }
+    if constexpr (GT) {                       // the slot partials of -1/2 (s - c)^2: (q0+q1)+(q2+q3), lanes g = 0..3, where rowdot_out goes
+        row_sums = false;
+        float rsq = gt_q;
+        rsq = __fadd_rn(rsq, __shfl_xor(rsq, 16));
+        rsq = __fadd_rn(rsq, __shfl_xor(rsq, 32));
+        const int slot = (i0 + wi * 16) / 16;
+        if (g == 0 && j < a.J && slot * 16 < a.I) a.rowdot_out[(size_t)slot * a.ld_part + j] = rsq;
     }
     if (row_sums) {                           // wave-uniform
         // per-lane quads (4 consecutive i, left to right); MI == 2: the lane's two quads are added
@@ -852,7 +906,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
 // geometries that equals the workgroups per CU; an 8-wave workgroup that should run twice per CU passes 4)
 template <class G, int MINB, bool SEG2, bool FAST, int ABL = 0, int PL = KM, int STG = STG_DMA, bool FE = false, bool LIT = false, bool MF = false,
           bool CL = false, bool RT = false, bool CR = false, bool CB = false, bool BP = false, bool NR = false, bool SM = false, bool SA = false,
-          bool DB = false>
+          bool DB = false, bool GT = false>
 BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap) {
     // (the block -> tile map is an argument of its own: the grid path indexes it with blockIdx & 7, and a dynamically
     //  indexed member made hipcc fetch EVERY ActArgs field lazily in small pieces - 50 scalar loads with their waits
@@ -928,7 +982,7 @@ BM_KERNEL __launch_bounds__(G::NT, MINB) void act_kernel(ActArgs a, TileMap tmap
 #endif
     BM_STAMP(1);
     if constexpr (MF) { if (side.aborted) return; }          // the loop had ended: nothing is written
-    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP, NR, SM, SA, DB>(a, key, acc, side, i0, j0);
+    float dmax = act_epilogue<G, ABL, decltype(side), false, FE, LIT, CL, RT, CR, CB, BP, NR, SM, SA, DB, GT>(a, key, acc, side, i0, j0);
     if (MF && a.maxdiff) {     // wave-uniform.  ONE atomic per workgroup: thousands of same-address atomics
                                // (one per wave) serialise in the L2 and doubled the duration of the sweep kernels
         __shared__ float s_wavemax[G::NT / 64];

@@ -40,6 +40,9 @@
 //        calling launch_act_sm_clamped, which runs the kernels of bm_softmax_cl.hip - the CL block behind the SM block
 //        SM + SA is the other flavour asked for by name (launch_act_sm_ais; bm_softmax_ais.hip): the softmax-group pass of the AIS over
 //        softmax visible units - free mult / bmult, absent groups held at zero, state . dot_vec from registers
+//        RT + GT is asked for by name as well (launch_act_gauss_pt; bm_gauss.hip): the prop-down of parallel tempering over Gaussian
+//        visible units - the row's temperature scales the variance of the draw, not the mean, and the slot partials
+//        of -1/2 (s - bias)^2 come from registers
 //        CR to SM take mult == bmult == 1 (BP: mult) and one K segment.  The instantiations of CL and RT live in bm355.hip, those of
 //        the other five in translation units of their own (ActFlavour::as) so that the kernels of every other unit are compiled
 //        exactly as before; BP and SM have the x-major kernels only (launch_act_xm_as)
@@ -163,15 +166,15 @@ template <class Args, class F> static inline int tune_tile_map(TuneTimer &tm, Ar
 static inline bool tune_log() { static const bool on = dbg("tune_log") != nullptr; return on; }
 
 // ---- act_kernel: one dispatcher for every flavour
-enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512, FL_NR = 1024, FL_SM = 2048, FL_SA = 4096, FL_DB = 8192 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
+enum : unsigned { FL_FE = 1, FL_LIT = 2, FL_MF = 4, FL_XM = 8, FL_SEG2 = 16, FL_CL = 32, FL_RT = 64, FL_CR = 128, FL_CB = 256, FL_BP = 512, FL_NR = 1024, FL_SM = 2048, FL_SA = 4096, FL_DB = 8192, FL_GT = 16384 };      // FL_XM / FL_SEG2: the flavour HAS x-major P / two-segment kernels
 template <class G, int MINB, int STG, unsigned FL, bool SEG2, int PL>
 static inline void launch_act_kernel(bool fast, unsigned dyn_lds, hipStream_t st, const ActArgs &a, const TileMap &tmap) {
     const dim3 grid(tile_grid<G>(a.I, a.J)), blk(G::NT);
     constexpr bool FE = (FL & FL_FE) != 0, LIT = (FL & FL_LIT) != 0, MF = (FL & FL_MF) != 0, CL = (FL & FL_CL) != 0,
                    RT = (FL & FL_RT) != 0, CR = (FL & FL_CR) != 0, CB = (FL & FL_CB) != 0, BP = (FL & FL_BP) != 0, NR = (FL & FL_NR) != 0,
-                   SM = (FL & FL_SM) != 0, SA = (FL & FL_SA) != 0, DB = (FL & FL_DB) != 0;
-    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA, DB>), grid, blk, dyn_lds, st, a, tmap);
-    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA, DB>), grid, blk, dyn_lds, st, a, tmap);
+                   SM = (FL & FL_SM) != 0, SA = (FL & FL_SA) != 0, DB = (FL & FL_DB) != 0, GT = (FL & FL_GT) != 0;
+    if (fast) hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, true, 0, PL, STG, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA, DB, GT>), grid, blk, dyn_lds, st, a, tmap);
+    else      hipLaunchKernelGGL((act_kernel<G, MINB, SEG2, false, 0, PL, STG_DMA, FE, LIT, MF, CL, RT, CR, CB, BP, NR, SM, SA, DB, GT>), grid, blk, dyn_lds, st, a, tmap);
 }
 template <class G, int MINB, int STG, unsigned FL>
 static inline void dispatch_act(const ActArgs &a, hipStream_t st, int map_xi, unsigned dyn_lds = 0) {
@@ -337,6 +340,24 @@ template <> struct ActFlavour<FL_SM | FL_SA | FL_RT> : ActFlavourDefaults {
         return ActFlavour<FL_SM | FL_SA>::admits(a) && !a.sm_absent && !a.rowen_out && (!a.sel_out || (a.sel_R >= 1 && a.sel_rows >= 0));
     }
     static void strip(ActArgs &p) { ActFlavour<FL_SM | FL_SA>::strip(p); ActFlavour<FL_RT>::strip(p); }
+};
+// RT + GT, the prop-down of parallel tempering over Gaussian visible units: a tempered Gaussian conditional keeps its
+// mean and changes its variance, which RT - a multiplier of z and of the bias - cannot express.  No entry of the table and asked for by
+// name (launch_act_gauss_pt; bm_gauss.hip), like SM + SA: a pass that carries gt_sd through launch_act is refused there.  The kernel
+// set is the x-major one (a prop-down from W itself); the pass samples, stores its states and leaves the slot partials of
+// -1/2 (s - bias)^2 where rowdot_out goes; no means, no hand-over of the beta = 1 rows (there is no tempered training of this model)
+void launch_act_gtpt_as(int, const ActArgs &, hipStream_t);
+template <> struct ActFlavour<FL_RT | FL_GT> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = true, geo5 = false;
+    static constexpr ActAsFn as = launch_act_gtpt_as;
+    static constexpr const char *no_kernel = "bm355: a variance-tempered Gaussian pass is a sampled single-segment prop-down from W itself that leaves -1/2 (s - bias)^2 and nothing else (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.gt_sd != nullptr; }
+    static bool admits(const ActArgs &a) {
+        return a.kind == 3 && a.p_xm && a.K2 == 0 && a.sample && a.states && !a.means && !a.negmeans && !a.rowacc && !a.rowen_out && !a.sel_out &&
+               a.rowdot_out && a.ld_part >= a.J && a.row_mult && a.gt_idx && a.bias;
+    }
+    // (the Bernoulli prop-down of the shape: the same contraction, a draw per output; the plain row dots would read dot_vec)
+    static void strip(ActArgs &p) { ActFlavour<FL_RT>::strip(p); p.gt_sd = nullptr; p.gt_idx = nullptr; p.kind = 0; p.rowdot_out = nullptr; p.ld_part = 0; }
 };
 
 // the table's order: most specific first.  first(f): f(std::integral_constant<unsigned, FL>) for each flavour until one returns true
@@ -620,7 +641,14 @@ static inline void launch_act_sm_pt(const ActArgs &a, hipStream_t st) {
     if (!F::selects(a) || (act_features(a) & ~(FL_SM | FL_RT)) != 0 || !F::admits(a)) { fputs(F::no_kernel, stderr); abort(); }
     launch_act_flavoured<FL_SM | FL_SA | FL_RT>(a, st);
 }
+// a variance-tempered Gaussian pass (ActFlavour<FL_RT | FL_GT>): the caller's explicit choice, not a route of launch_act
+static inline void launch_act_gauss_pt(const ActArgs &a, hipStream_t st) {
+    using F = ActFlavour<FL_RT | FL_GT>;
+    if (!F::selects(a) || (act_features(a) & ~FL_RT) != 0 || !F::admits(a)) { fputs(F::no_kernel, stderr); abort(); }
+    launch_act_flavoured<FL_RT | FL_GT>(a, st);
+}
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
+    if (a.gt_sd) { fputs("bm355: a variance-tempered Gaussian pass is asked for by name, launch_act_gauss_pt (no such route)\n", stderr); abort(); }
     if (a.sm_ais) { fputs("bm355: a tempered softmax-group pass (AIS) is asked for by name, launch_act_sm_ais (no such route)\n", stderr); abort(); }
     const ActRoute r = act_route(a);
     if (r.refusal) { fputs(r.refusal, stderr); abort(); }

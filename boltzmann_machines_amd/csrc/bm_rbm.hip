@@ -19,6 +19,7 @@
 #include "bm_rsm.h"
 #include "bm_softmax_ais.h"
 #include "bm_softmax_pt.h"
+#include "bm_gauss.h"
 
 #include <math.h>
 #include <atomic>
@@ -165,6 +166,21 @@ struct bm_rbm {
     // allocated with the ensemble; nothing else reads or writes it
     int gp_rows = 0;
     Mat gp_z;
+    // Gaussian visible units as one joint model over u = x / sigma (bm_rbm_gauss_*; bm_gauss.h), allocated at the
+    // first such call; nothing else in the handle reads or writes them.  gc / gones: the centre c = vb / sigma and a vector of ones
+    // [V], formed again by every call (the parameters may have moved).  gfe_*: the scaled rows [gfe_rows][V], the softplus slot
+    // partials [ceil(H/16)][gfe_rows] and F [gfe_rows] of bm_rbm_gauss_free_energy_rows.  gpt: the tempered ensemble of
+    // bm_rbm_gauss_pt_* - an ensemble of its own, bm_rbm_pt_* never see it - with the ladder's standard deviations gpt_sd [R] and,
+    // the generic route only, the raw z = h W^T [gpt_zrows][V] of its prop-down
+    DevBuf gc, gones;
+    int gfe_rows = 0;
+    Mat gfe_u;
+    DevBuf gfe_part;
+    DevArray<double> gfe_out;
+    PtEnsemble gpt;
+    DevBuf gpt_sd;
+    int gpt_zrows = 0;
+    Mat gpt_z;
     int fer_rows = 0;
     DevBuf fer_part, fer_out;          // bm_rbm_free_energy_rows: slot partials [ceil(H/16)][fer_rows] of sum softplus, F [fer_rows]
     // fast-binary mode (bm_bf3.h, bm_rbm_set_fast_binary): bf16 planes of W ([V][H]: the prop-down operand) and of
@@ -1218,9 +1234,10 @@ int bm_rbm_set_param_dev(bm_rbm *h, const char *name, const float *src_dev, size
 
 // The whole tempered ensemble, read only, dense (tests and tools; bm_rbm_pt_read / bm_rbm_groups_pt_read hand out the beta = 1 rows):
 // "pt_v" [M R][V], "pt_h" [M R][H], "pt_part_v" [ceil(V/16)][M R], "pt_part_h" [ceil(H/16)][M R], "pt_mult" [M R]
-static int pt_get_param(bm_rbm *h, const std::string &nm, float *host, size_t n) {
-    PtEnsemble &e = h->pt;
-    BM_CHECK(e.M > 0, "variable '%s': no ensemble (bm_rbm_pt_init / bm_rbm_groups_pt_init)", nm.c_str());
+// ("gpt_*": the same five of the ensemble of bm_rbm_gauss_pt_*, v in the scaled variable u, part_v the slots of -1/2 (u - c)^2)
+static int pt_get_param(bm_rbm *h, PtEnsemble &e, const std::string &full, float *host, size_t n) {
+    const std::string nm = full[0] == 'g' ? full.substr(1) : full;
+    BM_CHECK(e.M > 0, "variable '%s': no ensemble (bm_rbm_pt_init / bm_rbm_groups_pt_init / bm_rbm_gauss_pt_init)", full.c_str());
     const size_t rows = (size_t)e.nrows();
     const float *src = nullptr;
     size_t pitch = 0, width = 0, height = 0;
@@ -1229,9 +1246,21 @@ static int pt_get_param(bm_rbm *h, const std::string &nm, float *host, size_t n)
     else if (nm == "pt_part_v") { src = e.v.part.p; pitch = e.rows; width = rows; height = nslots(h->V); }
     else if (nm == "pt_part_h") { src = e.h1.part.p; pitch = e.rows; width = rows; height = nslots(h->H); }
     else if (nm == "pt_mult")   { src = e.mult.p; pitch = rows; width = rows; height = 1; }
-    BM_CHECK(src, "unknown RBM variable '%s'", nm.c_str());
-    BM_CHECK(n == width * height, "variable '%s' has %zu elements, got %zu", nm.c_str(), width * height, n);
+    BM_CHECK(src, "unknown RBM variable '%s'", full.c_str());
+    BM_CHECK(n == width * height, "variable '%s' has %zu elements, got %zu", full.c_str(), width * height, n);
     BM_HIP(hipMemcpy2D(host, width * sizeof(float), src, pitch * sizeof(float), width * sizeof(float), height, hipMemcpyDeviceToHost));
+    return 0;
+}
+// The chain states an AIS entry left behind, read only, dense (tests): "ais_v" [rows][V], "ais_h" [rows][H], rows = n / width of the
+// first rows of the AIS workspaces
+static int ais_get_param(bm_rbm *h, const std::string &nm, float *host, size_t n) {
+    const bool v = nm == "ais_v";
+    BM_CHECK(v || nm == "ais_h", "unknown RBM variable '%s'", nm.c_str());
+    const Mat &m = v ? h->av : h->ah;
+    const size_t width = v ? h->V : h->H;
+    BM_CHECK(n >= width && n % width == 0 && n / width <= (size_t)h->ais_rows, "variable '%s': %zu elements are no whole rows of the %d "
+             "AIS chains", nm.c_str(), n, h->ais_rows);
+    BM_HIP(hipMemcpy2D(host, width * sizeof(float), m.p, (size_t)m.ld * sizeof(float), width * sizeof(float), n / width, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1239,7 +1268,9 @@ int bm_rbm_get_param(bm_rbm *h, const char *name, float *host, size_t n) {
     const std::string nm(name ? name : "");
     BM_HIP(hipStreamSynchronize(h->stream));
     BM_TRY(check_device_status(h));        // never hand out variables computed from invalid tiles / a lost rank's sums
-    if (nm.compare(0, 3, "pt_") == 0) return pt_get_param(h, nm, host, n);
+    if (nm.compare(0, 3, "pt_") == 0) return pt_get_param(h, h->pt, nm, host, n);
+    if (nm.compare(0, 4, "gpt_") == 0) return pt_get_param(h, h->gpt, nm, host, n);
+    if (nm.compare(0, 4, "ais_") == 0) return ais_get_param(h, nm, host, n);
     bool ro = false;
     Mat *fm = find_fast_mat(h, nm, &ro);
     DevBuf *fb = fm ? nullptr : find_fast_vec(h, nm, &ro);
@@ -2403,7 +2434,9 @@ int bm_rbm_class_gibbs(bm_rbm *h, const float *V_dev, const int32_t *y_dev, int3
 // workspaces for R rows exist (ensure_ais_rows)
 static int ais_run(bm_rbm *h, int n_betas, int R, int k, const float *base_bias_host, uint64_t seed, int64_t chain0, const float *lengths,
                    const float *vdot, int vdot_slots, double logZ0, const double *logZ0_rows, float *values_host,
-                   const std::function<void()> &start, const std::function<void(float, int, const PhiloxKey &, bool)> &down) {
+                   const std::function<void()> &start, const std::function<void(float, int, const PhiloxKey &, bool)> &down,
+                   const float *vb_dev = nullptr) {
+    // vb_dev: the device vector that stands where vb stands in dvec and in the table (bm_rbm_gauss_ais: the centre c); null: vb itself
     const int V = h->V, H = h->H;
     if (!h->abase.p) { BM_TRY(h->adot.alloc(V)); BM_TRY(h->abase.alloc(V)); }
     if (h->atable.n < (size_t)n_betas * V) { BM_TRY(h->abeta.alloc(n_betas)); BM_TRY(h->atable.alloc((size_t)n_betas * V)); }
@@ -2417,7 +2450,7 @@ static int ais_run(bm_rbm *h, int n_betas, int R, int k, const float *base_bias_
     if (base_bias_host) BM_HIP(hipMemcpy(h->abase.p, base_bias_host, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
     else BM_HIP(hipMemset(h->abase.p, 0, (size_t)V * sizeof(float)));
     ensure_wt(h);
-    hipLaunchKernelGGL(rbm_ais_prep_kernel, dim3(512), dim3(256), 0, h->stream, (const float *)h->vb.p, (const float *)h->abase.p,
+    hipLaunchKernelGGL(rbm_ais_prep_kernel, dim3(512), dim3(256), 0, h->stream, vb_dev ? vb_dev : (const float *)h->vb.p, (const float *)h->abase.p,
                        (const float *)h->abeta.p, (int)n_betas, V, h->adot.p, h->atable.p);
     BM_HIP(hipMemsetAsync(h->alogw.p, 0, (size_t)R * sizeof(double), h->stream));
     const int ldp = h->ais_rows;
@@ -3024,6 +3057,193 @@ int bm_rbm_groups_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32
         BM_TRY(bm_rbm_groups_train_step_pt(h, X_dev + (size_t)s * h->V, B, lr, mom, k));
     }
     return 0;
+}
+
+// ---- Gaussian visible units as one joint model (bm355.h: bm_rbm_gauss_ais, bm_rbm_gauss_free_energy_rows, bm_rbm_gauss_pt_*;
+// bm_gauss.h).  Everything runs on u = x / sigma with unit variance and the centre c = vb / sigma; the entries of the
+// Bernoulli model (bm_rbm_ais, bm_rbm_free_energy_rows, bm_rbm_pt_*) keep refusing a Gaussian handle.
+static int check_gauss_joint(const bm_rbm *h, const char *what) {
+    BM_CHECK(h, "%s: null argument", what);
+    BM_CHECK(h->cfg.v_unit == BM_UNIT_GAUSSIAN, "%s needs Gaussian visible units (this handle's are Bernoulli: bm_rbm_ais, "
+             "bm_rbm_free_energy_rows and bm_rbm_pt_* serve those)", what);
+    BM_CHECK(!h->nrelu(), "%s is not available for NReLU hidden units (noisy rectified-linear, BM_UNIT_NRELU): the unit has no "
+             "closed-form free energy and real-valued hidden states; see DESIGN.md 3.23", what);
+    BM_CHECK(!h->multinomial(), "%s needs Bernoulli hidden units (this handle's are Multinomial)", what);
+    BM_CHECK(!h->cfg.dbm_first && !h->cfg.dbm_last, "%s: the conditionals of a dbm_first / dbm_last handle (one of them doubled) "
+             "belong to no single joint distribution", what);
+    return 0;
+}
+// c = vb / sigma and the ones vector under the parameters of NOW, in stream order
+static int gauss_prep(bm_rbm *h) {
+    if (!h->gc.p) { BM_TRY(h->gc.alloc(h->V)); BM_TRY(h->gones.alloc(h->V)); }
+    launch_gauss_prep(h->vb.p, h->sigma.p, h->V, h->gc.p, h->gones.p, h->stream);
+    return 0;
+}
+
+// u ~ N(table_k + beta W h, I) from ah into av: the Gaussian epilogue (kind 1) with mult = beta, the mixed centre of row `kbeta` of
+// the table taken once (bmult = 1) and a UNIT sigma - the ones vector, not null: draw4's ragged path reads ActArgs::sigma itself;
+// dot: the pass leaves the slot partials of u.(c - a) in apart_v for the next score
+static void gauss_ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &key, int64_t chain0, bool dot) {
+    LayerPass p = rbm_pass(h, false, R, in_of(h->ah), LayerOut{1, nullptr, h->av.p, h->av.ld, key, chain0}, beta)
+                      .bias(h->atable.p + (size_t)kbeta * h->V, 1.0f);
+    p.a.kind = BM_UNIT_GAUSSIAN; p.a.sigma = h->gones.p;
+    if (dot) p.statedot_rows(h->apart_v.p, h->ais_rows, h->adot.p);
+    issue(h, p);
+}
+
+// bm_rbm_ais with the base model N(a, I) over u and Gaussian transitions; the host loop, the table kernel (with c in place of vb),
+// the prop-up with its softplus partials, the score kernel and the double accumulation are bm_rbm_ais's own (ais_run).  The score's
+// visible term is linear in u, (beta_k - beta_{k-1}) u.(c - a); its constant, 1/2 (|a|^2 - |c|^2) over the whole path, is part of log Z_0
+int bm_rbm_gauss_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t k, const float *base_mean_host, uint64_t seed, int64_t chain0,
+                     float *values_host) {
+    BM_TRY(check_gauss_joint(h, "bm_rbm_gauss_ais"));
+    BM_CHECK(values_host, "bm_rbm_gauss_ais: null argument");
+    BM_CHECK(n_betas >= 2 && n_runs >= 1 && k >= 1 && chain0 >= 0, "bm_rbm_gauss_ais: bad AIS arguments (n_betas %d >= 2, n_runs %d >= 1, "
+             "n_gibbs_steps %d >= 1, chain0 %lld >= 0)", (int)n_betas, (int)n_runs, (int)k, (long long)chain0);
+    const int R = n_runs, V = h->V, H = h->H;
+    BM_TRY(ensure_ais_rows(h, R));
+    BM_TRY(gauss_prep(h));
+    // log Z_0 = (V/2) log 2 pi + H log 2 + sum_i log sigma_i + 1/2 (|a|^2 - |c|^2) in double, c as the device formed it
+    std::vector<float> c(V), sg(V);
+    BM_HIP(hipMemcpyAsync(c.data(), h->gc.p, (size_t)V * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipMemcpyAsync(sg.data(), h->sigma.p, (size_t)V * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    double logZ0 = 0.5 * (double)V * log(2.0 * M_PI) + (double)H * log(2.0), half = 0.0;
+    for (int i = 0; i < V; ++i) {
+        BM_CHECK(sg[i] > 0.f, "bm_rbm_gauss_ais: sigma[%d] = %g is not positive", i, (double)sg[i]);
+        const double ai = base_mean_host ? (double)base_mean_host[i] : 0.0;
+        logZ0 += log((double)sg[i]);
+        half += ai * ai - (double)c[i] * (double)c[i];
+    }
+    logZ0 += 0.5 * half;
+    return ais_run(h, n_betas, R, k, base_mean_host, seed, chain0, nullptr, h->apart_v.p, nslots(V), logZ0, nullptr, values_host,
+                   [&] {
+                       GaStartArgs s0;
+                       memset(&s0, 0, sizeof(s0));
+                       s0.v = h->av.p; s0.ld = h->av.ld; s0.rows = R; s0.V = V; s0.abase = h->abase.p; s0.dvec = h->adot.p;
+                       s0.key = ais_key(seed, SITE_AIS_V0, 0, 0); s0.row0 = (unsigned long long)chain0;
+                       s0.part = h->apart_v.p; s0.ld_part = h->ais_rows; s0.nslot = nslots(V);
+                       launch_gauss_ais_start(s0, h->stream);
+                   },
+                   [&](float bb, int b, const PhiloxKey &key, bool dot) { gauss_ais_down(h, R, bb, b, key, chain0, dot); }, h->gc.p);
+}
+
+// Per-row free energies F(u) = 1/2 |u - c|^2 - sum_j softplus((u W + hb)_j), u = x / sigma: the division of the training chain
+// (div_cols_kernel), one prop-up that only leaves its softplus slot partials, one row kernel.  No dropout, no RNG call consumed
+int bm_rbm_gauss_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, double *out_host) {
+    BM_TRY(check_gauss_joint(h, "bm_rbm_gauss_free_energy_rows"));
+    BM_CHECK(X_dev && out_host, "bm_rbm_gauss_free_energy_rows: null argument");
+    BM_CHECK(B >= 1, "bm_rbm_gauss_free_energy_rows: bad row count %d", (int)B);
+    if (B > h->gfe_rows) {
+        h->gfe_rows = 0;
+        BM_TRY(h->gfe_u.alloc(B, h->V)); BM_TRY(h->gfe_part.alloc((size_t)nslots(h->H) * B)); BM_TRY(h->gfe_out.alloc(B));
+        h->gfe_rows = B;
+    }
+    BM_TRY(gauss_prep(h));
+    ensure_wt(h);
+    hipLaunchKernelGGL(div_cols_kernel, dim3(256), dim3(256), 0, h->stream, X_dev, h->V, (const float *)h->sigma.p, h->gfe_u.p, h->gfe_u.ld,
+                       (int)B, h->V);
+    issue(h, rbm_pass(h, true, B, in_of(h->gfe_u), LayerOut{0, nullptr, nullptr, pad_ld(h->H), PhiloxKey{0, 0, 0, 0}, 0})
+                 .softplus_rows(h->gfe_part.p, h->gfe_rows, 0.f, 1.0f, 1));
+    launch_gauss_fe_rows(h->gfe_u.p, h->gfe_u.ld, B, h->V, h->gc.p, h->gfe_part.p, h->gfe_rows, nslots(h->H), h->gfe_out.p, h->stream);
+    BM_HIP(hipGetLastError());
+    BM_HIP(hipMemcpyAsync(out_host, h->gfe_out.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// The one-launch route of the tempered prop-down (the RT + GT flavour) unless BM355_DEBUG=gt_fused=0 asks for the generic one
+static bool gauss_pt_fused() {
+    static const bool off = bm::dbg("gt_fused") && atoi(bm::dbg("gt_fused")) == 0;
+    return !off;
+}
+// Step t of a tempered call: the RT prop-up and the swap of pt_step, unchanged - h | u at beta is Ber(sigmoid(beta (u W + hb))), and
+// with part_v = the slots of -1/2 |u - c|^2 the swap's E = -(sum part_v + sum part_h1) is 1/2 |u - c|^2 - h.(u W + hb) - then the
+// prop-down u ~ N(c + W h, I / beta_row).  Fused route: ONE launch.  Generic route: a raw pass (z = h W^T, the plain kernels) and the
+// row kernel - the same bits
+static void gauss_pt_step(bm_rbm *h, int t) {
+    PtEnsemble &e = h->gpt;
+    const int rows = e.nrows();
+    issue(h, rbm_pass(h, true, rows, in_of(e.v.x), value_out(1, e.h1.x.p, e.h1.x.ld, make_key(h, SITE_H, t), e.row0()))   // (mult: not read)
+                 .energy_rows(e.h1.part.p, e.rows).row_tempered(e.mult.p));
+    pt_launch_swap(e, h->stream, t, make_key(h, SITE_PT_SWAP, t));
+    const PhiloxKey key = make_key(h, SITE_V, t);
+    LayerPass p = rbm_pass(h, false, rows, in_of(e.h1.x), value_out(1, e.v.x.p, e.v.x.ld, key, e.row0()), 1.0f);
+    ActArgs &a = p.a;
+    a.bias = h->gc.p; a.sigma = nullptr;
+    if (gauss_pt_fused()) {
+        ProfScope _ps(h, KC_DOWN);
+        a.kind = 3;
+        a.rowdot_out = e.v.part.p; a.ld_part = e.rows; a.row_mult = e.mult.p; a.gt_sd = h->gpt_sd.p; a.gt_idx = e.idx.p;
+        launch_act_gauss_pt(a, h->stream);
+        return;
+    }
+    a.kind = 2; a.sample = 0; a.states = nullptr; a.means = h->gpt_z.p; a.ldo = h->gpt_z.ld;
+    {
+        ProfScope _ps(h, KC_DOWN);
+        launch_act(a, h->stream);
+    }
+    ProfScope _ps(h, KC_OTHER);
+    GpRowsArgs g;
+    memset(&g, 0, sizeof(g));
+    g.Z = h->gpt_z.p; g.ldz = h->gpt_z.ld; g.states = e.v.x.p; g.ld_states = e.v.x.ld; g.V = h->V; g.J = rows;
+    g.c = h->gc.p; g.sd = h->gpt_sd.p; g.idx = e.idx.p; g.key = key; g.row0 = e.row0(); g.part = e.v.part.p; g.ld_part = e.rows;
+    launch_gauss_pt_rows(g, h->stream);
+}
+
+int bm_rbm_gauss_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0) {
+    BM_TRY(check_gauss_joint(h, "bm_rbm_gauss_pt_init"));
+    BM_TRY(pt_check_ladder(n_chains, n_temps, betas_host, chain0));
+    h->gpt.M = 0;
+    const int rows = n_chains * n_temps;
+    if (!gauss_pt_fused() && rows > h->gpt_zrows) {
+        h->gpt_zrows = 0;
+        BM_TRY(h->gpt_z.alloc(rows, h->V));
+        h->gpt_zrows = rows;
+    }
+    // sd[r] = float32(1 / sqrt(double(beta_r))): exactly 1 at beta = 1
+    std::vector<float> sd(n_temps);
+    for (int r = 0; r < n_temps; ++r) sd[r] = (float)(1.0 / sqrt((double)betas_host[r]));
+    if (h->gpt_sd.n < (size_t)n_temps) BM_TRY(h->gpt_sd.alloc(n_temps));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_HIP(hipMemcpy(h->gpt_sd.p, sd.data(), (size_t)n_temps * sizeof(float), hipMemcpyHostToDevice));
+    BM_TRY(gauss_prep(h));
+    const int widths[3] = {h->V, h->H, 0};
+    const PhiloxKey key = make_key(h, SITE_PT_V0, 0);
+    return pt_begin_with(h->gpt, h->stream, widths, n_chains, n_temps, chain0, betas_host, [&](PtEnsemble &e, int nrows) {
+        GpStartArgs s0;
+        memset(&s0, 0, sizeof(s0));
+        s0.v = e.v.x.p; s0.ld = e.v.x.ld; s0.rows = nrows; s0.R = n_temps; s0.V = h->V;
+        s0.V0 = V0_dev; s0.c = h->gc.p; s0.sigma = h->sigma.p; s0.beta = e.beta.p; s0.sd = h->gpt_sd.p;
+        s0.key = key; s0.row0 = (unsigned long long)chain0 * (unsigned long long)n_temps;
+        s0.part = e.v.part.p; s0.ld_part = e.rows; s0.row_mult = e.mult.p; s0.idx = e.idx.p;
+        launch_gauss_pt_init(s0, h->stream);
+    });
+}
+
+int bm_rbm_gauss_pt_sweep(bm_rbm *h, int32_t n_steps) {
+    BM_TRY(check_gauss_joint(h, "bm_rbm_gauss_pt_sweep"));
+    BM_CHECK(h->gpt.M > 0, "bm_rbm_gauss_pt_sweep: no ensemble (call bm_rbm_gauss_pt_init first)");
+    BM_CHECK(n_steps >= 1, "bm_rbm_gauss_pt_sweep: n_steps must be >= 1 (got %d)", (int)n_steps);
+    BM_CHECK(gauss_pt_fused() || h->gpt.nrows() <= h->gpt_zrows, "bm_rbm_gauss_pt_sweep: the ensemble was built for the one-launch route");
+    ensure_wt(h);
+    for (int t = 0; t < n_steps; ++t) gauss_pt_step(h, t);
+    h->gpt.step += n_steps;
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// the beta = 1 rows: the gather of bm_rbm_pt_read, then x = u sigma on the dense result
+int bm_rbm_gauss_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
+    BM_TRY(check_gauss_joint(h, "bm_rbm_gauss_pt_read"));
+    BM_CHECK(h->gpt.M > 0, "bm_rbm_gauss_pt_read: no ensemble (call bm_rbm_gauss_pt_init first)");
+    BM_CHECK(V_dev || !H_dev, "bm_rbm_gauss_pt_read: H_dev without V_dev");
+    float *const dst[3] = {V_dev, H_dev, nullptr};
+    const int ldd[3] = {h->V, h->H, 0};
+    pt_launch_gather(h->gpt, h->stream, h->gpt.M, dst, ldd);
+    if (V_dev) launch_gauss_scale_rows(V_dev, h->gpt.M, h->V, h->sigma.p, h->stream);
+    return pt_read_host(h->gpt, h->stream, swaps_host, ladder_idx_host);
 }
 
 // the block -> tile map of a launch with tiles_i x tiles_j tiles (host evaluation of the device function, for tests and

@@ -105,6 +105,42 @@ class RbmGroupsPt(_PtCalls):
         check(self.lib.bm_rbm_groups_train_epoch_pt(self._h, Xd.offset_ptr(row * self.V), N, batch, lr, momentum, k))
 
 
+class RbmGaussPt(_PtCalls):
+    """The tempered ensemble of an RbmEngine with Gaussian visible units (bm355.h: bm_rbm_gauss_pt_*): pt_init /
+    pt_sweep / pt_read under the prefix 'bm_rbm_gauss', on the engine's handle.  V0_d of pt_init and the rows pt_read hands out are
+    in data units; the ensemble itself lives in the scaled variable u = x / sigma.  Every other attribute is the engine's."""
+    _pt_prefix, _pt_n_hidden = 'bm_rbm_gauss', 1
+
+    def __init__(self, engine):
+        self._engine = engine
+        self.lib, self.V = engine.lib, engine.V
+
+    @property
+    def _h(self):
+        return self._engine._h
+
+    def __getattr__(self, name):                  # (only what this object does not define itself)
+        if name == '_engine':
+            raise AttributeError(name)
+        return getattr(self._engine, name)
+
+    def pt_state(self):
+        """the whole ensemble as NumPy arrays (tests, tools): v [M R, V] (the scaled variable u), h [M R, H], part_v [ceil(V/16),
+        M R] (the slots of -1/2 (u - c)^2), part_h [ceil(H/16), M R], mult [M R], idx [M R] int32, swaps [2, R - 1] int64
+        (bm_rbm_get_param 'gpt_*' and pt_read); waits for the device"""
+        M, R = self._pt_shape
+        rows, eng = M * R, self._engine
+        shapes = dict(v=(rows, eng.V), h=(rows, eng.H), part_v=((eng.V + 15) // 16, rows), part_h=((eng.H + 15) // 16, rows), mult=(rows,))
+        out = {}
+        for name, shape in shapes.items():
+            a = np.empty(shape, dtype=np.float32)
+            check(self.lib.bm_rbm_get_param(self._h, ('gpt_' + name).encode(), a.ctypes.data_as(C.c_void_p), a.size))
+            out[name] = a
+        swaps, idx = self.pt_read()
+        out.update(idx=idx.reshape(-1), swaps=swaps)
+        return out
+
+
 class RbmEngine(_PtCalls):
     dtype = np.float32
     _pt_prefix, _pt_n_hidden = 'bm_rbm', 1
@@ -479,6 +515,52 @@ class RbmEngine(_PtCalls):
         check(self.lib.bm_rbm_ais(self._h, n_betas, n_runs, k, a.ctypes.data_as(C.c_void_p) if a is not None else None,
                                   int(seed), int(chain0), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    # Gaussian visible units as one joint model (bm355.h: bm_rbm_gauss_*; DESIGN.md 3.30)
+    def gauss_ais(self, n_betas, n_runs, k, seed, chain0=0, base_mean=None):
+        """[n_runs] float32 per-chain AIS estimates of the log normaliser of exp(-F(x / sigma)) over x of a handle with Gaussian
+        visible units (bm_rbm_gauss_ais); base_mean [V]: the mean `a` of the base model N(a, I) in the SCALED variable u = x / sigma,
+        None: a = 0"""
+        out = np.empty(n_runs, dtype=np.float32)
+        a = None
+        if base_mean is not None:
+            a = np.ascontiguousarray(base_mean, dtype=np.float32)
+            if a.shape != (self.V,):
+                raise ValueError('base_mean has shape %r, expected (%d,)' % (a.shape, self.V))
+        check(self.lib.bm_rbm_gauss_ais(self._h, n_betas, n_runs, k, a.ctypes.data_as(C.c_void_p) if a is not None else None,
+                                        int(seed), int(chain0), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def ais_state(self, n_runs):
+        """(v [n_runs, V], h [n_runs, H]): the chain states the last AIS entry left in the handle (tests)"""
+        v, h = np.empty((n_runs, self.V), np.float32), np.empty((n_runs, self.H), np.float32)
+        for name, a in (('ais_v', v), ('ais_h', h)):
+            check(self.lib.bm_rbm_get_param(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.size))
+        return v, h
+
+    def gauss_free_energy_rows(self, Xd, B, row=0):
+        """[B] float64: F(x / sigma) = 1/2 |u - c|^2 - sum_j softplus((u W + hb)_j) of rows [row, row + B) of Xd (data units;
+        bm_rbm_gauss_free_energy_rows); B is not bounded by max_batch"""
+        out = np.empty(B, dtype=np.float64)
+        check(self.lib.bm_rbm_gauss_free_energy_rows(self._h, Xd.offset_ptr(row * self.V), B, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    @property
+    def gauss_pt(self):
+        """the tempered ensemble of a handle with Gaussian visible units and its calls (RbmGaussPt), one object per engine"""
+        view = self.__dict__.get('_gauss_pt')
+        if view is None:
+            view = self.__dict__['_gauss_pt'] = RbmGaussPt(self)
+        return view
+
+    def gauss_pt_init(self, n_chains, betas, V0_d=None, chain0=0):
+        return self.gauss_pt.pt_init(n_chains, betas, V0_d, chain0)
+
+    def gauss_pt_sweep(self, n_steps):
+        return self.gauss_pt.pt_sweep(n_steps)
+
+    def gauss_pt_read(self, Vd=None, *Hd):
+        return self.gauss_pt.pt_read(Vd, *Hd)
 
     def gibbs(self, Hd, Vd, B, n_steps):
         check(self.lib.bm_rbm_gibbs(self._h, Hd.ptr, Vd.ptr, B, n_steps))

@@ -982,6 +982,110 @@ class GaussianRBM(BaseRBM):
     def _sigma_vector(self):
         return np.asarray(self._sigma_tmp, dtype=self._np_dtype)
 
+    # ---- the model as one joint: AIS, log-density and parallel tempering (no counterpart in the reference) --------
+    # With u = x / sigma and c = float32(vb / sigma) the free energy that `fit` reports, F(u) = 1/2 |u - c|^2 - sum_j softplus((uW + hb)_j),
+    # and the prop-down x ~ N(vb + sigma (W h), sigma^2) are the conditionals of ONE joint,
+    #     E(u, h) = 1/2 |u - c|^2 - u W h - hb.h,    h | u ~ Ber(sigmoid(uW + hb)),    u | h ~ N(c + W h, I),    x = sigma u.
+    # The methods below evaluate and sample that model.  (`fit` keeps the reference's chain, which feeds unscaled samples back into
+    # the prop-up - for sigma != 1 the Gibbs sampler of no joint; with sigma = 1 the two coincide.)  `log_Z`, `log_proba`, `sample_v`
+    # and `set_negative_phase('tempered')` stay refused for this class.
+    def _check_gauss_joint(self, what):
+        name = '%s.%s' % (self.__class__.__name__, what)
+        if self._H_UNIT == _ffi.UNIT_NRELU:
+            raise ValueError('%s: not defined with noisy rectified-linear (NReLU) hidden units (the unit has no closed-form free '
+                             'energy and real-valued hidden states)' % name)
+        if np.dtype(self.dtype) != np.float32:
+            raise NotImplementedError("%s: dtype='%s' models are not supported (float32 only)" % (name, np.dtype(self.dtype).name))
+        if self.dbm_first or self.dbm_last:
+            raise NotImplementedError('%s: a dbm_first / dbm_last model doubles one of its conditionals, which then belong to '
+                                      'no single joint distribution' % name)
+
+    def _base_mean(self, X_base):
+        """the mean `a` of the AIS base model N(a, I) in the scaled variable u = x / sigma, float32 [V]: None (a = 0), data [N][V]
+        -> mean(X / sigma), or a [V] vector - the base mean in data units -> float32(X_base / sigma)"""
+        if X_base is None:
+            return None
+        sigma = self._sigma_vector().astype(np.float32)
+        X = np.asarray(X_base, dtype=np.float32)
+        if X.ndim == 2 and X.shape[1] == self.n_visible:
+            return (X / sigma).astype(np.float64).mean(axis=0).astype(np.float32)
+        if X.shape != (self.n_visible,):
+            raise ValueError('`X_base` has invalid shape {0}: expected [N, {1}] or [{1}]'.format(X.shape, self.n_visible))
+        return (X / sigma).astype(np.float32)
+
+    def ais_log_Z(self, n_betas=100, n_runs=100, n_gibbs_steps=5, X_base=None):
+        """AIS estimate of the log normaliser of exp(-F(x / sigma)) over x (data units: sum_i log sigma_i included), so that
+        `log_density(X, log_Z)` integrates to one.  Returns log_mean, (log_low, log_high), values - as `BernoulliRBM.log_Z`.
+
+        `n_runs` chains run from the base model p_0(u) = N(a, I), h uniform, through `n_betas` temperatures linspace(0, 1, n_betas)
+        with `n_gibbs_steps` transitions each, the hidden layer summed out:
+        log p*_beta(u) = -(1 - beta) 1/2 |u - a|^2 - beta 1/2 |u - c|^2 + sum_j softplus(beta (uW + hb)_j).
+        X_base : None - a = 0; an [N, n_visible] array - a = mean(X / sigma), which makes AIS usable on trained models; an
+        [n_visible] array - the base mean in data units.
+        Both layers are always sampled, dropout is not applied.  One seed is drawn from the model's host stream; no parameter is
+        changed.  In a multi-GPU job every rank runs all chains."""
+        self._check_gauss_joint('ais_log_Z')
+        n_betas, n_runs, n_gibbs_steps = int(n_betas), int(n_runs), int(n_gibbs_steps)
+        if n_betas < 2 or n_runs < 1 or n_gibbs_steps < 1:
+            raise ValueError('%s.ais_log_Z: n_betas must be >= 2, n_runs and n_gibbs_steps >= 1 (got %d, %d, %d)'
+                             % (self.__class__.__name__, n_betas, n_runs, n_gibbs_steps))
+        return self._ais_log_Z_checked(n_betas, n_runs, n_gibbs_steps, self._base_mean(X_base))
+
+    @run_on_engine(update_seed=True)
+    def _ais_log_Z_checked(self, n_betas, n_runs, n_gibbs_steps, a):
+        values = self._on_device().gauss_ais(n_betas, n_runs, n_gibbs_steps, seed=self._graph_seed, base_mean=a)
+        log_mean = log_mean_exp(values)
+        log_std = log_std_exp(values, log_mean_exp_x=log_mean)
+        log_high = log_sum_exp([log_std, log_mean])
+        log_low = log_diff_exp([log_std, log_mean])[0]
+        return log_mean, (log_low, log_high), values
+
+    def free_energy(self, X):
+        """F(x / sigma) = 1/2 |u - c|^2 - sum_j softplus((uW + hb)_j) per row of X [N, n_visible] (data units), float64 [N]: the free
+        energy of the model's own parameters, no dropout.  Draws nothing: the model's state and seed streams stay as they are."""
+        self._check_gauss_joint('free_energy')
+        return self._free_energy_checked(X)
+
+    @run_on_engine()
+    def _free_energy_checked(self, X):
+        eng = self._on_device()
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.n_visible:
+            raise ValueError('`X` has invalid shape {0}: expected [N, {1}]'.format(X.shape, self.n_visible))
+        Xd = self._to_device(X)
+        F = np.empty(len(X))
+        for start in range(0, len(X), self.batch_size):
+            B = min(self.batch_size, len(X) - start)
+            F[start:start + B] = eng.gauss_free_energy_rows(Xd, B, row=start)
+        return F
+
+    def log_density(self, X, log_Z):
+        """log density of x per row of X: -F(x / sigma) - log_Z, `log_Z` e.g. from `ais_log_Z()`.  Draws nothing."""
+        self._check_gauss_joint('log_density')
+        return -self._free_energy_checked(X) - log_Z
+
+    def sample_v_tempered(self, n_samples, n_gibbs_steps=1000, n_temperatures=10, betas=None, V_init=None, return_stats=False):
+        """Unconditional samples of the visible units by parallel tempering (replica exchange), as `BernoulliRBM.sample_v`:
+        `n_samples` independent chains, each with one replica per temperature of the ladder 0 < betas[0] < ... < betas[-1] = 1,
+        run `n_gibbs_steps` steps of (h ~ Ber(sigmoid(beta (uW + hb))), exchange of neighbouring temperatures,
+        u ~ N(c + W h, I / beta)) on the scaled variable u = x / sigma - the temperature widens the variance of the visible
+        conditional and leaves its mean; the replica at beta = 1 of every chain is returned in data units, [n_samples, n_visible].
+
+        betas : the ladder; None: float32(linspace(0, 1, n_temperatures + 1)[1:]).  `n_temperatures=1` is plain Gibbs on the joint.
+        V_init : [n_samples, n_visible] start of every chain (all its replicas), in data units; None: u_0 ~ N(c, I / beta).
+        With `return_stats` also the acceptance rate of every neighbouring pair of temperatures, [n_temperatures - 1].
+        Both layers are always sampled, dropout is not applied.  One seed is drawn from the model's host stream; no parameter is
+        changed.  In a multi-GPU job every rank runs all chains."""
+        self._check_gauss_joint('sample_v_tempered')
+        n_samples, n_gibbs_steps = int(n_samples), int(n_gibbs_steps)
+        if n_samples < 1 or n_gibbs_steps < 1:
+            raise ValueError('`n_samples` and `n_gibbs_steps` must be >= 1 (got {0}, {1})'.format(n_samples, n_gibbs_steps))
+        return self._sample_v_tempered_checked(n_samples, n_gibbs_steps, resolve_ladder(n_temperatures, betas), V_init, return_stats)
+
+    @run_on_engine(update_seed=True)
+    def _sample_v_tempered_checked(self, n_samples, n_gibbs_steps, ladder, V_init, return_stats):
+        return run_tempered_sampler(self._on_device().gauss_pt, n_samples, n_gibbs_steps, ladder, V_init, self.n_visible, return_stats)
+
 
 class NReLUHidden(object):
     """Noisy rectified-linear hidden units (NReLU; Nair & Hinton 2010), mixed in in front of an RBM class.

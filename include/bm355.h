@@ -317,6 +317,52 @@ int bm_rbm_groups_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32
 int bm_rbm_rsm_ais(bm_rbm *h, int32_t n_betas, int32_t n_rows, int32_t n_gibbs_steps, const float *base_logits_host,
                    const float *lengths_host, uint64_t seed, int64_t chain0, float *values_host);
 
+/* Gaussian visible units as ONE joint model (no counterpart in the reference): AIS log Z, per-row free energies and
+ * parallel tempering for a float32 handle with Gaussian visible and Bernoulli hidden units, under names of their own - bm_rbm_ais,
+ * bm_rbm_free_energy_rows and bm_rbm_pt_* keep refusing such a handle.  The model is the joint over the scaled variable u = x / sigma
+ * whose conditionals are the reference's free energy and prop-down, c_i = fl32(vb_i / sigma_i):
+ *   E(u, h) = 1/2 |u - c|^2 - u W h - hb.h;   h | u ~ Ber(sigmoid(u W + hb));   u | h ~ N(c + W h, I);   x = sigma u.
+ * (The training chain of bm_rbm_train_step feeds UNSCALED samples back into its prop-up, as the reference does: for sigma != 1 that is
+ * the Gibbs sampler of no joint; these entries use the sampler above.  With sigma = 1 the two coincide.)  Everything runs on u; data
+ * units appear only as u = fl32(x / sigma) on the way in and x = fl32(u sigma) on the way out.  Always per-pass fp32 launches.
+ *
+ * bm_rbm_gauss_ais: bm_rbm_ais with the base model p_0(u) = N(a, I), h uniform; a = base_mean_host [n_visible] in the SCALED variable
+ * (NULL: a = 0).  beta_k = float32(linspace(0, 1, n_betas))[k],
+ *   log p*_beta(u) = -(1 - beta) 1/2 |u - a|^2 - beta 1/2 |u - c|^2 + sum_j softplus(beta (u W + hb)_j),
+ *   log Z_0 = (V/2) log 2 pi + H log 2 + sum_i log sigma_i + 1/2 (|a|^2 - |c|^2)      (host, double; the last term: see below)
+ * u_0 = a + n; for k = 1 .. n_betas - 1: logw += (beta_k - beta_{k-1}) u.(c - a) + sum_j [softplus(beta_k z_j) - softplus(beta_{k-1} z_j)],
+ * then n_gibbs_steps transitions h ~ Ber(sigmoid(beta_k (u W + hb))), u ~ N(a + beta_k (c - a) + beta_k W h, I); none behind the last
+ * score.  The score's visible term is (beta_k - beta_{k-1}) [u.(c - a) + 1/2 (|a|^2 - |c|^2)]: its constant sums to 1/2 (|a|^2 - |c|^2)
+ * over the path and is carried by log Z_0.  values_host [n_runs] receives logw + log Z_0: estimates of the log normaliser of
+ * exp(-F(x / sigma)) over x (data units: sum log sigma included).  RNG sites, call = beta step, chain0 and the chain-slice property as
+ * bm_rbm_ais; a normal draw is the one of the flat index (chain0 + r) n_visible + i under the Gaussian layer's word-to-draw mapping.
+ * The states are float32 and reproducible bit for bit; the log-weights are double sums of float32 partials.
+ *
+ * bm_rbm_gauss_free_energy_rows: F(x / sigma) = 1/2 |u - c|^2 - sum_j softplus((u W + hb)_j) of X_dev [B, n_visible] (data units) into
+ * out_host [B] DOUBLE; B is not bounded by max_batch; no dropout, no RNG call consumed.  log density(x) = -F - log Z.
+ *
+ * bm_rbm_gauss_pt_init / _sweep / _read: bm_rbm_pt_* on an ensemble of its own (bm_rbm_pt_* never see it).  The contracts are theirs -
+ * chain-major rows, the ladder checks, the swap step and its counters, the call counter (once per sweep), the step parity, chain0 and
+ * the chain-slice property - with these differences:
+ *   start      u_0 = fl(c + fl(n sd_r)), n the normal at flat index ((chain0 + c) R + r) V + i of site 11, or, with V0_dev [n_chains,
+ *              n_visible] in DATA units, u_0 = fl32(V0 / sigma) for all R replicas of a chain.
+ *   prop-down  u ~ N(c + W h, I / beta_row): m = fl(z + c), s = fl(m + fl(n sd[idx_row])), sd[r] = float32(1 / sqrt(double(beta_r))),
+ *              exactly 1 at beta = 1: the temperature changes the VARIANCE, not the mean.  One launch (the RT + GT flavour of
+ *              act_kernel) that also leaves the slot partials of -1/2 (s - c)^2 from its registers; BM355_DEBUG=gt_fused=0: a raw pass
+ *              and a row kernel, the same bits.
+ *   swap       unchanged: with those partials and the prop-up's h.(u W + hb), E = 1/2 |u - c|^2 - h.(u W + hb).
+ *   read       V_dev receives x = fl32(u sigma) of the beta = 1 rows.
+ * The centre c is the one of the parameters at init.  Refused, the handle staying usable, with a message that names the entry: a handle
+ * whose visible units are not Gaussian, Multinomial or NReLU hidden units, dbm_first / dbm_last, null pointers, bad AIS arguments, a bad
+ * ladder, n_steps < 1, sweep / read before init.  None of the entries changes a parameter or a momentum buffer; AIS and the free
+ * energies do not advance the call counter.  Float32, one process. */
+int bm_rbm_gauss_ais(bm_rbm *h, int32_t n_betas, int32_t n_runs, int32_t n_gibbs_steps, const float *base_mean_host, uint64_t seed,
+                     int64_t chain0, float *values_host);
+int bm_rbm_gauss_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, double *out_host);
+int bm_rbm_gauss_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0);
+int bm_rbm_gauss_pt_sweep(bm_rbm *h, int32_t n_steps);
+int bm_rbm_gauss_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host);
+
 /* Metric fetches of base_rbm.py:554-564,578,605,612: out[0]=msre (:486-488),
  * out[1]=pll (:496-513), out[2]=l2_loss (:482-484), out[3]=free_energy
  * (:516-517; rbm.py:17-22 / :109-116).  Runs the same chain as train_step
