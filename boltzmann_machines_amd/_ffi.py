@@ -156,6 +156,12 @@ SIGNATURES = {
     'bm_rbm_groups_train_step_pt': [_vp, _vp, _i32, _f32, _f32, _i32],
     'bm_rbm_groups_train_epoch_pt': [_vp, _vp, _i64, _i32, _f32, _f32, _i32],
     'bm_rbm_rsm_ais': [_vp, _i32, _i32, _i32, _vp, _vp, _u64, _i64, _vp],
+    'bm_rbm_rsm_pt_init': [_vp, _i32, _i32, _vp, _vp, _vp, _i64],
+    'bm_rbm_rsm_pt_sweep': [_vp, _i32],
+    'bm_debug_rsm_up': [_vp, _vp, _i32, _vp, _f32, _i32, _vp, _vp],
+    'bm_rbm_rsm_pt_read': [_vp, _vp, _vp, _vp, _vp],
+    'bm_rbm_rsm_train_step_pt': [_vp, _vp, _i32, _f32, _f32, _i32],
+    'bm_rbm_rsm_train_epoch_pt': [_vp, _vp, _i64, _i32, _f32, _f32, _i32],
     'bm_rbm_gauss_ais': [_vp, _i32, _i32, _i32, _vp, _u64, _i64, _vp],
     'bm_rbm_gauss_free_energy_rows': [_vp, _vp, _i32, _vp],
     'bm_rbm_gauss_pt_init': [_vp, _i32, _i32, _vp, _vp, _i64],

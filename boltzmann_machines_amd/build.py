@@ -11,7 +11,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libbm355.so')
-SOURCES = ['bm355.hip', 'bm_grad_cen.hip', 'bm_grad_fast.hip', 'bm_class.hip', 'bm_class_joint.hip', 'bm_class_semi.hip', 'bm_stack.hip', 'bm_nrelu.hip', 'bm_softmax_v.hip', 'bm_softmax_cl.hip', 'bm_softmax_ais.hip', 'bm_softmax_pt.hip', 'bm_rsm.hip', 'bm_gauss.hip']     # (all but the first: csrc/bm_launch.h says why they are units of their own)
+SOURCES = ['bm355.hip', 'bm_grad_cen.hip', 'bm_grad_fast.hip', 'bm_class.hip', 'bm_class_joint.hip', 'bm_class_semi.hip', 'bm_stack.hip', 'bm_nrelu.hip', 'bm_softmax_v.hip', 'bm_softmax_cl.hip', 'bm_softmax_ais.hip', 'bm_softmax_pt.hip', 'bm_rsm.hip', 'bm_rsm_pt.hip', 'bm_gauss.hip']     # (all but the first: csrc/bm_launch.h says why they are units of their own)
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',
          '-ffp-contract=off',          # every fma is an explicit fmaf (DESIGN.md "Numerics")
          '-mllvm', '-amdgpu-mfma-vgpr-form',   # MFMA accumulators stay in VGPRs: without it hipcc parks the FP64

@@ -625,7 +625,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                     continue;
                 }
                 if constexpr (DB) {            // beta (z + D hb): t as the row sums below form it, then ONE rounded product
-                    m[r] = sigmoid(__fmul_rn(a.mult, __fadd_rn(z[4 * hlf + r], b)));      // (mult == 1: t itself, the untempered pass)
+                    m[r] = sigmoid(__fmul_rn(RT ? rm : a.mult, __fadd_rn(z[4 * hlf + r], b)));      // (mult == 1: t itself, the untempered pass; DB + RT: the row's beta)
                     s[r] = m[r];
                     continue;
                 }
@@ -844,7 +844,7 @@ __device__ __forceinline__ float act_epilogue(const ActArgs &a, const PhiloxKey 
                     }
                     // the state of this element as it was just stored by this lane
                     if (a.rowdot_out) qd += a.states[(size_t)j * a.ldo + i] * a.dot_vec[i];
-                    if constexpr (RT) { if (a.rowen_out) qe += sv[e] * (z[e] + bs[e]); }
+                    if constexpr (RT) { if (a.rowen_out) qe += sv[e] * (z[e] + (DB ? __fmul_rn(dbm, bs[e]) : bs[e])); }      // (DB + RT: the untempered t)
                 }
                 if constexpr (RT) ren = (hlf == 0) ? qe : ren + qe;
                 racc = (hlf == 0) ? qa : racc + qa;

@@ -359,6 +359,21 @@ template <> struct ActFlavour<FL_RT | FL_GT> : ActFlavourDefaults {
     // (the Bernoulli prop-down of the shape: the same contraction, a draw per output; the plain row dots would read dot_vec)
     static void strip(ActArgs &p) { ActFlavour<FL_RT>::strip(p); p.gt_sd = nullptr; p.gt_idx = nullptr; p.kind = 0; p.rowdot_out = nullptr; p.ld_part = 0; }
 };
+// DB + RT, the prop-up of parallel tempering over replicated softmax visible units: the DB pass with a temperature
+// PER ROW - x = __fmul_rn(row_mult[j], __fadd_rn(z, __fmul_rn(row_bmult[j], bias))), the tempered DB pass of 3.28 with the row's beta
+// in place of the launch-uniform one - that leaves RT's rowen_out, the slot partials of sum_i s_i t_i with the UNTEMPERED t.  No entry
+// of the table - act_route sends a pass with both selectors to DB, which refuses it - and asked for by name (launch_act_db_pt;
+// bm_rsm_pt.hip); the kernel set is DB's.  No rowdot_out, no softplus partials, no hand-over (sel_out); row_mult == 1 gives the plain
+// DB pass bit for bit
+void launch_act_dbpt_as(int, const ActArgs &, hipStream_t);
+template <> struct ActFlavour<FL_DB | FL_RT> : ActFlavourDefaults {
+    static constexpr bool seg2 = false, xm_only = false, geo5 = false;
+    static constexpr ActAsFn as = launch_act_dbpt_as;
+    static constexpr const char *no_kernel = "bm355: a row-tempered length-scaled-bias pass is a single-segment Bernoulli prop-up with a temperature and a length per row that leaves its energy partials and nothing else (no such kernel)\n";
+    static bool selects(const ActArgs &a) { return a.row_bmult != nullptr && a.row_mult != nullptr; }
+    static bool admits(const ActArgs &a) { return a.kind == 0 && a.K2 == 0 && !a.rowdot_out && !a.rowacc && !a.sel_out && (!a.rowen_out || a.ld_part >= a.J); }
+    static void strip(ActArgs &p) { ActFlavour<FL_DB>::strip(p); ActFlavour<FL_RT>::strip(p); }
+};
 
 // the table's order: most specific first.  first(f): f(std::integral_constant<unsigned, FL>) for each flavour until one returns true
 template <unsigned... FL> struct ActFlavoursOf {
@@ -646,6 +661,12 @@ static inline void launch_act_gauss_pt(const ActArgs &a, hipStream_t st) {
     using F = ActFlavour<FL_RT | FL_GT>;
     if (!F::selects(a) || (act_features(a) & ~FL_RT) != 0 || !F::admits(a)) { fputs(F::no_kernel, stderr); abort(); }
     launch_act_flavoured<FL_RT | FL_GT>(a, st);
+}
+// a row-tempered length-scaled-bias pass (ActFlavour<FL_DB | FL_RT>): the caller's explicit choice, not a route of launch_act
+static inline void launch_act_db_pt(const ActArgs &a, hipStream_t st) {
+    using F = ActFlavour<FL_DB | FL_RT>;
+    if (!F::selects(a) || (act_features(a) & ~(FL_DB | FL_RT)) != 0 || !F::admits(a)) { fputs(F::no_kernel, stderr); abort(); }
+    launch_act_flavoured<FL_DB | FL_RT>(a, st);
 }
 static inline void launch_act(const ActArgs &a, hipStream_t st) {
     if (a.gt_sd) { fputs("bm355: a variance-tempered Gaussian pass is asked for by name, launch_act_gauss_pt (no such route)\n", stderr); abort(); }

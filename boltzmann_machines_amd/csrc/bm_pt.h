@@ -133,8 +133,12 @@ __global__ __launch_bounds__(256) void pt_gather_kernel(int M, int R, const int 
 // one layer of the ensemble: its states, the slot partials the swap energy sums, its width (0: the model has no such layer)
 struct PtLayer {
     Mat x;                                         // [rows][n]
-    DevBuf part;                                   // [nslots(n)][rows]
+    DevBuf part;                                   // [nslot()][rows]
     int n = 0;
+    // the slot count of `part`: nslots(n), the 16-column slots of the epilogue's order, unless the engine's passes leave another
+    // number (ns > 0; replicated softmax, DESIGN.md 3.31: the float32 pair of a double sum, two slots whatever n is)
+    int ns = 0;
+    int nslot() const { return ns > 0 ? ns : nslots(n); }
 };
 
 // The tempered ensemble of M chains x R replicas, chain-major rows (row c * R + r), allocated on demand for `rows` rows; the
@@ -153,17 +157,20 @@ struct PtEnsemble {
     int64_t row0() const { return chain0 * R; }    // global index of row 0 (Philox flat indices)
 
     // room for `want` rows of the widths {V, n1, n2} and a ladder of R_; grows only
-    int ensure(int want, int R_, const int widths[3]) {
+    // v_slots > 0: the visible layer's slot count (PtLayer::ns), else nslots(V); a change of it allocates again
+    int ensure(int want, int R_, const int widths[3], int v_slots = 0) {
         const size_t ncnt = (size_t)2 * std::max(R_ - 1, 1);
         if (cnt.n < ncnt) BM_TRY(cnt.alloc(ncnt));
         if (beta.n < (size_t)R_) BM_TRY(beta.alloc(R_));
-        if (want <= rows) return 0;
+        if (want <= rows && v.ns == v_slots) return 0;
+        want = std::max(want, rows);
         rows = 0;                                  // (set again once every buffer exists: a failure leaves none counted)
+        v.ns = v_slots;
         for (int i = 0; i < 3; ++i) {
             PtLayer &l = layer(i);
             l.n = widths[i];
             if (!l.n) continue;
-            BM_TRY(l.x.alloc(want, l.n)); BM_TRY(l.part.alloc((size_t)nslots(l.n) * want));
+            BM_TRY(l.x.alloc(want, l.n)); BM_TRY(l.part.alloc((size_t)l.nslot() * want));
         }
         BM_TRY(mult.alloc(want)); BM_TRY(idx.alloc(want));
         rows = want;
@@ -189,10 +196,10 @@ static inline int pt_check_ladder(int32_t n_chains, int32_t n_temps, const float
 // engine's own start launch on `stream` - it fills e.v.x (and e.h2.x), the first v.vb (h2.b2) partials, e.mult from e.beta and e.idx
 template <class StartFn>
 static inline int pt_begin_with(PtEnsemble &e, hipStream_t stream, const int widths[3], int M, int R, int64_t chain0,
-                                const float *betas_host, StartFn &&start) {
+                                const float *betas_host, StartFn &&start, int v_slots = 0) {
     const int rows = M * R;
     e.M = 0;                                       // (an ensemble exists once everything below went through)
-    BM_TRY(e.ensure(rows, R, widths));
+    BM_TRY(e.ensure(rows, R, widths, v_slots));
     BM_HIP(hipStreamSynchronize(stream));
     BM_HIP(hipMemcpy(e.beta.p, betas_host, (size_t)R * sizeof(float), hipMemcpyHostToDevice));
     BM_HIP(hipMemsetAsync(e.cnt.p, 0, (size_t)2 * std::max(R - 1, 1) * sizeof(unsigned long long), stream));
@@ -223,7 +230,7 @@ static inline void pt_launch_swap(PtEnsemble &e, hipStream_t stream, int t, Phil
     if (npair <= 0) return;
     const long long nthr = (long long)e.M * npair;
     hipLaunchKernelGGL(pt_swap_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, e.M, e.R, parity,
-                       (const float *)e.v.part.p, nslots(e.v.n), (const float *)e.h2.part.p, nslots(e.h2.n),
+                       (const float *)e.v.part.p, e.v.nslot(), (const float *)e.h2.part.p, nslots(e.h2.n),
                        (const float *)e.h1.part.p, nslots(e.h1.n), e.rows, e.mult.p, e.idx.p, e.cnt.p, key,
                        (unsigned long long)e.chain0);
 }

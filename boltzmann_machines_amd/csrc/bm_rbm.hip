@@ -166,6 +166,13 @@ struct bm_rbm {
     // allocated with the ensemble; nothing else reads or writes it
     int gp_rows = 0;
     Mat gp_z;
+    // bm_rbm_rsm_pt_* (DESIGN.md 3.31): the ensemble is `pt` with a two-slot visible partial array; rp_z: the raw z = h W^T
+    // [rp_rows][V] of its prop-down; rp_len [rp_rows]: the document length of every ensemble row (len[c R + r] = D_c); rp_clen
+    // [rp_rows]: the chains' lengths D_c, dense; rp_v0len: the row sums of a V0.  rsm_pt: the ensemble in `pt` is a count ensemble
+    int rp_rows = 0;
+    bool rsm_pt = false;
+    Mat rp_z;
+    DevBuf rp_len, rp_clen, rp_v0len, rp_probe;      // (rp_probe: the row_mult of bm_debug_rsm_up)
     // Gaussian visible units as one joint model over u = x / sigma (bm_rbm_gauss_*; bm_gauss.h), allocated at the
     // first such call; nothing else in the handle reads or writes them.  gc / gones: the centre c = vb / sigma and a vector of ones
     // [V], formed again by every call (the parameters may have moved).  gfe_*: the scaled rows [gfe_rows][V], the softplus slot
@@ -1243,7 +1250,8 @@ static int pt_get_param(bm_rbm *h, PtEnsemble &e, const std::string &full, float
     size_t pitch = 0, width = 0, height = 0;
     if (nm == "pt_v")           { src = e.v.x.p; pitch = e.v.x.ld; width = h->V; height = rows; }
     else if (nm == "pt_h")      { src = e.h1.x.p; pitch = e.h1.x.ld; width = h->H; height = rows; }
-    else if (nm == "pt_part_v") { src = e.v.part.p; pitch = e.rows; width = rows; height = nslots(h->V); }
+    else if (nm == "pt_part_v") { src = e.v.part.p; pitch = e.rows; width = rows; height = e.v.nslot(); }
+    else if (nm == "pt_len" && &e == &h->pt && h->rsm_pt) { src = h->rp_len.p; pitch = rows; width = rows; height = 1; }
     else if (nm == "pt_part_h") { src = e.h1.part.p; pitch = e.rows; width = rows; height = nslots(h->H); }
     else if (nm == "pt_mult")   { src = e.mult.p; pitch = rows; width = rows; height = 1; }
     BM_CHECK(src, "unknown RBM variable '%s'", full.c_str());
@@ -1629,7 +1637,12 @@ int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K) {
 // Replicated softmax visible units (bm355.h).  A property of the handle that issue() reads at every pass
 int bm_rbm_set_replicated_softmax(bm_rbm *h, int32_t max_length) {
     BM_CHECK(h, "null argument");
-    if (max_length == 0) { h->rsm_len = 0; h->rsm_user_n = 0; h->rsm_cur = nullptr; return 0; }
+    if (max_length == 0) {
+        // (an ensemble of count rows goes with the unit, DESIGN.md 3.31: a Bernoulli sweep never runs over it)
+        if (h->rsm_pt) { h->pt.M = 0; h->rsm_pt = false; }
+        h->rsm_len = 0; h->rsm_user_n = 0; h->rsm_cur = nullptr;
+        return 0;
+    }
     BM_CHECK(max_length >= 1 && max_length < (1 << 24), "replicated softmax visible units: max_length must be 0 (off) or in [1, 2^24) "
              "(got %d): the lengths are exact in float32", (int)max_length);
     BM_CHECK(h->V >= 2 && h->V <= RSM_MAX_V, "replicated softmax visible units: n_visible = %d is outside [2, %d] (a row's prefix sums and "
@@ -1644,7 +1657,8 @@ int bm_rbm_set_replicated_softmax(bm_rbm *h, int32_t max_length) {
     BM_CHECK(!h->cen_on, "replicated softmax visible units do not combine with centering (bm_rbm_set_centering(off) first)");
     BM_CHECK(!h->n_classes, "replicated softmax visible units do not combine with a class head (bm_rbm_set_classes(0) first)");
     BM_CHECK(!h->fw_on, "replicated softmax visible units do not combine with fast weights (bm_rbm_set_fast_weights(off) first)");
-    BM_CHECK(h->pt.M == 0, "replicated softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
+    // (the count ensemble of a handle that has the unit already is bm_rbm_rsm_pt_init's; a new max_length discards it)
+    BM_CHECK(h->pt.M == 0 || h->rsm_pt, "replicated softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
     BM_CHECK(!h->v_groups, "replicated softmax visible units do not combine with visible groups (bm_rbm_set_visible_groups(0) first)");
     if (!h->rsm_bad.p) {          // (allocated last: the workspaces are complete once the flag exists)
         BM_TRY(h->rsm_D.alloc(h->maxB)); BM_TRY(h->rsm_user.alloc(h->maxB));
@@ -1653,6 +1667,7 @@ int bm_rbm_set_replicated_softmax(bm_rbm *h, int32_t max_length) {
         BM_HIP(hipMemset(flag.p, 0, sizeof(int)));
         h->rsm_bad = std::move(flag);
     }
+    if (h->rsm_pt && h->rsm_len != max_length) { h->pt.M = 0; h->rsm_pt = false; }
     h->rsm_len = max_length;
     h->rsm_user_n = 0;
     h->rsm_cur = nullptr;
@@ -1679,7 +1694,8 @@ static int check_row_lengths(bm_rbm *h) {
     if (bad) {
         BM_HIP(hipMemset(h->rsm_bad.p, 0, sizeof(int)));
         BM_CHECK(false, "replicated softmax visible units: a row that is no count vector of 1 to max_length = %d tokens reached the "
-                 "engine:%s%s%s%s", h->rsm_len, (bad & RSM_BAD_NEGATIVE) ? " [a negative entry]" : "",
+                 "engine:%s%s%s%s%s", h->rsm_len, (bad & RSM_BAD_MISMATCH) ? " [a start row of bm_rbm_rsm_pt_init whose sum is not its chain's length]" : "",
+                 (bad & RSM_BAD_NEGATIVE) ? " [a negative entry]" : "",
                  (bad & RSM_BAD_FRACTION) ? " [a non-integer entry]" : "", (bad & RSM_BAD_EMPTY) ? " [an empty row, length 0]" : "",
                  (bad & RSM_BAD_LONG) ? " [a row longer than max_length]" : "");
     }
@@ -3055,6 +3071,230 @@ int bm_rbm_groups_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32
     for (int64_t s = 0; s < N; s += batch) {
         const int B = (int)((N - s < batch) ? (N - s) : batch);
         BM_TRY(bm_rbm_groups_train_step_pt(h, X_dev + (size_t)s * h->V, B, lr, mom, k));
+    }
+    return 0;
+}
+
+// ---- parallel tempering over replicated softmax visible units (bm355.h: bm_rbm_rsm_pt_* / _train_step_pt).  The
+// ensemble is the handle's one PtEnsemble with a two-slot visible partial array (the float32 pair of the double v.vb): a handle with
+// the unit holds no other (bm_rbm_pt_init refuses it, bm_rbm_set_replicated_softmax refuses a handle that holds a Bernoulli one), and
+// turning the unit off discards it.
+static int check_rsm_pt(const bm_rbm *h, const char *what, bool need_ensemble) {
+    BM_CHECK(h, "%s: null argument", what);
+    BM_CHECK(h->rsm_len, "%s needs a handle with replicated softmax visible units (bm_rbm_set_replicated_softmax): bm_rbm_pt_* / "
+             "bm_rbm_groups_pt_* serve the other units", what);
+    BM_CHECK(!need_ensemble || (h->pt.M > 0 && h->rsm_pt), "%s: no ensemble (call bm_rbm_rsm_pt_init first)", what);
+    return 0;
+}
+// the prop-up of step t: h ~ Ber(sigmoid(beta_row (v W + D_row hb))) from pt.v into pt.h1, leaving the slot partials of h.(vW + D hb):
+// the DB + RT flavour, asked for by name (issue() goes through launch_act, which has no such route); W^T x-major where the handle
+// keeps a valid one, as issue() reads it
+static void rsm_pt_up(bm_rbm *h, int t) {
+    PtEnsemble &e = h->pt;
+    LayerPass p = rbm_pass(h, true, e.nrows(), in_of(e.v.x), value_out(1, e.h1.x.p, e.h1.x.ld, make_key(h, SITE_H, t), e.row0()));   // (mult: not read)
+    p.energy_rows(e.h1.part.p, e.rows).row_tempered(e.mult.p);
+    ActArgs &a = p.a;
+    a.row_bmult = h->rp_len.p;
+    if (h->use_wt && h->wt_valid) { a.P1 = make_operand(h->Wt.p, h->Wt.ld, h->H); a.p_xm = 1; }
+    ProfScope _ps(h, KC_UP);
+    launch_act_db_pt(a, h->stream);
+}
+// the prop-down of step t: a raw pass z = h W^T (kind 2, mult 1: the plain kernels) into rp_z, then the PT flavour of the count kernel:
+// v ~ Multinomial(D_row, softmax(beta_row (z + vb))) into pt.v, the pair of v.vb into pt.v.part; sel_rows > 0: the beta = 1 row of
+// every chain c < sel_rows also goes to vs[c]
+static void rsm_pt_down(bm_rbm *h, int t, int sel_rows) {
+    PtEnsemble &e = h->pt;
+    const int rows = e.nrows();
+    const PhiloxKey key = make_key(h, SITE_V, t);
+    LayerPass p = rbm_pass(h, false, rows, in_of(e.h1.x), LayerOut{0, h->rp_z.p, nullptr, h->rp_z.ld, key, e.row0()}, 1.0f);
+    p.a.kind = 2; p.a.sample = 0; p.a.states = nullptr;
+    {
+        ProfScope _ps(h, KC_DOWN);
+        launch_act(p.a, h->stream);
+    }
+    ProfScope _ps(h, KC_OTHER);                        // (per-class event timing: the count kernel is the class `other`, as in 3.27)
+    McPtArgs m;
+    memset(&m, 0, sizeof(m));
+    m.L = h->rp_z.p; m.ld = h->rp_z.ld; m.states = e.v.x.p; m.ld_states = e.v.x.ld; m.lengths = h->rp_len.p;
+    m.V = h->V; m.J = rows; m.sample = 1; m.max_length = h->rsm_len; m.key = key; m.row0 = e.row0();
+    m.dvec = h->vb.p; m.part = e.v.part.p; m.ld_part = e.rows;
+    m.bias = h->vb.p; m.row_mult = e.mult.p;
+    if (sel_rows > 0) { m.sel_out = h->vs.p; m.sel_ld = h->vs.ld; m.sel_R = e.R; m.sel_rows = sel_rows; }
+    if (launch_multinomial_counts_pt(m, h->stream)) abort();       // (bm_rbm_set_replicated_softmax checked the width)
+}
+static void rsm_pt_step(bm_rbm *h, int t, int sel_rows = 0) {
+    rsm_pt_up(h, t);
+    pt_launch_swap(h->pt, h->stream, t, make_key(h, SITE_PT_SWAP, t));
+    rsm_pt_down(h, t, sel_rows);
+}
+
+int bm_rbm_rsm_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *lengths_host, const float *V0_dev,
+                       int64_t chain0) {
+    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_pt_init", false));
+    BM_TRY(pt_check_ladder(n_chains, n_temps, betas_host, chain0));
+    BM_CHECK(lengths_host, "bm_rbm_rsm_pt_init: null argument");
+    for (int c = 0; c < n_chains; ++c) {
+        const float D = lengths_host[c];
+        BM_CHECK(D >= 1.0f && D <= (float)h->rsm_len && D == truncf(D), "bm_rbm_rsm_pt_init: lengths_host[%d] = %g is no integer in "
+                 "[1, max_length = %d]", c, (double)D, h->rsm_len);
+    }
+    BM_CHECK(!h->pt.M || h->rsm_pt, "bm_rbm_rsm_pt_init: this handle holds a tempered ensemble of another unit");
+    h->pt.M = 0; h->rsm_pt = false;
+    const int M = n_chains, R = n_temps, rows = M * R;
+    if (rows > h->rp_rows) {                           // (a failed allocation leaves nothing counted)
+        h->rp_rows = 0;
+        BM_TRY(h->rp_z.alloc(rows, h->V)); BM_TRY(h->rp_len.alloc(rows)); BM_TRY(h->rp_clen.alloc(rows)); BM_TRY(h->rp_v0len.alloc(rows));
+        h->rp_rows = rows;
+    }
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_HIP(hipMemcpy(h->rp_clen.p, lengths_host, (size_t)M * sizeof(float), hipMemcpyHostToDevice));
+    // row_lengths_kernel's flag is the handle's: what an earlier batch left there and bm_rbm_sync has not reported yet is set aside
+    // for the start (the stream is idle) and put back behind it, so that the start answers for its own rows alone
+    int pending = 0;
+    if (V0_dev) {
+        BM_HIP(hipMemcpy(&pending, h->rsm_bad.p, sizeof(int), hipMemcpyDeviceToHost));
+        if (pending) BM_HIP(hipMemset(h->rsm_bad.p, 0, sizeof(int)));
+    }
+    const int widths[3] = {h->V, h->H, 0};
+    const PhiloxKey key = make_key(h, SITE_PT_V0, 0);
+    BM_TRY(pt_begin_with(h->pt, h->stream, widths, M, R, chain0, betas_host, [&](PtEnsemble &e, int nrows) {
+        // the sums of the start rows, with row_lengths_kernel's own flags; the start kernel compares them with the chains' lengths
+        if (V0_dev) launch_row_lengths(RowLenArgs{V0_dev, h->V, h->V, M, h->rp_v0len.p, h->rsm_len, h->rsm_bad.p}, h->stream);
+        RsmPtStartArgs s0;
+        memset(&s0, 0, sizeof(s0));
+        s0.v = e.v.x.p; s0.ld = e.v.x.ld; s0.rows = nrows; s0.R = R; s0.V = h->V;
+        s0.V0 = V0_dev; s0.V0_len = V0_dev ? h->rp_v0len.p : nullptr; s0.chain_len = h->rp_clen.p; s0.beta = e.beta.p;
+        s0.row_mult = e.mult.p; s0.len = h->rp_len.p; s0.idx = e.idx.p; s0.bad = h->rsm_bad.p;
+        launch_rsm_pt_start(s0, h->stream);
+        if (!V0_dev) {                                 // v_0 ~ Multinomial(D_c, uniform): the count flavour on zero z and zero bias
+            McPtArgs m;
+            memset(&m, 0, sizeof(m));
+            m.states = e.v.x.p; m.ld_states = e.v.x.ld; m.lengths = h->rp_len.p;
+            m.V = h->V; m.J = nrows; m.sample = 1; m.max_length = h->rsm_len; m.key = key;
+            m.row0 = (long long)chain0 * (long long)R;
+            m.dvec = h->vb.p; m.part = e.v.part.p; m.ld_part = e.rows; m.row_mult = e.mult.p;
+            if (launch_multinomial_counts_pt(m, h->stream)) abort();
+        }
+        launch_rsm_pt_rescore(e.v.x.p, e.v.x.ld, nrows, h->V, h->vb.p, e.v.part.p, e.rows, h->stream);
+    }, 2));
+    if (V0_dev) {                                      // a start row that is no count row of its chain's length: no ensemble
+        BM_HIP(hipStreamSynchronize(h->stream));
+        const int rc = check_row_lengths(h);
+        if (pending) BM_HIP(hipMemcpy(h->rsm_bad.p, &pending, sizeof(int), hipMemcpyHostToDevice));
+        if (rc) { h->pt.M = 0; return rc; }
+    }
+    h->rsm_pt = true;
+    return 0;
+}
+
+// A launch-level probe of the two tempered prop-ups (tests): h ~ Ber(sigmoid(beta (v W + D_j hb))) of the J rows of V_dev [J][V]
+// with the lengths lengths_dev [J] into H_dev [J][H] (dense), drawn at SITE_H, step 0, the handle's seed, call counter and row
+// offset.  per_row != 0: the DB + RT flavour with row_mult[j] == beta for every row (launch_act_db_pt), which also leaves its
+// energy partials in part_dev [ceil(H/16)][J] where that is not null; per_row == 0: the existing DB pass at mult == bmult == beta,
+// the pass of bm_rbm_rsm_ais.  The call counter does not advance: the two forms read the same stream
+int bm_debug_rsm_up(bm_rbm *h, const float *V_dev, int32_t J, const float *lengths_dev, float beta, int32_t per_row, float *H_dev,
+                    float *part_dev) {
+    BM_TRY(check_rsm_pt(h, "bm_debug_rsm_up", false));
+    BM_CHECK(V_dev && lengths_dev && H_dev && J >= 1 && beta > 0.f, "bm_debug_rsm_up: bad arguments");
+    BM_CHECK(per_row || !part_dev, "bm_debug_rsm_up: the energy partials are the per-row form's");
+    ensure_wt(h);
+    LayerPass p = rbm_pass(h, true, J, LayerIn{V_dev, h->V}, LayerOut{1, nullptr, H_dev, h->H, make_key(h, SITE_H, 0), h->row0}, beta);
+    p.a.row_bmult = lengths_dev;
+    if (!per_row) {
+        issue(h, p);
+        BM_HIP(hipGetLastError());
+        return 0;
+    }
+    if (h->rp_probe.n < (size_t)J) BM_TRY(h->rp_probe.alloc(J));
+    const std::vector<float> mult((size_t)J, beta);
+    BM_HIP(hipStreamSynchronize(h->stream));
+    BM_HIP(hipMemcpy(h->rp_probe.p, mult.data(), (size_t)J * sizeof(float), hipMemcpyHostToDevice));
+    ActArgs &a = p.a;
+    a.mult = a.bmult = 1.0f;                           // (not read: the row's beta takes their place)
+    p.row_tempered(h->rp_probe.p);
+    if (part_dev) p.energy_rows(part_dev, J);
+    if (h->use_wt && h->wt_valid) { a.P1 = make_operand(h->Wt.p, h->Wt.ld, h->H); a.p_xm = 1; }
+    launch_act_db_pt(a, h->stream);
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+int bm_rbm_rsm_pt_sweep(bm_rbm *h, int32_t n_steps) {
+    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_pt_sweep", true));
+    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
+    ensure_wt(h);
+    for (int t = 0; t < n_steps; ++t) rsm_pt_step(h, t);
+    h->pt.step += n_steps;
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+int bm_rbm_rsm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
+    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_pt_read", true));
+    BM_CHECK(V_dev || !H_dev, "bm_rbm_rsm_pt_read: H_dev without V_dev");
+    float *const dst[3] = {V_dev, H_dev, nullptr};
+    const int ldd[3] = {h->V, h->H, 0};
+    pt_launch_gather(h->pt, h->stream, h->pt.M, dst, ldd);
+    return pt_read_host(h->pt, h->stream, swaps_host, ladder_idx_host);
+}
+
+// bm_rbm_train_step_pt for a handle with replicated softmax visible units: the same seven steps (a handle with the unit has no
+// dropout, no sparsity penalty, no fast weights and no centering: bm_rbm_set_replicated_softmax).  No host synchronisation.
+int bm_rbm_rsm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
+    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_train_step_pt", false));
+    BM_CHECK(X_dev, "null argument");
+    BM_TRY(check_dw(h, "bm_rbm_rsm_train_step_pt"));
+    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_train_step_pt", true));
+    BM_CHECK(B >= 1 && B <= std::min(h->maxB, h->pt.M), "bm_rbm_rsm_train_step_pt: batch %d outside [1, min(max_batch=%d, n_chains=%d)]",
+             (int)B, h->maxB, h->pt.M);
+    BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
+    static const bool sel_in_pass = !dbg("pt_sel") || atoi(dbg("pt_sel")) != 0;      // BM355_DEBUG=pt_sel=0: a gather launch instead
+    PtEnsemble &e = h->pt;
+    ensure_wt(h);
+    // 1. the v.vb pair of the swap energy under the vb of NOW (the previous update changed it)
+    launch_rsm_pt_rescore(e.v.x.p, e.v.x.ld, e.nrows(), h->V, h->vb.p, e.v.part.p, e.rows, h->stream);
+    // 2. positive phase: the h0 means alone, plain DB with the batch's lengths
+    h->Xin = X_dev; h->Xin_ld = h->V;
+    h->fe_in_chain = false;
+    rsm_lengths_of(h, X_dev, h->V, B, h->rsm_D.p);
+    issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, rbm_out(h, 0, h->h0m.p, nullptr, h->h0m.ld, SITE_H0, 0)));
+    // 3. + 4. the tempered steps; the beta = 1 rows of the chains [0, B) go to vs
+    for (int t = 0; t < k; ++t) rsm_pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
+    if (!sel_in_pass) {
+        float *const dst[3] = {h->vs.p, nullptr, nullptr};
+        const int ldd[3] = {h->vs.ld, 0, 0};
+        pt_launch_gather(e, h->stream, B, dst, ldd);
+    }
+    // 5. negative means: only -h is consumed; plain DB with the CHAINS' lengths Dn_c, c < B
+    {
+        LayerPass neg = rbm_pass(h, true, B, in_of(h->vs), rbm_out(h, 0, nullptr, nullptr, h->hm.ld, SITE_H, 0)).negmeans_out(h->hneg.p);
+        neg.a.row_bmult = h->rp_clen.p;
+        issue(h, neg);
+    }
+    h->hm_is_neg = true;
+    // 6. + 7. the bias block with the two length vectors in front, then the unchanged grad_kernel without its bias tail
+    {
+        ProfScope _ps(h, KC_COLSUM);
+        RbmBiasFusedArgs a;
+        fill_bias_fused(h, B, lr, mom, a);
+        launch_rsm_bias2(a, h->rsm_D.p, h->rp_clen.p, h->stream);
+    }
+    rbm_grad(h, B, 1, (float)B, lr, mom, false);
+    e.step += k;
+    h->call++;
+    BM_HIP(hipGetLastError());
+    return 0;
+}
+
+// the native batch loop of bm_rbm_rsm_train_step_pt
+int bm_rbm_rsm_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t k) {
+    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_train_epoch_pt", false));
+    BM_CHECK(X_dev, "null argument");
+    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
+    for (int64_t s = 0; s < N; s += batch) {
+        const int B = (int)((N - s < batch) ? (N - s) : batch);
+        BM_TRY(bm_rbm_rsm_train_step_pt(h, X_dev + (size_t)s * h->V, B, lr, mom, k));
     }
     return 0;
 }

@@ -78,6 +78,43 @@ struct McAisArgs : McArgs {
 };
 int launch_multinomial_counts_ais(const McAisArgs &a, hipStream_t st);
 
+// ---- the PT flavour of multinomial_counts_kernel (a second template parameter on top of AIS: the plain and the AIS instantiations
+// carry none of it; bm_rbm_rsm_pt_*).  The prop-down of a tempered ensemble, behind a raw pass (kind 2, mult 1) that
+// left Z = h W^T in L:
+//   l[i] = __fadd_rn(__fmul_rn(beta_j, Z[j][i]), __fmul_rn(beta_j, bias[i])),  beta_j = row_mult[j]   - formed on load, never stored;
+//          RT's two rounded multiplies and one rounded add, so that beta_j == 1 gives l = z + b, the plain prop-down's logits
+//          (a null L / a null bias read as zeros: the uniform start of an ensemble)
+//   mx .. the draws: the operation sequence above (the prefix order, the bisection, the index (row0 + j) * max_length + d)
+//   no means are stored (L is read only); it always samples
+//   part: state . dvec as the AIS flavour leaves it (dvec = vb: the visible half of the swap energy, a float32 pair in TWO slots)
+//   sel_out non-null: a row with row_mult[j] == 1.0f and j / sel_R < sel_rows stores its counts a second time at
+//          sel_out + (j / sel_R) * sel_ld (the hand-over of a tempered update: what pt_gather_kernel would copy, bit for bit)
+// A tempered prop-down moves 8 V bytes per row (Z in, counts out) where the plain route moves 12 V (logits in, means and counts out).
+struct McPtArgs : McAisArgs {
+    const float *bias;               // [V] or null
+    const float *row_mult;           // [J]
+    float *sel_out; int sel_ld, sel_R, sel_rows;
+};
+int launch_multinomial_counts_pt(const McPtArgs &a, hipStream_t st);
+
+// ---- the kernels of bm_rsm_pt.hip
+// rsm_pt_start_kernel: row j < rows = M R (chain j / R, slot j % R) gets row_mult[j] = beta[j % R], idx[j] = j % R,
+// len[j] = chain_len[j / R] and, with a V0 [M][V] (dense), the count row of its chain.  V0_len [M] (row_lengths_kernel's sums of
+// V0; null without V0): a chain whose sum is not its length raises RSM_BAD_MISMATCH in *bad
+enum : int { RSM_BAD_MISMATCH = 16 };
+struct RsmPtStartArgs {
+    float *v; int ld;
+    int rows, R, V;
+    const float *V0, *V0_len, *chain_len, *beta;     // [M][V] or null, [M] or null, [M], [R]
+    float *row_mult, *len; int *idx;                 // [rows] each
+    int *bad;
+};
+void launch_rsm_pt_start(const RsmPtStartArgs &a, hipStream_t st);
+// rsm_pt_rescore_kernel: part[row] / part[ld_part + row] = the float32 pair of sum_i (double)x[row][i] * (double)vb[i] in the double
+// three-level order of the count kernel's AIS block (runs of 16, blocks of 16 runs, the blocks ascending; the padding adds exact
+// zeros) from the counts IN MEMORY: the bits the count kernel leaves under the same vb
+void launch_rsm_pt_rescore(const float *x, int ld, int rows, int V, const float *vb, float *part, int ld_part, hipStream_t st);
+
 // ---- rsm_fill_rows_kernel: L[j][i] = a[i] for j < J, i < V - the logits rows of the AIS start, v_0 ~ Multinomial(D_j, softmax(a))
 void launch_rsm_fill_rows(float *L, int ld, int J, int V, const float *a, hipStream_t st);
 
@@ -90,5 +127,9 @@ void launch_rsm_fill_rows(float *L, int ld, int J, int V, const float *a, hipStr
 // the plain column sum in the update of hb / dhb and in the published raw tail.
 struct RbmBiasFusedArgs;
 void launch_rsm_bias(const RbmBiasFusedArgs &a, const float *lengths, hipStream_t st);
+// the two-length flavour (the tempered update): the negative rows are chains with lengths of their own, lengths_neg
+// [B]; the term of row b is __fsub_rn(__fmul_rn(D_b, h0[b][h]), __fmul_rn(Dn_b, hk[b][h])) (from the negated store:
+// __fadd_rn(__fmul_rn(D_b, h0), __fmul_rn(Dn_b, -hk)), the same bits), summed as above.  A kernel of its own (rsm_bias2_kernel)
+void launch_rsm_bias2(const RbmBiasFusedArgs &a, const float *lengths, const float *lengths_neg, hipStream_t st);
 
 }  // namespace bm

@@ -46,8 +46,11 @@ void launch_row_lengths(const RowLenArgs &a, hipStream_t st) {
 // for unaligned rows.  Level 1 of the prefix order runs in the 16-lane groups of a wave (15 dependent shuffle steps, every group
 // of the workgroup at once), level 2 in thread 0 over at most 64 block totals.
 // AIS (bm_rsm.h: McAisArgs): behind the draws the row's state . dvec from the counts in LDS, in double, as a float32 pair.
-template <int RPT, bool AIS = false>
-__global__ __launch_bounds__(256) void multinomial_counts_kernel(std::conditional_t<AIS, McAisArgs, McArgs> a) {
+// PT (bm_rsm.h: McPtArgs; on top of AIS): the logits are formed on load from the raw z, the bias and the row's temperature and never
+// stored, no means are stored, the beta = 1 row of a chain repeats its counts in the dense particle store.
+template <int RPT, bool AIS = false, bool PT = false>
+__global__ __launch_bounds__(256) void multinomial_counts_kernel(std::conditional_t<PT, McPtArgs, std::conditional_t<AIS, McAisArgs, McArgs>> a) {
+    static_assert(AIS || !PT, "the PT flavour sits on top of the AIS flavour");
     constexpr int CAP = RPT * 4096;
     __shared__ __attribute__((aligned(16))) float s_c[CAP];
     __shared__ __attribute__((aligned(16))) int s_cnt[CAP];
@@ -59,10 +62,35 @@ __global__ __launch_bounds__(256) void multinomial_counts_kernel(std::conditiona
     constexpr float NEG = -3.402823466e38f;
     float v[RPT][16];
     float mx = NEG;
+    float beta = 1.0f;
+    (void)beta;
+    if constexpr (PT) beta = a.row_mult[row];
 #pragma unroll
     for (int p = 0; p < RPT; ++p) {
         const int i0 = (p * 256 + tid) * 16;
-        if (al && i0 + 16 <= V) {
+        if constexpr (PT) {
+            // l = fl(fl(beta z) + fl(beta b)): RT's two rounded multiplies and one rounded add (a null L / bias reads as zeros)
+            if (i0 < V) {
+                if (a.L && al && i0 + 16 <= V) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float4 t = *reinterpret_cast<const float4 *>(l + i0 + 4 * q);
+                        v[p][4 * q] = t.x; v[p][4 * q + 1] = t.y; v[p][4 * q + 2] = t.z; v[p][4 * q + 3] = t.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) v[p][k] = (a.L && i0 + k < V) ? l[i0 + k] : 0.0f;
+                }
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const float b = (a.bias && i0 + k < V) ? a.bias[i0 + k] : 0.0f;
+                    v[p][k] = (i0 + k < V) ? __fadd_rn(__fmul_rn(beta, v[p][k]), __fmul_rn(beta, b)) : NEG;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) v[p][k] = NEG;
+            }
+        } else if (al && i0 + 16 <= V) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float4 t = *reinterpret_cast<const float4 *>(l + i0 + 4 * q);
@@ -131,6 +159,7 @@ __global__ __launch_bounds__(256) void multinomial_counts_kernel(std::conditiona
     const bool counts = st && a.sample;
 #pragma unroll
     for (int p = 0; p < RPT; ++p) {
+        if constexpr (PT) break;                        // no means: the logits of a tempered row do not touch memory
         const int i0 = (p * 256 + tid) * 16;
         if (i0 >= V) continue;
 #pragma unroll
@@ -187,6 +216,12 @@ __global__ __launch_bounds__(256) void multinomial_counts_kernel(std::conditiona
             for (int k = 0; k < 16; ++k) if (i0 + k < V) st[i0 + k] = (float)s_cnt[i0 + k];
         }
     }
+    if constexpr (PT) {                                 // the hand-over: the chain's beta = 1 row, chains c < sel_rows (uniform over the workgroup)
+        if (a.sel_out && beta == 1.0f && row / a.sel_R < a.sel_rows) {
+            float *so = a.sel_out + (size_t)(row / a.sel_R) * a.sel_ld;
+            for (int i = tid; i < V; i += 256) so[i] = (float)s_cnt[i];
+        }
+    }
     if constexpr (AIS) {
         // state . dvec in double, by the three levels of the prefix order (bm_rsm.h): every product is exact, the padding adds zeros
         __shared__ double s_dr[RPT * 256], s_db[RPT * 16];
@@ -231,6 +266,19 @@ int launch_multinomial_counts_ais(const McAisArgs &a, hipStream_t st) {
     return 0;
 }
 
+int launch_multinomial_counts_pt(const McPtArgs &a, hipStream_t st) {
+    if (a.V < 2 || a.V > RSM_MAX_V || !a.sample || !a.states || !a.dvec || !a.part || a.ld_part < a.J || !a.row_mult ||
+        (a.sel_out && (a.sel_R < 1 || a.sel_rows < 0 || a.sel_ld < a.V))) {
+        fprintf(stderr, "bm355: the PT flavour of multinomial_counts_kernel draws the counts of rows of 2 to %d units (got %d) under a temperature "
+                "per row and leaves their state . dvec: it needs states, dvec, row_mult and partials of pitch >= J\n", RSM_MAX_V, a.V);
+        return 1;
+    }
+    if (a.J < 1) return 0;
+    if (a.V <= 4096) hipLaunchKernelGGL((multinomial_counts_kernel<1, true, true>), dim3(a.J), dim3(256), 0, st, a);
+    else             hipLaunchKernelGGL((multinomial_counts_kernel<4, true, true>), dim3(a.J), dim3(256), 0, st, a);
+    return 0;
+}
+
 // ---- rsm_fill_rows_kernel (bm_rsm.h): L[j][i] = a[i]
 __global__ __launch_bounds__(256) void rsm_fill_rows_kernel(float *L, int ld, int J, int V, const float *a) {
     const size_t n = (size_t)J * (size_t)V;
@@ -259,7 +307,11 @@ int launch_multinomial_counts(const McArgs &a, hipStream_t st) {
 }
 
 // ---- rsm_bias_kernel (bm_rsm.h): the grid of rbm_bias_fused_kernel; a visible group is rbm_bias_fused_block itself
-__global__ __launch_bounds__(NT) void rsm_bias_kernel(RbmBiasFusedArgs a, const float *lengths) {
+// TWO (the tempered update): the negative rows have lengths of their own, lengths_neg [B] - the term of row b is
+// __fsub_rn(__fmul_rn(D_b, h0), __fmul_rn(Dn_b, hk)), from the negated store __fadd_rn(__fmul_rn(D_b, h0), __fmul_rn(Dn_b, -hk)): the
+// same bits.  A compile-time flavour: the kernel of the CD path carries none of it
+template <bool TWO>
+__device__ __forceinline__ void rsm_bias_body(const RbmBiasFusedArgs &a, const float *lengths, const float *lengths_neg) {
     __shared__ __attribute__((aligned(16))) float smem[CS_SMEM_FLOATS];
     __shared__ float s_w[64];
     float *s_t = smem;                                  // [64][64] terms of a chunk of rows, ahead of block_colsum's use of smem
@@ -280,8 +332,13 @@ __global__ __launch_bounds__(NT) void rsm_bias_kernel(RbmBiasFusedArgs a, const 
                 float t = 0.f;
                 if (b < a.B && h < a.u.H) {
                     const float p = a.h0m[(size_t)b * a.ldh0 + h], n = a.hm[(size_t)b * a.ldh + h];
-                    const float d = a.hm_negated ? __fadd_rn(p, n) : __fsub_rn(p, n);
-                    t = __fmul_rn(lengths[b], d);
+                    if constexpr (TWO) {
+                        const float tp = __fmul_rn(lengths[b], p), tn = __fmul_rn(lengths_neg[b], n);
+                        t = a.hm_negated ? __fadd_rn(tp, tn) : __fsub_rn(tp, tn);
+                    } else {
+                        const float d = a.hm_negated ? __fadd_rn(p, n) : __fsub_rn(p, n);
+                        t = __fmul_rn(lengths[b], d);
+                    }
                 }
                 s_t[r * 64 + col] = t;
             }
@@ -318,6 +375,13 @@ __global__ __launch_bounds__(NT) void rsm_bias_kernel(RbmBiasFusedArgs a, const 
             }
         }
     }
+}
+__global__ __launch_bounds__(NT) void rsm_bias_kernel(RbmBiasFusedArgs a, const float *lengths) { rsm_bias_body<false>(a, lengths, nullptr); }
+__global__ __launch_bounds__(NT) void rsm_bias2_kernel(RbmBiasFusedArgs a, const float *lengths, const float *lengths_neg) {
+    rsm_bias_body<true>(a, lengths, lengths_neg);
+}
+void launch_rsm_bias2(const RbmBiasFusedArgs &a, const float *lengths, const float *lengths_neg, hipStream_t st) {
+    hipLaunchKernelGGL(rsm_bias2_kernel, dim3((a.u.V + 63) / 64 + (a.u.H + 63) / 64), dim3(NT), 0, st, a, lengths, lengths_neg);
 }
 void launch_rsm_bias(const RbmBiasFusedArgs &a, const float *lengths, hipStream_t st) {
     hipLaunchKernelGGL(rsm_bias_kernel, dim3((a.u.V + 63) / 64 + (a.u.H + 63) / 64), dim3(NT), 0, st, a, lengths);

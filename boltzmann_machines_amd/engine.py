@@ -105,6 +105,51 @@ class RbmGroupsPt(_PtCalls):
         check(self.lib.bm_rbm_groups_train_epoch_pt(self._h, Xd.offset_ptr(row * self.V), N, batch, lr, momentum, k))
 
 
+class RbmRsmPt(RbmGroupsPt):
+    """The tempered ensemble of an RbmEngine with replicated softmax visible units (bm355.h: bm_rbm_rsm_pt_* / _train_step_pt /
+    _train_epoch_pt): pt_init / pt_sweep / pt_read and the two tempered updates under the prefix 'bm_rbm_rsm', on
+    the engine's handle.  pt_init takes the chains' document lengths; `train_lengths` holds those of the ensemble that the next
+    tempered `fit` builds (rbm.py: set_count_tempering).  Every other attribute is the engine's."""
+    _pt_prefix, _pt_n_hidden = 'bm_rbm_rsm', 1
+    train_lengths = None
+
+    def pt_init(self, n_chains, betas, V0_d=None, chain0=0, lengths=None):
+        """build the tempered ensemble of n_chains x len(betas) replicas; lengths [n_chains]: the chains' document lengths
+        (None: `train_lengths`); V0_d [n_chains, V] count rows of those lengths, None: v_0 ~ Multinomial(D_c, uniform)"""
+        b = np.ascontiguousarray(betas, dtype=np.float32).ravel()
+        D = self.train_lengths if lengths is None else lengths
+        if D is None:
+            raise ValueError('pt_init: the chains of a count ensemble need their document lengths')
+        D = np.ascontiguousarray(D, dtype=np.float32).ravel()
+        if len(D) != int(n_chains):
+            raise ValueError('pt_init: %d lengths for %d chains' % (len(D), int(n_chains)))
+        check(self.lib.bm_rbm_rsm_pt_init(self._h, int(n_chains), len(b), b.ctypes.data_as(C.c_void_p), D.ctypes.data_as(C.c_void_p),
+                                          V0_d.ptr if V0_d is not None else None, int(chain0)))
+        self._pt_shape = (int(n_chains), len(b))
+        self._pt_train_key = None
+
+    def pt_state(self):
+        """RbmGroupsPt.pt_state with part_v [2, M R] (the float32 pair hi, lo of the double v.vb) and len [M R]"""
+        M, R = self._pt_shape
+        rows, eng = M * R, self._engine
+        shapes = dict(v=(rows, eng.V), h=(rows, eng.H), part_v=(2, rows), part_h=((eng.H + 15) // 16, rows), mult=(rows,), len=(rows,))
+        out = {}
+        for name, shape in shapes.items():
+            a = np.empty(shape, dtype=np.float32)
+            check(self.lib.bm_rbm_get_param(self._h, ('pt_' + name).encode(), a.ctypes.data_as(C.c_void_p), a.size))
+            out[name] = a
+        swaps, idx = self.pt_read()
+        out.update(idx=idx.reshape(-1), swaps=swaps)
+        return out
+
+    def train_step_pt(self, Xd, B, lr, momentum, k, row=0):
+        check(self.lib.bm_rbm_rsm_train_step_pt(self._h, Xd.offset_ptr(row * self.V), B, lr, momentum, k))
+
+    def train_epoch_pt(self, Xd, N, batch, lr, momentum, k, row=0):
+        """N rows starting at `row`, consecutive batches of `batch` rows, one tempered update each, driven from C"""
+        check(self.lib.bm_rbm_rsm_train_epoch_pt(self._h, Xd.offset_ptr(row * self.V), N, batch, lr, momentum, k))
+
+
 class RbmGaussPt(_PtCalls):
     """The tempered ensemble of an RbmEngine with Gaussian visible units (bm355.h: bm_rbm_gauss_pt_*): pt_init /
     pt_sweep / pt_read under the prefix 'bm_rbm_gauss', on the engine's handle.  V0_d of pt_init and the rows pt_read hands out are
@@ -374,6 +419,21 @@ class RbmEngine(_PtCalls):
         if view is None:
             view = self.__dict__['_groups_pt'] = RbmGroupsPt(self)
         return view
+
+    @property
+    def rsm_pt(self):
+        """the tempered ensemble of a handle with replicated softmax visible units and its calls (RbmRsmPt), one object per engine"""
+        view = self.__dict__.get('_rsm_pt')
+        if view is None:
+            view = self.__dict__['_rsm_pt'] = RbmRsmPt(self)
+        return view
+
+    def debug_rsm_up(self, Vd, J, Dd, beta, per_row, Hd, part_d=None):
+        """launch-level probe (tests; bm_debug_rsm_up): the tempered prop-up of the J count rows of Vd with lengths Dd into Hd at
+        site 4 of the current call - per_row: the DB + RT pass with every row at `beta` (its energy partials into part_d
+        [ceil(H/16), J]), else the existing DB pass at mult == bmult == beta; the call counter does not advance"""
+        check(self.lib.bm_debug_rsm_up(self._h, Vd.ptr, int(J), Dd.ptr, float(beta), int(bool(per_row)), Hd.ptr,
+                                       part_d.ptr if part_d is not None else None))
 
     def rsm_ais(self, n_betas, lengths, k, seed, chain0=0, base_logits=None):
         """[len(lengths)] float32 per-chain AIS estimates of log Z_D of a handle with replicated softmax visible units, chain r

@@ -1597,7 +1597,9 @@ class ReplicatedSoftmaxVisible(object):
     (1/N) sum_b D_b (h0_b - hk_b).  `fit`, `transform`, `sample_h`, checkpoints, `load_model` and `init_from` work as for the
     other classes; `sample_v_from_h` and `sample_v` take the documents' lengths; `free_energy` gives F per row; `encode` turns
     lists of token ids into count rows; `ais_log_Z` / `ais_log_Z_rows` estimate log Z per document length by AIS, and
-    `log_likelihood` / `perplexity` score held-out documents with it.  What is not built for word counts is refused with a ValueError before the engine is
+    `log_likelihood` / `perplexity` score held-out documents with it; `sample_v_tempered` samples documents by
+    parallel tempering and `set_count_tempering` makes `fit` take its negative particles from a tempered ensemble (DESIGN.md
+    3.31).  What is not built for word counts is refused with a ValueError before the engine is
     touched: the `pll` and `feg` metrics, `dropout`, a non-zero `sparsity_cost`, `dbm_first` / `dbm_last`, dtype='float64',
     `set_negative_phase` other than 'cd', `set_centering`, `set_classes`, `sample_v_given`, `log_Z` / `log_proba`,
     BM355_DATA_PARALLEL jobs, and use as a layer of a `DBM` or a `StackClassifier`."""
@@ -1836,7 +1838,7 @@ class ReplicatedSoftmaxVisible(object):
         return np.ascontiguousarray(D, dtype=np.float32)
 
     def fit(self, X, X_val=None, *args, **kwargs):
-        self._counts_of(X, 'fit')
+        self._fit_lengths = self._counts_of(X, 'fit')[1]       # (set_count_tempering: the chains' lengths come from these)
         if X_val is not None:
             self._counts_of(X_val, 'fit')
         return super(ReplicatedSoftmaxVisible, self).fit(X, X_val, *args, **kwargs)
@@ -1919,6 +1921,121 @@ class ReplicatedSoftmaxVisible(object):
         finally:
             eng.set_row_offset(0)
         return Vd.numpy()
+
+    # ---- parallel tempering and the tempered negative phase
+    def sample_v_tempered(self, n_samples, lengths, n_gibbs_steps=1000, n_temperatures=10, betas=None, V_init=None, return_stats=False):
+        """Unconditional documents of given lengths by parallel tempering (replica exchange), as `BernoulliRBM.sample_v`:
+        `n_samples` independent chains, each with one replica per temperature of the ladder 0 < betas[0] < ... < betas[-1] = 1,
+        run `n_gibbs_steps` steps of (h ~ Ber(sigmoid(beta (D hb + vW))), exchange of neighbouring temperatures,
+        v ~ Multinomial(D, softmax(beta (vb + W h)))); the replica at beta = 1 of every chain is returned as count rows
+        [n_samples, n_visible], every row summing to its length.  The multinomial coefficient is the base measure and is not
+        tempered; all replicas of a chain share its length.  The hot replicas cross between the topic mixtures the
+        single-temperature `sample_v` stays in.
+
+        lengths : the documents' lengths D, one integer or [n_samples] integers in [1, max_length].
+        betas : the ladder; None: float32(linspace(0, 1, n_temperatures + 1)[1:]).  `n_temperatures=1` is plain Gibbs.
+        V_init : [n_samples, n_visible] count rows of those lengths, the start of every chain (all its replicas); None: D tokens
+        drawn uniformly over the vocabulary on the device under the call's seed.
+        With `return_stats` also the acceptance rate of every neighbouring pair of temperatures, [n_temperatures - 1].
+        Both layers are always sampled.  One seed is drawn from the model's host stream; no parameter is changed.  It replaces
+        the ensemble of `set_count_tempering`, which the next `fit` builds again."""
+        n_samples, n_gibbs_steps = int(n_samples), int(n_gibbs_steps)
+        if n_samples < 1 or n_gibbs_steps < 1:
+            raise ValueError('`n_samples` and `n_gibbs_steps` must be >= 1 (got {0}, {1})'.format(n_samples, n_gibbs_steps))
+        D, scalar = self._ais_lengths(lengths, 'sample_v_tempered')
+        D = np.repeat(D, n_samples) if scalar else D
+        if len(D) != n_samples:
+            raise ValueError('%s.sample_v_tempered: `lengths` must be one integer or one per sample (%d for %d samples)'
+                             % (self.__class__.__name__, len(D), n_samples))
+        ladder = resolve_ladder(n_temperatures, betas)
+        if V_init is not None:
+            V_init, D0 = self._counts_of(V_init, 'sample_v_tempered')
+            if V_init.shape != (n_samples, self.n_visible) or np.any(D0 != D):
+                raise ValueError('`V_init` must be [{0}, {1}] count rows of the given lengths'.format(n_samples, self.n_visible))
+        return self._sample_v_tempered_checked(n_samples, D, n_gibbs_steps, ladder, V_init, return_stats)
+
+    @run_on_engine(update_seed=True)
+    def _sample_v_tempered_checked(self, n_samples, D, n_gibbs_steps, ladder, V_init, return_stats):
+        view = self._on_device().rsm_pt
+        V0d = _ffi.DeviceArray.from_numpy(V_init, np.float32) if V_init is not None else None
+        view.pt_init(n_samples, ladder, V0d, lengths=D)
+        view.pt_sweep(n_gibbs_steps)
+        Vd = _ffi.DeviceArray((n_samples, self.n_visible), np.float32)
+        swaps, _ = view.pt_read(Vd)
+        V = Vd.numpy()
+        return (V, acceptance_rates(swaps)) if return_stats else V
+
+    def _check_tempered_setting(self, what):
+        self._check_rsm_config(what)
+        if os.environ.get('BM355_DATA_PARALLEL', '0') == '1':
+            self._rsm_refuse(what, 'a tempered negative phase in data-parallel mode (BM355_DATA_PARALLEL: chains are not sharded '
+                                   'over ranks) is not built')
+
+    def set_count_tempering(self, enabled=True, n_temperatures=10, betas=None, n_chains=None, chain_lengths=None):
+        """Where the negative particles of `fit` come from: `enabled=True` - the beta = 1 replicas of a persistent tempered
+        ensemble of `n_chains` chains (None: `batch_size`; at least `batch_size`) over the ladder `betas` (None:
+        float32(linspace(0, 1, n_temperatures + 1)[1:])), every update sweeping all of it for `n_gibbs_steps` tempered steps -
+        `BernoulliRBM.set_negative_phase('tempered')` with the count sampler of `sample_v_tempered`; `enabled=False` - CD-k from
+        the batch again.
+
+        chain_lengths : [n_chains] integers in [1, max_length], the document length of every chain, fixed for the life of the
+        ensemble; None: the lengths of the first `n_chains` rows of the `X` of the `fit` call, cycled.  The chains' lengths STAND
+        FOR THE CORPUS'S LENGTH DISTRIBUTION in the negative term: negative particle b of an update is a document of chain b's
+        length, not of batch row b's, and its hidden-bias statistic is weighted by that length (D_b h0_b - Dn_b hk_b).  Take
+        them from the corpus (the default) unless there is a reason not to.
+
+        The ensemble starts at uniform tokens at the first update of every `fit()` call and again whenever the ladder, `n_chains`
+        or the chains' lengths changed; no extra seed is drawn; `tempering_stats()` reports its swap acceptance.  Neither the
+        ensemble nor this setting is written to checkpoints.  `set_negative_phase('tempered')` itself stays refused for this
+        class.  Returns self."""
+        self._fast_weights = None
+        if not enabled:
+            self._neg_phase = None
+            self._count_chain_lengths = None
+            return self
+        self._check_tempered_setting('set_count_tempering')
+        if chain_lengths is not None:
+            D, scalar = self._ais_lengths(chain_lengths, 'set_count_tempering')
+            want = int(self.batch_size if n_chains is None else n_chains)
+            if scalar or len(D) != want:
+                raise ValueError('%s.set_count_tempering: `chain_lengths` must hold one length per chain (%d chains)'
+                                 % (self.__class__.__name__, want))
+            chain_lengths = tuple(int(d) for d in D)
+        self._set_negative_phase('tempered', n_temperatures, betas, n_chains)
+        self._count_chain_lengths = chain_lengths
+        return self
+
+    def _train_chain_lengths(self):
+        n_chains = self._neg_phase[1]
+        given = getattr(self, '_count_chain_lengths', None)
+        if given is not None:
+            return tuple(given)
+        D = getattr(self, '_fit_lengths', None)
+        if D is None or not len(D):
+            raise RuntimeError('set_count_tempering: no chain lengths (fit() takes them from its X)')
+        return tuple(int(d) for d in np.resize(D, n_chains))
+
+    def _ensure_train_ensemble(self, eng):
+        """`eng` is the engine's rsm_pt view; a change of the chains' lengths builds the ensemble again"""
+        D = self._train_chain_lengths()
+        if getattr(eng, '_train_len_key', None) != D:
+            self._pt_fresh = True
+        eng.train_lengths, eng._train_len_key = np.asarray(D, dtype=np.float32), D
+        return super(ReplicatedSoftmaxVisible, self)._ensure_train_ensemble(eng)
+
+    def _train_epoch_tempered(self, eng, *args, **kwargs):
+        # (the ensemble and its updates live under the engine's rsm prefix; everything else the epoch calls is the engine's)
+        return super(ReplicatedSoftmaxVisible, self)._train_epoch_tempered(eng.rsm_pt, *args, **kwargs)
+
+    def tempering_stats(self):
+        """Acceptance rate (accepts / attempts) of every neighbouring pair of temperatures, [n_temperatures - 1], since the
+        ensemble of `set_count_tempering` was built.  Waits for the device; copies no states."""
+        eng = self._engine
+        view = eng.rsm_pt if eng is not None and hasattr(eng, 'rsm_pt') else None
+        if view is None or getattr(view, '_pt_train_key', None) is None:
+            raise RuntimeError('`tempering_stats`: no tempered ensemble (call set_count_tempering() and fit first)')
+        swaps, _ = view.pt_read()
+        return acceptance_rates(swaps)
 
 
 class ReplicatedSoftmaxRBM(ReplicatedSoftmaxVisible, BaseRBM):

@@ -293,6 +293,35 @@ int bm_rbm_groups_pt_sweep(bm_rbm *h, int32_t n_steps);
 int bm_rbm_groups_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host);
 int bm_rbm_groups_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t n_gibbs_steps);
 int bm_rbm_groups_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t n_gibbs_steps);
+/* Parallel tempering over replicated softmax visible units: bm_rbm_pt_* for a handle with the unit
+ * (bm_rbm_set_replicated_softmax).  The tempered family over count vectors of length D is p_beta(v, h) ~ (D!/prod v_i!)
+ * exp(-beta E(v, h)), E = -v W h - v.vb - D h.hb (the coefficient is the base measure, not tempered): h_j | v ~ Ber(sigmoid(beta (D hb_j
+ * + (vW)_j))), v | h ~ Multinomial(D, softmax(beta (vb + W h))).  Chain c has the length lengths_host[c], an integer in [1, max_length],
+ * shared by its n_temps replicas (ensemble row c * n_temps + r), so the exchange rule is bm_rbm_pt_sweep's.  V0_dev [n_chains][V]
+ * (dense count rows whose sums are the lengths - checked on the device, a mismatch is refused) starts every replica of a chain at its
+ * row; null: v_0 ~ Multinomial(D_c, uniform) at site 11 of the handle's seed and call counter.  A step t of a call: the prop-up at site
+ * 4 + 16 t, the exchange at site 10 + 16 t, the prop-down at site 3 + 16 t, draw d of global row (chain0 + c) n_temps + r at flat index
+ * row * max_length + d; the call counter and the step parity follow bm_rbm_pt_sweep: chains [chain0, chain0 + n_chains) of a larger
+ * ensemble give the bits they would give there.  bm_rbm_rsm_pt_read is bm_rbm_pt_read.  bm_rbm_rsm_train_step_pt /
+ * _train_epoch_pt: bm_rbm_train_step_pt / _train_epoch_pt with the negative particles of the chains [0, B); the positive rows carry
+ * the batch's lengths, the negative rows the chains' lengths (the hidden-bias term of row b is D_b h0 - Dn_b hk).  bm_rbm_get_param
+ * hands out "pt_v", "pt_h", "pt_part_v" [2][rows] (the float32 pair hi, lo of the double v.vb), "pt_part_h", "pt_mult" and "pt_len"
+ * [rows].  The handle keeps ONE ensemble: bm_rbm_pt_init refuses a handle with the unit, bm_rbm_set_replicated_softmax refuses a
+ * handle that holds a Bernoulli ensemble, bm_rbm_set_replicated_softmax(h, 0) discards a count ensemble.  Refused with an error that
+ * leaves the handle usable: a handle without the unit, sweep / read / update before init, lengths outside [1, max_length], B outside
+ * [1, min(max_batch, n_chains)], n_steps or n_gibbs_steps < 1, a bad ladder.  Float32, one process. */
+int bm_rbm_rsm_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *lengths_host,
+                       const float *V0_dev, int64_t chain0);
+int bm_rbm_rsm_pt_sweep(bm_rbm *h, int32_t n_steps);
+/* Launch-level probe of the tempered prop-ups of this unit (tests): h ~ Ber(sigmoid(beta (v W + D_j hb))) of the J rows of V_dev
+ * [J][V] with lengths_dev [J] into H_dev [J][H], at site 4, step 0 of the handle's seed, call counter and row offset; the counter does
+ * not advance.  per_row != 0: the pass of bm_rbm_rsm_pt_sweep with every row at beta (its energy partials to part_dev [ceil(H/16)][J]
+ * unless null); per_row == 0: the pass of bm_rbm_rsm_ais at the launch-uniform beta.  The two give the same bits. */
+int bm_debug_rsm_up(bm_rbm *h, const float *V_dev, int32_t J, const float *lengths_dev, float beta, int32_t per_row, float *H_dev,
+                    float *part_dev);
+int bm_rbm_rsm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host);
+int bm_rbm_rsm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t n_gibbs_steps);
+int bm_rbm_rsm_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t n_gibbs_steps);
 /* AIS estimates of the log partition functions of an RBM with replicated softmax visible units.  The partition
  * function depends on the document length, Z_D = sum_h exp(D h.hb) (sum_i exp(vb_i + (W h)_i))^D, so every chain has a length of
  * its own: row r is ONE chain over count vectors of lengths_host[r] tokens, an integer in [1, max_length]; chains of different
