@@ -2,6 +2,7 @@
 // (bm_kernels.h; their launchers and the launch tuner in bm_launch.h, included at its end) shared by the RBM and DBM entry
 // points, so both are compiled together; bm_rbm64.hip / bm_dbm64.hip are the float64 paths (own small kernels).
 #include "bm_rbm.hip"
+#include "bm_rbm_pt.hip"      // (the tempered entries of the RBM handle: part of this unit, it uses bm_rbm.hip's statics)
 #include "bm_dbm.hip"
 #include "bm_rbm64.hip"
 #include "bm_dbm64.hip"

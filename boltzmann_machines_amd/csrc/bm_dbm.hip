@@ -1283,8 +1283,7 @@ int bm_dbm_pt_sweep(bm_dbm *h, int32_t n_steps) {
     BM_CHECK(h->pt.M > 0, "bm_dbm_pt_sweep: no ensemble (call bm_dbm_pt_init first)");
     BM_TRY(check_pt_model(h, "bm_dbm_pt_sweep"));  // (the literal-sigmoid mode may have been switched on since the init)
     BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
-    for (int t = 0; t < n_steps; ++t) pt_step(h, t);
-    h->pt.step += n_steps;
+    pt_sweep_with(h->pt, n_steps, [&](int t) { pt_step(h, t); });
     h->call++;
     BM_HIP(hipGetLastError());
     return 0;
@@ -1297,8 +1296,7 @@ int bm_dbm_pt_read(bm_dbm *h, float *V_dev, float *H1_dev, float *H2_dev, int64_
     BM_CHECK(V_dev || !H1_dev, "bm_dbm_pt_read: H1_dev without V_dev");
     float *const dst[3] = {V_dev, H1_dev, H2_dev};
     const int ldd[3] = {h->V, h->n[1], h->L == 2 ? h->n[2] : 0};
-    pt_launch_gather(h->pt, h->stream, h->pt.M, dst, ldd);               // (one launch for the up to three matrices)
-    return pt_read_host(h->pt, h->stream, swaps_host, ladder_idx_host);
+    return pt_read_with(h->pt, h->stream, dst, ldd, swaps_host, ladder_idx_host);        // (one gather launch for the up to three matrices)
 }
 
 // One update whose negative particles are the beta = 1 rows of the tempered ensemble (bm355.h): bm_dbm_train_step

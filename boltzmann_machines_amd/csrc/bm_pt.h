@@ -2,8 +2,9 @@
 // (PtEnsemble: up to three layers of states and slot partials, the rows' temperatures and ladder indices, the ladder, the swap
 // counters), the checks of a ladder, the start of an ensemble, and the small kernels with their launches - the slot partial of a
 // state . bias product in the epilogue's order, the start, the replica exchange, the re-scoring of the partials under moved
-// biases, the gather of the beta = 1 rows, the read-out of counters and ladder indices.  An engine adds its model's check, its
-// row-tempered passes and their order within a step, and its Philox sites (bm_rbm.hip, bm_dbm.hip).
+// biases, the gather of the beta = 1 rows, the read-out of counters and ladder indices, the sweep loop and the read tail.  An
+// engine adds its model's check, its row-tempered passes and their order within a step, and its Philox sites (bm_rbm_pt.hip,
+// bm_dbm.hip).
 #pragma once
 #include "bm_common.h"
 #include "bm_rng.h"
@@ -266,6 +267,28 @@ static inline int pt_read_host(PtEnsemble &e, hipStream_t stream, int64_t *swaps
     }
     if (ladder_idx_host) BM_HIP(hipMemcpy(ladder_idx_host, e.idx.p, (size_t)e.nrows() * sizeof(int32_t), hipMemcpyDeviceToHost));
     return 0;
+}
+
+// the body of a *_pt_sweep: step(t) for the n_steps steps of the call, then the global step number moves on (the caller's checks
+// come before it, its call counter and hipGetLastError after it)
+template <class StepFn>
+static inline void pt_sweep_with(PtEnsemble &e, int n_steps, StepFn &&step) {
+    for (int t = 0; t < n_steps; ++t) step(t);
+    e.step += n_steps;
+}
+
+// the body of a *_pt_read: the gather of every chain's beta = 1 row, what the engine does to the gathered rows in stream order
+// (after_gather; the Gaussian unit scales them), pt_read_host
+template <class AfterFn>
+static inline int pt_read_with(PtEnsemble &e, hipStream_t stream, float *const dst[3], const int ldd[3], int64_t *swaps_host,
+                               int32_t *ladder_idx_host, AfterFn &&after_gather) {
+    pt_launch_gather(e, stream, e.M, dst, ldd);
+    after_gather();
+    return pt_read_host(e, stream, swaps_host, ladder_idx_host);
+}
+static inline int pt_read_with(PtEnsemble &e, hipStream_t stream, float *const dst[3], const int ldd[3], int64_t *swaps_host,
+                               int32_t *ladder_idx_host) {
+    return pt_read_with(e, stream, dst, ldd, swaps_host, ladder_idx_host, [] {});
 }
 
 #endif  // BM_KERNELS_ONLY

@@ -58,6 +58,9 @@ static int xchg_check_status(bm_xchg *x);                    // error when a wai
 static void xchg_bind_user(bm_xchg *x, bm_xchg **slot);      // the engine field that points at x (cleared by bm_xchg_destroy)
 static void xchg_dw_replaced(bm_xchg *x);                    // every replica's dW was overwritten whole (set_param)
 
+// the visible unit whose entries built the handle's tempered ensemble (bm_rbm::pt_unit)
+enum PtUnit { PT_NONE = 0, PT_BERNOULLI, PT_GROUPS, PT_COUNTS, PT_GAUSS };
+
 struct bm_rbm {
     bm_rbm_config cfg;
     bm_xchg *xchg_used = nullptr;     // the direct exchange this engine's gradients last went through (bm_rbm_sync checks it)
@@ -159,35 +162,31 @@ struct bm_rbm {
     int ra_rows = 0;
     Mat ra_l;
     DevBuf ra_len, ra_dot;
-    // bm_rbm_pt_*: the tempered ensemble (bm_pt.h; layers v and h1), allocated on demand - max_batch does not bound it; nothing
-    // else in the handle reads or writes it
+    // The tempered ensemble of the handle (bm_pt.h; layers v and h1; bm_rbm_pt.hip), allocated on demand - max_batch
+    // does not bound it; nothing else in the handle reads or writes it.  A handle holds at most one, and pt_unit says which visible
+    // unit's entries built it (bm_rbm_pt_*, bm_rbm_groups_pt_*, bm_rbm_rsm_pt_*, bm_rbm_gauss_pt_*): PT_NONE while pt.M == 0 (pt_drop),
+    // the family's tag once its *_pt_init went through; every other tempered entry asks for an ensemble of its own unit
     PtEnsemble pt;
-    // bm_rbm_groups_pt_* (DESIGN.md 3.29), the generic route only: the raw z = h W^T [gp_rows][V] of the ensemble's prop-down,
-    // allocated with the ensemble; nothing else reads or writes it
-    int gp_rows = 0;
-    Mat gp_z;
-    // bm_rbm_rsm_pt_* (DESIGN.md 3.31): the ensemble is `pt` with a two-slot visible partial array; rp_z: the raw z = h W^T
-    // [rp_rows][V] of its prop-down; rp_len [rp_rows]: the document length of every ensemble row (len[c R + r] = D_c); rp_clen
-    // [rp_rows]: the chains' lengths D_c, dense; rp_v0len: the row sums of a V0.  rsm_pt: the ensemble in `pt` is a count ensemble
+    PtUnit pt_unit = PT_NONE;
+    // the raw z = h W^T [ptz_rows][V] of the ensemble's prop-down where it takes more than one launch (the generic routes of the
+    // groups and of the Gaussian unit, the count unit always), allocated with the ensemble; grows only (ensure_pt_z)
+    int ptz_rows = 0;
+    Mat pt_z;
+    // bm_rbm_rsm_pt_* (DESIGN.md 3.31): the ensemble has a two-slot visible partial array; rp_len [rp_rows]: the document length of
+    // every ensemble row (len[c R + r] = D_c); rp_clen [rp_rows]: the chains' lengths D_c, dense; rp_v0len: the row sums of a V0
     int rp_rows = 0;
-    bool rsm_pt = false;
-    Mat rp_z;
     DevBuf rp_len, rp_clen, rp_v0len, rp_probe;      // (rp_probe: the row_mult of bm_debug_rsm_up)
     // Gaussian visible units as one joint model over u = x / sigma (bm_rbm_gauss_*; bm_gauss.h), allocated at the
     // first such call; nothing else in the handle reads or writes them.  gc / gones: the centre c = vb / sigma and a vector of ones
     // [V], formed again by every call (the parameters may have moved).  gfe_*: the scaled rows [gfe_rows][V], the softplus slot
-    // partials [ceil(H/16)][gfe_rows] and F [gfe_rows] of bm_rbm_gauss_free_energy_rows.  gpt: the tempered ensemble of
-    // bm_rbm_gauss_pt_* - an ensemble of its own, bm_rbm_pt_* never see it - with the ladder's standard deviations gpt_sd [R] and,
-    // the generic route only, the raw z = h W^T [gpt_zrows][V] of its prop-down
+    // partials [ceil(H/16)][gfe_rows] and F [gfe_rows] of bm_rbm_gauss_free_energy_rows.  gpt_sd [R]: the standard deviations of the
+    // ladder of bm_rbm_gauss_pt_* (its ensemble is `pt` under the tag PT_GAUSS: bm_rbm_pt_* never see it)
     DevBuf gc, gones;
     int gfe_rows = 0;
     Mat gfe_u;
     DevBuf gfe_part;
     DevArray<double> gfe_out;
-    PtEnsemble gpt;
     DevBuf gpt_sd;
-    int gpt_zrows = 0;
-    Mat gpt_z;
     int fer_rows = 0;
     DevBuf fer_part, fer_out;          // bm_rbm_free_energy_rows: slot partials [ceil(H/16)][fer_rows] of sum softplus, F [fer_rows]
     // fast-binary mode (bm_bf3.h, bm_rbm_set_fast_binary): bf16 planes of W ([V][H]: the prop-down operand) and of
@@ -253,6 +252,9 @@ static int check_dw(const bm_rbm *h, const char *what) {
              "every rank must call bm_rbm_exchange_gather_dw first (DirectExchange.gather_dw())", what);
     return 0;
 }
+
+// no tempered ensemble any more (the buffers stay: PtEnsemble::ensure grows only)
+static void pt_drop(bm_rbm *h) { h->pt.M = 0; h->pt_unit = PT_NONE; }
 
 // what a handle with softmax visible units does not do (DESIGN.md 3.24 says why, entry by entry)
 static int refuse_softmax_v(const bm_rbm *h, const char *what) {
@@ -905,26 +907,6 @@ static void ais_down(bm_rbm *h, int R, float beta, int kbeta, const PhiloxKey &k
     issue(h, p);
 }
 
-// ---- parallel tempering (bm355.h: bm_rbm_pt_init / _sweep / _read)
-
-// (the ensemble, its start, the replica exchange, the rescore and the gather: bm_pt.h, shared with bm_dbm_pt_*)
-
-// step t of a tempered call: the RT prop-up, the swap of the parity of the global step number, the RT prop-down.  The passes are
-// row-tempered (the RT flavour of act_kernel): up = h ~ Ber(sigmoid(beta_row (vW + hb))) from pt.v into pt.h1, leaving the slot
-// partials of h.(vW + hb); down = v ~ Ber(sigmoid(beta_row (hW^T + vb))) from pt.h1 into pt.v, leaving those of v.vb
-// sel_rows > 0: the prop-down also leaves the beta = 1 row of every chain c < sel_rows in vs[c] (ActArgs::sel_out)
-static void pt_step(bm_rbm *h, int t, int sel_rows = 0) {
-    PtEnsemble &e = h->pt;
-    const int rows = e.nrows();
-    issue(h, rbm_pass(h, true, rows, in_of(e.v.x), value_out(1, e.h1.x.p, e.h1.x.ld, make_key(h, SITE_H, t), e.row0()))   // (mult: not read)
-                 .energy_rows(e.h1.part.p, e.rows).row_tempered(e.mult.p));
-    pt_launch_swap(h->pt, h->stream, t, make_key(h, SITE_PT_SWAP, t));
-    LayerPass down = rbm_pass(h, false, rows, in_of(e.h1.x), value_out(1, e.v.x.p, e.v.x.ld, make_key(h, SITE_V, t), e.row0()))
-                         .statedot_rows(e.v.part.p, e.rows, pass_vb(h)).row_tempered(e.mult.p);
-    if (sel_rows > 0) down.select_rows(h->vs.p, h->vs.ld, e.R, sel_rows);
-    issue(h, down);
-}
-
 extern "C" {
 
 const char *bm_last_error(void) { return bm::g_err; }
@@ -1241,17 +1223,21 @@ int bm_rbm_set_param_dev(bm_rbm *h, const char *name, const float *src_dev, size
 
 // The whole tempered ensemble, read only, dense (tests and tools; bm_rbm_pt_read / bm_rbm_groups_pt_read hand out the beta = 1 rows):
 // "pt_v" [M R][V], "pt_h" [M R][H], "pt_part_v" [ceil(V/16)][M R], "pt_part_h" [ceil(H/16)][M R], "pt_mult" [M R]
-// ("gpt_*": the same five of the ensemble of bm_rbm_gauss_pt_*, v in the scaled variable u, part_v the slots of -1/2 (u - c)^2)
-static int pt_get_param(bm_rbm *h, PtEnsemble &e, const std::string &full, float *host, size_t n) {
-    const std::string nm = full[0] == 'g' ? full.substr(1) : full;
-    BM_CHECK(e.M > 0, "variable '%s': no ensemble (bm_rbm_pt_init / bm_rbm_groups_pt_init / bm_rbm_gauss_pt_init)", full.c_str());
+// ("gpt_*": the same five of the ensemble of bm_rbm_gauss_pt_*, v in the scaled variable u, part_v the slots of -1/2 (u - c)^2: the
+// names that read the ensemble while its tag is PT_GAUSS, as "pt_*" do while it is any other)
+static int pt_get_param(bm_rbm *h, const std::string &full, float *host, size_t n) {
+    const bool gauss = full[0] == 'g';
+    const std::string nm = gauss ? full.substr(1) : full;
+    PtEnsemble &e = h->pt;
+    BM_CHECK(h->pt_unit != PT_NONE && gauss == (h->pt_unit == PT_GAUSS),
+             "variable '%s': no ensemble (bm_rbm_pt_init / bm_rbm_groups_pt_init / bm_rbm_gauss_pt_init)", full.c_str());
     const size_t rows = (size_t)e.nrows();
     const float *src = nullptr;
     size_t pitch = 0, width = 0, height = 0;
     if (nm == "pt_v")           { src = e.v.x.p; pitch = e.v.x.ld; width = h->V; height = rows; }
     else if (nm == "pt_h")      { src = e.h1.x.p; pitch = e.h1.x.ld; width = h->H; height = rows; }
     else if (nm == "pt_part_v") { src = e.v.part.p; pitch = e.rows; width = rows; height = e.v.nslot(); }
-    else if (nm == "pt_len" && &e == &h->pt && h->rsm_pt) { src = h->rp_len.p; pitch = rows; width = rows; height = 1; }
+    else if (nm == "pt_len" && h->pt_unit == PT_COUNTS) { src = h->rp_len.p; pitch = rows; width = rows; height = 1; }
     else if (nm == "pt_part_h") { src = e.h1.part.p; pitch = e.rows; width = rows; height = nslots(h->H); }
     else if (nm == "pt_mult")   { src = e.mult.p; pitch = rows; width = rows; height = 1; }
     BM_CHECK(src, "unknown RBM variable '%s'", full.c_str());
@@ -1276,8 +1262,7 @@ int bm_rbm_get_param(bm_rbm *h, const char *name, float *host, size_t n) {
     const std::string nm(name ? name : "");
     BM_HIP(hipStreamSynchronize(h->stream));
     BM_TRY(check_device_status(h));        // never hand out variables computed from invalid tiles / a lost rank's sums
-    if (nm.compare(0, 3, "pt_") == 0) return pt_get_param(h, h->pt, nm, host, n);
-    if (nm.compare(0, 4, "gpt_") == 0) return pt_get_param(h, h->gpt, nm, host, n);
+    if (nm.compare(0, 3, "pt_") == 0 || nm.compare(0, 4, "gpt_") == 0) return pt_get_param(h, nm, host, n);
     if (nm.compare(0, 4, "ais_") == 0) return ais_get_param(h, nm, host, n);
     bool ro = false;
     Mat *fm = find_fast_mat(h, nm, &ro);
@@ -1613,7 +1598,7 @@ int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K) {
     BM_CHECK(h, "null argument");
     if (K == 0) {
         // (an ensemble of one-hot rows goes with the groups, DESIGN.md 3.29: a Bernoulli sweep never runs over it)
-        if (h->v_groups) h->pt.M = 0;
+        if (h->pt_unit == PT_GROUPS) pt_drop(h);
         h->v_groups = 0; h->groups_missing = false;
         return 0;
     }
@@ -1628,7 +1613,7 @@ int bm_rbm_set_visible_groups(bm_rbm *h, int32_t K) {
     BM_CHECK(!h->n_classes, "softmax visible units do not combine with a class head (bm_rbm_set_classes(0) first)");
     BM_CHECK(!h->fw_on, "softmax visible units do not combine with fast weights (bm_rbm_set_fast_weights(off) first)");
     // (the ensemble of a handle that has this width already is bm_rbm_groups_pt_init's, DESIGN.md 3.29: nothing changes)
-    BM_CHECK(h->pt.M == 0 || h->v_groups == K, "softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
+    BM_CHECK(h->pt_unit == PT_NONE || (h->pt_unit == PT_GROUPS && h->v_groups == K), "softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
     BM_CHECK(!h->rsm_len, "softmax visible units do not combine with replicated softmax visible units (bm_rbm_set_replicated_softmax(0) first)");
     h->v_groups = K;
     return 0;
@@ -1639,7 +1624,7 @@ int bm_rbm_set_replicated_softmax(bm_rbm *h, int32_t max_length) {
     BM_CHECK(h, "null argument");
     if (max_length == 0) {
         // (an ensemble of count rows goes with the unit, DESIGN.md 3.31: a Bernoulli sweep never runs over it)
-        if (h->rsm_pt) { h->pt.M = 0; h->rsm_pt = false; }
+        if (h->pt_unit == PT_COUNTS) pt_drop(h);
         h->rsm_len = 0; h->rsm_user_n = 0; h->rsm_cur = nullptr;
         return 0;
     }
@@ -1658,7 +1643,7 @@ int bm_rbm_set_replicated_softmax(bm_rbm *h, int32_t max_length) {
     BM_CHECK(!h->n_classes, "replicated softmax visible units do not combine with a class head (bm_rbm_set_classes(0) first)");
     BM_CHECK(!h->fw_on, "replicated softmax visible units do not combine with fast weights (bm_rbm_set_fast_weights(off) first)");
     // (the count ensemble of a handle that has the unit already is bm_rbm_rsm_pt_init's; a new max_length discards it)
-    BM_CHECK(h->pt.M == 0 || h->rsm_pt, "replicated softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
+    BM_CHECK(h->pt_unit == PT_NONE || h->pt_unit == PT_COUNTS, "replicated softmax visible units do not combine with a tempered ensemble (this handle holds one: bm_rbm_pt_init)");
     BM_CHECK(!h->v_groups, "replicated softmax visible units do not combine with visible groups (bm_rbm_set_visible_groups(0) first)");
     if (!h->rsm_bad.p) {          // (allocated last: the workspaces are complete once the flag exists)
         BM_TRY(h->rsm_D.alloc(h->maxB)); BM_TRY(h->rsm_user.alloc(h->maxB));
@@ -1667,7 +1652,7 @@ int bm_rbm_set_replicated_softmax(bm_rbm *h, int32_t max_length) {
         BM_HIP(hipMemset(flag.p, 0, sizeof(int)));
         h->rsm_bad = std::move(flag);
     }
-    if (h->rsm_pt && h->rsm_len != max_length) { h->pt.M = 0; h->rsm_pt = false; }
+    if (h->pt_unit == PT_COUNTS && h->rsm_len != max_length) pt_drop(h);
     h->rsm_len = max_length;
     h->rsm_user_n = 0;
     h->rsm_cur = nullptr;
@@ -2840,467 +2825,8 @@ int bm_rbm_rsm_ais(bm_rbm *h, int32_t n_betas, int32_t n_rows, int32_t k, const 
                    [&](float bb, int b, const PhiloxKey &key, bool) { rsm_ais_down(h, R, bb, b, key, chain0); });
 }
 
-// Parallel tempering (replica exchange).  The ensemble lives in the handle; see bm355.h for the contract.
-int bm_rbm_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0) {
-    BM_CHECK(h, "null argument");
-    BM_TRY(check_single_joint(h, "bm_rbm_pt_init"));
-    BM_TRY(pt_check_ladder(n_chains, n_temps, betas_host, chain0));
-    const int widths[3] = {h->V, h->H, 0};
-    const PhiloxKey key = make_key(h, SITE_PT_V0, 0);
-    BM_TRY(pt_begin(h->pt, h->stream, widths, n_chains, n_temps, chain0, betas_host, V0_dev, h->vb.p, nullptr, key, key));
-    return 0;
-}
-
-int bm_rbm_pt_sweep(bm_rbm *h, int32_t n_steps) {
-    BM_CHECK(h, "null argument");
-    BM_TRY(refuse_nrelu(h, "bm_rbm_pt_sweep"));
-    BM_CHECK(h->pt.M > 0, "bm_rbm_pt_sweep: no ensemble (call bm_rbm_pt_init first)");
-    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
-    ensure_wt(h);
-    for (int t = 0; t < n_steps; ++t) pt_step(h, t);
-    h->pt.step += n_steps;
-    h->call++;
-    BM_HIP(hipGetLastError());
-    return 0;
-}
-
-int bm_rbm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
-    BM_CHECK(h, "null argument");
-    BM_TRY(refuse_nrelu(h, "bm_rbm_pt_read"));
-    BM_CHECK(h->pt.M > 0, "bm_rbm_pt_read: no ensemble (call bm_rbm_pt_init first)");
-    BM_CHECK(V_dev || !H_dev, "bm_rbm_pt_read: H_dev without V_dev");
-    float *const dst[3] = {V_dev, H_dev, nullptr};
-    const int ldd[3] = {h->V, h->H, 0};
-    pt_launch_gather(h->pt, h->stream, h->pt.M, dst, ldd);
-    return pt_read_host(h->pt, h->stream, swaps_host, ladder_idx_host);
-}
-
-// One update whose negative phase is the tempered ensemble (bm355.h).  No host synchronisation.
-int bm_rbm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
-    BM_CHECK(h && X_dev, "null argument");
-    BM_TRY(refuse_nrelu(h, "bm_rbm_train_step_pt"));
-    BM_TRY(check_dw(h, "bm_rbm_train_step_pt"));
-    BM_CHECK(h->pt.M > 0, "bm_rbm_train_step_pt: no ensemble (call bm_rbm_pt_init first)");
-    BM_CHECK(h->cfg.dropout < 0.f, "bm_rbm_train_step_pt: the tempered family has no dropout (this handle's is %g)", (double)h->cfg.dropout);
-    const int Bmax = std::min(h->maxB, h->pt.M);
-    BM_CHECK(B >= 1 && B <= Bmax, "bm_rbm_train_step_pt: batch %d outside [1, min(max_batch=%d, n_chains=%d)]", (int)B, h->maxB, h->pt.M);
-    BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
-    static const bool sel_in_pass = !dbg("pt_sel") || atoi(dbg("pt_sel")) != 0;     // BM355_DEBUG=pt_sel=0: a gather launch instead
-    ensure_wt(h);
-    ensure_eff(h);
-    // 1. the v.vb partials of the swap energy under the vb of NOW (the previous update changed it; fast weights: the effective vb)
-    pt_launch_rescore(h->pt, h->stream, h->fw_on ? h->vbe.p : h->vb.p, nullptr);
-    // 2. positive phase: the h0 means alone
-    h->Xin = X_dev; h->Xin_ld = h->V;
-    h->fe_in_chain = false;
-    issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, rbm_out(h, 0, h->h0m.p, nullptr, h->h0m.ld, SITE_H0, 0)));
-    {
-        EffScope eff(h);      // fast weights: the whole negative phase lives under the effective set
-        // 3. + 4. the tempered steps; the last prop-down leaves the beta = 1 rows of the chains [0, B) in vs
-        for (int t = 0; t < k; ++t) pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
-        if (!sel_in_pass) {
-            float *const dst[3] = {h->vs.p, nullptr, nullptr};
-            const int ldd[3] = {h->vs.ld, 0, 0};
-            pt_launch_gather(h->pt, h->stream, B, dst, ldd);
-        }
-        // 5. negative means: only -h is consumed (run_chain's neg_only form)
-        issue(h, rbm_pass(h, true, B, in_of(h->vs), rbm_out(h, 0, nullptr, nullptr, h->hm.ld, SITE_H, 0)).negmeans_out(h->hneg.p));
-        h->hm_is_neg = true;
-    }
-    // 6. + 7. (fast weights: the fast and effective sets move in the same launches)
-    if (h->fw_on) launch_update_fast(h, B, lr, mom);
-    else launch_update_fused(h, B, lr, mom);
-    h->pt.step += k;
-    h->call++;
-    BM_HIP(hipGetLastError());
-    return 0;
-}
-
-// the native batch loop of bm_rbm_train_step_pt (as bm_rbm_train_epoch is to bm_rbm_train_step)
-int bm_rbm_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t k) {
-    BM_CHECK(h && X_dev, "null argument");
-    BM_TRY(refuse_nrelu(h, "bm_rbm_train_epoch_pt"));
-    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
-    for (int64_t s = 0; s < N; s += batch) {
-        const int B = (int)((N - s < batch) ? (N - s) : batch);
-        BM_TRY(bm_rbm_train_step_pt(h, X_dev + (size_t)s * h->V, B, lr, mom, k));
-    }
-    return 0;
-}
-
-// ---- parallel tempering over softmax visible units (bm355.h: bm_rbm_groups_pt_* / _train_step_pt).  The ensemble
-// is the handle's one PtEnsemble: a handle with visible groups holds no other (bm_rbm_pt_init refuses it, bm_rbm_set_visible_groups
-// refuses a handle that holds a Bernoulli one), and turning the groups off discards it.
-static int check_groups_pt(const bm_rbm *h, const char *what) {
-    BM_TRY(need_groups(h, what));
-    BM_CHECK(!h->groups_missing, "%s: not built for incomplete rows (bm_rbm_groups_set_missing is on): a row of the tempered ensemble "
-             "has no pattern of observed groups; see DESIGN.md 3.29", what);
-    return 0;
-}
-// the generic route's raw z for `rows` ensemble rows; a failed allocation leaves nothing counted
-static int ensure_groups_pt_rows(bm_rbm *h, int rows) {
-    if (groups_fused(h) || rows <= h->gp_rows) return 0;
-    h->gp_rows = 0;
-    BM_TRY(h->gp_z.alloc(rows, h->V));
-    h->gp_rows = rows;
-    return 0;
-}
-// The prop-down of step t: v_g ~ softmax_k(beta_row (h W^T + vb)_{gK+k}) from pt.h1 into pt.v, leaving the slot partials of v.vb.
-// Fused route: ONE launch, the SM + SA + RT flavour; sel_rows > 0: it also leaves the beta = 1 row of every chain c < sel_rows in
-// vs[c].  Generic route: a raw pass (z = h W^T, the plain kernels), the tempered groups kernel, the row-dot kernel - the same bits;
-// its hand-over is the caller's gather launch
-static void groups_pt_down(bm_rbm *h, int t, int sel_rows) {
-    PtEnsemble &e = h->pt;
-    const int rows = e.nrows();
-    const PhiloxKey key = make_key(h, SITE_V, t);
-    LayerPass p = rbm_pass(h, false, rows, in_of(e.h1.x), value_out(1, e.v.x.p, e.v.x.ld, key, e.row0()));
-    ActArgs &a = p.a;
-    if (groups_fused(h)) {
-        ProfScope _ps(h, KC_DOWN);
-        p.statedot_rows(e.v.part.p, e.rows, h->vb.p).row_tempered(e.mult.p);
-        if (sel_rows > 0) p.select_rows(h->vs.p, h->vs.ld, e.R, sel_rows);
-        a.kind = 3; a.sm_k = h->v_groups; a.sm_ais = 1; a.sm_absent = nullptr;
-        launch_act_sm_pt(a, h->stream);
-        return;
-    }
-    a.kind = 2; a.sample = 0; a.states = nullptr; a.means = h->gp_z.p; a.ldo = h->gp_z.ld;
-    {
-        ProfScope _ps(h, KC_DOWN);
-        launch_act(a, h->stream);
-    }
-    ProfScope _ps(h, KC_OTHER);                        // (per-class event timing: the route's extra launches are the class `other`)
-    SpGroupsArgs g;
-    memset(&g, 0, sizeof(g));
-    g.Z = h->gp_z.p; g.ldz = h->gp_z.ld; g.states = e.v.x.p; g.ld_states = e.v.x.ld;
-    g.V = h->V; g.K = h->v_groups; g.J = rows; g.bias = h->vb.p; g.row_mult = e.mult.p; g.key = key; g.row0 = e.row0();
-    launch_softmax_pt_groups(g, h->stream);
-    launch_softmax_ais_dot(e.v.x.p, e.v.x.ld, rows, h->V, h->vb.p, e.v.part.p, e.rows, h->stream);
-}
-// step t of a tempered call: the RT prop-up and the swap of pt_step, unchanged - for one-hot v they are this model's - then the
-// tempered softmax prop-down
-static void groups_pt_step(bm_rbm *h, int t, int sel_rows = 0) {
-    PtEnsemble &e = h->pt;
-    issue(h, rbm_pass(h, true, e.nrows(), in_of(e.v.x), value_out(1, e.h1.x.p, e.h1.x.ld, make_key(h, SITE_H, t), e.row0()))   // (mult: not read)
-                 .energy_rows(e.h1.part.p, e.rows).row_tempered(e.mult.p));
-    pt_launch_swap(e, h->stream, t, make_key(h, SITE_PT_SWAP, t));
-    groups_pt_down(h, t, sel_rows);
-}
-
-int bm_rbm_groups_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0) {
-    BM_TRY(check_groups_pt(h, "bm_rbm_groups_pt_init"));
-    BM_TRY(pt_check_ladder(n_chains, n_temps, betas_host, chain0));
-    h->pt.M = 0;
-    BM_TRY(ensure_groups_pt_rows(h, n_chains * n_temps));
-    const int widths[3] = {h->V, h->H, 0};
-    const PhiloxKey key = make_key(h, SITE_PT_V0, 0);
-    return pt_begin_with(h->pt, h->stream, widths, n_chains, n_temps, chain0, betas_host, [&](PtEnsemble &e, int rows) {
-        SpStartArgs s0;
-        memset(&s0, 0, sizeof(s0));
-        s0.v = e.v.x.p; s0.ld = e.v.x.ld; s0.rows = rows; s0.R = n_temps; s0.V = h->V; s0.K = h->v_groups;
-        s0.V0 = V0_dev; s0.vb = h->vb.p; s0.beta = e.beta.p;
-        s0.key = key; s0.row0 = (unsigned long long)chain0 * (unsigned long long)n_temps;
-        s0.part = e.v.part.p; s0.ld_part = e.rows; s0.row_mult = e.mult.p; s0.idx = e.idx.p;
-        launch_softmax_pt_init(s0, h->stream);
-    });
-}
-
-int bm_rbm_groups_pt_sweep(bm_rbm *h, int32_t n_steps) {
-    BM_TRY(check_groups_pt(h, "bm_rbm_groups_pt_sweep"));
-    BM_CHECK(h->pt.M > 0, "bm_rbm_groups_pt_sweep: no ensemble (call bm_rbm_groups_pt_init first)");
-    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
-    ensure_wt(h);
-    for (int t = 0; t < n_steps; ++t) groups_pt_step(h, t);
-    h->pt.step += n_steps;
-    h->call++;
-    BM_HIP(hipGetLastError());
-    return 0;
-}
-
-int bm_rbm_groups_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
-    BM_TRY(check_groups_pt(h, "bm_rbm_groups_pt_read"));
-    BM_CHECK(h->pt.M > 0, "bm_rbm_groups_pt_read: no ensemble (call bm_rbm_groups_pt_init first)");
-    BM_CHECK(V_dev || !H_dev, "bm_rbm_groups_pt_read: H_dev without V_dev");
-    float *const dst[3] = {V_dev, H_dev, nullptr};
-    const int ldd[3] = {h->V, h->H, 0};
-    pt_launch_gather(h->pt, h->stream, h->pt.M, dst, ldd);
-    return pt_read_host(h->pt, h->stream, swaps_host, ladder_idx_host);
-}
-
-// bm_rbm_train_step_pt for a handle with visible groups: the same seven steps (a handle with visible groups has no dropout, no
-// fast weights and no centering: bm_rbm_set_visible_groups).  No host synchronisation.
-int bm_rbm_groups_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
-    BM_TRY(check_groups_pt(h, "bm_rbm_groups_train_step_pt"));
-    BM_CHECK(X_dev, "null argument");
-    BM_TRY(check_dw(h, "bm_rbm_groups_train_step_pt"));
-    BM_CHECK(h->pt.M > 0, "bm_rbm_groups_train_step_pt: no ensemble (call bm_rbm_groups_pt_init first)");
-    const int Bmax = std::min(h->maxB, h->pt.M);
-    BM_CHECK(B >= 1 && B <= Bmax, "bm_rbm_groups_train_step_pt: batch %d outside [1, min(max_batch=%d, n_chains=%d)]", (int)B, h->maxB, h->pt.M);
-    BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
-    static const bool sel_env = !dbg("pt_sel") || atoi(dbg("pt_sel")) != 0;          // BM355_DEBUG=pt_sel=0: a gather launch instead
-    const bool sel_in_pass = sel_env && groups_fused(h);                             // (the generic route always gathers)
-    ensure_wt(h);
-    // 1. the v.vb partials of the swap energy under the vb of NOW (the previous update changed it)
-    pt_launch_rescore(h->pt, h->stream, h->vb.p, nullptr);
-    // 2. positive phase: the h0 means alone
-    h->Xin = X_dev; h->Xin_ld = h->V;
-    h->fe_in_chain = false;
-    issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, rbm_out(h, 0, h->h0m.p, nullptr, h->h0m.ld, SITE_H0, 0)));
-    // 3. + 4. the tempered steps; the beta = 1 rows of the chains [0, B) go to vs
-    for (int t = 0; t < k; ++t) groups_pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
-    if (!sel_in_pass) {
-        float *const dst[3] = {h->vs.p, nullptr, nullptr};
-        const int ldd[3] = {h->vs.ld, 0, 0};
-        pt_launch_gather(h->pt, h->stream, B, dst, ldd);
-    }
-    // 5. negative means: only -h is consumed (run_chain's neg_only form)
-    issue(h, rbm_pass(h, true, B, in_of(h->vs), rbm_out(h, 0, nullptr, nullptr, h->hm.ld, SITE_H, 0)).negmeans_out(h->hneg.p));
-    h->hm_is_neg = true;
-    // 6. + 7.
-    launch_update_fused(h, B, lr, mom);
-    h->pt.step += k;
-    h->call++;
-    BM_HIP(hipGetLastError());
-    return 0;
-}
-
-// the native batch loop of bm_rbm_groups_train_step_pt
-int bm_rbm_groups_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t k) {
-    BM_TRY(check_groups_pt(h, "bm_rbm_groups_train_epoch_pt"));
-    BM_CHECK(X_dev, "null argument");
-    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
-    for (int64_t s = 0; s < N; s += batch) {
-        const int B = (int)((N - s < batch) ? (N - s) : batch);
-        BM_TRY(bm_rbm_groups_train_step_pt(h, X_dev + (size_t)s * h->V, B, lr, mom, k));
-    }
-    return 0;
-}
-
-// ---- parallel tempering over replicated softmax visible units (bm355.h: bm_rbm_rsm_pt_* / _train_step_pt).  The
-// ensemble is the handle's one PtEnsemble with a two-slot visible partial array (the float32 pair of the double v.vb): a handle with
-// the unit holds no other (bm_rbm_pt_init refuses it, bm_rbm_set_replicated_softmax refuses a handle that holds a Bernoulli one), and
-// turning the unit off discards it.
-static int check_rsm_pt(const bm_rbm *h, const char *what, bool need_ensemble) {
-    BM_CHECK(h, "%s: null argument", what);
-    BM_CHECK(h->rsm_len, "%s needs a handle with replicated softmax visible units (bm_rbm_set_replicated_softmax): bm_rbm_pt_* / "
-             "bm_rbm_groups_pt_* serve the other units", what);
-    BM_CHECK(!need_ensemble || (h->pt.M > 0 && h->rsm_pt), "%s: no ensemble (call bm_rbm_rsm_pt_init first)", what);
-    return 0;
-}
-// the prop-up of step t: h ~ Ber(sigmoid(beta_row (v W + D_row hb))) from pt.v into pt.h1, leaving the slot partials of h.(vW + D hb):
-// the DB + RT flavour, asked for by name (issue() goes through launch_act, which has no such route); W^T x-major where the handle
-// keeps a valid one, as issue() reads it
-static void rsm_pt_up(bm_rbm *h, int t) {
-    PtEnsemble &e = h->pt;
-    LayerPass p = rbm_pass(h, true, e.nrows(), in_of(e.v.x), value_out(1, e.h1.x.p, e.h1.x.ld, make_key(h, SITE_H, t), e.row0()));   // (mult: not read)
-    p.energy_rows(e.h1.part.p, e.rows).row_tempered(e.mult.p);
-    ActArgs &a = p.a;
-    a.row_bmult = h->rp_len.p;
-    if (h->use_wt && h->wt_valid) { a.P1 = make_operand(h->Wt.p, h->Wt.ld, h->H); a.p_xm = 1; }
-    ProfScope _ps(h, KC_UP);
-    launch_act_db_pt(a, h->stream);
-}
-// the prop-down of step t: a raw pass z = h W^T (kind 2, mult 1: the plain kernels) into rp_z, then the PT flavour of the count kernel:
-// v ~ Multinomial(D_row, softmax(beta_row (z + vb))) into pt.v, the pair of v.vb into pt.v.part; sel_rows > 0: the beta = 1 row of
-// every chain c < sel_rows also goes to vs[c]
-static void rsm_pt_down(bm_rbm *h, int t, int sel_rows) {
-    PtEnsemble &e = h->pt;
-    const int rows = e.nrows();
-    const PhiloxKey key = make_key(h, SITE_V, t);
-    LayerPass p = rbm_pass(h, false, rows, in_of(e.h1.x), LayerOut{0, h->rp_z.p, nullptr, h->rp_z.ld, key, e.row0()}, 1.0f);
-    p.a.kind = 2; p.a.sample = 0; p.a.states = nullptr;
-    {
-        ProfScope _ps(h, KC_DOWN);
-        launch_act(p.a, h->stream);
-    }
-    ProfScope _ps(h, KC_OTHER);                        // (per-class event timing: the count kernel is the class `other`, as in 3.27)
-    McPtArgs m;
-    memset(&m, 0, sizeof(m));
-    m.L = h->rp_z.p; m.ld = h->rp_z.ld; m.states = e.v.x.p; m.ld_states = e.v.x.ld; m.lengths = h->rp_len.p;
-    m.V = h->V; m.J = rows; m.sample = 1; m.max_length = h->rsm_len; m.key = key; m.row0 = e.row0();
-    m.dvec = h->vb.p; m.part = e.v.part.p; m.ld_part = e.rows;
-    m.bias = h->vb.p; m.row_mult = e.mult.p;
-    if (sel_rows > 0) { m.sel_out = h->vs.p; m.sel_ld = h->vs.ld; m.sel_R = e.R; m.sel_rows = sel_rows; }
-    if (launch_multinomial_counts_pt(m, h->stream)) abort();       // (bm_rbm_set_replicated_softmax checked the width)
-}
-static void rsm_pt_step(bm_rbm *h, int t, int sel_rows = 0) {
-    rsm_pt_up(h, t);
-    pt_launch_swap(h->pt, h->stream, t, make_key(h, SITE_PT_SWAP, t));
-    rsm_pt_down(h, t, sel_rows);
-}
-
-int bm_rbm_rsm_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *lengths_host, const float *V0_dev,
-                       int64_t chain0) {
-    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_pt_init", false));
-    BM_TRY(pt_check_ladder(n_chains, n_temps, betas_host, chain0));
-    BM_CHECK(lengths_host, "bm_rbm_rsm_pt_init: null argument");
-    for (int c = 0; c < n_chains; ++c) {
-        const float D = lengths_host[c];
-        BM_CHECK(D >= 1.0f && D <= (float)h->rsm_len && D == truncf(D), "bm_rbm_rsm_pt_init: lengths_host[%d] = %g is no integer in "
-                 "[1, max_length = %d]", c, (double)D, h->rsm_len);
-    }
-    BM_CHECK(!h->pt.M || h->rsm_pt, "bm_rbm_rsm_pt_init: this handle holds a tempered ensemble of another unit");
-    h->pt.M = 0; h->rsm_pt = false;
-    const int M = n_chains, R = n_temps, rows = M * R;
-    if (rows > h->rp_rows) {                           // (a failed allocation leaves nothing counted)
-        h->rp_rows = 0;
-        BM_TRY(h->rp_z.alloc(rows, h->V)); BM_TRY(h->rp_len.alloc(rows)); BM_TRY(h->rp_clen.alloc(rows)); BM_TRY(h->rp_v0len.alloc(rows));
-        h->rp_rows = rows;
-    }
-    BM_HIP(hipStreamSynchronize(h->stream));
-    BM_HIP(hipMemcpy(h->rp_clen.p, lengths_host, (size_t)M * sizeof(float), hipMemcpyHostToDevice));
-    // row_lengths_kernel's flag is the handle's: what an earlier batch left there and bm_rbm_sync has not reported yet is set aside
-    // for the start (the stream is idle) and put back behind it, so that the start answers for its own rows alone
-    int pending = 0;
-    if (V0_dev) {
-        BM_HIP(hipMemcpy(&pending, h->rsm_bad.p, sizeof(int), hipMemcpyDeviceToHost));
-        if (pending) BM_HIP(hipMemset(h->rsm_bad.p, 0, sizeof(int)));
-    }
-    const int widths[3] = {h->V, h->H, 0};
-    const PhiloxKey key = make_key(h, SITE_PT_V0, 0);
-    BM_TRY(pt_begin_with(h->pt, h->stream, widths, M, R, chain0, betas_host, [&](PtEnsemble &e, int nrows) {
-        // the sums of the start rows, with row_lengths_kernel's own flags; the start kernel compares them with the chains' lengths
-        if (V0_dev) launch_row_lengths(RowLenArgs{V0_dev, h->V, h->V, M, h->rp_v0len.p, h->rsm_len, h->rsm_bad.p}, h->stream);
-        RsmPtStartArgs s0;
-        memset(&s0, 0, sizeof(s0));
-        s0.v = e.v.x.p; s0.ld = e.v.x.ld; s0.rows = nrows; s0.R = R; s0.V = h->V;
-        s0.V0 = V0_dev; s0.V0_len = V0_dev ? h->rp_v0len.p : nullptr; s0.chain_len = h->rp_clen.p; s0.beta = e.beta.p;
-        s0.row_mult = e.mult.p; s0.len = h->rp_len.p; s0.idx = e.idx.p; s0.bad = h->rsm_bad.p;
-        launch_rsm_pt_start(s0, h->stream);
-        if (!V0_dev) {                                 // v_0 ~ Multinomial(D_c, uniform): the count flavour on zero z and zero bias
-            McPtArgs m;
-            memset(&m, 0, sizeof(m));
-            m.states = e.v.x.p; m.ld_states = e.v.x.ld; m.lengths = h->rp_len.p;
-            m.V = h->V; m.J = nrows; m.sample = 1; m.max_length = h->rsm_len; m.key = key;
-            m.row0 = (long long)chain0 * (long long)R;
-            m.dvec = h->vb.p; m.part = e.v.part.p; m.ld_part = e.rows; m.row_mult = e.mult.p;
-            if (launch_multinomial_counts_pt(m, h->stream)) abort();
-        }
-        launch_rsm_pt_rescore(e.v.x.p, e.v.x.ld, nrows, h->V, h->vb.p, e.v.part.p, e.rows, h->stream);
-    }, 2));
-    if (V0_dev) {                                      // a start row that is no count row of its chain's length: no ensemble
-        BM_HIP(hipStreamSynchronize(h->stream));
-        const int rc = check_row_lengths(h);
-        if (pending) BM_HIP(hipMemcpy(h->rsm_bad.p, &pending, sizeof(int), hipMemcpyHostToDevice));
-        if (rc) { h->pt.M = 0; return rc; }
-    }
-    h->rsm_pt = true;
-    return 0;
-}
-
-// A launch-level probe of the two tempered prop-ups (tests): h ~ Ber(sigmoid(beta (v W + D_j hb))) of the J rows of V_dev [J][V]
-// with the lengths lengths_dev [J] into H_dev [J][H] (dense), drawn at SITE_H, step 0, the handle's seed, call counter and row
-// offset.  per_row != 0: the DB + RT flavour with row_mult[j] == beta for every row (launch_act_db_pt), which also leaves its
-// energy partials in part_dev [ceil(H/16)][J] where that is not null; per_row == 0: the existing DB pass at mult == bmult == beta,
-// the pass of bm_rbm_rsm_ais.  The call counter does not advance: the two forms read the same stream
-int bm_debug_rsm_up(bm_rbm *h, const float *V_dev, int32_t J, const float *lengths_dev, float beta, int32_t per_row, float *H_dev,
-                    float *part_dev) {
-    BM_TRY(check_rsm_pt(h, "bm_debug_rsm_up", false));
-    BM_CHECK(V_dev && lengths_dev && H_dev && J >= 1 && beta > 0.f, "bm_debug_rsm_up: bad arguments");
-    BM_CHECK(per_row || !part_dev, "bm_debug_rsm_up: the energy partials are the per-row form's");
-    ensure_wt(h);
-    LayerPass p = rbm_pass(h, true, J, LayerIn{V_dev, h->V}, LayerOut{1, nullptr, H_dev, h->H, make_key(h, SITE_H, 0), h->row0}, beta);
-    p.a.row_bmult = lengths_dev;
-    if (!per_row) {
-        issue(h, p);
-        BM_HIP(hipGetLastError());
-        return 0;
-    }
-    if (h->rp_probe.n < (size_t)J) BM_TRY(h->rp_probe.alloc(J));
-    const std::vector<float> mult((size_t)J, beta);
-    BM_HIP(hipStreamSynchronize(h->stream));
-    BM_HIP(hipMemcpy(h->rp_probe.p, mult.data(), (size_t)J * sizeof(float), hipMemcpyHostToDevice));
-    ActArgs &a = p.a;
-    a.mult = a.bmult = 1.0f;                           // (not read: the row's beta takes their place)
-    p.row_tempered(h->rp_probe.p);
-    if (part_dev) p.energy_rows(part_dev, J);
-    if (h->use_wt && h->wt_valid) { a.P1 = make_operand(h->Wt.p, h->Wt.ld, h->H); a.p_xm = 1; }
-    launch_act_db_pt(a, h->stream);
-    BM_HIP(hipGetLastError());
-    return 0;
-}
-
-int bm_rbm_rsm_pt_sweep(bm_rbm *h, int32_t n_steps) {
-    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_pt_sweep", true));
-    BM_CHECK(n_steps >= 1, "n_steps must be >= 1 (got %d)", (int)n_steps);
-    ensure_wt(h);
-    for (int t = 0; t < n_steps; ++t) rsm_pt_step(h, t);
-    h->pt.step += n_steps;
-    h->call++;
-    BM_HIP(hipGetLastError());
-    return 0;
-}
-
-int bm_rbm_rsm_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
-    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_pt_read", true));
-    BM_CHECK(V_dev || !H_dev, "bm_rbm_rsm_pt_read: H_dev without V_dev");
-    float *const dst[3] = {V_dev, H_dev, nullptr};
-    const int ldd[3] = {h->V, h->H, 0};
-    pt_launch_gather(h->pt, h->stream, h->pt.M, dst, ldd);
-    return pt_read_host(h->pt, h->stream, swaps_host, ladder_idx_host);
-}
-
-// bm_rbm_train_step_pt for a handle with replicated softmax visible units: the same seven steps (a handle with the unit has no
-// dropout, no sparsity penalty, no fast weights and no centering: bm_rbm_set_replicated_softmax).  No host synchronisation.
-int bm_rbm_rsm_train_step_pt(bm_rbm *h, const float *X_dev, int32_t B, float lr, float mom, int32_t k) {
-    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_train_step_pt", false));
-    BM_CHECK(X_dev, "null argument");
-    BM_TRY(check_dw(h, "bm_rbm_rsm_train_step_pt"));
-    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_train_step_pt", true));
-    BM_CHECK(B >= 1 && B <= std::min(h->maxB, h->pt.M), "bm_rbm_rsm_train_step_pt: batch %d outside [1, min(max_batch=%d, n_chains=%d)]",
-             (int)B, h->maxB, h->pt.M);
-    BM_CHECK(k >= 1, "n_gibbs_steps must be >= 1 (got %d)", (int)k);
-    static const bool sel_in_pass = !dbg("pt_sel") || atoi(dbg("pt_sel")) != 0;      // BM355_DEBUG=pt_sel=0: a gather launch instead
-    PtEnsemble &e = h->pt;
-    ensure_wt(h);
-    // 1. the v.vb pair of the swap energy under the vb of NOW (the previous update changed it)
-    launch_rsm_pt_rescore(e.v.x.p, e.v.x.ld, e.nrows(), h->V, h->vb.p, e.v.part.p, e.rows, h->stream);
-    // 2. positive phase: the h0 means alone, plain DB with the batch's lengths
-    h->Xin = X_dev; h->Xin_ld = h->V;
-    h->fe_in_chain = false;
-    rsm_lengths_of(h, X_dev, h->V, B, h->rsm_D.p);
-    issue(h, rbm_pass(h, true, B, LayerIn{X_dev, h->V}, rbm_out(h, 0, h->h0m.p, nullptr, h->h0m.ld, SITE_H0, 0)));
-    // 3. + 4. the tempered steps; the beta = 1 rows of the chains [0, B) go to vs
-    for (int t = 0; t < k; ++t) rsm_pt_step(h, t, (sel_in_pass && t == k - 1) ? B : 0);
-    if (!sel_in_pass) {
-        float *const dst[3] = {h->vs.p, nullptr, nullptr};
-        const int ldd[3] = {h->vs.ld, 0, 0};
-        pt_launch_gather(e, h->stream, B, dst, ldd);
-    }
-    // 5. negative means: only -h is consumed; plain DB with the CHAINS' lengths Dn_c, c < B
-    {
-        LayerPass neg = rbm_pass(h, true, B, in_of(h->vs), rbm_out(h, 0, nullptr, nullptr, h->hm.ld, SITE_H, 0)).negmeans_out(h->hneg.p);
-        neg.a.row_bmult = h->rp_clen.p;
-        issue(h, neg);
-    }
-    h->hm_is_neg = true;
-    // 6. + 7. the bias block with the two length vectors in front, then the unchanged grad_kernel without its bias tail
-    {
-        ProfScope _ps(h, KC_COLSUM);
-        RbmBiasFusedArgs a;
-        fill_bias_fused(h, B, lr, mom, a);
-        launch_rsm_bias2(a, h->rsm_D.p, h->rp_clen.p, h->stream);
-    }
-    rbm_grad(h, B, 1, (float)B, lr, mom, false);
-    e.step += k;
-    h->call++;
-    BM_HIP(hipGetLastError());
-    return 0;
-}
-
-// the native batch loop of bm_rbm_rsm_train_step_pt
-int bm_rbm_rsm_train_epoch_pt(bm_rbm *h, const float *X_dev, int64_t N, int32_t batch, float lr, float mom, int32_t k) {
-    BM_TRY(check_rsm_pt(h, "bm_rbm_rsm_train_epoch_pt", false));
-    BM_CHECK(X_dev, "null argument");
-    BM_CHECK(batch >= 1 && N >= 1, "bad N=%lld batch=%d", (long long)N, batch);
-    for (int64_t s = 0; s < N; s += batch) {
-        const int B = (int)((N - s < batch) ? (N - s) : batch);
-        BM_TRY(bm_rbm_rsm_train_step_pt(h, X_dev + (size_t)s * h->V, B, lr, mom, k));
-    }
-    return 0;
-}
-
-// ---- Gaussian visible units as one joint model (bm355.h: bm_rbm_gauss_ais, bm_rbm_gauss_free_energy_rows, bm_rbm_gauss_pt_*;
-// bm_gauss.h).  Everything runs on u = x / sigma with unit variance and the centre c = vb / sigma; the entries of the
+// ---- Gaussian visible units as one joint model (bm355.h: bm_rbm_gauss_ais, bm_rbm_gauss_free_energy_rows; bm_rbm_gauss_pt_* are in
+// bm_rbm_pt.hip; bm_gauss.h).  Everything runs on u = x / sigma with unit variance and the centre c = vb / sigma; the entries of the
 // Bernoulli model (bm_rbm_ais, bm_rbm_free_energy_rows, bm_rbm_pt_*) keep refusing a Gaussian handle.
 static int check_gauss_joint(const bm_rbm *h, const char *what) {
     BM_CHECK(h, "%s: null argument", what);
@@ -3390,100 +2916,6 @@ int bm_rbm_gauss_free_energy_rows(bm_rbm *h, const float *X_dev, int32_t B, doub
     BM_HIP(hipMemcpyAsync(out_host, h->gfe_out.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     return 0;
-}
-
-// The one-launch route of the tempered prop-down (the RT + GT flavour) unless BM355_DEBUG=gt_fused=0 asks for the generic one
-static bool gauss_pt_fused() {
-    static const bool off = bm::dbg("gt_fused") && atoi(bm::dbg("gt_fused")) == 0;
-    return !off;
-}
-// Step t of a tempered call: the RT prop-up and the swap of pt_step, unchanged - h | u at beta is Ber(sigmoid(beta (u W + hb))), and
-// with part_v = the slots of -1/2 |u - c|^2 the swap's E = -(sum part_v + sum part_h1) is 1/2 |u - c|^2 - h.(u W + hb) - then the
-// prop-down u ~ N(c + W h, I / beta_row).  Fused route: ONE launch.  Generic route: a raw pass (z = h W^T, the plain kernels) and the
-// row kernel - the same bits
-static void gauss_pt_step(bm_rbm *h, int t) {
-    PtEnsemble &e = h->gpt;
-    const int rows = e.nrows();
-    issue(h, rbm_pass(h, true, rows, in_of(e.v.x), value_out(1, e.h1.x.p, e.h1.x.ld, make_key(h, SITE_H, t), e.row0()))   // (mult: not read)
-                 .energy_rows(e.h1.part.p, e.rows).row_tempered(e.mult.p));
-    pt_launch_swap(e, h->stream, t, make_key(h, SITE_PT_SWAP, t));
-    const PhiloxKey key = make_key(h, SITE_V, t);
-    LayerPass p = rbm_pass(h, false, rows, in_of(e.h1.x), value_out(1, e.v.x.p, e.v.x.ld, key, e.row0()), 1.0f);
-    ActArgs &a = p.a;
-    a.bias = h->gc.p; a.sigma = nullptr;
-    if (gauss_pt_fused()) {
-        ProfScope _ps(h, KC_DOWN);
-        a.kind = 3;
-        a.rowdot_out = e.v.part.p; a.ld_part = e.rows; a.row_mult = e.mult.p; a.gt_sd = h->gpt_sd.p; a.gt_idx = e.idx.p;
-        launch_act_gauss_pt(a, h->stream);
-        return;
-    }
-    a.kind = 2; a.sample = 0; a.states = nullptr; a.means = h->gpt_z.p; a.ldo = h->gpt_z.ld;
-    {
-        ProfScope _ps(h, KC_DOWN);
-        launch_act(a, h->stream);
-    }
-    ProfScope _ps(h, KC_OTHER);
-    GpRowsArgs g;
-    memset(&g, 0, sizeof(g));
-    g.Z = h->gpt_z.p; g.ldz = h->gpt_z.ld; g.states = e.v.x.p; g.ld_states = e.v.x.ld; g.V = h->V; g.J = rows;
-    g.c = h->gc.p; g.sd = h->gpt_sd.p; g.idx = e.idx.p; g.key = key; g.row0 = e.row0(); g.part = e.v.part.p; g.ld_part = e.rows;
-    launch_gauss_pt_rows(g, h->stream);
-}
-
-int bm_rbm_gauss_pt_init(bm_rbm *h, int32_t n_chains, int32_t n_temps, const float *betas_host, const float *V0_dev, int64_t chain0) {
-    BM_TRY(check_gauss_joint(h, "bm_rbm_gauss_pt_init"));
-    BM_TRY(pt_check_ladder(n_chains, n_temps, betas_host, chain0));
-    h->gpt.M = 0;
-    const int rows = n_chains * n_temps;
-    if (!gauss_pt_fused() && rows > h->gpt_zrows) {
-        h->gpt_zrows = 0;
-        BM_TRY(h->gpt_z.alloc(rows, h->V));
-        h->gpt_zrows = rows;
-    }
-    // sd[r] = float32(1 / sqrt(double(beta_r))): exactly 1 at beta = 1
-    std::vector<float> sd(n_temps);
-    for (int r = 0; r < n_temps; ++r) sd[r] = (float)(1.0 / sqrt((double)betas_host[r]));
-    if (h->gpt_sd.n < (size_t)n_temps) BM_TRY(h->gpt_sd.alloc(n_temps));
-    BM_HIP(hipStreamSynchronize(h->stream));
-    BM_HIP(hipMemcpy(h->gpt_sd.p, sd.data(), (size_t)n_temps * sizeof(float), hipMemcpyHostToDevice));
-    BM_TRY(gauss_prep(h));
-    const int widths[3] = {h->V, h->H, 0};
-    const PhiloxKey key = make_key(h, SITE_PT_V0, 0);
-    return pt_begin_with(h->gpt, h->stream, widths, n_chains, n_temps, chain0, betas_host, [&](PtEnsemble &e, int nrows) {
-        GpStartArgs s0;
-        memset(&s0, 0, sizeof(s0));
-        s0.v = e.v.x.p; s0.ld = e.v.x.ld; s0.rows = nrows; s0.R = n_temps; s0.V = h->V;
-        s0.V0 = V0_dev; s0.c = h->gc.p; s0.sigma = h->sigma.p; s0.beta = e.beta.p; s0.sd = h->gpt_sd.p;
-        s0.key = key; s0.row0 = (unsigned long long)chain0 * (unsigned long long)n_temps;
-        s0.part = e.v.part.p; s0.ld_part = e.rows; s0.row_mult = e.mult.p; s0.idx = e.idx.p;
-        launch_gauss_pt_init(s0, h->stream);
-    });
-}
-
-int bm_rbm_gauss_pt_sweep(bm_rbm *h, int32_t n_steps) {
-    BM_TRY(check_gauss_joint(h, "bm_rbm_gauss_pt_sweep"));
-    BM_CHECK(h->gpt.M > 0, "bm_rbm_gauss_pt_sweep: no ensemble (call bm_rbm_gauss_pt_init first)");
-    BM_CHECK(n_steps >= 1, "bm_rbm_gauss_pt_sweep: n_steps must be >= 1 (got %d)", (int)n_steps);
-    BM_CHECK(gauss_pt_fused() || h->gpt.nrows() <= h->gpt_zrows, "bm_rbm_gauss_pt_sweep: the ensemble was built for the one-launch route");
-    ensure_wt(h);
-    for (int t = 0; t < n_steps; ++t) gauss_pt_step(h, t);
-    h->gpt.step += n_steps;
-    h->call++;
-    BM_HIP(hipGetLastError());
-    return 0;
-}
-
-// the beta = 1 rows: the gather of bm_rbm_pt_read, then x = u sigma on the dense result
-int bm_rbm_gauss_pt_read(bm_rbm *h, float *V_dev, float *H_dev, int64_t *swaps_host, int32_t *ladder_idx_host) {
-    BM_TRY(check_gauss_joint(h, "bm_rbm_gauss_pt_read"));
-    BM_CHECK(h->gpt.M > 0, "bm_rbm_gauss_pt_read: no ensemble (call bm_rbm_gauss_pt_init first)");
-    BM_CHECK(V_dev || !H_dev, "bm_rbm_gauss_pt_read: H_dev without V_dev");
-    float *const dst[3] = {V_dev, H_dev, nullptr};
-    const int ldd[3] = {h->V, h->H, 0};
-    pt_launch_gather(h->gpt, h->stream, h->gpt.M, dst, ldd);
-    if (V_dev) launch_gauss_scale_rows(V_dev, h->gpt.M, h->V, h->sigma.p, h->stream);
-    return pt_read_host(h->gpt, h->stream, swaps_host, ladder_idx_host);
 }
 
 // the block -> tile map of a launch with tiles_i x tiles_j tiles (host evaluation of the device function, for tests and

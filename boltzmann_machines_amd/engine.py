@@ -60,13 +60,21 @@ class _PtCalls(object):
                                     idx.ctypes.data_as(C.c_void_p) if idx.size else None))
         return swaps, idx
 
+    # tempered negative phase (bm355.h: <prefix>_train_step_pt / _train_epoch_pt); the ensemble of pt_init supplies the particles
+    def train_step_pt(self, Xd, B, lr, momentum, k, row=0):
+        check(getattr(self.lib, self._pt_prefix + '_train_step_pt')(self._h, Xd.offset_ptr(row * self.V), B, lr, momentum, k))
 
-class RbmGroupsPt(_PtCalls):
-    """The tempered ensemble of an RbmEngine with visible groups (bm355.h: bm_rbm_groups_pt_* / _train_step_pt / _train_epoch_pt;
-    DESIGN.md 3.29): pt_init / pt_sweep / pt_read and the two tempered updates under the prefix 'bm_rbm_groups', on the engine's
-    handle.  Every other attribute is the engine's, so that the tempered sampler and the tempered epoch of tempering.py / rbm.py
-    run on it as they run on an engine."""
-    _pt_prefix, _pt_n_hidden = 'bm_rbm_groups', 1
+    def train_epoch_pt(self, Xd, N, batch, lr, momentum, k, row=0):
+        """N rows starting at `row`, consecutive batches of `batch` rows, one tempered update each, driven from C"""
+        check(getattr(self.lib, self._pt_prefix + '_train_epoch_pt')(self._h, Xd.offset_ptr(row * self.V), N, batch, lr, momentum, k))
+
+
+class _RbmPtView(_PtCalls):
+    """The tempered ensemble of an RbmEngine whose visible unit has entries of its own, under their prefix, on the engine's handle.
+    Every other attribute is the engine's, so that the tempered sampler and the tempered epoch of tempering.py / rbm.py run on a
+    view as they run on an engine."""
+    _pt_n_hidden = 1
+    _pt_param = 'pt_'                             # the bm_rbm_get_param names of the ensemble: 'pt_*' / 'gpt_*'
 
     def __init__(self, engine):
         self._engine = engine
@@ -81,36 +89,38 @@ class RbmGroupsPt(_PtCalls):
             raise AttributeError(name)
         return getattr(self._engine, name)
 
+    def _pt_shapes(self, rows):
+        eng = self._engine
+        return dict(v=(rows, eng.V), h=(rows, eng.H), part_v=((eng.V + 15) // 16, rows), part_h=((eng.H + 15) // 16, rows), mult=(rows,))
+
     def pt_state(self):
         """the whole ensemble as NumPy arrays (tests, tools): v [M R, V], h [M R, H], part_v [ceil(V/16), M R], part_h
-        [ceil(H/16), M R], mult [M R], idx [M R] int32, swaps [2, R - 1] int64 (bm_rbm_get_param 'pt_*' and pt_read); waits for
-        the device"""
+        [ceil(H/16), M R], mult [M R], idx [M R] int32, swaps [2, R - 1] int64 (bm_rbm_get_param and pt_read); waits for the
+        device.  Counts: part_v [2, M R] (the float32 pair hi, lo of the double v.vb) and len [M R] besides.  Gaussian: v is the
+        scaled variable u, part_v the slots of -1/2 (u - c)^2"""
         M, R = self._pt_shape
-        rows, eng = M * R, self._engine
-        shapes = dict(v=(rows, eng.V), h=(rows, eng.H), part_v=((eng.V + 15) // 16, rows), part_h=((eng.H + 15) // 16, rows), mult=(rows,))
         out = {}
-        for name, shape in shapes.items():
+        for name, shape in self._pt_shapes(M * R).items():
             a = np.empty(shape, dtype=np.float32)
-            check(self.lib.bm_rbm_get_param(self._h, ('pt_' + name).encode(), a.ctypes.data_as(C.c_void_p), a.size))
+            check(self.lib.bm_rbm_get_param(self._h, (self._pt_param + name).encode(), a.ctypes.data_as(C.c_void_p), a.size))
             out[name] = a
         swaps, idx = self.pt_read()
         out.update(idx=idx.reshape(-1), swaps=swaps)
         return out
 
-    def train_step_pt(self, Xd, B, lr, momentum, k, row=0):
-        check(self.lib.bm_rbm_groups_train_step_pt(self._h, Xd.offset_ptr(row * self.V), B, lr, momentum, k))
 
-    def train_epoch_pt(self, Xd, N, batch, lr, momentum, k, row=0):
-        """N rows starting at `row`, consecutive batches of `batch` rows, one tempered update each, driven from C"""
-        check(self.lib.bm_rbm_groups_train_epoch_pt(self._h, Xd.offset_ptr(row * self.V), N, batch, lr, momentum, k))
+class RbmGroupsPt(_RbmPtView):
+    """The tempered ensemble of an RbmEngine with visible groups (bm355.h: bm_rbm_groups_pt_* / _train_step_pt / _train_epoch_pt;
+    DESIGN.md 3.29): pt_init / pt_sweep / pt_read and the two tempered updates under the prefix 'bm_rbm_groups'."""
+    _pt_prefix = 'bm_rbm_groups'
 
 
-class RbmRsmPt(RbmGroupsPt):
+class RbmRsmPt(_RbmPtView):
     """The tempered ensemble of an RbmEngine with replicated softmax visible units (bm355.h: bm_rbm_rsm_pt_* / _train_step_pt /
-    _train_epoch_pt): pt_init / pt_sweep / pt_read and the two tempered updates under the prefix 'bm_rbm_rsm', on
-    the engine's handle.  pt_init takes the chains' document lengths; `train_lengths` holds those of the ensemble that the next
-    tempered `fit` builds (rbm.py: set_count_tempering).  Every other attribute is the engine's."""
-    _pt_prefix, _pt_n_hidden = 'bm_rbm_rsm', 1
+    _train_epoch_pt): pt_init / pt_sweep / pt_read and the two tempered updates under the prefix 'bm_rbm_rsm'.
+    pt_init takes the chains' document lengths; `train_lengths` holds those of the ensemble that the next tempered `fit` builds
+    (rbm.py: set_count_tempering)."""
+    _pt_prefix = 'bm_rbm_rsm'
     train_lengths = None
 
     def pt_init(self, n_chains, betas, V0_d=None, chain0=0, lengths=None):
@@ -128,62 +138,15 @@ class RbmRsmPt(RbmGroupsPt):
         self._pt_shape = (int(n_chains), len(b))
         self._pt_train_key = None
 
-    def pt_state(self):
-        """RbmGroupsPt.pt_state with part_v [2, M R] (the float32 pair hi, lo of the double v.vb) and len [M R]"""
-        M, R = self._pt_shape
-        rows, eng = M * R, self._engine
-        shapes = dict(v=(rows, eng.V), h=(rows, eng.H), part_v=(2, rows), part_h=((eng.H + 15) // 16, rows), mult=(rows,), len=(rows,))
-        out = {}
-        for name, shape in shapes.items():
-            a = np.empty(shape, dtype=np.float32)
-            check(self.lib.bm_rbm_get_param(self._h, ('pt_' + name).encode(), a.ctypes.data_as(C.c_void_p), a.size))
-            out[name] = a
-        swaps, idx = self.pt_read()
-        out.update(idx=idx.reshape(-1), swaps=swaps)
-        return out
-
-    def train_step_pt(self, Xd, B, lr, momentum, k, row=0):
-        check(self.lib.bm_rbm_rsm_train_step_pt(self._h, Xd.offset_ptr(row * self.V), B, lr, momentum, k))
-
-    def train_epoch_pt(self, Xd, N, batch, lr, momentum, k, row=0):
-        """N rows starting at `row`, consecutive batches of `batch` rows, one tempered update each, driven from C"""
-        check(self.lib.bm_rbm_rsm_train_epoch_pt(self._h, Xd.offset_ptr(row * self.V), N, batch, lr, momentum, k))
+    def _pt_shapes(self, rows):
+        return dict(super(RbmRsmPt, self)._pt_shapes(rows), part_v=(2, rows), len=(rows,))
 
 
-class RbmGaussPt(_PtCalls):
+class RbmGaussPt(_RbmPtView):
     """The tempered ensemble of an RbmEngine with Gaussian visible units (bm355.h: bm_rbm_gauss_pt_*): pt_init /
-    pt_sweep / pt_read under the prefix 'bm_rbm_gauss', on the engine's handle.  V0_d of pt_init and the rows pt_read hands out are
-    in data units; the ensemble itself lives in the scaled variable u = x / sigma.  Every other attribute is the engine's."""
-    _pt_prefix, _pt_n_hidden = 'bm_rbm_gauss', 1
-
-    def __init__(self, engine):
-        self._engine = engine
-        self.lib, self.V = engine.lib, engine.V
-
-    @property
-    def _h(self):
-        return self._engine._h
-
-    def __getattr__(self, name):                  # (only what this object does not define itself)
-        if name == '_engine':
-            raise AttributeError(name)
-        return getattr(self._engine, name)
-
-    def pt_state(self):
-        """the whole ensemble as NumPy arrays (tests, tools): v [M R, V] (the scaled variable u), h [M R, H], part_v [ceil(V/16),
-        M R] (the slots of -1/2 (u - c)^2), part_h [ceil(H/16), M R], mult [M R], idx [M R] int32, swaps [2, R - 1] int64
-        (bm_rbm_get_param 'gpt_*' and pt_read); waits for the device"""
-        M, R = self._pt_shape
-        rows, eng = M * R, self._engine
-        shapes = dict(v=(rows, eng.V), h=(rows, eng.H), part_v=((eng.V + 15) // 16, rows), part_h=((eng.H + 15) // 16, rows), mult=(rows,))
-        out = {}
-        for name, shape in shapes.items():
-            a = np.empty(shape, dtype=np.float32)
-            check(self.lib.bm_rbm_get_param(self._h, ('gpt_' + name).encode(), a.ctypes.data_as(C.c_void_p), a.size))
-            out[name] = a
-        swaps, idx = self.pt_read()
-        out.update(idx=idx.reshape(-1), swaps=swaps)
-        return out
+    pt_sweep / pt_read under the prefix 'bm_rbm_gauss' (the unit has no tempered update).  V0_d of pt_init and the rows pt_read
+    hands out are in data units; the ensemble itself lives in the scaled variable u = x / sigma."""
+    _pt_prefix, _pt_param = 'bm_rbm_gauss', 'gpt_'
 
 
 class RbmEngine(_PtCalls):
@@ -633,14 +596,6 @@ class RbmEngine(_PtCalls):
         check(self.lib.bm_rbm_gibbs_clamped(self._h, Vd.offset_ptr(ov), Hd.offset_ptr(oh),
                                             Vmean_d.offset_ptr(ov) if Vmean_d is not None else None, B, n_steps,
                                             clamp_val_d.offset_ptr(ov), clamp_mask_d.offset_ptr(ov)))
-
-    # tempered negative phase (bm355.h: bm_rbm_train_step_pt / _train_epoch_pt); the ensemble of pt_init supplies the particles
-    def train_step_pt(self, Xd, B, lr, momentum, k, row=0):
-        check(self.lib.bm_rbm_train_step_pt(self._h, Xd.offset_ptr(row * self.V), B, lr, momentum, k))
-
-    def train_epoch_pt(self, Xd, N, batch, lr, momentum, k, row=0):
-        """N rows starting at `row`, consecutive batches of `batch` rows, one tempered update each, driven from C"""
-        check(self.lib.bm_rbm_train_epoch_pt(self._h, Xd.offset_ptr(row * self.V), N, batch, lr, momentum, k))
 
     def stream(self):
         p = C.c_void_p()

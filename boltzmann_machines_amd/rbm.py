@@ -21,7 +21,7 @@ from .base import EngineModel, is_attribute_name, run_on_engine
 from .centering import CenteredTraining
 from .classification import ClassHead
 from .engine import RbmEngine, RbmEngine64
-from .tempering import TemperedNegativePhase, acceptance_rates, resolve_ladder, run_tempered_sampler
+from .tempering import TemperedNegativePhase, resolve_ladder, run_tempered_sampler
 from .utils import epoch_iter, make_list_from, write_during_training
 from .utils import log_sum_exp, log_mean_exp, log_diff_exp, log_std_exp
 from .utils import philox
@@ -1195,6 +1195,7 @@ class SoftmaxVisible(object):
     incomplete rows, so that `log_proba(X, ais_log_Z_rows(X))` is their log-likelihood."""
 
     _UNIT_NAME = 'softmax visible units'
+    _PT_VIEW, _PT_SETTER = 'groups_pt', 'set_group_tempering()'      # (tempering_stats: the ensemble of `set_group_tempering`)
 
     @property
     def _V_GROUP_WIDTH(self):
@@ -1559,16 +1560,6 @@ class SoftmaxVisible(object):
         # (the ensemble and its updates live under the engine's groups prefix; everything else the epoch calls is the engine's)
         return super(SoftmaxVisible, self)._train_epoch_tempered(eng.groups_pt, *args, **kwargs)
 
-    def tempering_stats(self):
-        """Acceptance rate (accepts / attempts) of every neighbouring pair of temperatures, [n_temperatures - 1], since the
-        ensemble of `set_group_tempering` was built.  Waits for the device; copies no states."""
-        eng = self._engine
-        view = eng.groups_pt if eng is not None and hasattr(eng, 'groups_pt') else None
-        if view is None or getattr(view, '_pt_train_key', None) is None:
-            raise RuntimeError('`tempering_stats`: no tempered ensemble (call set_group_tempering() and fit first)')
-        swaps, _ = view.pt_read()
-        return acceptance_rates(swaps)
-
 
 class CategoricalRBM(SoftmaxVisible, BaseRBM):
     """RBM with softmax (categorical) visible units and Bernoulli hidden units: `n_groups` one-hot groups of `n_categories`
@@ -1605,6 +1596,7 @@ class ReplicatedSoftmaxVisible(object):
     BM355_DATA_PARALLEL jobs, and use as a layer of a `DBM` or a `StackClassifier`."""
 
     _UNIT_NAME = 'replicated softmax visible units'
+    _PT_VIEW, _PT_SETTER = 'rsm_pt', 'set_count_tempering()'         # (tempering_stats: the ensemble of `set_count_tempering`)
     _MAX_VISIBLE = 16384         # csrc/bm_rsm.h: RSM_MAX_V
 
     @property
@@ -1956,14 +1948,8 @@ class ReplicatedSoftmaxVisible(object):
 
     @run_on_engine(update_seed=True)
     def _sample_v_tempered_checked(self, n_samples, D, n_gibbs_steps, ladder, V_init, return_stats):
-        view = self._on_device().rsm_pt
-        V0d = _ffi.DeviceArray.from_numpy(V_init, np.float32) if V_init is not None else None
-        view.pt_init(n_samples, ladder, V0d, lengths=D)
-        view.pt_sweep(n_gibbs_steps)
-        Vd = _ffi.DeviceArray((n_samples, self.n_visible), np.float32)
-        swaps, _ = view.pt_read(Vd)
-        V = Vd.numpy()
-        return (V, acceptance_rates(swaps)) if return_stats else V
+        return run_tempered_sampler(self._on_device().rsm_pt, n_samples, n_gibbs_steps, ladder, V_init, self.n_visible, return_stats,
+                                    lengths=D)
 
     def _check_tempered_setting(self, what):
         self._check_rsm_config(what)
@@ -2026,16 +2012,6 @@ class ReplicatedSoftmaxVisible(object):
     def _train_epoch_tempered(self, eng, *args, **kwargs):
         # (the ensemble and its updates live under the engine's rsm prefix; everything else the epoch calls is the engine's)
         return super(ReplicatedSoftmaxVisible, self)._train_epoch_tempered(eng.rsm_pt, *args, **kwargs)
-
-    def tempering_stats(self):
-        """Acceptance rate (accepts / attempts) of every neighbouring pair of temperatures, [n_temperatures - 1], since the
-        ensemble of `set_count_tempering` was built.  Waits for the device; copies no states."""
-        eng = self._engine
-        view = eng.rsm_pt if eng is not None and hasattr(eng, 'rsm_pt') else None
-        if view is None or getattr(view, '_pt_train_key', None) is None:
-            raise RuntimeError('`tempering_stats`: no tempered ensemble (call set_count_tempering() and fit first)')
-        swaps, _ = view.pt_read()
-        return acceptance_rates(swaps)
 
 
 class ReplicatedSoftmaxRBM(ReplicatedSoftmaxVisible, BaseRBM):

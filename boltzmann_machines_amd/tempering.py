@@ -23,16 +23,17 @@ def acceptance_rates(swaps):
     return swaps[1] / np.maximum(swaps[0], 1).astype(np.float64)
 
 
-def run_tempered_sampler(eng, n_samples, n_gibbs_steps, betas, V_init, n_visible, return_stats):
+def run_tempered_sampler(eng, n_samples, n_gibbs_steps, betas, V_init, n_visible, return_stats, **init_kwargs):
     """a fresh ensemble of n_samples chains on `eng` (it replaces the ensemble of a tempered negative phase: _pt_train_key),
-    n_gibbs_steps tempered steps, the visible states of the beta = 1 replicas [n_samples, n_visible] (and the acceptance rates)"""
+    n_gibbs_steps tempered steps, the visible states of the beta = 1 replicas [n_samples, n_visible] (and the acceptance rates);
+    init_kwargs: what the engine's pt_init takes besides (the chains' `lengths` of a count ensemble)"""
     V0d = None
     if V_init is not None:
         V_init = np.ascontiguousarray(V_init, dtype=np.float32)
         if V_init.shape != (n_samples, n_visible):
             raise ValueError('`V_init` has invalid shape {0}: expected [{1}, {2}]'.format(V_init.shape, n_samples, n_visible))
         V0d = _ffi.DeviceArray.from_numpy(V_init, np.float32)
-    eng.pt_init(n_samples, betas, V0d)
+    eng.pt_init(n_samples, betas, V0d, **init_kwargs)
     eng.pt_sweep(int(n_gibbs_steps))
     Vd = _ffi.DeviceArray((n_samples, n_visible), np.float32)
     swaps, _ = eng.pt_read(Vd)
@@ -46,6 +47,8 @@ class TemperedNegativePhase(object):
     """The training side: `self._neg_phase` is None (the model's default negative phase) or (betas, n_chains) of the tempered
     ensemble.  A model class names the attribute that bounds n_chains from below and supplies `_check_tempered_setting`."""
     _PT_MIN_CHAINS = None                         # 'batch_size' / 'n_particles'
+    _PT_VIEW = None                               # the engine attribute that holds the ensemble's calls; None: the engine itself
+    _PT_SETTER = "set_negative_phase('tempered')"  # what switches the tempered negative phase on, for messages
 
     def _check_tempered_setting(self, what):
         """raise where the model as configured has no tempered negative phase (`what`: the calling method's name)"""
@@ -79,7 +82,9 @@ class TemperedNegativePhase(object):
         """Acceptance rate (accepts / attempts) of every neighbouring pair of temperatures, [n_temperatures - 1], since the
         ensemble of the tempered negative phase was built.  Waits for the device; copies no states."""
         eng = self._engine
+        if self._PT_VIEW is not None:
+            eng = getattr(eng, self._PT_VIEW, None) if eng is not None else None
         if getattr(eng, '_pt_train_key', None) is None:   # (no engine, a float64 engine, or an ensemble that sampling built)
-            raise RuntimeError('`tempering_stats`: no tempered ensemble (call set_negative_phase(\'tempered\') and fit first)')
+            raise RuntimeError('`tempering_stats`: no tempered ensemble (call %s and fit first)' % self._PT_SETTER)
         swaps, _ = eng.pt_read()
         return acceptance_rates(swaps)
